@@ -21,6 +21,8 @@ fine-tune + EMA over mixed aspect buckets — the full-parameter gradient exchan
 measured after the Flux timing at the same N; at N > 1 every entry carries `comm` (the gradient exchange's per-bucket timings).  `roofline` also names the
 MEASURED vendor GEMM ceiling of this pool's boxes (`measured_vendor_gemm_ceiling`, tools/hipblaslt_ceiling.py).  `ms_per_step_stats` =
 median / p95 / min / max of the per-step device timestamps; `--model sd15 | sdxl | sd3 --full | pixart` lines carry their own `parity_at_config`.
+`--dump-outputs DIR` writes what the last timed step of the headline workload computed (its loss and the trained parameters, float32 .npy; inputs, weights and
+the sample positions are seeded) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -124,13 +126,47 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="flux only: skip the SDXL-LoRA, SD3 full-fine-tune (mixed buckets) and Flux full-rank secondary measurements appended to the default line")
     ap.add_argument("--prof-dump", default=None, help="write one CSV line per launch of the timed steps (class,ms,flops,bytes,shape)")
     ap.add_argument("--no-prof", action="store_true", help="disable the per-launch hipEvent profiler (roofline becomes null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float32): loss.npy (the loss train_step returned) and "
+                         "trained_params.npy (the trainable parameters the optimizer wrote, in Trainer.params order: all of them, or a fixed seeded sample of "
+                         f"{DUMP_MAX_VALUES} values); --model vae: latents.npy (the scaled latents of the last encode).  Headline workload only, rank 0")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.batch is None:
         a.batch = {"flux": 8, "sd3": 8, "sdxl": 4, "vae": 4, "sd15": 1, "pixart": 1}[a.model]     # sd3: 8 (r02: batch 4 -> 8 = 19.7 -> 23.9 images/s full fine-tune)
     return a
 
 
 _T0 = time.time()
+DUMP_MAX_VALUES = 1 << 22        # --dump-outputs: values per array at most (16 MiB of float32)
+
+
+def _flat_sample(tensors, k=DUMP_MAX_VALUES, seed=0):
+    """the values of `tensors` (flattened, concatenated in order) as one float32 array: all of them when there are at most k, else the values at k
+    positions drawn from a generator of fixed seed (sorted; the same positions every run with the same arguments)"""
+    sizes = [t.numel() for t in tensors]
+    n = sum(sizes)
+    if n <= k:
+        return torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors]).numpy()
+    pos = torch.randint(0, n, (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    ends = torch.tensor(sizes, dtype=torch.int64).cumsum(0)
+    which = torch.searchsorted(ends, pos, right=True)
+    out = torch.empty(k, dtype=torch.float32)
+    for j in which.unique().tolist():
+        sel = which == j
+        local = (pos[sel] - (ends[j] - sizes[j])).to(tensors[j].device)
+        out[sel] = tensors[j].detach().reshape(-1)[local].float().cpu()
+    return out.numpy()
+
+
+def dump_outputs(dir_, arrays):
+    """write {name: array} as dir_/<name>.npy in float32"""
+    import numpy as np
+    os.makedirs(dir_, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dir_, f"{name}.npy"), np.asarray(a, dtype=np.float32))
+    _log(f"outputs of the last timed step written to {dir_}: " + ", ".join(f"{k}.npy {np.asarray(v).shape}" for k, v in arrays.items()))
 
 
 def _log(msg):
@@ -373,6 +409,8 @@ def bench_vae(args, dev, rank, world):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": _flat_sample([z])})
     prof = None
     if not args.no_prof:
         ops.prof_enable(False); prof = ops.prof_collect(); ops.prof_reset()
@@ -502,6 +540,7 @@ def main():
         keys = keys + ("published", "vs_baseline")
         for name, a_ in (("sdxl_lora", a2), ("sd3_full_buckets", a3), ("flux_full_rank", a4), ("sd3_lora_r128_bs3_published_row", a5)):
             a_.steps, a_.warmup, a_.no_cpu_baseline, a_.prof_dump, a_.fp8, a_.gradient_checkpointing = min(args.steps, 5), 2, True, None, False, False
+            a_.dump_outputs = None                # the dumped outputs are the headline workload's
             if name == "flux_full_rank":
                 a_.steps, a_.warmup, a_.optimizer, a_.gradient_checkpointing, a_.ckpt_interval, a_.ckpt_stride = min(args.steps, 3), 1, "adamw_bf16", True, 3, 4
             if name == "sd3_lora_r128_bs3_published_row":
@@ -745,6 +784,8 @@ def run_workload(args, dev, rank, world):
     per_step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     step_stats = {"median": round(per_step_ms[len(per_step_ms) // 2], 2), "p95": round(per_step_ms[min(len(per_step_ms) - 1, int(0.95 * len(per_step_ms)))], 2),
                   "min": round(per_step_ms[0], 2), "max": round(per_step_ms[-1], 2), "source": "device timestamps (hipEvents on the compute stream) per step, this rank"}
+    if args.dump_outputs and rank == 0:           # before the extra eager profiling step of --graph, which would move the parameters again
+        dump_outputs(args.dump_outputs, {"loss": [float(loss.item())], "trained_params": _flat_sample(trainer.params)})
     prof = None
     prof_steps = args.steps
     if args.graph and not args.no_prof:

@@ -1,39 +1,13 @@
 """Activation-checkpoint segment plans: FluxTransformer2DModel._checkpoint_segments must cut the block stacks exactly where the
-reference's `checkpoint_sequential_state` (helpers/training/gradient_checkpointing_interval.py:69-120, executed here from where it lies — a pure
-python module) opens / closes its checkpoint calls, for the published-table modes `layer`, `interval2`, `seg2-stride4` and a few others."""
-import importlib.util
+reference's `checkpoint_sequential_state` (helpers/training/gradient_checkpointing_interval.py:69-120) opens / closes its checkpoint calls, for the
+published-table modes `layer`, `interval2`, `seg2-stride4` and a few others.  The reference's plans are executed results stored in
+tests/golden/checkpoint_plan_vectors.json (tools/gen_checkpoint_plan_golden.py)."""
+import json
 from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference/simpletuner/helpers/training/gradient_checkpointing_interval.py")
-
-
-def _ref_plan(gci, n, interval, stride):
-    log = []
-
-    def run_block(i, blk, *st):
-        log.append(("blk", i))
-        return st
-
-    def ck(fn, *st, **kw):
-        log.append(("begin",))
-        r = fn(*st)
-        log.append(("end",))
-        return r
-
-    gci.checkpoint_sequential_state(list(range(n)), interval, (0,), run_block, ck, {}, stride)
-    segs, cur = [], None
-    for e in log:
-        if e[0] == "begin":
-            cur = []
-        elif e[0] == "end":
-            segs.append((cur[0], len(cur), True)); cur = None
-        elif cur is not None:
-            cur.append(e[1])
-        else:
-            segs.append((e[1], 1, False))
-    return segs
+GOLDEN = Path(__file__).resolve().parent / "golden" / "checkpoint_plan_vectors.json"
 
 
 def _model():
@@ -41,20 +15,20 @@ def _model():
     return FluxTransformer2DModel.__new__(FluxTransformer2DModel)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="the reference tree is only present in the build container")
 def test_segment_plans_equal_the_reference_helper():
-    spec = importlib.util.spec_from_file_location("ref_gci", str(REF))
-    gci = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gci)
+    ref = json.loads(GOLDEN.read_text())
+    cases = {(c["n"], c["interval"], c["stride"]) for c in ref["segmented"]}
+    assert cases == {(n, i, s) for n in (19, 38, 5, 1) for i, s in ((2, None), (2, 4), (3, 3), (4, 6), (2, 2))}, cases
     m = _model()
     m.gradient_checkpointing = True
-    for n in (19, 38, 5, 1):
-        for interval, stride in ((2, None), (2, 4), (3, 3), (4, 6), (2, 2)):
-            m.gradient_checkpointing_interval, m.gradient_checkpointing_segment_stride = interval, stride
-            assert m._checkpoint_segments(n) == _ref_plan(gci, n, interval, stride), (n, interval, stride)
-        # non-segmented: should_checkpoint_block(interval None) == every block its own checkpoint
-        m.gradient_checkpointing_interval, m.gradient_checkpointing_segment_stride = None, None
-        assert m._checkpoint_segments(n) == [(i, 1, gci.should_checkpoint_block(i, True, None)) for i in range(n)]
+    for c in ref["segmented"]:
+        m.gradient_checkpointing_interval, m.gradient_checkpointing_segment_stride = c["interval"], c["stride"]
+        assert m._checkpoint_segments(c["n"]) == [tuple(seg) for seg in c["plan"]], (c["n"], c["interval"], c["stride"])
+    # non-segmented: should_checkpoint_block(interval None) == every block its own checkpoint
+    assert sorted(c["n"] for c in ref["every_block"]) == [1, 5, 19, 38]
+    m.gradient_checkpointing_interval, m.gradient_checkpointing_segment_stride = None, None
+    for c in ref["every_block"]:
+        assert m._checkpoint_segments(c["n"]) == [(i, 1, ck) for i, ck in enumerate(c["checkpointed"])], c["n"]
 
 
 def test_modes_off_layer_and_bad_stride():
