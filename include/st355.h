@@ -189,6 +189,16 @@ int st355_gemm_bf16(void* stream, const st355_gemm_args* args);
 /* `count` independent problems with the SAME epilogue kind in as few launches as possible (pairs share one grid): the two
  * streams (img / txt) of an MMDiT block, or the per-batch slices of a joint buffer. */
 int st355_gemm_bf16_grouped(void* stream, const st355_gemm_args* args, int count);
+/* The schedule each problem would run on, without launching anything: routes[i] = the ST355_ROUTE_* of args[i] as st355_gemm_bf16_grouped(args, count) would
+ * launch it now (count == 1: as st355_gemm_bf16 would).  ST355_ROUTE_PQ_TAIL is reported only once the stream-K tail's XCD placement probe has confirmed
+ * round-robin placement on this device (st355_gemm_tail_placement() == 1); the plan never runs the probe.  Validates the arguments as the launch would. */
+enum { ST355_ROUTE_ROWS = 1 /* k_gemm_rows */, ST355_ROUTE_THIN = 2 /* k_gemm_thin */, ST355_ROUTE_SPLITK = 3 /* k_gemm_s2 split-K + k_splitk_reduce */,
+       ST355_ROUTE_S2 = 4 /* k_gemm_s2 (128x128) */, ST355_ROUTE_P3 = 5 /* k_gemm_p3 (256x128) */, ST355_ROUTE_PQ = 6 /* k_gemm_pq (256x256, one tile per workgroup) */,
+       ST355_ROUTE_PZ = 7 /* k_gemm_pz (persistent 256x256) */, ST355_ROUTE_PQ_TAIL = 8 /* k_gemm_pq with the stream-K tail */,
+       ST355_ROUTE_PQ_QK_ROPE = 9, ST355_ROUTE_PQ_HEADS = 10, ST355_ROUTE_PQ_GEGLU = 11 /* k_gemm_pq with EPI_GEGLU or EPI_GEGLU_GRAD */,
+       ST355_ROUTE_PZ_GEGLU_GRAD = 12, ST355_ROUTE_PAIR_PQ = 13 /* two problems in one k_gemm_pq grid */, ST355_ROUTE_PAIR_P3 = 14 /* ... one k_gemm_p3 grid */,
+       ST355_ROUTE_PAIR_HEADS = 15, ST355_ROUTE_PAIR_QK_ROPE = 16 };
+int st355_gemm_plan(const st355_gemm_args* args, int count, int32_t* routes);
 /* Schedule choice for the 256x256-tile problems (tuning / A-B hook; results are bit-identical either way): 1 = persistent workgroups that walk the
  * tile list and keep the LDS ring running across tile seams (k_gemm_pz: full tiles, > one round of tiles, plain NT bf16 with the five elementwise
  * epilogues), 0 = one tile per workgroup everywhere (k_gemm_pq), -1 = the default (environment ST355_GEMM_PERSIST, on).  Returns the previous setting. */

@@ -1997,12 +1997,6 @@ static int launch_pz(void* stream, const GemmP& p, int tiles) {
   return st355_check_launch("gemm_pz");
 }
 
-template <int EPI>
-static int launch_256(void* stream, const GemmGroup& g, int tiles) {
-  if (tiles == g.tiles0 && pz_ok(g.p[0], tiles)) return launch_pz<EPI>(stream, g.p[0], tiles);     // (a two-problem grid stays one-tile-per-workgroup)
-  return launch_pq<EPI>(stream, g, tiles);
-}
-
 #define DISPATCH_EPI(fn, epi, ...)                                                           \
   switch (epi) {                                                                             \
     case ST355_EPI_NONE: return fn<ST355_EPI_NONE>(__VA_ARGS__);                             \
@@ -2361,9 +2355,9 @@ static int tail_placement_ok(void* stream, void* scratch) {
   return good;
 }
 
-// true: run `p` as g (blocks = *blocks).  The last round of 256x256 tiles is cut when it fills at most half the chip and the problem is short enough for that
-// round to matter (<= 6 full rounds before it); 2..4 slices of >= 4 K-tiles each, slabs in the caller's workspace.
-static bool tail_plan(void* stream, const st355_gemm_args* a, const GemmP& p, GemmGroup& g, int* blocks) {
+// true: `p` may run as g (blocks = *blocks), once the XCD placement is confirmed (route_one).  The last round of 256x256 tiles is cut when it fills at most half
+// the chip and the problem is short enough for that round to matter (<= 6 full rounds before it); 2..4 slices of >= 4 K-tiles each, slabs in the caller's workspace.
+static bool tail_plan(const st355_gemm_args* a, const GemmP& p, GemmGroup& g, int* blocks) {
   if (!tail_enabled() || !a->workspace || !a->tile_flags || ((uintptr_t)a->workspace % 16) || p.partial || p.scale_b || p.conv_taps || p.img_add) return false;
   const int cus = device_cus();
   const int T = p4_tiles(p), rounds = T / cus, rem = T % cus;
@@ -2389,49 +2383,48 @@ static bool tail_plan(void* stream, const st355_gemm_args* a, const GemmP& p, Ge
   g.p[0] = p; g.p[1] = p; g.tiles0 = T;
   g.sk_first = rounds * cus; g.sk_s = s; g.sk_ws = (float*)a->workspace; g.sk_flags = (int*)a->tile_flags;
   *blocks = g.sk_first + (rem + 7) / 8 * 8 * s;
-  return tail_placement_ok(stream, a->workspace) != 0;
+  return true;
 }
 
-static int run_one(void* stream, const st355_gemm_args* a) {
-  if (rows_ok(a)) return launch_rows(stream, a);
-  if (thin_ok(a)) return launch_thin(stream, a);
-  GemmP p = to_p(a);
-  // thin problems (the LoRA rank-space projections: N <= 128, K in the thousands) stream A once and have only M/128 tiles: split
-  // K so that >= 2 workgroups per CU are in flight, partial sums through the caller's fp32 workspace (fixed-order reduce)
+// ---- schedule choice -------------------------------------------------------------------------------------------------------
+// Every schedule decision of run_one and st355_gemm_bf16_grouped is taken by route_one / route_group below; the launchers and st355_gemm_plan both call them,
+// so the plan reports exactly what a call would launch.
+
+// thin problems (the LoRA rank-space projections: N <= 128, K in the thousands) stream A once and have only M/128 tiles: split
+// K so that >= 2 workgroups per CU are in flight, partial sums through the caller's fp32 workspace (fixed-order reduce).  Returns the slice count (< 2: no split)
+static int thin_splitk_slices(const st355_gemm_args* a, const GemmP& p) {
   static int thin_splitk = -1;
   if (thin_splitk < 0) { const char* e = getenv("ST355_THIN_SPLITK"); thin_splitk = (e && e[0] == '0') ? 0 : 1; }      // A/B: 0 = no split-K for thin problems
-  if (thin_splitk && a->workspace && p.N <= S2_BN && p.K2 == 0 && a->epilogue == ST355_EPI_NONE && p.K >= 1024 && p.M >= 512 && !(a->seg_rows && a->seg_c)) {   // (the slab reduce writes compact C rows)
-    const int tiles = (p.M + S2_BM - 1) / S2_BM;
-    int ks = (512 + tiles - 1) / tiles;
-    // more than one round of resident workgroups already (288 row tiles for the LoRA projections of a 36 864-token batch): a split only adds slab traffic
-    // and a ragged second round — measured 83 us (ks = 2) / 77 (ks = 3) against 65 us on the 256x128 schedule without a split, which the code below picks
-    if (tiles > 256) ks = 1;
-    const int nt1 = p.K / BK;
-    if (ks > nt1 / 4) ks = nt1 / 4;                       // >= 4 K-tiles per slice
-    if (ks > 16) ks = 16;
-    if (ks >= 2 && (int64_t)ks * p.M * p.N * 4 <= a->workspace_bytes && ((uintptr_t)a->workspace % 16) == 0) return launch_splitk(stream, p, a, ks);
-  }
+  if (!(thin_splitk && a->workspace && p.N <= S2_BN && p.K2 == 0 && a->epilogue == ST355_EPI_NONE && p.K >= 1024 && p.M >= 512 && !(a->seg_rows && a->seg_c)))   // (the slab reduce writes compact C rows)
+    return 0;
+  const int tiles = (p.M + S2_BM - 1) / S2_BM;
+  int ks = (512 + tiles - 1) / tiles;
+  // more than one round of resident workgroups already (288 row tiles for the LoRA projections of a 36 864-token batch): a split only adds slab traffic
+  // and a ragged second round — measured 83 us (ks = 2) / 77 (ks = 3) against 65 us on the 256x128 schedule without a split, which route_one picks next
+  if (tiles > 256) ks = 1;
+  const int nt1 = p.K / BK;
+  if (ks > nt1 / 4) ks = nt1 / 4;                       // >= 4 K-tiles per slice
+  if (ks > 16) ks = 16;
+  return (ks >= 2 && (int64_t)ks * p.M * p.N * 4 <= a->workspace_bytes && ((uintptr_t)a->workspace % 16) == 0) ? ks : 0;
+}
+
+// the ST355_ROUTE_* of one problem.  placed(): is the stream-K tail's XCD placement confirmed (run_one probes it on first use; st355_gemm_plan only reads the
+// result of a probe that has already run).  *ksplit: the split-K slices (ST355_ROUTE_SPLITK); *tg, *tblocks: the cut grid (ST355_ROUTE_PQ_TAIL)
+template <class Placed>
+static int route_one(const st355_gemm_args* a, const GemmP& p, Placed placed, int* ksplit, GemmGroup* tg, int* tblocks) {
+  if (rows_ok(a)) return ST355_ROUTE_ROWS;
+  if (thin_ok(a)) return ST355_ROUTE_THIN;
+  if ((*ksplit = thin_splitk_slices(a, p)) >= 2) return ST355_ROUTE_SPLITK;
   // the deep-pipelined schedule needs enough tiles to fill 256 CUs; tiny problems stay on the 128x128 schedule
   // 256x256 tiles only when they (nearly) fill the 256 CUs at one workgroup each
-  if (a->epilogue == ST355_EPI_QK_NORM_ROPE) {          // the fused q/k epilogue exists in the 256x256 schedule only
-    GemmGroup g;
-    g.p[0] = p; g.p[1] = p; g.tiles0 = p4_tiles(p);
-    return launch_pq<ST355_EPI_QK_NORM_ROPE>(stream, g, g.tiles0);
-  }
-  if (a->epilogue == ST355_EPI_HEADS) {                 // ... and the head-splitting one
-    GemmGroup g;
-    g.p[0] = p; g.p[1] = p; g.tiles0 = p4_tiles(p);
-    return launch_pq<ST355_EPI_HEADS>(stream, g, g.tiles0);
-  }
-  if (a->epilogue == ST355_EPI_GEGLU || a->epilogue == ST355_EPI_GEGLU_GRAD) {      // likewise the GEGLU pair
-    GemmGroup g;
-    g.p[0] = p; g.p[1] = p; g.tiles0 = p4_tiles(p);
+  if (a->epilogue == ST355_EPI_QK_NORM_ROPE) return ST355_ROUTE_PQ_QK_ROPE;       // the fused q/k epilogue exists in the 256x256 schedule only
+  if (a->epilogue == ST355_EPI_HEADS) return ST355_ROUTE_PQ_HEADS;                // ... and the head-splitting one
+  if (a->epilogue == ST355_EPI_GEGLU || a->epilogue == ST355_EPI_GEGLU_GRAD) {    // likewise the GEGLU pair
     // the backward epilogue (reads the kept pre-activation, writes d value | d gate: 2.7 GB per launch at the SDXL 32^2 level of batch 32 against 0.43 PFLOP of
     // MFMA work) on the PERSISTENT schedule when the problem is made of full tiles (r6): the next tile's first K-tiles load under it.  ST355_GEGLU_GRAD_PZ=0: A/B
     static int gg_pz = -1;
     if (gg_pz < 0) { const char* e = getenv("ST355_GEGLU_GRAD_PZ"); gg_pz = (e && e[0] == '0') ? 0 : 1; }
-    if (gg_pz && a->epilogue == ST355_EPI_GEGLU_GRAD && !a->bias && pz_ok(p, g.tiles0)) return launch_pz<ST355_EPI_GEGLU_GRAD>(stream, p, g.tiles0);
-    return a->epilogue == ST355_EPI_GEGLU ? launch_pq<ST355_EPI_GEGLU>(stream, g, g.tiles0) : launch_pq<ST355_EPI_GEGLU_GRAD>(stream, g, g.tiles0);
+    return (gg_pz && a->epilogue == ST355_EPI_GEGLU_GRAD && !a->bias && pz_ok(p, p4_tiles(p))) ? ST355_ROUTE_PZ_GEGLU_GRAD : ST355_ROUTE_PQ_GEGLU;
   }
   // tile quantisation (r6 experiment knob ST355_GEMM_P3_WINDOW=lo,hi): a problem whose 256x256 tiles leave the chip's last round mostly empty — 320 tiles on
   // 256 CUs: two rounds for 1.25 rounds of work, the N = 1280 projections of the SDXL 32^2 level at batch 16 — may run better as 256x128 tiles (2.5 rounds of half the size)
@@ -2444,23 +2437,75 @@ static int run_one(void* stream, const st355_gemm_args* a) {
   static int n128_p3 = -1;
   if (n128_p3 < 0) { const char* e = getenv("ST355_GEMM_N128_P3"); n128_p3 = (e && e[0] == '0') ? 0 : 1; }
   const bool narrow = n128_p3 && p.N <= P3_BN && p.K2 == 0 && gemm_impl_choice() >= 1 && p.M > 128 && p3_tiles(p) >= 128;
-  if (gemm_impl_choice() >= 2 && !p3_window && !narrow) {
-    GemmGroup g;
-    int blocks = 0;
-    if (tail_plan(stream, a, p, g, &blocks)) { DISPATCH_EPI(launch_pq_sk, a->epilogue, stream, g, blocks); }
+  if (gemm_impl_choice() >= 2 && !p3_window && !narrow && tail_plan(a, p, *tg, tblocks) && placed()) return ST355_ROUTE_PQ_TAIL;
+  if (gemm_impl_choice() >= 2 && p4_tiles(p) >= min_tiles_256() && !p3_window && !narrow) return pz_ok(p, p4_tiles(p)) ? ST355_ROUTE_PZ : ST355_ROUTE_PQ;
+  if (gemm_impl_choice() >= 1 && p.M > 128 && p3_tiles(p) >= 128) return ST355_ROUTE_P3;
+  return ST355_ROUTE_S2;
+}
+
+static GemmGroup one_problem(const GemmP& p, int tiles) {
+  GemmGroup g;
+  g.p[0] = p; g.p[1] = p; g.tiles0 = tiles;
+  return g;
+}
+
+static int run_one(void* stream, const st355_gemm_args* a) {
+  const GemmP p = to_p(a);
+  int ks = 0, blocks = 0;
+  GemmGroup tg;
+  const int route = route_one(a, p, [&] { return tail_placement_ok(stream, a->workspace) != 0; }, &ks, &tg, &blocks);
+  switch (route) {
+    case ST355_ROUTE_ROWS: return launch_rows(stream, a);
+    case ST355_ROUTE_THIN: return launch_thin(stream, a);
+    case ST355_ROUTE_SPLITK: { GemmP ps = p; return launch_splitk(stream, ps, a, ks); }
+    case ST355_ROUTE_PQ_QK_ROPE: return launch_pq<ST355_EPI_QK_NORM_ROPE>(stream, one_problem(p, p4_tiles(p)), p4_tiles(p));
+    case ST355_ROUTE_PQ_HEADS: return launch_pq<ST355_EPI_HEADS>(stream, one_problem(p, p4_tiles(p)), p4_tiles(p));
+    case ST355_ROUTE_PZ_GEGLU_GRAD: return launch_pz<ST355_EPI_GEGLU_GRAD>(stream, p, p4_tiles(p));
+    case ST355_ROUTE_PQ_GEGLU:
+      return a->epilogue == ST355_EPI_GEGLU ? launch_pq<ST355_EPI_GEGLU>(stream, one_problem(p, p4_tiles(p)), p4_tiles(p))
+                                            : launch_pq<ST355_EPI_GEGLU_GRAD>(stream, one_problem(p, p4_tiles(p)), p4_tiles(p));
+    case ST355_ROUTE_PQ_TAIL: DISPATCH_EPI(launch_pq_sk, a->epilogue, stream, tg, blocks);
+    case ST355_ROUTE_PZ: DISPATCH_EPI(launch_pz, a->epilogue, stream, p, p4_tiles(p));
+    case ST355_ROUTE_PQ: DISPATCH_EPI(launch_pq, a->epilogue, stream, one_problem(p, p4_tiles(p)), p4_tiles(p));
+    case ST355_ROUTE_P3: DISPATCH_EPI(launch_p3, a->epilogue, stream, one_problem(p, p3_tiles(p)), p3_tiles(p));
+    default: DISPATCH_EPI(launch_s2, a->epilogue, stream, p);
   }
-  if (gemm_impl_choice() >= 2 && p4_tiles(p) >= min_tiles_256() && !p3_window && !narrow) {
-    GemmGroup g;
-    g.p[0] = p; g.p[1] = p; g.tiles0 = p4_tiles(p);
-    DISPATCH_EPI(launch_256, a->epilogue, stream, g, g.tiles0);
+}
+
+// how st355_gemm_bf16_grouped takes the problems from i on: a shared grid (ST355_ROUTE_PAIR_*; ST355_ROUTE_PQ_HEADS for the odd last EPI_HEADS problem), or
+// through run_one: 0 = problem i alone, GROUP_SEPARATE = problems i and i + 1 one after the other.  group_size(): how many problems that takes
+static constexpr int GROUP_SEPARATE = -1;
+static int route_group(const st355_gemm_args* args, int i, int count) {
+  const st355_gemm_args& a = args[i];
+  if (a.epilogue == ST355_EPI_GEGLU || a.epilogue == ST355_EPI_GEGLU_GRAD) return 0;      // (one launch per problem: these two exist as plain problems only)
+  if (a.epilogue == ST355_EPI_HEADS) return i + 1 < count ? ST355_ROUTE_PAIR_HEADS : ST355_ROUTE_PQ_HEADS;   // img + txt projections of one joint attention: one grid
+  if (i + 1 < count && a.epilogue == ST355_EPI_QK_NORM_ROPE) return ST355_ROUTE_PAIR_QK_ROPE;        // img + txt projections of one block: one grid
+  if (i + 1 < count && gemm_impl_choice() >= 2) {
+    const GemmP p0 = to_p(&args[i]), p1 = to_p(&args[i + 1]);
+    if (pz_ok(p0, p4_tiles(p0)) && pz_ok(p1, p4_tiles(p1))) return GROUP_SEPARATE;      // both fill the chip alone: nothing to gain from sharing a grid — two persistent launches
+    // (measured r5, SD3-Medium full fine-tune at batch 8: launching a small text-stream partner apart from an image problem whose 768 tiles quantise to exactly 3
+    // rounds — partner on the 128x128 schedule — did NOT pay: 319.6 vs 317.2 ms per step, GEMM class 152.2 vs 151.8 ms; the rule was removed.
+    // profiles/r05_sd3_full_b8_ungroup_rule_ab.txt)
+    if (p4_tiles(p0) + p4_tiles(p1) >= min_tiles_256()) return ST355_ROUTE_PAIR_PQ;
   }
-  const bool big = gemm_impl_choice() >= 1 && p.M > 128 && p3_tiles(p) >= 128;
-  if (big) {
-    GemmGroup g;
-    g.p[0] = p; g.p[1] = p; g.tiles0 = p3_tiles(p);
-    DISPATCH_EPI(launch_p3, a->epilogue, stream, g, g.tiles0);
+  if (i + 1 < count && gemm_impl_choice() >= 1 && p3_tiles(to_p(&args[i])) + p3_tiles(to_p(&args[i + 1])) >= 128) return ST355_ROUTE_PAIR_P3;
+  return 0;
+}
+static int group_size(int route) { return route == 0 || route == ST355_ROUTE_PQ_HEADS ? 1 : 2; }
+
+static int launch_group(void* stream, const st355_gemm_args* args, int route) {
+  GemmGroup g;
+  const int n = group_size(route);
+  g.p[0] = to_p(&args[0]); g.p[1] = to_p(&args[n - 1]);
+  const bool p3 = route == ST355_ROUTE_PAIR_P3;
+  g.tiles0 = p3 ? p3_tiles(g.p[0]) : p4_tiles(g.p[0]);
+  const int tiles = g.tiles0 + (n == 2 ? (p3 ? p3_tiles(g.p[1]) : p4_tiles(g.p[1])) : 0);
+  switch (route) {
+    case ST355_ROUTE_PAIR_HEADS: case ST355_ROUTE_PQ_HEADS: return launch_pq<ST355_EPI_HEADS>(stream, g, tiles);
+    case ST355_ROUTE_PAIR_QK_ROPE: return launch_pq<ST355_EPI_QK_NORM_ROPE>(stream, g, tiles);
+    case ST355_ROUTE_PAIR_PQ: DISPATCH_EPI(launch_pq, args[0].epilogue, stream, g, tiles);     // (a two-problem grid stays one-tile-per-workgroup)
+    default: DISPATCH_EPI(launch_p3, args[0].epilogue, stream, g, tiles);
   }
-  DISPATCH_EPI(launch_s2, a->epilogue, stream, p);
 }
 
 extern "C" int st355_gemm_tail_placement(void) {
@@ -2675,97 +2720,42 @@ extern "C" int st355_gemm_bf16_grouped(void* stream, const st355_gemm_args* args
   }
   int i = 0;
   while (i < count) {
-    if (args[i].epilogue == ST355_EPI_GEGLU || args[i].epilogue == ST355_EPI_GEGLU_GRAD) {      // (one launch per problem: these two exist as plain problems only)
-      ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]), gemm_bytes(&args[i]), "%dx%dx%d+%d e%d g", args[i].M, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-      int rc = run_one(stream, &args[i]);
-      if (rc) return rc;
-      i += 1;
-      continue;
-    }
-    if (args[i].epilogue == ST355_EPI_HEADS) {             // img + txt projections of one joint attention: one grid (or the last, odd problem alone)
-      GemmGroup g;
-      const int n2 = i + 1 < count ? 2 : 1;
-      g.p[0] = to_p(&args[i]); g.p[1] = to_p(&args[i + n2 - 1]);
-      g.tiles0 = p4_tiles(g.p[0]);
-      const int tiles = g.tiles0 + (n2 == 2 ? p4_tiles(g.p[1]) : 0);
-      ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]) + (n2 == 2 ? gemm_flops(&args[i + 1]) : 0.0), gemm_bytes(&args[i]) + (n2 == 2 ? gemm_bytes(&args[i + 1]) : 0.0),
-                   "%d&%dx%dx%d+%d e%d", args[i].M, n2 == 2 ? args[i + 1].M : 0, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-      int rc = launch_pq<ST355_EPI_HEADS>(stream, g, tiles);
-      if (rc) return rc;
-      i += n2;
-      continue;
-    }
-    if (i + 1 < count && args[i].epilogue == ST355_EPI_QK_NORM_ROPE) {      // img + txt projections of one block: one grid
-      GemmGroup g;
-      g.p[0] = to_p(&args[i]); g.p[1] = to_p(&args[i + 1]);
-      g.tiles0 = p4_tiles(g.p[0]);
-      const int tiles = g.tiles0 + p4_tiles(g.p[1]);
-      ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]) + gemm_flops(&args[i + 1]), gemm_bytes(&args[i]) + gemm_bytes(&args[i + 1]),
-                   "%d&%dx%dx%d+%d e%d", args[i].M, args[i + 1].M, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-      int rc = launch_pq<ST355_EPI_QK_NORM_ROPE>(stream, g, tiles);
-      if (rc) return rc;
-      i += 2;
-      continue;
-    }
-    if (i + 1 < count && gemm_impl_choice() >= 2) {
-      GemmGroup g;
-      g.p[0] = to_p(&args[i]); g.p[1] = to_p(&args[i + 1]);
-      g.tiles0 = p4_tiles(g.p[0]);
-      const int tiles = g.tiles0 + p4_tiles(g.p[1]);
-      if (pz_ok(g.p[0], g.tiles0) && pz_ok(g.p[1], tiles - g.tiles0)) {     // both fill the chip alone: nothing to gain from sharing a grid — two persistent launches
-        for (int k = 0; k < 2; k++) {
-          ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i + k]), gemm_bytes(&args[i + k]), "%dx%dx%d+%d e%d g", args[i + k].M, args[i + k].N, args[i + k].K,
-                       args[i + k].K2, args[i + k].epilogue);
-          int rc = run_one(stream, &args[i + k]);
-          if (rc) return rc;
-        }
-        i += 2;
-        continue;
-      }
-      // (measured r5, SD3-Medium full fine-tune at batch 8: launching a small text-stream partner apart from an image problem whose 768 tiles quantise to exactly 3
-      // rounds — partner on the 128x128 schedule — did NOT pay: 319.6 vs 317.2 ms per step, GEMM class 152.2 vs 151.8 ms; the rule was removed.
-      // profiles/r05_sd3_full_b8_ungroup_rule_ab.txt)
-      if (tiles >= min_tiles_256()) {
-        ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]) + gemm_flops(&args[i + 1]), gemm_bytes(&args[i]) + gemm_bytes(&args[i + 1]),
-                     "%d&%dx%dx%d+%d e%d", args[i].M, args[i + 1].M, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-        int rc;
-        switch (args[i].epilogue) {
-          case ST355_EPI_NONE: rc = launch_256<ST355_EPI_NONE>(stream, g, tiles); break;
-          case ST355_EPI_GELU: rc = launch_256<ST355_EPI_GELU>(stream, g, tiles); break;
-          case ST355_EPI_GATE_RESIDUAL: rc = launch_256<ST355_EPI_GATE_RESIDUAL>(stream, g, tiles); break;
-          case ST355_EPI_MUL_GELU_GRAD: rc = launch_256<ST355_EPI_MUL_GELU_GRAD>(stream, g, tiles); break;
-          default: rc = launch_256<ST355_EPI_ADD>(stream, g, tiles); break;
-        }
+    const int route = route_group(args, i, count), n = group_size(route);
+    if (route == 0 || route == GROUP_SEPARATE) {
+      for (int k = 0; k < n; k++) {
+        ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i + k]), gemm_bytes(&args[i + k]), "%dx%dx%d+%d e%d g", args[i + k].M, args[i + k].N, args[i + k].K,
+                     args[i + k].K2, args[i + k].epilogue);
+        int rc = run_one(stream, &args[i + k]);
         if (rc) return rc;
-        i += 2;
-        continue;
       }
+    } else {
+      ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]) + (n == 2 ? gemm_flops(&args[i + 1]) : 0.0), gemm_bytes(&args[i]) + (n == 2 ? gemm_bytes(&args[i + 1]) : 0.0),
+                   "%d&%dx%dx%d+%d e%d", args[i].M, n == 2 ? args[i + 1].M : 0, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
+      int rc = launch_group(stream, &args[i], route);
+      if (rc) return rc;
     }
-    if (i + 1 < count && gemm_impl_choice() >= 1) {
-      GemmGroup g;
-      g.p[0] = to_p(&args[i]); g.p[1] = to_p(&args[i + 1]);
-      g.tiles0 = p3_tiles(g.p[0]);
-      const int tiles = g.tiles0 + p3_tiles(g.p[1]);
-      if (tiles >= 128) {
-        ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]) + gemm_flops(&args[i + 1]), gemm_bytes(&args[i]) + gemm_bytes(&args[i + 1]),
-                     "%d&%dx%dx%d+%d e%d", args[i].M, args[i + 1].M, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-        int rc;
-        switch (args[i].epilogue) {
-          case ST355_EPI_NONE: rc = launch_p3<ST355_EPI_NONE>(stream, g, tiles); break;
-          case ST355_EPI_GELU: rc = launch_p3<ST355_EPI_GELU>(stream, g, tiles); break;
-          case ST355_EPI_GATE_RESIDUAL: rc = launch_p3<ST355_EPI_GATE_RESIDUAL>(stream, g, tiles); break;
-          case ST355_EPI_MUL_GELU_GRAD: rc = launch_p3<ST355_EPI_MUL_GELU_GRAD>(stream, g, tiles); break;
-          default: rc = launch_p3<ST355_EPI_ADD>(stream, g, tiles); break;
-        }
-        if (rc) return rc;
-        i += 2;
-        continue;
-      }
-    }
-    ProfScope ps(stream, ST355_K_GEMM, gemm_flops(&args[i]), gemm_bytes(&args[i]), "%dx%dx%d+%d e%d g", args[i].M, args[i].N, args[i].K, args[i].K2, args[i].epilogue);
-    int rc = run_one(stream, &args[i]);
+    i += n;
+  }
+  return ST355_OK;
+}
+
+extern "C" int st355_gemm_plan(const st355_gemm_args* args, int count, int32_t* routes) {
+  ST_REQUIRE(args && routes && count >= 1, "gemm_plan: bad args");
+  for (int i = 0; i < count; i++) {
+    int rc = validate(&args[i]);
     if (rc) return rc;
-    i += 1;
+    ST_REQUIRE(args[i].epilogue == args[0].epilogue, "gemm_plan: all problems must share one epilogue kind");
+  }
+  auto placed = [] { return st355_gemm_tail_placement() == 1; };      // never launches the probe
+  int i = 0;
+  while (i < count) {
+    const int route = route_group(args, i, count), n = group_size(route);
+    for (int k = 0; k < n; k++) {
+      int ks = 0, blocks = 0;
+      GemmGroup tg;
+      routes[i + k] = (route == 0 || route == GROUP_SEPARATE) ? route_one(&args[i + k], to_p(&args[i + k]), placed, &ks, &tg, &blocks) : route;
+    }
+    i += n;
   }
   return ST355_OK;
 }

@@ -485,6 +485,24 @@ def gemm_grouped(problems):
     return outs
 
 
+GEMM_ROUTES = {1: "ROWS", 2: "THIN", 3: "SPLITK", 4: "S2", 5: "P3", 6: "PQ", 7: "PZ", 8: "PQ_TAIL", 9: "PQ_QK_ROPE", 10: "PQ_HEADS", 11: "PQ_GEGLU",
+               12: "PZ_GEGLU_GRAD", 13: "PAIR_PQ", 14: "PAIR_P3", 15: "PAIR_HEADS", 16: "PAIR_QK_ROPE"}      # ST355_ROUTE_* (st355.h)
+
+
+def gemm_plan(problems):
+    """st355_gemm_plan: the schedule (a GEMM_ROUTES name) each problem would run on as gemm_grouped(problems) — for one problem, as gemm(**problems[0]) — without
+    launching anything.  Same dicts as gemm_grouped; outputs not given are allocated as there (and not written)."""
+    L = _l.load()
+    arr = (GemmArgs * len(problems))()
+    keep = []
+    for g, pr in zip(arr, problems):
+        pr = dict(pr)
+        keep.append(_gemm_args(g, pr.pop("a"), pr.pop("w"), **pr))
+    routes = (C.c_int32 * len(problems))()
+    _l.check(L.st355_gemm_plan(arr, len(problems), routes), "gemm_plan")
+    return [GEMM_ROUTES[r] for r in routes]
+
+
 def fp8_quantize_weight(w):
     """quantize_weight_to_fp8 (fp8_native.py:25-30): returns (q uint8 [N,K] holding e4m3fn bytes, scale fp32 [N])"""
     L = _l.load()
