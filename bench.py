@@ -13,16 +13,19 @@ One "step" = prepare_batch (in-kernel noise + flow noising + target) -> MMDiT fo
                                                               --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1)
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel class (the bf16 MFMA
-GEMM, measured live with hipEvent pairs on the launch stream by libst355's profiler), `cpu_baseline` (the oracle timed on the
-host cores for a bounded sample, N=1 only) and `parity_at_config` (the same sample through the HIP model, compared).  The default
-(Flux) line also carries `secondary.sdxl_lora` (the SDXL-LoRA half of BASELINE.json's metric), `secondary.sd3_full_buckets` (configs[3]: SD3-Medium full
-fine-tune + EMA over mixed aspect buckets — the full-parameter gradient exchange), `secondary.flux_full_rank` (Flux.1-dev full-rank, AdamWBF16) and
-`secondary.sd3_lora_r128_bs3_published_row` (the reference's own published single-GPU row run like for like under hipGraph replay: `published` + `vs_baseline`),
-measured after the Flux timing at the same N; at N > 1 every entry carries `comm` (the gradient exchange's per-bucket timings).  `roofline` also names the
+GEMM, measured live with hipEvent pairs on the launch stream by libst355's profiler during the timed steps).  `roofline` also names the
 MEASURED vendor GEMM ceiling of this pool's boxes (`measured_vendor_gemm_ceiling`, tools/hipblaslt_ceiling.py).  `ms_per_step_stats` =
-median / p95 / min / max of the per-step device timestamps; `--model sd15 | sdxl | sd3 --full | pixart` lines carry their own `parity_at_config`.
+median / p95 / min / max of the per-step device timestamps; at N > 1 the line carries `comm` (the gradient exchange's per-bucket timings).
 `--dump-outputs DIR` writes what the last timed step of the headline workload computed (its loss and the trained parameters, float32 .npy; inputs, weights and
 the sample positions are seeded) so that two builds can be compared output for output.
+
+A plain run does only that: set up, warm up, time the steps, write the outputs, print the line.  `--full` adds everything that takes runs of its own,
+after the timed steps: `cpu_baseline` (the oracle timed on the host cores for a bounded sample, N=1 only) and `parity_at_config` (the same sample through
+the HIP model, compared; `--model sd15 | sdxl | sd3 --full-finetune | pixart` lines carry their own); on the default (Flux) line `secondary.sdxl_lora` (the
+SDXL-LoRA half of BASELINE.json's metric), `secondary.sd3_full_buckets` (configs[3]: SD3-Medium full fine-tune + EMA over mixed aspect buckets — the
+full-parameter gradient exchange), `secondary.flux_full_rank` (Flux.1-dev full-rank, AdamWBF16) and `secondary.sd3_lora_r128_bs3_published_row` (the
+reference's own published single-GPU row run like for like under hipGraph replay: `published` + `vs_baseline`), measured after the Flux timing at the same N,
+and `parity_at_other_configs`; under `--graph`, the `roofline` / `kernels` figures of one extra eager step.
 """
 from __future__ import annotations
 
@@ -54,7 +57,7 @@ PUBLISHED_SD3_LORA_R128_BS3 = {"none": 0.529, "layer": 0.721, "interval2": 0.723
 
 def published_row(args):
     """-> (mode, H100 sec/step) when the command line is one of the published SD3 rows, else None"""
-    if not (args.model == "sd3" and not args.full and int(args.rank) == 128 and int(args.batch) == 3 and args.res == 1024 and args.layers == 19 and not args.buckets):
+    if not (args.model == "sd3" and not args.full_finetune and int(args.rank) == 128 and int(args.batch) == 3 and args.res == 1024 and args.layers == 19 and not args.buckets):
         return None
     if not args.gradient_checkpointing:
         mode = "none"
@@ -101,8 +104,11 @@ def parse():
     ap.add_argument("--fp8", action="store_true", help="pixart only: fp8-native Linears in the frozen trunk blocks (configs[4]: 'fp8 MFMA')")
     ap.add_argument("--lora", action="store_true", help="sdxl: LoRA on the attention projections instead of the full fine-tune (the metric's SDXL-LoRA); pixart: LoRA on the trunk's attention projections instead of the ControlNet branch")
     ap.add_argument("--graph", action="store_true", help="capture predict + loss + backward into a hipGraph after two eager steps and replay it (launch-bound "
-                    "steps: the SDXL UNet); the per-kernel breakdown is then taken from ONE extra eager step after the timed region")
-    ap.add_argument("--full", action="store_true", help="flux / sd3 / sdxl / sd15: full-parameter training (every parameter trains, bf16 arena, one fused optimizer launch); sd3 + EMA = BASELINE configs[3], flux = the reference's full-rank datapoint")
+                    "steps: the SDXL UNet); with --full the per-kernel breakdown is then taken from ONE extra eager step after the timed region")
+    ap.add_argument("--full-finetune", action="store_true", help="flux / sd3 / sdxl / sd15: full-parameter training (every parameter trains, bf16 arena, one fused optimizer launch); sd3 + EMA = BASELINE configs[3], flux = the reference's full-rank datapoint")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the host-core leg (`cpu_baseline`) and `parity_at_config`, the default line's "
+                    "`secondary` workloads and `parity_at_other_configs`, and under --graph the extra eager step that the per-kernel figures are taken from.  Without it a "
+                    "run sets up, warms up, times its steps, writes --dump-outputs and prints its line")
     ap.add_argument("--optimizer", default="st355-adamw", choices=["st355-adamw", "adamw_bf16"])
     ap.add_argument("--buckets", action="store_true",
                     help="sd3: cycle the mixed aspect buckets of SURVEY.md §8(d) (latents 128x128, 96x168, 168x96, 112x144, 144x112), one bucket "
@@ -122,9 +128,9 @@ def parse():
                     "(SURVEY.md §8(f)3); with --ckpt-interval K [--ckpt-stride S] the reference's segmented modes (interval2 = K 2; seg2-stride4 = K 2 S 4)")
     ap.add_argument("--ckpt-interval", type=int, default=None)
     ap.add_argument("--ckpt-stride", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="flux only: skip the SDXL-LoRA, SD3 full-fine-tune (mixed buckets) and Flux full-rank secondary measurements appended to the default line")
-    ap.add_argument("--prof-dump", default=None, help="write one CSV line per launch of the timed steps (class,ms,flops,bytes,shape)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-core leg and the parity checks")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full, flux only: skip the SDXL-LoRA, SD3 full-fine-tune (mixed buckets) and Flux full-rank secondary measurements appended to the default line")
+    ap.add_argument("--prof-dump", default=None, help="write one CSV line per launch of the timed steps (class,ms,flops,bytes,shape); with --graph, of the extra eager step (needs --full)")
     ap.add_argument("--no-prof", action="store_true", help="disable the per-launch hipEvent profiler (roofline becomes null)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float32): loss.npy (the loss train_step returned) and "
@@ -133,6 +139,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.graph and a.prof_dump and not a.full:
+        ap.error("--prof-dump with --graph dumps the extra eager step after the timed region: it needs --full")
     if a.batch is None:
         a.batch = {"flux": 8, "sd3": 8, "sdxl": 4, "vae": 4, "sd15": 1, "pixart": 1}[a.model]     # sd3: 8 (r02: batch 4 -> 8 = 19.7 -> 23.9 images/s full fine-tune)
     return a
@@ -505,7 +513,7 @@ def main():
     out = run_workload(args, dev, rank, world)
     if rank == 0:
         _log(f"{args.model}: workload done")
-    if args.model == "flux" and not args.no_secondary:
+    if args.full and args.model == "flux" and not args.no_secondary:
         # the metric names "SDXL-LoRA & Flux-dev 1024^2": the SDXL-LoRA half rides along as a secondary measurement of the same run
         # (r16 on attn1/attn2 to_q/to_k/to_v/to_out.0, a few steps; hipGraph replay at every N — the gradient exchange follows each replay).  Per-GPU batch 32 (r6; 16
         # until r5, kept as the `same_tree_at_batch_16` field): the UNet's 32^2 / 64^2 levels give a 256-CU chip too few tiles per launch at small batches (measured
@@ -516,7 +524,7 @@ def main():
         keys = ("metric", "value", "unit", "ms_per_step", "ms_per_step_stats", "steps", "warmup", "config", "step_model_tflops", "step_frac_of_bf16_mfma_peak",
                 "roofline", "loss", "peak_hbm_gib", "published_context", "comm")
         a2 = copy.copy(args)
-        a2.model, a2.lora, a2.rank, a2.batch, a2.full, a2.graph, a2.buckets = "sdxl", True, 16, 32, False, True, False
+        a2.model, a2.lora, a2.rank, a2.batch, a2.full_finetune, a2.graph, a2.buckets = "sdxl", True, 16, 32, False, True, False
         # BASELINE.json configs[3]: SD3-Medium full fine-tune + EMA over the mixed aspect buckets — the full-parameter gradient exchange (2.0 B bf16 gradients
         # per step, reduce-scatter + all-gather buckets behind the backward) and the shared token-balanced bucket schedule run at every N the driver launches
         a3 = copy.copy(args)
@@ -524,17 +532,17 @@ def main():
         # peak for the five bucket graphs) but buys nothing: 302.5 ms under replay against ~300 eager on the same tree — this step is not launch-bound)
         # per-GPU batch 16 (r6; 8 until r5, kept as `same_tree_at_batch_8`): the fused optimizer + EMA pass (9 ms over 2.0 B parameters) and the split-K weight gradients
         # amortise over twice the tokens — r06, same box and tree: batch 8 / 12 / 16 / 24 / 32 = 26.7 / 28.3 / 28.8 / 29.4 / 29.9 images/s at 84 / 108 / 133 / 183 / 233 GiB
-        a3.model, a3.lora, a3.rank, a3.batch, a3.full, a3.graph, a3.buckets = "sd3", False, 32, 16, True, False, True
+        a3.model, a3.lora, a3.rank, a3.batch, a3.full_finetune, a3.graph, a3.buckets = "sd3", False, 32, 16, True, False, True
         # Flux.1-dev FULL-rank (11.9 B bf16 parameters, AdamWBF16, per-GPU batch 8 — the configuration of the reference's multi-GPU Flux datapoint,
         # documentation/DISTRIBUTED.md:291-298): hand-written backward with every weight / bias / modulation / norm gradient, one fused optimizer launch over the
         # parameter arena, and at N > 1 the whole 24 GB bf16 gradient arena exchanged per step (fp32-accumulating reduce-scatter + all-gather buckets behind the
         # backward).  Checkpoint plan interval 3 / stride 4: three of every four blocks are recomputed, the fourth keeps its activations (peak 211 GiB of 268)
         a4 = copy.copy(args)
-        a4.model, a4.lora, a4.rank, a4.batch, a4.full, a4.graph, a4.buckets = "flux", False, 32, 8, True, False, False
+        a4.model, a4.lora, a4.rank, a4.batch, a4.full_finetune, a4.graph, a4.buckets = "flux", False, 32, 8, True, False, False
         # The reference's own published single-GPU row that this path covers like for like (example sd3.peft-lora — SD3-Medium LoRA r128, 1024^2,
         # batch 3, bf16, no activation checkpointing: 0.529 s/step on one H100): hipGraph replay of the captured step; `published` + `vs_baseline` ride on its entry
         a5 = copy.copy(args)
-        a5.model, a5.lora, a5.rank, a5.batch, a5.full, a5.graph, a5.buckets, a5.res = "sd3", False, 128, 3, False, True, False, 1024
+        a5.model, a5.lora, a5.rank, a5.batch, a5.full_finetune, a5.graph, a5.buckets, a5.res = "sd3", False, 128, 3, False, True, False, 1024
         if rank == 0:
             out["secondary"] = {}
         keys = keys + ("published", "vs_baseline")
@@ -619,8 +627,8 @@ def run_workload(args, dev, rank, world):
     cfg = default_config(model_family=args.model, lora_rank=args.rank, train_batch_size=args.batch, seed=42, lora_init_b_std=1e-3,   # weights / adapter init / rounding seeds are REPLICA-identical; the data RNG below is per rank
                          flux_lora_target=getattr(args, "lora_target", "default"),
                         
-                         model_type="full" if args.full else "lora", use_ema=bool(args.full) and args.model != "flux", optimizer=args.optimizer,
-                         learning_rate=1e-5 if args.full else 1e-4, hip_graph=bool(args.graph),
+                         model_type="full" if args.full_finetune else "lora", use_ema=bool(args.full_finetune) and args.model != "flux", optimizer=args.optimizer,
+                         learning_rate=1e-5 if args.full_finetune else 1e-4, hip_graph=bool(args.graph),
                          gradient_checkpointing=bool(getattr(args, "gradient_checkpointing", False)),
                          gradient_checkpointing_interval=getattr(args, "ckpt_interval", None), gradient_checkpointing_segment_stride=getattr(args, "ckpt_stride", None))
     acc = St355Accelerator(dev)
@@ -637,7 +645,7 @@ def run_workload(args, dev, rank, world):
         from simpletuner_amd.sdxl.model import SDXL
         from tools.flop_count import unet_flops_fwd            # arithmetic over the model's own config
         sdxl_lora = bool(args.lora)
-        args.full = not sdxl_lora
+        args.full_finetune = not sdxl_lora
         cfg.model_type, cfg.use_ema, cfg.learning_rate = ("lora" if sdxl_lora else "full"), False, (1e-4 if sdxl_lora else 1e-5)
         plugin = SDXL(cfg, acc)
         plugin.load_model()
@@ -649,10 +657,10 @@ def run_workload(args, dev, rank, world):
                 f"{args.res}^2 ({args.res // 8}^2 latents), epsilon objective, AdamW, random-init weights")
     elif args.model == "sd15":
         # BASELINE.json configs[0]: SD 1.5 UNet LoRA rank 16, 512^2, batch 1 (the reference's CPU-runnable plumbing case) — run it with
-        # `--model sd15 --rank 16 --res 512 --batch 1`; --full switches to the full fine-tune
+        # `--model sd15 --rank 16 --res 512 --batch 1`; --full-finetune switches to the full fine-tune
         from simpletuner_amd.sd1x.model import StableDiffusion1
         from tools.flop_count import unet_flops_fwd
-        sd15_lora = not args.full
+        sd15_lora = not args.full_finetune
         cfg.model_type, cfg.use_ema, cfg.learning_rate = ("lora" if sd15_lora else "full"), False, (1e-4 if sd15_lora else 1e-5)
         plugin = StableDiffusion1(cfg, acc)
         plugin.load_model()
@@ -698,9 +706,9 @@ def run_workload(args, dev, rank, world):
                 f"{args.res}^2 (S=4096+231), AdamW, random-init weights")
     if args.model == "pixart":
         pass
-    elif args.full:
+    elif args.full_finetune:
         if args.model not in ("sd3", "sdxl", "sd15", "flux"):
-            raise SystemExit("--full is wired for --model flux / sd3 / sdxl / sd15")
+            raise SystemExit("--full-finetune is wired for --model flux / sd3 / sdxl / sd15")
         plugin.enable_full_finetune()
         comp_ = plugin.get_trained_component()
         n_par = sum(p.numel() for p in (comp_.trainable_parameters() if hasattr(comp_, "trainable_parameters") else [q for q in comp_.parameters() if q.requires_grad]))
@@ -788,7 +796,8 @@ def run_workload(args, dev, rank, world):
         dump_outputs(args.dump_outputs, {"loss": [float(loss.item())], "trained_params": _flat_sample(trainer.params)})
     prof = None
     prof_steps = args.steps
-    if args.graph and not args.no_prof:
+    prof_extra = args.graph and args.full and not args.no_prof      # a step of its own after the timed region: --full only
+    if prof_extra:
         trainer._use_graph = False
         trainer.optimizer.zero_grad(set_to_none=True)
         trainer.release_graphs()                 # the captured step's pool (173 GiB at SDXL-LoRA batch 32) goes back before the eager step needs its own activations
@@ -796,7 +805,7 @@ def run_workload(args, dev, rank, world):
         trainer.train_step(dict(batches[0]))
         sync()
         prof_steps = 1
-    if not args.no_prof:
+    if prof_live or prof_extra:
         ops.prof_enable(False)
         prof = ops.prof_collect()
         if args.prof_dump and rank == 0:
@@ -825,7 +834,7 @@ def run_workload(args, dev, rank, world):
     if rank == 0:
         S_img = (lat // 2) ** 2
         step_flops = train_flops_per_image(n_blocks, D_model, S_img + S_txt) * B
-        if args.model == "flux" and not args.full and getattr(args, "lora_target", "default") in ("tiny", "nano"):
+        if args.model == "flux" and not args.full_finetune and getattr(args, "lora_target", "default") in ("tiny", "nano"):
             # single_transformer_blocks.7(.20).proj_out only: the backward runs from the last block down to single block 7 and stops — forward over every block, backward
             # (1x linears, 2x attention) over the blocks at or above it
             S_ = S_img + S_txt
@@ -834,11 +843,11 @@ def run_workload(args, dev, rank, world):
             step_flops = (n_blocks * (per_lin + per_att) + n_bwd * (per_lin + 2 * per_att)) * B
         if args.model == "pixart":
             step_flops = pix_step_flops * B
-        elif args.model in ("sdxl", "sd15") and not args.full:   # LoRA: forward + input gradients (no base weight gradients): 2x forward, attention bwd 2x
+        elif args.model in ("sdxl", "sd15") and not args.full_finetune:   # LoRA: forward + input gradients (no base weight gradients): 2x forward, attention bwd 2x
             step_flops = 2.0 * sdxl_fwd_flops * B
         elif args.model in ("sdxl", "sd15"):   # full fine-tune = 3x the forward (fwd + dgrad + wgrad; attention fwd + 2x bwd), tools/flop_count.py::unet_flops_fwd
             step_flops = 3.0 * sdxl_fwd_flops * B
-        elif args.full:      # full fine-tune: fwd + dgrad + wgrad on the linears (3x), attention fwd + 2x bwd (3x)  
+        elif args.full_finetune:      # full fine-tune: fwd + dgrad + wgrad on the linears (3x), attention fwd + 2x bwd (3x)  
             step_flops = 3.0 * (n_blocks * 2.0 * (S_img + S_txt) * 12 * D_model * D_model + n_blocks * 4.0 * (S_img + S_txt) ** 2 * D_model) * B
         ms_per_step = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
@@ -849,7 +858,7 @@ def run_workload(args, dev, rank, world):
             if g["ms"] > 0:
                 ach = g["flops"] / (g["ms"] * 1e-3) / 1e12
                 # the committed PMC passes: of the default command, and of the metric's second workload (SDXL-LoRA, eager launches of the same kernels)
-                traffic, tsrc = (hbm_traffic_per_gemm_launch() if (args.model == "flux" and not args.full) else
+                traffic, tsrc = (hbm_traffic_per_gemm_launch() if (args.model == "flux" and not args.full_finetune) else
                                  hbm_traffic_per_gemm_launch("sdxl_lora") if (args.model == "sdxl" and args.lora and B == 16) else (None, None))     # (that counter pass is of batch 16; at batch 32 rocprofv3 --pmc aborts with an AQL packet error, r06)
                 roof = {"bound": "mfma", "kernel": "k_gemm_* (all schedules / epilogues)", "achieved": round(ach, 1), "peak": PEAK_BF16_TFLOPS,
                         "unit": "TFLOP/s", "frac": round(ach / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_unit": "HBM bytes / launch",
@@ -869,7 +878,7 @@ def run_workload(args, dev, rank, world):
                        for k, v in prof.items() if v["launches"]}
         out = {
             "metric": f"training images/sec (whole node), {dict(flux='Flux.1-dev', sd3='SD3-Medium', sdxl='SDXL', sd15='SD 1.5', pixart='PixArt-Sigma')[args.model]} "
-                      f"{'ControlNet branch' if (args.model == 'pixart' and not args.lora) else ('full fine-tune' + (' + EMA' if cfg.use_ema else '')) if args.full else f'LoRA r{args.rank}'} {args.res}^2 train step",
+                      f"{'ControlNet branch' if (args.model == 'pixart' and not args.lora) else ('full fine-tune' + (' + EMA' if cfg.use_ema else '')) if args.full_finetune else f'LoRA r{args.rank}'} {args.res}^2 train step",
             "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 2), "ms_per_step_stats": step_stats, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16 (+ fp8 e5m2 x e4m3 trunk Linears)" if getattr(args, "fp8", False) else "bf16", "data": "synthetic",
@@ -898,17 +907,18 @@ def run_workload(args, dev, rank, world):
             out["published"] = {"row": f"SD3 LoRA r128 1024^2 bs 3, bf16, checkpointing mode {pub[0]!r} (example sd3.peft-lora, optimizer adamw_bf16; this run: optimizer {args.optimizer!r}" + (" — bf16 adapter values and bf16 gradients under the fused AdamWBF16, as in the example)" if args.optimizer == "adamw_bf16" else " — fused fp32 AdamW over the fp32 adapter arena, NOT the example's optimizer)"), "sec_per_step": pub[1],
                                 "images_per_s": round(ref_ips, 3), "hardware": "1x H100 (the reference's own sweep; BASELINE.md §1)",
                                 "source": "documentation/experimental/SEGMENTED_CHECKPOINTING.md:795-805", "this_run_sec_per_step": round(ms_per_step / 1e3, 4)}
-        if args.model == "flux" and args.full:
+        if args.model == "flux" and args.full_finetune:
             # context only (vs_baseline stays null: a 32-GPU multi-node DeepSpeed figure incl. its inter-node exchange is not this configuration)
             out["published_context"] = {"row": "Flux.1-dev (12B) full-rank, 1024 px buckets, batch 8 per accelerator, 4 nodes x 8 H100 SXM5, DeepSpeed: 15 s/step (anecdotal)",
                                         "images_per_s_per_gpu": round(8 / 15.0, 3), "source": "documentation/DISTRIBUTED.md:291-298 (BASELINE.md section 1)",
                                         "this_run_images_per_s_per_gpu": round(value / world, 3)}
-        if world == 1 and not args.no_cpu_baseline and args.model == "flux":
+        checks = args.full and world == 1 and not args.no_cpu_baseline      # the host-core leg and the oracle parity checks: --full only
+        if checks and args.model == "flux":
             del trainer, plugin, batches
             torch.cuda.empty_cache()
             _log("flux: timed region done, host-core leg")
             out["cpu_baseline"], out["parity_at_config"] = cpu_baseline(args, dev)
-            if out["parity_at_config"] is not None and args.layers == 19 and args.single_layers == 38 and not args.full and time.time() - _T0 < 240.0:
+            if out["parity_at_config"] is not None and args.layers == 19 and args.single_layers == 38 and not args.full_finetune and time.time() - _T0 < 240.0:
                 # the same check at the configuration's REAL depth (19 + 38 blocks, all 380 adapter gradients): the figures the GPU suite asserts
                 # (tests/test_baseline_shapes_gpu.py::test_flux_full_depth_step_matches_oracle) — the 1 + 1-block form above is what the host-core leg timed
                 try:
@@ -922,13 +932,13 @@ def run_workload(args, dev, rank, world):
                     gc.collect(); torch.cuda.empty_cache()
                 except Exception as e:            # noqa: BLE001
                     out["parity_at_config"] = {"full_depth": {"error": f"{type(e).__name__}: {e}"[:300]}, "one_plus_one_blocks_of_the_host_core_leg": out["parity_at_config"]}
-        elif world == 1 and not args.no_cpu_baseline and args.model in ("sd15", "sdxl"):
+        elif checks and args.model in ("sd15", "sdxl"):
             del trainer, plugin, batches
             torch.cuda.empty_cache()
-            out["cpu_baseline"] = cpu_baseline_unet(args, sd15=args.model == "sd15", lora=not args.full)
+            out["cpu_baseline"] = cpu_baseline_unet(args, sd15=args.model == "sd15", lora=not args.full_finetune)
             from tests import parity_at_config as PC       # the oracle as the checker of the HIP component at this configuration (never the thing timed)
-            out["parity_at_config"] = PC.unet(args.model, args.res, dev, lora=not args.full, rank=int(args.rank))
-        elif world == 1 and not args.no_cpu_baseline and args.model in ("sd3", "pixart"):
+            out["parity_at_config"] = PC.unet(args.model, args.res, dev, lora=not args.full_finetune, rank=int(args.rank))
+        elif checks and args.model in ("sd3", "pixart"):
             del trainer, plugin, batches
             torch.cuda.empty_cache()
             from tests import parity_at_config as PC
@@ -936,7 +946,7 @@ def run_workload(args, dev, rank, world):
                 pass                                  # (the LoRA-on-the-trunk mode is a secondary measurement: its parity is the GPU suite's, tests/test_pixart_model_gpu.py)
             elif args.model == "pixart":
                 out["parity_at_config"] = PC.pixart_controlnet(args.res, dev)
-            elif args.full:
+            elif args.full_finetune:
                 out["parity_at_config"] = PC.sd3_full(args.res, dev)
         return out
     return None

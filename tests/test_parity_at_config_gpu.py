@@ -1,5 +1,5 @@
 """Parity at the BASELINE.json configurations other than Flux: see tests/parity_at_config.py — the same functions bench.py reports as
-`parity_at_config` on `--model sd15 / sdxl / sd3 --full / pixart`.  (Flux: tests/test_baseline_shapes_gpu.py, full width AND full depth.)"""
+`parity_at_config` on `--model sd15 / sdxl / sd3 --full-finetune / pixart` under `--full`.  (Flux: tests/test_baseline_shapes_gpu.py, full width AND full depth.)"""
 import pytest
 import torch
 

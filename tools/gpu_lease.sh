@@ -1,14 +1,14 @@
 #!/bin/bash
 # The measurement recipes behind profiles/ as ONE script (run on the GPU box from the repo root, e.g. `gpurun --timeout 2400 -- tools/gpu_lease.sh final`).
 # Each recipe writes under gpurun_out/; what is kept is copied into profiles/ by hand (profiles/README.md says which file came from which recipe).
-#   final         the end-of-round sequence: rocprofv3 stats + PMC passes (tools/profile_round.sh), pytest -m gpu, smoke(), python bench.py
+#   final         the end-of-round sequence: rocprofv3 stats + PMC passes (tools/profile_round.sh), pytest -m gpu, smoke(), python bench.py --full
 #   validate      the same without the profile passes
 #   gemm_power    GEMM tile-group width sweep: rate, package power / sclk mid-run, FETCH_SIZE per launch        (profiles/r05_gemm_power.md; build the lab binaries first:
 #                 for g in 2 4 8 16 32; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -DST355_TILE_GROUP=$g tools/gemm_lab.hip -o tools/gemm_lab_g$g; done)
 #   tn_slices     split-K slice count of the weight-gradient GEMMs: lab sweep + in-step A/B                      (profiles/r05_tn_slice_count_*)
 #   attn_hd96     head_dim-96 attention bodies, committed vs a variant binary tools/attn_lab_<name>              (profiles/r05_attn_lab_hd96_*; tools/kgen/variants.sh builds variants)
 #   sd3_stats     rocprofv3 --kernel-trace --stats of the SD3-Medium full fine-tune step by kernel name           (profiles/r05_sd3_full_b8_rocprofv3_kernel_stats.csv)
-#   shapes MODEL… per-shape launch table of a bench workload: tools/gpu_lease.sh shapes --model sd3 --full --batch 8   (profiles/r05_*_shapes.txt)
+#   shapes MODEL… per-shape launch table of a bench workload: tools/gpu_lease.sh shapes --model sd3 --full-finetune --batch 8   (profiles/r05_*_shapes.txt)
 #   two_ranks     bench.py --gpus 2 on one device over gloo (plumbing) + a rank that fails on purpose             (profiles/r05_two_ranks_*)
 #   sanity        smoke(), the resume / graph / golden GPU tests, the headline step without secondaries (two minutes)
 #   pmc           PMC passes (matrix-pipe busy, LDS, waits) over the labs: GEMM on the step's shapes, attention at the Flux / PixArt 2K shapes   (profiles/r05_pmc_mfma_lds.md)
@@ -33,8 +33,8 @@ case "$recipe" in
     timeout 1500 python -m pytest tests -q -m gpu 2>&1 | grep -v "amdgpu.ids" | tail -15 | cut -c1-300 | tee gpurun_out/gpu_suite_summary.log
     echo "[lease] gpu suite done at +$(( $(date +%s) - t0 )) s" | tee -a gpurun_out/gpu_suite_summary.log
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v "amdgpu.ids" | tail -4 | tee -a gpurun_out/gpu_suite_summary.log
-    timeout 900 python bench.py > gpurun_out/bench_line.json 2> gpurun_out/bench_progress.log
-    echo "[lease] bench done at +$(( $(date +%s) - t0 )) s"; line gpurun_out/bench_line.json ;;
+    b=$(mktemp -d); timeout 900 python bench.py --full > $b/bench_line.json 2> $b/bench_progress.log      # the line and its progress stamps are printed below
+    echo "[lease] bench done at +$(( $(date +%s) - t0 )) s"; grep "^\[bench" $b/bench_progress.log; line $b/bench_line.json; tail -1 $b/bench_line.json; rm -rf $b ;;
   gemm_power)
     out=gpurun_out/gemm_tile_order.log; : > $out
     export ST355_GEMM_IMPL=pq
@@ -62,7 +62,7 @@ print('FETCH_SIZE/launch %.3f GB (x2 on gfx950: MI355X_MICROARCH.md)' % (2 * 102
       for ks in -1 0 3 5 7 9; do ST355_TN_KS=$ks LAB_TN=$shape timeout 60 tools/gemm_lab --child 2>&1 | grep "TN" >> $L; done
     done
     cut -c1-150 $L
-    for m in -1 0 -1 0; do ST355_TN_KS=$m timeout 400 python bench.py --model sd3 --full --batch 8 --steps 4 --warmup 2 --no-cpu-baseline > gpurun_out/sd3_full_b8_tnks$m.json 2> /dev/null; line gpurun_out/sd3_full_b8_tnks$m.json; done ;;
+    b=$(mktemp -d); for m in -1 0 -1 0; do ST355_TN_KS=$m timeout 400 python bench.py --model sd3 --full-finetune --batch 8 --steps 4 --warmup 2 --no-cpu-baseline > $b/sd3_full_b8_tnks$m.json 2> /dev/null; line $b/sd3_full_b8_tnks$m.json; done; rm -rf $b ;;
   attn_hd96)
     L=gpurun_out/attn_lab_hd96.log; : > $L
     for v in "$@"; do
@@ -73,7 +73,7 @@ print('FETCH_SIZE/launch %.3f GB (x2 on gfx950: MI355X_MICROARCH.md)' % (2 * 102
     grep -i "TFLOP\|===\|MISMATCH\|identical\|rounding" $L | cut -c1-160 ;;
   sd3_stats)
     R=$PWD; out=$R/gpurun_out/prof_sd3; rm -rf $out; mkdir -p $out
-    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python $R/bench.py --model sd3 --full --batch 8 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench.log 2>&1)
+    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python $R/bench.py --model sd3 --full-finetune --batch 8 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench.log 2>&1)
     python - <<'PY'
 import csv, glob
 rows = [r for f in glob.glob("gpurun_out/prof_sd3/stats/**/*kernel_stats.csv", recursive=True) for r in csv.DictReader(open(f))]
@@ -92,7 +92,7 @@ PY
     python tools/prof_shapes.py gpurun_out/shapes_dump.csv 3 | tee gpurun_out/shapes.txt | head -70 | cut -c1-150; rm -f gpurun_out/shapes_dump.csv; line gpurun_out/shapes_line.json ;;
   two_ranks)
     export ST355_BENCH_SHARE_GPU=1
-    for extra in "--rank 16" "--full"; do
+    for extra in "--rank 16" "--full-finetune"; do
       timeout 300 python bench.py --gpus 2 --model sd3 $extra --batch 1 --layers 2 --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/two_ranks_$(echo $extra | tr -d ' -').json 2> gpurun_out/two_ranks.log
       echo "exit code $?"; line gpurun_out/two_ranks_$(echo $extra | tr -d ' -').json
     done

@@ -1,5 +1,5 @@
 R=$PWD
-for cfg in "sdxl --model sdxl --lora --rank 16 --batch 16" "sd3 --model sd3 --full --batch 8 --buckets"; do
+for cfg in "sdxl --model sdxl --lora --rank 16 --batch 16" "sd3 --model sd3 --full-finetune --batch 8 --buckets"; do
   set -- $cfg; name=$1; shift
   out=$R/gpurun_out/prof_$name; rm -rf $out; mkdir -p $out
   (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python $R/bench.py "$@" --steps 4 --warmup 1 --no-cpu-baseline --no-prof > $out/bench.log 2>&1)
