@@ -352,7 +352,7 @@ int st355_qk_rope_norm_bwd(void* stream, const void* dQ, const void* dK, const v
 /* O: [B,S,H*d] token-major bf16 (row stride ld_o elements); lse2: [B,H,S] fp32 (log2-domain logsumexp of
  * scale*q.k); key_bias: fp32 [B,S] additive (natural-log units) or NULL.
  * d = 64, 96 or 128.  d = 96 is the width of a ZERO-PADDED narrower head (PixArt-Sigma's 72, SD 1.5's 80): channels [80, 96) of Q, K, V and dO must be zero — the
- * 64-row forward / dQ kernels contract q.k and dO.v over 80 channels (5 MFMA k-steps instead of 6; the d-output side keeps 96).  A head wider than 80 pads to 128. */
+ * 64-row forward / dQ kernels and the dkv4 dK / dV body contract q.k and dO.v over 80 channels (5 MFMA k-steps instead of 6; the d-output side keeps 96).  A head wider than 80 pads to 128. */
 /* Kernel choice for the no-bias self-attention shapes (tuning / A-B hook): the forward choice applies at head_dim 128 and 96, the dq / dkv choices at
  * head_dim 128, 96 and 64; every other shape (key bias, cross attention, row-major V) keeps the 32-query kernels whatever is set here.
  *   fwd: 64 = the hand-scheduled one-wave-per-SIMD forward where S % 64 == 0 (k_attn_fwd64: 64 queries per wave, stale-reference softmax; the scores are
@@ -380,6 +380,23 @@ int st355_attn_bwd(void* stream, const void* Q, const void* K, const void* Qt, c
                    const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o, const void* dO, int64_t ld_do,
                    const float* lse2, const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv,
                    int B, int H, int S, int Sp, int d, float scale, void* workspace);
+/* The kernels an attention forward + backward of this shape would run on now, without launching anything (the launchers take the same decisions).
+ * Sq / Sk: query / key lengths (self-attention: Sq = Sk); flags: ST355_ATTN_PLAN_* for what the call is given (key bias, row-major V in the forward, O_res,
+ * the Qt / Kt copies in the backward, the fused RoPE backward of st355_attn_bwd_rope).  Honours st355_attn_set_impl and ST355_ATTN_DQ_SHORT.
+ * routes[0] forward, [1] backward prep, [2] dK / dV, [3] dQ: ST355_ATTN_ROUTE_<kernel> + (0 / 1 / 2 for head_dim 64 / 96 / 128); routes[4] = 1 when a dQ tail
+ * launch (k_attn_bwd_dq over the last, ragged key tile) follows the 64-row dQ kernel, else 0.  Validates d and the flag combination as the launch would. */
+enum { ST355_ATTN_PLAN_BIAS = 1, ST355_ATTN_PLAN_VROWS = 2, ST355_ATTN_PLAN_RES = 4, ST355_ATTN_PLAN_QT = 8, ST355_ATTN_PLAN_KT = 16, ST355_ATTN_PLAN_ROPE = 32 };
+enum { ST355_ATTN_ROUTE_FWD64 = 10 /* k_attn_fwd64 (96, 128) */, ST355_ATTN_ROUTE_FWD4 = 20, ST355_ATTN_ROUTE_FWD4_BIAS = 30,
+       ST355_ATTN_ROUTE_FWD4_RES = 40 /* k_attn_fwd4 writing O_res */, ST355_ATTN_ROUTE_FWD4_RES_BIAS = 50,
+       ST355_ATTN_ROUTE_FWD4_VROWS = 60 /* k_attn_fwd4<128, *, true> (128) */, ST355_ATTN_ROUTE_FWD4_VROWS_BIAS = 70,
+       ST355_ATTN_ROUTE_PREP = 100, ST355_ATTN_ROUTE_PREP_RES = 110 /* delta from O + O_res */, ST355_ATTN_ROUTE_PREP_DOT = 120 /* + the dO^T copy */,
+       ST355_ATTN_ROUTE_PREP_RES_DOT = 130,
+       ST355_ATTN_ROUTE_DKV4 = 200, ST355_ATTN_ROUTE_DKV4_ROPE = 210 /* (128) */, ST355_ATTN_ROUTE_DKV3 = 220, ST355_ATTN_ROUTE_DKV3_ROPE = 230 /* (128) */,
+       ST355_ATTN_ROUTE_DKV2 = 240,
+       ST355_ATTN_ROUTE_DQ64 = 300, ST355_ATTN_ROUTE_DQ64_ROPE = 310 /* (128) */, ST355_ATTN_ROUTE_DQ_TR = 320 /* k_attn_bwd_dq<d, true, false> */,
+       ST355_ATTN_ROUTE_DQ_TR_BIAS = 330, ST355_ATTN_ROUTE_DQ = 340 /* k_attn_bwd_dq<d, false, false>: K^T copy given */, ST355_ATTN_ROUTE_DQ_BIAS = 350,
+       ST355_ATTN_ROUTE_DQ_TR_ROPE = 360 /* (128) */, ST355_ATTN_ROUTE_DQ_TR_BIAS_ROPE = 370 /* (128) */ };
+int st355_attn_plan(int B, int H, int Sq, int Sk, int d, int flags, int32_t* routes);
 
 /* ---- K16/K17: fused AdamW (+EMA) over a flat parameter arena (optimizer_param.py:87-96, ema.py:393-433) */
 /* p,g,m,v fp32 [n].  torch.optim.AdamW semantics (decoupled decay, bias correction, eps outside sqrt of v_hat).

@@ -361,6 +361,16 @@ static int attn_fwd_impl64() {
   return g_attn_fwd_impl;
 }
 
+// The forward's kernel choice (ST355_ATTN_ROUTE_* + head_dim index), shared by attn_fwd_impl and st355_attn_plan (attention_bwd.hip); d is 64, 96 or 128.
+// k_attn_fwd4 (r02) is the general kernel; k_attn_fwd64 (r04) takes the head_dim-128 / 96, no-bias, S % 64 == 0 shapes.
+int attn_fwd_route(int d, int S, bool bias, bool vrow, bool res) {
+  const int hd = d == 64 ? 0 : d == 96 ? 1 : 2;
+  if (!vrow && !bias && !res && (d == 128 || d == 96) && S % 64 == 0 && attn_fwd_impl64() == 64) return ST355_ATTN_ROUTE_FWD64 + hd;
+  if (vrow) return (bias ? ST355_ATTN_ROUTE_FWD4_VROWS_BIAS : ST355_ATTN_ROUTE_FWD4_VROWS) + hd;
+  if (res) return (bias ? ST355_ATTN_ROUTE_FWD4_RES_BIAS : ST355_ATTN_ROUTE_FWD4_RES) + hd;
+  return (bias ? ST355_ATTN_ROUTE_FWD4_BIAS : ST355_ATTN_ROUTE_FWD4) + hd;
+}
+
 // vrow != 0: Vt is the ROW-major V (token rows, head h at columns h*d) and Sp its leading dimension (k_attn_fwd4<128, *, true>)
 static int attn_fwd_impl(void* stream, const void* Q, const void* K, const void* Vt, const float* key_bias, void* O,
                          int64_t ld_o, float* lse2, int B, int H, int Sq, int S, int Sp, int d, float scale, int vrow = 0, void* O_res = nullptr) {
@@ -372,10 +382,10 @@ static int attn_fwd_impl(void* stream, const void* Q, const void* K, const void*
   const double bytes = 2.0 * (double)B * H * (Sq + S) * d * 2.0;
   ProfScope ps(stream, ST355_K_ATTN_FWD, flops, bytes);
   const float scale2 = scale * LOG2E;
-  // k_attn_fwd4 (r02) is the general kernel; k_attn_fwd64 (r04) takes the head_dim-128, no-bias, S % 64 == 0 shapes.  The r01 kernel lives on in
-  // tools/attn_fwd_variants.hip as the lab's A/B baseline (r02 lab, B8 H24 S4608 d128: 862 -> 927 TFLOP/s).  Measured and deleted in r02: an 8-wave /
-  // 256-query workgroup variant (843 TFLOP/s) and an 8-wave LDS-DMA half-tile-stagger variant (738); logs under profiles/archive/r02_attn_lab_*.log.
-  if (!vrow && !key_bias && !O_res && (d == 128 || d == 96) && S % 64 == 0 && attn_fwd_impl64() == 64) {      // hand-scheduled 64-queries-per-wave kernel
+  // The r01 kernel lives on in tools/attn_fwd_variants.hip as the lab's A/B baseline (r02 lab, B8 H24 S4608 d128: 862 -> 927 TFLOP/s).  Measured and deleted
+  // in r02: an 8-wave / 256-query workgroup variant (843 TFLOP/s) and an 8-wave LDS-DMA half-tile-stagger variant (738); logs under profiles/archive/r02_attn_lab_*.log.
+  const int route = attn_fwd_route(d, S, key_bias != nullptr, vrow != 0, O_res != nullptr);
+  if (route / 10 * 10 == ST355_ATTN_ROUTE_FWD64) {      // hand-scheduled 64-queries-per-wave kernel
     dim3 grid64((Sq + 255) / 256, H, B);
     const int lds64 = 4 * 2 * 64 * 256;
 #define ST355_FWD64_LAUNCH(HD_)                                                                                                           \
@@ -399,10 +409,10 @@ static int attn_fwd_impl(void* stream, const void* Q, const void* K, const void*
     hipLaunchKernelGGL((KERN), grid, block, lds, (hipStream_t)stream, (const bf16*)Q, (const bf16*)K, (const bf16*)Vt, key_bias,         \
                        (bf16*)O, ld_o, lse2, H, Sq, S, Sp, scale2, (bf16*)O_res);                                                       \
   } while (0)
-  if (vrow) {
-    if (key_bias) ST355_FWD_LAUNCH((k_attn_fwd4<128, true, true>));
-    else ST355_FWD_LAUNCH((k_attn_fwd4<128, false, true>));
-  } else if (key_bias) {
+  const int kind = route / 10 * 10;
+  if (kind == ST355_ATTN_ROUTE_FWD4_VROWS_BIAS) ST355_FWD_LAUNCH((k_attn_fwd4<128, true, true>));
+  else if (kind == ST355_ATTN_ROUTE_FWD4_VROWS) ST355_FWD_LAUNCH((k_attn_fwd4<128, false, true>));
+  else if (kind == ST355_ATTN_ROUTE_FWD4_BIAS || kind == ST355_ATTN_ROUTE_FWD4_RES_BIAS) {      // (O_res != NULL: the same kernel also writes the residual)
     if (d == 128) ST355_FWD_LAUNCH((k_attn_fwd4<128, true>));
     else if (d == 96) ST355_FWD_LAUNCH((k_attn_fwd4<96, true>));          // PixArt's head_dim 72 zero-padded to 96 (3 d-tiles of 32, 6 k-steps of 16)
     else ST355_FWD_LAUNCH((k_attn_fwd4<64, true>));

@@ -1022,6 +1022,40 @@ static int attn_dq_impl() {
   return g_attn_dq_impl;
 }
 
+// ST355_ATTN_DQ_SHORT=0: a ragged key axis shorter than 128 back on the 64-row dQ kernel + tail form (A/B)
+static int attn_dq_short() {
+  static int dq_short = -1;
+  if (dq_short < 0) { const char* e = getenv("ST355_ATTN_DQ_SHORT"); dq_short = (e && e[0] == '0') ? 0 : 1; }
+  return dq_short;
+}
+
+// The backward's kernel choices (ST355_ATTN_ROUTE_* + head_dim index per stage), shared by attn_bwd_impl and st355_attn_plan; d is 64, 96 or 128.
+// qt / kt: the Q^T (+ dO^T) / K^T copies are given; rope_q / rope_k: the fused RoPE epilogue writes dQ / dK (then no head-major dQ / dK exists).
+struct AttnBwdRoute { int prep, dkv, dq, dq_tail; };
+static AttnBwdRoute attn_bwd_route(int d, int Sk, bool qt, bool kt, bool bias, bool res, bool rope_q, bool rope_k) {
+  const int hd = d == 64 ? 0 : d == 96 ? 1 : 2;
+  AttnBwdRoute r{};
+  r.prep = (res ? (qt ? ST355_ATTN_ROUTE_PREP_RES_DOT : ST355_ATTN_ROUTE_PREP_RES) : (qt ? ST355_ATTN_ROUTE_PREP_DOT : ST355_ATTN_ROUTE_PREP)) + hd;
+  if (!qt && !bias && attn_dkv_impl() == 4) r.dkv = (rope_k ? ST355_ATTN_ROUTE_DKV4_ROPE : ST355_ATTN_ROUTE_DKV4) + hd;     // every head_dim built
+  else if (!qt) r.dkv = (rope_k ? ST355_ATTN_ROUTE_DKV3_ROPE : ST355_ATTN_ROUTE_DKV3) + hd;
+  else r.dkv = ST355_ATTN_ROUTE_DKV2 + hd;          // head-major Q^T / dO^T copies supplied: the LDS-DMA kernel over four tile images
+  // the 64-row kernel takes the full 64-key tiles; a ragged key tail (SD3's S = 4096 + 231, every mixed-aspect bucket) is added by the general kernel restricted
+  // to the last tile (kt0 / accumulate).  The fused-RoPE epilogue (head_dim 128, Flux: S % 64 == 0 always) writes projection rows, not dQ: no tail form.
+  const bool dq_tail = Sk % 64 != 0;
+  // a SHORT ragged key axis (the UNets' cross-attention: 77 text keys = one full tile + 13 keys) goes through the general kernel in ONE pass: as 64-row kernel + tail
+  // it was two memory-bound passes over Q / dO / dQ with a bf16 round trip of dQ between them (r6; ST355_ATTN_DQ_SHORT=0: A/B)
+  const bool short_ragged = attn_dq_short() && dq_tail && Sk < 128;
+  if (!kt && !bias && attn_dq_impl() == 64 && Sk >= 64 && !short_ragged && (!dq_tail || !rope_q)) {      // hand-scheduled 64-queries-per-wave kernel
+    r.dq = (rope_q ? ST355_ATTN_ROUTE_DQ64_ROPE : ST355_ATTN_ROUTE_DQ64) + hd;
+    r.dq_tail = dq_tail;
+  } else if (!kt) {                                  // no K^T copy: transposing-read kernel (K tile image at a 256-byte row pitch)
+    r.dq = (rope_q ? (bias ? ST355_ATTN_ROUTE_DQ_TR_BIAS_ROPE : ST355_ATTN_ROUTE_DQ_TR_ROPE) : (bias ? ST355_ATTN_ROUTE_DQ_TR_BIAS : ST355_ATTN_ROUTE_DQ_TR)) + hd;
+  } else {
+    r.dq = (bias ? ST355_ATTN_ROUTE_DQ_BIAS : ST355_ATTN_ROUTE_DQ) + hd;
+  }
+  return r;
+}
+
 extern int g_attn_fwd_impl;                        // attention.hip
 extern "C" int st355_attn_set_impl(int fwd, int dq, int dkv) {
   if (g_attn_fwd_impl < 0) { const char* e = getenv("ST355_ATTN_FWD64"); g_attn_fwd_impl = (e && e[0] == '0') ? 32 : 64; }
@@ -1052,7 +1086,9 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
   const double fl_unit = 2.0 * (double)B * H * (double)S * Sk * d;  // one Sq x Sk x d contraction
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  const bool use_dkv4 = !Qt && !key_bias && attn_dkv_impl() == 4;                // head_dim 128 / 96 / 64 (every head_dim built)
+  const AttnBwdRoute route = attn_bwd_route(d, Sk, Qt != nullptr, Kt != nullptr, key_bias != nullptr, O_res != nullptr, rq.out != nullptr, rk.out != nullptr);
+  const int dkv_kind = route.dkv / 10 * 10;
+  const bool use_dkv4 = dkv_kind == ST355_ATTN_ROUTE_DKV4 || dkv_kind == ST355_ATTN_ROUTE_DKV4_ROPE;
   {
     ProfScope ps(stream, ST355_K_ATTN_PREP, 2.0 * B * H * (double)S * d, 6.0 * B * H * (double)S * d);
     dim3 grid(Sp / 64, H, B);
@@ -1081,7 +1117,7 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
       else if (d == 96) ST355_DKV4_LAUNCH(96);
       else ST355_DKV4_LAUNCH(64);
 #undef ST355_DKV4_LAUNCH
-    } else if (!Qt) {
+    } else if (dkv_kind != ST355_ATTN_ROUTE_DKV2) {
       dim3 grid((Sk + 255) / 256, H, B);
       const int lds = 2 * (2 * 64 * 256 + 512);
 #define ST355_DKV3_LAUNCH(HD_)                                                                                                            \
@@ -1114,15 +1150,8 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
     }
     if ((rc = st355_check_launch("attn_bwd_dkv")) != 0) return rc;
   }
-  // the 64-row kernel takes the full 64-key tiles; a ragged key tail (SD3's S = 4096 + 231, every mixed-aspect bucket) is added by the general kernel restricted
-  // to the last tile (kt0 / accumulate above).  The fused-RoPE epilogue (head_dim 128, Flux: S % 64 == 0 always) writes projection rows, not dQ: no tail form.
-  const bool dq_tail = Sk % 64 != 0;
-  // a SHORT ragged key axis (the UNets' cross-attention: 77 text keys = one full tile + 13 keys) goes through the general kernel in ONE pass: as 64-row kernel + tail
-  // it was two memory-bound passes over Q / dO / dQ with a bf16 round trip of dQ between them (r6; ST355_ATTN_DQ_SHORT=0: A/B)
-  static int dq_short = -1;
-  if (dq_short < 0) { const char* e = getenv("ST355_ATTN_DQ_SHORT"); dq_short = (e && e[0] == '0') ? 0 : 1; }
-  const bool short_ragged = dq_short && dq_tail && Sk < 128;
-  if (!Kt && !key_bias && attn_dq_impl() == 64 && Sk >= 64 && !short_ragged && (!dq_tail || (rq.out == nullptr && dQ != nullptr))) {      // hand-scheduled 64-queries-per-wave kernel (k_attn_bwd_dq64)
+  const int dq_kind = route.dq / 10 * 10;
+  if (dq_kind == ST355_ATTN_ROUTE_DQ64 || dq_kind == ST355_ATTN_ROUTE_DQ64_ROPE) {      // hand-scheduled 64-queries-per-wave kernel (k_attn_bwd_dq64)
     ProfScope ps(stream, ST355_K_ATTN_BWD_DQ, 3.0 * fl_unit, 2.0 * (double)B * H * (S + Sk) * d * 3.0);
     dim3 grid((S + 255) / 256, H, B);
     const int lds = 3 * 2 * 64 * 256;
@@ -1138,7 +1167,7 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
     else ST355_DQ64_LAUNCH(64);
 #undef ST355_DQ64_LAUNCH
     if ((rc = st355_check_launch("attn_bwd_dq64")) != 0) return rc;
-    if (dq_tail) {
+    if (route.dq_tail) {      // (+ the last, ragged key tile through k_attn_bwd_dq, accumulating into dQ)
       const int lds_t = 2 * (64 * 256 + 64 * d * 2);
 #define ST355_DQT_LAUNCH(HD_)                                                                                                             \
   do {                                                                                                                                   \
@@ -1157,7 +1186,7 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
     ProfScope ps(stream, ST355_K_ATTN_BWD_DQ, 3.0 * fl_unit, 2.0 * (double)B * H * (S + Sk) * d * 3.0);
     dim3 grid((S + 255) / 256, H, B);
     const int ktb = 64 * d * 2;                                   // one row-major 64-key tile
-    const bool tr = !Kt;                                          // no K^T copy: transposing-read kernel (K tile image at a 256-byte row pitch)
+    const bool tr = dq_kind != ST355_ATTN_ROUTE_DQ && dq_kind != ST355_ATTN_ROUTE_DQ_BIAS;     // no K^T copy: transposing-read kernel (K tile image at a 256-byte row pitch)
     const int lds = 2 * ((tr ? 64 * 256 : ktb) + ktb + (tr ? 0 : d * 128));
 #define ST355_DQ_LAUNCH(KERN)                                                                                                            \
   do {                                                                                                                                   \
@@ -1220,4 +1249,22 @@ extern "C" int st355_attn_cross_bwd(void* stream, const void* Q, const void* K, 
                                     const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv, int B, int H, int Sq, int Sqp,
                                     int Sk, int Skp, int d, float scale, void* workspace) {
   return attn_bwd_impl(stream, Q, K, Qt, Kt, v_rows, ld_v, O, ld_o, dO, ld_do, lse2, key_bias, dQ, dK, dv_rows, ld_dv, B, H, Sq, Sqp, Sk, Skp, d, scale, workspace);
+}
+// st355.h: the routes of a forward + backward of this shape, from the decision functions the launchers call; launches nothing
+int attn_fwd_route(int d, int S, bool bias, bool vrow, bool res);     // attention.hip
+extern "C" int st355_attn_plan(int B, int H, int Sq, int Sk, int d, int flags, int32_t* routes) {
+  ST_REQUIRE(routes, "attn_plan: null routes");
+  ST_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0 && (flags & ~63) == 0, "attn_plan: bad arguments Sq=%d Sk=%d flags=%d", Sq, Sk, flags);
+  if (d != 128 && d != 64 && d != 96) { st355_set_error("attn_plan: head_dim %d not built", d); return ST355_ENOSYS; }
+  const bool bias = flags & ST355_ATTN_PLAN_BIAS, vrow = flags & ST355_ATTN_PLAN_VROWS, res = flags & ST355_ATTN_PLAN_RES;
+  const bool qt = flags & ST355_ATTN_PLAN_QT, kt = flags & ST355_ATTN_PLAN_KT, rope = flags & ST355_ATTN_PLAN_ROPE;
+  ST_REQUIRE(!vrow || (d == 128 && !res), "attn_plan: row-major V is built for head_dim 128 without O_res");
+  ST_REQUIRE(!rope || (d == 128 && Sq == Sk && !qt && !kt && !res), "attn_plan: the fused RoPE backward is self-attention at head_dim 128 without copies or O_res");
+  routes[0] = attn_fwd_route(d, Sk, bias, vrow, res);
+  const AttnBwdRoute r = attn_bwd_route(d, Sk, qt, kt, bias, res, rope, rope);
+  routes[1] = r.prep;
+  routes[2] = r.dkv;
+  routes[3] = r.dq;
+  routes[4] = r.dq_tail;
+  return ST355_OK;
 }

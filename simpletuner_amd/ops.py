@@ -472,6 +472,32 @@ def attn_set_impl(fwd: int = -1, dq: int = -1, dkv: int = -1):
     return prev // 65536, (prev // 256) % 256, prev % 256
 
 
+ATTN_ROUTE_KINDS = {10: "fwd64", 20: "fwd4", 30: "fwd4_bias", 40: "fwd4_res", 50: "fwd4_res_bias", 60: "fwd4_vrows", 70: "fwd4_vrows_bias",
+                    100: "prep", 110: "prep_res", 120: "prep_dot", 130: "prep_res_dot",
+                    200: "dkv4", 210: "dkv4_rope", 220: "dkv3", 230: "dkv3_rope", 240: "dkv2",
+                    300: "dq64", 310: "dq64_rope", 320: "dq_tr", 330: "dq_tr_bias", 340: "dq", 350: "dq_bias", 360: "dq_tr_rope",
+                    370: "dq_tr_bias_rope"}      # ST355_ATTN_ROUTE_* (st355.h) + 0 / 1 / 2 for head_dim 64 / 96 / 128
+ATTN_PLAN_FLAGS = {"key_bias": 1, "vrows": 2, "O_res": 4, "Qt": 8, "Kt": 16, "rope": 32}
+
+
+def attn_route_name(route: int) -> str:
+    kind, hd = route // 10 * 10, route % 10
+    return f"{ATTN_ROUTE_KINDS[kind]}<{(64, 96, 128)[hd]}>"
+
+
+def attn_plan(B, H, Sq, Sk, d, key_bias=False, vrows=False, O_res=False, Qt=False, Kt=False, rope=False):
+    """st355_attn_plan: the kernels a forward + backward of this shape would run on now, without launching anything.  The keyword arguments say what the calls
+    are given (truthy: present).  Returns {"fwd", "prep", "dkv", "dq": route names such as "dq64<128>", "dq_tail": bool}."""
+    flags = 0
+    for k, v in (("key_bias", key_bias), ("vrows", vrows), ("O_res", O_res), ("Qt", Qt), ("Kt", Kt), ("rope", rope)):
+        if v is not None and v is not False:
+            flags |= ATTN_PLAN_FLAGS[k]
+    routes = (C.c_int32 * 5)()
+    _l.check(_l.load().st355_attn_plan(int(B), int(H), int(Sq), int(Sk), int(d), flags, routes), "attn_plan")
+    return {"fwd": attn_route_name(routes[0]), "prep": attn_route_name(routes[1]), "dkv": attn_route_name(routes[2]), "dq": attn_route_name(routes[3]),
+            "dq_tail": bool(routes[4])}
+
+
 def gemm_grouped(problems):
     """run several independent GEMMs that share one epilogue kind in as few launches as possible.
     problems: list of dicts with keys a, w and the kwargs of gemm().  Returns the list of outputs."""
