@@ -714,6 +714,21 @@ int st355_layernorm_bwd(void* stream, const void* dy, int64_t lddy, const void* 
 size_t st355_layernorm_param_grads_workspace(int D);
 int st355_layernorm_param_grads(void* stream, const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t rows, int D, float eps, float* dweight,
                                 float* dbias, int accumulate, void* workspace);
+/* GroupNorm apply form for the calls that follow: 2 = row-walking passes (k_gn_apply_*_rows, the default), 1 = flat-index passes (k_gn_apply_fwd / _bwd);
+ * ST355_GN_APPLY=1 in the environment sets the initial form.  form 1 / 2: set; -1: back to the initial form; 0: unchanged.  Returns the previous form. */
+int st355_gn_set_apply(int form);
+/* The instance each normalisation / token-sum entry point would run for this shape, without launching anything (the launchers take the same decisions).
+ * dims / out by kind (out: 8 int32, unused entries 0):
+ *   LN         {D}                    -> {NC of k_ln_mod_fwd / k_ln_mod_bwd: 1,2,3,4,6,8}   (ln_modulate_*, layernorm_fwd / _bwd, layer_norm_xhat)
+ *   LN_PARAMS  {D}                    -> {NC of k_ln_param_partials: 1..4}                  (layernorm_param_grads)
+ *   LN_STATS   {D, rows_per_batch, gs}-> {NC of k_ln_mod_bwd_stats: 1,2,3,4,6, GS, 64-row chunks per batch element}   gs: a d_gate or d_bias output is given
+ *   COLS       {rows_per_batch}       -> {64-row chunks per batch element}                 (scale_cols_stats, colsum_rows)
+ *   GN         {B, H, W, C}           -> {apply form, chunks per image, grid rows per chunk, nwin, cw, RT of the row-walking passes}
+ *   QK         {d, B, H, S_part}      -> {head_dim, workgroups nblk, wgrad slices ns, partials per slice}
+ * Validates the shape as the launch would. */
+enum { ST355_NORM_PLAN_LN = 1, ST355_NORM_PLAN_LN_PARAMS = 2, ST355_NORM_PLAN_LN_STATS = 3, ST355_NORM_PLAN_COLS = 4, ST355_NORM_PLAN_GN = 5,
+       ST355_NORM_PLAN_QK = 6 };
+int st355_norm_plan(int kind, const int64_t* dims, int32_t* out);
 /* GEGLU (FeedForward activation_fn="geglu"): h = [value | gate] (row stride ldh), out = value * gelu_erf(gate) */
 int st355_geglu_fwd(void* stream, const void* h, int64_t ldh, void* out, int64_t M, int F);
 int st355_geglu_bwd(void* stream, const void* h, int64_t ldh, const void* dout, void* dh, int64_t lddh, int64_t M, int F);

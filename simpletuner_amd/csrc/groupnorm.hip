@@ -3,8 +3,10 @@
 //   UNet conv_norm_out + conv_act — the UNet the reference calls at sdxl/model.py:350-367, sd1x/model.py:224-270 (un-vendored diffusers).
 // HBM-bound: forward = stats pass (read x) + apply pass (read x, write y); backward = stats pass (read x, dy) + apply pass (read x, dy, write dx).
 // Deterministic: a thread owns a fixed 8-channel chunk and walks rows; row-lanes are combined through LDS in a fixed order; chunk partials are
-// combined by one wave per (image, group) in a fixed order.  Border positions hold zero, so statistics may sum over the whole padded image.
+// combined by one wave per (image, group) in a fixed order.  Border positions hold zero: the backward sums may run over the whole padded image; the forward
+// sums are shifted by a pivot and skip the border.
 #include "common.h"
+#include "norm_route.h"
 
 #define GN_THREADS 256
 #define GN_MAXC 2560           // largest channel count (SDXL up-block concat 1280+1280)
@@ -21,17 +23,40 @@ __device__ __forceinline__ int64_t token_of(int64_t pos, int H, int W) {
   return (b * H + yy - 1) * W + xx - 1;
 }
 
-// MODE 0: partial[b][chunk][c] = (sum x, sum x^2)       MODE 1: (sum g, sum g*xhat),  g = dy * (silu ? silu'(z) : 1), z = xhat*gamma + beta
+// first interior grid row at or after r (rows_img when there is none)
+__device__ __forceinline__ int gn_first_interior(int r, int H, int W) {
+  const int Wp = W + 2;
+  const int yy = r / Wp, xx = r - yy * Wp;
+  if (yy < 1) return Wp + 1;
+  if (yy > H) return (H + 2) * Wp;
+  if (xx < 1) return yy * Wp + 1;
+  if (xx > W) return yy + 1 <= H ? (yy + 1) * Wp + 1 : (H + 2) * Wp;
+  return r;
+}
+// interior positions among grid rows [0, r)
+__device__ __forceinline__ int gn_interior_before(int r, int H, int W) {
+  const int Wp = W + 2;
+  const int yy = r / Wp, xx = r - yy * Wp;
+  const int full = min(max(yy - 1, 0), H) * W;
+  return full + ((yy >= 1 && yy <= H) ? min(max(xx - 1, 0), W) : 0);
+}
+
+// MODE 0: partial[b][chunk][c] = (sum (x - p), sum (x - p)^2) over the chunk's interior positions, p = piv[b][chunk][c] = x at the chunk's first interior row
+//         (0 without one), and the chunk's interior count after the pivots: one pass, and the variance does not cancel at a large mean (sum x^2 / n - mean^2
+//         lost ~(mean/std)^2 2^-24 L relative)
+// MODE 1: (sum g, sum g*xhat),  g = dy * (silu ? silu'(z) : 1), z = xhat*gamma + beta
 template <int MODE>
 __global__ void __launch_bounds__(GN_THREADS) k_gn_stats(const bf16* __restrict__ x, const bf16* __restrict__ dy, const float* __restrict__ stats,
-                                                       const bf16* __restrict__ gamma, const bf16* __restrict__ beta, float* __restrict__ partial, int H, int W,
-                                                       int C, int rows_per_chunk, int nchunks, int silu, int dy_tokens) {
+                                                       const bf16* __restrict__ gamma, const bf16* __restrict__ beta, float* __restrict__ partial,
+                                                       float* __restrict__ piv, int H, int W, int C, int rows_per_chunk, int nchunks, int silu, int dy_tokens) {
   extern __shared__ float red[];                  // [RT][cw*8][2] for the current channel window
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int rows_img = (H + 2) * (W + 2);
   const int r0 = chunk * rows_per_chunk, r1 = min(rows_img, r0 + rows_per_chunk);
   const int c8 = C / 8;
   const int tid = threadIdx.x;
+  const int Wp = W + 2;
+  const int rp = MODE == 0 ? gn_first_interior(r0, H, W) : 0;
   for (int w0 = 0; w0 < c8; w0 += GN_THREADS) {          // channel windows of <= 256 chunks
     const int cw = min(c8 - w0, GN_THREADS);
     const int RT = GN_THREADS / cw;
@@ -41,6 +66,21 @@ __global__ void __launch_bounds__(GN_THREADS) k_gn_stats(const bf16* __restrict_
     for (int j = 0; j < 8; j++) { s0[j] = 0.f; s1[j] = 0.f; }
     if (rl < RT) {
       float mu[8], rs[8], ga[8], be[8];
+      if (MODE == 0) {
+        if (rp < r1) {
+          const bf16x8 pv = *(const bf16x8*)(x + ((int64_t)b * rows_img + rp) * C + ch * 8);
+#pragma unroll
+          for (int j = 0; j < 8; j++) mu[j] = bf2f(pv[j]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; j++) mu[j] = 0.f;
+        }
+        if (rl == 0) {
+#pragma unroll
+          for (int j = 0; j < 8; j++) piv[((int64_t)b * nchunks + chunk) * C + ch * 8 + j] = mu[j];
+        }
+        if (w0 == 0 && tid == 0) piv[(int64_t)gridDim.y * nchunks * C + (int64_t)b * nchunks + chunk] = (float)(gn_interior_before(r1, H, W) - gn_interior_before(r0, H, W));
+      }
       if (MODE == 1) {
         const bf16x8 gv = *(const bf16x8*)(gamma + ch * 8), bv = *(const bf16x8*)(beta + ch * 8);
 #pragma unroll
@@ -51,13 +91,19 @@ __global__ void __launch_bounds__(GN_THREADS) k_gn_stats(const bf16* __restrict_
       }
       // four rows per trip: all their requests leave before the first sum needs one (one request in flight per thread kept 12 KB per CU outstanding — the stats
       // passes ran at 2.0-3.5 TB/s, rocprofv3 r6); the sums are still taken row by row in the same order: bit-identical partials
+      int yy = (r0 + rl) / Wp, xx = r0 + rl - yy * Wp;       // MODE 0: grid position of row r + u * RT, advanced without a division
       for (int r = r0 + rl; r < r1; r += 4 * RT) {
         bf16x8 xv[4], dv[4];
-        bool ok[4];
+        bool ok[4], in[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int rr = r + u * RT;
           ok[u] = rr < r1;
+          if (MODE == 0) {
+            in[u] = yy >= 1 && yy <= H && xx >= 1 && xx <= W;
+            xx += RT;
+            while (xx >= Wp) { xx -= Wp; yy++; }
+          }
           const int64_t pos = (int64_t)b * rows_img + (ok[u] ? rr : r);
           xv[u] = *(const bf16x8*)(x + pos * C + ch * 8);
           if (MODE == 1) {
@@ -70,8 +116,9 @@ __global__ void __launch_bounds__(GN_THREADS) k_gn_stats(const bf16* __restrict_
         for (int u = 0; u < 4; u++) {
           if (!ok[u]) continue;
           if (MODE == 0) {
+            if (!in[u]) continue;                        // border rows hold zero: they are not x - p
 #pragma unroll
-            for (int j = 0; j < 8; j++) { const float v = bf2f(xv[u][j]); s0[j] += v; s1[j] += v * v; }
+            for (int j = 0; j < 8; j++) { const float v = bf2f(xv[u][j]) - mu[j]; s0[j] += v; s1[j] += v * v; }
           } else {
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -97,20 +144,29 @@ __global__ void __launch_bounds__(GN_THREADS) k_gn_stats(const bf16* __restrict_
   }
 }
 
-// one wave per (image, group): mean / rstd  ->  stats[b][c] = (mean_g, rstd_g) expanded per channel
-__global__ void __launch_bounds__(64) k_gn_finalize_fwd(const float* __restrict__ partial, float* __restrict__ stats, int C, int G, int nchunks, float count,
-                                                      float eps) {
+// one wave per (image, group): mean / rstd  ->  stats[b][c] = (mean_g, rstd_g) expanded per channel.  Partial k holds sums about its own pivot p_k over its
+// chunk's n_k interior positions (n_k after the B * nchunks * C pivots); about one reference pivot p0 of the group (its first channel's pivot in the chunk
+// holding the first interior row), with q_k = p_k - p0, in one fixed-order pass:
+//   A1 = sum_k n_k q_k + S1_k = sum (x - p0),   A2 = sum_k S2_k + 2 q_k S1_k + n_k q_k^2 = sum (x - p0)^2,   mean = p0 + A1 / n,   M2 = A2 - A1^2 / n
+// p0 is a value of the group, so |mean - p0| <= max |x - mean|: the subtraction cancels at most that spread, never (mean / std)^2
+__global__ void __launch_bounds__(64) k_gn_finalize_fwd(const float* __restrict__ partial, const float* __restrict__ piv, float* __restrict__ stats, int B, int C,
+                                                      int G, int nchunks, int rows_per_chunk, int W, float count, float eps) {
   const int g = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const int cg = C / G;
-  float s0 = 0.f, s1 = 0.f;
+  const float* cnt = piv + (int64_t)B * nchunks * C + (int64_t)b * nchunks;
+  const float p0 = piv[((int64_t)b * nchunks + (W + 3) / rows_per_chunk) * C + g * cg];
+  float a1 = 0.f, a2 = 0.f;
   for (int i = lane; i < nchunks * cg; i += 64) {
     const int chunk = i / cg, c = g * cg + i % cg;
-    const float* src = partial + (((int64_t)b * nchunks + chunk) * C + c) * 2;
-    s0 += src[0]; s1 += src[1];
+    const int64_t at = ((int64_t)b * nchunks + chunk) * C + c;
+    const float nk = cnt[chunk], q = piv[at] - p0, s1 = partial[at * 2];
+    a1 += nk * q + s1;
+    a2 += partial[at * 2 + 1] + 2.f * q * s1 + nk * q * q;
   }
-  s0 = wave_sum(s0); s1 = wave_sum(s1);
-  const float mean = s0 / count;
-  const float var = fmaxf(s1 / count - mean * mean, 0.f);
+  a1 = wave_sum(a1); a2 = wave_sum(a2);
+  const float d = a1 / count;
+  const float mean = p0 + d;
+  const float var = fmaxf(a2 / count - d * d, 0.f);
   const float rstd = rsqrtf(var + eps);
   for (int c = lane; c < cg; c += 64) { stats[((int64_t)b * C + g * cg + c) * 2] = mean; stats[((int64_t)b * C + g * cg + c) * 2 + 1] = rstd; }
 }
@@ -315,32 +371,26 @@ __global__ void __launch_bounds__(GN_THREADS) k_gn_apply_bwd_rows(const bf16* __
     while (xx >= Wp) { xx -= Wp; yy++; }
   }
 }
+// apply form: 2 = the row-walking passes (default), 1 = the flat-index passes; ST355_GN_APPLY=1 sets the initial form, st355_gn_set_apply changes it
+static int g_gn_apply = -1;
+static int gn_default_form() { const char* e = getenv("ST355_GN_APPLY"); return (e && e[0] == '1') ? 1 : 2; }
 static int gn_apply_form() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ST355_GN_APPLY"); v = (e && e[0] == '1') ? 1 : 2; }
-  return v;
+  if (g_gn_apply < 0) g_gn_apply = gn_default_form();
+  return g_gn_apply;
 }
-// launch geometry of the row-walking passes: channel windows of <= 256 chunks of equal width, RT rows per pass
-static void gn_rows_geom(int C, int* nwin, int* cw, int* RT) {
-  const int c8 = C / 8;
-  *nwin = (c8 + GN_THREADS - 1) / GN_THREADS;
-  *cw = (c8 + *nwin - 1) / *nwin;
-  *RT = GN_THREADS / *cw;
-  if (*RT < 1) *RT = 1;
+extern "C" int st355_gn_set_apply(int form) {
+  const int prev = gn_apply_form();
+  if (form == 1 || form == 2) g_gn_apply = form;
+  else if (form < 0) g_gn_apply = gn_default_form();
+  return prev;
 }
-
-static int gn_chunks(int B, int H, int W, int* rows_per_chunk) {
-  const int rows_img = (H + 2) * (W + 2);
-  int nch = (768 + B - 1) / B;
-  if (nch > (rows_img + 31) / 32) nch = (rows_img + 31) / 32;
-  if (nch < 1) nch = 1;
-  *rows_per_chunk = (rows_img + nch - 1) / nch;
-  return (rows_img + *rows_per_chunk - 1) / *rows_per_chunk;
-}
+static_assert(GN_THREADS == 256, "norm_route.h sizes the GroupNorm windows for 256 threads");
+static void gn_rows_geom(int C, int* nwin, int* cw, int* RT) { gn_route_rows_geom(C, nwin, cw, RT); }
+static int gn_chunks(int B, int H, int W, int* rows_per_chunk) { return gn_route_chunks(B, H, W, rows_per_chunk); }
 extern "C" size_t st355_groupnorm_workspace(int B, int H, int W, int C) {
   int rpc;
   const int nch = gn_chunks(B, H, W, &rpc);
-  return (size_t)B * nch * C * 2 * 4 + (size_t)B * C * 3 * 4 + 256;
+  return (size_t)B * nch * C * 2 * 4 + (size_t)B * C * 3 * 4 + (size_t)B * nch * (C + 1) * 4 + 256;      // partials, coefficients, pivots + interior counts
 }
 static size_t gn_lds(int C) { const int c8 = C / 8; const int cw = c8 < GN_THREADS ? c8 : GN_THREADS; return (size_t)(GN_THREADS / cw) * cw * 8 * 2 * 4; }
 
@@ -351,11 +401,12 @@ extern "C" int st355_groupnorm_fwd(void* stream, const void* x, const void* gamm
   int rpc;
   const int nch = gn_chunks(B, H, W, &rpc);
   float* partial = (float*)workspace;
+  float* piv = partial + (size_t)B * nch * C * 2 + (size_t)B * C * 3;
   ProfScope ps(stream, ST355_K_LN_MOD, 10.0 * B * H * W * C, 6.0 * B * (H + 2) * (W + 2) * C);
   hipLaunchKernelGGL(k_gn_stats<0>, dim3(nch, B), dim3(GN_THREADS), gn_lds(C), (hipStream_t)stream, (const bf16*)x, (const bf16*)nullptr, (const float*)nullptr,
-                     (const bf16*)nullptr, (const bf16*)nullptr, partial, H, W, C, rpc, nch, 0, 0);
-  hipLaunchKernelGGL(k_gn_finalize_fwd, dim3(groups, B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, stats, C, groups, nch,
-                     (float)((double)H * W * (C / groups)), eps);
+                     (const bf16*)nullptr, (const bf16*)nullptr, partial, piv, H, W, C, rpc, nch, 0, 0);
+  hipLaunchKernelGGL(k_gn_finalize_fwd, dim3(groups, B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, (const float*)piv, stats, B, C, groups, nch,
+                     rpc, W, (float)((double)H * W * (C / groups)), eps);
   if (gn_apply_form() == 2) {
     int nwin, cw, RT;
     gn_rows_geom(C, &nwin, &cw, &RT);
@@ -380,7 +431,7 @@ extern "C" int st355_groupnorm_bwd(void* stream, const void* dy, const void* x, 
   float* coef = partial + (size_t)B * nch * C * 2;
   ProfScope ps(stream, ST355_K_LN_MOD, 30.0 * B * H * W * C, 10.0 * B * (H + 2) * (W + 2) * C);
   hipLaunchKernelGGL(k_gn_stats<1>, dim3(nch, B), dim3(GN_THREADS), gn_lds(C), (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, stats, (const bf16*)gamma,
-                     (const bf16*)beta, partial, H, W, C, rpc, nch, silu, dy_tokens);
+                     (const bf16*)beta, partial, (float*)nullptr, H, W, C, rpc, nch, silu, dy_tokens);
   hipLaunchKernelGGL(k_gn_finalize_bwd, dim3(groups, B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, stats, (const bf16*)gamma, coef, C, groups, nch,
                      (float)((double)H * W * (C / groups)));
   if (dgamma && dbeta)

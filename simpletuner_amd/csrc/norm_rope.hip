@@ -4,6 +4,7 @@
 // Each kernel is one pass over HBM with 16-byte accesses; rows live in registers between the
 // statistics pass and the normalise pass (no re-read).
 #include "common.h"
+#include "norm_route.h"
 
 // ================================================================================================
 // K5: LayerNorm (no affine) + modulation. One wave per row, NC 16-byte chunks per lane.
@@ -70,12 +71,14 @@ static int ln_fwd_impl(void* stream, const void* x, int64_t ldx, const void* sca
 #define LAUNCH(NC)                                                                                                       \
   hipLaunchKernelGGL(k_ln_mod_fwd<NC>, grid, block, 0, (hipStream_t)stream, (const bf16*)x, ldx, (const bf16*)scale,       \
                      (const bf16*)shift, mod_stride, rows_per_batch, (bf16*)y, ldy, rows, D, eps, one)
-  if (D <= 512) LAUNCH(1);
-  else if (D <= 1024) LAUNCH(2);
-  else if (D <= 1536) LAUNCH(3);
-  else if (D <= 2048) LAUNCH(4);
-  else if (D <= 3072) LAUNCH(6);
-  else LAUNCH(8);
+  switch (ln_route_nc(D)) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 3: LAUNCH(3); break;
+    case 4: LAUNCH(4); break;
+    case 6: LAUNCH(6); break;
+    default: LAUNCH(8); break;
+  }
 #undef LAUNCH
   return st355_check_launch("ln_modulate_fwd");
 }
@@ -194,12 +197,14 @@ static int ln_bwd_impl(void* stream, const void* dy, int64_t lddy, const void* x
   hipLaunchKernelGGL(k_ln_mod_bwd<NC>, grid, block, 0, (hipStream_t)stream, (const bf16*)dy, lddy, (const bf16*)x, ldx,     \
                      (const bf16*)scale, mod_stride, rows_per_batch, (const bf16*)dres, lddres, (const bf16*)gate,          \
                      gate_stride, (bf16*)dx, lddx, (bf16*)dxg, lddxg, rows, D, eps, one)
-  if (D <= 512) LAUNCH(1);
-  else if (D <= 1024) LAUNCH(2);
-  else if (D <= 1536) LAUNCH(3);
-  else if (D <= 2048) LAUNCH(4);
-  else if (D <= 3072) LAUNCH(6);
-  else LAUNCH(8);
+  switch (ln_route_nc(D)) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 3: LAUNCH(3); break;
+    case 4: LAUNCH(4); break;
+    case 6: LAUNCH(6); break;
+    default: LAUNCH(8); break;
+  }
 #undef LAUNCH
   return st355_check_launch("ln_modulate_bwd");
 }
@@ -294,10 +299,12 @@ extern "C" int st355_layernorm_param_grads(void* stream, const void* dy, int64_t
   ST_REQUIRE(dy && x && dweight && dbias && workspace && rows > 0 && D % 8 == 0 && D <= 2048 && ldx % 8 == 0 && lddy % 8 == 0, "layernorm_param_grads: bad args");
   ProfScope ps(stream, ST355_K_LN_MOD, 8.0 * rows * D, 4.0 * rows * D);
 #define LAUNCH(NC) hipLaunchKernelGGL(k_ln_param_partials<NC>, dim3(LNP_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, lddy, (const bf16*)x, ldx, rows, D, eps, (float*)workspace)
-  if (D <= 512) LAUNCH(1);
-  else if (D <= 1024) LAUNCH(2);
-  else if (D <= 1536) LAUNCH(3);
-  else LAUNCH(4);
+  switch (lnp_route_nc(D)) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 3: LAUNCH(3); break;
+    default: LAUNCH(4); break;
+  }
 #undef LAUNCH
   hipLaunchKernelGGL(k_ln_param_reduce, dim3((D + 31) / 32), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, LNP_BLOCKS * 4, D, dweight, dbias, accumulate);
   return st355_check_launch("layernorm_param_grads");
@@ -596,7 +603,8 @@ extern "C" int st355_qk_norm_rope_bwd_wgrad(void* stream, const void* dQ, const 
   dim3 grid((S_part + 63) / 64, H, B), block(256);
   const int nblk = (int)(grid.x * grid.y * grid.z);
   // two-level fixed-order reduction of the nblk per-workgroup partials: <= 64 slices per weight, then the slices
-  const int ns = nblk < 64 * 32 ? (nblk + 31) / 32 : 64, per = (nblk + ns - 1) / ns;
+  int ns, per;
+  qk_wgrad_route_slices(nblk, &ns, &per);
   float* part2 = (float*)workspace + (size_t)2 * nblk * d;
   if (d == 128) {
     hipLaunchKernelGGL(k_qk_norm_rope_bwd<128>, grid, block, 0, (hipStream_t)stream, (const bf16*)dQ, (const bf16*)dK, (const bf16*)qkv, ld_qkv,
@@ -698,6 +706,60 @@ extern "C" int st355_qk_rope_norm_bwd(void* stream, const void* dQ, const void* 
   hipLaunchKernelGGL(k_qk_rope_norm_bwd_z<128>, grid, block, 0, (hipStream_t)stream, (const bf16*)dQ, (const bf16*)dK, (const bf16*)Q, (const bf16*)K,
                      rrms, (const bf16*)wq, (const bf16*)wk, cos, sin, (bf16*)dqkv, ld_dqkv, H, S_part, pos0, S);
   return st355_check_launch("qk_rope_norm_bwd");
+}
+
+// ---- route plan (st355.h): the instance each normalisation / token-sum entry point would run, from the helpers its launcher calls (norm_route.h) ----
+extern "C" int st355_gn_set_apply(int form);
+extern "C" int st355_norm_plan(int kind, const int64_t* dims, int32_t* out) {
+  ST_REQUIRE(dims && out, "norm_plan: null pointer");
+  for (int i = 0; i < 8; i++) out[i] = 0;
+  switch (kind) {
+    case ST355_NORM_PLAN_LN: {
+      const int64_t D = dims[0];
+      ST_REQUIRE(D > 0 && D % 8 == 0 && D <= 4096, "norm_plan: LayerNorm D=%lld", (long long)D);
+      out[0] = ln_route_nc((int)D);
+      return ST355_OK;
+    }
+    case ST355_NORM_PLAN_LN_PARAMS: {
+      const int64_t D = dims[0];
+      ST_REQUIRE(D > 0 && D % 8 == 0 && D <= 2048, "norm_plan: layernorm_param_grads D=%lld", (long long)D);
+      out[0] = lnp_route_nc((int)D);
+      return ST355_OK;
+    }
+    case ST355_NORM_PLAN_LN_STATS: {
+      const int64_t D = dims[0], rpb = dims[1];
+      ST_REQUIRE(D > 0 && D % 8 == 0 && D <= 3072 && rpb > 0, "norm_plan: ln_modulate_bwd_stats D=%lld", (long long)D);
+      out[0] = ln_stats_route_nc((int)D); out[1] = dims[2] ? 1 : 0; out[2] = stats_route_chunks(rpb);
+      return ST355_OK;
+    }
+    case ST355_NORM_PLAN_COLS: {
+      ST_REQUIRE(dims[0] > 0, "norm_plan: rows_per_batch");
+      out[0] = stats_route_chunks(dims[0]);
+      return ST355_OK;
+    }
+    case ST355_NORM_PLAN_GN: {
+      const int64_t B = dims[0], H = dims[1], W = dims[2], C = dims[3];
+      ST_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 2560, "norm_plan: GroupNorm C=%lld", (long long)C);
+      int rpc, nwin, cw, RT;
+      out[0] = st355_gn_set_apply(0);
+      out[1] = gn_route_chunks((int)B, (int)H, (int)W, &rpc);
+      out[2] = rpc;
+      gn_route_rows_geom((int)C, &nwin, &cw, &RT);
+      out[3] = nwin; out[4] = cw; out[5] = RT;
+      return ST355_OK;
+    }
+    case ST355_NORM_PLAN_QK: {
+      const int64_t d = dims[0], B = dims[1], H = dims[2], S_part = dims[3];
+      ST_REQUIRE((d == 64 || d == 128) && B > 0 && H > 0 && S_part > 0, "norm_plan: q/k norm head_dim %lld", (long long)d);
+      const int nblk = (int)(((S_part + 63) / 64) * H * B);
+      int ns, per;
+      qk_wgrad_route_slices(nblk, &ns, &per);
+      out[0] = (int)d; out[1] = nblk; out[2] = ns; out[3] = per;
+      return ST355_OK;
+    }
+  }
+  ST_REQUIRE(false, "norm_plan: unknown kind %d", kind);
+  return ST355_EINVAL;
 }
 
 // ================================================================================================

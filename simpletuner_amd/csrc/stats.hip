@@ -9,8 +9,10 @@
 // A workgroup owns 64 consecutive rows of ONE batch element: waves accumulate in registers (a lane owns the same columns for every row), meet through LDS in a fixed
 // order and leave one fp32 partial row per sum; k_stats_finalize adds the partial rows in index order — deterministic, no atomics.
 #include "common.h"
+#include "norm_route.h"
 
 #define SR_ROWS 64
+static_assert(SR_ROWS == 64, "norm_route.h counts 64-row chunks");
 
 struct StatOutD {
   float* f32; bf16* b16;
@@ -60,7 +62,7 @@ static int finalize(void* stream, const float* ws, int nchunks, int nb, int NS, 
 extern "C" size_t st355_stats_workspace(int64_t rows, int N, int64_t rows_per_batch, int nsums) {
   if (rows <= 0 || rows_per_batch <= 0 || N <= 0 || nsums <= 0) return 0;
   const int64_t nb = rows / rows_per_batch;
-  return (size_t)nb * (size_t)cdiv64(rows_per_batch, SR_ROWS) * (size_t)nsums * (size_t)N * sizeof(float);
+  return (size_t)nb * (size_t)stats_route_chunks(rows_per_batch) * (size_t)nsums * (size_t)N * sizeof(float);
 }
 
 // ================================================================================================
@@ -245,7 +247,7 @@ extern "C" int st355_ln_modulate_bwd_stats(void* stream, const void* dy, int64_t
   const bool gs = (d_gate && d_gate->out) || (d_bias && d_bias->out);
   if (d_gate && d_gate->out) ST_REQUIRE(y_branch && ld_y % 8 == 0, "ln_modulate_bwd_stats: the gate gradient needs the branch output");
   if (d_bias && d_bias->out) ST_REQUIRE(dxg, "ln_modulate_bwd_stats: the bias gradient is the column sum of the gated output");
-  const int nb = (int)(rows / rows_per_batch), nchunks = (int)cdiv64(rows_per_batch, SR_ROWS);
+  const int nb = (int)(rows / rows_per_batch), nchunks = stats_route_chunks(rows_per_batch);
   const int NS = gs ? 4 : 2;
   {
     ProfScope ps(stream, ST355_K_LN_MOD, (16.0 + 2.0 * NS) * rows * D, (6.0 + (dres ? 2.0 : 0.0) + (dxg ? 2.0 : 0.0) + ((gs && y_branch) ? 2.0 : 0.0)) * rows * D);
@@ -256,11 +258,13 @@ extern "C" int st355_ln_modulate_bwd_stats(void* stream, const void* dy, int64_t
                      (const bf16*)((d_gate && d_gate->out) ? y_branch : nullptr), ld_y, D, eps, 1.f, (float*)workspace, nchunks)
 #define PICK(GS_)                        \
   do {                                   \
-    if (D <= 512) LAUNCH(1, GS_);        \
-    else if (D <= 1024) LAUNCH(2, GS_);  \
-    else if (D <= 1536) LAUNCH(3, GS_);  \
-    else if (D <= 2048) LAUNCH(4, GS_);  \
-    else LAUNCH(6, GS_);                 \
+    switch (ln_stats_route_nc(D)) {      \
+      case 1: LAUNCH(1, GS_); break;     \
+      case 2: LAUNCH(2, GS_); break;     \
+      case 3: LAUNCH(3, GS_); break;     \
+      case 4: LAUNCH(4, GS_); break;     \
+      default: LAUNCH(6, GS_); break;    \
+    }                                    \
   } while (0)
     if (gs) PICK(true); else PICK(false);
 #undef PICK
@@ -334,7 +338,7 @@ extern "C" int st355_scale_cols_stats(void* stream, const void* in, int64_t ld_i
                  M % rows_per_batch == 0, "scale_cols_stats: bad args");
   const bool want_gate = d_gate && d_gate->out;
   if (want_gate) ST_REQUIRE(y_branch && ld_y % 8 == 0, "scale_cols_stats: the gate gradient needs the branch output");
-  const int nb = (int)(M / rows_per_batch), nchunks = (int)cdiv64(rows_per_batch, SR_ROWS);
+  const int nb = (int)(M / rows_per_batch), nchunks = stats_route_chunks(rows_per_batch);
   {
     ProfScope ps(stream, ST355_K_ELEMENTWISE, 3.0 * M * N, (4.0 + (want_gate ? 2.0 : 0.0)) * M * N);
     hipLaunchKernelGGL(k_cols_stats, dim3((N + 511) / 512, nchunks, nb), dim3(256), 0, (hipStream_t)stream, (const bf16*)in, ld_in, (const bf16*)gate, gate_stride,
@@ -354,7 +358,7 @@ extern "C" int st355_colsum_rows(void* stream, const void* a, int64_t lda, int64
                                  const st355_stat_out* out, void* workspace) {
   ST_REQUIRE(a && out && out->out && workspace && N % 8 == 0 && lda % 8 == 0 && rows_per_batch > 0 && batch_stride_rows >= rows_per_batch && nb > 0 &&
                  ((uintptr_t)a % 16 == 0), "colsum_rows: bad args");
-  const int nchunks = (int)cdiv64(rows_per_batch, SR_ROWS);
+  const int nchunks = stats_route_chunks(rows_per_batch);
   {
     ProfScope ps(stream, ST355_K_ELEMENTWISE, 1.0 * nb * rows_per_batch * N, 2.0 * nb * rows_per_batch * N);
     hipLaunchKernelGGL(k_cols_stats, dim3((N + 511) / 512, nchunks, nb), dim3(256), 0, (hipStream_t)stream, (const bf16*)a, lda, (const bf16*)nullptr, 0,

@@ -1385,6 +1385,27 @@ def _gn_workspace(B, H, W, Cn, device):
     return ws
 
 
+def gn_set_apply(form: int) -> int:
+    """st355_gn_set_apply: GroupNorm apply form for the calls that follow, 2 = row-walking passes (default), 1 = flat-index passes, -1 = the initial form
+    (ST355_GN_APPLY), 0 = unchanged; returns the previous form"""
+    return int(_l.load().st355_gn_set_apply(int(form)))
+
+
+NORM_PLAN_KINDS = {"ln": 1, "ln_params": 2, "ln_stats": 3, "cols": 4, "gn": 5, "qk": 6}      # ST355_NORM_PLAN_* (st355.h)
+
+
+def norm_plan(kind: str, *dims):
+    """st355_norm_plan: the instance a normalisation / token-sum entry point would run for this shape, without launching anything.
+    ln (D) -> {"nc"}; ln_params (D) -> {"nc"}; ln_stats (D, rows_per_batch, gs) -> {"nc", "gs", "chunks"}; cols (rows_per_batch) -> {"chunks"};
+    gn (B, H, W, C) -> {"form", "nch", "rows_per_chunk", "nwin", "cw", "RT"}; qk (d, B, H, S_part) -> {"hd", "nblk", "ns", "per"}"""
+    keys = {"ln": ("nc",), "ln_params": ("nc",), "ln_stats": ("nc", "gs", "chunks"), "cols": ("chunks",),
+            "gn": ("form", "nch", "rows_per_chunk", "nwin", "cw", "RT"), "qk": ("hd", "nblk", "ns", "per")}[kind]
+    d = (C.c_int64 * 8)(*[int(v) for v in dims])
+    out = (C.c_int32 * 8)()
+    _l.check(_l.load().st355_norm_plan(NORM_PLAN_KINDS[kind], d, out), "norm_plan")
+    return {k: int(out[i]) for i, k in enumerate(keys)}
+
+
 def groupnorm_fwd(x, gamma, beta, B: int, H: int, W: int, groups: int = 32, eps: float = 1e-5, silu: bool = True, out_tokens: bool = False):
     """returns (y, stats).  y: grid [.., C] or dense tokens [B*H*W, C]; stats [B,C,2] fp32 for the backward"""
     L = _l.load()
