@@ -432,6 +432,26 @@ int st355_grad_clamp(void* stream, void* g, int64_t n, int elem_bytes, float c);
  * + 1e-6)) in place, stats2 = the two floats st355_grad_norm wrote; pre_scale = 1/world when g still holds rank sums.  No host sync. */
 int st355_grad_clip_norm(void* stream, void* g, int64_t n, int elem_bytes, const float* stats2, float max_norm, float pre_scale);
 
+/* ---- Muon (MuonClip, optimizers/muon/__init__.py) over an fp32 arena of 2-D matrices, short side <= 128 ----
+ * st355_muon_plan (host only): matrix i is [rows[i], cols[i]] row-major at element offsets[i] of the arena (ascending, non-overlapping).
+ * Fills plan (ST355_MUON_PLAN_HEADER + n * ST355_MUON_PLAN_RECORD int64) and the workspace size in floats.  The caller copies the plan to
+ * the device once and allocates the workspace once; both entries below then launch 2 + 3 * ns_steps kernels per short-side class present
+ * (short side rounded up to 32: at most 4 classes) whatever n is, with no
+ * host sync and no allocation, and reduce in a fixed order (bit-identical results run to run).
+ * coeffs: 3 * ns_steps host floats (a_i, b_i, c_i): X <- a_i X + (b_i A + c_i A A) X, A = X X^T, X = the matrix or its transpose
+ * (rows > cols) so that X is short x long. */
+#define ST355_MUON_PLAN_HEADER 8
+#define ST355_MUON_PLAN_RECORD 16
+int st355_muon_plan(const int64_t* offsets, const int32_t* rows, const int32_t* cols, int n, int64_t* plan, int64_t* ws_floats);
+/* one Muon step: m <- m + (1-momentum)(grad_scale g - m); X = m (or m^T) / max(||m||_F, eps); ns_steps iterations;
+ * O = X (or X^T) * sqrt(max(rows, cols)) * rms_scale_factor; p <- p + (-lr weight_decay) p; p <- p + (-lr) O.  p, g, m fp32 arenas. */
+int st355_muon_step(void* stream, const int64_t* plan_host, const int64_t* plan_dev, float* p, const float* g, float* m, float* ws,
+                    int64_t ws_floats, float grad_scale, double momentum, double lr, double weight_decay, double eps,
+                    double rms_scale_factor, int ns_steps, const float* coeffs);
+/* the bare orthogonalisation: out = NS(x) per matrix (same layout as x), x first divided by max(||x||_F, eps) if normalize */
+int st355_muon_orthogonalize(void* stream, const int64_t* plan_host, const int64_t* plan_dev, const float* x, float* out, float* ws,
+                             int64_t ws_floats, int normalize, double eps, int ns_steps, const float* coeffs);
+
 /* LoRA operand packing (K12): from fp32 A[r,K], B[N,r] write the bf16 GEMM operands of ONE adapter into the (zero-initialised)
  * block-structured operands of a fused projection group with K2 padded low-rank columns and N_total outputs:
  *   A_cat   [K2,K]       rows  k2_off..k2_off+r-1      = A

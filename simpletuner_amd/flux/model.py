@@ -50,6 +50,7 @@ class Flux(ModelFoundation):
     VAE_CONFIG = dict(latent_channels=16, scaling_factor=0.3611, shift_factor=0.1159, use_quant_conv=False)
     DEFAULT_MODEL_FLAVOUR = "dev"
     DEFAULT_LORA_TARGET = ["to_k", "to_q", "to_v", "to_out.0"]
+    SUPPORTS_MUON_CLIP = True                                        # flux/model.py:50
 
     def convert_text_embed_for_pipeline(self, text_embedding: dict) -> dict:
         """flux/model.py:453-472: prompt / pooled embeddings (+ the text mask as `prompt_mask` only under flux_attention_masked_training)"""

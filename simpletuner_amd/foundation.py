@@ -478,8 +478,15 @@ class ModelFoundation(ExplorativeModelingMixin):
         """common.py:1452.  GLIGEN grounding layers are out of the hot path: never advertised"""
         return False
 
+    SUPPORTS_MUON_CLIP = False          # models/common.py: families opt in (the reference sets it on Flux only among the families built here)
+
     def enable_muon_clip_logging(self):
-        raise NotImplementedError("optimizer 'muon' is not built on the st355 path")
+        """Flux publishes per-head max logits keyed by the base layer's `attn.to_q.weight` name (flux/transformer.py:192, training/qk_clip_logging.py).
+        Under LoRA none of them names a trained parameter, so St355Muon's QK-clip never acts and nothing has to be collected: a no-op for the
+        families that support Muon; the rest never reach it (the trainer refuses 'muon' for them first)"""
+        if not self.SUPPORTS_MUON_CLIP:
+            raise NotImplementedError(f"optimizer 'muon' is not supported by {type(self).__name__} on the st355 path")
+        return None
 
     def configure_assistant_lora_for_training(self):
         if getattr(self.config, "assistant_lora_path", None) not in (None, "", "None"):

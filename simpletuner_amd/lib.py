@@ -25,6 +25,7 @@ SYMBOLS = [
     "st355_qk_norm_rope_fwd", "st355_qk_norm_rope_bwd", "st355_qk_norm_wgrad_workspace", "st355_qk_norm_rope_bwd_wgrad", "st355_qk_rope_norm_bwd",
     "st355_attn_set_impl", "st355_attn_plan", "st355_attn_fwd", "st355_attn_fwd_vrows", "st355_attn_bwd_workspace", "st355_attn_bwd", "st355_attn_bwd_rope",
     "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
+    "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
     "st355_lora_pack",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
@@ -338,6 +339,9 @@ def _declare(lib):
         "st355_grad_norm_ws": (C.c_int, [vp, vp, i64, i32, vp, vp]),
         "st355_grad_clamp": (C.c_int, [vp, vp, i64, i32, f32]),
         "st355_grad_clip_norm": (C.c_int, [vp, vp, i64, i32, vp, f32, f32]),
+        "st355_muon_plan": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+        "st355_muon_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]),
+        "st355_muon_orthogonalize": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, C.c_double, i32, vp]),
         "st355_lora_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),

@@ -1001,6 +1001,70 @@ def grad_clip_norm_(g, stats, max_norm: float, pre_scale: float = 1.0):
     return g
 
 
+class MuonPlan:
+    """st355_muon_plan for a fixed list of matrices of one fp32 arena (element offsets, shapes): the host plan, its device copy and the
+    workspace, all made once here — the step itself then allocates nothing and never syncs"""
+
+    HEADER, RECORD = 8, 16
+
+    def __init__(self, offsets, shapes, device):
+        n = len(shapes)
+        if n == 0 or len(offsets) != n:
+            raise _l.St355Error("muon_plan: expected one offset per matrix shape")
+        L = _l.load()
+        off = (C.c_int64 * n)(*[int(o) for o in offsets])
+        rows = (C.c_int32 * n)(*[int(s[0]) for s in shapes])
+        cols = (C.c_int32 * n)(*[int(s[1]) for s in shapes])
+        self.host = torch.zeros(self.HEADER + self.RECORD * n, dtype=torch.int64)
+        ws = C.c_int64(0)
+        _l.check(L.st355_muon_plan(off, rows, cols, n, _ptr(self.host), C.byref(ws)), "muon_plan")
+        self.n = n
+        self.ws_floats = int(ws.value)
+        self.dev = self.host.to(device)
+        self.ws = torch.empty(self.ws_floats, dtype=F32, device=device)
+
+    def launches(self, ns_steps: int) -> int:
+        """kernel launches of one call: prep + norm + (gram, poly, update) per iteration and per short-side class present"""
+        rp = self.host[self.HEADER:].view(self.n, self.RECORD)[:, 5]
+        return 2 + 3 * ns_steps * len(set(rp.tolist()))
+
+
+def _coeffs(coeffs):
+    flat = [float(v) for abc in coeffs for v in abc]
+    if not flat or len(flat) % 3:
+        raise _l.St355Error("muon: coefficients must be a list of (a, b, c) triples, one per iteration")
+    return (C.c_float * len(flat))(*flat), len(flat) // 3
+
+
+def muon_step(plan: MuonPlan, p, g, m, coeffs, lr: float, momentum: float = 0.95, weight_decay: float = 0.1, eps: float = 1e-7,
+              rms_scale_factor: float = 0.2, grad_scale: float = 1.0):
+    """one Muon step over the arena (p, g, m: fp32 flat, plan offsets into them): momentum, Newton-Schulz with one (a, b, c) per iteration,
+    scale, decoupled decay, apply — in place on p and m"""
+    L = _l.load()
+    for t, nm in ((p, "p"), (g, "g"), (m, "m")):
+        _chk(t, F32, nm)
+        if not t.is_contiguous() or t.numel() != p.numel():
+            raise _l.St355Error(f"muon_step: {nm} must be a contiguous fp32 arena of {p.numel()} elements")
+    cf, ns = _coeffs(coeffs)
+    _l.check(L.st355_muon_step(_stream(), _ptr(plan.host), _ptr(plan.dev), _ptr(p), _ptr(g), _ptr(m), _ptr(plan.ws), plan.ws_floats,
+                               float(grad_scale), float(momentum), float(lr), float(weight_decay), float(eps), float(rms_scale_factor), ns, cf),
+             "muon_step")
+
+
+def muon_orthogonalize(plan: MuonPlan, x, coeffs, normalize: bool = True, eps: float = 1e-7, out=None):
+    """the bare orthogonalisation of every matrix of the arena x (fp32 flat): out = NS(x) (x / max(||x||_F, eps) first if normalize)"""
+    L = _l.load()
+    _chk(x, F32, "x")
+    if not x.is_contiguous():
+        raise _l.St355Error("muon_orthogonalize: x must be contiguous")
+    out = torch.zeros_like(x) if out is None else out
+    _chk(out, F32, "out")
+    cf, ns = _coeffs(coeffs)
+    _l.check(L.st355_muon_orthogonalize(_stream(), _ptr(plan.host), _ptr(plan.dev), _ptr(x), _ptr(out), _ptr(plan.ws), plan.ws_floats,
+                                        int(bool(normalize)), float(eps), ns, cf), "muon_orthogonalize")
+    return out
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

@@ -8,7 +8,8 @@ torch.optim.Optimizer API so `accelerator.prepare(optimizer)` / `accelerator.sav
 """
 from __future__ import annotations
 
-from typing import Optional
+import math
+from typing import Callable, Dict, Optional
 
 import torch
 
@@ -289,4 +290,223 @@ OPTIMIZER_CHOICE = {
         "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-6},
         "class": St355AdamWBF16,
     },
+}
+
+
+# ---- Muon ------------------------------------------------------------------------------------------------------------------------
+MUON_NS_COEFFICIENTS = (3.4445, -4.7750, 2.0315)     # muon/__init__.py:16-19 (DEFAULT_A, DEFAULT_B, DEFAULT_C)
+MUON_NS_STEPS = 5
+MUON_EPS = 1e-7
+MUON_MAX_SHORT_SIDE = 128
+
+
+def muon_cans_coefficients(ns_steps: int, cans_a_bound: float):
+    """the CANS schedule of muon/__init__.py:45-78 in float64 on the host: iteration i is X <- c1 X + c3 (X X^T) X, i.e. (a, b, c) = (c1, c3, 0)"""
+    lower, upper, inv_3 = float(cans_a_bound), 1.0, 1.0 / 3.0
+    out = []
+    for _ in range(ns_steps):
+        a_sq, b_sq, ab = lower * lower, upper * upper, lower * upper
+        e_sq = (a_sq + ab + b_sq) * inv_3
+        e_pow_1_5 = e_sq * math.sqrt(e_sq)
+        common_den_part = 2.0 * e_pow_1_5
+        ab_part = a_sq * upper + b_sq * lower
+        alpha_den = common_den_part + ab_part
+        alpha = 6.0 / alpha_den
+        out.append((alpha * e_sq, -alpha * inv_3, 0.0))
+        eps_val = (common_den_part - ab_part) / alpha_den
+        lower, upper = 1.0 - eps_val, 1.0 + eps_val
+    return out
+
+
+def muon_coefficients(group: dict):
+    """one (a, b, c) per Newton-Schulz iteration for a parameter group's settings"""
+    if group["use_cans"]:
+        return muon_cans_coefficients(group["ns_steps"], group["cans_a_bound"])
+    return [tuple(float(v) for v in group["ns_coefficients"])] * group["ns_steps"]
+
+
+class St355Muon(torch.optim.Optimizer):
+    """MuonClip (optimizers/muon/__init__.py) over the fp32 adapter arena, as one st355_muon_step call per parameter group.
+
+    Same constructor (every keyword of MuonClip), same `step(closure=None, attention_max_logits=None)`, same per-parameter state keys
+    (`momentum_buffer`, `factored=False`; the buffers are views of one flat fp32 arena), same `register_attention_params[_from_model]` and
+    `state_dict()["param_names"]`.  The arithmetic is the reference's intent, not its literal output: the Newton-Schulz
+    iterate is never written over its own input and the momentum buffer keeps m.  Parameters must be 2-D fp32 views of one contiguous arena
+    with a short side of at most 128 (the LoRA adapter arena); `stochastic_rounding` is accepted and, as for the reference's non-bf16
+    parameters, has no effect.  `use_smmf` and `vector_reshape` are refused."""
+
+    def __init__(self, params, lr: float = 2e-4, momentum: float = 0.95, weight_decay: float = 0.1, qk_clip_threshold: float = 100.0,
+                 qk_clip_alpha: float = 0.5, ns_steps: int = MUON_NS_STEPS, ns_coefficients=MUON_NS_COEFFICIENTS, eps: float = MUON_EPS,
+                 rms_scale_factor: float = 0.2, use_smmf: bool = False, vector_reshape: bool = False, stochastic_rounding: bool = True,
+                 use_cans: bool = False, cans_a_bound: float = 1e-4):
+        if lr < 0.0:                                               # muon/__init__.py:171-180, same texts
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0 or momentum >= 1.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if ns_steps >= 100:
+            raise ValueError("Number of steps must be less than 100 for computational efficiency")
+        if not use_cans and len(ns_coefficients) != 3:
+            raise ValueError("ns_coefficients must be a tuple of exactly 3 values")
+        if use_smmf:
+            raise NotImplementedError("muon: use_smmf (the factored momentum) is not built on the st355 path")
+        if vector_reshape:
+            raise NotImplementedError("muon: vector_reshape (factored 1-D momentum) is not built on the st355 path")
+        if ns_steps < 1:
+            raise NotImplementedError("muon: ns_steps must be at least 1 on the st355 path")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, qk_clip_threshold=qk_clip_threshold, qk_clip_alpha=qk_clip_alpha,
+                        ns_steps=ns_steps, ns_coefficients=ns_coefficients, eps=eps, rms_scale_factor=rms_scale_factor, use_smmf=use_smmf,
+                        vector_reshape=vector_reshape, use_cans=use_cans, cans_a_bound=cans_a_bound)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            ps = group["params"]
+            for i, p in enumerate(ps):
+                if p.dim() != 2:
+                    raise NotImplementedError(f"muon: parameter {i} has {p.dim()} dimensions; only 2-D matrices are built on the st355 path")
+                if min(p.shape) > MUON_MAX_SHORT_SIDE:
+                    raise NotImplementedError(f"muon: parameter {i} of shape {tuple(p.shape)} has a short side above {MUON_MAX_SHORT_SIDE}")
+                if p.dtype != F32:
+                    raise NotImplementedError(f"muon: parameter {i} is {p.dtype}; the st355 path steps fp32 adapter values")
+            if not _contiguous_run([p.data for p in ps]):
+                raise NotImplementedError("muon: the parameters of a group must be one contiguous fp32 run (the adapter arena)")
+        self.stochastic_rounding = stochastic_rounding
+        self._param_to_name: Dict[int, str] = {}
+        self.grad_scale = 1.0           # set by the gradient-sync layer (1/world_size) or by clipping: folded into the momentum update
+        self.abi_calls = 0              # st355 calls issued by step(): one per parameter group, whatever the number of matrices
+        self._flat = {}
+
+    def _group_flat(self, gi, group):
+        st = self._flat.get(gi)
+        if st is None:
+            ps = list(group["params"])
+            base = ps[0].data_ptr()
+            n = sum(p.numel() for p in ps)
+            plan = ops.MuonPlan([(p.data_ptr() - base) // 4 for p in ps], [tuple(p.shape) for p in ps], ps[0].device)
+            st = dict(ps=ps, n=n, plan=plan, m=torch.zeros(n, dtype=F32, device=ps[0].device))
+            off = 0
+            for p in ps:   # MuonClip's per-parameter state (:243-244) = views of the flat momentum
+                self.state[p] = dict(momentum_buffer=st["m"][off:off + p.numel()].view_as(p), factored=False)
+                off += p.numel()
+            self._flat[gi] = st
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None, attention_max_logits: Optional[Dict[str, torch.Tensor]] = None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if attention_max_logits is not None:
+            self._check_qk_clip(attention_max_logits)
+        for gi, group in enumerate(self.param_groups):
+            if all(p.grad is None for p in group["params"]):
+                continue
+            st = self._group_flat(gi, group)
+            grads = [p.grad for p in st["ps"]]
+            if any(g is None for g in grads) or not _contiguous_run(grads):
+                raise RuntimeError("St355Muon expects the gradients of every parameter of a group as one flat fp32 arena (fused step)")
+            pflat = torch.as_strided(st["ps"][0].data, (st["n"],), (1,))
+            gflat = torch.as_strided(grads[0], (st["n"],), (1,))
+            ops.muon_step(st["plan"], pflat, gflat, st["m"], muon_coefficients(group), group["lr"], momentum=group["momentum"],
+                          weight_decay=group["weight_decay"], eps=group["eps"], rms_scale_factor=group["rms_scale_factor"],
+                          grad_scale=self.grad_scale)
+            self.abi_calls += 1
+        return loss
+
+    def _check_qk_clip(self, attention_max_logits: Dict[str, torch.Tensor]) -> None:
+        """MuonClip._apply_qk_clip (:347-378) matches parameters to the published max logits by name and skips the rest.  Under LoRA no trained
+        parameter's name is ever published (the logits are keyed by the base layer's weight), so the clip never runs; a match would mean a
+        clip this path does not implement, and is refused rather than skipped"""
+        for group in self.param_groups:
+            for p in group["params"]:
+                name = self._get_param_name(p)
+                if name and name in attention_max_logits:
+                    raise NotImplementedError(f"muon: QK-clip of trained parameter '{name}' is not built on the st355 path")
+
+    def _get_param_name(self, param: torch.Tensor) -> str:
+        return self._param_to_name.get(id(param), "")
+
+    def register_attention_params(self, param_name_mapping: Dict[str, torch.nn.Parameter]) -> None:
+        self._param_to_name.update({id(param): name for name, param in param_name_mapping.items()})
+
+    def register_attention_params_from_model(self, model: torch.nn.Module, name_filter: Optional[Callable[[str], bool]] = None) -> None:
+        if model is None:
+            return
+        if name_filter is None:
+            name_filter = lambda n: ("attn" in n.lower() or "attention" in n.lower()) and ("q" in n.lower() or "k" in n.lower())  # noqa: E731
+        mapping = {name: param for name, param in model.named_parameters() if param is not None and name_filter(name)}
+        if mapping:
+            self.register_attention_params(mapping)
+
+    def state_dict(self) -> Dict[str, object]:
+        base = super().state_dict()
+        base["param_names"] = {gi: [self._param_to_name.get(id(p), "") for p in group.get("params", [])] for gi, group in enumerate(self.param_groups)}
+        return base
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: dict) -> None:
+        """resume: the saved momentum buffers are copied INTO the flat fp32 arena (created here if the optimizer has not stepped yet); the
+        saved parameter names are registered again (MuonClip.load_state_dict)"""
+        state_dict = dict(state_dict)
+        param_names = state_dict.pop("param_names", None)
+        saved = _unpack_saved_state(self, state_dict)
+        self._flat = {}
+        for p in list(self.state):
+            del self.state[p]
+        for gi, group in enumerate(self.param_groups):
+            st = self._group_flat(gi, group)
+            for p in st["ps"]:
+                old = saved.get(p)
+                if old is not None and "momentum_buffer" in old:
+                    self.state[p]["momentum_buffer"].copy_(old["momentum_buffer"].to(device=p.device, dtype=F32).view_as(p))
+        if param_names:
+            for gi, names in param_names.items():
+                gi = int(gi)
+                if gi >= len(self.param_groups):
+                    continue
+                for p, name in zip(self.param_groups[gi].get("params", []), names):
+                    if name:
+                        self._param_to_name[id(p)] = name
+
+
+def parse_optimizer_config(config) -> dict:
+    """convert_arg_to_parameters (optimizer_param.py:885-909): `--optimizer_config=k=v,k=v` by the reference's rules, plus the generic beta pair"""
+    out = {}
+    text = getattr(config, "optimizer_config", None)
+    if text is not None and text:
+        for param in [kv.split("=") for kv in text.split(",")]:
+            if "." in param[1]:
+                out[param[0]] = float(param[1])
+            elif str(param[1]).isdigit():
+                out[param[0]] = int(param[1])
+            elif param[1].lower() == "true":
+                out[param[0]] = True
+            elif param[1].lower() == "false":
+                out[param[0]] = False
+            elif param[1].lower() == "none":
+                out[param[0]] = None
+            elif "e-" in param[1]:
+                out[param[0]] = float(param[1])
+            else:
+                out[param[0]] = param[1]
+    if getattr(config, "optimizer_beta1", None) is not None and getattr(config, "optimizer_beta2", None) is not None:
+        out["betas"] = tuple([config.optimizer_beta1, config.optimizer_beta2])
+    return out
+
+
+def optimizer_settings(name: str, config) -> dict:
+    """optimizer_parameters (optimizer_param.py): the registry's default settings updated by the parsed optimizer_config"""
+    import copy
+    settings = copy.deepcopy(OPTIMIZER_CHOICE[name].get("default_settings", {}))
+    settings.update(parse_optimizer_config(config))
+    return settings
+
+
+# the reference's own "muon" entry (optimizer_param.py:432-447), with the fused class substituted
+OPTIMIZER_CHOICE["muon"] = {
+    "precision": "any",
+    "default_settings": {"momentum": 0.95, "weight_decay": 0.1, "eps": 1e-7, "rms_scale_factor": 0.2, "use_smmf": False, "vector_reshape": False,
+                         "stochastic_rounding": True, "use_cans": False, "cans_a_bound": 1e-4, "qk_clip_threshold": 100.0, "qk_clip_alpha": 0.5},
+    "class": St355Muon,
 }

@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16
+from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Muon, optimizer_settings
 
 
 class St355Accelerator:
@@ -105,10 +105,21 @@ class Trainer:
                        else [p for p in comp.parameters() if p.requires_grad])
         # optimizer_param.py:76-96 registry semantics: name -> class (+ default settings)
         opt_name = getattr(config, "optimizer", "st355-adamw")
-        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw"):                   # never a silently different optimizer
-            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, st355-adamw = torch-adamw semantics)")
+        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon"):           # never a silently different optimizer
+            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, st355-adamw = torch-adamw semantics)")
         self._bf16_shadow = None
-        if opt_name == "adamw_bf16":
+        if opt_name == "muon":
+            if not getattr(self.model, "SUPPORTS_MUON_CLIP", False):                   # trainer.py:332-339
+                raise ValueError(f"Optimizer 'muon' is not supported by model family {getattr(config, 'model_family', None)}. "
+                                 "Choose a supported optimizer or enable MuonClip explicitly on the model.")
+            if getattr(comp, "full", False):
+                raise NotImplementedError("optimizer 'muon' is built for LoRA adapters only: a full-rank matrix has a short side up to 3072 (the kernel "
+                                          "takes at most 128), and QK-clip would then act on trained q/k weights, which needs per-head max logits "
+                                          "from the attention forward")
+            if hasattr(self.model, "enable_muon_clip_logging"):
+                self.model.enable_muon_clip_logging()
+            self.optimizer = St355Muon(self.params, lr=config.learning_rate, **optimizer_settings("muon", config))
+        elif opt_name == "adamw_bf16":
             opt_params = self.params
             if any(p.dtype != torch.bfloat16 for p in self.params):
                 opt_params = self._make_bf16_shadow()
