@@ -473,16 +473,29 @@ int st355_lora_pack(void* stream, const float* A, const float* Bm, int r, int K,
 int64_t st355_conv_grid_rows(int B, int H, int W);
 int st355_conv_bf16(void* stream, const void* x, const void* w, const void* bias, const void* img_add, int64_t img_add_stride,
                     const void* residual, void* out, int B, int H, int W, int Cin, int Cout, int taps);
-/* dw[co, tap*Cin + ci] (+)= sum_pos dy[pos, co] * x[pos + shift(tap), ci]   (one TN GEMM per tap; workspace: optional fp32 split-K scratch) */
+/* dw[co, tap*Cin + ci] (+)= sum_pos dy[pos, co] * x[pos + shift(tap), ci]   (taps 9: nine column blocks of one TN GEMM; workspace: optional fp32 split-K scratch).
+ * x AND dy must be whole grid buffers: the contraction runs over every grid row from W+3 on, rounded up to a multiple of 64 (into the tail rows), so dy's border
+ * positions and tail rows must be ZERO (they meet interior values of x) and x's tail rows finite.  One rounding per element, with or without split-K. */
 int st355_conv_wgrad_bf16(void* stream, const void* x, const void* dy, void* dw, int B, int H, int W, int Cin, int Cout, int taps,
                           int accumulate, void* workspace, int64_t workspace_bytes);
+/* What the two launchers above would run for these arguments, without launching anything (they take every decision through the same host helpers).
+ * dims / out by kind (dims: 8 int64; out: 8 int32, unused entries 0):
+ *   FWD    {B, H, W, Cin, Cout, taps, residual given}                    -> {kernel ST355_CONV_KERNEL_*, epilogue ST355_EPI_NONE | ST355_EPI_ADD, tiles (256 x 256
+ *          on PQ, 128 x 128 on S2), 64-column wave groups of the last column tile that lie beyond Cout and issue no MFMAs (PQ only: 3 / 2 / 0 at Cout 320 / 640 / 1280)}
+ *   WGRAD  {B, H, W, Cin, Cout, taps, accumulate, workspace_bytes}       -> {taps (9: nine column blocks in one launch, 1: single TN GEMM), 256 x 256 output tiles,
+ *          K-slices ks (1 = no split-K: direct store), contraction rows Mc (the grid's GEMM rows rounded up to 64), epilogue of the direct store (0 under split-K)}
+ *          workspace_bytes: size of a 16-byte-aligned workspace, 0 = none.
+ * Validates the shape as the launch would. */
+enum { ST355_CONV_PLAN_FWD = 1, ST355_CONV_PLAN_WGRAD = 2 };
+enum { ST355_CONV_KERNEL_PQ = 1, ST355_CONV_KERNEL_S2 = 2 };
+int st355_conv_plan(int kind, const int64_t* dims, int32_t* out);
 /* layout passes (conv.hip) */
 int st355_grid_from_nchw(void* stream, const void* x /*[B,C,H,W] bf16*/, void* grid /*[.., Cpad]*/, int B, int C, int H, int W, int Cpad);
 int st355_grid_to_nchw(void* stream, const void* grid, void* y, int B, int C, int H, int W, int Cpad);
 /* columns on the OUTPUT grid of a 3x3 conv with stride 1|2: col[(b,yo,xo), tap*C + c]; columns >= 9*C up to Kpad are zero.
  * pad 1: symmetric padding 1 (UNet Downsample2D, conv_in);  pad 0 (stride 2 only): the VAE encoder's Downsample2D = F.pad(x,(0,1,0,1)) + pad-0 conv */
 int st355_im2col3x3(void* stream, const void* x, void* col, int B, int H, int W, int C, int stride, int Kpad, int pad);
-int st355_col2im3x3(void* stream, const void* dcol, void* dx, int B, int H, int W, int C, int stride, int Kpad, int pad);   /* adjoint (gather form) */
+int st355_col2im3x3(void* stream, const void* dcol, void* dx, int B, int H, int W, int C, int stride, int Kpad, int pad);   /* adjoint (gather form); same pad rule: pad 0 with stride 2 only */
 /* ---- block-level entry points ---------------------------------------------------------------------------------------------------
  * One FluxSingleTransformerBlock (flux/transformer.py:473-510) forward / backward as ONE call: the functions sequence the entry points above (AdaLN
  * modulate, the fused QKV projection, attention, the GELU and gated-residual GEMMs; their backward forms and the rank-space adapter gradients) in the order

@@ -112,6 +112,7 @@ extern "C" int st355_im2col3x3(void* stream, const void* x, void* col, int B, in
 extern "C" int st355_col2im3x3(void* stream, const void* dcol, void* dx, int B, int H, int W, int C, int stride, int Kpad, int pad) {
   ST_REQUIRE(dcol && dx && C % 8 == 0 && Kpad % 8 == 0 && Kpad >= 9 * C && (stride == 1 || stride == 2) && H % stride == 0 && W % stride == 0,
              "col2im3x3: bad args");
+  ST_REQUIRE(pad == 1 || (pad == 0 && stride == 2), "col2im3x3: pad 0 is the stride-2 (0,1,0,1)-padded form only");
   const int64_t n = (int64_t)B * (H + 2) * (W + 2) * (C / 8);
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 0.0, 16.0 * n * (1 + 9.0 / (stride * stride)));
   hipLaunchKernelGGL(k_col2im3x3, dim3((unsigned)std::min<int64_t>(cdiv64(n, 256), 65536)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dcol, (bf16*)dx, B, H, W, C,

@@ -2556,6 +2556,78 @@ extern "C" int st355_linear_fp8(void* stream, const void* xq, int64_t ldx, const
 }
 
 // ---- weight-gradient form -------------------------------------------------------------------------------------------------------
+// ---- the schedule decisions of the TN (weight-gradient) GEMM and of the convolution: gemm_tn_impl / st355_conv_bf16 and st355_conv_plan all call these ----
+static int tn_tiles(int P, int Q, int taps) { return ((P + PQ_BM - 1) / PQ_BM) * ((Q + PQ_BN - 1) / PQ_BN) * taps; }
+
+// K-slices of a TN GEMM with nt_all K-tiles and tiles0 output tiles; 1 = no split-K (direct EPI_NONE / EPI_ADD store).
+// weight matrices are small next to the token count: when the output has too few 256x256 tiles for 256 CUs, slice the contraction
+// (fp32 slabs in the caller's workspace, fixed-order reduce — deterministic)
+static int tn_slices(int nt_all, int tiles0, int P, int Q, int taps, const void* workspace, int64_t workspace_bytes) {
+  int ks = (384 + tiles0 - 1) / tiles0;
+  if (ks > nt_all / 8) ks = nt_all / 8;                // >= 8 K-tiles per slice
+  if (ks > 16) ks = 16;
+  {
+    // r5: the slice count from a cost model instead of "about 384 workgroups": rounds of workgroups over the CUs x (K-tiles per slice + ~6 K-tiles' worth of
+    // prologue / slab epilogue), plus the reduce pass's read of one fp32 slab per slice (tiles0 * 256 KiB at ~4.8 TB/s ~= 0.026 K-tile times per tile).  The old rule
+    // gave 144 output tiles 3 slices = 1.69 rounds (2 rounds for 84 % of the work); 5 or 7 slices fill their last round.  ST355_TN_KS: 0 = this model, -1 = the old
+    // rule, n = n slices (lab).
+    static int mode = -2;
+    if (mode == -2) { const char* e = getenv("ST355_TN_KS"); mode = e ? atoi(e) : 0; }
+    if (mode > 0) ks = mode;
+    else if (mode == 0 && tiles0 < 2 * device_cus()) {
+      const int cus = device_cus();
+      double best = 1e30; int best_ks = 1;
+      const int ks_max = nt_all / 8 < 16 ? (nt_all / 8 < 1 ? 1 : nt_all / 8) : 16;
+      for (int k = 1; k <= ks_max; k++) {
+        const int per = (nt_all + k - 1) / k;
+        const int rounds = (tiles0 * k + cus - 1) / cus;
+        const double cost = (double)rounds * (per + 6) + (k > 1 ? 0.026 * tiles0 * k : 0.0);
+        if (cost < best - 1e-9) { best = cost; best_ks = k; }
+      }
+      ks = best_ks;
+    }
+  }
+  while (ks >= 2 && workspace && (int64_t)ks * P * Q * taps * 4 > workspace_bytes) ks--;      // as many slices as the caller's slab space holds (never fall back to ONE round of full-K tiles)
+  if (ks >= 2) { const int per = (nt_all + ks - 1) / ks; ks = (nt_all + per - 1) / per; }   // no empty K-slices (the ring prologue assumes >= 1 K-tile)
+  return (ks >= 2 && workspace && ((uintptr_t)workspace % 16 == 0) && (int64_t)ks * P * Q * taps * 4 <= workspace_bytes) ? ks : 1;
+}
+
+// the shape requirements of a TN GEMM (gemm_tn_impl; st355_conv_plan validates a weight gradient with the same function)
+static int tn_check_shape(int64_t Mc, int P, int Q, int64_t ldl, int64_t ldr, int64_t ldc) {
+  ST_REQUIRE(Mc > 0 && P > 0 && Q > 0, "gemm_tn: bad args");
+  ST_REQUIRE(Mc % PQ_BK == 0, "gemm_tn: the contraction length (%lld rows) must be a multiple of 64 (pad the operands with zero rows)", (long long)Mc);
+  ST_REQUIRE(P % 8 == 0 && Q % 8 == 0 && ldl % 8 == 0 && ldr % 8 == 0 && ldc % 8 == 0, "gemm_tn: P, Q and the leading dimensions must be multiples of 8");
+  ST_REQUIRE(Mc * (int64_t)(ldl > ldr ? ldl : ldr) * 2 < ((int64_t)1 << 31), "gemm_tn: operand too large for the 32-bit buffer offsets (2 GiB)");
+  return ST355_OK;
+}
+
+// contraction length of the convolution weight gradient: the GEMM rows of the grid, rounded up to whole K-tiles (the rows added are border / tail rows)
+static int64_t conv_wgrad_rows(int B, int H, int W) {
+  const int64_t Mtot = (int64_t)B * (H + 2) * (W + 2), p0 = W + 3;
+  return ((Mtot - 2 * p0 + 63) / 64) * 64;
+}
+
+// forward convolution: the 256x256 conv instance of k_gemm_pq when its tiles (nearly) fill the chip, else k_gemm_s2 (128x128)
+static bool conv_on_pq(const GemmP& p) { return gemm_impl_choice() >= 4 && p4_tiles(p) >= min_tiles_256(); }
+static int conv_skip_dead() {
+  static int sd = -1;
+  if (sd < 0) { const char* e = getenv("ST355_CONV_SKIP_DEAD"); sd = (e && e[0] == '0') ? 0 : 1; }
+  return sd;
+}
+
+// the shape requirements of st355_conv_bf16 (st355_conv_plan validates with the same function)
+static int conv_check_shape(int B, int H, int W, int Cin, int Cout, int taps) {
+  ST_REQUIRE(B > 0 && H > 0 && W > 0, "conv: bad args");
+  ST_REQUIRE(taps == 1 || taps == 9, "conv: taps must be 1 or 9");
+  ST_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv: Cin (%d) must be a multiple of 64 and Cout (%d) of 8", Cin, Cout);
+  const int64_t Wp = W + 2, Mc = (int64_t)B * (H + 2) * Wp - 2 * (Wp + 1);
+  ST_REQUIRE(Mc > 0 && Mc < ((int64_t)1 << 31), "conv: grid too large");
+  ST_REQUIRE(256 * (int64_t)Cin * 2 + (2 * (int64_t)Wp + 2) * Cin * 2 + Cin * 2 < ((int64_t)1 << 31), "conv: a tile must fit 32-bit offsets");
+  return ST355_OK;
+}
+// 64-column wave groups of the last 256-wide column tile that issue no MFMAs (k_gemm_pq, CONV: mma_live = n0 + wn * 64 < N); k_gemm_s2 has no such test
+static int conv_dead_groups(int N, bool on_pq) { return (on_pq && conv_skip_dead()) ? (((N + PQ_BN - 1) / PQ_BN) * PQ_BN - N) / 64 : 0; }
+
 template <int EPI>
 static int launch_tn(void* stream, const GemmGroup& g, int tiles) {
   static St355AttrOnce attr_set;
@@ -2576,10 +2648,9 @@ static int gemm_tn_impl(void* stream, const void* L, int64_t ldl, const void* R,
     const int64_t span_l = ((nseg - 1) * (seg_l ? seg_l : seg_rows) + seg_rows) * ldl * 2, span_r = ((nseg - 1) * (seg_r ? seg_r : seg_rows) + seg_rows) * ldr * 2;
     ST_REQUIRE(span_l < ((int64_t)1 << 31) && span_r < ((int64_t)1 << 31) && Mc / PQ_BK < 65536, "gemm_tn_seg: operand too large for the 32-bit buffer offsets (2 GiB)");
   }
-  ST_REQUIRE(Mc % PQ_BK == 0, "gemm_tn: the contraction length (%lld rows) must be a multiple of 64 (pad the operands with zero rows)", (long long)Mc);
-  ST_REQUIRE(P % 8 == 0 && Q % 8 == 0 && ldl % 8 == 0 && ldr % 8 == 0 && ldc % 8 == 0, "gemm_tn: P, Q and the leading dimensions must be multiples of 8");
+  int rc_shape = tn_check_shape(Mc, P, Q, ldl, ldr, ldc);
+  if (rc_shape) return rc_shape;
   ST_REQUIRE(((uintptr_t)L % 16 == 0) && ((uintptr_t)R % 16 == 0) && ((uintptr_t)C % 16 == 0), "gemm_tn: misaligned pointer");
-  ST_REQUIRE(Mc * (int64_t)(ldl > ldr ? ldl : ldr) * 2 < ((int64_t)1 << 31), "gemm_tn: operand too large for the 32-bit buffer offsets (2 GiB)");
   GemmP p;
   memset(&p, 0, sizeof(p));
   p.A = (const bf16*)L; p.lda = ldl; p.B = (const bf16*)R; p.ldb = ldr; p.C = (bf16*)C; p.ldc = ldc;
@@ -2594,38 +2665,10 @@ static int gemm_tn_impl(void* stream, const void* L, int64_t ldl, const void* R,
   if (accumulate) { p.aux_in = (const bf16*)C; p.ld_aux_in = ldc; }
   GemmGroup g;
   g.p[0] = p; g.p[1] = p;
-  g.tiles0 = ((P + PQ_BM - 1) / PQ_BM) * ((Q + PQ_BN - 1) / PQ_BN) * taps;
+  g.tiles0 = tn_tiles(P, Q, taps);
   ProfScope ps(stream, ST355_K_GEMM, 2.0 * (double)Mc * P * Q * taps, 2.0 * ((double)Mc * (P + Q) + (double)P * Q * taps * (accumulate ? 2 : 1)), "TN%d %dx%dx%lld", taps, P, Q, (long long)Mc);
-  // weight matrices are small next to the token count: when the output has too few 256x256 tiles for 256 CUs, slice the contraction
-  // (fp32 slabs in the caller's workspace, fixed-order reduce — deterministic)
-  const int nt_all = (int)(Mc / PQ_BK);
-  int ks = (384 + g.tiles0 - 1) / g.tiles0;
-  if (ks > nt_all / 8) ks = nt_all / 8;                // >= 8 K-tiles per slice
-  if (ks > 16) ks = 16;
-  {
-    // r5: the slice count from a cost model instead of "about 384 workgroups": rounds of workgroups over the CUs x (K-tiles per slice + ~6 K-tiles' worth of
-    // prologue / slab epilogue), plus the reduce pass's read of one fp32 slab per slice (tiles0 * 256 KiB at ~4.8 TB/s ~= 0.026 K-tile times per tile).  The old rule
-    // gave 144 output tiles 3 slices = 1.69 rounds (2 rounds for 84 % of the work); 5 or 7 slices fill their last round.  ST355_TN_KS: 0 = this model, -1 = the old
-    // rule, n = n slices (lab).
-    static int mode = -2;
-    if (mode == -2) { const char* e = getenv("ST355_TN_KS"); mode = e ? atoi(e) : 0; }
-    if (mode > 0) ks = mode;
-    else if (mode == 0 && g.tiles0 < 2 * device_cus()) {
-      const int cus = device_cus();
-      double best = 1e30; int best_ks = 1;
-      const int ks_max = nt_all / 8 < 16 ? (nt_all / 8 < 1 ? 1 : nt_all / 8) : 16;
-      for (int k = 1; k <= ks_max; k++) {
-        const int per = (nt_all + k - 1) / k;
-        const int rounds = (g.tiles0 * k + cus - 1) / cus;
-        const double cost = (double)rounds * (per + 6) + (k > 1 ? 0.026 * g.tiles0 * k : 0.0);
-        if (cost < best - 1e-9) { best = cost; best_ks = k; }
-      }
-      ks = best_ks;
-    }
-  }
-  while (ks >= 2 && workspace && (int64_t)ks * P * Q * taps * 4 > workspace_bytes) ks--;      // as many slices as the caller's slab space holds (never fall back to ONE round of full-K tiles)
-  if (ks >= 2) { const int per = (nt_all + ks - 1) / ks; ks = (nt_all + per - 1) / per; }   // no empty K-slices (the ring prologue assumes >= 1 K-tile)
-  if (ks >= 2 && workspace && ((uintptr_t)workspace % 16 == 0) && (int64_t)ks * P * Q * taps * 4 <= workspace_bytes) {
+  const int ks = tn_slices((int)(Mc / PQ_BK), g.tiles0, P, Q, taps, workspace, workspace_bytes);
+  if (ks >= 2) {
     g.p[0].partial = (float*)workspace; g.p[0].ksplit = ks; g.p[0].aux_in = nullptr;
     g.p[1] = g.p[0];
     static St355AttrOnce attr_set;
@@ -2666,13 +2709,11 @@ extern "C" int64_t st355_conv_grid_rows(int B, int H, int W) { return (int64_t)B
 extern "C" int st355_conv_bf16(void* stream, const void* x, const void* w, const void* bias, const void* img_add, int64_t img_add_stride,
                                const void* residual, void* out, int B, int H, int W, int Cin, int Cout, int taps) {
   ST_REQUIRE(x && w && out && B > 0 && H > 0 && W > 0, "conv: bad args");
-  ST_REQUIRE(taps == 1 || taps == 9, "conv: taps must be 1 or 9");
-  ST_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv: Cin (%d) must be a multiple of 64 and Cout (%d) of 8", Cin, Cout);
   ST_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)out % 16 == 0), "conv: misaligned pointer");
   const int Hp = H + 2, Wp = W + 2;
   const int64_t Mtot = (int64_t)B * Hp * Wp, p0 = Wp + 1, Mc = Mtot - 2 * p0;
-  ST_REQUIRE(Mc > 0 && Mc < ((int64_t)1 << 31), "conv: grid too large");
-  ST_REQUIRE(256 * (int64_t)Cin * 2 + (2 * (int64_t)Wp + 2) * Cin * 2 + Cin * 2 < ((int64_t)1 << 31), "conv: a tile must fit 32-bit offsets");
+  int rc_shape = conv_check_shape(B, H, W, Cin, Cout, taps);
+  if (rc_shape) return rc_shape;
   GemmP p;
   memset(&p, 0, sizeof(p));
   p.A = (const bf16*)x + (taps == 9 ? 0 : p0 * Cin); p.lda = Cin;
@@ -2682,13 +2723,13 @@ extern "C" int st355_conv_bf16(void* stream, const void* x, const void* w, const
   p.bias = (const bf16*)bias;
   if (residual) { p.aux_in = (const bf16*)residual + p0 * Cout; p.ld_aux_in = Cout; }
   p.conv_taps = taps; p.conv_tpt = Cin / BK; p.conv_wp = Wp; p.conv_hp = Hp; p.conv_row0 = p0;
-  { static int sd = -1; if (sd < 0) { const char* e = getenv("ST355_CONV_SKIP_DEAD"); sd = (e && e[0] == '0') ? 0 : 1; } p.skip_dead = sd; }
+  p.skip_dead = conv_skip_dead();
   p.img_add = (const bf16*)img_add; p.img_add_stride = img_add_stride;
   // the first / last Wp+1 positions are border positions that no GEMM row covers: they keep the caller's zeros (grid buffers are allocated
   // zero-filled and no kernel ever writes a border position non-zero), which saves two memset launches per convolution
   ProfScope ps(stream, ST355_K_GEMM, 2.0 * (double)Mc * Cout * taps * Cin, 2.0 * ((double)Mtot * Cin + (double)Cout * taps * Cin + (double)Mtot * Cout * (residual ? 2 : 1)),
                "CONV%d %dx%dx%d b%d %dx%d", taps, (int)Mc, Cout, taps * Cin, B, H, W);
-  if (gemm_impl_choice() >= 4 && p4_tiles(p) >= min_tiles_256()) {
+  if (conv_on_pq(p)) {
     GemmGroup g;
     g.p[0] = p; g.p[1] = p; g.tiles0 = p4_tiles(p);
     return residual ? launch_pq_conv<ST355_EPI_ADD>(stream, g, g.tiles0) : launch_pq_conv<ST355_EPI_NONE>(stream, g, g.tiles0);
@@ -2702,12 +2743,46 @@ extern "C" int st355_conv_wgrad_bf16(void* stream, const void* x, const void* dy
                                      int accumulate, void* workspace, int64_t workspace_bytes) {
   ST_REQUIRE(x && dy && dw && (taps == 1 || taps == 9), "conv_wgrad: bad args");
   const int Hp = H + 2, Wp = W + 2;
-  const int64_t Mtot = (int64_t)B * Hp * Wp, p0 = Wp + 1;
-  const int64_t Mc = ((Mtot - 2 * p0 + 63) / 64) * 64;
+  const int64_t p0 = Wp + 1, Mc = conv_wgrad_rows(B, H, W);
   if (taps == 9)      // all nine taps in one launch: R = x from the grid start (p0 + shift(tap) >= 0 for every tap)
     return gemm_tn_impl(stream, (const bf16*)dy + p0 * Cout, Cout, (const bf16*)x, Cin, dw, (int64_t)9 * Cin, Mc, Cout, Cin, accumulate, workspace, workspace_bytes, 9, Wp);
   int rc = st355_gemm_tn_bf16(stream, (const bf16*)dy + p0 * Cout, Cout, (const bf16*)x + p0 * Cin, Cin, dw, Cin, Mc, Cout, Cin, accumulate, workspace, workspace_bytes);
   if (rc) return rc;
+  return ST355_OK;
+}
+
+// what st355_conv_bf16 / st355_conv_wgrad_bf16 would launch for these arguments — the same helpers as the launchers above, nothing is launched
+extern "C" int st355_conv_plan(int kind, const int64_t* dims, int32_t* out) {
+  ST_REQUIRE(dims && out, "conv_plan: null pointer");
+  for (int i = 0; i < 8; i++) out[i] = 0;
+  const int B = (int)dims[0], H = (int)dims[1], W = (int)dims[2], Cin = (int)dims[3], Cout = (int)dims[4], taps = (int)dims[5];
+  if (kind == ST355_CONV_PLAN_FWD) {
+    int rc = conv_check_shape(B, H, W, Cin, Cout, taps);
+    if (rc) return rc;
+    GemmP p;
+    memset(&p, 0, sizeof(p));
+    p.M = (int)((int64_t)B * (H + 2) * (W + 2) - 2 * (W + 3)); p.N = Cout;
+    const bool pq = conv_on_pq(p);
+    out[0] = pq ? ST355_CONV_KERNEL_PQ : ST355_CONV_KERNEL_S2;
+    out[1] = dims[6] ? ST355_EPI_ADD : ST355_EPI_NONE;
+    out[2] = pq ? p4_tiles(p) : ((p.M + S2_BM - 1) / S2_BM) * ((p.N + S2_BN - 1) / S2_BN);
+    out[3] = conv_dead_groups(Cout, pq);
+    return ST355_OK;
+  }
+  if (kind == ST355_CONV_PLAN_WGRAD) {
+    ST_REQUIRE(taps == 1 || taps == 9, "conv_wgrad: bad args");
+    ST_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_plan: bad shape");
+    const int64_t Mc = conv_wgrad_rows(B, H, W);
+    int rc = tn_check_shape(Mc, Cout, Cin, Cout, Cin, (int64_t)taps * Cin);
+    if (rc) return rc;
+    const int tiles = tn_tiles(Cout, Cin, taps);
+    // dims[7]: bytes of a 16-byte-aligned workspace, 0 = none given
+    const int ks = tn_slices((int)(Mc / PQ_BK), tiles, Cout, Cin, taps, dims[7] > 0 ? (const void*)16 : nullptr, dims[7]);
+    out[0] = taps; out[1] = tiles; out[2] = ks; out[3] = (int)Mc;
+    out[4] = ks >= 2 ? 0 : (dims[6] ? ST355_EPI_ADD : ST355_EPI_NONE);      // the direct store's epilogue (split-K: k_splitk_reduce adds the old value)
+    return ST355_OK;
+  }
+  ST_REQUIRE(false, "conv_plan: unknown kind %d", kind);
   return ST355_OK;
 }
 

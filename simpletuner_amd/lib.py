@@ -30,7 +30,7 @@ SYMBOLS = [
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
     # UNet path (SDXL / SD1.5)
-    "st355_conv_grid_rows", "st355_conv_bf16", "st355_conv_wgrad_bf16", "st355_grid_from_nchw", "st355_grid_to_nchw", "st355_im2col3x3", "st355_col2im3x3", "st355_softmax_rows", "st355_vae_encode_workspace", "st355_vae_encode", "st355_block_flux_single_fwd", "st355_block_flux_single_bwd", "st355_block_flux_double_fwd", "st355_block_flux_double_bwd", "st355_block_pixart_fwd", "st355_block_pixart_bwd", "st355_block_sd3_joint_fwd", "st355_block_sd3_joint_bwd",
+    "st355_conv_grid_rows", "st355_conv_bf16", "st355_conv_wgrad_bf16", "st355_conv_plan", "st355_grid_from_nchw", "st355_grid_to_nchw", "st355_im2col3x3", "st355_col2im3x3", "st355_softmax_rows", "st355_vae_encode_workspace", "st355_vae_encode", "st355_block_flux_single_fwd", "st355_block_flux_single_bwd", "st355_block_flux_double_fwd", "st355_block_flux_double_bwd", "st355_block_pixart_fwd", "st355_block_pixart_bwd", "st355_block_sd3_joint_fwd", "st355_block_sd3_joint_bwd",
     "st355_upsample2x", "st355_upsample2x_bwd", "st355_tokens_to_grid", "st355_grid_to_tokens",
     "st355_groupnorm_workspace", "st355_groupnorm_fwd", "st355_groupnorm_bwd", "st355_gn_set_apply", "st355_norm_plan",
     "st355_layernorm_fwd", "st355_layernorm_bwd", "st355_layernorm_param_grads_workspace", "st355_layernorm_param_grads",
@@ -353,6 +353,7 @@ def _declare(lib):
         "st355_conv_grid_rows": (i64, [i32, i32, i32]),
         "st355_conv_bf16": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32]),
         "st355_conv_wgrad_bf16": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64]),
+        "st355_conv_plan": (C.c_int, [i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
         "st355_grid_from_nchw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32]),
         "st355_grid_to_nchw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32]),
         "st355_im2col3x3": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32]),

@@ -1211,6 +1211,27 @@ def conv_wgrad(x, dy, dw, B: int, H: int, W: int, taps: int = 9, accumulate: boo
     return dw
 
 
+def conv_plan(B: int, H: int, W: int, Cin: int, Cout: int, taps: int = 9, residual: bool = False):
+    """st355_conv_plan, forward: what conv() would launch for this shape, without launching.  {"kernel": "pq_conv" | "s2", "epilogue": "NONE" | "ADD",
+    "tiles", "dead": 64-column wave groups of the last column tile that issue no MFMAs}"""
+    d = (C.c_int64 * 8)(B, H, W, Cin, Cout, taps, 1 if residual else 0, 0)
+    out = (C.c_int32 * 8)()
+    _l.check(_l.load().st355_conv_plan(1, d, out), "conv_plan")
+    return {"kernel": {1: "pq_conv", 2: "s2"}[out[0]], "epilogue": {EPI_NONE: "NONE", EPI_ADD: "ADD"}[out[1]], "tiles": int(out[2]), "dead": int(out[3])}
+
+
+def conv_wgrad_plan(B: int, H: int, W: int, Cin: int, Cout: int, taps: int = 9, accumulate: bool = False, workspace_bytes: int = -1):
+    """st355_conv_plan, weight gradient: what conv_wgrad() would launch.  workspace_bytes: -1 = the workspace conv_wgrad() passes on the current device.
+    {"taps": 9 | 1, "tiles", "ks": K-slices (1 = direct store), "Mc": rounded contraction rows, "store": "SPLITK" | "NONE" | "ADD"}"""
+    if workspace_bytes < 0:
+        workspace_bytes = _gemm_workspace(torch.device("cuda", torch.cuda.current_device())).numel() * 4
+    d = (C.c_int64 * 8)(B, H, W, Cin, Cout, taps, 1 if accumulate else 0, workspace_bytes)
+    out = (C.c_int32 * 8)()
+    _l.check(_l.load().st355_conv_plan(2, d, out), "conv_plan")
+    ks = int(out[2])
+    return {"taps": int(out[0]), "tiles": int(out[1]), "ks": ks, "Mc": int(out[3]), "store": "SPLITK" if ks >= 2 else {EPI_NONE: "NONE", EPI_ADD: "ADD"}[out[4]]}
+
+
 def im2col3x3(x, B: int, H: int, W: int, stride: int = 1, pad: int = 1):
     L = _l.load()
     _chk(x, BF16, "x")
