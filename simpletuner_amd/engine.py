@@ -1,0 +1,360 @@
+"""Host code the engines share (flux/, sd3/, pixart/ transformer.py, unet/unet.py): nothing here knows a model family.
+
+  * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
+  * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
+  * `pad64` / `pad64_empty`: operands of the TN weight-gradient GEMM (contraction granule: 64 rows);
+  * `ArenaModule`: every base parameter a view of ONE bf16 arena (two-pass construction), checkpoint load / save over the parameter names;
+  * `FullGrads`: the per-backward helper of full-rank training — weight / bias gradients into the gradient arena, the modulation rows' reductions, the fused
+    modulation matrix's gradient row block by row block, the modulation Linear's and the conditioning MLPs' backward.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import ops
+
+BF16 = torch.bfloat16
+F32 = torch.float32
+
+
+# ------------------------------------------------------------------------------------------------
+# helpers to register parameters under dotted (checkpoint) names
+# ------------------------------------------------------------------------------------------------
+class Holder(nn.Module):
+    pass
+
+
+def attach(root: nn.Module, dotted: str, param: nn.Parameter):
+    parts = dotted.split(".")
+    mod = root
+    for p in parts[:-1]:
+        if not hasattr(mod, p):
+            mod.add_module(p, Holder())
+        mod = getattr(mod, p)
+    mod.register_parameter(parts[-1], param)
+
+
+def frozen(t: torch.Tensor) -> nn.Parameter:
+    return nn.Parameter(t, requires_grad=False)
+
+
+class LoraGroup:
+    """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A x."""
+
+    def __init__(self, K: int, N_total: int, targets: List[Tuple[str, int, int]], rank: int, alpha: float, device):
+        self.K, self.N_total, self.targets = K, N_total, targets
+        self.rank, self.scale = rank, alpha / rank
+        # adapter columns inside the K-extension: 32 / 64 (one pass of the rank-space kernels), above 64 a multiple of 64 walked in 64-column slabs
+        # (the reference's sd3.peft-lora example trains rank 128)
+        self.r_pad = 32 if rank <= 32 else (rank + 63) // 64 * 64
+        self.K2 = (len(targets) * self.r_pad + 63) // 64 * 64
+        self.k2_real = len(targets) * rank          # adapter columns inside the padded extension (algorithmic-work accounting of the profiler)
+        z = lambda *s: torch.zeros(*s, dtype=BF16, device=device)
+        self.A_cat, self.A_cat_T = z(self.K2, K), z(K, self.K2)
+        self.B_blk, self.B_blk_T = z(N_total, self.K2), z(self.K2, N_total)
+        self.A: List[torch.Tensor] = []   # fp32 params (views into the flat arena), filled by the owner
+        self.B: List[torch.Tensor] = []
+        self.gA: List[torch.Tensor] = []  # fp32 grad views
+        self.gB: List[torch.Tensor] = []
+        self.flat_lo = self.flat_hi = 0   # this group's [lo, hi) element range inside the flat gradient arena
+
+    def pack(self):
+        for g, (_, n_off, _) in enumerate(self.targets):
+            ops.lora_pack(self.A[g], self.B[g], self.scale, self.A_cat, self.A_cat_T, self.B_blk, self.B_blk_T,
+                          k2_off=g * self.r_pad, n_off=n_off)
+
+    def grads(self, x, T, dy, U, accumulate: bool, sync=None):
+        """dB_g = s * dy_g^T T_g ; dA_g = U_g^T x   (rank-space backward: both products are [*, r]).  x: the projection's input, or — an input that only
+        exists as K segments (the single block's proj_out reads [attn | mlp] as a two-segment K loop) — a list of (segment, first input column)."""
+        segs = x if isinstance(x, (list, tuple)) else [(x, 0)]
+        multi = len(segs) == 1 and 1 < len(self.targets) <= 4 and self.r_pad == 32 and U.shape[1] >= 128   # q / k / v share x: dA of all three in ONE pass over x
+        cw = min(self.r_pad, 64)                                 # rank-space kernels take 32 or 64 adapter columns per pass
+        for g, (_, n_off, N) in enumerate(self.targets):
+            for s0 in range(0, self.rank, cw):
+                c0, r_used = g * self.r_pad + s0, min(cw, self.rank - s0)
+                ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], self.gB[g][:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=accumulate)
+                if not multi:
+                    for (xs, k0) in segs:
+                        ops.skinny_tn(xs, U[:, c0:c0 + cw], self.gA[g][s0:, k0:], 1, self.K, r_used, alpha=1.0, accumulate=accumulate)
+        if multi:
+            ops.skinny_tn_multi(x, U, self.gA, 1, self.K, self.rank, alpha=1.0, accumulate=accumulate)
+        if sync is not None:
+            sync.ready(self.flat_lo, self.flat_hi)
+
+
+# ------------------------------------------------------------------------------------------------
+# a stream's rows of a joint [B * S, C] buffer as GEMM operands
+# ------------------------------------------------------------------------------------------------
+def rows_of(joint, lo: int, rows: int, B: int, S: int):
+    """rows [lo, lo + rows) of every sample of a joint [B * S, C] buffer, as a GEMM / skinny operand: a [B, rows, C] strided view (no copy)"""
+    return joint.view(B, S, -1)[:, lo:lo + rows]
+
+
+def problems(B: int, rows: int, pr: dict):
+    """One projection over the `rows`-row block of every sample.  Operands may be compact [B * rows, C] tensors or [B, rows, C] views of joint
+    buffers (rows_of).  When the blocks are tile-aligned (rows % 256 == 0) that is ONE segmented problem (st355_gemm_args.seg_rows: one grid of
+    B * rows / 256 row tiles instead of B launches that each fill the 256 CUs badly); otherwise one problem per sample."""
+    ROWED = ("a", "a2", "out", "aux_in", "aux_out")
+    if B == 1:
+        return [{k: (v[0] if k in ROWED and torch.is_tensor(v) and v.dim() == 3 else v) for k, v in pr.items()}]
+    if rows % 256 == 0:
+        return [pr]
+    out = []
+    for b in range(B):
+        q = {}
+        for k, v in pr.items():
+            if k in ROWED and torch.is_tensor(v):
+                q[k] = v[b] if v.dim() == 3 else v[b * rows:(b + 1) * rows]
+            elif k == "gate":          # one gate row per sample, or — tokenwise timesteps — one per token row of this stream
+                q[k] = v[b:b + 1] if v.shape[0] == B else v[b * rows:(b + 1) * rows]
+            else:
+                q[k] = v
+        out.append(q)
+    return out
+
+
+def compact(t, B: int, rows: int):
+    """a [B, rows, C] view as an operand of the rank-space gradient kernels: as is when they can walk it segmented, else a compact copy"""
+    if t.dim() != 3:
+        return t
+    if B == 1:
+        return t[0]
+    return t if rows % 256 == 0 else t.reshape(B * rows, -1)
+
+
+# ------------------------------------------------------------------------------------------------
+# operands of the TN weight-gradient GEMM (contraction granule: 64 rows)
+# ------------------------------------------------------------------------------------------------
+def pad64_empty(rows: int, cols: int, dev):
+    """[rows, cols] bf16, uninitialised, as the head of a parent buffer whose row count is rounded up to 64 and whose tail rows are ZERO: the weight-gradient GEMM
+    reads the parent directly instead of a zero-padded copy of the tensor (two launches and a full copy per operand).  The view remembers its parent in
+    `_st355_pad64`."""
+    rp = (rows + 63) // 64 * 64
+    if rp == rows:
+        return torch.empty(rows, cols, dtype=BF16, device=dev)
+    par = torch.empty(rp, cols, dtype=BF16, device=dev)
+    par[rows:].zero_()
+    t = par[:rows]
+    t._st355_pad64 = par
+    return t
+
+
+def pad64(t):
+    """the operand with a multiple of 64 contraction rows: as is when aligned or segmented (3-D), its zero-tailed parent when it was allocated by
+    pad64_empty, else a zero-padded copy"""
+    if t.dim() == 3:
+        return t
+    r = t.shape[0]
+    if r % 64 == 0 and t.is_contiguous():
+        return t
+    par = getattr(t, "_st355_pad64", None)
+    if par is not None:
+        return par
+    o = torch.zeros((r + 63) // 64 * 64, t.shape[1], dtype=BF16, device=t.device)
+    o[:r] = t
+    return o
+
+
+def sincos_2d_hw(embed_dim: int, h: int, w: int, base_size: int, interpolation_scale: float) -> torch.Tensor:
+    """diffusers get_2d_sincos_pos_embed on a (h, w) grid: [h * w, embed_dim] fp32 (first half from the w coordinate, which varies fastest; sin then cos)"""
+    gh = (torch.arange(h, dtype=torch.float32) / (h / base_size) / interpolation_scale).double()
+    gw = (torch.arange(w, dtype=torch.float32) / (w / base_size) / interpolation_scale).double()
+    cw = gw[None, :].expand(h, w).reshape(-1)
+    chh = gh[:, None].expand(h, w).reshape(-1)
+
+    def one_d(dim, pos):
+        omega = 1.0 / 10000 ** (torch.arange(dim // 2, dtype=torch.float64) / (dim / 2.0))
+        out = pos[:, None] * omega[None, :]
+        return torch.cat([out.sin(), out.cos()], dim=1)
+
+    return torch.cat([one_d(embed_dim // 2, cw), one_d(embed_dim // 2, chh)], dim=1).float()
+
+
+# ------------------------------------------------------------------------------------------------
+# one bf16 arena under every base parameter
+# ------------------------------------------------------------------------------------------------
+class ArenaModule(nn.Module):
+    """Every weight / bias / norm weight / modulation row is a view of ONE bf16 arena (allocation order = arena order): full-rank training then has a gradient
+    arena of the same layout, ONE fused optimizer launch and contiguous slices for the gradient exchange.  The subclass's `_build()` allocates through
+    `_alloc` and names parameters through `_reg`; it runs twice — pass 1 counts on meta tensors, pass 2 hands out the views.  Hooks: `_extra_state()` (checkpoint
+    entries that are no parameters), `_weights_changed()` (drop what was derived from the weights), `_all_linears()`."""
+
+    def _build_arena(self, dev):
+        self._arena_numel, self._counting = 0, True
+        self._build()
+        self.arena = torch.zeros(self._arena_numel, dtype=BF16, device=dev)
+        self._arena_numel, self._counting = 0, False
+        self._build()
+
+    def _alloc(self, *shape):
+        n = 1
+        for d in shape:
+            n *= d
+        off = self._arena_numel
+        self._arena_numel += (n + 7) // 8 * 8               # every tensor starts 16-byte aligned inside the arena
+        if self._counting:
+            return torch.empty(*shape, dtype=BF16, device="meta")
+        return self.arena[off:off + n].view(*shape)
+
+    def _reg(self, name, param):
+        if not self._counting:
+            attach(self, name, param)
+
+    def _extra_state(self) -> Dict[str, torch.Tensor]:
+        return {}
+
+    def _weights_changed(self):
+        self._prepared = False
+
+    @torch.no_grad()
+    def load_flat_state(self, state: Dict[str, torch.Tensor]):
+        """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
+        own = dict(self.named_parameters())
+        missing = [k for k in own if k not in state and ".lora_" not in k]
+        if missing:
+            raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
+        own.update(self._extra_state())
+        for k, v in state.items():
+            if k in own:
+                own[k].data.copy_(v.to(device=own[k].device, dtype=own[k].dtype))
+        self._weights_changed()
+
+    def load_diffusers_state(self, state: Dict[str, torch.Tensor]):
+        self.load_flat_state(state)
+
+    def diffusers_state_dict(self) -> Dict[str, torch.Tensor]:
+        """{diffusers checkpoint key: tensor} of the base parameters (the parameter names ARE the checkpoint keys) + `_extra_state()`: what `save_pretrained`
+        writes (training/trainer.py save_state)"""
+        sd = {k: v.detach() for k, v in self.named_parameters() if ".lora_" not in k}
+        sd.update({k: v.detach() for k, v in self._extra_state().items()})
+        return sd
+
+    @torch.no_grad()
+    def init_synthetic(self, seed: int = 42):
+        """seed-deterministic random init on device, same distribution family as the oracle's init_params (benchmarks)."""
+        g = torch.Generator(device=self.device_).manual_seed(seed)
+        for name, p in self.named_parameters():
+            if ".lora_" in name:
+                continue
+            if "norm_q" in name or "norm_k" in name or "norm_added" in name:
+                p.data.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g, device=self.device_))
+            elif name.endswith(".bias"):
+                p.data.copy_(0.02 * torch.randn(p.shape, generator=g, device=self.device_))
+            else:
+                p.data.copy_(torch.randn(p.shape, generator=g, device=self.device_, dtype=BF16) * (1.0 / math.sqrt(p[0].numel())))      # fan-in
+        self._weights_changed()
+
+    def trainable_parameters(self):
+        return list(self._full_params) if self.full else list(self._lora_params)
+
+    def _refresh_transposed(self):
+        """W^T follows the weights (2 B read + 2 B write per parameter per step: ~12 ms for Flux.1-dev's 12 B parameters, ~1 ms for SD3-Medium)"""
+        for l in self._all_linears():
+            if getattr(l, "wT", None) is not None:
+                ops.transpose(l.w, out=l.wT)
+
+
+def mod_grads(D: int, dn, x_in, rows: int, k_shift: int, k_scale: int, dm, xhat=None):
+    """d shift = sum_t dY, d scale = sum_t dY * LN(x) of one AdaLN instance, per sample, into chunks k_shift / k_scale of its slice `dm` of the modulation-row
+    gradient.  x_in = the LayerNorm's input (LN(x) is recomputed: recovering it from the saved modulated output divides by 1 + scale, singular where a scale
+    entry is -1), or xhat = LN(x) when the caller already has it."""
+    ops.colsum_prod(dn, dm[:, k_shift * D:(k_shift + 1) * D], rows_per_batch=rows)
+    ops.colsum_prod(dn, dm[:, k_scale * D:(k_scale + 1) * D], b=ops.layer_norm_xhat(x_in) if xhat is None else xhat, rows_per_batch=rows)
+
+
+# ------------------------------------------------------------------------------------------------
+# full-rank training: what one backward shares between the families
+# ------------------------------------------------------------------------------------------------
+class FullGrads:
+    """One per backward of full-rank training.  Owns d loss / d (modulation Linear output) `dmod` [B, mod_total] fp32, the per-width bias temporaries and the
+    zero-padded silu(temb) `st_p`.  Reads `lin.gw` / `lin.gb` / `model.g_mod_*` at call time (SD3 re-points them between its two gradient arenas).
+    `front_hi`: the arena offset below which the fused modulation matrix must lie for its rows to be handed to `sync` block by block."""
+
+    def __init__(self, model, B: int, dev, sync, front_hi: int, st):
+        self.model, self.B, self.dev, self.sync = model, B, dev, sync
+        self.Bp = (B + 63) // 64 * 64
+        self.dmod = torch.zeros(B, model.mod_total, dtype=F32, device=dev)
+        self.st_p = self._pad_batch(st)
+        self._tmp_b = {}
+        self.mw_lo = (model.mod_w.data_ptr() - model.arena.data_ptr()) // 2
+        self.mw_hi = self.mw_lo + model.mod_total * model.D
+        self.mod_in_front = 0 <= self.mw_lo and self.mw_hi <= front_hi
+        self.mod_rows_lo = model.mod_total                # rows [mod_rows_lo, mod_total) of dW_mod are written (and handed over)
+
+    def _pad_batch(self, t):
+        """[B, C] -> bf16 [Bp, C], zero rows up to the TN GEMM's granule"""
+        o = torch.zeros(self.Bp, t.shape[1], dtype=BF16, device=self.dev)
+        o[:self.B] = t
+        return o
+
+    def bgrad(self, lin, dy):
+        N = dy.shape[1]
+        t = self._tmp_b.get(N)
+        if t is None:
+            t = self._tmp_b[N] = torch.empty(1, N, dtype=F32, device=self.dev)
+        ops.colsum_prod(dy, t)
+        lin.gb.copy_(t[0])
+
+    def wgrad(self, lin, dy, x, bias: bool = True):
+        """dW = dY^T X ; db = colsum(dY)   (into the gradient arena views of `lin`; bias=False: the bias gradient was already taken by a fused pass)"""
+        ops.gemm_tn(pad64(dy), pad64(x), out=lin.gw)
+        if bias:
+            self.bgrad(lin, dy)
+
+    def mod_grads(self, dn, x_in, rows, k_shift, k_scale, dm, xhat=None):
+        mod_grads(self.model.D, dn, x_in, rows, k_shift, k_scale, dm, xhat)
+
+    def mod_rows_grad(self, r0: int):
+        """The fused modulation matrix gets its gradient rows block by block: dW_mod[r0:r1] = dmod[:, r0:r1]^T silu(temb) as soon as the block that owns rows
+        [r0, r1) has run, so that the exchange takes them behind the backward instead of as one exposed region after it.  Same arithmetic per row (one 64-deep
+        contraction over the zero-padded batch): bit-equal to the one-product form."""
+        m, r1 = self.model, self.mod_rows_lo
+        if r1 <= r0:
+            return
+        ops.gemm_tn(self._pad_batch(self.dmod[:, r0:r1]), self.st_p, out=m.g_mod_w[r0:r1])
+        self.mod_rows_lo = r0
+        if self.sync is not None and self.mod_in_front:
+            self.sync.ready(self.mw_lo + r0 * m.D, self.mw_lo + r1 * m.D)
+
+    def mod_linear_bwd(self, temb):
+        """modulation Linear mod = silu(temb) W_mod^T + b: the rows of dW_mod not handed over yet, db, and d temb"""
+        m, B, dev = self.model, self.B, self.dev
+        D = m.D
+        dmod_p = self._pad_batch(self.dmod)
+        self.mod_rows_grad(0)
+        tb = torch.empty(1, m.mod_total, dtype=F32, device=dev)
+        ops.colsum_prod(dmod_p, tb)
+        m.g_mod_b.copy_(tb[0])
+        # d silu(temb) = dmod @ W_mod -> [B, D], as (W_mod^T dmod^T)^T with the TN GEMM.  The contraction runs over the mod_total rows of W_mod (1.06 M for
+        # Flux.1-dev): walked in row blocks that stay inside the TN GEMM's 2 GiB operand window, accumulated into one [D, B8] output
+        B8 = 8 * ((B + 7) // 8)
+        dmod_t = ops.transpose(dmod_p[:B8])                                   # [mod_total, B8]
+        blk_rows = max(64, (getattr(m, "_tn_window_bytes", (1 << 31) - 1) // (2 * max(D, B8))) // 64 * 64)        # (attribute: tests shrink the window)
+        acc = torch.empty(D, B8, dtype=BF16, device=dev)
+        for i, r0 in enumerate(range(0, m.mod_total, blk_rows)):
+            r1 = min(m.mod_total, r0 + blk_rows)
+            ops.gemm_tn(m.mod_w[r0:r1], dmod_t[r0:r1], out=acc, accumulate=i > 0)
+        return ops.silu_bwd(temb, ops.transpose(acc)[:B].contiguous())
+
+    def mlp_bwd(self, l1, l2, x_in, pre1, act1, dy):
+        """TimestepEmbedding / guidance / pooled-text projection: y = l2(silu(l1(x)))"""
+        dyp = self._pad_batch(dy)
+        ops.gemm_tn(dyp, self._pad_batch(act1), out=l2.gw)
+        self.bgrad(l2, dyp)
+        d1p = self._pad_batch(ops.silu_bwd(pre1, ops.gemm(dy, l2.wT)))
+        ops.gemm_tn(d1p, self._pad_batch(x_in), out=l1.gw)
+        self.bgrad(l1, d1p)
+
+    def ready_front(self, hi: int):
+        """hand over what lies around the modulation matrix's rows below arena offset `hi` (embedders, the modulation bias)"""
+        if self.sync is None:
+            return
+        if self.mod_in_front:
+            self.sync.ready(self.mw_hi, hi)
+            self.sync.ready(0, self.mw_lo)
+        else:
+            self.sync.ready(0, hi)

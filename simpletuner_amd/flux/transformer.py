@@ -21,6 +21,7 @@ Storage layout (designed for 288 GB HBM, not for a 24 GB card):
 from __future__ import annotations
 
 import math
+import os
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -28,88 +29,25 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..engine import ArenaModule, FullGrads, LoraGroup, attach, compact, frozen, mod_grads, pad64, problems, rows_of
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_QK_NORM_ROPE
+from ..training.checkpoint_plan import CheckpointPlanMixin
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-_FUSED_QKV = __import__("os").environ.get("ST355_FUSED_QKV", "1") != "0"      # A/B switch: 0 = separate RMSNorm + RoPE pass after the QKV projection
-_FUSED_ROPE_BWD = __import__("os").environ.get("ST355_FUSED_ROPE_BWD", "1") != "0"   # A/B switch: 0 = RoPE / RMSNorm backward as its own pass after the attention backward
-_FUSED_VT = __import__("os").environ.get("ST355_FUSED_VT", "1") != "0"        # A/B switch: 0 = no V^T from the fused epilogue, forward attention reads row-major V
-_BLOCK_ABI = __import__("os").environ.get("ST355_BLOCK_ABI", "1") != "0"          # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_flux_*
-_BLOCK_ABI_ONLY = __import__("os").environ.get("ST355_BLOCK_ABI_ONLY", "")           # debugging aid: "single" / "double" / "fwd" / "bwd" restricts the C entry points to that subset
+_FUSED_QKV = os.environ.get("ST355_FUSED_QKV", "1") != "0"      # A/B switch: 0 = separate RMSNorm + RoPE pass after the QKV projection
+_FUSED_ROPE_BWD = os.environ.get("ST355_FUSED_ROPE_BWD", "1") != "0"   # A/B switch: 0 = RoPE / RMSNorm backward as its own pass after the attention backward
+_FUSED_VT = os.environ.get("ST355_FUSED_VT", "1") != "0"        # A/B switch: 0 = no V^T from the fused epilogue, forward attention reads row-major V
+_BLOCK_ABI = os.environ.get("ST355_BLOCK_ABI", "1") != "0"          # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_flux_*
+_BLOCK_ABI_ONLY = os.environ.get("ST355_BLOCK_ABI_ONLY", "")           # debugging aid: "single" / "double" / "fwd" / "bwd" restricts the C entry points to that subset
+_TRANSPOSED_COPIES = os.environ.get("ST355_ATTN_BWD_T") == "1"      # A/B switch: keep the pre-transposed Q^T / K^T copies (dkv2 / dq kernels) at head_dim 128
 
 
 def _block_abi_ok() -> bool:
     return _BLOCK_ABI
-_TRANSPOSED_COPIES = __import__("os").environ.get("ST355_ATTN_BWD_T") == "1"      # A/B switch: keep the pre-transposed Q^T / K^T copies (dkv2 / dq kernels) at head_dim 128
 
 
-# ------------------------------------------------------------------------------------------------
-# helpers to register parameters under dotted (checkpoint) names
-# ------------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    pass
-
-
-def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
-    parts = dotted.split(".")
-    mod = root
-    for p in parts[:-1]:
-        if not hasattr(mod, p):
-            mod.add_module(p, _Holder())
-        mod = getattr(mod, p)
-    mod.register_parameter(parts[-1], param)
-
-
-def _frozen(t: torch.Tensor) -> nn.Parameter:
-    return nn.Parameter(t, requires_grad=False)
-
-
-class LoraGroup:
-    """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A x."""
-
-    def __init__(self, K: int, N_total: int, targets: List[Tuple[str, int, int]], rank: int, alpha: float, device):
-        self.K, self.N_total, self.targets = K, N_total, targets
-        self.rank, self.scale = rank, alpha / rank
-        # adapter columns inside the K-extension: 32 / 64 (one pass of the rank-space kernels), above 64 a multiple of 64 walked in 64-column slabs
-        # (the reference's sd3.peft-lora example trains rank 128)
-        self.r_pad = 32 if rank <= 32 else (rank + 63) // 64 * 64
-        self.K2 = (len(targets) * self.r_pad + 63) // 64 * 64
-        self.k2_real = len(targets) * rank          # adapter columns inside the padded extension (algorithmic-work accounting of the profiler)
-        z = lambda *s: torch.zeros(*s, dtype=BF16, device=device)
-        self.A_cat, self.A_cat_T = z(self.K2, K), z(K, self.K2)
-        self.B_blk, self.B_blk_T = z(N_total, self.K2), z(self.K2, N_total)
-        self.A: List[torch.Tensor] = []   # fp32 params (views into the flat arena), filled by the owner
-        self.B: List[torch.Tensor] = []
-        self.gA: List[torch.Tensor] = []  # fp32 grad views
-        self.gB: List[torch.Tensor] = []
-        self.flat_lo = self.flat_hi = 0   # this group's [lo, hi) element range inside the flat gradient arena
-
-    def pack(self):
-        for g, (_, n_off, _) in enumerate(self.targets):
-            ops.lora_pack(self.A[g], self.B[g], self.scale, self.A_cat, self.A_cat_T, self.B_blk, self.B_blk_T,
-                          k2_off=g * self.r_pad, n_off=n_off)
-
-    def grads(self, x, T, dy, U, accumulate: bool, sync=None):
-        """dB_g = s * dy_g^T T_g ; dA_g = U_g^T x   (rank-space backward: both products are [*, r]).  x: the projection's input, or — an input that only
-        exists as K segments (the single block's proj_out reads [attn | mlp] as a two-segment K loop) — a list of (segment, first input column)."""
-        segs = x if isinstance(x, (list, tuple)) else [(x, 0)]
-        multi = len(segs) == 1 and 1 < len(self.targets) <= 4 and self.r_pad == 32 and U.shape[1] >= 128   # q / k / v share x: dA of all three in ONE pass over x
-        cw = min(self.r_pad, 64)                                 # rank-space kernels take 32 or 64 adapter columns per pass
-        for g, (_, n_off, N) in enumerate(self.targets):
-            for s0 in range(0, self.rank, cw):
-                c0, r_used = g * self.r_pad + s0, min(cw, self.rank - s0)
-                ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], self.gB[g][:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=accumulate)
-                if not multi:
-                    for (xs, k0) in segs:
-                        ops.skinny_tn(xs, U[:, c0:c0 + cw], self.gA[g][s0:, k0:], 1, self.K, r_used, alpha=1.0, accumulate=accumulate)
-        if multi:
-            ops.skinny_tn_multi(x, U, self.gA, 1, self.K, self.rank, alpha=1.0, accumulate=accumulate)
-        if sync is not None:
-            sync.ready(self.flat_lo, self.flat_hi)
-
-
-class FluxTransformer2DModel(nn.Module):
+class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
     def __init__(self, patch_size: int = 1, in_channels: int = 64, num_layers: int = 19, num_single_layers: int = 38,
                  attention_head_dim: int = 128, num_attention_heads: int = 24, joint_attention_dim: int = 4096,
                  pooled_projection_dim: int = 768, guidance_embeds: bool = False, axes_dims_rope: Tuple[int, ...] = (16, 56, 56),
@@ -133,11 +71,7 @@ class FluxTransformer2DModel(nn.Module):
         # every weight / bias / norm weight / modulation row is a view of ONE bf16 arena (allocation order = arena order): full-rank training then has one
         # gradient arena of the same layout, ONE fused optimizer launch and contiguous slices for the gradient exchange (as in sd3/transformer.py).  Pass 1
         # counts on meta tensors, pass 2 hands out the views.  Every tensor of Flux.1 holds a multiple of 64 elements, so all views start 128-byte aligned.
-        self._arena_numel, self._counting = 0, True
-        self._build()
-        self.arena = torch.zeros(self._arena_numel, dtype=BF16, device=dev)
-        self._arena_numel, self._counting = 0, False
-        self._build()
+        self._build_arena(dev)
 
         self.lora_groups: List[LoraGroup] = []
         self.mod_lora: Optional[LoraGroup] = None          # 'ai-toolkit': adapters on every block's AdaLN modulation Linear (one group over the fused modulation GEMM)
@@ -159,20 +93,6 @@ class FluxTransformer2DModel(nn.Module):
         self._last_grad_flat = None
         self.full = False                # enable_full_finetune(): every base parameter trains
 
-    def _alloc(self, *shape):
-        n = 1
-        for d in shape:
-            n *= d
-        off = self._arena_numel
-        self._arena_numel += (n + 7) // 8 * 8               # every tensor starts 16-byte aligned inside the arena
-        if self._counting:
-            return torch.empty(*shape, dtype=BF16, device="meta")
-        return self.arena[off:off + n].view(*shape)
-
-    def _reg(self, name, param):
-        if not self._counting:
-            _attach(self, name, param)
-
     def _build(self):
         c = self.config
         D, dev, e = self.D, self.device_, self._alloc
@@ -182,7 +102,7 @@ class FluxTransformer2DModel(nn.Module):
         # ---- embedders ----
         def lin(name, out_f, in_f):
             w, b = e(out_f, in_f), e(out_f)
-            self._reg(name + ".weight", _frozen(w)); self._reg(name + ".bias", _frozen(b))
+            self._reg(name + ".weight", frozen(w)); self._reg(name + ".bias", frozen(b))
             return SimpleNamespace(w=w, b=b, wT=None, lora=None)
 
         self.l_x = lin("x_embedder", D, in_channels)
@@ -202,7 +122,7 @@ class FluxTransformer2DModel(nn.Module):
 
         def mod_slice(name, n):
             nonlocal off
-            self._reg(name + ".weight", _frozen(self.mod_w[off:off + n])); self._reg(name + ".bias", _frozen(self.mod_b[off:off + n]))
+            self._reg(name + ".weight", frozen(self.mod_w[off:off + n])); self._reg(name + ".bias", frozen(self.mod_b[off:off + n]))
             o = off
             off += n
             return o
@@ -211,15 +131,15 @@ class FluxTransformer2DModel(nn.Module):
             n = len(names)
             w, b = e(n * out_each, in_f), e(n * out_each)
             for j, nm in enumerate(names):
-                self._reg(f"{prefix}{nm}.weight", _frozen(w[j * out_each:(j + 1) * out_each]))
-                self._reg(f"{prefix}{nm}.bias", _frozen(b[j * out_each:(j + 1) * out_each]))
+                self._reg(f"{prefix}{nm}.weight", frozen(w[j * out_each:(j + 1) * out_each]))
+                self._reg(f"{prefix}{nm}.bias", frozen(b[j * out_each:(j + 1) * out_each]))
             return SimpleNamespace(w=w, b=b, wT=None, lora=None)
 
         def normw(name):
             w = e(self.hd)
             if not self._counting:
                 w.fill_(1.0)
-            self._reg(name + ".weight", _frozen(w))
+            self._reg(name + ".weight", frozen(w))
             return w
 
         self.double: List[SimpleNamespace] = []
@@ -259,32 +179,7 @@ class FluxTransformer2DModel(nn.Module):
     # ------------------------------------------------------------------------------------------------
     # weights
     # ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def load_flat_state(self, state: Dict[str, torch.Tensor]):
-        """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
-        own = dict(self.named_parameters())
-        missing = [k for k in own if k not in state and ".lora_" not in k]
-        if missing:
-            raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
-        for k, v in state.items():
-            if k in own:
-                own[k].data.copy_(v.to(device=own[k].device, dtype=own[k].dtype))
-        self._prepared = False
-        self._norm_w_ok.clear()
-
-    @torch.no_grad()
-    def init_synthetic(self, seed: int = 42):
-        """seed-deterministic random init on device, same distribution family as oracle.flux.init_params (benchmarks)."""
-        g = torch.Generator(device=self.device_).manual_seed(seed)
-        for name, p in self.named_parameters():
-            if ".lora_" in name:
-                continue
-            if "norm_q" in name or "norm_k" in name or "norm_added" in name:
-                p.data.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g, device=self.device_))
-            elif name.endswith(".bias"):
-                p.data.copy_(0.02 * torch.randn(p.shape, generator=g, device=self.device_))
-            else:
-                p.data.copy_(torch.randn(p.shape, generator=g, device=self.device_, dtype=BF16) * (1.0 / math.sqrt(p.shape[1])))
+    def _weights_changed(self):
         self._prepared = False
         self._norm_w_ok.clear()
 
@@ -409,13 +304,10 @@ class FluxTransformer2DModel(nn.Module):
             if init_b_std > 0:
                 b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
             pa, pb = nn.Parameter(a), nn.Parameter(b)
-            _attach(self, name + ".lora_A.default.weight", pa); _attach(self, name + ".lora_B.default.weight", pb)
+            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             self._lora_params += [pa, pb]
         return self._lora_params
-
-    def trainable_parameters(self):
-        return list(self._full_params) if self.full else list(self._lora_params)
 
     # ------------------------------------------------------------------------------------------------
     # rope tables (FluxPosEmbed, theta=1e4, float64 frequencies -> fp32 tables); cached per id layout
@@ -470,76 +362,6 @@ class FluxTransformer2DModel(nn.Module):
         if lin.lora is not None:
             lin.lora.grads(x, T, dy, U, self.accumulate_lora_grads, self.grad_sync)
         return dx
-
-    # ------------------------------------------------------------------------------------------------
-    # activation checkpointing (SURVEY.md §8(f)3; flux/transformer.py:816-835, 1142-1209, gradient_checkpointing_interval.py:51-120)
-    # ------------------------------------------------------------------------------------------------
-    def set_gradient_checkpointing_interval(self, value):
-        self.gradient_checkpointing_interval = None if value is None else int(value)
-
-    def set_gradient_checkpointing_segment_stride(self, segment_stride):
-        self.gradient_checkpointing_segment_stride = None if segment_stride is None else int(segment_stride)
-
-    def set_gradient_checkpointing_backend(self, backend: str):
-        if backend != "torch":      # "unsloth" = CPU-offloaded checkpoints (pointless with 288 GB), "*-ffn" = FFN-only scope: not built, never silently ignored
-            raise NotImplementedError(f"gradient_checkpointing_backend={backend!r} is not implemented on the st355 path (built: 'torch' = recompute)")
-        self.gradient_checkpointing_backend = backend
-
-    def enable_gradient_checkpointing(self, *a, **k):
-        self.gradient_checkpointing = True
-
-    def disable_gradient_checkpointing(self):
-        self.gradient_checkpointing = False
-
-    def _checkpoint_segments(self, n_blocks: int):
-        """[(first block, block count, recompute?)] over one block stack, the reference's three modes:
-             gradient_checkpointing off                  -> every block keeps its activations;
-             on, interval None / <= 1  ("layer")         -> every block is its own checkpoint (only its input is kept, the block is re-run in backward);
-             on, interval k > 1 [, segment_stride s >= k] -> the first k blocks of every s-block window form ONE checkpoint (only the segment input is
-                                                            kept), the s - k blocks of the gap keep their activations  (`checkpoint_sequential_state`)."""
-        from ..training.checkpoint_plan import segments
-        return segments(n_blocks, self.gradient_checkpointing, self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride)
-
-    # ------------------------------------------------------------------------------------------------
-    # forward / backward engines
-    # ------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _rows_of(joint, lo: int, rows: int, env):
-        """rows [lo, lo + rows) of every sample of a joint [B * S, C] buffer, as a GEMM / skinny operand: a [B, rows, C] strided view (no copy)"""
-        return joint.view(env.B, env.S, -1)[:, lo:lo + rows]
-
-    @staticmethod
-    def _problems(env, rows: int, pr: dict):
-        """One projection over the `rows`-row block of every sample.  Operands may be compact [B * rows, C] tensors or [B, rows, C] views of joint
-        buffers (_rows_of).  When the blocks are tile-aligned (rows % 256 == 0) that is ONE segmented problem (st355_gemm_args.seg_rows: one grid of
-        B * rows / 256 row tiles instead of B launches that each fill the 256 CUs badly); otherwise one problem per sample, as before."""
-        B = env.B
-        ROWED = ("a", "a2", "out", "aux_in", "aux_out")
-        if B == 1:
-            return [{k: (v[0] if k in ROWED and torch.is_tensor(v) and v.dim() == 3 else v) for k, v in pr.items()}]
-        if rows % 256 == 0:
-            return [pr]
-        out = []
-        for b in range(B):
-            q = {}
-            for k, v in pr.items():
-                if k in ROWED and torch.is_tensor(v):
-                    q[k] = v[b] if v.dim() == 3 else v[b * rows:(b + 1) * rows]
-                elif k == "gate":          # one gate row per sample, or — tokenwise timesteps — one per token row of this stream
-                    q[k] = v[b:b + 1] if v.shape[0] == B else v[b * rows:(b + 1) * rows]
-                else:
-                    q[k] = v
-            out.append(q)
-        return out
-
-    @staticmethod
-    def _compact(t, env, rows: int):
-        """a [B, rows, C] view as an operand of the rank-space gradient kernels: as is when they can walk it segmented, else a compact copy"""
-        if t.dim() != 3:
-            return t
-        if env.B == 1:
-            return t[0]
-        return t if rows % 256 == 0 else t.reshape(env.B * rows, -1)
 
     def _fused_qkv_ok(self, rows_list, norms) -> bool:
         """May this attention's input projection run with RMSNorm + RoPE + the head-major re-layout fused into the GEMM epilogue (ST355_EPI_QK_NORM_ROPE,
@@ -653,10 +475,10 @@ class FluxTransformer2DModel(nn.Module):
             Q = torch.empty(B, H, S, hd, dtype=BF16, device=dev); K = torch.empty_like(Q)
             V = torch.empty(B * S, D, dtype=BF16, device=dev); rrms = torch.empty(B * S, 2 * H, dtype=F32, device=dev)
             Vt = torch.empty(B, H, hd, S, dtype=BF16, device=dev) if _FUSED_VT else None      # (S is a multiple of 256 here: no padded columns)
-            ops.gemm_grouped(self._problems(env, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=self._rows_of(V, St, Si, env), epilogue=EPI_QK_NORM_ROPE,
+            ops.gemm_grouped(problems(B, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=rows_of(V, St, Si, B, S), epilogue=EPI_QK_NORM_ROPE,
                                                           rope=ops.qk_rope(Q, K, rrms, blk.norm_q, blk.norm_k, env.cos_p, env.sin_p, H, S, St, Vt=Vt),
                                                           rows_per_batch=Si, **kw_i))
-                             + self._problems(env, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=self._rows_of(V, 0, St, env),
+                             + problems(B, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=rows_of(V, 0, St, B, S),
                                                             epilogue=EPI_QK_NORM_ROPE, rows_per_batch=St,
                                                             rope=ops.qk_rope(Q, K, rrms, blk.norm_added_q, blk.norm_added_k, env.cos_p, env.sin_p, H, S, 0, Vt=Vt),
                                                             **kw_t)))
@@ -665,8 +487,8 @@ class FluxTransformer2DModel(nn.Module):
         else:
             qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
             # both streams project into the joint [txt || img] rows of qkv (flux/transformer.py:171-190 concatenates q, k, v of the two streams)
-            ops.gemm_grouped(self._problems(env, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=self._rows_of(qkv, St, Si, env), **kw_i))
-                             + self._problems(env, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=self._rows_of(qkv, 0, St, env), **kw_t)))
+            ops.gemm_grouped(problems(B, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=rows_of(qkv, St, Si, B, S), **kw_i))
+                             + problems(B, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=rows_of(qkv, 0, St, B, S), **kw_t)))
             Q, K, Qt, Kt, Vt = self._alloc_heads(env)
             self._qk_fwd(env, qkv, blk.norm_added_q, blk.norm_added_k, Q, K, Qt, Kt, Vt, St, 0)
             self._qk_fwd(env, qkv, blk.norm_q, blk.norm_k, Q, K, Qt, Kt, Vt, Si, St)
@@ -675,7 +497,7 @@ class FluxTransformer2DModel(nn.Module):
         x1_img = torch.empty(B * Si, D, dtype=BF16, device=dev); x1_txt = torch.empty(B * St, D, dtype=BF16, device=dev)
         T_o = torch.empty(B * Si, blk.to_out.lora.K2, dtype=BF16, device=dev) if blk.to_out.lora is not None else None
         T_ao = torch.empty(B * St, blk.to_add_out.lora.K2, dtype=BF16, device=dev) if blk.to_add_out.lora is not None else None
-        O_i, O_t = self._rows_of(O, St, Si, env), self._rows_of(O, 0, St, env)       # the attention output is split back by rows, in place
+        O_i, O_t = rows_of(O, St, Si, B, S), rows_of(O, 0, St, B, S)       # the attention output is split back by rows, in place
         kw_i, kw_t = {}, {}
         ya_i = ya_t = yf_i = yf_t = None
         if keep_y:                   # the un-gated branch outputs (gate gradients: d gate = sum_rows dOut * y)
@@ -683,16 +505,16 @@ class FluxTransformer2DModel(nn.Module):
             ya_t, yf_t = (torch.empty(B * St, D, dtype=BF16, device=dev) for _ in range(2))
             kw_i["aux_out"], kw_t["aux_out"] = ya_i, ya_t
         if T_o is not None:
-            for pr in self._problems(env, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o)):
+            for pr in problems(B, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o)):
                 ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
             kw_i.update(a2=T_o, b2=blk.to_out.lora.B_blk, k2_real=blk.to_out.lora.k2_real)
         if T_ao is not None:
-            for pr in self._problems(env, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao)):
+            for pr in problems(B, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao)):
                 ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
             kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_blk, k2_real=blk.to_add_out.lora.k2_real)
-        ops.gemm_grouped(self._problems(env, Si, dict(a=O_i, w=blk.to_out.w, bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
+        ops.gemm_grouped(problems(B, Si, dict(a=O_i, w=blk.to_out.w, bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
                                                       gate=mi[:, 2 * D:3 * D], rows_per_batch=rpi, **kw_i))
-                         + self._problems(env, St, dict(a=O_t, w=blk.to_add_out.w, bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
+                         + problems(B, St, dict(a=O_t, w=blk.to_add_out.w, bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
                                                         aux_in=txt, gate=mt[:, 2 * D:3 * D], rows_per_batch=St, **kw_t)))
         # MLPs
         n2_i = ops.ln_modulate_fwd(x1_img, mi[:, 4 * D:5 * D], mi[:, 3 * D:4 * D], rpi)
@@ -714,10 +536,10 @@ class FluxTransformer2DModel(nn.Module):
             # the last double block's MLP down-projections write the joint [txt || img] sequence of the single blocks in place
             # (flux/transformer.py:1332 `torch.cat`): one problem per (stream, sample), no concat pass
             x = torch.empty(B * S, D, dtype=BF16, device=dev)
-            ops.gemm_grouped(self._problems(env, Si, dict(a=h_i, w=blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img,
-                                                          gate=mi[:, 5 * D:6 * D], rows_per_batch=rpi, out=self._rows_of(x, St, Si, env), **kf_i))
-                             + self._problems(env, St, dict(a=h_t, w=blk.ffc2.w, bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt,
-                                                            gate=mt[:, 5 * D:6 * D], rows_per_batch=St, out=self._rows_of(x, 0, St, env), **kf_t)))
+            ops.gemm_grouped(problems(B, Si, dict(a=h_i, w=blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img,
+                                                          gate=mi[:, 5 * D:6 * D], rows_per_batch=rpi, out=rows_of(x, St, Si, B, S), **kf_i))
+                             + problems(B, St, dict(a=h_t, w=blk.ffc2.w, bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt,
+                                                            gate=mt[:, 5 * D:6 * D], rows_per_batch=St, out=rows_of(x, 0, St, B, S), **kf_t)))
         else:
             x2_img, x2_txt = ops.gemm_grouped([
                 dict(a=h_i, w=blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D], rows_per_batch=rpi, **kf_i),
@@ -1026,13 +848,6 @@ class FluxTransformer2DModel(nn.Module):
         else:
             ops.qk_norm_rope_bwd(dQ, dK, sv.qkv, wq, wk, env.cos, env.sin, dqkv, B, H, hd, rows, pos0, S)
 
-    def _mod_grads(self, dn, x_in, rows: int, k_shift: int, k_scale: int, dm):
-        """d shift = sum_rows dY, d scale = sum_rows dY * LN(x) of one AdaLN instance, per sample, into chunks k_shift / k_scale of its slice `dm` of the modulation-row
-        gradient (the reductions of the full-rank engine's `mod_grads`; here for adapters on the modulation Linears under a frozen base)"""
-        D = self.D
-        ops.colsum_prod(dn, dm[:, k_shift * D:(k_shift + 1) * D], rows_per_batch=rows)
-        ops.colsum_prod(dn, dm[:, k_scale * D:(k_scale + 1) * D], b=ops.layer_norm_xhat(x_in), rows_per_batch=rows)
-
     def _single_bwd(self, li: int, sv, dx, dxg, env):
         """backward of single block li.  Returns (dx, dxg, d_txt, d_img): block 0 of a model with double blocks writes its input gradient — the joint
         gradient of the double stack — per (stream, sample) straight into the two stream-major buffers (no split / gather pass)."""
@@ -1093,7 +908,7 @@ class FluxTransformer2DModel(nn.Module):
         del dO
         dn = self._lin_bwd(blk.qkv, dqkv, x=sv.n, T=sv.T, epilogue=EPI_ADD, aux_in=dn_mlp)
         if dm is not None:
-            self._mod_grads(dn, sv.x, S, 0, 1, dm)
+            mod_grads(D, dn, sv.x, S, 0, 1, dm)
         d_txt = d_img = None
         if li > 0:
             gprev = msl(li - 1)[:, 2 * D:3 * D]
@@ -1177,7 +992,7 @@ class FluxTransformer2DModel(nn.Module):
             del U_f2, U_c2, U_f1, U_c1
         del g_i, g_t, dh_i, dh_t
         if dmi is not None:
-            self._mod_grads(dn2_i, sv.x1_img, Si, 3, 4, dmi); self._mod_grads(dn2_t, sv.x1_txt, St, 3, 4, dmt)
+            mod_grads(D, dn2_i, sv.x1_img, Si, 3, 4, dmi); mod_grads(D, dn2_t, sv.x1_txt, St, 3, 4, dmt)
         dx1_i, dx1g_i = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], rpi, dres=d_img, gate=mi[:, 2 * D:3 * D], want_gated=True)
         dx1_t, dx1g_t = ops.ln_modulate_bwd(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dres=d_txt, gate=mt[:, 2 * D:3 * D], want_gated=True)
         del dn2_i, dn2_t
@@ -1190,18 +1005,18 @@ class FluxTransformer2DModel(nn.Module):
         U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_blk_T) if blk.to_add_out.lora is not None else None
         kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T, k2_real=blk.to_out.lora.k2_real) if U_i is not None else {}
         kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T, k2_real=blk.to_add_out.lora.k2_real) if U_t is not None else {}
-        ops.gemm_grouped(self._problems(env, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=self._rows_of(dO, St, Si, env), **kw_i))
-                         + self._problems(env, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=self._rows_of(dO, 0, St, env), **kw_t)))
+        ops.gemm_grouped(problems(B, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, St, Si, B, S), **kw_i))
+                         + problems(B, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, 0, St, B, S), **kw_t)))
         for (lin, U, T_, dxg, lo, rows) in ((blk.to_out, U_i, sv.T_o, dx1g_i, St, Si), (blk.to_add_out, U_t, sv.T_ao, dx1g_t, 0, St)):
             if lin.lora is not None:       # dA = U^T O over this stream's rows of the joint attention output, read in place
-                lin.lora.grads(self._compact(self._rows_of(sv.O, lo, rows, env), env, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
+                lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
         del dx1g_i, dx1g_t, U_i, U_t
         dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
         self._attn_rope_backward(sv, dO, dqkv, env, (blk.norm_added_q, blk.norm_added_k), (blk.norm_q, blk.norm_k), St)
         del dO
         last = li == 0 and self.l_x.lora is None and dmi is None      # (an adapter on x_embedder needs the image stream's input gradient of block 0; the modulation adapters d n of both streams)
         # the two streams' rows of the joint dqkv, in place (the reference's autograd splits the concatenated gradient the same way)
-        dq_i, dq_t = self._rows_of(dqkv, St, Si, env), self._rows_of(dqkv, 0, St, env)
+        dq_i, dq_t = rows_of(dqkv, St, Si, B, S), rows_of(dqkv, 0, St, B, S)
         streams = [("img", blk.qkv, dq_i, sv.n_img, sv.T_img, Si), ("txt", blk.add_qkv, dq_t, sv.n_txt, sv.T_txt, St)]
         if last:
             streams = [s_ for s_ in streams if s_[1].lora is not None]   # frozen embedders: only adapter grads remain to compute
@@ -1210,21 +1025,21 @@ class FluxTransformer2DModel(nn.Module):
             kw = {}
             if lin.lora is not None:
                 Us[name] = torch.empty(B * rows, lin.lora.B_blk_T.shape[0], dtype=BF16, device=dev)
-                for pr in self._problems(env, rows, dict(a=dq, w=lin.lora.B_blk_T, out=Us[name])):
+                for pr in problems(B, rows, dict(a=dq, w=lin.lora.B_blk_T, out=Us[name])):
                     ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
                 kw = dict(a2=Us[name], b2=lin.lora.A_cat_T, k2_real=lin.lora.k2_real)
             if not last:
                 dns.append(torch.empty(B * rows, D, dtype=BF16, device=dev))
-                probs += self._problems(env, rows, dict(a=dq, w=lin.wT, out=dns[-1], **kw))
+                probs += problems(B, rows, dict(a=dq, w=lin.wT, out=dns[-1], **kw))
         if probs:
             ops.gemm_grouped(probs)
         for (name, lin, dq, n_in, T_, rows) in streams:
             if lin.lora is not None:
-                lin.lora.grads(n_in, T_, self._compact(dq, env, rows), Us[name], self.accumulate_lora_grads, self.grad_sync)
+                lin.lora.grads(n_in, T_, compact(dq, B, rows), Us[name], self.accumulate_lora_grads, self.grad_sync)
         if last:
             return None, None
         if dmi is not None:
-            self._mod_grads(dns[0], sv.img, Si, 0, 1, dmi); self._mod_grads(dns[1], sv.txt, St, 0, 1, dmt)
+            mod_grads(D, dns[0], sv.img, Si, 0, 1, dmi); mod_grads(D, dns[1], sv.txt, St, 0, 1, dmt)
         d_img, _ = ops.ln_modulate_bwd(dns[0], sv.img, mi[:, D:2 * D], rpi, dres=dx1_i)
         d_txt, _ = ops.ln_modulate_bwd(dns[1], sv.txt, mt[:, D:2 * D], St, dres=dx1_t)
         return d_img, d_txt
@@ -1367,19 +1182,6 @@ class FluxTransformer2DModel(nn.Module):
         self.prepare_for_training()
         return ps
 
-    def _refresh_transposed(self):
-        """W^T follows the weights (2 B read + 2 B write per parameter per step: ~12 ms for Flux.1-dev's 12 B parameters)"""
-        for l in self._all_linears():
-            if getattr(l, "wT", None) is not None:
-                ops.transpose(l.w, out=l.wT)
-
-    def diffusers_state_dict(self) -> Dict[str, torch.Tensor]:
-        """{diffusers checkpoint key: tensor} of the base parameters (the parameter names ARE the checkpoint keys): what `save_pretrained` writes"""
-        return {k: v.detach() for k, v in self.named_parameters() if ".lora_" not in k}
-
-    def load_diffusers_state(self, state: Dict[str, torch.Tensor]):
-        self.load_flat_state(state)
-
     def _single_bwd_full(self, li: int, sv, dx, env, fb):
         """backward of single block li with every parameter gradient; returns the gradient of the block's input (joint [txt || img] rows)"""
         D, H, hd, dev = self.D, self.H, self.hd, self.device_
@@ -1389,9 +1191,9 @@ class FluxTransformer2DModel(nn.Module):
         ops.colsum_prod(dx, dms[:, 2 * D:3 * D], b=sv.y, rows_per_batch=S)                         # d gate
         g = ops.scale_cols(dx, ms[:, 2 * D:3 * D], S)
         # proj_out reads [attention output | MLP activation] as two K segments: its weight gradient is written as the two column blocks
-        gp = fb.P64(g)
-        ops.gemm_tn(gp, fb.P64(sv.O), out=blk.proj_out.gw[:, :D])
-        ops.gemm_tn(gp, fb.P64(sv.hact), out=blk.proj_out.gw[:, D:])
+        gp = pad64(g)
+        ops.gemm_tn(gp, pad64(sv.O), out=blk.proj_out.gw[:, :D])
+        ops.gemm_tn(gp, pad64(sv.hact), out=blk.proj_out.gw[:, D:])
         fb.bgrad(blk.proj_out, g)
         dO = ops.gemm(g, blk.proj_out.wT[:D])
         dhpre = ops.gemm(g, blk.proj_out.wT[D:], epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre)
@@ -1436,8 +1238,8 @@ class FluxTransformer2DModel(nn.Module):
         # ---- attention output projections (joint order [txt || img]) ----
         fb.wgrad(blk.to_out, dx1g_i, rows(sv.O, St, Si)); fb.wgrad(blk.to_add_out, dx1g_t, rows(sv.O, 0, St))
         dO = torch.empty(B * S, D, dtype=BF16, device=dev)
-        ops.gemm_grouped(self._problems(env, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=self._rows_of(dO, St, Si, env)))
-                         + self._problems(env, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=self._rows_of(dO, 0, St, env))))
+        ops.gemm_grouped(problems(B, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, St, Si, B, S)))
+                         + problems(B, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, 0, St, B, S))))
         del dx1g_i, dx1g_t
         # ---- attention, RoPE / RMSNorm (+ norm weight gradients) ----
         dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
@@ -1461,49 +1263,20 @@ class FluxTransformer2DModel(nn.Module):
         env = ctx.env
         B, Si, St, S, mod = env.B, env.Si, env.St, env.S, env.mod
         self._refresh_transposed()
-        fb = SimpleNamespace(dmod=torch.zeros(B, self.mod_total, dtype=F32, device=dev))        # d loss / d (modulation linear output)
-        tmp_b = {}
-
-        def P64(t):
-            """zero-padded copy with a multiple of 64 rows (the TN GEMM's contraction granule); no copy when already aligned"""
-            r = t.shape[0]
-            if r % 64 == 0 and t.is_contiguous():
-                return t
-            o = torch.zeros((r + 63) // 64 * 64, t.shape[1], dtype=BF16, device=dev)
-            o[:r] = t
-            return o
-
-        def bgrad(lin, dy):
-            N = dy.shape[1]
-            t = tmp_b.get(N)
-            if t is None:
-                t = tmp_b[N] = torch.empty(1, N, dtype=F32, device=dev)
-            ops.colsum_prod(dy, t)
-            lin.gb.copy_(t[0])
-
-        def wgrad(lin, dy, x):
-            """dW = dY^T X ; db = colsum(dY)   (into the gradient arena views of `lin`)"""
-            ops.gemm_tn(P64(dy), P64(x), out=lin.gw)
-            bgrad(lin, dy)
-
-        def mod_grads(dn, x_in, rows, k_shift, k_scale, dm, xhat=None):
-            """d shift = sum_t dY, d scale = sum_t dY * LN(x) of one AdaLN instance (chunk indices k_* inside its slice dm of the modulation gradient);
-            x_in = the LayerNorm's input (or xhat = LN(x) when the caller already has it)"""
-            ops.colsum_prod(dn, dm[:, k_shift * D:(k_shift + 1) * D], rows_per_batch=rows)
-            ops.colsum_prod(dn, dm[:, k_scale * D:(k_scale + 1) * D], b=ops.layer_norm_xhat(x_in) if xhat is None else xhat, rows_per_batch=rows)
-
-        fb.P64, fb.bgrad, fb.wgrad, fb.mod_grads = P64, bgrad, wgrad, mod_grads
         sync = self.grad_sync
+        # arena offset below which the fused modulation matrix must lie for its gradient rows to be handed over block by block
+        front_hi = self.double[0].arena_lo if self.double else (self.single[0].arena_lo if self.single else self._head_arena_lo)
+        fb = FullGrads(self, B, dev, sync, front_hi, ctx.emb.st)
         # ---- output head (AdaLayerNormContinuous: chunk order (scale, shift)) ----
         dout = dout.reshape(B * Si, -1).to(BF16).contiguous()
         mo = mod[:, self.mod_off_out:self.mod_off_out + 2 * D]
         dmo = fb.dmod[:, self.mod_off_out:self.mod_off_out + 2 * D]
-        wgrad(self.l_out, dout, ctx.n_out)
+        fb.wgrad(self.l_out, dout, ctx.n_out)
         dn = ops.gemm(dout, self.l_out.wT)
         xhat = torch.empty(B * Si, D, dtype=BF16, device=dev)
         for b in range(B):          # LN of the image rows of the joint sequence (strided per-sample views)
             ops.layer_norm_xhat(ctx.x_final[b * S + St:(b + 1) * S], out=xhat[b * Si:(b + 1) * Si])
-        mod_grads(dn, None, Si, 1, 0, dmo, xhat=xhat)
+        fb.mod_grads(dn, None, Si, 1, 0, dmo, xhat=xhat)
         del xhat
         dx = torch.zeros(B * S, D, dtype=BF16, device=dev)      # the txt rows of the last single block get no gradient
         for b in range(B):
@@ -1512,29 +1285,8 @@ class FluxTransformer2DModel(nn.Module):
         ctx.x_final = ctx.n_out = None
         if sync is not None:
             sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
-        # The fused modulation matrix (every block's adaLN Linear as rows of ONE [mod_total, D] matrix: 3.2 B of Flux.1-dev's 11.9 B parameters, 6.5 GB of gradient)
-        # gets its gradient rows block by block (r6): dW_mod[r0:r1] = dmod[:, r0:r1]^T silu(temb) as soon as the block that owns rows [r0, r1) has run, so that
-        # the exchange takes them behind the backward instead of as one exposed region after it.  Same arithmetic per row (one 64-deep contraction over the
-        # zero-padded batch): bit-equal to the one-product form.
-        Bp = (B + 63) // 64 * 64
-        st_p = torch.zeros(Bp, D, dtype=BF16, device=dev); st_p[:B] = ctx.emb.st
-        mw_lo = (self.mod_w.data_ptr() - self.arena.data_ptr()) // 2
-        mw_hi = mw_lo + self.mod_total * D
-        front_hi = self.double[0].arena_lo if self.double else (self.single[0].arena_lo if self.single else self._head_arena_lo)
-        mod_in_front = 0 <= mw_lo and mw_hi <= front_hi
-        mod_rows_lo = [self.mod_total]                    # rows [mod_rows_lo, mod_total) of dW_mod are written (and handed over)
-
-        def mod_rows_grad(r0):
-            r1 = mod_rows_lo[0]
-            if r1 <= r0:
-                return
-            dp = torch.zeros(Bp, r1 - r0, dtype=BF16, device=dev); dp[:B] = fb.dmod[:, r0:r1]
-            ops.gemm_tn(dp, st_p, out=self.g_mod_w[r0:r1])
-            mod_rows_lo[0] = r0
-            if sync is not None and mod_in_front:
-                sync.ready(mw_lo + r0 * D, mw_lo + r1 * D)
-
-        mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
+        # the fused modulation matrix (3.2 B of Flux.1-dev's 11.9 B parameters, 6.5 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
+        fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
         # ---- single blocks, reversed ----
         for (s0, n, ck) in reversed(ctx.segs_s):
             if ck:
@@ -1546,7 +1298,7 @@ class FluxTransformer2DModel(nn.Module):
                 dx = self._single_bwd_full(li, ctx.sgl.pop(li), dx, ctx.env_s[li], fb)
                 if sync is not None:
                     sync.ready(self.single[li].arena_lo, self.single[li].arena_hi)
-                mod_rows_grad(self.single[li].mod_off)
+                fb.mod_rows_grad(self.single[li].mod_off)
         # ---- split the joint gradient [txt || img] ----
         dxv = dx.view(B, S, D)
         d_txt, d_img = dxv[:, :St].reshape(B * St, D), dxv[:, St:].reshape(B * Si, D)
@@ -1562,49 +1314,17 @@ class FluxTransformer2DModel(nn.Module):
                 d_img, d_txt = self._double_bwd_full(li, ctx.dbl.pop(li), d_img, d_txt, ctx.env_d[li], fb)
                 if sync is not None:
                     sync.ready(self.double[li].arena_lo, self.double[li].arena_hi)
-                mod_rows_grad(self.double[li].mod_off)
+                fb.mod_rows_grad(self.double[li].mod_off)
         # ---- embedders ----
         em = ctx.emb
-        wgrad(self.l_x, d_img, em.x2d)
-        wgrad(self.l_ctx, d_txt, em.enc2d)
-        # modulation linear: mod = silu(temb) W_mod^T + b
-        dmod_p = torch.zeros(Bp, self.mod_total, dtype=BF16, device=dev); dmod_p[:B] = fb.dmod
-        mod_rows_grad(0)                                                    # whatever rows are left (none when the model has blocks: the last block handed over row 0)
-        tb = torch.empty(1, self.mod_total, dtype=F32, device=dev)
-        ops.colsum_prod(dmod_p, tb)
-        self.g_mod_b.copy_(tb[0])
-        # d silu(temb) = dmod @ W_mod -> [B, D], as (W_mod^T dmod^T)^T with the TN GEMM.  The contraction runs over the mod_total rows of W_mod (1.06 M for
-        # Flux.1-dev): walked in row blocks that stay inside the TN GEMM's 2 GiB operand window, accumulated into one [D, B8] output
-        B8 = 8 * ((B + 7) // 8)
-        dmod_t = ops.transpose(dmod_p[:B8])                                   # [mod_total, B8]
-        blk_rows = max(64, (getattr(self, "_tn_window_bytes", (1 << 31) - 1) // (2 * max(D, B8))) // 64 * 64)        # (attribute: tests shrink the window)
-        acc = torch.empty(D, B8, dtype=BF16, device=dev)
-        for i, r0 in enumerate(range(0, self.mod_total, blk_rows)):
-            r1 = min(self.mod_total, r0 + blk_rows)
-            ops.gemm_tn(self.mod_w[r0:r1], dmod_t[r0:r1], out=acc, accumulate=i > 0)
-        dst = ops.transpose(acc)[:B].contiguous()
-        dtemb = ops.silu_bwd(em.temb, dst)
-
-        def mlp_bwd(l1, l2, x_in, pre1, act1, dy):
-            """TimestepEmbedding / guidance / pooled-text projection: y = l2(silu(l1(x)))"""
-            pad = lambda t: torch.cat([t, torch.zeros(Bp - B, t.shape[1], dtype=BF16, device=dev)], dim=0)
-            dyp = pad(dy)
-            ops.gemm_tn(dyp, pad(act1), out=l2.gw)
-            bgrad(l2, dyp)
-            d1p = pad(ops.silu_bwd(pre1, ops.gemm(dy, l2.wT)))
-            ops.gemm_tn(d1p, pad(x_in), out=l1.gw)
-            bgrad(l1, d1p)
-
-        mlp_bwd(self.l_t1, self.l_t2, em.tproj, em.t1, em.st1, dtemb)
+        fb.wgrad(self.l_x, d_img, em.x2d)
+        fb.wgrad(self.l_ctx, d_txt, em.enc2d)
+        dtemb = fb.mod_linear_bwd(em.temb)          # (whatever modulation rows are left: none when the model has blocks, the last block handed over row 0)
+        fb.mlp_bwd(self.l_t1, self.l_t2, em.tproj, em.t1, em.st1, dtemb)
         if self.config.guidance_embeds:
-            mlp_bwd(self.l_g1, self.l_g2, em.gproj, em.g1, em.sg1, dtemb)
-        mlp_bwd(self.l_p1, self.l_p2, em.pooled, em.p1, em.sp1, dtemb)
-        if sync is not None:
-            if mod_in_front:                                                   # embedders + the modulation bias: what lies around the modulation matrix's rows
-                sync.ready(mw_hi, front_hi)
-                sync.ready(0, mw_lo)
-            else:
-                sync.ready(0, front_hi)                                        # embedders + the modulation matrix
+            fb.mlp_bwd(self.l_g1, self.l_g2, em.gproj, em.g1, em.sg1, dtemb)
+        fb.mlp_bwd(self.l_p1, self.l_p2, em.pooled, em.p1, em.sp1, dtemb)
+        fb.ready_front(front_hi)                    # embedders + the modulation bias (+ the modulation matrix when it was not handed over by rows)
         return None
 
     # ------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ head_dim 96 (192-byte LDS rows with a 2-bit XOR swizzle) with scale 1/sqrt(72): 
 from __future__ import annotations
 
 import math
+import os
 from types import SimpleNamespace
 from typing import Dict, List, Optional
 
@@ -22,38 +23,14 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..flux.transformer import LoraGroup, _attach, _frozen
+from ..engine import LoraGroup, attach, frozen, mod_grads, pad64, sincos_2d_hw
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-_BLOCK_ABI = __import__("os").environ.get("ST355_BLOCK_ABI", "1") != "0"      # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_pixart_*
+_BLOCK_ABI = os.environ.get("ST355_BLOCK_ABI", "1") != "0"      # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_pixart_*
 HP = 96           # padded head width (72 -> 96: three 32-row MFMA tiles; was 128 before the head_dim-96 kernels existed)
-
-
-def sincos_2d_hw(embed_dim: int, h: int, w: int, base_size: int, interpolation_scale: float) -> torch.Tensor:
-    """diffusers get_2d_sincos_pos_embed on a (h, w) grid (first half from the w coordinate; sin then cos)"""
-    gh = (torch.arange(h, dtype=torch.float32) / (h / base_size) / interpolation_scale).double()
-    gw = (torch.arange(w, dtype=torch.float32) / (w / base_size) / interpolation_scale).double()
-    cw = gw[None, :].expand(h, w).reshape(-1)
-    chh = gh[:, None].expand(h, w).reshape(-1)
-
-    def one_d(dim, pos):
-        omega = 1.0 / 10000 ** (torch.arange(dim // 2, dtype=torch.float64) / (dim / 2.0))
-        out = pos[:, None] * omega[None, :]
-        return torch.cat([out.sin(), out.cos()], dim=1)
-
-    return torch.cat([one_d(embed_dim // 2, cw), one_d(embed_dim // 2, chh)], dim=1).float()
-
-
-def _p64(t):
-    r = t.shape[0]
-    if r % 64 == 0 and t.is_contiguous():
-        return t
-    o = torch.zeros((r + 63) // 64 * 64, t.shape[1], dtype=BF16, device=t.device)
-    o[:r] = t
-    return o
 
 
 class _Block:
@@ -145,7 +122,7 @@ class PixArtTransformer2DModel(nn.Module):
 
         def alloc(name, shape):
             t = torch.zeros(*shape, dtype=BF16, device=dev)
-            _attach(self, name, _frozen(t))
+            attach(self, name, frozen(t))
             return t
 
         self.P = {}
@@ -224,7 +201,7 @@ class PixArtTransformer2DModel(nn.Module):
                 if N == Dp:
                     b[pad_rows] = 0
             pa, pb = nn.Parameter(a), nn.Parameter(b)
-            _attach(self, name + ".lora_A.default.weight", pa); _attach(self, name + ".lora_B.default.weight", pb)
+            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             self._lora_params += [pa, pb]
         return self._lora_params
@@ -498,7 +475,7 @@ class PixArtTransformer2DModel(nn.Module):
         def wgrad(name, dy, x, unpad):
             if not tr:
                 return
-            gw = ops.gemm_tn(_p64(dy), _p64(x))
+            gw = ops.gemm_tn(pad64(dy), pad64(x))
             tb = torch.empty(1, dy.shape[1], dtype=F32, device=dy.device)
             ops.colsum_prod(dy, tb)
             unpad(gw, tb[0])
@@ -522,13 +499,6 @@ class PixArtTransformer2DModel(nn.Module):
             def f(gw, gb):
                 blk.G[nm + ".weight"].copy_(gw); blk.G[nm + ".bias"].copy_(gb)
             return f
-
-        def mod_grads(dn, x_in, k_shift, k_scale):
-            """d shift = sum_t dY, d scale = sum_t dY * LN(x); x_in = the LayerNorm's input (LN(x) recomputed: no division by 1 + scale)"""
-            if not tr:
-                return
-            ops.colsum_prod(dn, dmod[:, k_shift * D:(k_shift + 1) * D], rows_per_batch=S)
-            ops.colsum_prod(dn, dmod[:, k_scale * D:(k_scale + 1) * D], b=ops.layer_norm_xhat(x_in), rows_per_batch=S)
 
         L = blk.lora
         acc, sync = self.accumulate_lora_grads, self.grad_sync
@@ -561,14 +531,14 @@ class PixArtTransformer2DModel(nn.Module):
                 ops.colsum_prod(d3, dmod[:, 5 * D:6 * D], b=sv.yf, rows_per_batch=S)
                 wgrad("ff2", dyf, sv.a, plain("ff.net.2"))
                 wgrad("ff1", dpre, sv.n2, plain("ff.net.0.proj"))
-                mod_grads(dn2, sv.h2, 3, 4)
+                mod_grads(D, dn2, sv.h2, S, 3, 4, dmod)
                 wgrad("out2", d2, sv.O2, unpad_cols("attn2.to_out.0"))
                 wgrad("q2", dq2, sv.h1, unpad_rows(["attn2.to_q"]))
                 wgrad("kv2", dkv, ctx2d, unpad_rows(["attn2.to_k", "attn2.to_v"]))
                 ops.colsum_prod(d1, dmod[:, 2 * D:3 * D], b=sv.ya, rows_per_batch=S)
                 wgrad("out1", dya, sv.O, unpad_cols("attn1.to_out.0"))
                 wgrad("qkv", dqkv, sv.n1, unpad_rows(["attn1.to_q", "attn1.to_k", "attn1.to_v"]))
-                mod_grads(dn1, sv.h, 0, 1)
+                mod_grads(D, dn1, sv.h, S, 0, 1, dmod)
                 blk.G["scale_shift_table"].copy_(dmod.sum(0).view(6, D))
             return d0
         # ---- feed-forward ----
@@ -579,7 +549,8 @@ class PixArtTransformer2DModel(nn.Module):
         dpre = ops.gemm(dyf, W.ff2_wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.pre)
         wgrad("ff1", dpre, sv.n2, plain("ff.net.0.proj"))
         dn2 = ops.gemm(dpre, W.ff1_wT)
-        mod_grads(dn2, sv.h2, 3, 4)
+        if tr:
+            mod_grads(D, dn2, sv.h2, S, 3, 4, dmod)
         d2, _ = ops.ln_modulate_bwd(dn2, sv.h2, m[4], S, dres=d3)
         # ---- cross-attention (no pre-norm, no gate) ----
         wgrad("out2", d2, sv.O2, unpad_cols("attn2.to_out.0"))
@@ -608,7 +579,8 @@ class PixArtTransformer2DModel(nn.Module):
         ops.head_merge(dK, dqkv[:, Dp:2 * Dp], B, H, HP, S)
         wgrad("qkv", dqkv, sv.n1, unpad_rows(["attn1.to_q", "attn1.to_k", "attn1.to_v"]))
         dn1 = lora_dgrad(L.qkv if L is not None else None, dqkv, W.qkv_wT, sv.n1, getattr(sv, "T_qkv", None))
-        mod_grads(dn1, sv.h, 0, 1)
+        if tr:
+            mod_grads(D, dn1, sv.h, S, 0, 1, dmod)
         d0, _ = ops.ln_modulate_bwd(dn1, sv.h, m[1], S, dres=d1)
         if tr:
             blk.G["scale_shift_table"].copy_(dmod.sum(0).view(6, D))
@@ -798,7 +770,7 @@ class PixArtSigmaControlNetTransformerModel(CheckpointPlanMixin, nn.Module):
             s.t = self.arena[s.off:s.off + s.numel].view(*s.shape)
             s.g = self.grad_arena[s.off:s.off + s.numel].view(*s.shape)
             par = nn.Parameter(s.t, requires_grad=True)
-            _attach(self, s.name, par)
+            attach(self, s.name, par)
             params.append(par)
         self._params = params
         self._offsets = [(s.off, s.numel) for s in specs]
@@ -907,14 +879,14 @@ class PixArtSigmaControlNetTransformerModel(CheckpointPlanMixin, nn.Module):
                 blk, ex = self.cblocks[i - 1]
                 cs_out = ctx.cs_in.pop(i - 1)
                 # h' = h + after_proj(cs_out):  d after_proj, d cs_out (+ what the next control block sent back)
-                ops.gemm_tn(_p64(dh), _p64(cs_out), out=ex.G["after_proj.weight"])
+                ops.gemm_tn(pad64(dh), pad64(cs_out), out=ex.G["after_proj.weight"])
                 tb = torch.empty(1, dh.shape[1], dtype=F32, device=dh.device)
                 ops.colsum_prod(dh, tb); ex.G["after_proj.bias"].copy_(tb[0])
                 wT = ex.after_proj_weight.t().contiguous()
                 dcs = ops.gemm(dh, wT) if dcs is None else ops.gemm(dh, wT, epilogue=EPI_ADD, aux_in=dcs)
                 dcs = T._block_bwd(blk, ctx.ctrl.pop(i - 1), dcs, ctx.ctx2d, ctx.kb, B, S, Sk)
                 if i == 1:                                         # cs_in = h + before_proj(cs0): h gets dcs too (unused: nothing trainable before it)
-                    ops.gemm_tn(_p64(dcs), _p64(ctx.cs0), out=ex.G["before_proj.weight"])
+                    ops.gemm_tn(pad64(dcs), pad64(ctx.cs0), out=ex.G["before_proj.weight"])
                     ops.colsum_prod(dcs, tb); ex.G["before_proj.bias"].copy_(tb[0])
 
     def forward(self, hidden_states, encoder_hidden_states=None, timestep=None, controlnet_cond=None, added_cond_kwargs=None, cross_attention_kwargs=None,

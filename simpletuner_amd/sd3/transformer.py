@@ -16,6 +16,7 @@ GEMMs, token-axis reductions for the modulation rows, q / k RMSNorm weight gradi
 from __future__ import annotations
 
 import math
+import os
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -23,57 +24,28 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..flux.transformer import FluxTransformer2DModel as _FluxEngine, LoraGroup, _attach, _frozen
+from ..engine import ArenaModule, FullGrads, LoraGroup, attach, compact, frozen, pad64_empty, problems, rows_of, sincos_2d_hw
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-_BLOCK_ABI = __import__("os").environ.get("ST355_BLOCK_ABI", "1") != "0"      # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_sd3_joint_*
+_BLOCK_ABI = os.environ.get("ST355_BLOCK_ABI", "1") != "0"      # A/B switch: 0 = sequence the blocks' kernels from the host instead of st355_block_sd3_joint_*
 
 
 def sincos_2d(embed_dim: int, grid_size: int, base_size: int, interpolation_scale: float = 1.0) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed: [grid_size^2, embed_dim] fp32 (w axis first, sin then cos per axis)"""
-    ar = torch.arange(grid_size, dtype=torch.float32) / (grid_size / base_size) / interpolation_scale
-    gw = ar[None, :].expand(grid_size, grid_size).reshape(-1).double()      # meshgrid(grid_w, grid_h): w varies fastest
-    gh = ar[:, None].expand(grid_size, grid_size).reshape(-1).double()
-
-    def one_d(dim, pos):
-        omega = 1.0 / 10000 ** (torch.arange(dim // 2, dtype=torch.float64) / (dim / 2.0))
-        out = pos[:, None] * omega[None, :]
-        return torch.cat([out.sin(), out.cos()], dim=1)
-
-    return torch.cat([one_d(embed_dim // 2, gw), one_d(embed_dim // 2, gh)], dim=1).float()
-
-
-
-def _pad64_empty(rows: int, cols: int, dev):
-    """[rows, cols] bf16, uninitialised, as the head of a parent buffer whose row count is rounded up to 64 and whose tail rows are ZERO: the weight-gradient GEMM
-    (contraction granule 64 rows) reads the parent directly instead of a zero-padded copy of the tensor (round 5: two launches and a full copy per text-stream
-    operand, 192 hipMemcpy + 224 fill launches per SD3 full fine-tune step).  The view remembers its parent in `_st355_pad64`."""
-    rp = (rows + 63) // 64 * 64
-    if rp == rows:
-        return torch.empty(rows, cols, dtype=BF16, device=dev)
-    par = torch.empty(rp, cols, dtype=BF16, device=dev)
-    par[rows:].zero_()
-    t = par[:rows]
-    t._st355_pad64 = par
-    return t
-
-
-def _rows3(joint, lo: int, rows: int, B: int, S: int):
-    """rows [lo, lo + rows) of every sample of a joint [B * S, C] buffer as a GEMM operand ([B, rows, C] strided view, no copy)"""
-    return _FluxEngine._rows_of(joint, lo, rows, SimpleNamespace(B=B, S=S))
+    return sincos_2d_hw(embed_dim, grid_size, grid_size, base_size, interpolation_scale)
 
 
 def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] = None):
     """one projection over the `rows`-row block of every sample as ONE problem: segmented operands when the block is tile-aligned (the 4096 image rows,
-    FluxTransformer2DModel._problems); otherwise (the 154 text rows) through compact copies of the joint-buffer operands — the rows are gathered before the
+    engine.problems); otherwise (the 154 text rows) through compact copies of the joint-buffer operands — the rows are gathered before the
     GEMM, a joint-buffer `out` is written to a compact temporary and scattered back by the closures appended to `after` (run them once the launch is
     issued).  A few MB of copies instead of B tiny launches per projection (measured: the per-sample form of the text stream cost as much as the image
     stream's segmentation saved)."""
     if B == 1 or rows % 256 == 0 or after is None or rows >= 1024:       # big unaligned blocks (odd aspect buckets): one problem per sample beats copying them
-        return _FluxEngine._problems(SimpleNamespace(B=B, S=S), rows, pr)
+        return problems(B, rows, pr)
     q = dict(pr)
     for k in ("a", "a2", "aux_in"):
         v = q.get(k)
@@ -89,7 +61,7 @@ def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] 
 
 
 
-class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
+class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     def __init__(self, sample_size: int = 128, patch_size: int = 2, in_channels: int = 16, num_layers: int = 18,
                  attention_head_dim: int = 64, num_attention_heads: int = 18, joint_attention_dim: int = 4096,
                  caption_projection_dim: int = 1152, pooled_projection_dim: int = 2048, out_channels: int = 16,
@@ -123,13 +95,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         # every weight / bias / modulation row is a view of ONE bf16 arena (allocation order = arena order): the full fine-tune then
         # has one gradient arena of the same layout, ONE fused optimizer launch and contiguous slices for the RCCL all-reduce.
         # Pass 1 counts (meta tensors), pass 2 hands out the views.
-        self._arena_numel = 0
-        self._counting = True
-        self._build(lambda *s_: self._alloc(s_))
-        self.arena = torch.zeros(self._arena_numel, dtype=BF16, device=dev)
-        self._arena_numel = 0
-        self._counting = False
-        self._build(lambda *s_: self._alloc(s_))
+        self._build_arena(dev)
         self.pos_embed.register_buffer("pos_embed", torch.zeros(1, pos_embed_max_size * pos_embed_max_size, D, dtype=F32, device=dev))
 
         self.lora_groups: List[LoraGroup] = []
@@ -147,35 +113,20 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         self._last_grad_flat = None
         self.full = False
 
-    def _alloc(self, shape):
-        n = 1
-        for d in shape:
-            n *= d
-        n_pad = (n + 7) // 8 * 8                      # every tensor starts 16-byte aligned inside the arena
-        off = self._arena_numel
-        self._arena_numel += n_pad
-        if self._counting:
-            return torch.empty(*shape, dtype=BF16, device="meta")
-        return self.arena[off:off + n].view(*shape)
-
-    def _reg(self, name, param):
-        if not self._counting:
-            _attach(self, name, param)
-
-    def _build(self, e):
+    def _build(self):
         c = self.config
-        D, dev = self.D, self.device_
+        D, dev, e = self.D, self.device_, self._alloc
         in_channels, out_channels, num_layers, qk_norm = c.in_channels, c.out_channels, c.num_layers, c.qk_norm
         joint_attention_dim, pooled_projection_dim = c.joint_attention_dim, c.pooled_projection_dim
 
         def lin(name, out_f, in_f):
             w, b = e(out_f, in_f), e(out_f)
-            self._reg(name + ".weight", _frozen(w)); self._reg(name + ".bias", _frozen(b))
+            self._reg(name + ".weight", frozen(w)); self._reg(name + ".bias", frozen(b))
             return SimpleNamespace(w=w, b=b, wT=None, lora=None)
 
         # PatchEmbed: the Conv2d weight keeps its checkpoint shape; the GEMM reads it as [D, C*p*p]
         conv_w, conv_b = e(D, in_channels, 2, 2), e(D)
-        self._reg("pos_embed.proj.weight", _frozen(conv_w)); self._reg("pos_embed.proj.bias", _frozen(conv_b))
+        self._reg("pos_embed.proj.weight", frozen(conv_w)); self._reg("pos_embed.proj.bias", frozen(conv_b))
         self.l_patch = SimpleNamespace(w=conv_w.view(D, 4 * in_channels), b=conv_b)
         self.l_t1 = lin("time_text_embed.timestep_embedder.linear_1", D, 256)
         self.l_t2 = lin("time_text_embed.timestep_embedder.linear_2", D, D)
@@ -190,7 +141,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
 
         def mod_slice(name, n):
             nonlocal off
-            self._reg(name + ".weight", _frozen(self.mod_w[off:off + n])); self._reg(name + ".bias", _frozen(self.mod_b[off:off + n]))
+            self._reg(name + ".weight", frozen(self.mod_w[off:off + n])); self._reg(name + ".bias", frozen(self.mod_b[off:off + n]))
             o = off
             off += n
             return o
@@ -199,8 +150,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             n = len(names)
             w, b = e(n * out_each, in_f), e(n * out_each)
             for j, nm in enumerate(names):
-                self._reg(f"{prefix}{nm}.weight", _frozen(w[j * out_each:(j + 1) * out_each]))
-                self._reg(f"{prefix}{nm}.bias", _frozen(b[j * out_each:(j + 1) * out_each]))
+                self._reg(f"{prefix}{nm}.weight", frozen(w[j * out_each:(j + 1) * out_each]))
+                self._reg(f"{prefix}{nm}.bias", frozen(b[j * out_each:(j + 1) * out_each]))
             return SimpleNamespace(w=w, b=b, wT=None, lora=None)
 
         def normw(name):
@@ -209,7 +160,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             w = e(self.hd)
             if not self._counting:
                 w.fill_(1.0)
-            self._reg(name + ".weight", _frozen(w))
+            self._reg(name + ".weight", frozen(w))
             return w
 
         self.blocks: List[SimpleNamespace] = []
@@ -244,37 +195,18 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
     # ------------------------------------------------------------------------------------------------
     # weights
     # ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def load_flat_state(self, state: Dict[str, torch.Tensor]):
-        own = dict(self.named_parameters())
-        missing = [k for k in own if k not in state and ".lora_" not in k]
-        if missing:
-            raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
-        for k, v in state.items():
-            if k in own:
-                own[k].data.copy_(v.to(device=own[k].device, dtype=own[k].dtype))
-        if "pos_embed.pos_embed" in state:
-            self.pos_embed.pos_embed.copy_(state["pos_embed.pos_embed"].to(self.device_, F32))
+    def _extra_state(self):
+        return {"pos_embed.pos_embed": self.pos_embed.pos_embed}          # the position table: a buffer, saved and loaded with the parameters
+
+    def _weights_changed(self):
         self._prepared = False
         self._cache.clear()
 
     @torch.no_grad()
     def init_synthetic(self, seed: int = 42):
-        g = torch.Generator(device=self.device_).manual_seed(seed)
-        for name, p in self.named_parameters():
-            if ".lora_" in name:
-                continue
-            if "norm_q" in name or "norm_k" in name or "norm_added" in name:
-                p.data.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g, device=self.device_))
-            elif name.endswith(".bias"):
-                p.data.copy_(0.02 * torch.randn(p.shape, generator=g, device=self.device_))
-            else:
-                fan_in = p[0].numel()
-                p.data.copy_(torch.randn(p.shape, generator=g, device=self.device_, dtype=BF16) * (1.0 / math.sqrt(fan_in)))
+        super().init_synthetic(seed)
         c = self.config
         self.pos_embed.pos_embed.copy_(sincos_2d(self.D, c.pos_embed_max_size, c.sample_size // c.patch_size)[None].to(self.device_))
-        self._prepared = False
-        self._cache.clear()
 
     @torch.no_grad()
     def prepare_for_training(self):
@@ -334,7 +266,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             if init_b_std > 0:
                 b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
             pa, pb = nn.Parameter(a), nn.Parameter(b)
-            _attach(self, name + ".lora_A.default.weight", pa); _attach(self, name + ".lora_B.default.weight", pb)
+            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             g.flat_hi = off
             self._lora_params += [pa, pb]
@@ -383,8 +315,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_blk) if T_txt is not None else {}
         # the image stream (4096 rows per sample: tile-aligned) is ONE segmented problem over the joint buffer; the 154 text rows stay per sample
         after = []
-        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=_rows3(qkv, 0, Si, B, S), **kw_i), after)
-                         + _stream_problems(B, S, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=_rows3(qkv, Si, St, B, S), **kw_t), after))
+        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **kw_i), after)
+                         + _stream_problems(B, S, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=rows_of(qkv, Si, St, B, S), **kw_t), after))
         for f in after:
             f()
         Q = torch.empty(B, H, S, hd, dtype=BF16, device=dev); K = torch.empty_like(Q)
@@ -406,7 +338,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         T_ao = (torch.empty(B * St, blk.to_add_out.lora.K2, dtype=BF16, device=dev)
                 if (not blk.last and blk.to_add_out.lora is not None) else None)
         ya_i, ya_t = ybuf(B * Si), (None if blk.last else ybuf(B * St))
-        O_i, O_t = _rows3(O, 0, Si, B, S), _rows3(O, Si, St, B, S)
+        O_i, O_t = rows_of(O, 0, Si, B, S), rows_of(O, Si, St, B, S)
         kw_i, kw_t = {}, {}
         if ya_i is not None:
             kw_i["aux_out"] = ya_i
@@ -506,7 +438,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         K2a, kr_a, A_a, Bb_a, _, _ = self._lk(blk.add_qkv)
         K2o, kr_o, A_o, Bb_o, _, _ = self._lk(blk.to_out)
         K2t, kr_t, A_t, Bb_t, _, _ = self._lk(None if last else blk.to_add_out)
-        et = (lambda r, c: _pad64_empty(r, c, dev)) if (full and save) else e        # text-stream tensors a full fine-tune contracts over tokens: zero-tailed to 64 rows
+        et = (lambda r, c: pad64_empty(r, c, dev)) if (full and save) else e        # text-stream tensors a full fine-tune contracts over tokens: zero-tailed to 64 rows
         n_img, n_txt, qkv, O, x1_img, hpre_img, n2_i, h_i, x2_img = (e(B * Si, D), et(B * St, D), e(B * S, 3 * D), e(B * S, D), e(B * Si, D), e(B * Si, 4 * D),
                                                                      e(B * Si, D), e(B * Si, 4 * D), e(B * Si, D))
         Q, K, lse2 = e(B, H, S, hd), e(B, H, S, hd), e(B, H, S, dt=F32)
@@ -560,7 +492,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
                             dO=(torch.zeros if last else torch.empty)(B * S, D, dtype=BF16, device=dev), dqkv=e(B * S, 3 * D),
                             U_o=e(B * Si, K2o) if K2o else None, U_ao=e(B * St, K2t) if K2t else None, U_q=e(B * Si, K2q) if K2q else None,
                             U_a=e(B * St, K2a) if K2a else None, dn_i=None, dn_t=None, c_img=None, c_txt=None)
-        et = (lambda r, c: _pad64_empty(r, c, dev)) if dmod is not None else e       # (full fine-tune: the text-stream gradients are weight-gradient operands)
+        et = (lambda r, c: pad64_empty(r, c, dev)) if dmod is not None else e       # (full fine-tune: the text-stream gradients are weight-gradient operands)
         if not last:
             G.g_t, G.dh_t, G.dn2_t, G.dx1_t, G.dx1g_t = et(B * St, D), et(B * St, 4 * D), e(B * St, D), e(B * St, D), et(B * St, D)
         if B > 1 and Si % 256:
@@ -590,9 +522,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             dx1_txt=G.dx1_t, dx1g_txt=G.dx1g_t, U_o=G.U_o, U_ao=G.U_ao, dO=G.dO, dqkv=G.dqkv, dQ=dQ, dK=dK, U_qkv=G.U_q, U_aqkv=G.U_a,
             dn_img=G.dn_i, dn_txt=G.dn_t, c_img=G.c_img, c_txt=G.c_txt, d_img_out=d_img_out, d_txt_out=d_txt_out)
         # each stream's rows of dqkv in the operand form the C entry used: in place (a 3-D view, segmented) when B == 1 or tile-aligned, else its compact copy
-        envs = SimpleNamespace(B=B, S=S)
-        G.dq_i = G.c_img if G.c_img is not None else _FluxEngine._compact(_rows3(G.dqkv, 0, Si, B, S), envs, Si)
-        G.dq_t = G.c_txt if G.c_txt is not None else _FluxEngine._compact(_rows3(G.dqkv, Si, St, B, S), envs, St)
+        G.dq_i = G.c_img if G.c_img is not None else compact(rows_of(G.dqkv, 0, Si, B, S), B, Si)
+        G.dq_t = G.c_txt if G.c_txt is not None else compact(rows_of(G.dqkv, Si, St, B, S), B, St)
         return d_img_out, d_txt_out, G
 
     def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False):
@@ -735,14 +666,13 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             rpb_i = rpb if rpb == 1 else Si             # (inside a TREAD route Si is the kept-token count)
             if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous()) and rpb != 1:
                 # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then the rank-space adapter gradients from the gradients it left behind
-                envs = SimpleNamespace(B=B, S=S)
                 d_img, d_txt, G = self._block_bwd_c(blk, sv, ctx.envs[li], mod, cos, sin, d_img, d_txt, li != 0)
                 pairs = [(blk.to_out, G.U_o, sv.T_o, G.dx1g_i, 0, Si)]
                 if not blk.last:
                     pairs.append((blk.to_add_out, G.U_ao, sv.T_ao, G.dx1g_t, Si, St))
                 for (lin, U, T_, dxg, lo, rows) in pairs:
                     if lin.lora is not None:
-                        lin.lora.grads(_FluxEngine._compact(_rows3(sv.O, lo, rows, B, S), envs, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
+                        lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
                 for (lin, dq, n_in, T_, U) in ((blk.qkv, G.dq_i, sv.n_img, sv.T_img, G.U_q), (blk.add_qkv, G.dq_t, sv.n_txt, sv.T_txt, G.U_a)):
                     if lin.lora is not None:
                         lin.lora.grads(n_in, T_, dq, U, self.accumulate_lora_grads, self.grad_sync)
@@ -794,20 +724,19 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_blk_T) if (not blk.last and blk.to_add_out.lora is not None) else None
             after = []
             kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T) if U_i is not None else {}
-            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=_rows3(dO, 0, Si, B, S), **kw_i), after)
+            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S), **kw_i), after)
             if not blk.last:
                 kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T) if U_t is not None else {}
-                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=_rows3(dO, Si, St, B, S), **kw_t), after)
+                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S), **kw_t), after)
             ops.gemm_grouped(probs)
             for f in after:
                 f()
             pairs = [(blk.to_out, U_i, sv.T_o, dx1g_i, 0, Si)]
             if not blk.last:
                 pairs.append((blk.to_add_out, U_t, sv.T_ao, dx1g_t, Si, St))
-            envs = SimpleNamespace(B=B, S=S)
             for (lin, U, T_, dxg, lo, rows) in pairs:
                 if lin.lora is not None:       # this stream's rows of the joint attention output: read in place when tile-aligned (image rows), else a compact copy
-                    lin.lora.grads(_FluxEngine._compact(_rows3(sv.O, lo, rows, B, S), envs, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
+                    lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
             del dx1g_i, dx1g_t, U_i, U_t
             dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
             dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
@@ -817,7 +746,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             del dQ, dK, dO
             first = li == 0
             # the two streams' rows of the joint dqkv: the image rows in place (segmented operands), the 154 text rows as a compact copy
-            dq_i = _FluxEngine._compact(_rows3(dqkv, 0, Si, B, S), envs, Si); dq_t = _FluxEngine._compact(_rows3(dqkv, Si, St, B, S), envs, St)
+            dq_i = compact(rows_of(dqkv, 0, Si, B, S), B, Si); dq_t = compact(rows_of(dqkv, Si, St, B, S), B, St)
             streams = [("img", blk.qkv, dq_i, sv.n_img, sv.T_img, Si), ("txt", blk.add_qkv, dq_t, sv.n_txt, sv.T_txt, St)]
             if first:
                 streams = [s_ for s_ in streams if s_[1].lora is not None]     # frozen embedders: only adapter grads remain
@@ -920,70 +849,15 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         """training.grad_sync.hand_over_gradients: the arena just filled now belongs to autograd; the next backward takes the other one"""
         self._select_grad_arena(1 - self._grad_sel)
 
-    def trainable_parameters(self):
-        return list(self._full_params) if getattr(self, "full", False) else list(self._lora_params)
-
-    def diffusers_state_dict(self) -> Dict[str, torch.Tensor]:
-        """{diffusers checkpoint key: tensor} of the base parameters + the position table (the parameter names ARE the checkpoint keys): what `save_pretrained`
-        writes for a full fine-tune (training/trainer.py save_state)"""
-        sd = {k: v.detach() for k, v in self.named_parameters() if ".lora_" not in k}
-        sd["pos_embed.pos_embed"] = self.pos_embed.pos_embed.detach()
-        return sd
-
-    def load_diffusers_state(self, state: Dict[str, torch.Tensor]):
-        self.load_flat_state(state)
-
-    def _refresh_transposed(self):
-        """W^T follows the weights (2 B read + 2 B write per parameter; ~1 ms for SD3-Medium)"""
-        for l in self._all_linears():
-            if getattr(l, "wT", None) is not None:
-                ops.transpose(l.w, out=l.wT)
-
     def _engine_backward_full(self, ctx, dout):
         D, H, hd = self.D, self.H, self.hd
         B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
         dev = self.device_
         scale = 1.0 / math.sqrt(hd)
         self._refresh_transposed()
-        dmod = torch.zeros(B, self.mod_total, dtype=F32, device=dev)        # d loss / d (modulation linear output)
-        tmp_b = {}
-
-        def pad64_rows(rows, cols):
-            """an uninitialised [rows, cols] buffer that lives in a zero-tailed parent with a multiple of 64 rows: P64 hands the parent to the TN GEMM, no copy"""
-            return _pad64_empty(rows, cols, dev)
-
-        def P64(t):
-            """the operand with a multiple of 64 contraction rows (the TN GEMM's granule): as is when aligned or segmented, its zero-tailed parent when it was
-            allocated by _pad64_empty, else a zero-padded copy"""
-            if t.dim() == 3:
-                return t
-            r = t.shape[0]
-            if r % 64 == 0 and t.is_contiguous():
-                return t
-            par = getattr(t, "_st355_pad64", None)
-            if par is not None:
-                return par
-            o = torch.zeros((r + 63) // 64 * 64, t.shape[1], dtype=BF16, device=dev)
-            o[:r] = t
-            return o
-
-        def wgrad(lin, dy, x, bias: bool = True):
-            """dW = dY^T X ; db = colsum(dY)   (into the gradient arena views of `lin`; bias=False: the bias gradient was already taken by a fused pass)"""
-            ops.gemm_tn(P64(dy), P64(x), out=lin.gw)
-            if not bias:
-                return
-            N = dy.shape[1]
-            t = tmp_b.get(N)
-            if t is None:
-                t = tmp_b[N] = torch.empty(1, N, dtype=F32, device=dev)
-            ops.colsum_prod(dy, t)
-            lin.gb.copy_(t[0])
-
-        def mod_grads(dn, x_in, rows, k_shift, k_scale, dm):
-            """d shift = sum_t dY, d scale = sum_t dY * LN(x) of one AdaLN instance (chunk indices k_* inside its slice dm of the modulation gradient); x_in = the
-            LayerNorm's input.  (LN(x) is recomputed: recovering it from the saved modulated output divides by 1 + scale, singular where a scale entry is -1.)"""
-            ops.colsum_prod(dn, dm[:, k_shift * D:(k_shift + 1) * D], rows_per_batch=rows)
-            ops.colsum_prod(dn, dm[:, k_scale * D:(k_scale + 1) * D], b=ops.layer_norm_xhat(x_in), rows_per_batch=rows)
+        sync = self.grad_sync
+        fb = FullGrads(self, B, dev, sync, self._blocks_arena_lo, ctx.emb.st)
+        dmod, wgrad = fb.dmod, fb.wgrad
 
         def qk_bwd(dQ_, dK_, qkv_, wq, wk, dqkv_, rows, pos0, S_, gq, gk):
             """RMSNorm (+ identity RoPE) backward of one stream's q / k; with norm weights (SD3.5) also their gradients (sd3/transformer.py:155-165)"""
@@ -992,16 +866,16 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             else:
                 ops.qk_norm_rope_bwd_wgrad(dQ_, dK_, qkv_, wq, wk, cos, sin, dqkv_, B, H, hd, rows, pos0, S_, gq, gk)
 
-        def rows_of(t, lo, n, seg: bool = False):
+        def grad_rows(t, lo, n, seg: bool = False):
             """rows [lo, lo+n) of every batch element of a joint [B*S, C] buffer as a weight-gradient operand.  seg: in place — a [B, n, C] strided view, the
             segmented-contraction form of st355_gemm_tn_seg_bf16 — when n is a whole number of 64-row K-tiles (the image rows of every bucket); else (the text
-            rows, and callers that also read the operand as a plain matrix) a compact copy, its row count zero-tailed to 64 (P64 below takes it as is)"""
+            rows, and callers that also read the operand as a plain matrix) a compact copy, its row count zero-tailed to 64 (pad64 takes it as is)"""
             if B == 1:
                 return t[lo:lo + n]
             v = t.view(B, S, -1)[:, lo:lo + n]
             if seg and n % 64 == 0 and n >= 128:
                 return v
-            o = pad64_rows(B * n, t.shape[1])
+            o = pad64_empty(B * n, t.shape[1], dev)
             o.view(B, n, -1).copy_(v)
             return o
 
@@ -1011,34 +885,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         dmo = dmod[:, self.mod_off_out:self.mod_off_out + 2 * D]
         wgrad(self.l_out, dpk, ctx.n_out)
         dn = ops.gemm(dpk, self.l_out.wT)
-        mod_grads(dn, ctx.x_img_final, Si, 1, 0, dmo)                        # AdaLayerNormContinuous: (scale, shift)
+        fb.mod_grads(dn, ctx.x_img_final, Si, 1, 0, dmo)                        # AdaLayerNormContinuous: (scale, shift)
         d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], Si)
         d_txt = None
         del dn, dpk
-        sync = self.grad_sync
         if sync is not None:
             sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
-        # The fused modulation matrix (every block's adaLN Linear as rows of ONE [mod_total, D] matrix: a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its
-        # gradient rows block by block (r6) — dW_mod[r0:r1] = dmod[:, r0:r1]^T silu(temb) as soon as the block that owns rows [r0, r1) has run — so that the exchange
-        # can take them behind the backward; as one product at the end of the backward the whole region left as one exposed 1.5 GB slice.  Same arithmetic per row
-        # (one 64-deep contraction over the zero-padded batch), so the gradient is bit-equal to the one-product form.
-        Bp = (B + 63) // 64 * 64
-        st_p = torch.zeros(Bp, D, dtype=BF16, device=dev); st_p[:B] = ctx.emb.st
-        mw_lo = (self.mod_w.data_ptr() - self.arena.data_ptr()) // 2
-        mw_hi = mw_lo + self.mod_total * D
-        mod_rows_lo = [self.mod_total]                    # rows [mod_rows_lo, mod_total) of dW_mod are written (and handed over)
-
-        def mod_rows_grad(r0):
-            r1 = mod_rows_lo[0]
-            if r1 <= r0:
-                return
-            dp = torch.zeros(Bp, r1 - r0, dtype=BF16, device=dev); dp[:B] = dmod[:, r0:r1]
-            ops.gemm_tn(dp, st_p, out=self.g_mod_w[r0:r1])
-            mod_rows_lo[0] = r0
-            if sync is not None and 0 <= mw_lo and mw_hi <= self._blocks_arena_lo:
-                sync.ready(mw_lo + r0 * D, mw_lo + r1 * D)
-
-        mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
+        # the fused modulation matrix (a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
+        fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
@@ -1053,7 +907,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
                 nb = self.blocks[li + 1]
                 if sync is not None:
                     sync.ready(nb.arena_lo, nb.arena_hi)                      # the block processed last iteration: its slice can go out
-                mod_rows_grad(nb.mod_off)                                     # ... and so can its rows of the modulation matrix
+                fb.mod_rows_grad(nb.mod_off)                                     # ... and so can its rows of the modulation matrix
             mi = mod[:, blk.mod_off:blk.mod_off + 6 * D]; dmi = dmod[:, blk.mod_off:blk.mod_off + 6 * D]
             nct = 2 if blk.last else 6
             mt = mod[:, blk.mod_off_c:blk.mod_off_c + nct * D]; dmt = dmod[:, blk.mod_off_c:blk.mod_off_c + nct * D]
@@ -1069,11 +923,11 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
                 if not blk.last:
                     wgrad(blk.ffc2, G.g_t, sv.h_t, bias=False)
                     wgrad(blk.ffc1, G.dh_t, sv.n2_t, bias=False)
-                wgrad(blk.to_out, G.dx1g_i, rows_of(sv.O, 0, Si, seg=True), bias=False)
+                wgrad(blk.to_out, G.dx1g_i, grad_rows(sv.O, 0, Si, seg=True), bias=False)
                 if not blk.last:
-                    wgrad(blk.to_add_out, G.dx1g_t, rows_of(sv.O, Si, St), bias=False)
-                wgrad(blk.qkv, G.c_img if G.c_img is not None else rows_of(G.dqkv, 0, Si, seg=True), sv.n_img, bias=False)       # (c_*: the compact copy the entry left)
-                wgrad(blk.add_qkv, G.c_txt if G.c_txt is not None else rows_of(G.dqkv, Si, St), sv.n_txt, bias=False)
+                    wgrad(blk.to_add_out, G.dx1g_t, grad_rows(sv.O, Si, St), bias=False)
+                wgrad(blk.qkv, G.c_img if G.c_img is not None else grad_rows(G.dqkv, 0, Si, seg=True), sv.n_img, bias=False)       # (c_*: the compact copy the entry left)
+                wgrad(blk.add_qkv, G.c_txt if G.c_txt is not None else grad_rows(G.dqkv, Si, St), sv.n_txt, bias=False)
                 del sv, G
                 if li in ctx.route_start:
                     ops.scatter_rows(d_img.view(B, Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
@@ -1122,18 +976,18 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
                 ops.colsum_rows(dh_t, St, St, B, blk.ffc1.gb)
                 del g_t, dh_t, dn2_t
             # ---- attention output projections ----
-            O_i = rows_of(sv.O, 0, Si)
+            O_i = grad_rows(sv.O, 0, Si)
             wgrad(blk.to_out, dx1g_i, O_i, bias=False)
             dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
             after = []
-            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=_rows3(dO, 0, Si, B, S)), after)
+            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S)), after)
             if not blk.last:
-                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=_rows3(dO, Si, St, B, S)), after)
+                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S)), after)
             ops.gemm_grouped(probs)
             for f in after:
                 f()
             if not blk.last:
-                wgrad(blk.to_add_out, dx1g_t, rows_of(sv.O, Si, St), bias=False)
+                wgrad(blk.to_add_out, dx1g_t, grad_rows(sv.O, Si, St), bias=False)
             del dx1g_i, dx1g_t, O_i
             # ---- attention ----
             dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
@@ -1144,7 +998,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
             del dQ, dK, dO
             ops.colsum_rows(dqkv, Si, S, B, blk.qkv.gb)                    # d b_qkv / d b_add_qkv: each stream's rows of the joint dqkv, summed in place
             ops.colsum_rows(dqkv[Si:], St, S, B, blk.add_qkv.gb)
-            dq_i, dq_t = rows_of(dqkv, 0, Si), rows_of(dqkv, Si, St)
+            dq_i, dq_t = grad_rows(dqkv, 0, Si), grad_rows(dqkv, Si, St)
             wgrad(blk.qkv, dq_i, sv.n_img, bias=False)
             wgrad(blk.add_qkv, dq_t, sv.n_txt, bias=False)
             dn_i, dn_t = ops.gemm_grouped([dict(a=dq_i, w=blk.qkv.wT), dict(a=dq_t, w=blk.add_qkv.wT)])
@@ -1165,36 +1019,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, nn.Module):
         em = ctx.emb
         wgrad(self.l_patch, d_img, em.patches)                              # PatchEmbed conv == GEMM on the patches; the position table is a buffer
         wgrad(self.l_ctx, d_txt, em.enc2d)
-        # modulation linear: mod = silu(temb) W_mod^T + b
-        dmod_p = torch.zeros(Bp, self.mod_total, dtype=BF16, device=dev); dmod_p[:B] = dmod
-        mod_rows_grad(0)                                                    # block 0's rows (every other block's went out behind the block after it)
-        tb = torch.empty(1, self.mod_total, dtype=F32, device=dev)
-        ops.colsum_prod(dmod_p, tb)
-        self.g_mod_b.copy_(tb[0])
-        dmod_t = ops.transpose(dmod_p[:8 * ((B + 7) // 8)])                 # [mod_total, B8]
-        dst = ops.transpose(ops.gemm_tn(self.mod_w, dmod_t))[:B].contiguous()   # d silu(temb) = dmod @ W_mod  ->  [B, D]
-        dtemb = ops.silu_bwd(em.temb, dst)
-
-        def mlp_bwd(l1, l2, x_in, pre1, act1, dy):
-            """TimestepEmbedding / text projection: y = l2(silu(l1(x)))"""
-            dyp = torch.zeros(Bp, dy.shape[1], dtype=BF16, device=dev); dyp[:B] = dy
-            a1p = torch.zeros(Bp, act1.shape[1], dtype=BF16, device=dev); a1p[:B] = act1
-            ops.gemm_tn(dyp, a1p, out=l2.gw)
-            tb2 = torch.empty(1, dy.shape[1], dtype=F32, device=dev); ops.colsum_prod(dyp, tb2); l2.gb.copy_(tb2[0])
-            d1 = ops.silu_bwd(pre1, ops.gemm(dy, l2.wT))
-            d1p = torch.zeros(Bp, d1.shape[1], dtype=BF16, device=dev); d1p[:B] = d1
-            xp = torch.zeros(Bp, x_in.shape[1], dtype=BF16, device=dev); xp[:B] = x_in
-            ops.gemm_tn(d1p, xp, out=l1.gw)
-            ops.colsum_prod(d1p, tb2); l1.gb.copy_(tb2[0])
-
-        mlp_bwd(self.l_t1, self.l_t2, em.tproj, em.t1, em.st1, dtemb)
-        mlp_bwd(self.l_p1, self.l_p2, em.pooled, em.p1, em.sp1, dtemb)
-        if sync is not None:
-            if 0 <= mw_lo and mw_hi <= self._blocks_arena_lo:                 # embedders, modulation bias, block 0: what lies around the modulation matrix's rows
-                sync.ready(mw_hi, self.blocks[0].arena_hi)
-                sync.ready(0, mw_lo)
-            else:
-                sync.ready(0, self.blocks[0].arena_hi)
+        dtemb = fb.mod_linear_bwd(em.temb)          # (+ block 0's modulation rows: every other block's went out behind the block after it)
+        fb.mlp_bwd(self.l_t1, self.l_t2, em.tproj, em.t1, em.st1, dtemb)
+        fb.mlp_bwd(self.l_p1, self.l_p2, em.pooled, em.p1, em.sp1, dtemb)
+        fb.ready_front(self.blocks[0].arena_hi)     # embedders, modulation bias, block 0
         return None
 
     # ------------------------------------------------------------------------------------------------

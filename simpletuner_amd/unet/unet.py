@@ -26,21 +26,12 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..flux.transformer import LoraGroup, _attach, _frozen
+from ..engine import LoraGroup, attach, frozen, pad64
 from ..ops import EPI_ADD, EPI_GEGLU, EPI_GEGLU_GRAD, EPI_HEADS, EPI_NONE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-
-
-def _p64(t):
-    r = t.shape[0]
-    if r % 64 == 0 and t.is_contiguous():
-        return t
-    o = torch.zeros((r + 63) // 64 * 64, t.shape[1], dtype=BF16, device=t.device)
-    o[:r] = t
-    return o
 
 
 # ST355_HEADS_FUSED=0: the attention input projections write [M, 3C] / [M, C] and st355_head_split_pad re-lays them out (A/B switch for ST355_EPI_HEADS)
@@ -122,10 +113,10 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
             s.t = self.arena[s.off:s.off + s.numel].view(*s.shape)
             s.g = None
             if s.views is None:
-                _attach(self, s.name, _frozen(s.t))
+                attach(self, s.name, frozen(s.t))
             else:                                   # fused projections: the diffusers keys are row-slices of the one matrix
                 for nm, lo, hi in s.views:
-                    _attach(self, nm, _frozen(s.t[lo:hi]))
+                    attach(self, nm, frozen(s.t[lo:hi]))
         self.grad_arena = None
         self.full = False
         self.grad_sync = None
@@ -433,7 +424,7 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
             if init_b_std > 0:
                 b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
             pa, pb = nn.Parameter(a), nn.Parameter(b)
-            _attach(self, name + ".lora_A.default.weight", pa); _attach(self, name + ".lora_B.default.weight", pb)
+            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             g.flat_hi = off
             self._lora_params += [pa, pb]
@@ -502,7 +493,7 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
         """weight / bias / adapter gradients of y = x W^T (+ low-rank term) from dy, and dx = dy W (+ rank-space term)"""
         lo = l.lora
         if self.full:
-            ops.gemm_tn(_p64(dy), _p64(x), out=l.w.g)
+            ops.gemm_tn(pad64(dy), pad64(x), out=l.w.g)
             if l.b is not None:
                 self._bias_grad(dy, l.b)
             self._ready(l.b, l.w) if (l.b is not None and l.b.off > l.w.off) else self._ready(l.w, l.b)

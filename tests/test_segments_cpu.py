@@ -1,13 +1,11 @@
 """Host logic of the segmented-row operands (st355_gemm_args.seg_rows): how a [B, rows, C] strided view of a joint [B, S, C] buffer turns into
 (ld, seg_rows, seg_stride) and how the Flux engine decides between ONE segmented problem per stream and one problem per sample.
-No device work: `_seg` only reads shapes / strides, `_problems` only slices views."""
-from types import SimpleNamespace
-
+No device work: `_seg` only reads shapes / strides, `problems` only slices views."""
 import pytest
 import torch
 
+from simpletuner_amd import engine as M
 from simpletuner_amd import ops
-from simpletuner_amd.flux.transformer import FluxTransformer2DModel as M
 from simpletuner_amd.lib import St355Error
 
 
@@ -30,49 +28,44 @@ def test_seg_descriptor_of_views():
         ops._seg_join(512, 256, "t")
 
 
-def _env(B, S, Si, St):
-    return SimpleNamespace(B=B, S=S, Si=Si, St=St)
-
-
 def test_rows_of_and_problem_expansion():
     B, Si, St, C = 4, 512, 256, 8
     S = Si + St
-    env = _env(B, S, Si, St)
     joint = torch.arange(B * S * C, dtype=torch.float32).view(B * S, C)
-    img = M._rows_of(joint, St, Si, env)
+    img = M.rows_of(joint, St, Si, B, S)
     assert img.shape == (B, Si, C) and img.data_ptr() == joint[St].data_ptr() and img.stride() == (S * C, C, 1)
     assert torch.equal(img[2], joint[2 * S + St:3 * S])
     compact = torch.zeros(B * Si, C)
     gate = torch.zeros(B, C)
     # tile-aligned rows: ONE segmented problem, operands untouched
     pr = dict(a=compact, w=torch.zeros(C, C), out=img, aux_in=compact, gate=gate, rows_per_batch=Si, epilogue=2)
-    assert M._problems(env, Si, pr) == [pr]
+    assert M.problems(B, Si, pr) == [pr]
     # rows not a multiple of the 256-row tile: one problem per sample, views / slices per sample, gate row per sample
-    env2 = _env(B, 300 + 40, 300, 40)
-    joint2 = torch.zeros(B * env2.S, C)
-    out2 = M._rows_of(joint2, 40, 300, env2)
+    S2 = 300 + 40
+    joint2 = torch.zeros(B * S2, C)
+    out2 = M.rows_of(joint2, 40, 300, B, S2)
     c2 = torch.zeros(B * 300, C)
-    ps = M._problems(env2, 300, dict(a=c2, w=torch.zeros(C, C), out=out2, gate=gate, rows_per_batch=300))
+    ps = M.problems(B, 300, dict(a=c2, w=torch.zeros(C, C), out=out2, gate=gate, rows_per_batch=300))
     assert len(ps) == B
     for b, q in enumerate(ps):
         assert q["a"].shape == (300, C) and q["a"].data_ptr() == c2[b * 300].data_ptr()
-        assert q["out"].shape == (300, C) and q["out"].data_ptr() == joint2[b * env2.S + 40].data_ptr()
+        assert q["out"].shape == (300, C) and q["out"].data_ptr() == joint2[b * S2 + 40].data_ptr()
         assert q["gate"].shape == (1, C) and q["gate"].data_ptr() == gate[b].data_ptr() and q["rows_per_batch"] == 300
     # batch 1: 3-D views collapse to plain 2-D operands
-    env1 = _env(1, S, Si, St)
     j1 = torch.zeros(S, C)
-    (p1,) = M._problems(env1, Si, dict(a=torch.zeros(Si, C), w=torch.zeros(C, C), out=M._rows_of(j1, St, Si, env1)))
+    (p1,) = M.problems(1, Si, dict(a=torch.zeros(Si, C), w=torch.zeros(C, C), out=M.rows_of(j1, St, Si, 1, S)))
     assert p1["out"].dim() == 2 and p1["out"].data_ptr() == j1[St].data_ptr()
     # operands of the rank-space gradient kernels
-    assert M._compact(img, env, Si) is img                                     # aligned: walked in place
-    assert M._compact(out2, env2, 300).shape == (B * 300, C)                    # unaligned: compact copy
-    assert M._compact(M._rows_of(j1, St, Si, env1), env1, Si).dim() == 2
+    assert M.compact(img, B, Si) is img                                     # aligned: walked in place
+    assert M.compact(out2, B, 300).shape == (B * 300, C)                    # unaligned: compact copy
+    assert M.compact(M.rows_of(j1, St, Si, 1, S), 1, Si).dim() == 2
 
 
 def test_sd3_stream_problems_policy():
     """SD3's joint blocks: aligned image rows -> one segmented problem; the short unaligned text rows -> ONE compact problem with gather copies of the
     joint-buffer inputs and a scatter-back closure for a joint-buffer output; big unaligned blocks (odd aspect buckets) -> one problem per sample."""
-    from simpletuner_amd.sd3.transformer import _rows3, _stream_problems
+    from simpletuner_amd.engine import rows_of as _rows3
+    from simpletuner_amd.sd3.transformer import _stream_problems
 
     B, Si, St, C = 3, 512, 154, 8
     S = Si + St
