@@ -2,7 +2,9 @@
 //     C[M,N] = A[M,K] · B[N,K]^T  (+ A2[M,K2] · B2[N,K2]^T)   with fused epilogues.
 //
 // Common gfx950 design (cdna_hip_programming.md §5):
-//   * v_mfma_f32_32x32x16_bf16; each wave owns a 64x64 output sub-tile (2x2 MFMA tiles, 64 fp32 accumulators / lane).
+//   * v_mfma_f32_32x32x16_bf16; each wave owns a 64x64 output sub-tile (2x2 MFMA tiles, 64 fp32 accumulators / lane).  The NT bf16 K loop of the 256x256
+//     schedules (k_gemm_pq outside conv mode, k_gemm_pz: 64 features x 128 tokens per wave) runs on v_mfma_f32_16x16x32_bf16 instead — less energy per FLOP under the package
+//     power cap (profiles/gemm_mfma16_ab.md) — and hands the epilogues the 32x32 accumulator layout (pq_acc_swap16).
 //   * operands are SWAPPED inside the MFMA (weights = MFMA "A", activations = MFMA "B") so that a lane's 4
 //     consecutive accumulator registers are 4 consecutive FEATURES of one token: row-major C gets 8-byte
 //     packed stores and the epilogue reads bias / gate / residual with the same contiguity.
@@ -846,7 +848,7 @@ __global__ void __launch_bounds__(P3_THREADS, 2) k_gemm_p3(GemmGroup g) {
 //   XA = the first 64 tokens of each group's 128 (tile rows 0-63, 128-191)   XB = the last 64 (64-127, 192-255)
 //   WA = the first 32 features of each wave's 64                            WB = the last 32
 // Phases of K-tile t (buffer t&1):  P0: WA x XA (reads XA, WA)   P1: WB x XA (reads WB)   P2: WB x XB (reads XB)   P3: WA x XB (-)
-// Each phase = 8 MFMAs (2 accumulators x 4 k-steps) and ONE region refill (2 LDS-DMA pieces per wave), issued in the order
+// Each phase = 8 MFMAs of 32x32x16 (2 accumulators x 4 k-steps; NT bf16: the same product as 16 MFMAs of 16x16x32, pq_mma16) and ONE region refill (2 LDS-DMA pieces per wave), issued in the order
 //   ... XA(t+2)@P2  WA(t+2)@P3  WB(t+2)@P0'  XB(t+2)@P1' ...   — every region is refilled >= 2 phases after its last read
 // (WAR-safe across the one-barrier stagger of the two wave groups) and retired by the uniform  s_waitcnt vmcnt(8)  at the end of
 // each phase's load section, 4 phases after its issue (RAW-safe: it is first read one phase after that wait).
@@ -881,7 +883,7 @@ __device__ __forceinline__ i32x8 frag32(const long* p) {       // four consecuti
 #define PQ_PRIO 1                           // raise the wave priority around the MFMA clusters (T5)
 #endif
 #ifndef PQ_GL
-#define PQ_GL 1                             // where a phase issues its LDS-DMA pieces: 0 before the ds_reads, 1 after them, 2 at the end of the previous MFMA section
+#define PQ_GL 1                             // where a phase issues its LDS-DMA pieces: 0 before the ds_reads, 1 after them, 2 at the end of the previous MFMA section, 3 halfway through the MFMA section
 #endif
 
 __device__ __forceinline__ void wait_vm_rt(int n) {    // n = LDS-DMA pieces that may stay in flight (even, 0..8)
@@ -890,6 +892,62 @@ __device__ __forceinline__ void wait_vm_rt(int n) {    // n = LDS-DMA pieces tha
   else if (n == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// ---- the NT bf16 K loop of k_gemm_pq / k_gemm_pz on v_mfma_f32_16x16x32_bf16 ----
+// A phase (32 features x 64 tokens x 64 k) is 16 MFMAs of 16x16x32 on the same 4 + 8 ds_read_b128 fragments as 8 MFMAs of 32x32x16: fragment q = 2 * tile + ks of a
+// 32-row block is row (lane & 15) of 16-row tile `tile` at 16-byte chunk 4 ks + (lane >> 4), swizzled as staged (chunk ^ ((row >> 1) & 7): (row >> 1) & 7 of sixteen
+// consecutive rows are 0..7 twice and row & 1 picks the 128-byte half of the 256-byte bank line, so sixteen consecutive lanes touch 16 distinct 16-byte bank groups).
+// The 16x16 result (lane: token lane & 15, features 4 (lane >> 4) + b of the tile) is accumulated IN PLACE in the f32x16 the epilogues read: the tile of feature half
+// fi and token half tj of a 32 x 32 block owns registers 8 fi + 4 tj + b.  The epilogues' layout (lane: token lane & 31, features 8 a + 4 (lane >> 5) + b, register
+// 4 a + b) differs from that by a rotation of (lane bit 5, lane bit 4, register bit 2):
+//   * the W fragment is read with bits 2 and 3 of its in-tile row swapped (free: the sixteen lanes of a group read the same sixteen rows), which makes lane bit 5
+//     the feature bit 2 and lane bit 4 the feature bit 3 of the result;
+//   * pq_acc_swap16, once after the K loop, exchanges lane bit 4 with register bit 2 (v_permlane16_swap: the odd 16-lane rows of the first register with the even
+//     rows of the second): 64 swaps per wave and output tile.
+// tests/test_gemm_mfma16_map_cpu.py is the index model of this map.
+__device__ __forceinline__ void pq_frag16(int lane, int xbase, int wbase, int (&xk)[4], int (&wk)[4]) {
+  const int l15 = lane & 15, kq = lane >> 4;
+  const int w15 = (l15 & 3) | ((l15 & 4) << 1) | ((l15 & 8) >> 1);
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int tile = q >> 1, ks = q & 1;
+    xk[q] = xbase + (16 * tile + l15) * 128 + (((4 * ks + kq) ^ ((l15 >> 1) & 7)) << 4);
+    wk[q] = wbase + (16 * tile + w15) * 128 + (((4 * ks + kq) ^ ((w15 >> 1) & 7)) << 4);
+  }
+}
+// k half `ks` (32 of the K-tile's 64) of one phase, 8 independent MFMAs: acc0 / acc1 = the two 32-token blocks of the phase's 64 tokens, wf[2 fi + ks] /
+// xf[j][2 tj + ks] as addressed by pq_frag16.  A phase calls it for ks = 0, then 1: an accumulator quarter meets its next MFMA eight MFMAs later.
+__device__ __forceinline__ void pq_mma16(f32x16& acc0, f32x16& acc1, const bf16x8 (&wf)[4], const bf16x8 (&xf)[2][4], int ks) {
+#pragma unroll
+  for (int fi = 0; fi < 2; fi++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int tj = 0; tj < 2; tj++) {
+        f32x16& acc = j ? acc1 : acc0;
+        const int r0 = 8 * fi + 4 * tj;
+        f32x4 c;
+#pragma unroll
+        for (int b = 0; b < 4; b++) c[b] = acc[r0 + b];
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[2 * fi + ks], xf[j][2 * tj + ks], c, 0, 0, 0);
+#pragma unroll
+        for (int b = 0; b < 4; b++) acc[r0 + b] = c[b];
+      }
+}
+__device__ __forceinline__ void pq_acc_swap16(f32x16 (&acc)[2][4]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int fi = 0; fi < 2; fi++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][j][8 * fi + b]), __float_as_uint(acc[i][j][8 * fi + 4 + b]), false, false);
+          acc[i][j][8 * fi + b] = __uint_as_float(r[0]);
+          acc[i][j][8 * fi + 4 + b] = __uint_as_float(r[1]);
+        }
 }
 
 // TN = true: the "weight-gradient" form  C[P,Q] = sum_m L[m,P] R[m,Q]  (GemmP: A = L, B = R, M = P, N = Q, K = contraction length):
@@ -1052,15 +1110,23 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pq(GemmGroup g) {
     else { if (!check || t + 2 < nt) stage_w(t + 2, 0); }
   };
 
-  // fragment addresses: region row (lane&31) + block base, 16-byte chunk (2ks+khalf) ^ ((row>>1)&7)
+  // the plain NT bf16 K loop runs on v_mfma_f32_16x16x32_bf16 (pq_frag16 / pq_mma16 / pq_acc_swap16); TN and fp8 stay on 32x32x16, and so does conv mode: on the
+  // SDXL levels the 16x16x32 loop measured -3.5 ... +0.6 % there (waves of the dead column groups issue no MFMAs, so the power cap binds less and the
+  // accumulator swap is not paid back; profiles/gemm_mfma16_ab.md)
+  constexpr bool M16 = !TN && !F8 && !CONV;
+  // (register budget, -Rpass-analysis=kernel-resource-usage: the NT instances sit at 236-248 of 256 VGPRs, the x GELU' one (EPI 3, its aux rows prefetched) at 256
+  //  with 0 B scratch: it has no headroom left — anything added to its epilogue or kept live across the K loop spills accumulators)
   const int khalf = lane >> 5;
   const int l31 = lane & 31;
-  int xk[4], wk[4];
+  int xk[4] = {}, wk[4] = {};           // NT bf16 fragment addresses (+ j*4096 (32-token block), + region, + buffer); TN and fp8 address their fragments below
+  if (M16) pq_frag16(lane, wm * 64 * 128, 2 * PQ_REGION + wn * 32 * 128, xk, wk);
+  else if (CONV) {                      // 32x32x16: region row (lane&31) + block base, 16-byte chunk (2ks+khalf) ^ ((row>>1)&7)
 #pragma unroll
-  for (int ks = 0; ks < 4; ks++) {
-    const int ch = ((2 * ks + khalf) ^ ((l31 >> 1) & 7)) << 4;
-    xk[ks] = (wm * 64 + l31) * 128 + ch;                       // + j*4096 (block), + region, + buffer
-    wk[ks] = 2 * PQ_REGION + (wn * 32 + l31) * 128 + ch;
+    for (int ks = 0; ks < 4; ks++) {
+      const int ch = ((2 * ks + khalf) ^ ((l31 >> 1) & 7)) << 4;
+      xk[ks] = (wm * 64 + l31) * 128 + ch;
+      wk[ks] = 2 * PQ_REGION + (wn * 32 + l31) * 128 + ch;
+    }
   }
   // TN: transposed-read bases.  group g = lane>>4, ti = (lane>>2)&3 (row inside a 4-row block), ts = lane&3 (4-column segment)
   const int tg = lane >> 4, tti = (lane >> 2) & 3, tts = lane & 3;
@@ -1129,7 +1195,12 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pq(GemmGroup g) {
       _Pragma("unroll") for (int ks = 0; ks < 8; ks++)                                                        \
         _Pragma("unroll") for (int j = 0; j < 2; j++)                                                         \
           acc[I][J0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_fp8_bf8(WF##8[ks], xf8[j][ks], acc[I][J0 + j], 0, 0, 0); \
-    } else if (!CONV || mma_live)                                                                             \
+    } else if (M16) {                                                                                         \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                      \
+        pq_mma16(acc[I][J0], acc[I][J0 + 1], WF, xf, ks);                                                     \
+        if (PQ_GL == 3 && ks == 0) { __builtin_amdgcn_sched_barrier(0); refill(T, PH, TAIL); __builtin_amdgcn_sched_barrier(0); } \
+      }                                                                                                       \
+    } else if (!CONV || mma_live)                             /* TN, conv mode: 32x32x16 */                   \
     _Pragma("unroll") for (int ks = 0; ks < 4; ks++) {                                                        \
       _Pragma("unroll") for (int j = 0; j < 2; j++)                                                           \
         acc[I][J0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(WF[ks], xf[j][ks], acc[I][J0 + j], 0, 0, 0); \
@@ -1258,6 +1329,7 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pq(GemmGroup g) {
       }
     if (tid == 0) __hip_atomic_store(flag, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if (M16) pq_acc_swap16(acc);                         // the epilogues read the layout of the 32x32 MFMA (the stream-K slabs above are lane-linear in either)
   if (EPI == EPI_SPLITK) {
     GemmP ps = p;
     ps.partial = p.partial + (int64_t)slice * p.M * p.part_ld + (int64_t)wtap * p.N;
@@ -1495,15 +1567,8 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pz(GemmP p, int ntiles) 
         wo[r][j] = (uint32_t)((lr >> 5) * 64 + (lr & 31) + r * 32) * ldb_b + scb;
       }
     }
-    const int khalf = ln >> 5;
-    const int l31 = ln & 31;
     int xk[4], wk[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      const int ch = ((2 * ks + khalf) ^ ((l31 >> 1) & 7)) << 4;
-      xk[ks] = (wm * 64 + l31) * 128 + ch;
-      wk[ks] = 2 * PQ_REGION + (wn * 32 + l31) * 128 + ch;
-    }
+    pq_frag16(ln, wm * 64 * 128, 2 * PQ_REGION + wn * 32 * 128, xk, wk);
     auto ld_x = [&](const char* base, int j, int ks) -> bf16x8 { return *(const bf16x8*)(base + xk[ks] + j * 4096); };
     auto ld_w = [&](const char* base, int ks) -> bf16x8 { return *(const bf16x8*)(base + wk[ks]); };
     const bool has_next = tile_id + G < ntiles;
@@ -1580,9 +1645,7 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pz(GemmP p, int ntiles) 
 #define PZ_MMA(WF, I, J0)                                                                                     \
   do {                                                                                                        \
     __builtin_amdgcn_s_setprio(1);                                                                            \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ks++)                                                          \
-      _Pragma("unroll") for (int j = 0; j < 2; j++)                                                           \
-        acc[I][J0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(WF[ks], xf[j][ks], acc[I][J0 + j], 0, 0, 0); \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ks++) pq_mma16(acc[I][J0], acc[I][J0 + 1], WF, xf, ks);        \
     __builtin_amdgcn_s_setprio(0);                                                                            \
   } while (0)
 
@@ -1639,6 +1702,7 @@ __global__ void __launch_bounds__(PQ_THREADS, 2) k_gemm_pz(GemmP p, int ntiles) 
     if (wm == 0) PP_BARRIER();                         // pairs with group 1's extra barrier: every wave is past its last ring read of this tile
     // in flight now (has_next): WB(n0) XB(n0) [issued in the last K-tile's P0 / P1] and XA(n1) WA(n1) [P2 / P3]; retire the first two BEFORE any store
     wait_vm_rt(4);
+    pq_acc_swap16(acc);                                // into the layout the epilogue reads
     {
       GemmP ps = p;
       ps.C = p.C + cur.segi * p.seg_xc;
