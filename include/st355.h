@@ -293,6 +293,10 @@ int st355_skinny_tn_seg(void* stream, const void* L, int64_t ldl, const void* R,
                         float* out, int64_t so_p, int64_t so_r, int64_t M, int64_t P, int Rn, int r_used,
                         float alpha, int accumulate, void* workspace, int64_t seg_rows, int64_t seg_l, int64_t seg_r);
 
+/* the split-M plan st355_skinny_tn / _seg / _multi would launch for this shape, without launching anything: out2 = {rows per workgroup (256 / 512 / 1024),
+ * number of chunks = partials the reduce sums}.  Calls the launchers' own chunk choice. */
+int st355_skinny_plan(int64_t M, int64_t P, int64_t seg_rows, int32_t* out2);
+
 /* nout (1..4) adapters sharing L: outs[g][p*so_p + r*so_r] (+)= alpha * sum_m L[m,p] * R[m, 32 g + r], r < r_used <= 32; R has 128 columns (row stride ldr).
  * One pass over L instead of nout (the q / k / v adapters of a fused projection).  workspace: st355_skinny_tn_workspace(M, P, 128) bytes. */
 int st355_skinny_tn_multi(void* stream, const void* L, int64_t ldl, const void* R, int64_t ldr, float* const* outs, int nout,

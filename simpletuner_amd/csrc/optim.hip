@@ -145,8 +145,9 @@ extern "C" int st355_adamw_ema_step_bf16(void* stream, void* p, const void* g, f
 // parameter are updated with stochastic rounding (a random 16-bit integer added to the fp32 bit pattern before truncation); weight
 // decay is owed per tensor and applied to `shift` only once it exceeds 5e-3.  The reference runs ~25 small kernels per parameter
 // tensor with fp32 temporaries; here it is ONE pass over a flat arena: 5 bf16 reads + 4 bf16 writes = 18 B/param.
-// Every operation below keeps the reference's order and rounding points (no FMA contraction: the fp32 temporaries of the reference
-// are separate multiply / add / divide results), so that with the same random draws the states are bit-identical.
+// Every operation below keeps the reference's order and rounding points (contraction is off: the fp32 temporaries of the reference
+// are separate multiply / add / divide results; the one fused multiply-add it does make, inside addcmul, is an explicit fmaf), so
+// that with the same random draws the states are bit-identical.
 struct Bf16OptC {
   float beta1, one_m_beta1, beta2, one_m_beta2, eps, value /* -lr * sqrt(1 - beta2^step) */, grad_scale;
 };
@@ -156,6 +157,9 @@ __device__ __forceinline__ bf16 sr_bf16(float x, uint32_t r16) {           // co
   return __builtin_bit_cast(bf16, (uint16_t)(bits >> 16));
 }
 
+// (the pragma binds only under -ffp-contract=fast-honor-pragmas, which the Makefile sets for this file: plain =fast fused g + (1 - beta1) m1 and the decay add
+// anyway, one element in ~2^16 then drew a different stochastic rounding than the reference.  The one fused multiply-add the reference does have is written out:
+// ATen's CPU addcmul evaluates self + (value * t1) * t2 with the last product and the sum contracted, which is what produced the golden states.)
 #pragma clang fp contract(off)
 __device__ __forceinline__ void adamw_bf16_one(bf16& p, bf16 g_in, bf16& m, bf16& v, bf16& sh, const Bf16OptC& c, float decay,
                                                const uint32_t (&r)[4]) {
@@ -164,7 +168,7 @@ __device__ __forceinline__ void adamw_bf16_one(bf16& p, bf16 g_in, bf16& m, bf16
   const bf16 m1 = f2bf(bf2f(m) * c.beta1);                                // exp_avg.mul_(beta1)
   const bf16 m_new = sr_bf16(g + c.one_m_beta1 * bf2f(m1), r[0]);         // add_stochastic_(exp_avg, grad, alpha): other + alpha*input (sic)
   const bf16 v1 = f2bf(bf2f(v) * c.beta2);                                // exp_avg_sq.mul_(beta2)
-  const bf16 v_new = f2bf(bf2f(v1) + (c.one_m_beta2 * g) * g);            // .addcmul_(grad, grad, value=1-beta2)
+  const bf16 v_new = f2bf(__builtin_fmaf(c.one_m_beta2 * g, g, bf2f(v1)));  // .addcmul_(grad, grad, value=1-beta2): fma((1-beta2) g, g, v1), as ATen
   const bf16 denom = f2bf(bf2f(f2bf(sqrtf(bf2f(v_new)))) + c.eps);        // exp_avg_sq.sqrt().add_(eps)
   const bf16 sh1 = sr_bf16(bf2f(sh) + (c.value * bf2f(m_new)) / bf2f(denom), r[1]);   // addcdiv_stochastic_(shift, exp_avg, denom, value)
   const bf16 p_new = sr_bf16(bf2f(sh1) + bf2f(p), r[2]);                  // add_stochastic_(p, shift)

@@ -226,6 +226,14 @@ static int skinny_chunk(int64_t M, int64_t P, int64_t seg_rows) {
     if ((seg_rows == 0 || seg_rows % mc == 0) && cdiv64(M, mc) * pt >= 512) return mc;
   return SK_MC;
 }
+// what the launchers below would run for this shape, without launching anything: out2 = {mc, nchunks}
+extern "C" int st355_skinny_plan(int64_t M, int64_t P, int64_t seg_rows, int32_t* out2) {
+  ST_REQUIRE(out2 && M > 0 && P > 0 && seg_rows >= 0, "skinny_plan: bad arguments");
+  const int mc = skinny_chunk(M, P, seg_rows);
+  out2[0] = mc;
+  out2[1] = (int32_t)cdiv64(M, mc);
+  return 0;
+}
 extern "C" size_t st355_skinny_tn_workspace(int64_t M, int64_t P, int Rn) {
   return (size_t)cdiv64(M, SK_MC) * (size_t)P * (size_t)Rn * sizeof(float);
 }

@@ -721,7 +721,18 @@ def transpose(src, out=None):
     return out
 
 
+# One split-M workspace per device, not per (device, stream) as grad_norm's scratch: no caller issues skinny products on two streams at once.  LoraGroup.grads and
+# the block megakernels run on the training stream; the trainer's graph warm-up / capture stream is joined with wait_stream before and after, so the two never
+# overlap; grad_sync's comm stream runs collectives only.  A caller that does overlap them must bring its own workspace through the C ABI.
 _skinny_ws = {}
+
+
+def skinny_plan(M: int, P: int, seg_rows: int = 0):
+    """st355_skinny_plan: the split-M plan skinny_tn / skinny_tn_multi would launch for this shape ({"mc": rows per workgroup, "nchunks": partials the
+    reduce sums}), from the launchers' own chunk choice, without launching anything"""
+    out = (C.c_int32 * 2)()
+    _l.check(_l.load().st355_skinny_plan(int(M), int(P), int(seg_rows), out), "skinny_plan")
+    return {"mc": int(out[0]), "nchunks": int(out[1])}
 
 
 def skinny_tn(Lm, R, out, so_p: int, so_r: int, r_used: int, alpha: float = 1.0, accumulate: bool = False):
