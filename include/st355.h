@@ -456,6 +456,17 @@ int st355_muon_step(void* stream, const int64_t* plan_host, const int64_t* plan_
 int st355_muon_orthogonalize(void* stream, const int64_t* plan_host, const int64_t* plan_dev, const float* x, float* out, float* ws,
                              int64_t ws_floats, int normalize, double eps, int ns_steps, const float* coeffs);
 
+/* ---- LayerSync (helpers/training/layersync.py): self-alignment of two block outputs, cosine per token row, F.normalize semantics x / max(|x|, 1e-12) ----
+ * student, teacher: [B, rows, D] bf16 views with row stride ld and their own batch strides (elements), e.g. the image rows of a joint [B * S, D] buffer; the
+ * teacher is a constant (detached).  Per row c = <s^, t^> -> cos_rows[B * rows] fp32; G[B * rows, D] bf16 (compact) = (t^ - c s^) / max(|s|, 1e-12) / (B * rows)
+ * = d mean(c) / d s; G may be the student buffer itself.  A second single-block launch sums cos_rows in a fixed order: sim[0] = mean(c) — no atomics, two calls
+ * on the same inputs are bit-identical.  fp32 arithmetic, D % 8 == 0, D <= 4096, 16-byte aligned operands.  ws: not used (pass NULL).
+ * st355_layersync_inject: dx[b, r, :] = bf16(float(dx) + scale_dev[0] * float(G)) over a view of the same kind; scale_dev = ONE fp32 on the device (the upstream
+ * gradient of sim as autograd hands it over: no host read). */
+int st355_layersync_fwd(void* stream, const void* student, const void* teacher, void* G, float* cos_rows, float* sim, int B, int rows, int D, int64_t ld,
+                        int64_t s_bstride, int64_t t_bstride, void* ws);
+int st355_layersync_inject(void* stream, void* dx, const void* G, const float* scale_dev, int B, int rows, int D, int64_t ld, int64_t bstride);
+
 /* LoRA operand packing (K12): from fp32 A[r,K], B[N,r] write the bf16 GEMM operands of ONE adapter into the (zero-initialised)
  * block-structured operands of a fused projection group with K2 padded low-rank columns and N_total outputs:
  *   A_cat   [K2,K]       rows  k2_off..k2_off+r-1      = A

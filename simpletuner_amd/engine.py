@@ -2,6 +2,7 @@
 
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
+  * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `pad64` / `pad64_empty`: operands of the TN weight-gradient GEMM (contraction granule: 64 rows);
   * `ArenaModule`: every base parameter a view of ONE bf16 arena (two-pass construction), checkpoint load / save over the parameter names;
   * `FullGrads`: the per-backward helper of full-rank training — weight / bias gradients into the gradient arena, the modulation rows' reductions, the fused
@@ -124,6 +125,48 @@ def compact(t, B: int, rows: int):
     if B == 1:
         return t[0]
     return t if rows % 256 == 0 else t.reshape(B * rows, -1)
+
+
+# ------------------------------------------------------------------------------------------------
+# LayerSync (helpers/training/layersync.py): the regulariser's forward taps and its gradient's way into the hand-written dX chain
+# ------------------------------------------------------------------------------------------------
+def layersync_indices(student_idx, teacher_idx, n_blocks: int):
+    """validated 0-based (student, teacher) block indices of `set_layersync`; the teacher defaults to the student (the reference's default when
+    `layersync_teacher_block` is unset: similarity 1, gradient 0 up to rounding)"""
+    s = int(student_idx)
+    t = s if teacher_idx is None else int(teacher_idx)
+    for role, i in (("student", s), ("teacher", t)):
+        if not 0 <= i < n_blocks:
+            raise ValueError(f"set_layersync: {role} block {i} is out of range (this model has {n_blocks} blocks)")
+    if t < s:
+        raise ValueError(f"set_layersync: the teacher block ({t}) must not lie below the student block ({s})")
+    return s, t
+
+
+class LayerSyncTap:
+    """One per training forward (kept in its ctx).  `tap(g, view)` after block g of the saving forward — never in the recompute pass of a checkpointed segment —
+    copies the student block's image-token rows [B, rows, D] into ONE compact bf16 buffer and, at the teacher block, turns that buffer in place into
+    G = d sim / d student (ops.layersync_fwd; the teacher is read as the view it is).  `inject(view, dsim)` right before the student block's own backward adds
+    dsim * G to the gradient with respect to that block's output; dsim stays on the device (it carries -lambda, the accumulation division and any loss scale)."""
+
+    def __init__(self, student: int, teacher: int):
+        self.student, self.teacher = student, teacher
+        self.G = self.cos = self.sim = None
+
+    def tap(self, g: int, view):
+        if g == self.student:
+            B, rows, D = view.shape
+            self.G = torch.empty(B * rows, D, dtype=BF16, device=view.device)
+            self.cos = torch.empty(B * rows, dtype=F32, device=view.device)
+            self.sim = torch.empty((), dtype=F32, device=view.device)
+            self.G.view(B, rows, D).copy_(view)
+        if g == self.teacher:
+            B, rows, D = view.shape
+            ops.layersync_fwd(self.G.view(B, rows, D), view, self.G, self.cos, self.sim)
+
+    def inject(self, view, dsim):
+        ops.layersync_inject(view, self.G, dsim.detach().to(F32))
+        self.G = None
 
 
 # ------------------------------------------------------------------------------------------------

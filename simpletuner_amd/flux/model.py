@@ -222,7 +222,7 @@ class Flux(ModelFoundation):
                 raise ValueError("No attention mask was discovered when attempting validation - this means you need to recreate your text embed cache.")
             if attention_mask.dim() == 3 and attention_mask.size(1) == 1:
                 attention_mask = attention_mask.squeeze(1)          # [B, 1, S] -> [B, S]
-        model_pred = self.model(
+        res = self.model(
             hidden_states=packed,
             timestep=prepared_batch["timesteps"],
             guidance=guidance,
@@ -234,13 +234,15 @@ class Flux(ModelFoundation):
             return_dict=False,
             attention_mask=attention_mask,
             rope_layout_key=rope_key,
-        )[0]
+        )
+        model_pred = res[0]
         if use_cond and getattr(self.config, "model_flavour", None) == "kontext":      # drop the reference-image tokens before unpacking (flux/model.py:844-847)
             model_pred = model_pred[:, :scene_len, :]
         return {
             "model_prediction": _UnpackFn.apply(model_pred, Hh * 8, Ww * 8),
             "crepa_hidden_states": None,
             "hidden_states_buffer": None,
+            **({"layersync_similarity": res[1]} if len(res) > 1 else {}),          # LayerSync (set_layersync): the training forward's second output
         }
 
 

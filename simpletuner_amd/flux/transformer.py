@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ArenaModule, FullGrads, LoraGroup, attach, compact, frozen, mod_grads, pad64, problems, rows_of
+from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, mod_grads, pad64, problems, rows_of
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_QK_NORM_ROPE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -92,6 +92,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.grad_sync = None            # training.grad_sync.GradSync over lora_grad_flat / grad_arena (data-parallel replicas)
         self._last_grad_flat = None
         self.full = False                # enable_full_finetune(): every base parameter trains
+        self._layersync: Optional[Tuple[int, int]] = None      # set_layersync(): 0-based (student, teacher) block indices, double blocks first
 
     def _build(self):
         c = self.config
@@ -748,6 +749,10 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         # nothing below the first block that carries an adapter is differentiated (add_lora_adapter: 'tiny' / 'nano' start at single block 7): those blocks keep
         # no activations and no checkpoint inputs
         stop = 0 if full else getattr(self, "_bwd_stop", 0)
+        ls = None
+        if save and self._layersync is not None:
+            self._layersync_refusals(stop, tokenwise)
+            ls = ctx.ls = LayerSyncTap(*self._layersync)
         # ---- double blocks ----
         for (s0, n, ck) in segs_d:
             for bi in range(s0, s0 + n):
@@ -759,6 +764,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                 img, txt, x, sv = self._double_fwd(bi, img, txt, rt.env, save and not ck and bi >= stop)
                 if sv is not None:
                     ctx.dbl[bi] = sv
+                if ls is not None:                            # LayerSync: the block's image-token output (the last double block wrote the joint sequence)
+                    ls.tap(bi, img.view(B, Si, D) if x is None else rows_of(x, St, Si, B, S))
                 if ends(bi):
                     if x is not None:                         # the last double block wrote the joint [txt || kept img] sequence: re-open it
                         xv = x.view(B, rt.env.S, D)
@@ -785,6 +792,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                 x, sv = self._single_fwd(bi, x, rt.env, save and not ck and g >= stop)
                 if sv is not None:
                     ctx.sgl[bi] = sv
+                if ls is not None:
+                    ls.tap(g, rows_of(x, St, Si, B, S))
                 if ends(g):
                     xv = x.view(B, rt.env.S, D)
                     t_part = xv[:, :St]
@@ -1044,9 +1053,10 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_txt, _ = ops.ln_modulate_bwd(dns[1], sv.txt, mt[:, D:2 * D], St, dres=dx1_t)
         return d_img, d_txt
 
-    def _engine_backward(self, ctx, dout):
+    def _engine_backward(self, ctx, dout, dsim=None):
         """hand-written backward for frozen-base (LoRA) training: dX chain + rank-space adapter gradients.  Checkpointed segments are re-run from
-        their kept input first (same kernels, same order: the recomputed activations are bit-identical to the ones a plain forward keeps)."""
+        their kept input first (same kernels, same order: the recomputed activations are bit-identical to the ones a plain forward keeps).
+        dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the chain at the student block's output."""
         if not self._prepared:
             raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
         D = self.D
@@ -1073,6 +1083,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         stop = getattr(self, "_bwd_stop", 0)          # global index of the first block with an adapter (add_lora_adapter)
         dxg = d_txt = d_img = d_full = None
         keep_of = lambda info: info.keep_i32()
+        ls = getattr(ctx, "ls", None)
         for (s0, n, ck) in reversed(ctx.segs_s):
             if ck:
                 # a segment that straddles the stop block: blocks below it are re-run (their outputs feed the ones above) but keep nothing — the backward returns at `stop`
@@ -1089,6 +1100,9 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                     d_full = dxv[:, St:].contiguous()
                     dx = torch.cat([dxv[:, :St], ops.gather_rows(d_full, keep_of(ctx.route_end[g]))], dim=1).reshape(-1, D)
                     dxg = None
+                if ls is not None and g == ls.student:
+                    ls.inject(rows_of(dx, St, Si, B, S), dsim)
+                    dxg = None                               # the pre-gated copy of dx is stale: _single_bwd / the block entry point gate the new dx themselves
                 dx, dxg, d_txt, d_img = self._single_bwd(li, ctx.sgl.pop(li), dx, dxg, e)
                 if g == stop and g > 0:
                     ctx.sgl.clear(); ctx.dbl.clear(); ctx.ck_s.clear(); ctx.ck_d.clear()
@@ -1119,6 +1133,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                 if li in ctx.route_end:
                     d_full = d_img.view(B, Si, D)
                     d_img = ops.gather_rows(d_full, keep_of(ctx.route_end[li])).view(-1, D)
+                if ls is not None and li == ls.student:      # (the last double block: single block 0 handed its input gradient back stream-major)
+                    ls.inject(d_img.view(B, Si, D), dsim)
                 d_img, d_txt = self._double_bwd(li, ctx.dbl.pop(li), d_img, d_txt, e)
                 if li == stop and li > 0:
                     ctx.dbl.clear(); ctx.ck_d.clear()
@@ -1255,7 +1271,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_txt_in, _ = ops.ln_modulate_bwd(dn_t, sv.txt, mt[:, D:2 * D], St, dres=dx1_t)
         return d_img_in, d_txt_in
 
-    def _engine_backward_full(self, ctx, dout):
+    def _engine_backward_full(self, ctx, dout, dsim=None):
         """hand-written backward of full-rank training: the dX chain of `_engine_backward` plus a TN weight-gradient GEMM and a bias column sum per Linear,
         token-axis reductions for the modulation rows / gates, the q / k RMSNorm weight gradients, and the embedders.  Checkpointed segments are re-run from
         their kept input first (same kernels, same order, bit-identical activations)."""
@@ -1287,6 +1303,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
         # the fused modulation matrix (3.2 B of Flux.1-dev's 11.9 B parameters, 6.5 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
+        ls, nd = getattr(ctx, "ls", None), len(self.double)         # LayerSync: dsim * G enters at the student block's output (see _engine_backward)
         # ---- single blocks, reversed ----
         for (s0, n, ck) in reversed(ctx.segs_s):
             if ck:
@@ -1295,6 +1312,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                     xr, ctx.sgl[bi] = self._single_fwd(bi, xr, ctx.env_s[bi], True)
                 del xr
             for li in range(s0 + n - 1, s0 - 1, -1):
+                if ls is not None and nd + li == ls.student:
+                    ls.inject(rows_of(dx, St, Si, B, S), dsim)
                 dx = self._single_bwd_full(li, ctx.sgl.pop(li), dx, ctx.env_s[li], fb)
                 if sync is not None:
                     sync.ready(self.single[li].arena_lo, self.single[li].arena_hi)
@@ -1311,6 +1330,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                     ir, tr, _, ctx.dbl[bi] = self._double_fwd(bi, ir, tr, ctx.env_d[bi], True)
                 del ir, tr
             for li in range(s0 + n - 1, s0 - 1, -1):
+                if ls is not None and li == ls.student:
+                    ls.inject(d_img.view(B, Si, D), dsim)
                 d_img, d_txt = self._double_bwd_full(li, ctx.dbl.pop(li), d_img, d_txt, ctx.env_d[li], fb)
                 if sync is not None:
                     sync.ready(self.double[li].arena_lo, self.double[li].arena_hi)
@@ -1330,6 +1351,21 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
     # ------------------------------------------------------------------------------------------------
     # public forward (reference signature: flux/transformer.py:940-960)
     # ------------------------------------------------------------------------------------------------
+    def set_layersync(self, student_idx, teacher_idx=None):
+        """LayerSync (helpers/training/layersync.py; the reference captures at flux/transformer.py:1326 / 1499): 0-based block indices, double blocks first, then
+        single blocks, as the reference's `capture_idx` counts.  A training forward then also returns the mean cosine between the two blocks' image-token outputs
+        (teacher detached) and the backward adds its gradient into the dX chain at the student block."""
+        self._layersync = layersync_indices(student_idx, teacher_idx, len(self.double) + len(self.single))
+
+    def _layersync_refusals(self, stop: int, tokenwise: bool):
+        if self._tread_router is not None:
+            raise NotImplementedError("LayerSync under TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
+        if tokenwise:
+            raise NotImplementedError("LayerSync with tokenwise timesteps is not built on the st355 path")
+        if self._layersync[0] < stop:
+            raise NotImplementedError(f"LayerSync: student block {self._layersync[0]} lies below the first block that carries an adapter ({stop}: the 'tiny' / 'nano' target "
+                                      f"sets): the backward never reaches it")
+
     def set_router(self, router, routes):
         """flux/transformer.py:829-831: TREAD router + [{selection_ratio, start_layer_idx, end_layer_idx}] (training/tread.py)"""
         self._tread_router, self._tread_routes = router, routes
@@ -1360,6 +1396,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             key_bias = torch.ones(B_, S_tot, dtype=F32, device=self.device_)
             key_bias[:, :am.shape[1]] = (am.to(self.device_) > 0).to(F32)
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or self.full)
+        sim = None                                         # LayerSync (set_layersync): the training nodes return the similarity as a second output
         if need_grad and not self._prepared:
             # the K-major dgrad operands follow the weights: load_flat_state / init_synthetic / the replica start-state broadcast
             # (training.grad_sync.sync_module_states) mark them stale, the next training forward rebuilds them
@@ -1367,16 +1404,20 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         if need_grad and self.full:
             out = _FluxFullFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, guidance, img_ids, txt_ids, key_bias,
                                     *self._full_params)
+            if self._layersync is not None:
+                out, sim = out
         elif need_grad:
             out = _FluxFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, guidance, img_ids, txt_ids, key_bias,
                                 *self._lora_params)
+            if self._layersync is not None:
+                out, sim = out
         else:
             with torch.no_grad():
                 out, _ = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep,
                                               guidance, img_ids, txt_ids, save=False, key_bias=key_bias)
         if not return_dict:
-            return (out,)
-        return SimpleNamespace(sample=out)
+            return (out,) if sim is None else (out, sim)
+        return SimpleNamespace(sample=out) if sim is None else SimpleNamespace(sample=out, layersync_similarity=sim)
 
 
 class _FluxFn(torch.autograd.Function):
@@ -1387,14 +1428,14 @@ class _FluxFn(torch.autograd.Function):
         out, ctx = model._engine_forward(hidden_states.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(),
                                          None if guidance is None else guidance.detach(), img_ids, txt_ids, save=True, key_bias=key_bias)
         fctx.model, fctx.ectx, fctx.n_lora = model, ctx, len(lora_params)
-        return out
+        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
 
     @staticmethod
-    def backward(fctx, dout):
+    def backward(fctx, dout, dsim=None):
         model = fctx.model
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout)
+        model._engine_backward(fctx.ectx, dout, dsim)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()   # all slices reduced (SUM); optimizer folds 1/world
@@ -1419,14 +1460,14 @@ class _FluxFullFn(torch.autograd.Function):
         out, ctx = model._engine_forward(hidden_states.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(),
                                          None if guidance is None else guidance.detach(), img_ids, txt_ids, save=True, key_bias=key_bias, full=True)
         fctx.model, fctx.ectx = model, ctx
-        return out
+        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
 
     @staticmethod
-    def backward(fctx, dout):
+    def backward(fctx, dout, dsim=None):
         model = fctx.model
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout)
+        model._engine_backward_full(fctx.ectx, dout, dsim)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world

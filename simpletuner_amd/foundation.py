@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import math
 from enum import Enum
+from types import SimpleNamespace
 from typing import Any, Dict, Optional, Type
 
 import torch
@@ -455,12 +456,53 @@ class ModelFoundation(ExplorativeModelingMixin):
 
     def post_model_load_setup(self):
         """common.py:3638 / 6704 (ImageModelFoundation).  The reference attaches its representation-alignment regularisers here (LayerSync, internal guidance,
-        NextLat, CREPA / U-REPA: hooks into a diffusers module's blocks).  None of them is built on the st355 path: asking for one is refused, otherwise there is
-        nothing to set up — defined here so that a reference flow calling it never reaches the reference's regulariser initialisers through the MRO."""
-        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled", "layersync_enabled", "internal_guidance_enabled", "nextlat_enabled"):
+        NextLat, CREPA / U-REPA: hooks into a diffusers module's blocks).  LayerSync is built for the components that expose `set_layersync` (Flux, SD3: it needs
+        nothing outside the model); asking for any other is refused — defined here so that a reference flow calling it never reaches the reference's regulariser
+        initialisers through the MRO."""
+        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled", "internal_guidance_enabled", "nextlat_enabled"):
             if getattr(self.config, flag, False):
                 raise NotImplementedError(f"{flag}: representation-alignment regularisers hook diffusers modules and are not built on the st355 path")
+        self.layersync = None
+        if getattr(self.config, "layersync_enabled", False):
+            self._layersync_init()
         return None
+
+    @staticmethod
+    def _layersync_resolve(idx, role: str, n_blocks: int) -> int:
+        """layersync.py:72-93 `_resolve_layer` over the layers the reference captures for it (common.py:5237-5243: idx and idx - 1): an index i > 0 names the
+        0-based block i - 1 (depths start at 1), 0 names block 0"""
+        if idx is None:
+            raise ValueError(f"LayerSync could not find {role} layer because no index was provided.")
+        try:
+            i = int(idx)
+        except Exception as exc:
+            raise ValueError(f"LayerSync {role} index {idx!r} is not an int.") from exc
+        candidates = ([i - 1] if i > 0 else []) + [i]
+        for cand in candidates:
+            if 0 <= cand < n_blocks:
+                return cand
+        raise ValueError(f"LayerSync could not find {role} layer at indices {candidates}.")
+
+    def _layersync_init(self):
+        """layersync.py:14-25 (LayerSyncRegularizer.__init__) + the index resolution, then the trained component is told which two block outputs to align"""
+        cfg = self.config
+        comp = self.unwrap_model(self.get_trained_component()) if self.get_trained_component() is not None else None
+        if comp is None or not hasattr(comp, "set_layersync"):
+            raise NotImplementedError(f"layersync_enabled: LayerSync is not built for {self.NAME} on the st355 path (built: Flux, SD3)")
+        tc = getattr(cfg, "tread_config", None)
+        if tc and tc.get("routes", None):
+            raise NotImplementedError("layersync_enabled with TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
+        student, teacher = getattr(cfg, "layersync_student_block", None), getattr(cfg, "layersync_teacher_block", None)
+        weight = float(getattr(cfg, "layersync_lambda", 0.2) or 0.2)          # "match LayerSync paper default when enabled"
+        if student is None:
+            raise ValueError("layersync_student_block must be set when LayerSync is enabled.")
+        if weight <= 0:
+            raise ValueError("layersync_lambda must be greater than zero when LayerSync is enabled.")
+        n = int(comp.config.num_layers) + int(getattr(comp.config, "num_single_layers", 0) or 0)
+        s = self._layersync_resolve(student, "student", n)
+        t = self._layersync_resolve(teacher if teacher is not None else student, "teacher", n)
+        comp.set_layersync(s, t)
+        self.layersync = SimpleNamespace(weight=weight, student=s, teacher=t)
 
     def post_quantization_setup(self):
         """common.py:3650"""
@@ -1117,7 +1159,16 @@ class ModelFoundation(ExplorativeModelingMixin):
         return self.loss(prepared_batch, model_output, apply_conditioning_mask), None
 
     def auxiliary_loss(self, model_output, prepared_batch: dict, loss: torch.Tensor):
-        return loss, None
+        """common.py:5364-5374 `_apply_layersync_regularizer`: loss - lambda * similarity, the two logs as host floats (layersync.py:55-58).  The similarity and its
+        gradient come from the engine (model_output["layersync_similarity"]); the `.item()` reads happen here, outside it."""
+        ls = getattr(self, "layersync", None)
+        if ls is None:
+            return loss, None
+        sim = model_output.get("layersync_similarity") if isinstance(model_output, dict) else None
+        if sim is None:
+            raise ValueError("LayerSync enabled but no hidden state buffer was provided.")          # layersync.py:33-34: the prediction did not come from a training forward
+        ls_loss = -sim * ls.weight
+        return loss + ls_loss, {"layersync_loss": ls_loss.detach().item(), "layersync_similarity": sim.detach().item()}
 
 
 class _CondLossFn(torch.autograd.Function):

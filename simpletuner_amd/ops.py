@@ -1076,6 +1076,42 @@ def muon_orthogonalize(plan: MuonPlan, x, coeffs, normalize: bool = True, eps: f
     return out
 
 
+def _token_view(t, name: str):
+    """a [B, rows, D] bf16 view with unit inner stride (e.g. the image rows of a joint [B * S, D] buffer): (B, rows, D, row stride, batch stride)"""
+    _chk(t, BF16, name)
+    if t.dim() != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
+        raise _l.St355Error(f"{name}: expected a [B, rows, D] view with unit inner stride, got shape {tuple(t.shape)} stride {t.stride()}")
+    return t.shape[0], t.shape[1], t.shape[2], t.stride(1), t.stride(0)
+
+
+def layersync_fwd(student, teacher, G, cos_rows, sim):
+    """LayerSync (st355_layersync_fwd): student / teacher [B, rows, D] bf16 views of one row stride; cos_rows[B * rows] fp32 = the per-token cosine, sim (one fp32)
+    = its mean, G [B * rows, D] bf16 contiguous = d sim / d student.  G may be the student's own (compact) buffer.  Writes into the tensors given, allocates nothing."""
+    L = _l.load()
+    B, rows, D, ld, sb = _token_view(student, "student")
+    Bt, rt, Dt, ldt, tb = _token_view(teacher, "teacher")
+    _chk(G, BF16, "G"); _chk(cos_rows, F32, "cos_rows"); _chk(sim, F32, "sim")
+    if (Bt, rt, Dt, ldt) != (B, rows, D, ld):
+        raise _l.St355Error(f"layersync_fwd: student {tuple(student.shape)} (row stride {ld}) and teacher {tuple(teacher.shape)} (row stride {ldt}) must agree")
+    if not G.is_contiguous() or G.numel() != B * rows * D or not cos_rows.is_contiguous() or cos_rows.numel() != B * rows or sim.numel() != 1:
+        raise _l.St355Error("layersync_fwd: G must be contiguous with B * rows * D elements, cos_rows contiguous with B * rows, sim one element")
+    if G.data_ptr() == student.data_ptr() and not student.is_contiguous():
+        raise _l.St355Error("layersync_fwd: G may alias the student only when the student is compact")
+    _l.check(L.st355_layersync_fwd(_stream(), _ptr(student), _ptr(teacher), _ptr(G), _ptr(cos_rows), _ptr(sim), B, rows, D, ld, sb, tb, None), "layersync_fwd")
+    return G, cos_rows, sim
+
+
+def layersync_inject(dx, G, scale):
+    """dx[b, r, :] = bf16(float(dx) + scale * float(G)) in place (st355_layersync_inject): dx a [B, rows, D] bf16 view, G [B * rows, D] contiguous, scale ONE fp32 on the device"""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(dx, "dx")
+    _chk(G, BF16, "G"); _chk(scale, F32, "scale")
+    if not G.is_contiguous() or G.numel() != B * rows * D or scale.numel() != 1:
+        raise _l.St355Error("layersync_inject: G must be contiguous with B * rows * D elements, scale one fp32 element")
+    _l.check(L.st355_layersync_inject(_stream(), _ptr(dx), _ptr(G), _ptr(scale), B, rows, D, ld, bs), "layersync_inject")
+    return dx
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

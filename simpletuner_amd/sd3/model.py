@@ -54,14 +54,17 @@ class SD3(ModelFoundation):
         """sd3/model.py:540-570"""
         self._require_per_sample_timesteps(prepared_batch, tokenwise_ok=True)      # [B] or tokenwise [B, S_img], handed through unchanged (sd3/model.py:542)
         dev = self.accelerator.device
-        model_pred = self.model(
+        res = self.model(
             hidden_states=prepared_batch["noisy_latents"].to(device=dev, dtype=BF16),
             timestep=prepared_batch["timesteps"].to(device=dev, dtype=torch.float32),
             encoder_hidden_states=prepared_batch["encoder_hidden_states"].to(device=dev, dtype=BF16),
             pooled_projections=prepared_batch["add_text_embeds"].to(device=dev, dtype=BF16),
             return_dict=False,
-        )[0]
-        return {"model_prediction": model_pred, "crepa_hidden_states": None, "hidden_states_buffer": None}
+        )
+        out = {"model_prediction": res[0], "crepa_hidden_states": None, "hidden_states_buffer": None}
+        if len(res) > 1:                  # LayerSync (set_layersync): the training forward's second output
+            out["layersync_similarity"] = res[1]
+        return out
 
 
 ModelRegistry.register("sd3", SD3)

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ArenaModule, FullGrads, LoraGroup, attach, compact, frozen, pad64_empty, problems, rows_of, sincos_2d_hw
+from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, pad64_empty, problems, rows_of, sincos_2d_hw
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -109,6 +109,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.gradient_checkpointing_interval = None
         self.gradient_checkpointing_segment_stride = None
         self._tread_router, self._tread_routes = None, None
+        self._layersync = None           # set_layersync(): 0-based (student, teacher) joint-block indices
         self.grad_sync = None
         self._last_grad_flat = None
         self.full = False
@@ -595,6 +596,13 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             from ..training.checkpoint_plan import per_block as _per_block
             ctx.segs = _per_block(len(self.blocks), bool(self.gradient_checkpointing), self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride)
         ctx.envs, ctx.route_start, ctx.route_end = [env] * len(self.blocks), {}, {}
+        ls = None
+        if save and self._layersync is not None:
+            if self._tread_router is not None:
+                raise NotImplementedError("LayerSync under TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
+            if tokenwise:
+                raise NotImplementedError("LayerSync with tokenwise timesteps is not built on the st355 path")
+            ls = ctx.ls = LayerSyncTap(*self._layersync)
         rp, info, saved, env_cur = 0, None, None, env
         for (s0, n, ck) in ctx.segs:
             for bi in range(s0, s0 + n):
@@ -609,6 +617,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     ctx.ck[s0] = (img, txt)
                 ctx.envs[bi] = env_cur
                 img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, env_cur, save and not ck)
+                if ls is not None:                            # LayerSync: the block's image-stream output (the recompute pass, _recompute_segment, never taps)
+                    ls.tap(bi, img.view(B, Si, D))
                 if info is not None and bi == routes[rp]["end_layer_idx"]:
                     full_seq = saved.clone()                                                        # TREADRouter.end_route(original_x=saved)
                     ops.scatter_rows(img.view(B, env_cur.Si, D), info.keep_i32(), full_seq.view(B, Si, D))
@@ -626,6 +636,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 ctx.n_out = n_out
         return ops.unpatchify(out.view(B, Si, -1), self.out_channels, Hh, Ww, order=1), ctx
 
+    def set_layersync(self, student_idx, teacher_idx=None):
+        """LayerSync (helpers/training/layersync.py; the reference captures at sd3/transformer.py:872): 0-based joint-block indices.  A training forward then also
+        returns the mean cosine between the two blocks' image-stream outputs (teacher detached) and the backward adds its gradient into the dX chain at the
+        student block."""
+        self._layersync = layersync_indices(student_idx, teacher_idx, len(self.blocks))
+
     def set_router(self, router, routes):
         """sd3/transformer.py:407-409: TREAD router + [{selection_ratio, start_layer_idx, end_layer_idx}] (training/tread.py)"""
         self._tread_router, self._tread_routes = router, routes
@@ -637,7 +653,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for bi in range(s0, s0 + n):
             img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, ctx.envs[bi], True)
 
-    def _engine_backward(self, ctx, dout):
+    def _engine_backward(self, ctx, dout, dsim=None):
+        """dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the dX chain at the student block's output"""
         if not self._prepared:
             raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
         D, H, hd = self.D, self.H, self.hd
@@ -651,9 +668,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], rpb)
         d_txt = None
         del dn, dpk
+        ls = getattr(ctx, "ls", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
+            if ls is not None and li == ls.student:
+                ls.inject(d_img.view(B, ctx.Si, D), dsim)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -849,7 +869,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """training.grad_sync.hand_over_gradients: the arena just filled now belongs to autograd; the next backward takes the other one"""
         self._select_grad_arena(1 - self._grad_sel)
 
-    def _engine_backward_full(self, ctx, dout):
+    def _engine_backward_full(self, ctx, dout, dsim=None):
         D, H, hd = self.D, self.H, self.hd
         B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
         dev = self.device_
@@ -893,9 +913,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
         # the fused modulation matrix (a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
+        ls = getattr(ctx, "ls", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
+            if ls is not None and li == ls.student:
+                ls.inject(d_img.view(B, ctx.Si, D), dsim)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -1039,18 +1062,23 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if timestep.ndim not in (1, 2):
             raise ValueError(f"timestep: expected [B] or tokenwise [B, S_img], got {tuple(timestep.shape)}")
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or getattr(self, "full", False))
+        sim = None                                         # LayerSync (set_layersync): the training nodes return the similarity as a second output
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
         if need_grad and getattr(self, "full", False):
             out = _SD3FullFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._full_params)
+            if self._layersync is not None:
+                out, sim = out
         elif need_grad:
             out = _SD3Fn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._lora_params)
+            if self._layersync is not None:
+                out, sim = out
         else:
             with torch.no_grad():
                 out, _ = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False)
         if not return_dict:
-            return (out,)
-        return SimpleNamespace(sample=out)
+            return (out,) if sim is None else (out, sim)
+        return SimpleNamespace(sample=out) if sim is None else SimpleNamespace(sample=out, layersync_similarity=sim)
 
 
 class _SD3Fn(torch.autograd.Function):
@@ -1060,14 +1088,14 @@ class _SD3Fn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *lora_params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True)
         fctx.model, fctx.ectx = model, ctx
-        return out
+        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
 
     @staticmethod
-    def backward(fctx, dout):
+    def backward(fctx, dout, dsim=None):
         model = fctx.model
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout)
+        model._engine_backward(fctx.ectx, dout, dsim)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()
@@ -1089,15 +1117,15 @@ class _SD3FullFn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True, full=True)
         fctx.model, fctx.ectx = model, ctx
-        return out
+        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
 
     @staticmethod
-    def backward(fctx, dout):
+    def backward(fctx, dout, dsim=None):
         model = fctx.model
         model._pick_grad_arena()
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout)
+        model._engine_backward_full(fctx.ectx, dout, dsim)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world

@@ -57,7 +57,8 @@ def default_config(**over) -> SimpleNamespace:
                flux_fast_schedule=False, flux_guidance_mode="constant", flux_guidance_value=1.0, flux_attention_masked_training=False,
                flux_lora_target="default", snr_gamma=None, loss_type="l2", max_grad_norm=0.0, grad_clip_method="norm",
                gradient_accumulation_steps=1, train_batch_size=1, gradient_checkpointing=False, input_perturbation=0,
-               offset_noise=False, seed=42, lora_init_b_std=0.0)
+               offset_noise=False, seed=42, lora_init_b_std=0.0, layersync_enabled=False, layersync_student_block=None, layersync_teacher_block=None,
+               layersync_lambda=None)
     cfg.update(over)
     return SimpleNamespace(**cfg)
 
@@ -170,12 +171,15 @@ class Trainer:
             raise NotImplementedError("hip_graph: gradient_accumulation_steps == 1 only")
         if self._use_graph and getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
             raise NotImplementedError("hip_graph: XM noise candidates read their logs on the host every step and cannot be captured")
+        if self._use_graph and getattr(config, "layersync_enabled", False):
+            raise NotImplementedError("hip_graph: LayerSync (layersync_enabled) reads its logs on the host every step and cannot be captured")
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
         self.last_loss = None          # device scalar, no host sync
         self.last_grad_norm = None
         self.last_grad_absmax = None
+        self.last_aux_logs = None      # auxiliary_loss's logs of the last micro-step (LayerSync: layersync_loss / layersync_similarity as floats)
 
     def _make_bf16_shadow(self):
         """adamw_bf16 over an fp32 adapter arena (LoRA): the reference's example trains bf16 adapter weights with bf16 gradients under AdamWBF16
@@ -232,7 +236,7 @@ class Trainer:
         else:
             pred = self.model.model_predict(prepared)                                    # :7097 -> :6085
             loss, _ = self.model.loss_with_logs(prepared, pred)
-            loss, _ = self.model.auxiliary_loss(pred, prepared, loss)
+            loss, self.last_aux_logs = self.model.auxiliary_loss(pred, prepared, loss)
             if cfg.gradient_accumulation_steps > 1:
                 loss = loss / cfg.gradient_accumulation_steps
             self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)   # :7114 (C2)
