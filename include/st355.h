@@ -423,6 +423,18 @@ int st355_adamw_bf16_sr_step(void* stream, void* p, const void* g, void* exp_avg
                              int64_t step, double lr, double beta1, double beta2, double eps, const int64_t* seg_end,
                              const float* seg_decay, int nseg, const int32_t* rand_bits, uint64_t seed, uint64_t offset,
                              float grad_scale);
+/* Lion (Chen et al. 2023; the registry's "optimi-lion") over a flat arena, one launch, one momentum buffer.  Per element, fp32 internally:
+ *   g' = g grad_scale ; c = m + (g' - m)(1 - beta1) ; s = sign(c) in {-1, 0, +1} ; m <- m + (g' - m)(1 - beta2) ; d = -lr s - (lr weight_decay) p ; p <- p + d
+ * (decoupled decay scaled by lr, optimi's decouple_lr=False).  p, g, m fp32 [n]; ema (fp32 [n], may be NULL) and p_bf16 (may be NULL) as for
+ * st355_adamw_ema_step, applied to the element just updated.  20 B/param (+8 with ema, +2 with p_bf16). */
+int st355_lion_step(void* stream, float* p, const float* g, float* m, float* ema, void* p_bf16, int64_t n, float lr, float beta1,
+                    float beta2, float weight_decay, float grad_scale, float ema_decay);
+/* bf16 arena (full fine-tune): p, g, m bf16 [n], n % 8 == 0; m is rounded once (RNE).  comp (bf16 [n] or NULL) is a Kahan compensation buffer:
+ *   t = comp + d ; p <- bf16(p + t) ; comp <- bf16(t - (p_new - p_old)), so updates (and the decay) below half a bf16 ulp of p accumulate instead of
+ * rounding away; with comp == NULL p <- bf16(p + d).  ema bf16 [n] or NULL, (ema - p_new) materialised in bf16 as st355_ema_update does.
+ * 14 B/param with comp, 10 without, +4 with ema. */
+int st355_lion_step_bf16(void* stream, void* p, const void* g, void* m, void* comp, void* ema, int64_t n, float lr, float beta1,
+                         float beta2, float weight_decay, float grad_scale, float ema_decay);
 /* standalone EMA: s -= (1-decay) (s - p)   (ema.py:423); fp32 or bf16 by elem_bytes in {4,2} */
 int st355_ema_update(void* stream, void* shadow, const void* param, int64_t n, float decay, int elem_bytes);
 /* K15: sum of squares (fp32 out[0]) and max-abs (out[1]) of a flat gradient; out zeroed by the call */

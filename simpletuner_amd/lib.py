@@ -24,7 +24,7 @@ SYMBOLS = [
     "st355_ln_modulate_fwd", "st355_ln_modulate_bwd",
     "st355_qk_norm_rope_fwd", "st355_qk_norm_rope_bwd", "st355_qk_norm_wgrad_workspace", "st355_qk_norm_rope_bwd_wgrad", "st355_qk_rope_norm_bwd",
     "st355_attn_set_impl", "st355_attn_plan", "st355_attn_fwd", "st355_attn_fwd_vrows", "st355_attn_bwd_workspace", "st355_attn_bwd", "st355_attn_bwd_rope",
-    "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
+    "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_lion_step", "st355_lion_step_bf16", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
     "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
     "st355_layersync_fwd", "st355_layersync_inject",
     "st355_lora_pack",
@@ -334,6 +334,8 @@ def _declare(lib):
                                       i32, i32, i32, i32, i32, f32, vp]),
         "st355_adamw_ema_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, f32]),
         "st355_adamw_ema_step_bf16": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, f32]),
+        "st355_lion_step": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32]),
+        "st355_lion_step_bf16": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32]),
         "st355_adamw_bf16_sr_step": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, i32,
                                                vp, u64, u64, f32]),
         "st355_ema_update": (C.c_int, [vp, vp, vp, i64, f32, i32]),

@@ -968,6 +968,38 @@ def adamw_ema_step(p, g, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps
                  "adamw_ema_step_bf16")
 
 
+def lion_step(p, g, m, lr: float, beta1=0.9, beta2=0.99, weight_decay=0.0, grad_scale: float = 1.0, comp=None, ema=None,
+              ema_decay: float = 0.0, p_bf16=None):
+    """Lion over a flat arena (st355_lion_step*): fp32 p / g / m (optional fp32 ema, bf16 copy p_bf16), or bf16 p / g / m with an optional bf16 Kahan
+    compensation buffer `comp` (and bf16 ema)"""
+    L = _l.load()
+    if p.dtype == F32:
+        for t, n in ((p, "p"), (g, "g"), (m, "m")):
+            _chk(t, F32, n)
+        if comp is not None:
+            raise _l.St355Error("lion_step: an fp32 arena takes no compensation buffer")
+        if ema is not None:
+            _chk(ema, F32, "ema")
+        if p_bf16 is not None:
+            _chk(p_bf16, BF16, "p_bf16")
+        if any(t is not None and (t.numel() != p.numel() or not t.is_contiguous()) for t in (p, g, m, ema, p_bf16)):
+            raise _l.St355Error("lion_step: every arena must be contiguous and have p's length")
+        _l.check(L.st355_lion_step(_stream(), _ptr(p), _ptr(g), _ptr(m), _ptr(ema), _ptr(p_bf16), p.numel(),
+                                   lr, beta1, beta2, weight_decay, grad_scale, ema_decay), "lion_step")
+    else:
+        for t, n in ((p, "p"), (g, "g"), (m, "m")):
+            _chk(t, BF16, n)
+        if p_bf16 is not None:
+            raise _l.St355Error("lion_step: p_bf16 belongs to the fp32 arena")
+        for t, n in ((comp, "comp"), (ema, "ema")):
+            if t is not None:
+                _chk(t, BF16, n)
+        if any(t is not None and (t.numel() != p.numel() or not t.is_contiguous()) for t in (p, g, m, comp, ema)):
+            raise _l.St355Error("lion_step: every arena must be contiguous and have p's length")
+        _l.check(L.st355_lion_step_bf16(_stream(), _ptr(p), _ptr(g), _ptr(m), _ptr(comp), _ptr(ema), p.numel(),
+                                        lr, beta1, beta2, weight_decay, grad_scale, ema_decay), "lion_step_bf16")
+
+
 def ema_update(shadow, param, decay: float):
     L = _l.load()
     if shadow.dtype != param.dtype:

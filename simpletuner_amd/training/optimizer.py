@@ -277,6 +277,120 @@ class St355AdamWBF16(torch.optim.Optimizer):
         return loss
 
 
+class St355Lion(torch.optim.Optimizer):
+    """Lion (Chen et al. 2023) with the constructor of optimi's Lion — the reference's "optimi-lion" entry (optimizer_param.py:327-338) — as ONE
+    st355_lion_step launch per parameter group when the group's parameters and gradients are contiguous runs (the LoRA adapter arena in fp32,
+    a full-fine-tune arena in bf16), else one launch per tensor.
+
+    Per-parameter state: `exp_avg` in the parameter's dtype and, for bf16 parameters with `kahan_sum` true or None, `kahan_comp` (bf16) — views of
+    flat buffers on the one-launch path.  fp32 parameters never carry a compensation buffer.  Weight decay is decoupled and scaled by the
+    learning rate (decouple_lr=False); `decouple_lr=True` is refused, `max_lr` only matters there; `foreach` is accepted and ignored.  optimi is
+    not executed anywhere in this project: the rule is the published one, and exchanging optimizer checkpoints with optimi
+    itself is unverified."""
+
+    def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.99), weight_decay: float = 0.0, decouple_lr: bool = False, max_lr=None,
+                 kahan_sum=True, foreach=True, **_ignored):
+        if decouple_lr:
+            raise NotImplementedError("optimi-lion: decouple_lr=True (fully decoupled weight decay) is not built on the st355 path")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: lr={lr}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta1 parameter: beta1={betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta2 parameter: beta2={betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight decay: weight_decay={weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, decouple_lr=False, max_lr=max_lr, kahan_sum=kahan_sum))
+        self.grad_scale = 1.0           # set by the gradient-sync layer (1/world_size) or by clipping: folded into the kernel
+        self.ema_shadow_flat: Optional[torch.Tensor] = None   # optional fused EMA (flat arena path only)
+        self.ema_decay = 0.0
+        self.ema_applied = False
+        self._flat = {}
+
+    @staticmethod
+    def _kahan(group, p) -> bool:
+        return p.dtype == torch.bfloat16 and group["kahan_sum"] in (True, None)
+
+    def _group_flat(self, gi, group):
+        st = self._flat.get(gi)
+        if st is None:
+            ps = [p for p in group["params"] if p.requires_grad]
+            for p in ps:
+                if p.dtype not in (F32, torch.bfloat16):
+                    raise NotImplementedError(f"optimi-lion: parameters must be fp32 or bf16 on the st355 path, got {p.dtype}")
+            ok = _contiguous_run([p.data for p in ps])
+            n = sum(p.numel() for p in ps)
+            st = dict(ok=ok, ps=ps, n=n, m=None, comp=None)
+            if ok:
+                st["m"] = torch.zeros(n, dtype=ps[0].dtype, device=ps[0].device)
+                if self._kahan(group, ps[0]):
+                    st["comp"] = torch.zeros(n, dtype=torch.bfloat16, device=ps[0].device)
+                off = 0
+                for p in ps:   # per-parameter state = views of the flat buffers
+                    self.state[p] = dict(exp_avg=st["m"][off:off + p.numel()].view_as(p))
+                    if st["comp"] is not None:
+                        self.state[p]["kahan_comp"] = st["comp"][off:off + p.numel()].view_as(p)
+                    off += p.numel()
+            self._flat[gi] = st
+        return st
+
+    def _tensor_state(self, group, p):
+        s = self.state[p]
+        if "exp_avg" not in s:
+            s["exp_avg"] = torch.zeros(p.numel(), dtype=p.dtype, device=p.device).view_as(p)
+            if self._kahan(group, p):
+                s["kahan_comp"] = torch.zeros(p.numel(), dtype=torch.bfloat16, device=p.device).view_as(p)
+        return s
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: dict) -> None:
+        """resume: the saved momentum (and compensation) tensors are copied INTO the flat buffers (created here if the optimizer has not stepped yet),
+        in the dtype this optimizer keeps them in, so the one-launch path continues from them"""
+        saved = _unpack_saved_state(self, state_dict)
+        self._flat = {}
+        for p in list(self.state):
+            del self.state[p]
+        for gi, group in enumerate(self.param_groups):
+            st = self._group_flat(gi, group)
+            for p in st["ps"]:
+                old = saved.get(p)
+                if old is None or "exp_avg" not in old:
+                    continue
+                mine = self.state[p] if st["ok"] else self._tensor_state(group, p)
+                mine["exp_avg"].copy_(old["exp_avg"].to(device=p.device, dtype=p.dtype).view_as(p))
+                if "kahan_comp" in mine and old.get("kahan_comp") is not None:
+                    mine["kahan_comp"].copy_(old["kahan_comp"].to(device=p.device, dtype=torch.bfloat16).view_as(p))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for gi, group in enumerate(self.param_groups):
+            st = self._group_flat(gi, group)
+            ps = [p for p in st["ps"] if p.grad is not None]
+            if not ps:
+                continue
+            b1, b2 = group["betas"]
+            grads = [p.grad for p in ps]
+            if st["ok"] and len(ps) == len(st["ps"]) and _contiguous_run(grads) and grads[0].dtype == ps[0].dtype:
+                pflat = torch.as_strided(ps[0].data, (st["n"],), (1,))
+                gflat = torch.as_strided(grads[0], (st["n"],), (1,))
+                ema = self.ema_shadow_flat if (self.ema_shadow_flat is not None and len(self.param_groups) == 1
+                                               and self.ema_shadow_flat.numel() == st["n"] and self.ema_shadow_flat.dtype == pflat.dtype) else None
+                ops.lion_step(pflat, gflat, st["m"], group["lr"], b1, b2, group["weight_decay"], grad_scale=self.grad_scale, comp=st["comp"],
+                              ema=ema, ema_decay=self.ema_decay)
+                self.ema_applied = ema is not None      # the trainer falls back to EMAModel.step when the fused form did not run
+                continue
+            for p in ps:   # generic path: one launch per tensor
+                s = self._tensor_state(group, p)
+                g = p.grad.contiguous()
+                if g.dtype != p.dtype:
+                    g = g.to(p.dtype)
+                comp = s.get("kahan_comp")
+                ops.lion_step(p.data.view(-1), g.view(-1), s["exp_avg"].view(-1), group["lr"], b1, b2, group["weight_decay"],
+                              grad_scale=self.grad_scale, comp=None if comp is None else comp.view(-1))
+        return loss
+
+
 # what `optimizer_choices["st355-adamw"]` looks like in the reference's registry (optimizer_param.py:76-96)
 OPTIMIZER_CHOICE = {
     "st355-adamw": {
@@ -509,4 +623,11 @@ OPTIMIZER_CHOICE["muon"] = {
     "default_settings": {"momentum": 0.95, "weight_decay": 0.1, "eps": 1e-7, "rms_scale_factor": 0.2, "use_smmf": False, "vector_reshape": False,
                          "stochastic_rounding": True, "use_cans": False, "cans_a_bound": 1e-4, "qk_clip_threshold": 100.0, "qk_clip_alpha": 0.5},
     "class": St355Muon,
+}
+
+# the reference's own "optimi-lion" entry (optimizer_param.py:327-338), with the fused class substituted
+OPTIMIZER_CHOICE["optimi-lion"] = {
+    "precision": "any",
+    "default_settings": {"betas": (0.9, 0.99), "weight_decay": 0.0, "decouple_lr": False, "max_lr": None, "kahan_sum": True, "foreach": True},
+    "class": St355Lion,
 }

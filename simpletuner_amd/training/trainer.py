@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Muon, optimizer_settings
+from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, optimizer_settings
 
 
 class St355Accelerator:
@@ -106,8 +106,8 @@ class Trainer:
                        else [p for p in comp.parameters() if p.requires_grad])
         # optimizer_param.py:76-96 registry semantics: name -> class (+ default settings)
         opt_name = getattr(config, "optimizer", "st355-adamw")
-        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon"):           # never a silently different optimizer
-            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, st355-adamw = torch-adamw semantics)")
+        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion"):           # never a silently different optimizer
+            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, st355-adamw = torch-adamw semantics)")
         self._bf16_shadow = None
         if opt_name == "muon":
             if not getattr(self.model, "SUPPORTS_MUON_CLIP", False):                   # trainer.py:332-339
@@ -127,6 +127,9 @@ class Trainer:
             self.optimizer = St355AdamWBF16(opt_params, lr=config.learning_rate, betas=(config.adam_beta1, config.adam_beta2),
                                             eps=OPTIMIZER_CHOICE["adamw_bf16"]["default_settings"]["eps"], weight_decay=config.adam_weight_decay,
                                             seed=int(getattr(config, "seed", 0) or 0))
+        elif opt_name == "optimi-lion":
+            # fp32 adapter arena or bf16 full-fine-tune arena (Kahan-compensated there), one launch either way; no override_lr_scheduler in the registry entry
+            self.optimizer = St355Lion(self.params, lr=config.learning_rate, **optimizer_settings("optimi-lion", config))
         else:
             self.optimizer = St355AdamW(self.params, lr=config.learning_rate, betas=(config.adam_beta1, config.adam_beta2),
                                         eps=config.adam_epsilon, weight_decay=config.adam_weight_decay)
@@ -297,7 +300,7 @@ class Trainer:
             # step count alone (ema.py:322-349), so it is known here; the kernel applies s -= (1 - d)(s - p_new) to the element it just updated — the same
             # arithmetic as the separate pass (ema.py:393-433), minus its 3 x 2 B/param of HBM traffic and one launch
             ema_decay = None
-            if self.ema_model is not None and isinstance(self.optimizer, St355AdamW):
+            if self.ema_model is not None and isinstance(self.optimizer, (St355AdamW, St355Lion)):
                 ema_decay = self.ema_model.fused_decay(self.params, self.state["global_step"] + 1)
             if ema_decay is not None:
                 self.optimizer.ema_shadow_flat, self.optimizer.ema_decay, self.optimizer.ema_applied = self.ema_model.shadow_flat, float(ema_decay), False
