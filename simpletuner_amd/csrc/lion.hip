@@ -13,15 +13,7 @@
 //   bf16 arena, no comp:    p' = bf16(p + d)
 //   bf16 arena, comp:       t = comp + d ; p' = bf16(p + t) ; comp' = bf16(t - (p' - p))       (Kahan: what the rounding of p' dropped is carried)
 // The decay goes through the compensated sum on purpose: a bf16 p *= 1 - lr wd rounds the decay away whenever lr wd < 2^-9.
-#include "common.h"
-
-#define LION_THREADS 256
-static inline int lion_blocks(int64_t items) {
-  int64_t b = cdiv64(items, LION_THREADS);
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+#include "optim_common.h"
 
 struct LionC {
   float lr, omb1, omb2, lrwd, grad_scale, ema_omd;   // omb = 1 - beta, lrwd = lr * weight_decay, ema_omd = 1 - ema_decay: all formed in fp32
@@ -39,8 +31,8 @@ __device__ __forceinline__ float lion_one(float p, float g, float& m, const Lion
 // d == 0 (a zero gradient on a zero momentum, no decay) leaves the parameter's bits alone, also those of -0
 __device__ __forceinline__ float lion_apply(float p, float d) { return d == 0.f ? p : p + d; }
 
-__global__ void __launch_bounds__(LION_THREADS) k_lion_f32(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ ema, bf16* __restrict__ pb, int64_t n, LionC c) {
+__global__ void __launch_bounds__(OP_THREADS) k_lion_f32(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ ema, bf16* __restrict__ pb, int64_t n, LionC c) {
   const int64_t nv = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
     f32x4 pv = *(f32x4*)(p + i * 4), gv = *(const f32x4*)(g + i * 4), mv = *(f32x4*)(m + i * 4);
@@ -52,31 +44,20 @@ __global__ void __launch_bounds__(LION_THREADS) k_lion_f32(float* __restrict__ p
     }
     *(f32x4*)(p + i * 4) = pv;
     *(f32x4*)(m + i * 4) = mv;
-    if (ema) {
-      f32x4 ev = *(f32x4*)(ema + i * 4);
-#pragma unroll
-      for (int j = 0; j < 4; j++) ev[j] = ev[j] - c.ema_omd * (ev[j] - pv[j]);
-      *(f32x4*)(ema + i * 4) = ev;
-    }
-    if (pb) {
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = f2bf(pv[j]);
-      *(bf16x4*)(pb + i * 4) = o;
-    }
+    if (ema) ema_tail_f32x4(ema, i, pv, c.ema_omd);
+    if (pb) mirror_store_bf16x4(pb, i, pv);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail
     const int64_t i = (nv << 2) + threadIdx.x;
     float mv = m[i];
     const float pv = lion_apply(p[i], lion_one(p[i], g[i], mv, c));
     p[i] = pv; m[i] = mv;
-    if (ema) ema[i] = ema[i] - c.ema_omd * (ema[i] - pv);
-    if (pb) pb[i] = f2bf(pv);
+    ema_mirror_one(ema, pb, i, pv, c.ema_omd);
   }
 }
 
-__global__ void __launch_bounds__(LION_THREADS) k_lion_bf16(bf16* __restrict__ p, const bf16* __restrict__ g, bf16* __restrict__ m,
-                                                           bf16* __restrict__ comp, bf16* __restrict__ ema, int64_t n, LionC c) {
+__global__ void __launch_bounds__(OP_THREADS) k_lion_bf16(bf16* __restrict__ p, const bf16* __restrict__ g, bf16* __restrict__ m,
+                                                         bf16* __restrict__ comp, bf16* __restrict__ ema, int64_t n, LionC c) {
   const int64_t nv = n >> 3;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
     bf16x8 pb = *(bf16x8*)(p + i * 8), gb = *(const bf16x8*)(g + i * 8), mb = *(bf16x8*)(m + i * 8);
@@ -103,12 +84,7 @@ __global__ void __launch_bounds__(LION_THREADS) k_lion_bf16(bf16* __restrict__ p
     }
     *(bf16x8*)(p + i * 8) = pb;
     *(bf16x8*)(m + i * 8) = mb;
-    if (ema) {
-      bf16x8 eb = *(bf16x8*)(ema + i * 8);
-#pragma unroll
-      for (int j = 0; j < 8; j++) { const float e = bf2f(eb[j]); const float diff = bf2f(f2bf(e - bf2f(pb[j]))); eb[j] = f2bf(e - c.ema_omd * diff); }   // as k_adamw_bf16: (s - p) materialised in bf16 (ema.py:393-433)
-      *(bf16x8*)(ema + i * 8) = eb;
-    }
+    if (ema) ema_tail_bf16x8(ema, i, pb, c.ema_omd);
   }
 }
 
@@ -125,7 +101,7 @@ extern "C" int st355_lion_step(void* stream, float* p, const float* g, float* m,
              "lion_step: arena must be 16-byte aligned");
   ProfScope ps(stream, ST355_K_OPTIM, 8.0 * n, (20.0 + (ema ? 8.0 : 0.0) + (p_bf16 ? 2.0 : 0.0)) * n);
   LionC c = make_lion(lr, beta1, beta2, weight_decay, grad_scale, ema_decay);
-  hipLaunchKernelGGL(k_lion_f32, dim3(lion_blocks(n / 4 + 1)), dim3(LION_THREADS), 0, (hipStream_t)stream, p, g, m, ema, (bf16*)p_bf16, n, c);
+  hipLaunchKernelGGL(k_lion_f32, dim3(op_blocks(n / 4 + 1)), dim3(OP_THREADS), 0, (hipStream_t)stream, p, g, m, ema, (bf16*)p_bf16, n, c);
   return st355_check_launch("lion_step");
 }
 
@@ -136,7 +112,7 @@ extern "C" int st355_lion_step_bf16(void* stream, void* p, const void* g, void* 
              "lion_step_bf16: arena must be 16-byte aligned");
   ProfScope ps(stream, ST355_K_OPTIM, 8.0 * n, ((comp ? 14.0 : 10.0) + (ema ? 4.0 : 0.0)) * n);
   LionC c = make_lion(lr, beta1, beta2, weight_decay, grad_scale, ema_decay);
-  hipLaunchKernelGGL(k_lion_bf16, dim3(lion_blocks(n / 8)), dim3(LION_THREADS), 0, (hipStream_t)stream, (bf16*)p, (const bf16*)g, (bf16*)m,
+  hipLaunchKernelGGL(k_lion_bf16, dim3(op_blocks(n / 8)), dim3(OP_THREADS), 0, (hipStream_t)stream, (bf16*)p, (const bf16*)g, (bf16*)m,
                      (bf16*)comp, (bf16*)ema, n, c);
   return st355_check_launch("lion_step_bf16");
 }

@@ -2,7 +2,7 @@
 // gradient norm, and the LoRA operand packer.  All HBM-streaming: 16-byte accesses, one read and one write
 // of every state word per step (22-28 B/param depending on layout).
 #include <math.h>
-#include "common.h"
+#include "optim_common.h"
 
 // zero-fill as a KERNEL (not hipMemsetAsync): memset nodes inside a captured hipGraph were observed to misbehave on replay (ROCm 7.2), and the
 // trainer replays the whole predict + loss + backward as one graph
@@ -14,14 +14,6 @@ static inline void zero_words(void* stream, void* p, int n_words) {
   hipLaunchKernelGGL(k_zero_words, dim3((n_words + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint32_t*)p, n_words);
 }
 
-
-#define OP_THREADS 256
-static inline int op_blocks(int64_t items) {
-  int64_t b = cdiv64(items, OP_THREADS);
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 struct AdamC {
   float lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, grad_scale, ema_omd;  // ema_omd = 1 - ema_decay
@@ -53,26 +45,15 @@ __global__ void __launch_bounds__(OP_THREADS) k_adamw_f32(float* __restrict__ p,
     *(f32x4*)(p + i * 4) = pv;
     *(f32x4*)(m + i * 4) = mv;
     *(f32x4*)(v + i * 4) = vv;
-    if (ema) {
-      f32x4 ev = *(f32x4*)(ema + i * 4);
-#pragma unroll
-      for (int j = 0; j < 4; j++) ev[j] = ev[j] - c.ema_omd * (ev[j] - pv[j]);
-      *(f32x4*)(ema + i * 4) = ev;
-    }
-    if (pb) {
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = f2bf(pv[j]);
-      *(bf16x4*)(pb + i * 4) = o;
-    }
+    if (ema) ema_tail_f32x4(ema, i, pv, c.ema_omd);
+    if (pb) mirror_store_bf16x4(pb, i, pv);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail
     const int64_t i = (nv << 2) + threadIdx.x;
     float pv = p[i], mv = m[i], vv = v[i];
     adam_one(pv, g[i], mv, vv, c);
     p[i] = pv; m[i] = mv; v[i] = vv;
-    if (ema) ema[i] = ema[i] - c.ema_omd * (ema[i] - pv);
-    if (pb) pb[i] = f2bf(pv);
+    ema_mirror_one(ema, pb, i, pv, c.ema_omd);
   }
 }
 
@@ -96,12 +77,7 @@ __global__ void __launch_bounds__(OP_THREADS) k_adamw_bf16(bf16* __restrict__ p,
     *(bf16x8*)(p + i * 8) = pb;
     *(f32x4*)(m + i * 8) = m0; *(f32x4*)(m + i * 8 + 4) = m1;
     *(f32x4*)(v + i * 8) = v0; *(f32x4*)(v + i * 8 + 4) = v1;
-    if (ema) {
-      bf16x8 eb = *(bf16x8*)(ema + i * 8);
-#pragma unroll
-      for (int j = 0; j < 8; j++) { const float e = bf2f(eb[j]); const float diff = bf2f(f2bf(e - bf2f(pb[j]))); eb[j] = f2bf(e - c.ema_omd * diff); }   // as k_ema<bf16>: (s - p) materialised in bf16 (ema.py:393-433)
-      *(bf16x8*)(ema + i * 8) = eb;
-    }
+    if (ema) ema_tail_bf16x8(ema, i, pb, c.ema_omd);
   }
 }
 
@@ -260,14 +236,10 @@ extern "C" int st355_adamw_bf16_sr_step(void* stream, void* p, const void* g, vo
   return st355_check_launch("adamw_bf16_sr_step");
 }
 
-// s -= (1-d) (s - p)      (ema.py:423: torch._foreach_sub_(s, torch._foreach_sub(s, p), alpha=1-d))
+// the standalone EMA pass: ema_one (optim_common.h) over the whole arena
 template <typename T>
 __global__ void __launch_bounds__(OP_THREADS) k_ema(T* __restrict__ s, const T* __restrict__ p, int64_t n, float omd) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float sf = (float)s[i], pf = (float)p[i];
-    const T diff = (T)(sf - pf);                 // the reference materialises (s - p) in the parameter dtype
-    s[i] = (T)(sf - omd * (float)diff);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s[i] = ema_one(s[i], p[i], omd);
 }
 extern "C" int st355_ema_update(void* stream, void* shadow, const void* param, int64_t n, float decay, int elem_bytes) {
   ST_REQUIRE(shadow && param && n > 0 && (elem_bytes == 4 || elem_bytes == 2), "ema_update: bad args");

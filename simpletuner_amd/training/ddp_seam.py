@@ -116,11 +116,10 @@ class St355DistributedDataParallel(torch.nn.Module):
             # boundary of a gradient accumulation: ONE exchange of the accumulated flat .grad (DDP semantics of trainer.py:7009)
             params = (self.module.trainable_parameters() if hasattr(self.module, "trainable_parameters")
                       else [p for p in self.module.parameters() if p.requires_grad])
-            grads = [p.grad for p in params]
-            from .optimizer import _contiguous_run
-            if any(g is None for g in grads) or not _contiguous_run(grads):
+            from .optimizer import flat_view
+            flat = flat_view([p.grad for p in params])
+            if flat is None:
                 raise RuntimeError("accumulated gradients are not one flat arena (st355 components hand autograd one flat buffer per backward)")
-            flat = torch.as_strided(grads[0], (sum(g.numel() for g in grads),), (1,))
             W = self.grad_sync.world_size
             if W > 1:
                 self.grad_sync.all_reduce_now(flat)

@@ -16,7 +16,7 @@ from typing import Any, Dict, Iterable, Optional, Union
 import torch
 
 from .. import ops
-from .optimizer import _contiguous_run
+from .optimizer import flat_view
 
 
 def should_update_ema(args, step) -> bool:
@@ -45,10 +45,10 @@ class EMAModel:
         tracked = [p for p in parameters]
         self._tracked_param_ids = [id(p) for p in tracked]
         self._tracked_refs = [weakref.ref(p) for p in tracked]      # an id() is only meaningful while its object lives: a freed parameter's id gets reused
-        self._flat = _contiguous_run([p.data for p in tracked]) and len(tracked) > 0
+        flat = flat_view([p.data for p in tracked])
+        self._flat = flat is not None
         if self._flat:
-            n = sum(p.numel() for p in tracked)
-            self.shadow_flat = torch.as_strided(tracked[0].data, (n,), (1,)).clone()
+            self.shadow_flat = flat.clone()
             self.shadow_params, off = [], 0
             for p in tracked:
                 self.shadow_params.append(self.shadow_flat[off:off + p.numel()].view_as(p))
@@ -91,9 +91,9 @@ class EMAModel:
             self.optimization_step += 1
         decay = self.get_decay(self.optimization_step)
         self.cur_decay_value = decay
-        if self._flat and _contiguous_run([p.data for p in parameters]):
-            n = self.shadow_flat.numel()
-            ops.ema_update(self.shadow_flat, torch.as_strided(parameters[0].data, (n,), (1,)), decay)
+        pflat = flat_view([p.data for p in parameters]) if self._flat else None
+        if pflat is not None and pflat.numel() == self.shadow_flat.numel():
+            ops.ema_update(self.shadow_flat, pflat, decay)
             return
         for s, p in zip(self.shadow_params, parameters):
             if p.requires_grad:
@@ -111,7 +111,7 @@ class EMAModel:
         if self.rank0_only and getattr(self.accelerator, "process_index", 0) != 0:
             return None
         parameters = list(parameters)
-        if len(parameters) != len(self.shadow_params) or not self._flat or not _contiguous_run([p.data for p in parameters]):
+        if len(parameters) != len(self.shadow_params) or not self._flat or flat_view([p.data for p in parameters]) is None:
             return None
         if parameters[0].dtype != self.shadow_flat.dtype:
             return None

@@ -31,6 +31,14 @@ def _contiguous_run(tensors):
     return True
 
 
+def flat_view(tensors):
+    """The 1-D view over `tensors` when they are back-to-back views of one allocation (`_contiguous_run`), else None — also for an empty list or a
+    list with a missing (None) entry, so callers need no pre-check.  Writes through the view land in the tensors."""
+    if not tensors or any(t is None for t in tensors) or not _contiguous_run(tensors):
+        return None
+    return torch.as_strided(tensors[0], (sum(t.numel() for t in tensors),), (1,))
+
+
 def _unpack_saved_state(opt: torch.optim.Optimizer, state_dict: dict):
     """torch.optim.Optimizer.load_state_dict's matching rules (groups by position, parameters by position inside a group; saved hyper-parameters
     replace the live ones) WITHOUT its dtype policy: torch casts every floating state tensor to the parameter's dtype, which would round the fp32
@@ -51,62 +59,139 @@ def _unpack_saved_state(opt: torch.optim.Optimizer, state_dict: dict):
     return by_param
 
 
-class St355AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 amsgrad: bool = False, **_ignored):
-        if amsgrad:
-            raise NotImplementedError("amsgrad is not implemented in the fused kernel")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _ArenaOptimizer(torch.optim.Optimizer):
+    """What the four fused optimizers share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
+    per-parameter state installed as views of them (`_flat[gi]`: ok, ps, n, one entry per declared buffer, the subclass's extras); a
+    `load_state_dict` that copies a checkpoint INTO those buffers in the dtype each is kept in; and the test for the one-launch path.
+    A subclass declares `_buffers`, adds its extras in `_group_extras` / `_load_extras`, and issues its `ops.*` calls in `step`."""
+    fuses_ema = False        # True where the kernel can apply the EMA update in the same launch (the trainer then hands over ema_shadow_flat / ema_decay)
+    always_flat = False      # True: flat state buffers even when the parameters are not one contiguous run
+    _buffers: Dict[str, tuple] = {}    # per-parameter state key -> (key in _flat[gi], dtype; None = the parameter's own)
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self.grad_scale = 1.0           # set by the gradient-sync layer (1/world_size) or by clipping: folded into the kernel
-        self.ema_shadow_flat: Optional[torch.Tensor] = None   # optional fused EMA (flat arena path only)
+        self.ema_shadow_flat: Optional[torch.Tensor] = None   # optional fused EMA (flat arena path only; used where fuses_ema)
         self.ema_decay = 0.0
         self.ema_applied = False
         self._flat = {}
 
-    def _group_flat(self, gi, group):
-        st = self._flat.get(gi)
-        if st is None:
-            ps = [p for p in group["params"] if p.requires_grad]
-            ok = _contiguous_run([p.data for p in ps])
-            n = sum(p.numel() for p in ps)
-            st = dict(ok=ok, ps=ps, n=n, step=0, m=None, v=None)
-            if ok:
-                st["m"] = torch.zeros(n, dtype=F32, device=ps[0].device)
-                st["v"] = torch.zeros(n, dtype=F32, device=ps[0].device)
-                off = 0
-                for p in ps:   # torch-compatible per-parameter state = views of the flat moments
-                    self.state[p] = dict(step=torch.tensor(0.0), exp_avg=st["m"][off:off + p.numel()].view_as(p),
-                                         exp_avg_sq=st["v"][off:off + p.numel()].view_as(p))
-                    off += p.numel()
-            self._flat[gi] = st
+    # ---- what a subclass may override ----
+    def _group_params(self, group):
+        return [p for p in group["params"] if p.requires_grad]
+
+    def _check_param(self, p) -> None:
+        """refuse a parameter this optimizer cannot step"""
+
+    def _buffer_dtype(self, key, group, p):
+        """dtype of state buffer `key` for parameters like p, or None where the group carries no such buffer"""
+        dtype = self._buffers[key][1]
+        return p.dtype if dtype is None else dtype
+
+    def _group_extras(self, gi, group, st) -> None:
+        """whatever `_flat[gi]` and the per-parameter states hold beyond the declared buffers"""
+
+    def _load_extras(self, st, mine, old) -> None:
+        """restore one parameter's extras (`mine`: its live state, `old`: its saved state)"""
+
+    # ---- group construction ----
+    def _build_group(self, gi, group):
+        ps = self._group_params(group)
+        for p in ps:
+            self._check_param(p)
+        st = dict(ok=flat_view([p.data for p in ps]) is not None, ps=ps, n=sum(p.numel() for p in ps))
+        flat = st["ok"] or self.always_flat
+        for key, (flat_key, _) in self._buffers.items():
+            dtype = self._buffer_dtype(key, group, ps[0]) if flat else None
+            st[flat_key] = None if dtype is None else torch.zeros(st["n"], dtype=dtype, device=ps[0].device)
+        if flat:
+            off = 0
+            for p in ps:   # torch-compatible per-parameter state = views of the flat buffers
+                self.state[p] = {key: st[flat_key][off:off + p.numel()].view_as(p)
+                                 for key, (flat_key, _) in self._buffers.items() if st[flat_key] is not None}
+                off += p.numel()
+        self._group_extras(gi, group, st)
+        self._flat[gi] = st
         return st
 
+    def _group_flat(self, gi, group):
+        st = self._flat.get(gi)
+        return st if st is not None else self._build_group(gi, group)
+
+    def _tensor_state(self, group, p):
+        """p's state with every declared buffer present: the flat views where the group has them, else per-tensor buffers created on first use"""
+        s = self.state[p]
+        for key in self._buffers:
+            if key not in s:
+                dtype = self._buffer_dtype(key, group, p)
+                if dtype is not None:
+                    s[key] = torch.zeros(p.numel(), dtype=dtype, device=p.device).view_as(p)
+        return s
+
+    # ---- resume ----
     @torch.no_grad()
     def load_state_dict(self, state_dict: dict) -> None:
-        """resume (`accelerator.load_state`, save_hooks.py): the saved per-parameter moments are copied INTO the flat fp32 arenas (created here if
-        the optimizer has not stepped yet) so the one-launch path continues from them; step counters are restored"""
+        """resume (`accelerator.load_state`, save_hooks.py): the saved per-parameter buffers are copied INTO the flat buffers (created here if the
+        optimizer has not stepped yet), each in the dtype this optimizer keeps it in, so the one-launch path continues from them; `_load_extras`
+        restores the rest"""
         saved = _unpack_saved_state(self, state_dict)
         self._flat = {}
         for p in list(self.state):
             del self.state[p]
         for gi, group in enumerate(self.param_groups):
-            st = self._group_flat(gi, group)
-            steps = [0]
+            st = self._build_group(gi, group)
             for p in st["ps"]:
                 old = saved.get(p)
-                if old is None:
+                if not old:
                     continue
-                k = int(float(old["step"]))
-                steps.append(k)
-                if st["ok"]:
-                    mine = self.state[p]
-                    mine["exp_avg"].copy_(old["exp_avg"].to(device=p.device, dtype=F32).view_as(p))
-                    mine["exp_avg_sq"].copy_(old["exp_avg_sq"].to(device=p.device, dtype=F32).view_as(p))
-                    mine["step"] = torch.tensor(float(k))
-                else:
-                    self.state[p] = dict(step=torch.tensor(float(k)), exp_avg=old["exp_avg"].to(device=p.device, dtype=F32).clone().view_as(p),
-                                         exp_avg_sq=old["exp_avg_sq"].to(device=p.device, dtype=F32).clone().view_as(p))
-            st["step"] = max(steps)
+                mine = self._tensor_state(group, p)
+                for key in self._buffers:
+                    if key in mine and old.get(key) is not None:
+                        mine[key].copy_(old[key].to(device=p.device, dtype=mine[key].dtype).view_as(p))
+                self._load_extras(st, mine, old)
+
+    # ---- the one-launch path ----
+    def _fused_views(self, st, ps):
+        """(pflat, gflat, ema) when `ps` are all of the group's parameters and they and their gradients are contiguous runs, else None.  ema is the
+        shadow arena the launch should update as well: only with one group, of the arena's length and dtype"""
+        if not st["ok"] or len(ps) != len(st["ps"]):
+            return None
+        gflat = flat_view([p.grad for p in ps])
+        pflat = flat_view([p.data for p in ps]) if gflat is not None else None
+        if pflat is None:
+            return None
+        ema = self.ema_shadow_flat if self.fuses_ema else None
+        if ema is not None and not (len(self.param_groups) == 1 and ema.numel() == st["n"] and ema.dtype == pflat.dtype):
+            ema = None
+        return pflat, gflat, ema
+
+
+class St355AdamW(_ArenaOptimizer):
+    fuses_ema = True
+    _buffers = {"exp_avg": ("m", F32), "exp_avg_sq": ("v", F32)}     # fp32 moments, also for bf16 parameters
+
+    def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False, **_ignored):
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not implemented in the fused kernel")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _group_extras(self, gi, group, st):
+        st["step"] = 0
+        if st["ok"]:
+            for p in st["ps"]:
+                self.state[p]["step"] = torch.tensor(0.0)
+
+    def _tensor_state(self, group, p):
+        s = super()._tensor_state(group, p)
+        if "step" not in s:
+            s["step"] = torch.tensor(0.0)
+        return s
+
+    def _load_extras(self, st, mine, old):
+        k = int(float(old["step"]))
+        mine["step"] = torch.tensor(float(k))
+        st["step"] = max(st["step"], k)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -119,12 +204,9 @@ class St355AdamW(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             st["step"] += 1
             step = st["step"]
-            grads = [p.grad for p in ps]
-            if st["ok"] and len(ps) == len(st["ps"]) and _contiguous_run(grads):
-                pflat = torch.as_strided(ps[0].data, (st["n"],), (1,))
-                gflat = torch.as_strided(grads[0], (st["n"],), (1,))
-                ema = self.ema_shadow_flat if (self.ema_shadow_flat is not None and len(self.param_groups) == 1
-                                               and self.ema_shadow_flat.numel() == st["n"] and self.ema_shadow_flat.dtype == pflat.dtype) else None
+            fused = self._fused_views(st, ps)
+            if fused is not None:
+                pflat, gflat, ema = fused
                 ops.adamw_ema_step(pflat, gflat, st["m"], st["v"], step, group["lr"], b1, b2, group["eps"], group["weight_decay"],
                                    grad_scale=self.grad_scale, ema=ema, ema_decay=self.ema_decay)
                 self.ema_applied = ema is not None      # the trainer falls back to EMAModel.step when the fused form did not run
@@ -132,11 +214,7 @@ class St355AdamW(torch.optim.Optimizer):
                     self.state[p]["step"] += 1
                 continue
             for p in ps:   # generic path: one launch per tensor
-                s = self.state[p]
-                if "exp_avg" not in s:
-                    s["step"] = torch.tensor(0.0)
-                    s["exp_avg"] = torch.zeros(p.numel(), dtype=F32, device=p.device).view_as(p)
-                    s["exp_avg_sq"] = torch.zeros(p.numel(), dtype=F32, device=p.device).view_as(p)
+                s = self._tensor_state(group, p)
                 s["step"] += 1
                 g = p.grad.contiguous()
                 if g.dtype != p.dtype:
@@ -146,7 +224,7 @@ class St355AdamW(torch.optim.Optimizer):
         return loss
 
 
-class St355AdamWBF16(torch.optim.Optimizer):
+class St355AdamWBF16(_ArenaOptimizer):
     """AdamWBF16 — the reference examples' default optimizer (optimizers/adamw_bfloat16/__init__.py:20-111), as ONE fused launch.
 
     Same constructor (keyword-only lr, betas, eps, weight_decay), same `step(zero_grad=False)`, same per-parameter state keys
@@ -156,6 +234,8 @@ class St355AdamWBF16(torch.optim.Optimizer):
     Parameters must be bf16 and, for the fused path, views of one contiguous arena (as the full-fine-tune engine allocates them);
     otherwise one launch per tensor.  `rand_bits_hook(p_index, step) -> int32[4, n]` lets parity tests inject the reference's draws."""
     decay_threshold = 5e-3
+    always_flat = True
+    _buffers = {"exp_avg": ("m", torch.bfloat16), "exp_avg_sq": ("v", torch.bfloat16), "shift": ("shift", torch.bfloat16)}
 
     def __init__(self, params, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, seed: int = 0):
         if not 0.0 <= eps:
@@ -167,66 +247,41 @@ class St355AdamWBF16(torch.optim.Optimizer):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, dict(betas=betas, eps=eps, weight_decay=weight_decay, lr=lr))
-        self.grad_scale = 1.0
         self.seed = int(seed)
         self.rand_bits_hook = None
         self._launches = 0
-        self._flat = {}
+
+    def _check_param(self, p):
+        assert p.dtype == torch.bfloat16, "only bfloat 16 is supported."
 
     def _init_group(self, gi, group):
-        ps = [p for p in group["params"] if p.requires_grad]
-        for p in ps:
-            assert p.dtype == torch.bfloat16, "only bfloat 16 is supported."
-        ok = _contiguous_run([p.data for p in ps])
-        n = sum(p.numel() for p in ps)
-        dev = ps[0].device
-        st = dict(ok=ok, ps=ps, n=n, step=0)
-        mk = lambda: torch.zeros(n, dtype=torch.bfloat16, device=dev)
-        st["m"], st["v"], st["shift"] = mk(), mk(), mk()
-        ends, off = [], 0
+        return self._build_group(gi, group)
+
+    def _group_extras(self, gi, group, st):
+        st["step"] = 0
         # "Each weight has its own starting point to avoid simultaneous updates in all weights" (:80-84).  The reference draws these phases from the
         # global torch RNG; here they come from a generator private to (optimizer seed, group), so data-parallel replicas — whose global RNG streams
         # differ by rank — release their delayed decay on the same steps and stay bit-identical.
         phase_rng = torch.Generator().manual_seed(1_000_003 * self.seed + gi)
-        for p in ps:
-            k = p.numel()
-            self.state[p] = dict(step=0.0, exp_avg=st["m"][off:off + k].view_as(p), exp_avg_sq=st["v"][off:off + k].view_as(p),
-                                 shift=st["shift"][off:off + k].view_as(p),
-                                 accumulated_decay=float(torch.rand([], generator=phase_rng) * self.decay_threshold))
-            off += k
+        ends, off = [], 0
+        for p in st["ps"]:
+            self.state[p].update(step=0.0, accumulated_decay=float(torch.rand([], generator=phase_rng) * self.decay_threshold))
+            off += p.numel()
             ends.append(off)
-        st["seg_end"] = torch.tensor(ends, dtype=torch.int64, device=dev)
-        self._flat[gi] = st
-        return st
+        st["seg_end"] = torch.tensor(ends, dtype=torch.int64, device=st["ps"][0].device)
 
-    @torch.no_grad()
-    def load_state_dict(self, state_dict: dict) -> None:
-        """resume: moments / shift copied into the flat bf16 arenas, per-tensor step and the owed decay restored (the delayed-decay phase of every
-        tensor continues where it stopped, optimizers/adamw_bfloat16/__init__.py:80-95)"""
-        saved = _unpack_saved_state(self, state_dict)
-        self._flat = {}
-        for p in list(self.state):
-            del self.state[p]
-        for gi, group in enumerate(self.param_groups):
-            st = self._init_group(gi, group)
-            steps = [0]
-            for p in st["ps"]:
-                old = saved.get(p)
-                if old is None:
-                    continue
-                mine = self.state[p]
-                for k in ("exp_avg", "exp_avg_sq", "shift"):
-                    mine[k].copy_(old[k].to(device=p.device, dtype=torch.bfloat16).view_as(p))
-                mine["step"] = float(old["step"])
-                mine["accumulated_decay"] = float(old["accumulated_decay"])
-                steps.append(int(float(old["step"])))
-            st["step"] = max(steps)
+    def _load_extras(self, st, mine, old):
+        """per-tensor step and the owed decay: the delayed-decay phase of every tensor continues where it stopped
+        (optimizers/adamw_bfloat16/__init__.py:80-95)"""
+        mine["step"] = float(old["step"])
+        mine["accumulated_decay"] = float(old["accumulated_decay"])
+        st["step"] = max(st["step"], int(float(old["step"])))
 
     @torch.no_grad()
     def step(self, zero_grad: bool = False, closure=None):
         loss = closure() if closure is not None else None
         for gi, group in enumerate(self.param_groups):
-            st = self._flat.get(gi) or self._init_group(gi, group)
+            st = self._group_flat(gi, group)
             ps = st["ps"]
             if any(p.grad is None for p in ps):
                 raise RuntimeError("St355AdamWBF16 expects a gradient for every parameter of the group (fused arena step)")
@@ -250,11 +305,9 @@ class St355AdamWBF16(torch.optim.Optimizer):
                 seg_decay = st.get("zero_decay")
                 if seg_decay is None:
                     seg_decay = st["zero_decay"] = torch.zeros(len(ps), dtype=F32, device=ps[0].device)
-            grads = [p.grad for p in ps]
-            fused = st["ok"] and _contiguous_run(grads) and self.rand_bits_hook is None
-            if fused:
-                pflat = torch.as_strided(ps[0].data, (st["n"],), (1,))
-                gflat = torch.as_strided(grads[0], (st["n"],), (1,))
+            fused = self._fused_views(st, ps) if self.rand_bits_hook is None else None
+            if fused is not None:
+                pflat, gflat, _ = fused
                 ops.adamw_bf16_sr_step(pflat, gflat, st["m"], st["v"], st["shift"], st["step"], lr, beta1, beta2, group["eps"],
                                        seg_end=st["seg_end"], seg_decay=seg_decay, seed=self.seed, offset=4 * st["n"] * st["step"],
                                        grad_scale=self.grad_scale)
@@ -277,7 +330,7 @@ class St355AdamWBF16(torch.optim.Optimizer):
         return loss
 
 
-class St355Lion(torch.optim.Optimizer):
+class St355Lion(_ArenaOptimizer):
     """Lion (Chen et al. 2023) with the constructor of optimi's Lion — the reference's "optimi-lion" entry (optimizer_param.py:327-338) — as ONE
     st355_lion_step launch per parameter group when the group's parameters and gradients are contiguous runs (the LoRA adapter arena in fp32,
     a full-fine-tune arena in bf16), else one launch per tensor.
@@ -287,6 +340,8 @@ class St355Lion(torch.optim.Optimizer):
     learning rate (decouple_lr=False); `decouple_lr=True` is refused, `max_lr` only matters there; `foreach` is accepted and ignored.  optimi is
     not executed anywhere in this project: the rule is the published one, and exchanging optimizer checkpoints with optimi
     itself is unverified."""
+    fuses_ema = True
+    _buffers = {"exp_avg": ("m", None), "kahan_comp": ("comp", torch.bfloat16)}
 
     def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.99), weight_decay: float = 0.0, decouple_lr: bool = False, max_lr=None,
                  kahan_sum=True, foreach=True, **_ignored):
@@ -301,65 +356,15 @@ class St355Lion(torch.optim.Optimizer):
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight decay: weight_decay={weight_decay}")
         super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, decouple_lr=False, max_lr=max_lr, kahan_sum=kahan_sum))
-        self.grad_scale = 1.0           # set by the gradient-sync layer (1/world_size) or by clipping: folded into the kernel
-        self.ema_shadow_flat: Optional[torch.Tensor] = None   # optional fused EMA (flat arena path only)
-        self.ema_decay = 0.0
-        self.ema_applied = False
-        self._flat = {}
 
-    @staticmethod
-    def _kahan(group, p) -> bool:
-        return p.dtype == torch.bfloat16 and group["kahan_sum"] in (True, None)
+    def _check_param(self, p):
+        if p.dtype not in (F32, torch.bfloat16):
+            raise NotImplementedError(f"optimi-lion: parameters must be fp32 or bf16 on the st355 path, got {p.dtype}")
 
-    def _group_flat(self, gi, group):
-        st = self._flat.get(gi)
-        if st is None:
-            ps = [p for p in group["params"] if p.requires_grad]
-            for p in ps:
-                if p.dtype not in (F32, torch.bfloat16):
-                    raise NotImplementedError(f"optimi-lion: parameters must be fp32 or bf16 on the st355 path, got {p.dtype}")
-            ok = _contiguous_run([p.data for p in ps])
-            n = sum(p.numel() for p in ps)
-            st = dict(ok=ok, ps=ps, n=n, m=None, comp=None)
-            if ok:
-                st["m"] = torch.zeros(n, dtype=ps[0].dtype, device=ps[0].device)
-                if self._kahan(group, ps[0]):
-                    st["comp"] = torch.zeros(n, dtype=torch.bfloat16, device=ps[0].device)
-                off = 0
-                for p in ps:   # per-parameter state = views of the flat buffers
-                    self.state[p] = dict(exp_avg=st["m"][off:off + p.numel()].view_as(p))
-                    if st["comp"] is not None:
-                        self.state[p]["kahan_comp"] = st["comp"][off:off + p.numel()].view_as(p)
-                    off += p.numel()
-            self._flat[gi] = st
-        return st
-
-    def _tensor_state(self, group, p):
-        s = self.state[p]
-        if "exp_avg" not in s:
-            s["exp_avg"] = torch.zeros(p.numel(), dtype=p.dtype, device=p.device).view_as(p)
-            if self._kahan(group, p):
-                s["kahan_comp"] = torch.zeros(p.numel(), dtype=torch.bfloat16, device=p.device).view_as(p)
-        return s
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict: dict) -> None:
-        """resume: the saved momentum (and compensation) tensors are copied INTO the flat buffers (created here if the optimizer has not stepped yet),
-        in the dtype this optimizer keeps them in, so the one-launch path continues from them"""
-        saved = _unpack_saved_state(self, state_dict)
-        self._flat = {}
-        for p in list(self.state):
-            del self.state[p]
-        for gi, group in enumerate(self.param_groups):
-            st = self._group_flat(gi, group)
-            for p in st["ps"]:
-                old = saved.get(p)
-                if old is None or "exp_avg" not in old:
-                    continue
-                mine = self.state[p] if st["ok"] else self._tensor_state(group, p)
-                mine["exp_avg"].copy_(old["exp_avg"].to(device=p.device, dtype=p.dtype).view_as(p))
-                if "kahan_comp" in mine and old.get("kahan_comp") is not None:
-                    mine["kahan_comp"].copy_(old["kahan_comp"].to(device=p.device, dtype=torch.bfloat16).view_as(p))
+    def _buffer_dtype(self, key, group, p):
+        if key == "kahan_comp" and not (p.dtype == torch.bfloat16 and group["kahan_sum"] in (True, None)):
+            return None          # fp32 parameters, or kahan_sum=False: no compensation buffer
+        return super()._buffer_dtype(key, group, p)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -370,12 +375,9 @@ class St355Lion(torch.optim.Optimizer):
             if not ps:
                 continue
             b1, b2 = group["betas"]
-            grads = [p.grad for p in ps]
-            if st["ok"] and len(ps) == len(st["ps"]) and _contiguous_run(grads) and grads[0].dtype == ps[0].dtype:
-                pflat = torch.as_strided(ps[0].data, (st["n"],), (1,))
-                gflat = torch.as_strided(grads[0], (st["n"],), (1,))
-                ema = self.ema_shadow_flat if (self.ema_shadow_flat is not None and len(self.param_groups) == 1
-                                               and self.ema_shadow_flat.numel() == st["n"] and self.ema_shadow_flat.dtype == pflat.dtype) else None
+            fused = self._fused_views(st, ps)
+            if fused is not None and fused[1].dtype == fused[0].dtype:
+                pflat, gflat, ema = fused
                 ops.lion_step(pflat, gflat, st["m"], group["lr"], b1, b2, group["weight_decay"], grad_scale=self.grad_scale, comp=st["comp"],
                               ema=ema, ema_decay=self.ema_decay)
                 self.ema_applied = ema is not None      # the trainer falls back to EMAModel.step when the fused form did not run
@@ -389,22 +391,6 @@ class St355Lion(torch.optim.Optimizer):
                 ops.lion_step(p.data.view(-1), g.view(-1), s["exp_avg"].view(-1), group["lr"], b1, b2, group["weight_decay"],
                               grad_scale=self.grad_scale, comp=None if comp is None else comp.view(-1))
         return loss
-
-
-# what `optimizer_choices["st355-adamw"]` looks like in the reference's registry (optimizer_param.py:76-96)
-OPTIMIZER_CHOICE = {
-    "st355-adamw": {
-        "precision": "any",
-        "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-8},
-        "class": St355AdamW,
-    },
-    # the reference's own "adamw_bf16" entry (optimizer_param.py), with the fused class substituted
-    "adamw_bf16": {
-        "precision": "bf16",
-        "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-6},
-        "class": St355AdamWBF16,
-    },
-}
 
 
 # ---- Muon ------------------------------------------------------------------------------------------------------------------------
@@ -439,7 +425,7 @@ def muon_coefficients(group: dict):
     return [tuple(float(v) for v in group["ns_coefficients"])] * group["ns_steps"]
 
 
-class St355Muon(torch.optim.Optimizer):
+class St355Muon(_ArenaOptimizer):
     """MuonClip (optimizers/muon/__init__.py) over the fp32 adapter arena, as one st355_muon_step call per parameter group.
 
     Same constructor (every keyword of MuonClip), same `step(closure=None, attention_max_logits=None)`, same per-parameter state keys
@@ -448,6 +434,7 @@ class St355Muon(torch.optim.Optimizer):
     iterate is never written over its own input and the momentum buffer keeps m.  Parameters must be 2-D fp32 views of one contiguous arena
     with a short side of at most 128 (the LoRA adapter arena); `stochastic_rounding` is accepted and, as for the reference's non-bf16
     parameters, has no effect.  `use_smmf` and `vector_reshape` are refused."""
+    _buffers = {"momentum_buffer": ("m", F32)}
 
     def __init__(self, params, lr: float = 2e-4, momentum: float = 0.95, weight_decay: float = 0.1, qk_clip_threshold: float = 100.0,
                  qk_clip_alpha: float = 0.5, ns_steps: int = MUON_NS_STEPS, ns_coefficients=MUON_NS_COEFFICIENTS, eps: float = MUON_EPS,
@@ -482,28 +469,21 @@ class St355Muon(torch.optim.Optimizer):
                     raise NotImplementedError(f"muon: parameter {i} of shape {tuple(p.shape)} has a short side above {MUON_MAX_SHORT_SIDE}")
                 if p.dtype != F32:
                     raise NotImplementedError(f"muon: parameter {i} is {p.dtype}; the st355 path steps fp32 adapter values")
-            if not _contiguous_run([p.data for p in ps]):
+            if flat_view([p.data for p in ps]) is None:
                 raise NotImplementedError("muon: the parameters of a group must be one contiguous fp32 run (the adapter arena)")
         self.stochastic_rounding = stochastic_rounding
         self._param_to_name: Dict[int, str] = {}
-        self.grad_scale = 1.0           # set by the gradient-sync layer (1/world_size) or by clipping: folded into the momentum update
         self.abi_calls = 0              # st355 calls issued by step(): one per parameter group, whatever the number of matrices
-        self._flat = {}
 
-    def _group_flat(self, gi, group):
-        st = self._flat.get(gi)
-        if st is None:
-            ps = list(group["params"])
-            base = ps[0].data_ptr()
-            n = sum(p.numel() for p in ps)
-            plan = ops.MuonPlan([(p.data_ptr() - base) // 4 for p in ps], [tuple(p.shape) for p in ps], ps[0].device)
-            st = dict(ps=ps, n=n, plan=plan, m=torch.zeros(n, dtype=F32, device=ps[0].device))
-            off = 0
-            for p in ps:   # MuonClip's per-parameter state (:243-244) = views of the flat momentum
-                self.state[p] = dict(momentum_buffer=st["m"][off:off + p.numel()].view_as(p), factored=False)
-                off += p.numel()
-            self._flat[gi] = st
-        return st
+    def _group_params(self, group):
+        return list(group["params"])
+
+    def _group_extras(self, gi, group, st):
+        ps = st["ps"]
+        base = ps[0].data_ptr()
+        st["plan"] = ops.MuonPlan([(p.data_ptr() - base) // 4 for p in ps], [tuple(p.shape) for p in ps], ps[0].device)
+        for p in ps:   # MuonClip's per-parameter state (:243-244)
+            self.state[p]["factored"] = False
 
     @torch.no_grad()
     def step(self, closure=None, attention_max_logits: Optional[Dict[str, torch.Tensor]] = None):
@@ -517,11 +497,10 @@ class St355Muon(torch.optim.Optimizer):
             if all(p.grad is None for p in group["params"]):
                 continue
             st = self._group_flat(gi, group)
-            grads = [p.grad for p in st["ps"]]
-            if any(g is None for g in grads) or not _contiguous_run(grads):
+            fused = self._fused_views(st, st["ps"])
+            if fused is None:
                 raise RuntimeError("St355Muon expects the gradients of every parameter of a group as one flat fp32 arena (fused step)")
-            pflat = torch.as_strided(st["ps"][0].data, (st["n"],), (1,))
-            gflat = torch.as_strided(grads[0], (st["n"],), (1,))
+            pflat, gflat, _ = fused
             ops.muon_step(st["plan"], pflat, gflat, st["m"], muon_coefficients(group), group["lr"], momentum=group["momentum"],
                           weight_decay=group["weight_decay"], eps=group["eps"], rms_scale_factor=group["rms_scale_factor"],
                           grad_scale=self.grad_scale)
@@ -558,30 +537,43 @@ class St355Muon(torch.optim.Optimizer):
         base["param_names"] = {gi: [self._param_to_name.get(id(p), "") for p in group.get("params", [])] for gi, group in enumerate(self.param_groups)}
         return base
 
-    @torch.no_grad()
     def load_state_dict(self, state_dict: dict) -> None:
-        """resume: the saved momentum buffers are copied INTO the flat fp32 arena (created here if the optimizer has not stepped yet); the
-        saved parameter names are registered again (MuonClip.load_state_dict)"""
-        state_dict = dict(state_dict)
-        param_names = state_dict.pop("param_names", None)
-        saved = _unpack_saved_state(self, state_dict)
-        self._flat = {}
-        for p in list(self.state):
-            del self.state[p]
-        for gi, group in enumerate(self.param_groups):
-            st = self._group_flat(gi, group)
-            for p in st["ps"]:
-                old = saved.get(p)
-                if old is not None and "momentum_buffer" in old:
-                    self.state[p]["momentum_buffer"].copy_(old["momentum_buffer"].to(device=p.device, dtype=F32).view_as(p))
-        if param_names:
-            for gi, names in param_names.items():
-                gi = int(gi)
-                if gi >= len(self.param_groups):
-                    continue
-                for p, name in zip(self.param_groups[gi].get("params", []), names):
-                    if name:
-                        self._param_to_name[id(p)] = name
+        """resume: the momentum buffers as in the base class; the saved parameter names are registered again (MuonClip.load_state_dict)"""
+        super().load_state_dict(state_dict)
+        for gi, names in (state_dict.get("param_names") or {}).items():
+            gi = int(gi)
+            if gi >= len(self.param_groups):
+                continue
+            for p, name in zip(self.param_groups[gi].get("params", []), names):
+                if name:
+                    self._param_to_name[id(p)] = name
+
+
+# what the reference's registry `optimizer_choices` holds for these names (optimizer_param.py:76-96 "st355-adamw"-style entry, the reference's own
+# "adamw_bf16", "muon" :432-447 and "optimi-lion" :327-338), with the fused classes substituted
+OPTIMIZER_CHOICE = {
+    "st355-adamw": {
+        "precision": "any",
+        "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-8},
+        "class": St355AdamW,
+    },
+    "adamw_bf16": {
+        "precision": "bf16",
+        "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-6},
+        "class": St355AdamWBF16,
+    },
+    "muon": {
+        "precision": "any",
+        "default_settings": {"momentum": 0.95, "weight_decay": 0.1, "eps": 1e-7, "rms_scale_factor": 0.2, "use_smmf": False, "vector_reshape": False,
+                             "stochastic_rounding": True, "use_cans": False, "cans_a_bound": 1e-4, "qk_clip_threshold": 100.0, "qk_clip_alpha": 0.5},
+        "class": St355Muon,
+    },
+    "optimi-lion": {
+        "precision": "any",
+        "default_settings": {"betas": (0.9, 0.99), "weight_decay": 0.0, "decouple_lr": False, "max_lr": None, "kahan_sum": True, "foreach": True},
+        "class": St355Lion,
+    },
+}
 
 
 def parse_optimizer_config(config) -> dict:
@@ -615,19 +607,3 @@ def optimizer_settings(name: str, config) -> dict:
     settings = copy.deepcopy(OPTIMIZER_CHOICE[name].get("default_settings", {}))
     settings.update(parse_optimizer_config(config))
     return settings
-
-
-# the reference's own "muon" entry (optimizer_param.py:432-447), with the fused class substituted
-OPTIMIZER_CHOICE["muon"] = {
-    "precision": "any",
-    "default_settings": {"momentum": 0.95, "weight_decay": 0.1, "eps": 1e-7, "rms_scale_factor": 0.2, "use_smmf": False, "vector_reshape": False,
-                         "stochastic_rounding": True, "use_cans": False, "cans_a_bound": 1e-4, "qk_clip_threshold": 100.0, "qk_clip_alpha": 0.5},
-    "class": St355Muon,
-}
-
-# the reference's own "optimi-lion" entry (optimizer_param.py:327-338), with the fused class substituted
-OPTIMIZER_CHOICE["optimi-lion"] = {
-    "precision": "any",
-    "default_settings": {"betas": (0.9, 0.99), "weight_decay": 0.0, "decouple_lr": False, "max_lr": None, "kahan_sum": True, "foreach": True},
-    "class": St355Lion,
-}

@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, optimizer_settings
+from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, flat_view, optimizer_settings
 
 
 class St355Accelerator:
@@ -190,11 +190,10 @@ class Trainer:
         The trained values live in a bf16 arena that the optimizer steps (compensated stochastic-rounding update, its `shift` buffer); the engine's fp32
         arena mirrors it exactly (every value is a bf16 number), and the fp32 rank-space gradients are rounded to bf16 once per step — what autograd hands
         a bf16 parameter.  Returns the bf16 parameters the optimizer owns (same order, same shapes)."""
-        from .optimizer import _contiguous_run
-        if not _contiguous_run([p.data for p in self.params]):
+        flat32 = flat_view([p.data for p in self.params])
+        if flat32 is None:
             raise NotImplementedError("adamw_bf16 over fp32 trainables needs them as one flat arena (the LoRA adapter arena)")
-        n = sum(p.numel() for p in self.params)
-        flat32 = torch.as_strided(self.params[0].data, (n,), (1,))
+        n = flat32.numel()
         master = flat32.to(torch.bfloat16)
         flat32.copy_(master)                                  # the engine computes with exactly the values the optimizer holds
         grad16 = torch.zeros(n, dtype=torch.bfloat16, device=flat32.device)
@@ -251,21 +250,17 @@ class Trainer:
         grad_scale = getattr(comp, "grad_scale_from_sync", 1.0) if sync is not None else 1.0
         if acc.num_processes > 1 and not self._overlapped_sync:
             # gradient accumulation: reduce the ACCUMULATED .grad once at the boundary (DDP no_sync semantics, trainer.py:7009)
-            from .optimizer import _contiguous_run
-            grads = [p.grad for p in self.params]
-            if not _contiguous_run(grads):
+            gflat = flat_view([p.grad for p in self.params])
+            if gflat is None:
                 raise RuntimeError("accumulated gradients are not one flat arena")
-            n = sum(g.numel() for g in grads)
-            dist.all_reduce(torch.as_strided(grads[0], (n,), (1,)), op=dist.ReduceOp.SUM)
+            dist.all_reduce(gflat, op=dist.ReduceOp.SUM)
             grad_scale = 1.0 / acc.num_processes
         if getattr(cfg, "max_grad_norm", 0) and cfg.max_grad_norm > 0:                   # :7138-7217
             # the flat view is built from the gradients autograd actually holds: with gradient accumulation AccumulateGrad adds later micro-steps IN
             # PLACE into the first micro-step's buffer, so `p.grad` (not the component's last backward buffer) is what gets clipped, reduced and stepped
-            from .optimizer import _contiguous_run
-            grads = [p.grad for p in self.params]
-            if any(g is None for g in grads) or not _contiguous_run(grads):
+            gflat = flat_view([p.grad for p in self.params])
+            if gflat is None:
                 raise NotImplementedError("gradient clipping needs the trainable gradients as one flat arena (every parameter with a gradient, back to back)")
-            gflat = torch.as_strided(grads[0], (sum(g.numel() for g in grads),), (1,))
             method = getattr(cfg, "grad_clip_method", "norm")
             if method == "value":                                                        # accelerator.clip_grad_value_ (:7209-7213)
                 ops.grad_clamp_(gflat, cfg.max_grad_norm / grad_scale)                   # gradients are rank SUMS here; 1/world lives in grad_scale
@@ -280,11 +275,10 @@ class Trainer:
         ema_fused = False
         sh = self._bf16_shadow
         if sh is not None:                                                               # adamw_bf16 over the fp32 adapter arena: bf16 gradients in, bf16 weights out
-            from .optimizer import _contiguous_run
-            grads = [p.grad for p in self.params]
-            if any(g is None for g in grads) or not _contiguous_run(grads):
+            gflat = flat_view([p.grad for p in self.params])
+            if gflat is None:
                 raise RuntimeError("adamw_bf16 (LoRA): the adapter gradients are not one flat arena")
-            sh.grad16.copy_(torch.as_strided(grads[0], (sh.n,), (1,)))
+            sh.grad16.copy_(gflat)
             if any(q.grad is None for q in sh.params):      # (a zero_grad(set_to_none=True) by the caller must not detach the optimizer's parameters from their gradient arena)
                 off = 0
                 for q in sh.params:
@@ -300,7 +294,7 @@ class Trainer:
             # step count alone (ema.py:322-349), so it is known here; the kernel applies s -= (1 - d)(s - p_new) to the element it just updated — the same
             # arithmetic as the separate pass (ema.py:393-433), minus its 3 x 2 B/param of HBM traffic and one launch
             ema_decay = None
-            if self.ema_model is not None and isinstance(self.optimizer, (St355AdamW, St355Lion)):
+            if self.ema_model is not None and getattr(self.optimizer, "fuses_ema", False):
                 ema_decay = self.ema_model.fused_decay(self.params, self.state["global_step"] + 1)
             if ema_decay is not None:
                 self.optimizer.ema_shadow_flat, self.optimizer.ema_decay, self.optimizer.ema_applied = self.ema_model.shadow_flat, float(ema_decay), False
