@@ -468,6 +468,29 @@ int st355_muon_step(void* stream, const int64_t* plan_host, const int64_t* plan_
 int st355_muon_orthogonalize(void* stream, const int64_t* plan_host, const int64_t* plan_dev, const float* x, float* out, float* ws,
                              int64_t ws_floats, int normalize, double eps, int ns_steps, const float* coeffs);
 
+/* ---- SOAP (optimizers/soap/__init__.py) over an fp32 arena of 2-D matrices, short side r <= 128, the RANK side preconditioned only ----
+ * (the reference with short <= max_precond_dim < long: state["GG"] / state["Q"] hold one r x r matrix and [] for the long side, :252-256).
+ * st355_soap_plan (host only): matrices as for st355_muon_plan.  Fills plan (ST355_SOAP_PLAN_HEADER + n * ST355_SOAP_PLAN_RECORD int64) and the
+ * workspace size in floats; plan[3] = sum of r^2 = the length of the gg and q arenas (matrix i dense r x r at record field 8), plan[4] = sum of r.
+ * Every matrix is viewed as r x L, short side first (transposed if tall).  Launches per call do not depend on n; no atomics, no host sync, no
+ * allocation; fixed summation orders (bit-identical run to run). */
+#define ST355_SOAP_PLAN_HEADER 8
+#define ST355_SOAP_PLAN_RECORD 12
+int st355_soap_plan(const int64_t* offsets, const int32_t* rows, const int32_t* cols, int n, int64_t* plan, int64_t* ws_floats);
+/* one call of SOAP.step (:120-225) for every matrix.  p, g, m (exp_avg, original basis), v (exp_avg_sq, rotated basis): fp32 arenas; gg, q: plan[3] floats.
+ *   first != 0 (:138-155): GG <- lerp(GG, g' g'^T, gg_weight), Q = eigenvectors of GG by descending eigenvalue (:361-394); p, m, v untouched.
+ *   else (:157-225): g' = grad_scale g; m <- beta1 m + (1-beta1) g'; gp = Q^T g'; v <- beta2 v + (1-beta2) gp^2; mp = Q^T m;
+ *     u = Q (mp / (sqrt(v) + eps)); p <- p - step_size u; if lr_weight_decay > 0: p <- p - lr_weight_decay p (:205-216); then GG as above (:290-327);
+ *     refresh != 0 (:331-332, :396-453): est = diag(Q^T GG Q), stable descending sort, Q <- qr(GG Q[:, idx]).Q (column signs free; a zero or
+ *     dependent column gets an orthonormal completion), v permuted along the short side by idx.
+ * step_size carries the bias correction (lr sqrt(1 - beta2^t) / (1 - beta1^t), :187-191), computed by the caller in double; gg_weight = 1 - shampoo_beta. */
+int st355_soap_step(void* stream, const int64_t* plan_host, const int64_t* plan_dev, float* p, const float* g, float* m, float* v, float* gg,
+                    float* q, float* ws, int64_t ws_floats, float grad_scale, double beta1, double beta2, double eps, double step_size,
+                    double lr_weight_decay, double gg_weight, int first, int refresh);
+/* the bare eigensolver: q = eigenvectors (columns) of every symmetric r x r matrix of gg, eigenvalues descending (written to evals, plan[4] floats at
+ * record field 10, unless NULL) — flip(eigh(.)) of :385-389.  A zero matrix gives the identity. */
+int st355_soap_eigh(void* stream, const int64_t* plan_host, const int64_t* plan_dev, const float* gg, float* q, float* evals);
+
 /* ---- LayerSync (helpers/training/layersync.py): self-alignment of two block outputs, cosine per token row, F.normalize semantics x / max(|x|, 1e-12) ----
  * student, teacher: [B, rows, D] bf16 views with row stride ld and their own batch strides (elements), e.g. the image rows of a joint [B * S, D] buffer; the
  * teacher is a constant (detached).  Per row c = <s^, t^> -> cos_rows[B * rows] fp32; G[B * rows, D] bf16 (compact) = (t^ - c s^) / max(|s|, 1e-12) / (B * rows)

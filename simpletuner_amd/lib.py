@@ -26,6 +26,7 @@ SYMBOLS = [
     "st355_attn_set_impl", "st355_attn_plan", "st355_attn_fwd", "st355_attn_fwd_vrows", "st355_attn_bwd_workspace", "st355_attn_bwd", "st355_attn_bwd_rope",
     "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_lion_step", "st355_lion_step_bf16", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
     "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
+    "st355_soap_plan", "st355_soap_step", "st355_soap_eigh",
     "st355_layersync_fwd", "st355_layersync_inject",
     "st355_lora_pack",
     "st355_workspace_bytes",
@@ -346,6 +347,9 @@ def _declare(lib):
         "st355_muon_plan": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "st355_muon_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]),
         "st355_muon_orthogonalize": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, C.c_double, i32, vp]),
+        "st355_soap_plan": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+        "st355_soap_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32]),
+        "st355_soap_eigh": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "st355_layersync_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, vp]),
         "st355_layersync_inject": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
         "st355_lora_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32]),

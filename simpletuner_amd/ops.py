@@ -1108,6 +1108,80 @@ def muon_orthogonalize(plan: MuonPlan, x, coeffs, normalize: bool = True, eps: f
     return out
 
 
+class SoapPlan:
+    """st355_soap_plan for a fixed list of matrices of one fp32 arena (element offsets, shapes): the host plan, its device copy and the workspace,
+    made once.  `qq` is the length of the GG / Q arenas (sum of r^2, r = a matrix's short side), `rr` the sum of r; `q_offsets[i]`, `short[i]`
+    place matrix i's r x r block in them"""
+
+    HEADER, RECORD = 8, 12
+
+    def __init__(self, offsets, shapes, device):
+        n = len(shapes)
+        if n == 0 or len(offsets) != n:
+            raise _l.St355Error("soap_plan: expected one offset per matrix shape")
+        L = _l.load()
+        off = (C.c_int64 * n)(*[int(o) for o in offsets])
+        rows = (C.c_int32 * n)(*[int(s[0]) for s in shapes])
+        cols = (C.c_int32 * n)(*[int(s[1]) for s in shapes])
+        self.host = torch.zeros(self.HEADER + self.RECORD * n, dtype=torch.int64)
+        ws = C.c_int64(0)
+        _l.check(L.st355_soap_plan(off, rows, cols, n, _ptr(self.host), C.byref(ws)), "soap_plan")
+        self.n = n
+        self.ws_floats = int(ws.value)
+        self.qq, self.rr = int(self.host[3]), int(self.host[4])
+        rec = self.host[self.HEADER:].view(n, self.RECORD)
+        self.short = rec[:, 1].tolist()
+        self.q_offsets = rec[:, 8].tolist()
+        self.r_offsets = rec[:, 10].tolist()
+        self.idx_offsets = rec[:, 9].tolist()
+        self.dev = self.host.to(device)
+        self.ws = torch.zeros(self.ws_floats, dtype=F32, device=device)
+
+    def launches(self, first: bool = False, refresh: bool = False) -> int:
+        """kernel launches of one call: the step (or the Gram pass) per short-side class present, the fold, then the eigensolver on the first call or
+        the refresh and one permutation per class"""
+        ncls = len(set(self.host[self.HEADER:].view(self.n, self.RECORD)[:, 3].tolist()))
+        return ncls + 1 + (1 if first else (1 + ncls if refresh else 0))
+
+    def sort_index(self, i: int):
+        """the index the last refresh sorted matrix i's eigenbasis by (int32 [r], a view of the workspace)"""
+        o = self.idx_offsets[i]
+        return self.ws[o:o + self.short[i]].view(torch.int32)
+
+
+def soap_step(plan: SoapPlan, p, g, m, v, gg, q, step_size: float, beta1: float, beta2: float, eps: float, lr_weight_decay: float,
+              gg_weight: float, first: bool, refresh: bool, grad_scale: float = 1.0):
+    """one SOAP call over the arena (p, g, m, v: fp32 flat, plan offsets into them; gg, q: the plan's r x r blocks), in place.  first: only
+    GG and the eigenbasis; refresh: the basis is re-sorted and re-orthogonalised after the update.  step_size carries the bias correction"""
+    L = _l.load()
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _chk(t, F32, nm)
+        if not t.is_contiguous() or t.numel() != p.numel():
+            raise _l.St355Error(f"soap_step: {nm} must be a contiguous fp32 arena of {p.numel()} elements")
+    for t, nm in ((gg, "gg"), (q, "q")):
+        _chk(t, F32, nm)
+        if not t.is_contiguous() or t.numel() != plan.qq:
+            raise _l.St355Error(f"soap_step: {nm} must be a contiguous fp32 arena of {plan.qq} elements")
+    _l.check(L.st355_soap_step(_stream(), _ptr(plan.host), _ptr(plan.dev), _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(gg), _ptr(q), _ptr(plan.ws),
+                               plan.ws_floats, float(grad_scale), float(beta1), float(beta2), float(eps), float(step_size), float(lr_weight_decay),
+                               float(gg_weight), int(bool(first)), int(bool(refresh))), "soap_step")
+
+
+def soap_eigh(plan: SoapPlan, gg, q=None, evals=None):
+    """eigenvectors (columns of each r x r block of q) and eigenvalues (descending, plan.rr floats) of every symmetric block of gg"""
+    L = _l.load()
+    _chk(gg, F32, "gg")
+    if not gg.is_contiguous() or gg.numel() != plan.qq:
+        raise _l.St355Error(f"soap_eigh: gg must be a contiguous fp32 arena of {plan.qq} elements")
+    q = torch.zeros_like(gg) if q is None else q
+    evals = torch.zeros(plan.rr, dtype=F32, device=gg.device) if evals is None else evals
+    _chk(q, F32, "q"); _chk(evals, F32, "evals")
+    if q.numel() != plan.qq or evals.numel() != plan.rr or not q.is_contiguous() or not evals.is_contiguous():
+        raise _l.St355Error("soap_eigh: q / evals do not match the plan")
+    _l.check(L.st355_soap_eigh(_stream(), _ptr(plan.host), _ptr(plan.dev), _ptr(gg), _ptr(q), _ptr(evals)), "soap_eigh")
+    return q, evals
+
+
 def _token_view(t, name: str):
     """a [B, rows, D] bf16 view with unit inner stride (e.g. the image rows of a joint [B * S, D] buffer): (B, rows, D, row stride, batch stride)"""
     _chk(t, BF16, name)

@@ -60,7 +60,7 @@ def _unpack_saved_state(opt: torch.optim.Optimizer, state_dict: dict):
 
 
 class _ArenaOptimizer(torch.optim.Optimizer):
-    """What the four fused optimizers share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
+    """What the fused arena optimizers (AdamW, AdamWBF16, Lion, Muon, SOAP) share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
     per-parameter state installed as views of them (`_flat[gi]`: ok, ps, n, one entry per declared buffer, the subclass's extras); a
     `load_state_dict` that copies a checkpoint INTO those buffers in the dtype each is kept in; and the test for the one-launch path.
     A subclass declares `_buffers`, adds its extras in `_group_extras` / `_load_extras`, and issues its `ops.*` calls in `step`."""
@@ -549,8 +549,134 @@ class St355Muon(_ArenaOptimizer):
                     self._param_to_name[id(p)] = name
 
 
+# ---- SOAP ------------------------------------------------------------------------------------------------------------------------
+SOAP_MAX_SHORT_SIDE = 128
+
+
+class St355Soap(_ArenaOptimizer):
+    """SOAP (optimizers/soap/__init__.py: Adam in the eigenbasis of Shampoo's preconditioner) over the fp32 adapter arena, as one st355_soap_step
+    call per parameter group, with the RANK side of every adapter matrix preconditioned and the long side left as identity: every parameter
+    needs short <= max_precond_dim < long (DESIGN.md §7 — with the long side preconditioned as well the reference's own trajectory is not
+    reproducible, so that is refused, not approximated).
+
+    Same constructor (every keyword of SOAP, same defaults), same per-parameter state in the reference's layout: `step` (int), `exp_avg`
+    (original basis), `exp_avg_sq` (rotated basis), `GG` and `Q` as two-element lists with `[]` on the identity side, `precondition_frequency`,
+    `shampoo_beta` — the tensors are views of flat fp32 buffers, and a `state_dict()` of the reference class loads here.  The first call only
+    builds GG and its eigenbasis (:138-155); afterwards the basis is refreshed after the update of every step with step % precondition_frequency
+    == 0 (:331-332).  Parameters must be 2-D fp32 views of one contiguous arena with a short side of at most 128.  `merge_dims` and
+    `normalize_grads` are refused; `precondition_1d` and `data_format` have no effect on 2-D parameters and are accepted."""
+    _buffers = {"exp_avg": ("m", F32), "exp_avg_sq": ("v", F32)}
+
+    def __init__(self, params, lr: float = 3e-3, betas=(0.95, 0.95), shampoo_beta: float = -1, eps: float = 1e-8, weight_decay: float = 0.01,
+                 precondition_frequency: int = 10, max_precond_dim: int = 10000, merge_dims: bool = False, precondition_1d: bool = False,
+                 normalize_grads: bool = False, data_format: str = "channels_first", correct_bias: bool = True):
+        if merge_dims:
+            raise NotImplementedError("soap: merge_dims=True is not built on the st355 path")
+        if normalize_grads:
+            raise NotImplementedError("soap: normalize_grads=True (a per-tensor mean before the apply) is not built on the st355 path")
+        if int(precondition_frequency) < 1:
+            raise ValueError(f"Invalid precondition_frequency: {precondition_frequency}")
+        defaults = dict(lr=lr, betas=betas, shampoo_beta=shampoo_beta, eps=eps, weight_decay=weight_decay,
+                        precondition_frequency=precondition_frequency, max_precond_dim=max_precond_dim, merge_dims=merge_dims,
+                        precondition_1d=precondition_1d, normalize_grads=normalize_grads, correct_bias=correct_bias)
+        super().__init__(params, defaults)
+        self._data_format = data_format
+        for group in self.param_groups:
+            ps = group["params"]
+            mpd = group["max_precond_dim"]
+            for i, p in enumerate(ps):
+                if p.dim() != 2:
+                    raise NotImplementedError(f"soap: parameter {i} has {p.dim()} dimensions; only 2-D matrices are built on the st355 path")
+                if p.dtype != F32:
+                    raise NotImplementedError(f"soap: parameter {i} is {p.dtype}; the st355 path steps fp32 adapter values")
+                short, long = min(p.shape), max(p.shape)
+                if short > SOAP_MAX_SHORT_SIDE:
+                    raise NotImplementedError(f"soap: parameter {i} of shape {tuple(p.shape)} has a short side above {SOAP_MAX_SHORT_SIDE}")
+                if not short <= mpd < long:
+                    hint = SOAP_MAX_SHORT_SIDE if short <= SOAP_MAX_SHORT_SIDE < long else short
+                    raise NotImplementedError(
+                        f"soap: max_precond_dim={mpd} with parameter {i} of shape {tuple(p.shape)} is not built on the st355 path: only the rank side "
+                        f"is preconditioned, which needs {short} <= max_precond_dim <= {long - 1} (short side <= max_precond_dim < long side); "
+                        f"set --optimizer_config=max_precond_dim={hint}")
+            if flat_view([p.data for p in ps]) is None:
+                raise NotImplementedError("soap: the parameters of a group must be one contiguous fp32 run (the adapter arena)")
+        self.abi_calls = 0              # st355 calls issued by step(): one per parameter group, whatever the number of matrices
+
+    def _group_params(self, group):
+        return list(group["params"])
+
+    def _group_extras(self, gi, group, st):
+        ps = st["ps"]
+        base = ps[0].data_ptr()
+        plan = st["plan"] = ops.SoapPlan([(p.data_ptr() - base) // 4 for p in ps], [tuple(p.shape) for p in ps], ps[0].device)
+        st["gg"] = torch.zeros(plan.qq, dtype=F32, device=ps[0].device)
+        st["q"] = torch.zeros(plan.qq, dtype=F32, device=ps[0].device)
+        st["step"] = 0
+        st["ready"] = False             # True once the first call has built the eigenbasis
+        st["precondition_frequency"] = int(group["precondition_frequency"])
+        st["shampoo_beta"] = float(group["shampoo_beta"] if group["shampoo_beta"] >= 0 else group["betas"][1])     # :144
+        for p, off, r in zip(ps, plan.q_offsets, plan.short):
+            gg, q = st["gg"][off:off + r * r].view(r, r), st["q"][off:off + r * r].view(r, r)
+            wide = p.shape[0] < p.shape[1]
+            self.state[p].update(step=0, GG=[gg, []] if wide else [[], gg], Q=[q, []] if wide else [[], q],
+                                 precondition_frequency=st["precondition_frequency"], shampoo_beta=st["shampoo_beta"])
+
+    def _load_extras(self, st, mine, old):
+        """the preconditioner, its eigenbasis and the counters of one parameter (reference layout: the matrix on the rank side, [] on the other)"""
+        for key in ("GG", "Q"):
+            saved = old.get(key)
+            if saved is None:
+                continue
+            for dst, src in zip(mine[key], saved):
+                if torch.is_tensor(dst) != torch.is_tensor(src) or (torch.is_tensor(dst) and dst.shape != src.shape):
+                    raise NotImplementedError(f"soap: the saved {key} preconditions another side than the st355 path (max_precond_dim must lie between "
+                                              "the two sides of every parameter)")
+                if torch.is_tensor(dst):
+                    dst.copy_(src.to(device=dst.device, dtype=F32))
+        k = int(old.get("step", 0))
+        mine["step"] = k
+        # the basis exists once the first call has run: the buffers hold an all-zero Q until then (also in a checkpoint written before any step)
+        ready = old.get("Q") is not None and any(torch.is_tensor(t) and bool(t.any()) for t in old["Q"])
+        freq, sb = int(old.get("precondition_frequency", st["precondition_frequency"])), float(old.get("shampoo_beta", st["shampoo_beta"]))
+        if st.get("_loaded") and (st["step"], st["ready"], st["precondition_frequency"], st["shampoo_beta"]) != (k, ready, freq, sb):
+            raise NotImplementedError("soap: the parameters of a group must share step, precondition_frequency and shampoo_beta (one fused call)")
+        st.update(step=k, ready=ready, precondition_frequency=freq, shampoo_beta=sb, _loaded=True)
+        mine["precondition_frequency"], mine["shampoo_beta"] = freq, sb
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for gi, group in enumerate(self.param_groups):
+            if all(p.grad is None for p in group["params"]):
+                continue
+            st = self._group_flat(gi, group)
+            fused = self._fused_views(st, st["ps"])
+            if fused is None:
+                raise RuntimeError("St355Soap expects the gradients of every parameter of a group as one flat fp32 arena (fused step)")
+            pflat, gflat, _ = fused
+            b1, b2 = group["betas"]
+            lr = group["lr"]
+            first = not st["ready"]
+            step_size, refresh = 0.0, False
+            if not first:
+                st["step"] += 1
+                t = st["step"]
+                step_size = lr
+                if group["correct_bias"]:                                      # :187-191, host doubles
+                    step_size = step_size * ((1.0 - b2 ** t) ** 0.5) / (1.0 - b1 ** t)
+                refresh = t % st["precondition_frequency"] == 0               # :331-332
+            ops.soap_step(st["plan"], pflat, gflat, st["m"], st["v"], st["gg"], st["q"], step_size, b1, b2, group["eps"],
+                          lr * group["weight_decay"] if group["weight_decay"] > 0.0 else 0.0, 1.0 - st["shampoo_beta"], first, refresh,
+                          grad_scale=self.grad_scale)
+            st["ready"] = True
+            self.abi_calls += 1
+            for p in st["ps"]:
+                self.state[p]["step"] = st["step"]
+        return loss
+
+
 # what the reference's registry `optimizer_choices` holds for these names (optimizer_param.py:76-96 "st355-adamw"-style entry, the reference's own
-# "adamw_bf16", "muon" :432-447 and "optimi-lion" :327-338), with the fused classes substituted
+# "adamw_bf16", "muon" :432-447, "optimi-lion" :327-338 and "soap" :415-431), with the fused classes substituted
 OPTIMIZER_CHOICE = {
     "st355-adamw": {
         "precision": "any",
@@ -572,6 +698,13 @@ OPTIMIZER_CHOICE = {
         "precision": "any",
         "default_settings": {"betas": (0.9, 0.99), "weight_decay": 0.0, "decouple_lr": False, "max_lr": None, "kahan_sum": True, "foreach": True},
         "class": St355Lion,
+    },
+    "soap": {
+        "precision": "any",
+        "default_settings": {"betas": (0.95, 0.95), "shampoo_beta": -1, "eps": 1e-8, "weight_decay": 0.01, "precondition_frequency": 10,
+                             "max_precond_dim": 10000, "merge_dims": False, "precondition_1d": False, "normalize_grads": False,
+                             "data_format": "channels_first", "correct_bias": True},
+        "class": St355Soap,
     },
 }
 

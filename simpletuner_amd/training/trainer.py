@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, flat_view, optimizer_settings
+from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, St355Soap, flat_view, optimizer_settings
 
 
 class St355Accelerator:
@@ -106,8 +106,8 @@ class Trainer:
                        else [p for p in comp.parameters() if p.requires_grad])
         # optimizer_param.py:76-96 registry semantics: name -> class (+ default settings)
         opt_name = getattr(config, "optimizer", "st355-adamw")
-        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion"):           # never a silently different optimizer
-            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, st355-adamw = torch-adamw semantics)")
+        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap"):   # never a silently different optimizer
+            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, st355-adamw = torch-adamw semantics)")
         self._bf16_shadow = None
         if opt_name == "muon":
             if not getattr(self.model, "SUPPORTS_MUON_CLIP", False):                   # trainer.py:332-339
@@ -120,6 +120,13 @@ class Trainer:
             if hasattr(self.model, "enable_muon_clip_logging"):
                 self.model.enable_muon_clip_logging()
             self.optimizer = St355Muon(self.params, lr=config.learning_rate, **optimizer_settings("muon", config))
+        elif opt_name == "soap":
+            if getattr(comp, "full", False):
+                raise NotImplementedError("optimizer 'soap' is built for LoRA adapters only: a full-rank matrix or a full fine-tune has short sides up to "
+                                          "3072 (the kernel preconditions a rank side of at most 128)")
+            if getattr(config, "hip_graph", False):
+                raise NotImplementedError("optimizer 'soap' cannot run under hip_graph: the eigenbasis refresh changes the launch sequence on some steps")
+            self.optimizer = St355Soap(self.params, lr=config.learning_rate, **optimizer_settings("soap", config))
         elif opt_name == "adamw_bf16":
             opt_params = self.params
             if any(p.dtype != torch.bfloat16 for p in self.params):
