@@ -64,6 +64,32 @@ def _seg_join(cur: int, new: int, name: str) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# device scratch
+# ------------------------------------------------------------------------------------------------
+# One scratch per (name, device), not per (device, stream) as grad_norm's (its key= is the stream): no caller issues skinny products, or any other scratch user
+# but grad_norm, on two streams at once.  LoraGroup.grads and the block megakernels run on the training stream; the trainer's graph warm-up / capture stream is
+# joined with wait_stream before and after, so the two never overlap; grad_sync's comm stream runs collectives only.  A caller that does overlap them must bring
+# its own workspace through the C ABI.
+_scratch_bufs = {}
+_scratch_retired = []       # outgrown scratch buffers stay alive: a captured hipGraph may still hold their addresses
+
+
+def _scratch(name: str, dev, nbytes: int, key=()):
+    """caller-owned device scratch of at least nbytes bytes (uint8; the kernels only receive the pointer); libst355 never allocates.  Grow-only; an outgrown
+    buffer is retired, never freed (a hipGraph captured earlier keeps its address), and growing DURING a capture is refused (the capture would bake in a pointer
+    of its private pool).  A first allocation is allowed inside a capture."""
+    k = (name, dev.type, dev.index) + key
+    ws = _scratch_bufs.get(k)
+    if ws is None or ws.numel() < nbytes:
+        if ws is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _l.St355Error(f"the {name} scratch would have to grow ({ws.numel()} -> {nbytes} bytes) inside a hipGraph capture: run one eager step first")
+            _scratch_retired.append(ws)
+        ws = _scratch_bufs[k] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+# ------------------------------------------------------------------------------------------------
 # streaming ops
 # ------------------------------------------------------------------------------------------------
 def flow_noise_mix(x, sigma, noise=None, seed: int = 0, offset: int = 0, want_target: bool = True):
@@ -275,7 +301,6 @@ def scale_cols(x, gate, rows_per_batch: int, out=None):
 # ------------------------------------------------------------------------------------------------
 # GEMM family
 # ------------------------------------------------------------------------------------------------
-_gemm_ws = {}
 _GEMM_WS_BYTES = 512 << 20           # ONE size for every caller (r5 advice: a smaller first request made a later one re-allocate under captured graphs): the largest
                                      # user is the weight-gradient split-K (7 slices of a 6144 x 1536 gradient: 264 MB); the stream-K tail keeps up to 128 x 3 tile slabs (96 MiB)
 _gemm_flags = {}
@@ -292,22 +317,9 @@ def _gemm_tile_flags(dev):
     return f
 
 
-
-_ws_retired = []       # outgrown scratch buffers stay alive: a captured hipGraph may still hold their addresses
-
-
-def _gemm_workspace(dev, nbytes: int = _GEMM_WS_BYTES):
-    """caller-owned fp32 scratch for the split-K paths (thin GEMMs, weight gradients); libst355 never allocates.  Grow-only; an outgrown buffer is retired, never
-    freed (a hipGraph captured earlier keeps its address), and growing DURING a capture is refused (the capture would bake in a pointer of its private pool)"""
-    ws = _gemm_ws.get(dev.index)
-    if ws is None or ws.numel() * 4 < nbytes:
-        if ws is not None:
-            if torch.cuda.is_current_stream_capturing():
-                raise _l.St355Error(f"the shared GEMM scratch would have to grow ({ws.numel() * 4} -> {nbytes} bytes) inside a hipGraph capture: run one eager step first")
-            _ws_retired.append(ws)
-        ws = torch.empty(nbytes // 4, dtype=F32, device=dev)
-        _gemm_ws[dev.index] = ws
-    return ws
+def _gemm_workspace(dev):
+    """the shared scratch of the split-K paths (thin GEMMs, weight gradients) and the stream-K tail; its byte count is .numel()"""
+    return _scratch("gemm", dev, _GEMM_WS_BYTES)
 
 
 def qk_rope(Q, K, rrms, wq, wk, cos, sin, H: int, S: int, pos0: int, eps: float = 1e-6, Vt=None):
@@ -397,7 +409,7 @@ def _gemm_args(g, a, w, bias=None, out=None, epilogue: int = EPI_NONE, a2=None, 
     g.epilogue = epilogue
     if (N <= 128 and M >= 1024) or (M * N >= 128 * 65536 and epilogue <= EPI_ADD):       # thin problems (split-K slabs); 128+ tiles of 256x256 (stream-K tail)
         ws = _gemm_workspace(a.device)
-        g.workspace, g.workspace_bytes = _ptr(ws), ws.numel() * 4
+        g.workspace, g.workspace_bytes = _ptr(ws), ws.numel()
         g.tile_flags = _ptr(_gemm_tile_flags(a.device))
     if aux_out is not None:
         _chk(aux_out, BF16, "aux_out")
@@ -602,14 +614,11 @@ def gemm_tn(Lm, R, out=None, accumulate: bool = False):
         if seg_a and seg_b and seg_a != seg_b:
             raise _l.St355Error("gemm_tn: two segmented operands must share the segment length")
         _l.check(L.st355_gemm_tn_seg_bf16(_stream(), _ptr(Lm), ldl, str_a if seg_a else 0, _ptr(R), ldr, str_b if seg_b else 0, _ptr(out), _rows(out, "out"),
-                                          M, seg, P, Q, 1 if accumulate else 0, _ptr(ws), ws.numel() * 4), "gemm_tn_seg_bf16")
+                                          M, seg, P, Q, 1 if accumulate else 0, _ptr(ws), ws.numel()), "gemm_tn_seg_bf16")
         return out
     _l.check(L.st355_gemm_tn_bf16(_stream(), _ptr(Lm), ldl, _ptr(R), ldr, _ptr(out), _rows(out, "out"), M, P, Q,
-                                  1 if accumulate else 0, _ptr(ws), ws.numel() * 4), "gemm_tn_bf16")
+                                  1 if accumulate else 0, _ptr(ws), ws.numel()), "gemm_tn_bf16")
     return out
-
-
-_colsum_ws = {}
 
 
 def colsum_prod(a, out, b=None, rows_per_batch: Optional[int] = None, mode: int = 0, prev=None, shift=None, scale=None, accumulate: bool = False):
@@ -620,11 +629,7 @@ def colsum_prod(a, out, b=None, rows_per_batch: Optional[int] = None, mode: int 
     rpb = rows if rows_per_batch is None else rows_per_batch
     if b is not None:
         _chk(b, BF16, "b")
-    need = L.st355_colsum_workspace(rows, N, rpb)
-    ws = _colsum_ws.get(a.device.index)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=F32, device=a.device)
-        _colsum_ws[a.device.index] = ws
+    ws = _scratch("colsum", a.device, L.st355_colsum_workspace(rows, N, rpb))
     ms = 0
     if mode == 1:
         _chk(shift, BF16, "shift"); _chk(scale, BF16, "scale"); _chk(prev, F32, "prev")
@@ -635,18 +640,6 @@ def colsum_prod(a, out, b=None, rows_per_batch: Optional[int] = None, mode: int 
                                  _rows(out, "out"), mode, _ptr(prev), _rows(prev, "prev") if prev is not None else 0, _ptr(shift), _ptr(scale),
                                  ms, 1 if accumulate else 0, _ptr(ws)), "colsum_prod")
     return out
-
-
-_stats_ws = {}
-
-
-def _stats_workspace(dev, nbytes: int):
-    ws = _stats_ws.get(dev.index)
-    if ws is None or ws.numel() * 4 < nbytes:
-        if ws is not None:
-            _ws_retired.append(ws)
-        ws = _stats_ws[dev.index] = torch.empty((nbytes + 3) // 4, dtype=F32, device=dev)
-    return ws
 
 
 def stat_out(out, reduce_batches: bool = False, accumulate: bool = False):
@@ -672,7 +665,7 @@ def ln_modulate_bwd_stats(dy, x, scale, rows_per_batch: int, d_shift, d_scale, d
     rows, D = x.shape
     dx = torch.empty(rows, D, dtype=BF16, device=x.device) if out is None else out
     dxg = torch.empty(rows, D, dtype=BF16, device=x.device) if want_gated else None
-    ws = _stats_workspace(x.device, L.st355_stats_workspace(rows, D, rows_per_batch, 4))
+    ws = _scratch("stats", x.device, L.st355_stats_workspace(rows, D, rows_per_batch, 4))
     outs = [stat_out(d_shift), stat_out(d_scale), stat_out(d_gate), stat_out(d_bias, reduce_batches=True)]
     _l.check(L.st355_ln_modulate_bwd_stats(_stream(), _ptr(dy), _rows(dy, "dy"), _ptr(x), _rows(x, "x"), _ptr(scale), _rows(scale, "scale"), rows_per_batch,
                                            _ptr(dres), _rows(dres, "dres") if dres is not None else 0, _ptr(gate) if want_gated else None,
@@ -689,7 +682,7 @@ def scale_cols_stats(x, gate, rows_per_batch: int, y_branch=None, d_gate=None, d
     M, N = x.shape
     if out is None:
         out = torch.empty(M, N, dtype=BF16, device=x.device)
-    ws = _stats_workspace(x.device, L.st355_stats_workspace(M, N, rows_per_batch, 2))
+    ws = _scratch("stats", x.device, L.st355_stats_workspace(M, N, rows_per_batch, 2))
     og, ob = stat_out(d_gate), stat_out(d_bias, reduce_batches=True)
     _l.check(L.st355_scale_cols_stats(_stream(), _ptr(x), _rows(x, "x"), _ptr(gate), _rows(gate, "gate"), rows_per_batch, _ptr(out), _rows(out, "out"), M, N,
                                       _ptr(y_branch), _rows(y_branch, "y_branch") if y_branch is not None else 0, C.byref(og), C.byref(ob), _ptr(ws)),
@@ -703,7 +696,7 @@ def colsum_rows(a, rows_per_batch: int, batch_stride_rows: int, nb: int, out, pe
     L = _l.load()
     _chk(a, BF16, "a")
     N = a.shape[1]
-    ws = _stats_workspace(a.device, L.st355_stats_workspace(nb * rows_per_batch, N, rows_per_batch, 1))
+    ws = _scratch("stats", a.device, L.st355_stats_workspace(nb * rows_per_batch, N, rows_per_batch, 1))
     o = stat_out(out, reduce_batches=not per_batch, accumulate=accumulate)
     _l.check(L.st355_colsum_rows(_stream(), _ptr(a), _rows(a, "a"), rows_per_batch, batch_stride_rows, nb, N, C.byref(o), _ptr(ws)), "colsum_rows")
     return out
@@ -721,10 +714,9 @@ def transpose(src, out=None):
     return out
 
 
-# One split-M workspace per device, not per (device, stream) as grad_norm's scratch: no caller issues skinny products on two streams at once.  LoraGroup.grads and
-# the block megakernels run on the training stream; the trainer's graph warm-up / capture stream is joined with wait_stream before and after, so the two never
-# overlap; grad_sync's comm stream runs collectives only.  A caller that does overlap them must bring its own workspace through the C ABI.
-_skinny_ws = {}
+def _skinny_scratch(dev, M: int, P: int, R: int):
+    """the split-M partials of skinny_tn / skinny_tn_multi and of the Flux backward blocks: one scratch per device (see _scratch)"""
+    return _scratch("skinny", dev, _l.load().st355_skinny_tn_workspace(M, P, R))
 
 
 def skinny_plan(M: int, P: int, seg_rows: int = 0):
@@ -744,12 +736,7 @@ def skinny_tn(Lm, R, out, so_p: int, so_r: int, r_used: int, alpha: float = 1.0,
     if Mr != M:
         raise _l.St355Error(f"skinny_tn: L has {M} rows, R has {Mr}")
     seg = _seg_join(seg, sr, "skinny_tn")
-    need = L.st355_skinny_tn_workspace(M, P, Rn)
-    key = (Lm.device.index,)
-    ws = _skinny_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=F32, device=Lm.device)
-        _skinny_ws[key] = ws
+    ws = _skinny_scratch(Lm.device, M, P, Rn)
     _l.check(L.st355_skinny_tn_seg(_stream(), _ptr(Lm), ldl, _ptr(R), ldr, _ptr(out), so_p, so_r, M, P, Rn,
                                    r_used, alpha, 1 if accumulate else 0, _ptr(ws), seg, seg_l, seg_r), "skinny_tn")
     return out
@@ -766,12 +753,7 @@ def skinny_tn_multi(Lm, R, outs, so_p: int, so_r: int, r_used: int, alpha: float
     seg = _seg_join(seg, sr, "skinny_tn_multi")
     for o in outs:
         _chk(o, F32, "out")
-    need = L.st355_skinny_tn_workspace(M, P, 128)
-    key = (Lm.device.index,)
-    ws = _skinny_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=F32, device=Lm.device)
-        _skinny_ws[key] = ws
+    ws = _skinny_scratch(Lm.device, M, P, 128)
     arr = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
     _l.check(L.st355_skinny_tn_multi(_stream(), _ptr(Lm), ldl, _ptr(R), ldr, arr, len(outs), so_p, so_r, M, P, r_used, alpha, 1 if accumulate else 0,
                                      _ptr(ws), seg, seg_l, seg_r), "skinny_tn_multi")
@@ -849,9 +831,6 @@ def qk_norm_rope_bwd(dQ, dK, qkv, wq, wk, cos, sin, dqkv, B, H, d, S_part, pos0,
              "qk_norm_rope_bwd")
 
 
-_qkwg_ws = {}
-
-
 def qk_norm_rope_bwd_wgrad(dQ, dK, qkv, wq, wk, cos, sin, dqkv, B, H, d, S_part, pos0, S, gwq, gwk, accumulate: bool = False, eps: float = 1e-6):
     """qk_norm_rope_bwd + d loss / d (norm_q.weight, norm_k.weight) into the bf16 [d] views gwq / gwk (None: absent / frozen)"""
     L = _l.load()
@@ -859,11 +838,7 @@ def qk_norm_rope_bwd_wgrad(dQ, dK, qkv, wq, wk, cos, sin, dqkv, B, H, d, S_part,
     for g in (gwq, gwk):
         if g is not None:
             _chk(g, BF16, "gw")
-    need = L.st355_qk_norm_wgrad_workspace(B, H, d, S_part)
-    ws = _qkwg_ws.get(dQ.device.index)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=F32, device=dQ.device)
-        _qkwg_ws[dQ.device.index] = ws
+    ws = _scratch("qk_norm_wgrad", dQ.device, L.st355_qk_norm_wgrad_workspace(B, H, d, S_part))
     _l.check(L.st355_qk_norm_rope_bwd_wgrad(_stream(), _ptr(dQ), _ptr(dK), _ptr(qkv), _rows(qkv, "qkv"), _ptr(wq), _ptr(wk), _ptr(cos), _ptr(sin),
                                             _ptr(dqkv), _rows(dqkv, "dqkv"), B, H, d, S_part, pos0, S, eps, _ptr(gwq), _ptr(gwk),
                                             1 if accumulate else 0, _ptr(ws)), "qk_norm_rope_bwd_wgrad")
@@ -907,7 +882,9 @@ def attn_fwd_vrows(Q, K, v_rows, O, lse2, B, H, S, d, scale: float, key_bias=Non
                                     _ptr(lse2), B, H, S, d, scale), "attn_fwd_vrows")
 
 
-_attn_ws = {}
+def _attn_bwd_scratch(dev, B, H, S, Sp, d):
+    """the partials of the attention backward: one scratch per device, shared by attn_bwd, attn_bwd_rope, attn_cross_bwd and the block backward entry points"""
+    return _scratch("attn_bwd", dev, _l.load().st355_attn_bwd_workspace(B, H, S, Sp, d))
 
 
 # ST355_ATTN_TR=0: the engines build head-major Q^T / K^T copies and the backward reads them (dkv2 / dq); default: no copies, transposing LDS reads
@@ -916,12 +893,7 @@ ATTN_TR = os.environ.get("ST355_ATTN_TR", "1") != "0"
 
 def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None):
     L = _l.load()
-    need = L.st355_attn_bwd_workspace(B, H, S, Sp, d)
-    key = (Q.device.index,)
-    ws = _attn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=Q.device)
-        _attn_ws[key] = ws
+    ws = _attn_bwd_scratch(Q.device, B, H, S, Sp, d)
     if O_res is not None:          # delta = rowsum(dO * (O + O_res))
         _res_ok(O, O_res)
         _l.check(L.st355_attn_bwd_res(_stream(), _ptr(Q), _ptr(K), _ptr(Qt), _ptr(Kt), _ptr(v_rows), _rows(v_rows, "v_rows"),
@@ -939,12 +911,7 @@ def attn_bwd_rope(Q, K, v_rows, O, dO, lse2, rrms, wq_lo, wk_lo, wq_hi, wk_hi, s
     written straight into the rows of the projection gradient dqkv [B*S, >= 3*H*d]; joint positions < split use the *_lo norm weights."""
     L = _l.load()
     _chk(Q, BF16, "Q"); _chk(K, BF16, "K"); _chk(rrms, F32, "rrms"); _chk(dqkv, BF16, "dqkv"); _chk(cos_p, F32, "cos_p"); _chk(sin_p, F32, "sin_p")
-    need = L.st355_attn_bwd_workspace(B, H, S, Sp, d)
-    key = (Q.device.index,)
-    ws = _attn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=Q.device)
-        _attn_ws[key] = ws
+    ws = _attn_bwd_scratch(Q.device, B, H, S, Sp, d)
     _l.check(L.st355_attn_bwd_rope(_stream(), _ptr(Q), _ptr(K), _ptr(v_rows), _rows(v_rows, "v_rows"), _ptr(O), _rows(O, "O"), _ptr(dO), _rows(dO, "dO"),
                                    _ptr(lse2), _ptr(key_bias), _ptr(rrms), _ptr(wq_lo), _ptr(wk_lo), _ptr(wq_hi), _ptr(wk_hi), split, _ptr(cos_p), _ptr(sin_p),
                                    _ptr(dqkv), _rows(dqkv, "dqkv"), B, H, S, Sp, d, scale, _ptr(ws)), "attn_bwd_rope")
@@ -1007,19 +974,13 @@ def ema_update(shadow, param, decay: float):
     _l.check(L.st355_ema_update(_stream(), _ptr(shadow), _ptr(param), shadow.numel(), decay, shadow.element_size()), "ema_update")
 
 
-_gn_ws = {}
-
-
 def grad_norm(g):
     """returns fp32 [2] device tensor: (sum of squares, max |g|).  The per-block partials live in a scratch of this (device, stream): norms on different streams
     (a side-stream EMA / ControlNet norm, a hipGraph capture next to eager calls) never share one"""
     L = _l.load()
     out = torch.empty(2, dtype=F32, device=g.device)
     st = _stream()
-    key = (g.device.index, int(st) if st is not None else 0)
-    ws = _gn_ws.get(key)
-    if ws is None:
-        ws = _gn_ws[key] = torch.empty(2 * 1024, dtype=F32, device=g.device)
+    ws = _scratch("grad_norm", g.device, 2 * 1024 * 4, key=(st,))          # 2 x 1024 fp32 partials
     _l.check(L.st355_grad_norm_ws(st, _ptr(g), g.numel(), g.element_size(), _ptr(out), _ptr(ws)), "grad_norm")
     return out
 
@@ -1290,9 +1251,6 @@ def grid_rows(B: int, H: int, W: int) -> int:
     return int(_l.load().st355_conv_grid_rows(B, H, W))
 
 
-_grid_pool = {}
-
-
 def grid_zeros(B: int, H: int, W: int, C_: int, device, pool: bool = False):
     """a zero-filled grid buffer [grid_rows, C] (border + 64 tail rows stay zero: kernels never write them non-zero)"""
     return torch.zeros(grid_rows(B, H, W), C_, dtype=BF16, device=device)
@@ -1360,7 +1318,7 @@ def conv_wgrad(x, dy, dw, B: int, H: int, W: int, taps: int = 9, accumulate: boo
         raise _l.St355Error(f"conv_wgrad: dw must be a contiguous [{Cout}, {taps * Cin}] tensor")
     ws = _gemm_workspace(x.device)
     _l.check(L.st355_conv_wgrad_bf16(_stream(), _ptr(x), _ptr(dy), _ptr(dw), B, H, W, Cin, Cout, taps, 1 if accumulate else 0, _ptr(ws),
-                                     ws.numel() * 4), "conv_wgrad_bf16")
+                                     ws.numel()), "conv_wgrad_bf16")
     return dw
 
 
@@ -1377,7 +1335,7 @@ def conv_wgrad_plan(B: int, H: int, W: int, Cin: int, Cout: int, taps: int = 9, 
     """st355_conv_plan, weight gradient: what conv_wgrad() would launch.  workspace_bytes: -1 = the workspace conv_wgrad() passes on the current device.
     {"taps": 9 | 1, "tiles", "ks": K-slices (1 = direct store), "Mc": rounded contraction rows, "store": "SPLITK" | "NONE" | "ADD"}"""
     if workspace_bytes < 0:
-        workspace_bytes = _gemm_workspace(torch.device("cuda", torch.cuda.current_device())).numel() * 4
+        workspace_bytes = _gemm_workspace(torch.device("cuda", torch.cuda.current_device())).numel()
     d = (C.c_int64 * 8)(B, H, W, Cin, Cout, taps, 1 if accumulate else 0, workspace_bytes)
     out = (C.c_int32 * 8)()
     _l.check(_l.load().st355_conv_plan(2, d, out), "conv_plan")
@@ -1438,121 +1396,81 @@ def _fill(st, **kw):
     return st
 
 
+def _block_call(name: str, a):
+    """st355_<name>(stream, &a), checked and counted in BLOCK_CALLS[name]"""
+    _l.check(getattr(_l.load(), "st355_" + name)(_stream(), C.byref(a)), name)
+    BLOCK_CALLS[name] = BLOCK_CALLS.get(name, 0) + 1
+
+
 def block_flux_single_fwd(**kw):
     """st355_block_flux_single_fwd: one FluxSingleTransformerBlock forward as ONE C call (field names of st355_flux_single_fwd_args)"""
-    L = _l.load()
     ws = _gemm_workspace(kw["x"].device)
-    a = _fill(_l.FluxSingleFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, **kw)
-    _l.check(L.st355_block_flux_single_fwd(_stream(), C.byref(a)), "block_flux_single_fwd")
-    BLOCK_CALLS["block_flux_single_fwd"] = BLOCK_CALLS.get("block_flux_single_fwd", 0) + 1
+    _block_call("block_flux_single_fwd", _fill(_l.FluxSingleFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), **kw))
 
 
 def block_flux_double_fwd(**kw):
     """st355_block_flux_double_fwd: one FluxTransformerBlock forward as ONE C call (field names of st355_flux_double_fwd_args)"""
-    L = _l.load()
     ws = _gemm_workspace(kw["img"].device)
-    a = _fill(_l.FluxDoubleFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, **kw)
-    _l.check(L.st355_block_flux_double_fwd(_stream(), C.byref(a)), "block_flux_double_fwd")
-    BLOCK_CALLS["block_flux_double_fwd"] = BLOCK_CALLS.get("block_flux_double_fwd", 0) + 1
+    _block_call("block_flux_double_fwd", _fill(_l.FluxDoubleFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), **kw))
 
 
 def block_flux_double_bwd(grads, **kw):
     """st355_block_flux_double_bwd (field names of st355_flux_double_bwd_args); grads: {"gA_qkv": [...], "gB_qkv": [...], "gA_out": [...], "gB_out": [...]}"""
-    L = _l.load()
     dev = kw["img"].device
     B, S, H, D = kw["B"], kw["Si"] + kw["St"], kw["H"], kw["D"]
     ws = _gemm_workspace(dev)
-    need = L.st355_attn_bwd_workspace(B, H, S, S, 128)
-    aws = _attn_ws.get((dev.index,))
-    if aws is None or aws.numel() < need:
-        aws = _attn_ws[(dev.index,)] = torch.empty(need, dtype=torch.uint8, device=dev)
-    sws = None
-    if kw.get("K2_qkv") or kw.get("K2_out"):
-        need = L.st355_skinny_tn_workspace(B * kw["Si"], D, 128)
-        sws = _skinny_ws.get((dev.index,))
-        if sws is None or sws.numel() * 4 < need:
-            sws = _skinny_ws[(dev.index,)] = torch.empty((need + 3) // 4, dtype=F32, device=dev)
-    a = _fill(_l.FluxDoubleBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, attn_ws=aws, skinny_ws=sws, **kw)
+    aws = _attn_bwd_scratch(dev, B, H, S, S, 128)
+    sws = _skinny_scratch(dev, B * kw["Si"], D, 128) if kw.get("K2_qkv") or kw.get("K2_out") else None
+    a = _fill(_l.FluxDoubleBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), attn_ws=aws, skinny_ws=sws, **kw)
     for name, ts in (grads or {}).items():
         arr = getattr(a, name)
         for i, t in enumerate(ts or []):
             _chk(t, F32, name); arr[i] = t.data_ptr()
-    _l.check(L.st355_block_flux_double_bwd(_stream(), C.byref(a)), "block_flux_double_bwd")
-    BLOCK_CALLS["block_flux_double_bwd"] = BLOCK_CALLS.get("block_flux_double_bwd", 0) + 1
+    _block_call("block_flux_double_bwd", a)
 
 
 def block_flux_single_bwd(gA, gB, **kw):
     """st355_block_flux_single_bwd (field names of st355_flux_single_bwd_args); gA / gB: lists of the adapters' fp32 gradient views"""
-    L = _l.load()
     dev = kw["x"].device
     B, S, H, D = kw["B"], kw["S"], kw["H"], kw["D"]
     ws = _gemm_workspace(dev)
-    need = L.st355_attn_bwd_workspace(B, H, S, S, 128)
-    aws = _attn_ws.get((dev.index,))
-    if aws is None or aws.numel() < need:
-        aws = _attn_ws[(dev.index,)] = torch.empty(need, dtype=torch.uint8, device=dev)
-    sws = None
-    if kw.get("K2"):
-        need = L.st355_skinny_tn_workspace(B * S, D, 128)
-        sws = _skinny_ws.get((dev.index,))
-        if sws is None or sws.numel() * 4 < need:
-            sws = _skinny_ws[(dev.index,)] = torch.empty((need + 3) // 4, dtype=F32, device=dev)
-    a = _fill(_l.FluxSingleBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, attn_ws=aws, skinny_ws=sws, **kw)
+    aws = _attn_bwd_scratch(dev, B, H, S, S, 128)
+    sws = _skinny_scratch(dev, B * S, D, 128) if kw.get("K2") else None
+    a = _fill(_l.FluxSingleBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), attn_ws=aws, skinny_ws=sws, **kw)
     for i, t in enumerate(gA or []):
         _chk(t, F32, "gA"); a.gA[i] = t.data_ptr()
     for i, t in enumerate(gB or []):
         _chk(t, F32, "gB"); a.gB[i] = t.data_ptr()
-    _l.check(L.st355_block_flux_single_bwd(_stream(), C.byref(a)), "block_flux_single_bwd")
-    BLOCK_CALLS["block_flux_single_bwd"] = BLOCK_CALLS.get("block_flux_single_bwd", 0) + 1
+    _block_call("block_flux_single_bwd", a)
 
 
 def block_pixart_fwd(**kw):
     """st355_block_pixart_fwd: one PixArt BasicTransformerBlock(ada_norm_single) forward as ONE C call (field names of st355_pixart_block_fwd_args)"""
-    L = _l.load()
-    a = _fill(_l.PixartBlockFwdArgs(), **kw)
-    _l.check(L.st355_block_pixart_fwd(_stream(), C.byref(a)), "block_pixart_fwd")
-    BLOCK_CALLS["block_pixart_fwd"] = BLOCK_CALLS.get("block_pixart_fwd", 0) + 1
+    _block_call("block_pixart_fwd", _fill(_l.PixartBlockFwdArgs(), **kw))
 
 
 def block_pixart_bwd(**kw):
     """st355_block_pixart_bwd: the data path of that block's backward as ONE C call (field names of st355_pixart_block_bwd_args)"""
-    L = _l.load()
-    dev = kw["h"].device
-    Sp = (kw["S"] + 63) // 64 * 64
-    need = L.st355_attn_bwd_workspace(kw["B"], kw["H"], kw["S"], Sp, kw["d_pad"])
-    aws = _attn_ws.get((dev.index,))
-    if aws is None or aws.numel() < need:
-        aws = _attn_ws[(dev.index,)] = torch.empty(need, dtype=torch.uint8, device=dev)
-    a = _fill(_l.PixartBlockBwdArgs(), attn_ws=aws, **kw)
-    _l.check(L.st355_block_pixart_bwd(_stream(), C.byref(a)), "block_pixart_bwd")
-    BLOCK_CALLS["block_pixart_bwd"] = BLOCK_CALLS.get("block_pixart_bwd", 0) + 1
+    aws = _attn_bwd_scratch(kw["h"].device, kw["B"], kw["H"], kw["S"], (kw["S"] + 63) // 64 * 64, kw["d_pad"])
+    _block_call("block_pixart_bwd", _fill(_l.PixartBlockBwdArgs(), attn_ws=aws, **kw))
 
 
 def block_sd3_joint_fwd(**kw):
     """st355_block_sd3_joint_fwd: one SD3 JointTransformerBlock forward as ONE C call (field names of st355_sd3_joint_fwd_args)"""
-    L = _l.load()
     ws = _gemm_workspace(kw["img"].device)
-    a = _fill(_l.Sd3JointFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, **kw)
-    _l.check(L.st355_block_sd3_joint_fwd(_stream(), C.byref(a)), "block_sd3_joint_fwd")
-    BLOCK_CALLS["block_sd3_joint_fwd"] = BLOCK_CALLS.get("block_sd3_joint_fwd", 0) + 1
+    _block_call("block_sd3_joint_fwd", _fill(_l.Sd3JointFwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), **kw))
 
 
 def block_sd3_joint_bwd(**kw):
     """st355_block_sd3_joint_bwd: the data path of that block's backward as ONE C call (field names of st355_sd3_joint_bwd_args)"""
-    L = _l.load()
     dev = kw["img"].device
     S = kw["Si"] + kw["St"]
-    need = L.st355_attn_bwd_workspace(kw["B"], kw["H"], S, (S + 63) // 64 * 64, kw["hd"])
-    aws = _attn_ws.get((dev.index,))
-    if aws is None or aws.numel() < need:
-        aws = _attn_ws[(dev.index,)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    aws = _attn_bwd_scratch(dev, kw["B"], kw["H"], S, (S + 63) // 64 * 64, kw["hd"])
     ws = _gemm_workspace(dev)
     if kw.get("dmod_img") is not None:          # the fused-statistics form (full fine-tune): fp32 partial rows of its column sums
         rmax = max(kw["Si"], kw["St"])
-        kw["stats_ws"] = _stats_workspace(dev, L.st355_stats_workspace(kw["B"] * rmax, 4 * kw["D"], rmax, 1))
-    a = _fill(_l.Sd3JointBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel() * 4, attn_ws=aws, **kw)
-    _l.check(L.st355_block_sd3_joint_bwd(_stream(), C.byref(a)), "block_sd3_joint_bwd")
-    BLOCK_CALLS["block_sd3_joint_bwd"] = BLOCK_CALLS.get("block_sd3_joint_bwd", 0) + 1
+        kw["stats_ws"] = _scratch("stats", dev, _l.load().st355_stats_workspace(kw["B"] * rmax, 4 * kw["D"], rmax, 1))
+    _block_call("block_sd3_joint_bwd", _fill(_l.Sd3JointBwdArgs(), gemm_ws=ws, gemm_ws_bytes=ws.numel(), attn_ws=aws, **kw))
 
 
 class VaeEncoderTable:
@@ -1574,9 +1492,6 @@ class VaeEncoderTable:
         self.struct = st
 
 
-_vae_ws = {}
-
-
 def vae_encode(table: VaeEncoderTable, x):
     """AutoencoderKL.encode as one C call: pixels [B, C, H, W] bf16 -> moments [B, 2L, H/2^(n-1), W/2^(n-1)] bf16"""
     L = _l.load()
@@ -1588,9 +1503,7 @@ def vae_encode(table: VaeEncoderTable, x):
     need = L.st355_vae_encode_workspace(C.byref(st), B, H, W)
     if need == 0:
         raise _l.St355Error("vae_encode: " + L.st355_last_error().decode("utf-8", "replace"))
-    ws = _vae_ws.get(x.device.index)
-    if ws is None or ws.numel() < need:
-        ws = _vae_ws[x.device.index] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = _scratch("vae_encode", x.device, need)
     out = torch.empty(B, 2 * st.latent_channels, H // f, W // f, dtype=BF16, device=x.device)
     _l.check(L.st355_vae_encode(_stream(), C.byref(st), _ptr(x), _ptr(out), B, H, W, _ptr(ws), ws.numel()), "vae_encode")
     return out
@@ -1612,15 +1525,8 @@ def grid_to_tokens(g, B: int, H: int, W: int):
     return t
 
 
-_gn_ws = {}
-
-
 def _gn_workspace(B, H, W, Cn, device):
-    need = _l.load().st355_groupnorm_workspace(B, H, W, Cn)
-    ws = _gn_ws.get(device.index)
-    if ws is None or ws.numel() < need:
-        ws = _gn_ws[device.index] = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
+    return _scratch("groupnorm", device, _l.load().st355_groupnorm_workspace(B, H, W, Cn))
 
 
 def gn_set_apply(form: int) -> int:
@@ -1688,17 +1594,11 @@ def layernorm_bwd(dy, x, weight, dres=None, eps: float = 1e-5):
     return dx
 
 
-_lnp_ws = {}
-
-
 def layernorm_param_grads(dy, x, dweight, dbias, eps: float = 1e-5, accumulate: bool = False):
     L = _l.load()
     _chk(dy, BF16, "dy"); _chk(x, BF16, "x"); _chk(dweight, F32, "dweight"); _chk(dbias, F32, "dbias")
     rows, D = x.shape
-    need = L.st355_layernorm_param_grads_workspace(D)
-    ws = _lnp_ws.get(x.device.index)
-    if ws is None or ws.numel() < need:
-        ws = _lnp_ws[x.device.index] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = _scratch("layernorm_param_grads", x.device, L.st355_layernorm_param_grads_workspace(D))
     _l.check(L.st355_layernorm_param_grads(_stream(), _ptr(dy), _rows(dy, "dy"), _ptr(x), _rows(x, "x"), rows, D, eps, _ptr(dweight), _ptr(dbias),
                                            1 if accumulate else 0, _ptr(ws)), "layernorm_param_grads")
 
@@ -1757,12 +1657,7 @@ def attn_cross_fwd(Q, K, Vt, O, lse2, B, H, Sq, Sk, Skp, d, scale: float, key_bi
 
 def attn_cross_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, Sq, Sqp, Sk, Skp, d, scale: float, key_bias=None, O_res=None):
     L = _l.load()
-    need = L.st355_attn_bwd_workspace(B, H, Sq, Sqp, d)
-    key = (Q.device.index,)
-    ws = _attn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=Q.device)
-        _attn_ws[key] = ws
+    ws = _attn_bwd_scratch(Q.device, B, H, Sq, Sqp, d)
     if O_res is not None:
         _res_ok(O, O_res)
         _l.check(L.st355_attn_bwd_res(_stream(), _ptr(Q), _ptr(K), _ptr(Qt), _ptr(Kt), _ptr(v_rows), _rows(v_rows, "v_rows"),

@@ -241,7 +241,7 @@ def _wgrad(ops, name, B, H, W, Cin, Cout, taps, accumulate, store, ks, data="uni
     x_img = _randn(g, B, H, W, Cin, data=data)
     dy_img = _randn(g, B, H, W, Cout, data="unit" if data == "offset" else data)
     old = _randn(g, Cout, taps * Cin, scale=math.sqrt(B * H * W)) if accumulate else None
-    ws_bytes = workspace_bytes if workspace_bytes is not None else ops._gemm_workspace(dev()).numel() * 4
+    ws_bytes = workspace_bytes if workspace_bytes is not None else ops._gemm_workspace(dev()).numel()
     plan = ops.conv_wgrad_plan(B, H, W, Cin, Cout, taps, accumulate=accumulate, workspace_bytes=ws_bytes)
     assert (plan["taps"], plan["store"], plan["ks"]) == (taps, store, ks), f"{name}: planned {plan}"
     assert plan["Mc"] == (CB.grid_positions(B, H, W) - 2 * (W + 3) + 63) // 64 * 64

@@ -359,6 +359,52 @@ def test_skinny_tn_multi_equals_separate_products(ops):
     assert all(torch.equal(a, 2 * o) for a, o in zip(acc, outs))
 
 
+def test_captured_skinny_tn_survives_growth_of_its_scratch(ops, monkeypatch):
+    """a hipGraph bakes in the scratch address it was captured with: when a later, larger shape outgrows that scratch, the old buffer must stay allocated
+    (ops._scratch retires it), so that replaying the graph neither writes into memory the allocator has handed to someone else nor computes anything else"""
+    from simpletuner_amd import lib
+
+    monkeypatch.setattr(ops, "_scratch_bufs", {})           # a table of this test's own: what ran before in this process must not have grown the scratch already
+    monkeypatch.setattr(ops, "_scratch_retired", [])
+    L = lib.load()
+    P, Rn, r, M_small, M_large = 64, 32, 32, 256, 4096
+    need_small, need_large = L.st355_skinny_tn_workspace(M_small, P, Rn), L.st355_skinny_tn_workspace(M_large, P, Rn)
+    assert 0 < need_small < need_large
+    torch.manual_seed(17)
+    Ls, Rs = torch.randn(M_small, P, device=dev()).to(BF16), torch.randn(M_small, Rn, device=dev()).to(BF16)
+    Ll, Rl = torch.randn(M_large, P, device=dev()).to(BF16), torch.randn(M_large, Rn, device=dev()).to(BF16)
+    out_g, out_l, out_e = (torch.zeros(P, r, device=dev()) for _ in range(3))
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            ops.skinny_tn(Ls, Rs, out_g, r, 1, r)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        ops.skinny_tn(Ls, Rs, out_g, r, 1, r)
+    torch.cuda.current_stream().wait_stream(side)
+    captured = ops._scratch("skinny", dev(), need_small)
+    captured_ptr, captured_bytes = captured.data_ptr(), captured.numel()
+    assert captured_bytes < need_large
+    del captured
+
+    ops.skinny_tn(Ll, Rl, out_l, r, 1, r)                 # outgrows the scratch
+    assert ops._scratch("skinny", dev(), need_small).data_ptr() != captured_ptr
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    squatters = [torch.full((captured_bytes,), 0xFF, dtype=torch.uint8, device=dev()) for _ in range(4)]
+    out_g.fill_(float("nan"))
+    g.replay()
+    torch.cuda.synchronize()
+
+    assert [t.data_ptr() for t in ops._scratch_retired] == [captured_ptr]
+    assert all(t.data_ptr() != captured_ptr and bool((t == 0xFF).all()) for t in squatters)
+    ops.skinny_tn(Ls, Rs, out_e, r, 1, r)
+    assert torch.equal(out_g, out_e)
+    assert report("skinny_tn replayed", out_g, Ls.float().t() @ Rs.float())[0] < 1e-5 * math.sqrt(M_small) + 1e-6
+
+
 @pytest.mark.parametrize("B,rows,lo,S,N,K", [(3, 256, 256, 768, 512, 256), (8, 512, 0, 4608, 256, 192), (2, 4096, 512, 4608, 768, 256)])
 def test_gemm_segmented_rows_bit_equal_to_per_sample_problems(ops, B, rows, lo, S, N, K):
     """st355_gemm_args.seg_rows: the per-sample row blocks [lo, lo + rows) of joint [B, S, *] buffers as ONE problem (3-D strided views), on the A side, the
