@@ -502,6 +502,25 @@ int st355_layersync_fwd(void* stream, const void* student, const void* teacher, 
                         int64_t s_bstride, int64_t t_bstride, void* ws);
 int st355_layersync_inject(void* stream, void* dx, const void* G, const float* scale_dev, int B, int rows, int D, int64_t ld, int64_t bstride);
 
+/* ---- Internal Guidance (helpers/training/internal_guidance.py): the auxiliary head LayerNorm(D, eps 1e-6) -> Linear(D -> N = 64) on one block's image-token output ----
+ * fp32 arithmetic, bf16 only in memory, no atomics, fixed-order reductions (two calls give the same bits).  D % 8 == 0, D <= 4096, N == 64, 16-byte aligned operands.
+ * params_bf16: gamma, beta [D], W [N, D], b [N] (and the four gradients of st355_ig_wgrad) are bf16 (the full fine-tune's arenas) instead of fp32 (adapter arena).
+ * st355_ig_fold: Wf [N, D] = bf16(gamma * W), WfT [D, N] its transpose, c [N] = bf16(W beta + b): with xhat = LN(h) without affine the head is y = xhat Wf^T + c,
+ * one thin st355_gemm_bf16 on xhat.  Run once per forward (the parameters move with every optimizer step).
+ * st355_ig_head_fwd: h = [B, rows, D] bf16 view (row stride ld, batch stride bstride, elements) read once, a row per wave kept in registers; xhat [B * rows, D]
+ * compact bf16 = (h - mean) * rstd with the CENTRED biased variance, rstd [B * rows] fp32 = 1 / sqrt(var + 1e-6).
+ * st355_ig_head_bwd: dy [B * rows, N] bf16 compact.  dx (a view like h) += rstd * (g - mean_D(g) - xhat * mean_D(g * xhat)) with g = dy Wf formed per 16-row tile on
+ * the MFMA and never stored; fp32 sum with the value already there, ONE bf16 rounding.  Rows outside the view are not touched.
+ * st355_ig_wgrad: P [N, D] fp32 = dy^T xhat (st355_skinny_tn_seg), db [N] fp32 = sum_m dy (st355_colsum_prod) -> g_W = P * gamma + db beta^T, g_b = db,
+ * g_gamma[d] = sum_n W[n, d] P[n, d], g_beta[d] = sum_n W[n, d] db[n] (= the column sums of dn * xhat and dn, dn = dy W: the contraction with the unfolded W, no
+ * division by gamma).  accumulate != 0 adds to what the gradient tensors hold (gradient accumulation). */
+int st355_ig_fold(void* stream, const void* gamma, const void* beta, const void* W, const void* b, int params_bf16, void* Wf, void* WfT, void* c, int N, int D);
+int st355_ig_head_fwd(void* stream, const void* h, void* xhat, float* rstd, int B, int rows, int D, int64_t ld, int64_t bstride);
+int st355_ig_head_bwd(void* stream, const void* xhat, const float* rstd, const void* dy, const void* WfT, void* dx, int B, int rows, int D, int N, int64_t ld,
+                      int64_t bstride);
+int st355_ig_wgrad(void* stream, const float* P, const float* db, const void* gamma, const void* beta, const void* W, int params_bf16, void* g_gamma, void* g_beta,
+                   void* g_W, void* g_b, int N, int D, int accumulate);
+
 /* LoRA operand packing (K12): from fp32 A[r,K], B[N,r] write the bf16 GEMM operands of ONE adapter into the (zero-initialised)
  * block-structured operands of a fused projection group with K2 padded low-rank columns and N_total outputs:
  *   A_cat   [K2,K]       rows  k2_off..k2_off+r-1      = A

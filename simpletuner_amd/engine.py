@@ -3,6 +3,7 @@
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
+  * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
   * `pad64` / `pad64_empty`: operands of the TN weight-gradient GEMM (contraction granule: 64 rows);
   * `ArenaModule`: every base parameter a view of ONE bf16 arena (two-pass construction), checkpoint load / save over the parameter names;
   * `FullGrads`: the per-backward helper of full-rank training — weight / bias gradients into the gradient arena, the modulation rows' reductions, the fused
@@ -170,6 +171,98 @@ class LayerSyncTap:
 
 
 # ------------------------------------------------------------------------------------------------
+# Internal Guidance (helpers/training/internal_guidance.py): an auxiliary head LayerNorm(D, eps 1e-6) -> Linear(D -> 64) on one block's image-token output
+# ------------------------------------------------------------------------------------------------
+IG_NAMES = ("norm.weight", "norm.bias", "proj.weight", "proj.bias")          # under `internal_guidance_head.`: the reference module's parameter names
+
+
+def internal_guidance_index(block_index, n_blocks: int) -> int:
+    """validated 0-based block index (internal_guidance.py:194-197: used as it is, no LayerSync-style idx - 1 rule)"""
+    i = int(block_index)
+    if not 0 <= i < n_blocks:
+        raise ValueError(f"internal_guidance_block_index must be within [0, {n_blocks - 1}], got {i}.")
+    return i
+
+
+def internal_guidance_shapes(D: int):
+    return ((D,), (D,), (ops.IG_N, D), (ops.IG_N,))
+
+
+class InternalGuidanceHead:
+    """The head's four trainable tensors as views of the arena that trains (fp32 at the tail of the adapter arena, or bf16 inside the base parameter arena), their
+    gradient views, the [lo, hi) element range of the gradient arena they span, and the folded bf16 operands the kernels read (ops.ig_fold, once per forward)."""
+
+    def __init__(self, block: int, D: int, params, grads, flat_lo: int, flat_hi: int, device):
+        self.block, self.D = block, D
+        self.gamma, self.beta, self.W, self.b = params
+        self.g_gamma, self.g_beta, self.g_W, self.g_b = grads          # re-pointed by the owner when it switches gradient arenas
+        self.flat_lo, self.flat_hi = flat_lo, flat_hi
+        self.Wf = torch.empty(ops.IG_N, D, dtype=BF16, device=device)
+        self.WfT = torch.empty(D, ops.IG_N, dtype=BF16, device=device)
+        self.c = torch.empty(ops.IG_N, dtype=BF16, device=device)
+
+    @property
+    def grads(self):
+        return (self.g_gamma, self.g_beta, self.g_W, self.g_b)
+
+    @torch.no_grad()
+    def init_reference(self):
+        """internal_guidance.py:93-97: LayerNorm affine (1, 0), zero projection"""
+        self.gamma.fill_(1.0); self.beta.zero_(); self.W.zero_(); self.b.zero_()
+
+    def fold(self):
+        ops.ig_fold(self.gamma, self.beta, self.W, self.b, self.Wf, self.WfT, self.c)
+
+
+class InternalGuidanceTap:
+    """One per forward that wants the head's prediction (kept in the training forward's ctx).  `tap(g, view)` after block g of the saving forward — never in the
+    recompute pass of a checkpointed segment — folds the current parameters and runs the head on the block's image-token rows [B, rows, D] (read as the view they
+    are): xhat / rstd stay for the backward, y holds the tokens.  `prediction(H, W)`: the [B, 16, H, W] bf16 latent-shaped prediction.  `backward(d_pred, dx_view)`
+    right before block g's own backward fills the head's four gradient views and adds d loss / d h into the gradient with respect to that block's output
+    (dx_view None: the block lies below the first one that trains, only the head's gradients are wanted), then hands the head's range to `sync`."""
+
+    def __init__(self, head: InternalGuidanceHead, channels: int = 16):
+        self.head, self.block, self.channels = head, head.block, channels
+        self.xhat = self.rstd = self.y = None
+        self.B = self.rows = 0
+
+    def tap(self, g: int, view):
+        if g != self.block:
+            return
+        B, rows, D = view.shape
+        dev = view.device
+        self.B, self.rows = B, rows
+        self.xhat = torch.empty(B * rows, D, dtype=BF16, device=dev)
+        self.rstd = torch.empty(B * rows, dtype=F32, device=dev)
+        self.y = torch.empty(B * rows, ops.IG_N, dtype=BF16, device=dev)
+        self.head.fold()
+        ops.ig_head_fwd(view, self.head.Wf, self.head.c, self.xhat, self.rstd, self.y)
+
+    def prediction(self, H: int, W: int):
+        if self.y is None:
+            raise RuntimeError(f"Internal Guidance: block {self.block} was never reached by the forward")
+        if (H // 2) * (W // 2) != self.rows:
+            raise ValueError("Internal Guidance hidden-state token count does not match the diffusion target: "
+                             f"tokens={self.rows}, patch_volume=4, spatial_shape=({H}, {W}).")
+        return ops.unpatchify(self.y.view(self.B, self.rows, ops.IG_N), self.channels, H, W, order=1)
+
+    def backward(self, d_pred, dx_view, accumulate: bool = False, sync=None):
+        h = self.head
+        if d_pred is None:                       # the prediction took no part in the loss
+            if not accumulate:
+                for g in h.grads:
+                    g.zero_()
+        else:
+            dy = ops.patchify(d_pred.to(BF16).contiguous(), order=1).view(self.B * self.rows, ops.IG_N)
+            ops.ig_wgrad(self.xhat, dy, h.gamma, h.beta, h.W, *h.grads, accumulate=accumulate)
+            if dx_view is not None:
+                ops.ig_head_bwd(self.xhat, self.rstd, dy, h.WfT, dx_view)
+        if sync is not None:
+            sync.ready(h.flat_lo, h.flat_hi)
+        self.xhat = self.rstd = None
+
+
+# ------------------------------------------------------------------------------------------------
 # operands of the TN weight-gradient GEMM (contraction granule: 64 rows)
 # ------------------------------------------------------------------------------------------------
 def pad64_empty(rows: int, cols: int, dev):
@@ -257,7 +350,8 @@ class ArenaModule(nn.Module):
     def load_flat_state(self, state: Dict[str, torch.Tensor]):
         """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
         own = dict(self.named_parameters())
-        missing = [k for k in own if k not in state and ".lora_" not in k]
+        # (an Internal Guidance head is optional in a file: without one it keeps the reference's initial values)
+        missing = [k for k in own if k not in state and ".lora_" not in k and not k.startswith("internal_guidance_head.")]
         if missing:
             raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
         own.update(self._extra_state())

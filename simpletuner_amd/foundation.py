@@ -436,7 +436,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         full fine-tune exposes exactly its arena views; the VAE / ControlNet trunk never carry gradients"""
         if "lora" in str(getattr(self.config, "model_type", "lora")) and self.model is not None:
             for n, p_ in self.unwrap_model(self.model).named_parameters():
-                if ".lora_" not in n:
+                if ".lora_" not in n and not (n.startswith("internal_guidance_head.") and p_.dtype == torch.float32):      # (the head's fp32 masters train with the adapters)
                     p_.requires_grad_(False)
         elif str(getattr(self.config, "model_type", "lora")) == "full" and self.model is not None:
             # the reference leaves a full-rank model as diffusers loaded it — every parameter trainable — and `Trainer._get_trainable_parameters` collects
@@ -459,13 +459,47 @@ class ModelFoundation(ExplorativeModelingMixin):
         NextLat, CREPA / U-REPA: hooks into a diffusers module's blocks).  LayerSync is built for the components that expose `set_layersync` (Flux, SD3: it needs
         nothing outside the model); asking for any other is refused — defined here so that a reference flow calling it never reaches the reference's regulariser
         initialisers through the MRO."""
-        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled", "internal_guidance_enabled", "nextlat_enabled"):
+        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled", "nextlat_enabled"):
             if getattr(self.config, flag, False):
                 raise NotImplementedError(f"{flag}: representation-alignment regularisers hook diffusers modules and are not built on the st355 path")
         self.layersync = None
         if getattr(self.config, "layersync_enabled", False):
             self._layersync_init()
+        self.internal_guidance = None
+        if getattr(self.config, "internal_guidance_enabled", False):
+            self._internal_guidance_init()
         return None
+
+    def internal_guidance_block_index(self, n_blocks: int) -> int:
+        """internal_guidance.py:194-197: `internal_guidance_block_index` as it is (0-based), default max(0, n_blocks // 4)"""
+        from .engine import internal_guidance_index
+        configured = getattr(self.config, "internal_guidance_block_index", None)
+        return internal_guidance_index(configured if configured is not None else max(0, n_blocks // 4), n_blocks)          # (the range check and its text live there)
+
+    def _internal_guidance_init(self):
+        """common.py:5166-5195 `_init_internal_guidance_regularizer` + internal_guidance.py:186-199: the configuration checks in the reference's order and with its
+        texts, then the trained component is told which block output feeds the head (the head itself was laid out with the component's arenas)"""
+        cfg = self.config
+        if self.MODEL_TYPE is not ModelTypes.TRANSFORMER:
+            raise ValueError("Internal Guidance is only supported for diffusion transformer models.")
+        if getattr(self.PREDICTION_TYPE, "value", None) == "autoregressive_next_token":          # (no st355 family has it; a registered reference family may)
+            raise ValueError("Internal Guidance is not defined for autoregressive next-token models.")
+        if str(getattr(cfg, "lora_type", "standard") or "standard").lower() == "lycoris":
+            raise ValueError("Internal Guidance requires standard PEFT LoRA or full-model training so its auxiliary head is optimized and saved.")
+        comp = self.unwrap_model(self.get_trained_component()) if self.get_trained_component() is not None else None
+        if comp is None or not hasattr(comp, "set_internal_guidance"):
+            raise NotImplementedError(f"internal_guidance_enabled: Internal Guidance is not built for {self.NAME} on the st355 path (built: SD3)")
+        weight = float(getattr(cfg, "internal_guidance_loss_weight", 0.5) or 0.0)
+        if weight <= 0:
+            raise ValueError("internal_guidance_loss_weight must be greater than zero.")
+        tc = getattr(cfg, "tread_config", None)
+        if tc and tc.get("routes", None):
+            raise NotImplementedError("internal_guidance_enabled with TREAD routing (the routed block's token count no longer matches the diffusion target) is not built on the st355 path")
+        if getattr(getattr(self, "xm_config", None), "enabled", False):
+            raise NotImplementedError("internal_guidance_enabled with XM noise candidates is not built on the st355 path")
+        idx = self.internal_guidance_block_index(int(comp.config.num_layers))
+        comp.set_internal_guidance(idx)
+        self.internal_guidance = SimpleNamespace(weight=weight, block_index=idx)
 
     @staticmethod
     def _layersync_resolve(idx, role: str, n_blocks: int) -> int:
@@ -609,7 +643,23 @@ class ModelFoundation(ExplorativeModelingMixin):
         comp = component if component is not None else self.get_trained_component()
         src = comp.lora_state_dict().items() if hasattr(comp, "lora_state_dict") else ((n, p.detach()) for n, p in comp.named_parameters() if ".lora_" in n)
         # (a component whose working layout pads the adapter factors — PixArt's 72 -> 96 head lanes — hands out the true peft shapes itself)
-        return {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in src}
+        sd = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in src}
+        sd.update(self._internal_guidance_head_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
+        return sd
+
+    IG_PREFIX = "internal_guidance_head."          # internal_guidance.py:184 MODULE_NAME; in an adapter file under `transformer.`
+
+    @staticmethod
+    def _internal_guidance_head_state(comp, dtype) -> dict:
+        """the Internal Guidance head as the reference saves it with the adapter (its module's state dict under `internal_guidance_head.`): the four tensors in the
+        dtype the adapter tensors are saved in and `block_index` as an int64 scalar.  Empty when the component trains no head with its adapters."""
+        head = getattr(comp, "_ig", None)
+        if head is None or not getattr(comp, "lora_groups", None):
+            return {}
+        own = dict(comp.named_parameters())
+        out = {ModelFoundation.IG_PREFIX + nm: own[ModelFoundation.IG_PREFIX + nm].detach().to(dtype) for nm in ("norm.weight", "norm.bias", "proj.weight", "proj.bias")}
+        out[ModelFoundation.IG_PREFIX + "block_index"] = torch.tensor(int(head.block), dtype=torch.int64)
+        return out
 
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = None     # common.py:524; Flux / SD3 / PixArt keep their `transformer.` prefix in ComfyUI files
     AUTO_LORA_FORMAT_DETECTION = False                  # flux/model.py:56: a diffusers-configured run still recognises a ComfyUI file on load
@@ -632,7 +682,9 @@ class ModelFoundation(ExplorativeModelingMixin):
     def save_lora_weights(self, output_dir, **layers):
         """writes `pytorch_lora_weights.safetensors` with diffusers' component prefix (`transformer.` / `unet.`), as the diffusers pipelines'
         save_lora_weights the reference calls (common.py:2072-2120); `layers` = {"<subfolder>_lora_layers": state} or nothing (= the trained
-        component).  `config.lora_format == "comfyui"` converts the keys on the way out (ComfyUI / kohya names + one `.alpha` tensor per module)."""
+        component).  `config.lora_format == "comfyui"` converts the keys on the way out (ComfyUI / kohya names + one `.alpha` tensor per module); that export
+        DROPS an Internal Guidance head (`internal_guidance_head.*`: ComfyUI has no module to load it into) — keep the diffusers-format file to resume or to sample
+        with the head."""
         import os
 
         from safetensors.torch import save_file
@@ -653,6 +705,7 @@ class ModelFoundation(ExplorativeModelingMixin):
                 flat[f"{prefix}.{k}"] = v.detach().to("cpu").contiguous()
         fmt = normalize_lora_format(getattr(self.config, "lora_format", None))
         if fmt == PEFTLoRAFormat.COMFYUI and not getattr(self, "NATIVE_COMFYUI_LORA_SUPPORT", False):
+            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k}
             flat = self._convert_lora_state_dict_to_comfyui(flat, adapter_metadata=meta or self._lora_adapter_metadata(), component_adapter_metadata=comp_meta)
             flat = {k: v.contiguous() for k, v in flat.items()}
         os.makedirs(output_dir, exist_ok=True)
@@ -673,7 +726,8 @@ class ModelFoundation(ExplorativeModelingMixin):
     def load_lora_weights(self, models=None, input_dir=None):
         """common.py:1875-2047: read the file back into the adapters of the trained component (strict on the adapter keys).  ComfyUI-dialect files
         (configured, or detected when AUTO_LORA_FORMAT_DETECTION) are converted first; a per-module alpha that disagrees with the configured
-        adapter scale is an error here — the adapters' alpha/r scale is fixed at construction, loading must not silently change the model."""
+        adapter scale is an error here — the adapters' alpha/r scale is fixed at construction, loading must not silently change the model.  An Internal Guidance
+        head is read back strictly from a diffusers-format file; a ComfyUI-dialect file cannot carry one and is refused while a head is configured."""
         import os
 
         from safetensors.torch import load_file
@@ -707,6 +761,23 @@ class ModelFoundation(ExplorativeModelingMixin):
                 k0 = next(iter(bad))
                 raise ValueError(f"LoRA file alpha {bad[k0]} for {k0} differs from the configured lora_alpha {want}; set lora_alpha to match the file")
         own = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in comp.named_parameters() if ".lora_" in n}
+        # an Internal Guidance head travels with the adapter (diffusers-format files): read back strictly — every head tensor when a head is configured, and a file
+        # that carries one needs a component that has one
+        in_file = sorted(k for k in flat if self.IG_PREFIX in k)
+        head = getattr(comp, "_ig", None)
+        if in_file and (head is None or not getattr(comp, "lora_groups", None)):
+            raise ValueError(f"LoRA checkpoint carries an Internal Guidance head ({in_file[0]}, ...) but none is configured: set internal_guidance_enabled (and the "
+                             "file's internal_guidance_block_index) before loading it")
+        if head is not None and getattr(comp, "lora_groups", None) and fmt != PEFTLoRAFormat.DIFFUSERS:
+            raise ValueError("a ComfyUI-format LoRA file cannot carry the Internal Guidance head (the export drops it): load the diffusers-format file, or turn "
+                             "internal_guidance_enabled off to load the adapters alone")
+        if head is not None and getattr(comp, "lora_groups", None):
+            own.update({n: p for n, p in comp.named_parameters() if n.startswith(self.IG_PREFIX)})
+            bi = flat.get(prefix + self.IG_PREFIX + "block_index")
+            if bi is None:
+                raise KeyError(f"LoRA checkpoint is missing the Internal Guidance head's block index ({prefix}{self.IG_PREFIX}block_index)")
+            if int(bi.item()) != int(head.block):
+                raise ValueError(f"LoRA checkpoint's Internal Guidance head was trained on block {int(bi.item())}, the configured internal_guidance_block_index is {int(head.block)}")
         missing = [k for k in own if prefix + k not in flat]
         if missing:
             raise KeyError(f"LoRA checkpoint is missing {len(missing)} adapter tensors, e.g. {missing[:3]}")
@@ -1161,14 +1232,27 @@ class ModelFoundation(ExplorativeModelingMixin):
     def auxiliary_loss(self, model_output, prepared_batch: dict, loss: torch.Tensor):
         """common.py:5364-5374 `_apply_layersync_regularizer`: loss - lambda * similarity, the two logs as host floats (layersync.py:55-58).  The similarity and its
         gradient come from the engine (model_output["layersync_similarity"]); the `.item()` reads happen here, outside it."""
+        logs = {}
+        ig = getattr(self, "internal_guidance", None)
+        if ig is not None:
+            # common.py:6461-6469 / internal_guidance.py:229-254, before the LayerSync term (the reference's order): weight * the plugin's own loss() on the head's
+            # prediction (model_output["internal_guidance_prediction"], from the engine's tap), the two logs as host floats
+            pred = model_output.get("internal_guidance_prediction") if isinstance(model_output, dict) else None
+            if pred is None:
+                raise ValueError("Internal Guidance is enabled but the model did not return a hidden-state buffer.")
+            inter = self.loss(prepared_batch, {"model_prediction": pred}, apply_conditioning_mask=True)
+            weighted = inter * ig.weight
+            loss = loss + weighted
+            logs.update(internal_guidance_loss=weighted.detach().item(), internal_guidance_unweighted_loss=inter.detach().item())
         ls = getattr(self, "layersync", None)
-        if ls is None:
-            return loss, None
-        sim = model_output.get("layersync_similarity") if isinstance(model_output, dict) else None
-        if sim is None:
-            raise ValueError("LayerSync enabled but no hidden state buffer was provided.")          # layersync.py:33-34: the prediction did not come from a training forward
-        ls_loss = -sim * ls.weight
-        return loss + ls_loss, {"layersync_loss": ls_loss.detach().item(), "layersync_similarity": sim.detach().item()}
+        if ls is not None:
+            sim = model_output.get("layersync_similarity") if isinstance(model_output, dict) else None
+            if sim is None:
+                raise ValueError("LayerSync enabled but no hidden state buffer was provided.")          # layersync.py:33-34: the prediction did not come from a training forward
+            ls_loss = -sim * ls.weight
+            loss = loss + ls_loss
+            logs.update(layersync_loss=ls_loss.detach().item(), layersync_similarity=sim.detach().item())
+        return loss, (logs or None)
 
 
 class _CondLossFn(torch.autograd.Function):

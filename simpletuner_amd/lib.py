@@ -28,6 +28,7 @@ SYMBOLS = [
     "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
     "st355_soap_plan", "st355_soap_step", "st355_soap_eigh",
     "st355_layersync_fwd", "st355_layersync_inject",
+    "st355_ig_fold", "st355_ig_head_fwd", "st355_ig_head_bwd", "st355_ig_wgrad",
     "st355_lora_pack",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
@@ -352,6 +353,10 @@ def _declare(lib):
         "st355_soap_eigh": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "st355_layersync_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, vp]),
         "st355_layersync_inject": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
+        "st355_ig_fold": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32]),
+        "st355_ig_head_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
+        "st355_ig_head_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64]),
+        "st355_ig_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32]),
         "st355_lora_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),

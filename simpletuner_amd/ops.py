@@ -1179,6 +1179,89 @@ def layersync_inject(dx, G, scale):
     return dx
 
 
+IG_N = 64          # output features of the Internal Guidance head (16 latent channels x a 2 x 2 patch)
+
+
+def _ig_params(name: str, gamma, beta, W, b):
+    """the head's four parameters (or their gradients): all fp32 (adapter arena) or all bf16 (full fine-tune arena), contiguous, W [64, D].  Returns (D, bf16?)"""
+    dt = W.dtype
+    if dt not in (F32, BF16) or any(t.dtype != dt for t in (gamma, beta, b)):
+        raise _l.St355Error(f"{name}: gamma, beta, W and b must share one dtype, fp32 or bf16")
+    for t in (gamma, beta, W, b):
+        _dev(t, name)
+    if W.dim() != 2 or W.shape[0] != IG_N:
+        raise _l.St355Error(f"{name}: the head has N = {IG_N} output features, got W {tuple(W.shape)}")
+    D = W.shape[1]
+    if gamma.numel() != D or beta.numel() != D or b.numel() != IG_N or not all(t.is_contiguous() for t in (gamma, beta, W, b)):
+        raise _l.St355Error(f"{name}: expected contiguous gamma [D], beta [D], W [{IG_N}, D], b [{IG_N}]")
+    return D, int(dt == BF16)
+
+
+def ig_fold(gamma, beta, W, b, Wf, WfT, c):
+    """Internal Guidance head (st355_ig_fold): Wf [64, D] = bf16(gamma * W), WfT [D, 64] its transpose, c [64] = bf16(W beta + b) — the operands of
+    ig_head_fwd / ig_head_bwd, from the current parameters (fp32 or bf16).  Writes into the tensors given."""
+    L = _l.load()
+    D, p16 = _ig_params("ig_fold", gamma, beta, W, b)
+    _chk(Wf, BF16, "Wf"); _chk(WfT, BF16, "WfT"); _chk(c, BF16, "c")
+    if tuple(Wf.shape) != (IG_N, D) or tuple(WfT.shape) != (D, IG_N) or c.numel() != IG_N or not (Wf.is_contiguous() and WfT.is_contiguous() and c.is_contiguous()):
+        raise _l.St355Error(f"ig_fold: expected contiguous Wf [{IG_N}, {D}], WfT [{D}, {IG_N}], c [{IG_N}]")
+    _l.check(L.st355_ig_fold(_stream(), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b), p16, _ptr(Wf), _ptr(WfT), _ptr(c), IG_N, D), "ig_fold")
+    return Wf, WfT, c
+
+
+def ig_head_fwd(h, Wf, c, xhat, rstd, y):
+    """Internal Guidance head forward: h a [B, rows, D] bf16 view (read once, no compact copy) -> xhat [B * rows, D] compact bf16 = LN(h) without affine (centred
+    variance), rstd [B * rows] fp32 (st355_ig_head_fwd), then the tokens y [B * rows, 64] bf16 = xhat Wf^T + c on the thin GEMM route (D % 64 == 0).  Writes into the
+    tensors given."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(h, "h")
+    _chk(xhat, BF16, "xhat"); _chk(rstd, F32, "rstd"); _chk(y, BF16, "y"); _chk(Wf, BF16, "Wf"); _chk(c, BF16, "c")
+    M = B * rows
+    if tuple(Wf.shape) != (IG_N, D):
+        raise _l.St355Error(f"ig_head_fwd: the head has N = {IG_N} output features over D = {D}, got Wf {tuple(Wf.shape)}")
+    if D % 64:
+        raise _l.St355Error(f"ig_head_fwd: D must be a multiple of 64, the contraction granule of the projection's GEMM (got {D}; the row kernel itself takes D % 8 == 0)")
+    if tuple(xhat.shape) != (M, D) or not xhat.is_contiguous() or rstd.numel() != M or not rstd.is_contiguous() or tuple(y.shape) != (M, IG_N) or not y.is_contiguous():
+        raise _l.St355Error(f"ig_head_fwd: expected contiguous xhat [{M}, {D}], rstd [{M}], y [{M}, {IG_N}]")
+    _l.check(L.st355_ig_head_fwd(_stream(), _ptr(h), _ptr(xhat), _ptr(rstd), B, rows, D, ld, bs), "ig_head_fwd")
+    gemm(xhat, Wf, bias=c, out=y)
+    return xhat, rstd, y
+
+
+def ig_head_bwd(xhat, rstd, dy, WfT, dx):
+    """Internal Guidance head backward into the dX chain (st355_ig_head_bwd): dx, a [B, rows, D] bf16 view, += rstd * (g - mean(g) - xhat * mean(g * xhat)) with
+    g = dy Wf never stored (dy [B * rows, 64] bf16 compact, WfT [D, 64]); fp32 sum, one bf16 rounding, rows outside the view untouched."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(dx, "dx")
+    _chk(xhat, BF16, "xhat"); _chk(rstd, F32, "rstd"); _chk(dy, BF16, "dy"); _chk(WfT, BF16, "WfT")
+    M = B * rows
+    if dy.dim() != 2 or dy.shape[1] != IG_N or tuple(WfT.shape) != (D, IG_N):
+        raise _l.St355Error(f"ig_head_bwd: the head has N = {IG_N} output features over D = {D}, got dy {tuple(dy.shape)}, WfT {tuple(WfT.shape)}")
+    if tuple(xhat.shape) != (M, D) or dy.shape[0] != M or rstd.numel() != M or not (xhat.is_contiguous() and dy.is_contiguous() and rstd.is_contiguous() and WfT.is_contiguous()):
+        raise _l.St355Error(f"ig_head_bwd: expected contiguous xhat [{M}, {D}], rstd [{M}], dy [{M}, {IG_N}], WfT [{D}, {IG_N}]")
+    _l.check(L.st355_ig_head_bwd(_stream(), _ptr(xhat), _ptr(rstd), _ptr(dy), _ptr(WfT), _ptr(dx), B, rows, D, IG_N, ld, bs), "ig_head_bwd")
+    return dx
+
+
+def ig_wgrad(xhat, dy, gamma, beta, W, g_gamma, g_beta, g_W, g_b, accumulate: bool = False):
+    """the head's four parameter gradients (st355_ig_wgrad) from P = dy^T xhat (skinny_tn: fp32 [64, D]) and db = colsum(dy): g_W = P * gamma + db beta^T, g_b = db,
+    g_gamma = sum_n W * P, g_beta = sum_n W * db.  Parameters and gradients share one dtype (fp32 or bf16); accumulate adds to what the gradients hold."""
+    L = _l.load()
+    D, p16 = _ig_params("ig_wgrad", gamma, beta, W, g_b)
+    D2, g16 = _ig_params("ig_wgrad", g_gamma, g_beta, g_W, g_b)
+    _chk(xhat, BF16, "xhat"); _chk(dy, BF16, "dy")
+    if D2 != D or g16 != p16 or xhat.dim() != 2 or dy.dim() != 2 or xhat.shape[1] != D or dy.shape[1] != IG_N or dy.shape[0] != xhat.shape[0] \
+            or not (xhat.is_contiguous() and dy.is_contiguous()):
+        raise _l.St355Error(f"ig_wgrad: expected contiguous xhat [M, {D}], dy [M, {IG_N}] and gradients in the parameters' dtype and shapes")
+    ws = _scratch("ig_wgrad", xhat.device, (IG_N * D + IG_N) * 4).view(F32)
+    P, db = ws[:IG_N * D].view(IG_N, D), ws[IG_N * D:IG_N * D + IG_N].view(1, IG_N)
+    skinny_tn(xhat, dy, P, 1, D, IG_N)
+    colsum_prod(dy, db)
+    _l.check(L.st355_ig_wgrad(_stream(), _ptr(P), _ptr(db), _ptr(gamma), _ptr(beta), _ptr(W), p16, _ptr(g_gamma), _ptr(g_beta), _ptr(g_W), _ptr(g_b), IG_N, D,
+                              1 if accumulate else 0), "ig_wgrad")
+    return g_gamma, g_beta, g_W, g_b
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

@@ -264,14 +264,22 @@ def cfg_combine(pred_pair: torch.Tensor, guidance_scale: float) -> torch.Tensor:
 def sample_images(plugin, prompt_embeds: torch.Tensor, pooled: Optional[torch.Tensor], latent_height: int, latent_width: int, num_inference_steps: int = 20,
                   generator: Optional[torch.Generator] = None, scheduler=None, mu: Optional[float] = None,
                   decode: bool = True, extra_batch: Optional[dict] = None, guidance_scale: float = 1.0, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                  negative_pooled: Optional[torch.Tensor] = None, negative_extra_batch: Optional[dict] = None, latents: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  negative_pooled: Optional[torch.Tensor] = None, negative_extra_batch: Optional[dict] = None, latents: Optional[torch.Tensor] = None,
+                  internal_guidance_scale: Optional[float] = None) -> torch.Tensor:
     """The validation sampling loop end to end on the st355 kernels (training/validation.py -> <family>/pipeline.py `__call__`):
     Gaussian latents -> `num_inference_steps` steps over the plugin's OWN forward (`model_predict`, so packing / ids / guidance / timestep conventions are the
     family's) -> `vae.decode(z / scaling_factor + shift_factor)`.  The scheduler follows the family's prediction type: flow matching -> Euler
     (FlowMatchEulerDiscreteScheduler), epsilon / v-prediction -> DDIM (the reference's default, DEFAULT_NOISE_SCHEDULER).  Classifier-free guidance
     (`guidance_scale` > 1 with negative embeddings): every step runs the model ONCE on the batch [negative ; positive] and combines the halves
     (sd3/pipeline.py:1769-1785).  Returns pixels [B, 3, 8h, 8w] in [-1, 1] (bf16), or the final latents with decode=False.  IP adapters, skip-layer guidance,
-    CFG-zero* and the image post-processing of the diffusers pipelines stay outside this tier."""
+    CFG-zero* and the image post-processing of the diffusers pipelines stay outside this tier.
+    `internal_guidance_scale` (default: config.validation_internal_guidance_scale, itself 1.0; internal_guidance.py:256-264, 303-350): 1.0 never touches the head;
+    any other positive s makes every model call return inter + s * (final - inter), inter = the Internal Guidance head's prediction from its block of the SAME
+    forward — per forward, hence before the classifier-free-guidance combine."""
+    cfg_scale = getattr(plugin.config, "validation_internal_guidance_scale", None)
+    ig_scale = float(internal_guidance_scale if internal_guidance_scale is not None else (1.0 if cfg_scale is None else cfg_scale))
+    if ig_scale != 1.0 and ig_scale <= 0:
+        raise ValueError("validation_internal_guidance_scale must be greater than zero.")
     dev = plugin.accelerator.device
     B = prompt_embeds.shape[0]
     C = int(plugin.LATENT_CHANNEL_COUNT)
@@ -316,7 +324,16 @@ def sample_images(plugin, prompt_embeds: torch.Tensor, pooled: Optional[torch.Te
                     batch[k] = merged
                 else:
                     batch[k] = pair(v, neg.get(k)) if do_cfg else v
-        out = plugin.model_predict(batch)["model_prediction"].to(xt.dtype)
+        if ig_scale != 1.0:
+            batch["return_internal_guidance"] = True
+        res = plugin.model_predict(batch)
+        out = res["model_prediction"].to(xt.dtype)
+        if ig_scale != 1.0:
+            inter = res.get("internal_guidance_prediction")
+            if inter is None:
+                raise ValueError("The transformer does not have an internal_guidance_head.")          # internal_guidance.py:405
+            inter = inter.float()
+            out = (inter + ig_scale * (out.float() - inter)).to(xt.dtype)
         return cfg_combine(out, float(guidance_scale)) if do_cfg else out
 
     if flow:

@@ -29,6 +29,11 @@ class SD3(ModelFoundation):
     HUGGINGFACE_PATHS = {"medium": "stabilityai/stable-diffusion-3-medium-diffusers", "large": "stabilityai/stable-diffusion-3.5-large"}
 
     def load_model(self, state_dict=None, **arch):
+        if getattr(self.config, "internal_guidance_enabled", False) and "internal_guidance_block_index" not in arch:
+            # Internal Guidance: the head is laid out with the component's arenas (post_model_load_setup repeats the checks in the reference's order)
+            import inspect
+            n_layers = arch.get("num_layers", inspect.signature(SD3Transformer2DModel.__init__).parameters["num_layers"].default)          # (the constructor's own default)
+            arch = dict(arch, internal_guidance_block_index=self.internal_guidance_block_index(int(n_layers)))
         self.model = SD3Transformer2DModel(device=self.accelerator.device, **arch)
         if state_dict is not None:
             self.model.load_flat_state(state_dict)
@@ -59,11 +64,14 @@ class SD3(ModelFoundation):
             timestep=prepared_batch["timesteps"].to(device=dev, dtype=torch.float32),
             encoder_hidden_states=prepared_batch["encoder_hidden_states"].to(device=dev, dtype=BF16),
             pooled_projections=prepared_batch["add_text_embeds"].to(device=dev, dtype=BF16),
-            return_dict=False,
+            return_dict=True,
+            **({"return_internal_guidance": True} if prepared_batch.get("return_internal_guidance") else {}),          # sampling with validation_internal_guidance_scale != 1
         )
-        out = {"model_prediction": res[0], "crepa_hidden_states": None, "hidden_states_buffer": None}
-        if len(res) > 1:                  # LayerSync (set_layersync): the training forward's second output
-            out["layersync_similarity"] = res[1]
+        # further outputs travel by name; (a component that hands back a plain tuple has only its sample)
+        out = {"model_prediction": res[0] if isinstance(res, tuple) else res.sample, "crepa_hidden_states": None, "hidden_states_buffer": None}
+        for k in ("layersync_similarity", "internal_guidance_prediction"):          # LayerSync / Internal Guidance: the training forward's further outputs
+            if getattr(res, k, None) is not None:
+                out[k] = getattr(res, k)
         return out
 
 

@@ -24,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, pad64_empty, problems, rows_of, sincos_2d_hw
+from ..engine import (IG_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraGroup, attach, compact, frozen,
+                      internal_guidance_index, internal_guidance_shapes, layersync_indices, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -66,8 +67,11 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                  attention_head_dim: int = 64, num_attention_heads: int = 18, joint_attention_dim: int = 4096,
                  caption_projection_dim: int = 1152, pooled_projection_dim: int = 2048, out_channels: int = 16,
                  pos_embed_max_size: int = 96, dual_attention_layers: Tuple[int, ...] = (), qk_norm: Optional[str] = None,
-                 device=None, **_ignored):
+                 internal_guidance_block_index: Optional[int] = None, device=None, **_ignored):
         super().__init__()
+        # Internal Guidance (set_internal_guidance): given here, the head's four tensors get their place in the base parameter arena (what a full fine-tune trains)
+        self._ig_block = None if internal_guidance_block_index is None else internal_guidance_index(internal_guidance_block_index, num_layers)
+        self._ig_arena, self._ig = None, None
         if patch_size != 2:
             raise ValueError("patch_size must be 2 (the patchify kernels are 2x2)")
         self.dual_layers = frozenset(int(i) for i in (dual_attention_layers or ()))
@@ -191,6 +195,15 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         assert off == self.mod_total
         self._head_arena_lo = self._arena_numel
         self.l_out = lin("proj_out", 4 * out_channels, D)
+        self._head_arena_hi = self._arena_numel
+        if self._ig_block is not None:         # the Internal Guidance head, last in the arena: LayerNorm affine (1, 0), zero projection (internal_guidance.py:93-97)
+            if 4 * out_channels != ops.IG_N:
+                raise NotImplementedError(f"Internal Guidance: the head kernels are built for {ops.IG_N} output features (16 channels, 2 x 2 patch), got {4 * out_channels}")
+            self._ig_arena = tuple(e(*shp) for shp in internal_guidance_shapes(D))
+            for nm, t in zip(IG_NAMES, self._ig_arena):
+                self._reg("internal_guidance_head." + nm, frozen(t))
+            if not self._counting:
+                self._ig_arena[0].fill_(1.0)
 
 
     # ------------------------------------------------------------------------------------------------
@@ -206,6 +219,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     @torch.no_grad()
     def init_synthetic(self, seed: int = 42):
         super().init_synthetic(seed)
+        if self._ig_arena is not None:         # the head keeps the reference's initial values (registered last: the draws of every other parameter are unchanged)
+            for t, v in zip(self._ig_arena, (1.0, 0.0, 0.0, 0.0)):
+                t.fill_(v)
         c = self.config
         self.pos_embed.pos_embed.copy_(sincos_2d(self.D, c.pos_embed_max_size, c.sample_size // c.patch_size)[None].to(self.device_))
 
@@ -249,6 +265,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 if blk.to_add_out is not None:
                     group(blk.to_add_out, p, ["to_add_out"], D)
         total = sum(rank * K + N * rank for (_, _, N, K) in plan)
+        ig_lo = total                             # Internal Guidance: the head's fp32 masters follow the adapters in the same arena (one run for the optimizer)
+        if self._ig_block is not None:
+            total += sum(math.prod(shp) for shp in internal_guidance_shapes(D))
         total = (total + 7) // 8 * 8
         self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
         self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
@@ -271,6 +290,21 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             g.flat_hi = off
             self._lora_params += [pa, pb]
+        if self._ig_block is not None:
+            assert off == ig_lo
+            ps, gs = [], []
+            for nm, shp in zip(IG_NAMES, internal_guidance_shapes(D)):
+                n = math.prod(shp)
+                pr = nn.Parameter(self.lora_flat[off:off + n].view(shp))
+                attach(self, "internal_guidance_head." + nm, pr)          # (replaces the frozen arena view of the same name, when there is one)
+                ps.append(pr.data); gs.append(self.lora_grad_flat[off:off + n].view(shp))
+                self._lora_params.append(pr)
+                off += n
+            self._ig = InternalGuidanceHead(self._ig_block, D, ps, gs, ig_lo, off, dev)
+            self._ig.init_reference()
+            if self._ig_arena is not None:
+                for dst, src in zip(ps, self._ig_arena):
+                    dst.copy_(src)                   # a head that came with the loaded weights
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
@@ -527,7 +561,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         G.dq_t = G.c_txt if G.c_txt is not None else compact(rows_of(G.dqkv, Si, St, B, S), B, St)
         return d_img_out, d_txt_out, G
 
-    def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False):
+    def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False, want_ig: bool = False):
         D, H, hd = self.D, self.H, self.hd
         B, C, Hh, Ww = latents.shape
         h, w = Hh // 2, Ww // 2
@@ -603,6 +637,13 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if tokenwise:
                 raise NotImplementedError("LayerSync with tokenwise timesteps is not built on the st355 path")
             ls = ctx.ls = LayerSyncTap(*self._layersync)
+        ig = None
+        if self._ig_block is not None and (save or want_ig):
+            if save and self._tread_router is not None:
+                raise NotImplementedError("Internal Guidance under TREAD routing (the routed block's token count no longer matches the diffusion target) is not built on the st355 path")
+            ig = ctx.ig = InternalGuidanceTap(self._ig_head(), self.out_channels)
+        elif want_ig:
+            raise ValueError("The transformer does not have an internal_guidance_head.")          # internal_guidance.py:405
         rp, info, saved, env_cur = 0, None, None, env
         for (s0, n, ck) in ctx.segs:
             for bi in range(s0, s0 + n):
@@ -619,6 +660,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, env_cur, save and not ck)
                 if ls is not None:                            # LayerSync: the block's image-stream output (the recompute pass, _recompute_segment, never taps)
                     ls.tap(bi, img.view(B, Si, D))
+                if ig is not None:                            # Internal Guidance: the head on this block's image-stream output (the recompute pass never taps)
+                    ig.tap(bi, img.view(B, Si, D))
                 if info is not None and bi == routes[rp]["end_layer_idx"]:
                     full_seq = saved.clone()                                                        # TREADRouter.end_route(original_x=saved)
                     ops.scatter_rows(img.view(B, env_cur.Si, D), info.keep_i32(), full_seq.view(B, Si, D))
@@ -634,7 +677,32 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ctx.x_img_final = img
             if full:
                 ctx.n_out = n_out
+        if ig is not None:
+            ctx.ig_pred = ig.prediction(Hh, Ww)
         return ops.unpatchify(out.view(B, Si, -1), self.out_channels, Hh, Ww, order=1), ctx
+
+    def set_internal_guidance(self, block_index):
+        """Internal Guidance (helpers/training/internal_guidance.py; the reference captures `layer_{i}` at sd3/transformer.py:872): the 0-based joint block whose
+        image-stream output feeds the auxiliary head LayerNorm -> Linear(D -> 64).  Call it before `add_lora_adapter` (the head's fp32 masters go to the tail of the
+        adapter arena); a full fine-tune needs the constructor's `internal_guidance_block_index` (the head lives inside the base parameter arena, laid out once).
+        A training forward then also returns the head's [B, 16, H, W] prediction and the backward takes its gradient at that block."""
+        i = internal_guidance_index(block_index, len(self.blocks))
+        if self._ig is not None or self._ig_arena is not None:
+            self._ig_block = i                        # the head exists: only the tap moves
+            if self._ig is not None:
+                self._ig.block = i
+            return
+        if self.lora_groups or self.full:
+            raise RuntimeError("set_internal_guidance: the trainable arena is already laid out without the head — call it before add_lora_adapter(), or construct the "
+                               "model with internal_guidance_block_index")
+        self._ig_block = i
+
+    def _ig_head(self) -> InternalGuidanceHead:
+        if self._ig is None:
+            if self._ig_arena is None:
+                raise RuntimeError("Internal Guidance: no head is laid out (add_lora_adapter() after set_internal_guidance(), or the constructor's internal_guidance_block_index)")
+            self._ig = InternalGuidanceHead(self._ig_block, self.D, self._ig_arena, (None,) * 4, 0, 0, self.device_)          # inference: the arena's bf16 head, no gradients
+        return self._ig
 
     def set_layersync(self, student_idx, teacher_idx=None):
         """LayerSync (helpers/training/layersync.py; the reference captures at sd3/transformer.py:872): 0-based joint-block indices.  A training forward then also
@@ -653,8 +721,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for bi in range(s0, s0 + n):
             img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, ctx.envs[bi], True)
 
-    def _engine_backward(self, ctx, dout, dsim=None):
-        """dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the dX chain at the student block's output"""
+    def _engine_backward(self, ctx, dout, dsim=None, d_ig=None):
+        """dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the dX chain at the student block's output; d_ig: upstream gradient of the
+        Internal Guidance prediction (set_internal_guidance), taken by the head's backward right before its block's own"""
         if not self._prepared:
             raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
         D, H, hd = self.D, self.H, self.hd
@@ -668,12 +737,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], rpb)
         d_txt = None
         del dn, dpk
-        ls = getattr(ctx, "ls", None)
+        ls, ig = getattr(ctx, "ls", None), getattr(ctx, "ig", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
             if ls is not None and li == ls.student:
                 ls.inject(d_img.view(B, ctx.Si, D), dsim)
+            if ig is not None and li == ig.block:
+                ig.backward(d_ig, d_img.view(B, ctx.Si, D), self.accumulate_lora_grads, self.grad_sync)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -836,6 +907,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 else:
                     setattr(blk, "g_" + nm, None)
         gview(self, "g_mod_w", self.mod_w); gview(self, "g_mod_b", self.mod_b)
+        if self._ig_block is not None:                # Internal Guidance: the head trains inside the base arena like every other parameter
+            if self._ig_arena is None:
+                raise RuntimeError("Internal Guidance under a full fine-tune: construct the model with internal_guidance_block_index (the head lives inside the base "
+                                   "parameter arena, which is laid out once)")
+            lo = (self._ig_arena[0].data_ptr() - base) // 2
+            self._ig = InternalGuidanceHead(self._ig_block, self.D, self._ig_arena, (None,) * 4, lo, self.arena.numel(), self.device_)
+            for attr, t in zip(("g_gamma", "g_beta", "g_W", "g_b"), self._ig_arena):
+                gview(self._ig, attr, t)
         ps = sorted([p for n, p in self.named_parameters() if ".lora_" not in n], key=lambda p: p.data_ptr())
         for p in ps:
             p.requires_grad_(True)
@@ -869,7 +948,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """training.grad_sync.hand_over_gradients: the arena just filled now belongs to autograd; the next backward takes the other one"""
         self._select_grad_arena(1 - self._grad_sel)
 
-    def _engine_backward_full(self, ctx, dout, dsim=None):
+    def _engine_backward_full(self, ctx, dout, dsim=None, d_ig=None):
         D, H, hd = self.D, self.H, self.hd
         B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
         dev = self.device_
@@ -910,15 +989,17 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_txt = None
         del dn, dpk
         if sync is not None:
-            sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
+            sync.ready(self._head_arena_lo, self._head_arena_hi)             # proj_out gradients are final (an Internal Guidance head behind it: at its block)
         # the fused modulation matrix (a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
-        ls = getattr(ctx, "ls", None)
+        ls, ig = getattr(ctx, "ls", None), getattr(ctx, "ig", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
             if ls is not None and li == ls.student:
                 ls.inject(d_img.view(B, ctx.Si, D), dsim)
+            if ig is not None and li == ig.block:
+                ig.backward(d_ig, d_img.view(B, ctx.Si, D), False, sync)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -1052,7 +1133,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     # public forward (reference signature: sd3/transformer.py:560-575)
     # ------------------------------------------------------------------------------------------------
     def forward(self, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None, block_controlnet_hidden_states=None,
-                joint_attention_kwargs=None, return_dict: bool = True, force_keep_mask=None, **unsupported):
+                joint_attention_kwargs=None, return_dict: bool = True, force_keep_mask=None, return_internal_guidance: bool = False, **unsupported):
         self._force_keep_mask = force_keep_mask            # TREAD: tokens that may never be routed away (sd3/transformer.py:571, 699-703)
         if block_controlnet_hidden_states is not None:
             raise NotImplementedError("SD3 ControlNet residuals are not wired to the st355 path yet")
@@ -1062,23 +1143,47 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if timestep.ndim not in (1, 2):
             raise ValueError(f"timestep: expected [B] or tokenwise [B, S_img], got {tuple(timestep.shape)}")
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or getattr(self, "full", False))
-        sim = None                                         # LayerSync (set_layersync): the training nodes return the similarity as a second output
+        sim = igp = None                                   # LayerSync / Internal Guidance: the training nodes return the similarity / the head's prediction as further outputs
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
         if need_grad and getattr(self, "full", False):
             out = _SD3FullFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._full_params)
-            if self._layersync is not None:
-                out, sim = out
+            out, sim, igp = _split_outputs(self, out)
         elif need_grad:
             out = _SD3Fn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._lora_params)
-            if self._layersync is not None:
-                out, sim = out
+            out, sim, igp = _split_outputs(self, out)
         else:
             with torch.no_grad():
-                out, _ = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False)
+                out, ectx = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False,
+                                                 want_ig=bool(return_internal_guidance))
+                igp = getattr(ectx, "ig_pred", None)            # sampling: the intermediate prediction next to the final one
+        extra = {k: v for k, v in (("layersync_similarity", sim), ("internal_guidance_prediction", igp)) if v is not None}
         if not return_dict:
-            return (out,) if sim is None else (out, sim)
-        return SimpleNamespace(sample=out) if sim is None else SimpleNamespace(sample=out, layersync_similarity=sim)
+            return (out,) + tuple(extra.values())               # order: (out, sim, ig_pred)
+        return SimpleNamespace(sample=out, **extra)
+
+
+def _split_outputs(model, out):
+    """the training nodes' outputs: out, then the LayerSync similarity, then the Internal Guidance prediction, each only when its feature is on"""
+    if not isinstance(out, tuple):
+        return out, None, None
+    rest = list(out[1:])
+    sim = rest.pop(0) if model._layersync is not None else None
+    igp = rest.pop(0) if model._ig_block is not None else None
+    return out[0], sim, igp
+
+
+def _node_outputs(out, ctx):
+    extra = ([ctx.ls.sim] if getattr(ctx, "ls", None) is not None else []) + ([ctx.ig_pred] if getattr(ctx, "ig", None) is not None else [])
+    return out if not extra else (out, *extra)
+
+
+def _node_grads(ctx, rest):
+    """(dsim, d_ig) from the gradients of the nodes' further outputs, in _node_outputs' order"""
+    rest = list(rest)
+    dsim = rest.pop(0) if getattr(ctx, "ls", None) is not None else None
+    d_ig = rest.pop(0) if getattr(ctx, "ig", None) is not None else None
+    return dsim, d_ig
 
 
 class _SD3Fn(torch.autograd.Function):
@@ -1088,14 +1193,14 @@ class _SD3Fn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *lora_params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True)
         fctx.model, fctx.ectx = model, ctx
-        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
+        return _node_outputs(out, ctx)
 
     @staticmethod
-    def backward(fctx, dout, dsim=None):
+    def backward(fctx, dout, *rest):
         model = fctx.model
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout, dsim)
+        model._engine_backward(fctx.ectx, dout, *_node_grads(fctx.ectx, rest))
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()
@@ -1117,15 +1222,15 @@ class _SD3FullFn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True, full=True)
         fctx.model, fctx.ectx = model, ctx
-        return out if getattr(ctx, "ls", None) is None else (out, ctx.ls.sim)
+        return _node_outputs(out, ctx)
 
     @staticmethod
-    def backward(fctx, dout, dsim=None):
+    def backward(fctx, dout, *rest):
         model = fctx.model
         model._pick_grad_arena()
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout, dsim)
+        model._engine_backward_full(fctx.ectx, dout, *_node_grads(fctx.ectx, rest))
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world

@@ -58,7 +58,8 @@ def default_config(**over) -> SimpleNamespace:
                flux_lora_target="default", snr_gamma=None, loss_type="l2", max_grad_norm=0.0, grad_clip_method="norm",
                gradient_accumulation_steps=1, train_batch_size=1, gradient_checkpointing=False, input_perturbation=0,
                offset_noise=False, seed=42, lora_init_b_std=0.0, layersync_enabled=False, layersync_student_block=None, layersync_teacher_block=None,
-               layersync_lambda=None)
+               layersync_lambda=None, internal_guidance_enabled=False, internal_guidance_loss_weight=0.5, internal_guidance_block_index=None,
+               validation_internal_guidance_scale=1.0)
     cfg.update(over)
     return SimpleNamespace(**cfg)
 
@@ -108,6 +109,9 @@ class Trainer:
         opt_name = getattr(config, "optimizer", "st355-adamw")
         if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap"):   # never a silently different optimizer
             raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, st355-adamw = torch-adamw semantics)")
+        if opt_name in ("muon", "soap") and getattr(config, "internal_guidance_enabled", False):
+            raise NotImplementedError(f"optimizer '{opt_name}' with internal_guidance_enabled: the trainable arena then holds the head's 1-D tensors, which the "
+                                      "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
         self._bf16_shadow = None
         if opt_name == "muon":
             if not getattr(self.model, "SUPPORTS_MUON_CLIP", False):                   # trainer.py:332-339
@@ -183,6 +187,11 @@ class Trainer:
             raise NotImplementedError("hip_graph: XM noise candidates read their logs on the host every step and cannot be captured")
         if self._use_graph and getattr(config, "layersync_enabled", False):
             raise NotImplementedError("hip_graph: LayerSync (layersync_enabled) reads its logs on the host every step and cannot be captured")
+        if getattr(config, "internal_guidance_enabled", False):
+            if self._use_graph:
+                raise NotImplementedError("hip_graph: Internal Guidance (internal_guidance_enabled) reads its logs on the host every step and cannot be captured")
+            if getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
+                raise NotImplementedError("internal_guidance_enabled with XM noise candidates is not built on the st355 path")
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
