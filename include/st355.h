@@ -384,12 +384,32 @@ int st355_attn_bwd(void* stream, const void* Q, const void* K, const void* Qt, c
                    const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o, const void* dO, int64_t ld_do,
                    const float* lse2, const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv,
                    int B, int H, int S, int Sp, int d, float scale, void* workspace);
+/* ---- the dS-spill backward (head_dim 128, no key bias, Sq % 256 == 0 and Sk % 256 == 0) ----------------------------------------------------------------
+ * k_attn_bwd_dkv4 and k_attn_bwd_dq64 both recompute S = Q K^T and dP = dO V^T: seven S x S x d contractions run where five are needed.  On this route dkv4 writes
+ * the packed dS it holds in registers once (bf16, unscaled, B H Sk Sqp elements in the kernels' own fragment order), and dQ = scale dS K becomes one memory-bound pass
+ * (k_attn_bwd_dq_ds).  dK / dV are bit-identical to the dkv4 route; dQ differs from dq64's by bf16-rounded dS in another summation order.  No atomics, deterministic.
+ * The buffer is the CALLER's opt-in: `ds` with `ds_bytes` >= st355_attn_bwd_ds_bytes(...) (256-byte aligned); NULL or too small silently runs the routes above.
+ * With a buffer the route is taken when B * H * (Sk / 256) >= 3 * (compute units), i.e. the dK / dV grid runs at least three full rounds (measured down to Flux
+ * batch 2, 3.4 rounds; nothing smaller has been measured), unless st355_attn_set_ds says otherwise: 0 = never (exactly the routes above: the A/B switch), 1 = wherever the kernels are built, whatever the size
+ * (tests), -1 = the size gate (default; environment ST355_ATTN_DS=0|1 presets it).  Returns the previous mode. */
+size_t st355_attn_bwd_ds_bytes(int B, int H, int Sq, int Sqp, int Sk, int d);
+int st355_attn_set_ds(int mode);
+int st355_attn_bwd_ds(void* stream, const void* Q, const void* K, const void* Qt, const void* Kt,
+                      const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o, const void* dO, int64_t ld_do,
+                      const float* lse2, const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv,
+                      int B, int H, int S, int Sp, int d, float scale, void* workspace, void* ds, size_t ds_bytes);
+int st355_attn_bwd_rope_ds(void* stream, const void* Q, const void* K, const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o,
+                           const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, const float* rrms,
+                           const void* wq_lo, const void* wk_lo, const void* wq_hi, const void* wk_hi, int split,
+                           const float* cos_p, const float* sin_p, void* dqkv, int64_t ld_dqkv, int B, int H, int S, int Sp, int d, float scale,
+                           void* workspace, void* ds, size_t ds_bytes);
 /* The kernels an attention forward + backward of this shape would run on now, without launching anything (the launchers take the same decisions).
  * Sq / Sk: query / key lengths (self-attention: Sq = Sk); flags: ST355_ATTN_PLAN_* for what the call is given (key bias, row-major V in the forward, O_res,
- * the Qt / Kt copies in the backward, the fused RoPE backward of st355_attn_bwd_rope).  Honours st355_attn_set_impl and ST355_ATTN_DQ_SHORT.
+ * the Qt / Kt copies in the backward, the fused RoPE backward of st355_attn_bwd_rope, a dS^T spill buffer).  Honours st355_attn_set_impl, st355_attn_set_ds and ST355_ATTN_DQ_SHORT.
  * routes[0] forward, [1] backward prep, [2] dK / dV, [3] dQ: ST355_ATTN_ROUTE_<kernel> + (0 / 1 / 2 for head_dim 64 / 96 / 128); routes[4] = 1 when a dQ tail
  * launch (k_attn_bwd_dq over the last, ragged key tile) follows the 64-row dQ kernel, else 0.  Validates d and the flag combination as the launch would. */
-enum { ST355_ATTN_PLAN_BIAS = 1, ST355_ATTN_PLAN_VROWS = 2, ST355_ATTN_PLAN_RES = 4, ST355_ATTN_PLAN_QT = 8, ST355_ATTN_PLAN_KT = 16, ST355_ATTN_PLAN_ROPE = 32 };
+enum { ST355_ATTN_PLAN_BIAS = 1, ST355_ATTN_PLAN_VROWS = 2, ST355_ATTN_PLAN_RES = 4, ST355_ATTN_PLAN_QT = 8, ST355_ATTN_PLAN_KT = 16, ST355_ATTN_PLAN_ROPE = 32,
+       ST355_ATTN_PLAN_DS = 64 /* a large-enough dS^T spill buffer is given (st355_attn_bwd_ds / st355_attn_bwd_rope_ds) */ };
 enum { ST355_ATTN_ROUTE_FWD64 = 10 /* k_attn_fwd64 (96, 128) */, ST355_ATTN_ROUTE_FWD4 = 20, ST355_ATTN_ROUTE_FWD4_BIAS = 30,
        ST355_ATTN_ROUTE_FWD4_RES = 40 /* k_attn_fwd4 writing O_res */, ST355_ATTN_ROUTE_FWD4_RES_BIAS = 50,
        ST355_ATTN_ROUTE_FWD4_VROWS = 60 /* k_attn_fwd4<128, *, true> (128) */, ST355_ATTN_ROUTE_FWD4_VROWS_BIAS = 70,
@@ -399,7 +419,9 @@ enum { ST355_ATTN_ROUTE_FWD64 = 10 /* k_attn_fwd64 (96, 128) */, ST355_ATTN_ROUT
        ST355_ATTN_ROUTE_DKV2 = 240,
        ST355_ATTN_ROUTE_DQ64 = 300, ST355_ATTN_ROUTE_DQ64_ROPE = 310 /* (128) */, ST355_ATTN_ROUTE_DQ_TR = 320 /* k_attn_bwd_dq<d, true, false> */,
        ST355_ATTN_ROUTE_DQ_TR_BIAS = 330, ST355_ATTN_ROUTE_DQ = 340 /* k_attn_bwd_dq<d, false, false>: K^T copy given */, ST355_ATTN_ROUTE_DQ_BIAS = 350,
-       ST355_ATTN_ROUTE_DQ_TR_ROPE = 360 /* (128) */, ST355_ATTN_ROUTE_DQ_TR_BIAS_ROPE = 370 /* (128) */ };
+       ST355_ATTN_ROUTE_DQ_TR_ROPE = 360 /* (128) */, ST355_ATTN_ROUTE_DQ_TR_BIAS_ROPE = 370 /* (128) */,
+       ST355_ATTN_ROUTE_DKV4_DS = 250 /* k_attn_bwd_dkv4<128, true>: dkv4 + the dS^T spill (128) */, ST355_ATTN_ROUTE_DKV4_ROPE_DS = 260 /* (128) */,
+       ST355_ATTN_ROUTE_DQ_DS = 380 /* k_attn_bwd_dq_ds<128>: dQ = scale dS K from the spill (128) */, ST355_ATTN_ROUTE_DQ_DS_ROPE = 390 /* (128) */ };
 int st355_attn_plan(int B, int H, int Sq, int Sk, int d, int flags, int32_t* routes);
 
 /* ---- K16/K17: fused AdamW (+EMA) over a flat parameter arena (optimizer_param.py:87-96, ema.py:393-433) */
@@ -606,6 +628,7 @@ typedef struct st355_flux_single_bwd_args {
   void* g; void* dO; void* dhpre; void* dn_mlp; void* dqkv; void* U; void* dn;   /* scratch: [B*S,D], [B*S,D], [B*S,4D], [B*S,D], [B*S,3D], [B*S,K2], [B*S,D] */
   void* gemm_ws; int64_t gemm_ws_bytes; void* attn_ws; void* skinny_ws;   /* st355_attn_bwd_workspace(B,H,S,S,128), st355_skinny_tn_workspace(B*S, D, 128) bytes */
   void* dx_out; void* dxg_out;                              /* d loss / d x [B*S, D]; gate_prev * that, or NULL */
+  void* attn_ds; int64_t attn_ds_bytes;                     /* optional dS^T spill buffer of st355_attn_bwd_rope_ds (st355_attn_bwd_ds_bytes(B,H,S,S,S,128) bytes) or NULL / 0: no spill route */
 } st355_flux_single_bwd_args;
 int st355_block_flux_single_bwd(void* stream, const st355_flux_single_bwd_args* args);
 
@@ -636,7 +659,8 @@ int st355_block_flux_double_fwd(void* stream, const st355_flux_double_fwd_args* 
  * Kept activations as written by the forward; wT_*: K-major weight copies ([in, out]); At_* / Bbt_*: the adapters' transposed packed operands; gA_* / gB_*:
  * fp32 adapter gradients ([rank, D] / [D, rank] per target: to_q, to_k, to_v; to_out.0); d_img / d_txt: gradients of the block outputs; every other pointer
  * is scratch of the stated logical shape ([rows, D] unless the name says otherwise: dh_* [rows, 4D], dqkv [B*S, 3D], dO [B*S, D], U_* [B*Si, K2]);
- * attn_ws: st355_attn_bwd_workspace(B, H, S, S, 128) bytes, skinny_ws: st355_skinny_tn_workspace(B*Si, D, 128) bytes. */
+ * attn_ws: st355_attn_bwd_workspace(B, H, S, S, 128) bytes, skinny_ws: st355_skinny_tn_workspace(B*Si, D, 128) bytes.  attn_ds / attn_ds_bytes (both blocks'
+ * backward structs): the caller's opt-in to the dS-spill attention backward — never carved out of attn_ws, never inferred from the shape. */
 typedef struct st355_flux_double_bwd_args {
   int32_t B; int32_t Si; int32_t St; int32_t H; int32_t D; int32_t K2_qkv; int32_t k2r_qkv; int32_t K2_out;
   int32_t k2r_out; int32_t rank_qkv; int32_t rpad_qkv; int32_t rank_out; int32_t rpad_out; int32_t accumulate;
@@ -654,6 +678,7 @@ typedef struct st355_flux_double_bwd_args {
   void* gemm_ws;
   int64_t gemm_ws_bytes;
   void* attn_ws; void* skinny_ws; void* d_img_out; void* d_txt_out;
+  void* attn_ds; int64_t attn_ds_bytes;                     /* optional dS^T spill buffer of st355_attn_bwd_rope_ds over the joint sequence (NULL / 0: no spill route) */
 } st355_flux_double_bwd_args;
 int st355_block_flux_double_bwd(void* stream, const st355_flux_double_bwd_args* args);
 

@@ -149,8 +149,8 @@ __device__ __forceinline__ void rope_bwd_finish(const RopeBwd& rp, const bf16* z
     if (tok0 + t < ntok) *(bf16x8*)(rp.out + ((int64_t)b * rp.S + tok) * rp.ldo + (int64_t)head * 128 + c * 8) = o;
   }
 }
-__device__ __forceinline__ void rope_bwd_store(const RopeBwd& rp, const f32x16 (&acc)[4], float scale, const bf16* zhead, int b, int head, int tok0, int ntok,
-                                               int lane, char* stage) {   // zhead: roped head-major activations of (b, head); tok0: the wave's first token
+// first half: park the wave's 32 tokens x 128 channels (accumulators * scale, rounded to bf16) in `stage` in the layout rope_bwd_finish reads
+__device__ __forceinline__ void park_rows(const f32x16 (&acc)[4], float scale, int lane, char* stage) {
   const int h = lane >> 5, l31 = lane & 31;
 #pragma unroll
   for (int dt = 0; dt < 4; dt++)
@@ -162,6 +162,10 @@ __device__ __forceinline__ void rope_bwd_store(const RopeBwd& rp, const f32x16 (
       const int ch16 = 4 * dt + a;                                        // 16-byte chunk of the token row; h picks its 8-byte half
       *(bf16x4*)(stage + l31 * 256 + ((ch16 ^ (l31 & 15)) << 4) + 8 * h) = o;
     }
+}
+__device__ __forceinline__ void rope_bwd_store(const RopeBwd& rp, const f32x16 (&acc)[4], float scale, const bf16* zhead, int b, int head, int tok0, int ntok,
+                                               int lane, char* stage) {   // zhead: roped head-major activations of (b, head); tok0: the wave's first token
+  park_rows(acc, scale, lane, stage);
   rope_bwd_finish(rp, zhead, b, head, tok0, ntok, lane, stage);
 }
 
@@ -788,20 +792,27 @@ __global__ void __launch_bounds__(512, 2) k_attn_bwd_dkv3(const bf16* __restrict
 // same fp32 sums as dkv3's (K and V only change sign); dK / dV differ from dkv3 by fp32 summation order only (bf16-rounding agreement, not bit for bit).  HIP code computes the lane
 // addresses in front of the statement and finishes behind it (dK through the fused RoPE + RMSNorm backward or as head-major rows, dV as token rows).
 // ------------------------------------------------------------------------------------------------
-#define ST355_DKV4_OPERANDS                                                                                                                            \
-        :                                                                                                                                          \
-        : [koffs] "v"(koffs), [voffs] "v"(voffs), [rowb] "v"(rowb), [trb] "v"(trb), [statb] "v"(statb), [drow] "v"(drow), [dcol] "v"(dcol),          \
+#define ST355_DKV4_INPUTS                                                                                                                              \
+          [koffs] "v"(koffs), [voffs] "v"(voffs), [rowb] "v"(rowb), [trb] "v"(trb), [statb] "v"(statb), [drow] "v"(drow), [dcol] "v"(dcol),          \
           [kbase] "s"(kbase), [vbase] "s"(vbase), [qbase] "s"(qbase), [gbase] "s"(gbase), [lbase] "s"(lbase), [dbase] "s"(dbase), [lds] "s"(lds), [wv] "s"(wvu), \
-          [nqt] "s"(nqt), [sq] "s"(sq), [stmax] "s"(stmax), [ldo2] "s"(ldo2), [q2] "s"(q2), [scale] "s"(scale), [nscale2] "s"(nscale2)                \
-        : "memory", "vcc", "scc",
+          [nqt] "s"(nqt), [sq] "s"(sq), [stmax] "s"(stmax), [ldo2] "s"(ldo2), [q2] "s"(q2), [scale] "s"(scale), [nscale2] "s"(nscale2)
+#define ST355_DKV4_OPERANDS : : ST355_DKV4_INPUTS : "memory", "vcc", "scc",
+// the spill body (DKV_DS=1) also takes the lane's byte offset into the dS^T rows of its (b, h) and their base
+#define ST355_DKV4_DS_OPERANDS : : ST355_DKV4_INPUTS, [dsoff] "v"(dsoff), [dsbase] "s"(dsbase) : "memory", "vcc", "scc",
 
 // HD = 128 (Flux) or 96 (PixArt-Sigma's head_dim 72, zero padded); the fused RoPE epilogue is head_dim 128 only
-template <int HD>
+// DS (head_dim 128, Sq % 64 == 0, Sk % 256 == 0): the spill body — the same instruction stream plus two 16-byte stores per 32-query block that write the packed dS
+// registers (bf16, unscaled) to dsT for k_attn_bwd_dq_ds; dK / dV are bit-identical to the default body's.  dsT is FRAGMENT-major:
+//   dsT[b h][kb = key / 32][qt = query / 64][j = (query % 64) / 16][h = (query % 16) / 8][key % 32][query % 8]      (Sqp / 64 query tiles per key block)
+// i.e. per (wave, query tile) one 4-KiB block of four 1-KiB pieces, piece j = 2 qb + m holding the wave's registers lane-linearly: each store instruction writes
+// whole cache lines (key-major rows, 32 rows x 32 bytes per instruction, cost the dK / dV kernel 0.77 ms of 3.38 at the Flux shape)
+template <int HD, bool DS = false>
 __global__ void __launch_bounds__(512, 2) k_attn_bwd_dkv4(const bf16* __restrict__ Q, const bf16* __restrict__ K, const bf16* __restrict__ Vrows, int64_t ld_v,
                                                           const bf16* __restrict__ dO, int64_t ld_do, const float* __restrict__ lsep,
                                                           const float* __restrict__ delta, bf16* __restrict__ dK, bf16* __restrict__ dVrows, int64_t ld_dv,
-                                                          int H, int Sq, int Sqp, int Sk, float scale, float scale2, RopeBwd rp) {
+                                                          int H, int Sq, int Sqp, int Sk, float scale, float scale2, RopeBwd rp, bf16* __restrict__ dsT = nullptr) {
   static_assert(HD == 128 || HD == 96 || HD == 64, "k_attn_bwd_dkv4: head_dim 128, 96 or 64");
+  static_assert(!DS || HD == 128, "k_attn_bwd_dkv4: the dS spill is built for head_dim 128");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -834,7 +845,20 @@ __global__ void __launch_bounds__(512, 2) k_attn_bwd_dkv4(const bf16* __restrict
     const uint32_t nqt = (uint32_t)((Sq + 63) / 64), sq = (uint32_t)Sq, stmax = (uint32_t)(Sqp - 64), ldo2 = (uint32_t)(ld_do * 2), q2 = (uint32_t)(HD * 2);
     const uint32_t wvu = (uint32_t)wv;
     const float nscale2 = -scale2;
-    if constexpr (HD == 128) {
+    if constexpr (DS) {
+      // the wave's key block (no clamp: Sk % 256 == 0), the lane's 16 bytes inside a piece; piece j and the query tile: immediates and the scalar base; Sk * Sqp * 2 < 2^32 (launcher)
+      const uint32_t dsoff = (uint32_t)(wg.tile * 8 + wv) * (uint32_t)(Sqp / 64) * 4096u + 16u * lane;
+      bf16* dsbase = dsT + bh * (int64_t)Sk * Sqp;
+      asm volatile(
+#ifdef ST355_DKV4_DS_BODY_INC     // tools/attn_lab builds: a generator variant under test
+#include ST355_DKV4_DS_BODY_INC
+#else
+#include "gen/attn_dkv4_ds_body.inc"
+#endif
+          ST355_DKV4_DS_OPERANDS
+#include "gen/attn_dkv4_clobbers.inc"
+      );
+    } else if constexpr (HD == 128) {
       asm volatile(
 #ifdef ST355_DKV4_BODY_INC        // tools/attn_lab builds: a generator variant under test
 #include ST355_DKV4_BODY_INC
@@ -1002,6 +1026,141 @@ __global__ void __launch_bounds__(256, 1) k_attn_bwd_dq64(const bf16* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// dQ from the SPILLED dS (head_dim 128, r7): dQ = scale * dS K, one memory-bound batched product over dsT (fragment-major, see k_attn_bwd_dkv4) as k_attn_bwd_dkv4<128, true>
+// wrote it — no S = Q K^T, no dP = dO V^T, no exponentials: one S x S x d contraction where k_attn_bwd_dq64 runs three.  Plain HIP: the kernel streams 2 bytes per
+// (query, key) and does 256 FLOP on them, ~1/5 of what the matrix pipe could take.
+//   workgroup = 128 queries of one (b, h) (4 waves x 32 queries; 48 KiB of LDS: three workgroups per CU), walking the keys in 32-key tiles
+//   tile = [dS image: the 8 KiB of (key block, two query tiles), contiguous in dsT | K image: 32 keys x 128 channels, 256-byte rows, swz_q chunk swizzle on the DMA source];
+//   the dS image keeps dsT's order (piece = 4 (query tile) + j, 16-byte slot 32 h + key inside it); slot c holds source slot c ^ ((2 (j & 1) + (c >> 5)) << 2) so that the
+//   sixteen lanes of a transposing read (four keys x {j & 1, h} x two halves) fall on distinct banks
+//   LDS-DMA into a ring of three 16-KiB slots, TWO tiles in flight per workgroup (counted vmcnt, raw barrier, one barrier per tile): ~96 KiB outstanding per CU
+//   dQ^T[d][q] += K^T[d][key] dS^T[key][q]: BOTH operands contract over the tile's rows, so both are gathered by transposing reads with the lane base of
+//   dq<TR> / dkv3 for the K^T fragment of d tile dt, and for the dS^T fragment of the wave's own 32 queries with the same lane roles on the fragment-major image (a
+//   lane's 8-byte piece = 4 consecutive queries of one key, wherever it lies)
+//   epilogue as dq64: * scale, bf16, parked as token rows in the idle ring, rope_bwd_finish (or whole 256-byte head-major rows)
+// Fixed summation order, no atomics.  AUX: cache policy of the dS DMA loads (tools/attn_lab: 2 = non-temporal).
+// ------------------------------------------------------------------------------------------------
+template <int AUX>
+__device__ __forceinline__ void a_glds16x(const void* g, char* l) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, AUX);
+}
+// A k-fragment by two transposing reads issued from an asm statement, NOT waited for.  hipcc orders every LDS read it can see behind all LDS-DMA in flight (a
+// vmcnt(0) in front of the tile's first ds_read: the ring would never hold more than the tile being read); reads inside asm are ordered by the kernel's own counted
+// waits.  The consumer names the fragments in tr_wait (lgkmcnt(0)) before it uses them.
+__device__ __forceinline__ bf16x8 lds_tr16x2_nowait(uint32_t a0, uint32_t a1) {
+  u32x2 lo, hi;
+  asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3" : "=&v"(lo), "=&v"(hi) : "v"(a0), "v"(a1) : "memory");
+  u32x4 w;
+  w[0] = lo[0]; w[1] = lo[1]; w[2] = hi[0]; w[3] = hi[1];
+  return *(bf16x8*)&w;
+}
+__device__ __forceinline__ void tr_wait(bf16x8& a, bf16x8& b, bf16x8& c, bf16x8& d, bf16x8& e) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : : "memory");
+}
+#ifndef ST355_DQ_DS_AUX
+#define ST355_DQ_DS_AUX 0
+#endif
+template <int HD, int AUX = ST355_DQ_DS_AUX>
+__global__ void __launch_bounds__(256, 3) k_attn_bwd_dq_ds(const bf16* __restrict__ dsT, const bf16* __restrict__ K, const bf16* __restrict__ Q, bf16* __restrict__ dQ,
+                                                           int H, int Sq, int Sqp, int Sk, float scale, RopeBwd rp) {
+  static_assert(HD == 128, "k_attn_bwd_dq_ds: head_dim 128");
+  constexpr int KT = 32;                      // keys per tile
+  constexpr int IMG = KT * 256;               // one image (8 KiB)
+  constexpr int SLOT = 2 * IMG;               // [dS^T image | K image]
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int h = lane >> 5;
+  const WgMap wg = attn_wg_map();
+  const int head = wg.head, b = wg.b;
+  const int64_t bh = (int64_t)b * H + head;
+  const int q0 = wg.tile * 128;
+  // LDS-DMA: piece = wave + 4 p (1 KiB = 4 rows), lane -> row piece * 4 + lane / 16; LDS chunk position c of row r holds source chunk c ^ f(r)
+  const bf16* ds_src[2]; const bf16* k_src[2];
+  const int nqt = Sqp / 64;
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const int piece = wv + 4 * p;             // dS image: piece = 4 (query tile of the pair) + j
+    const int row = piece * 4 + (lane >> 4);  // K image: 4 rows per piece
+    const int chunk = (lane & 15) ^ swz_q(row);
+    ds_src[p] = dsT + bh * (int64_t)Sk * Sqp + (int64_t)(2 * wg.tile) * 2048 + piece * 512 + (lane ^ (((2 * (piece & 1) + (lane >> 5)) & 3) << 2)) * 8;
+    k_src[p] = K + (bh * Sk + row) * (int64_t)HD + chunk * 8;
+  }
+  const int64_t ds_step = (int64_t)nqt * 2048;          // one 32-key block further: Sqp / 64 blocks of 4 KiB
+  auto stage = [&](int kt, int slot) {
+    char* img = smem + slot * SLOT;
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+      a_glds16x<AUX>(ds_src[p] + kt * ds_step, img + (wv + 4 * p) * 1024);
+      a_glds16x<0>(k_src[p] + kt * (KT * HD), img + IMG + (wv + 4 * p) * 1024);        // (K is shared by the head's 36 workgroups through L2: always cached)
+    }
+  };
+  // transposed-fragment lane base (dkv3): lane = 16 g + 4 r + s reads row 8 h + r, chunk (2 ihalf + (s >> 1)) ^ f(row), half (s & 1); ^ (4 * block) << 4 picks the 32-column block
+  const int tr_r = (lane >> 2) & 3, tr_s = lane & 3, tr_ih = (lane >> 4) & 1;
+  const uint32_t tr_base = (8 * h + tr_r) * 256 + ((((2 * tr_ih + (tr_s >> 1)) ^ (4 * tr_r + 2 * h))) << 4) + (tr_s & 1) * 8;
+  const uint32_t lds = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;
+  // dS^T fragment of this wave's queries 32 wv + l31 (query tile wv >> 1, block qb = wv & 1): lane = 32 h + 16 ih + 4 r + s reads key 8 h + r (+ 4: ^ 64, + 16 m: + 256),
+  // queries 16 ih + 4 s .. + 3: piece 4 (wv >> 1) + 2 (wv & 1) + ih, slot (32 (s >> 1) + key) ^ swizzle, half s & 1
+  const uint32_t ds_base = (4 * (wv >> 1) + 2 * (wv & 1) + tr_ih) * 1024 + (((32 * (tr_s >> 1) + 8 * h + tr_r) ^ ((2 * tr_ih + (tr_s >> 1)) << 2)) << 4) + (tr_s & 1) * 8;
+  static_assert(KT == 32, "k_attn_bwd_dq_ds: the tile's fragments are waited for as two k-steps");
+  f32x16 acc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[dt][r] = 0.f;
+  const int nkt = Sk / KT;
+  stage(0, 0);
+  if (nkt > 1) stage(1, 1);
+  int slot = 0, slot2 = 2;                    // ring positions of tile kt and of tile kt + 2
+  for (int kt = 0; kt < nkt; kt++) {
+    // tile kt has landed (each wave issues 4 DMA instructions per tile; tile kt + 1 may stay in flight), every wave is done reading tile kt - 1: its slot is staged next
+    if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (kt + 2 < nkt) stage(kt + 2, slot2);
+    const uint32_t dsi = lds + slot * SLOT, ki = dsi + IMG;
+    bf16x8 dsf[KT / 16], kf[KT / 16][4];
+#pragma unroll
+    for (int m = 0; m < KT / 16; m++) {       // 16 keys per MFMA k-step: rows 16 m + 8 h + 0..7 (two transposing reads: + 0..3, + 4..7)
+      const uint32_t o0 = (16 * m) * 256, o1 = (16 * m + 4) * 256;
+      dsf[m] = lds_tr16x2_nowait(dsi + ds_base + 256 * m, dsi + (ds_base ^ 64) + 256 * m);                                  // dS^T[keys][q = 32 wv + l31]
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++)
+        kf[m][dt] = lds_tr16x2_nowait(ki + (tr_base ^ ((4 * dt) << 4)) + o0, ki + (tr_base ^ (((4 * dt) ^ 1) << 4)) + o1);    // K^T[d = 32 dt + l31][keys]
+    }
+#pragma unroll
+    for (int m = 0; m < KT / 16; m++) {
+      if (m == 0) {                           // one wait covers the tile's twenty reads (the other workgroups of the CU fill the gap)
+        tr_wait(dsf[0], kf[0][0], kf[0][1], kf[0][2], kf[0][3]);
+        tr_wait(dsf[1], kf[1][0], kf[1][1], kf[1][2], kf[1][3]);
+      }
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++) acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[m][dt], dsf[m], acc[dt], 0, 0, 0);
+    }
+    slot = slot == 2 ? 0 : slot + 1;
+    slot2 = slot2 == 2 ? 0 : slot2 + 1;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();               // the ring is idle: each wave parks its 32 token rows in its own 8 KiB
+  asm volatile("" ::: "memory");
+  char* mine = smem + wv * 8192;
+  const int tok0 = q0 + wv * 32;
+  park_rows(acc, scale, lane, mine);
+  if (rp.out != nullptr) {
+    rope_bwd_finish(rp, Q + bh * (int64_t)Sq * HD, b, head, tok0, Sq, lane, mine);
+  } else {
+    const int tl = lane >> 4, c = lane & 15;
+#pragma unroll
+    for (int it = 0; it < 8; it++) {
+      const int t = it * 4 + tl;
+      if (tok0 + t < Sq) *(bf16x8*)(dQ + (bh * Sq + tok0 + t) * (int64_t)HD + c * 8) = *(const bf16x8*)(mine + t * 256 + ((c ^ (t & 15)) << 4));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 static inline size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 extern "C" size_t st355_attn_bwd_workspace(int B, int H, int S, int Sp, int d) {   // S, Sp: the QUERY length and its padding
@@ -1029,10 +1188,45 @@ static int attn_dq_short() {
   return dq_short;
 }
 
+// The dS-spill route (k_attn_bwd_dkv4<128, true> + k_attn_bwd_dq_ds<128>): -1 = the size gate (default), 0 = never, 1 = wherever it is built.  ST355_ATTN_DS=0|1 presets it.
+int g_attn_ds_mode = -2;
+static int attn_ds_mode() {
+  if (g_attn_ds_mode < -1) { const char* e = getenv("ST355_ATTN_DS"); g_attn_ds_mode = (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : -1; }
+  return g_attn_ds_mode;
+}
+extern "C" int st355_attn_set_ds(int mode) {
+  const int prev = attn_ds_mode();
+  if (mode >= -1 && mode <= 1) g_attn_ds_mode = mode;
+  return prev;
+}
+static int attn_device_cus() {
+  static int v = -1;
+  if (v < 0) {
+    int dev = 0; hipDeviceProp_t pr;
+    v = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+  }
+  return v;
+}
+extern "C" size_t st355_attn_bwd_ds_bytes(int B, int H, int Sq, int Sqp, int Sk, int d) {
+  (void)Sq;
+  return d == 128 ? (size_t)B * H * Sk * Sqp * 2 : 0;                       // dS^T [B, H, Sk, Sqp] bf16
+}
+// Is the spill route taken?  Built for head_dim 128 without key bias or transposed copies, on the default dkv4 / dq64 choices, Sq and Sk multiples of 256 (dkv4's 256-key
+// workgroups and the dQ kernel's 128-query workgroups meet no ragged edge) and 32-bit lane offsets into one head's dS^T.  Default gate: the dK / dV grid runs at least
+// THREE full rounds of the device.  Measured at the Flux shape (H24 S4608, 256 CUs; profiles/attn_ds_route_ab.md): batch 8 (3456 workgroups) 5.56 vs 5.66 ms per pair, batch 4
+// (1728) 2.72 vs 2.82, batch 2 (864 = 3.4 rounds) 1.47 vs 1.57 — each beyond its repeat-to-repeat spread; nothing smaller has been measured, so it keeps the recompute kernels.
+static bool attn_ds_route(int B, int H, int Sq, int Sqp, int Sk, int d, bool qt, bool kt, bool bias, bool given) {
+  if (!given || attn_ds_mode() == 0) return false;
+  if (d != 128 || qt || kt || bias || Sq % 256 != 0 || Sk % 256 != 0 || Sqp < Sq || (uint64_t)Sk * Sqp * 2 >= (1ull << 32)) return false;
+  if (attn_ds_mode() == 1) return true;
+  return (int64_t)B * H * (Sk / 256) >= 3 * (int64_t)attn_device_cus();
+}
+
 // The backward's kernel choices (ST355_ATTN_ROUTE_* + head_dim index per stage), shared by attn_bwd_impl and st355_attn_plan; d is 64, 96 or 128.
 // qt / kt: the Q^T (+ dO^T) / K^T copies are given; rope_q / rope_k: the fused RoPE epilogue writes dQ / dK (then no head-major dQ / dK exists).
 struct AttnBwdRoute { int prep, dkv, dq, dq_tail; };
-static AttnBwdRoute attn_bwd_route(int d, int Sk, bool qt, bool kt, bool bias, bool res, bool rope_q, bool rope_k) {
+// ds: attn_ds_route said yes (dkv4 / dq64 are replaced together; a forced dkv3 or 32-row dQ keeps the recompute route)
+static AttnBwdRoute attn_bwd_route(int d, int Sk, bool qt, bool kt, bool bias, bool res, bool rope_q, bool rope_k, bool ds = false) {
   const int hd = d == 64 ? 0 : d == 96 ? 1 : 2;
   AttnBwdRoute r{};
   r.prep = (res ? (qt ? ST355_ATTN_ROUTE_PREP_RES_DOT : ST355_ATTN_ROUTE_PREP_RES) : (qt ? ST355_ATTN_ROUTE_PREP_DOT : ST355_ATTN_ROUTE_PREP)) + hd;
@@ -1041,6 +1235,11 @@ static AttnBwdRoute attn_bwd_route(int d, int Sk, bool qt, bool kt, bool bias, b
   else r.dkv = ST355_ATTN_ROUTE_DKV2 + hd;          // head-major Q^T / dO^T copies supplied: the LDS-DMA kernel over four tile images
   // the 64-row kernel takes the full 64-key tiles; a ragged key tail (SD3's S = 4096 + 231, every mixed-aspect bucket) is added by the general kernel restricted
   // to the last tile (kt0 / accumulate).  The fused-RoPE epilogue (head_dim 128, Flux: S % 64 == 0 always) writes projection rows, not dQ: no tail form.
+  if (ds && attn_dkv_impl() == 4 && attn_dq_impl() == 64) {
+    r.dkv = (rope_k ? ST355_ATTN_ROUTE_DKV4_ROPE_DS : ST355_ATTN_ROUTE_DKV4_DS) + hd;
+    r.dq = (rope_q ? ST355_ATTN_ROUTE_DQ_DS_ROPE : ST355_ATTN_ROUTE_DQ_DS) + hd;
+    return r;
+  }
   const bool dq_tail = Sk % 64 != 0;
   // a SHORT ragged key axis (the UNets' cross-attention: 77 text keys = one full tile + 13 keys) goes through the general kernel in ONE pass: as 64-row kernel + tail
   // it was two memory-bound passes over Q / dO / dQ with a bf16 round trip of dQ between them (r6; ST355_ATTN_DQ_SHORT=0: A/B)
@@ -1069,7 +1268,8 @@ extern "C" int st355_attn_set_impl(int fwd, int dq, int dkv) {
 static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void* Qt, const void* Kt, const void* v_rows,
                               int64_t ld_v, const void* O, int64_t ld_o, const void* dO, int64_t ld_do, const float* lse2,
                               const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv, int B, int H, int S, int Sp, int Sk, int Skp,
-                              int d, float scale, void* workspace, const RopeBwd* rope_q = nullptr, const RopeBwd* rope_k = nullptr, const void* O_res = nullptr) {
+                              int d, float scale, void* workspace, const RopeBwd* rope_q = nullptr, const RopeBwd* rope_k = nullptr, const void* O_res = nullptr,
+                              void* ds = nullptr, size_t ds_bytes = 0) {
   const RopeBwd rq = rope_q ? *rope_q : RopeBwd{}, rk = rope_k ? *rope_k : RopeBwd{};       // out == NULL: head-major dQ / dK as before
   ST_REQUIRE(Q && K && v_rows && O && dO && lse2 && (dQ || rq.out) && (dK || rk.out) && dv_rows && workspace, "attn_bwd: null pointer");
   // Qt == NULL selects the third-generation dK/dV kernel, Kt == NULL the transposing-read dQ kernel (head_dim 128): Q^T / dO^T / K^T fragments come
@@ -1086,9 +1286,13 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
   const double fl_unit = 2.0 * (double)B * H * (double)S * Sk * d;  // one Sq x Sk x d contraction
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  const AttnBwdRoute route = attn_bwd_route(d, Sk, Qt != nullptr, Kt != nullptr, key_bias != nullptr, O_res != nullptr, rq.out != nullptr, rk.out != nullptr);
+  // the spill buffer is the caller's opt-in: null, misaligned or too small selects the recompute route silently
+  const bool ds_given = ds != nullptr && ((uintptr_t)ds & 255) == 0 && (d == 128) && ds_bytes >= st355_attn_bwd_ds_bytes(B, H, S, Sp, Sk, d);
+  const bool ds_route = attn_ds_route(B, H, S, Sp, Sk, d, Qt != nullptr, Kt != nullptr, key_bias != nullptr, ds_given);
+  const AttnBwdRoute route = attn_bwd_route(d, Sk, Qt != nullptr, Kt != nullptr, key_bias != nullptr, O_res != nullptr, rq.out != nullptr, rk.out != nullptr, ds_route);
   const int dkv_kind = route.dkv / 10 * 10;
-  const bool use_dkv4 = dkv_kind == ST355_ATTN_ROUTE_DKV4 || dkv_kind == ST355_ATTN_ROUTE_DKV4_ROPE;
+  const bool use_dkv4_ds = dkv_kind == ST355_ATTN_ROUTE_DKV4_DS || dkv_kind == ST355_ATTN_ROUTE_DKV4_ROPE_DS;
+  const bool use_dkv4 = use_dkv4_ds || dkv_kind == ST355_ATTN_ROUTE_DKV4 || dkv_kind == ST355_ATTN_ROUTE_DKV4_ROPE;
   {
     ProfScope ps(stream, ST355_K_ATTN_PREP, 2.0 * B * H * (double)S * d, 6.0 * B * H * (double)S * d);
     dim3 grid(Sp / 64, H, B);
@@ -1102,8 +1306,15 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
     if ((rc = st355_check_launch("attn_bwd_prep")) != 0) return rc;
   }
   {
-    ProfScope ps(stream, ST355_K_ATTN_BWD_DKV, 4.0 * fl_unit, 2.0 * (double)B * H * (S + Sk) * d * 4.0);
-    if (use_dkv4) {                                                    // hand-scheduled body (k_attn_bwd_dkv4)
+    ProfScope ps(stream, ST355_K_ATTN_BWD_DKV, 4.0 * fl_unit, 2.0 * (double)B * H * (S + Sk) * d * 4.0 + (use_dkv4_ds ? 2.0 * (double)B * H * Sk * Sp : 0.0));
+    if (use_dkv4_ds) {                                                 // dkv4 + the dS^T spill (head_dim 128)
+      dim3 grid(Sk / 256, H, B);
+      const int lds = 8 * 16384;
+      static St355AttrOnce set;
+      if (set.need()) { hipFuncSetAttribute((const void*)k_attn_bwd_dkv4<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); }
+      hipLaunchKernelGGL((k_attn_bwd_dkv4<128, true>), grid, dim3(512), lds, st, (const bf16*)Q, (const bf16*)K, (const bf16*)v_rows, ld_v, (const bf16*)dO, ld_do,
+                         (const float*)lsep, (const float*)delta, (bf16*)dK, (bf16*)dv_rows, ld_dv, H, S, Sp, Sk, scale, scale2, rk, (bf16*)ds);
+    } else if (use_dkv4) {                                                    // hand-scheduled body (k_attn_bwd_dkv4)
       dim3 grid((Sk + 255) / 256, H, B);
       const int lds = 8 * 16384;                                       // the two ring slots (66.5 KiB); 16 KiB per wave for the parked dK / dV rows
 #define ST355_DKV4_LAUNCH(HD_)                                                                                                            \
@@ -1151,7 +1362,15 @@ static int attn_bwd_impl(void* stream, const void* Q, const void* K, const void*
     if ((rc = st355_check_launch("attn_bwd_dkv")) != 0) return rc;
   }
   const int dq_kind = route.dq / 10 * 10;
-  if (dq_kind == ST355_ATTN_ROUTE_DQ64 || dq_kind == ST355_ATTN_ROUTE_DQ64_ROPE) {      // hand-scheduled 64-queries-per-wave kernel (k_attn_bwd_dq64)
+  if (dq_kind == ST355_ATTN_ROUTE_DQ_DS || dq_kind == ST355_ATTN_ROUTE_DQ_DS_ROPE) {           // dQ = scale dS K from the spill: one contraction, memory bound
+    ProfScope ps(stream, ST355_K_ATTN_BWD_DQ, 1.0 * fl_unit, 2.0 * (double)B * H * Sk * Sp + 2.0 * (double)B * H * (2.0 * S + Sk) * d);
+    dim3 grid(S / 128, H, B);
+    const int lds = 3 * 2 * 32 * 256;
+    static St355AttrOnce set;
+    if (set.need()) { hipFuncSetAttribute((const void*)k_attn_bwd_dq_ds<128>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); }
+    hipLaunchKernelGGL(k_attn_bwd_dq_ds<128>, grid, dim3(256), lds, st, (const bf16*)ds, (const bf16*)K, (const bf16*)Q, (bf16*)dQ, H, S, Sp, Sk, scale, rq);
+    if ((rc = st355_check_launch("attn_bwd_dq_ds")) != 0) return rc;
+  } else if (dq_kind == ST355_ATTN_ROUTE_DQ64 || dq_kind == ST355_ATTN_ROUTE_DQ64_ROPE) {      // hand-scheduled 64-queries-per-wave kernel (k_attn_bwd_dq64)
     ProfScope ps(stream, ST355_K_ATTN_BWD_DQ, 3.0 * fl_unit, 2.0 * (double)B * H * (S + Sk) * d * 3.0);
     dim3 grid((S + 255) / 256, H, B);
     const int lds = 3 * 2 * 64 * 256;
@@ -1220,6 +1439,13 @@ extern "C" int st355_attn_bwd(void* stream, const void* Q, const void* K, const 
                               int d, float scale, void* workspace) {
   return attn_bwd_impl(stream, Q, K, Qt, Kt, v_rows, ld_v, O, ld_o, dO, ld_do, lse2, key_bias, dQ, dK, dv_rows, ld_dv, B, H, S, Sp, S, Sp, d, scale, workspace);
 }
+extern "C" int st355_attn_bwd_ds(void* stream, const void* Q, const void* K, const void* Qt, const void* Kt, const void* v_rows,
+                                 int64_t ld_v, const void* O, int64_t ld_o, const void* dO, int64_t ld_do, const float* lse2,
+                                 const float* key_bias, void* dQ, void* dK, void* dv_rows, int64_t ld_dv, int B, int H, int S, int Sp,
+                                 int d, float scale, void* workspace, void* ds, size_t ds_bytes) {
+  return attn_bwd_impl(stream, Q, K, Qt, Kt, v_rows, ld_v, O, ld_o, dO, ld_do, lse2, key_bias, dQ, dK, dv_rows, ld_dv, B, H, S, Sp, S, Sp, d, scale, workspace,
+                       nullptr, nullptr, nullptr, ds, ds_bytes);
+}
 // st355_attn_bwd / st355_attn_cross_bwd with delta = rowsum(dO * (O + O_res)): O_res is what st355_attn_fwd_res wrote (attention.hip has the why)
 extern "C" int st355_attn_bwd_res(void* stream, const void* Q, const void* K, const void* Qt, const void* Kt, const void* v_rows, int64_t ld_v, const void* O,
                                   int64_t ld_o, const void* O_res, const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, void* dQ, void* dK,
@@ -1230,10 +1456,10 @@ extern "C" int st355_attn_bwd_res(void* stream, const void* Q, const void* K, co
 }
 // Self-attention backward with the RoPE + RMSNorm backward fused into the dQ / dK epilogues (head_dim 128, the fused-projection form): dq, dk and dv all
 // land in the rows of the projection gradient dqkv [B*S, ld] (column blocks q | k | v of width D = H*128); no head-major dQ / dK exists.
-extern "C" int st355_attn_bwd_rope(void* stream, const void* Q, const void* K, const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o,
-                                   const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, const float* rrms, const void* wq_lo,
-                                   const void* wk_lo, const void* wq_hi, const void* wk_hi, int split, const float* cos_p, const float* sin_p,
-                                   void* dqkv, int64_t ld_dqkv, int B, int H, int S, int Sp, int d, float scale, void* workspace) {
+extern "C" int st355_attn_bwd_rope_ds(void* stream, const void* Q, const void* K, const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o,
+                                      const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, const float* rrms, const void* wq_lo,
+                                      const void* wk_lo, const void* wq_hi, const void* wk_hi, int split, const float* cos_p, const float* sin_p,
+                                      void* dqkv, int64_t ld_dqkv, int B, int H, int S, int Sp, int d, float scale, void* workspace, void* ds, size_t ds_bytes) {
   ST_REQUIRE(d == 128, "attn_bwd_rope: head_dim %d not built (128 only)", d);
   ST_REQUIRE(rrms && cos_p && sin_p && dqkv && ld_dqkv % 8 == 0 && ld_dqkv >= 3 * (int64_t)H * d && split >= 0 && split <= S, "attn_bwd_rope: bad arguments");
   ST_REQUIRE((wq_lo == nullptr) == (wq_hi == nullptr) && (wk_lo == nullptr) == (wk_hi == nullptr), "attn_bwd_rope: a norm weight needs both position ranges");
@@ -1241,7 +1467,14 @@ extern "C" int st355_attn_bwd_rope(void* stream, const void* Q, const void* K, c
   RopeBwd rq{rrms, (const bf16*)wq_lo, (const bf16*)wq_hi, cos_p, sin_p, (bf16*)dqkv, ld_dqkv, split, H, S, 0};
   RopeBwd rk{rrms, (const bf16*)wk_lo, (const bf16*)wk_hi, cos_p, sin_p, (bf16*)dqkv + D, ld_dqkv, split, H, S, H};
   return attn_bwd_impl(stream, Q, K, nullptr, nullptr, v_rows, ld_v, O, ld_o, dO, ld_do, lse2, key_bias, nullptr, nullptr, (bf16*)dqkv + 2 * D, ld_dqkv,
-                       B, H, S, Sp, S, Sp, d, scale, workspace, &rq, &rk);
+                       B, H, S, Sp, S, Sp, d, scale, workspace, &rq, &rk, nullptr, ds, ds_bytes);
+}
+extern "C" int st355_attn_bwd_rope(void* stream, const void* Q, const void* K, const void* v_rows, int64_t ld_v, const void* O, int64_t ld_o,
+                                   const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, const float* rrms, const void* wq_lo,
+                                   const void* wk_lo, const void* wq_hi, const void* wk_hi, int split, const float* cos_p, const float* sin_p,
+                                   void* dqkv, int64_t ld_dqkv, int B, int H, int S, int Sp, int d, float scale, void* workspace) {
+  return st355_attn_bwd_rope_ds(stream, Q, K, v_rows, ld_v, O, ld_o, dO, ld_do, lse2, key_bias, rrms, wq_lo, wk_lo, wq_hi, wk_hi, split, cos_p, sin_p, dqkv, ld_dqkv,
+                                B, H, S, Sp, d, scale, workspace, nullptr, 0);
 }
 // cross-attention backward: Q,Qt over Sq (padded Sqp) queries; K,Kt, v_rows / dv_rows ([B*Sk, ld]) over Sk (padded Skp) keys; workspace sized for (Sq, Sqp)
 extern "C" int st355_attn_cross_bwd(void* stream, const void* Q, const void* K, const void* Qt, const void* Kt, const void* v_rows,
@@ -1254,14 +1487,15 @@ extern "C" int st355_attn_cross_bwd(void* stream, const void* Q, const void* K, 
 int attn_fwd_route(int d, int S, bool bias, bool vrow, bool res);     // attention.hip
 extern "C" int st355_attn_plan(int B, int H, int Sq, int Sk, int d, int flags, int32_t* routes) {
   ST_REQUIRE(routes, "attn_plan: null routes");
-  ST_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0 && (flags & ~63) == 0, "attn_plan: bad arguments Sq=%d Sk=%d flags=%d", Sq, Sk, flags);
+  ST_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0 && (flags & ~127) == 0, "attn_plan: bad arguments Sq=%d Sk=%d flags=%d", Sq, Sk, flags);
   if (d != 128 && d != 64 && d != 96) { st355_set_error("attn_plan: head_dim %d not built", d); return ST355_ENOSYS; }
   const bool bias = flags & ST355_ATTN_PLAN_BIAS, vrow = flags & ST355_ATTN_PLAN_VROWS, res = flags & ST355_ATTN_PLAN_RES;
   const bool qt = flags & ST355_ATTN_PLAN_QT, kt = flags & ST355_ATTN_PLAN_KT, rope = flags & ST355_ATTN_PLAN_ROPE;
   ST_REQUIRE(!vrow || (d == 128 && !res), "attn_plan: row-major V is built for head_dim 128 without O_res");
   ST_REQUIRE(!rope || (d == 128 && Sq == Sk && !qt && !kt && !res), "attn_plan: the fused RoPE backward is self-attention at head_dim 128 without copies or O_res");
   routes[0] = attn_fwd_route(d, Sk, bias, vrow, res);
-  const AttnBwdRoute r = attn_bwd_route(d, Sk, qt, kt, bias, res, rope, rope);
+  const bool ds = attn_ds_route(B, H, Sq, (Sq + 63) / 64 * 64, Sk, d, qt, kt, bias, (flags & ST355_ATTN_PLAN_DS) != 0);
+  const AttnBwdRoute r = attn_bwd_route(d, Sk, qt, kt, bias, res, rope, rope, ds);
   routes[1] = r.prep;
   routes[2] = r.dkv;
   routes[3] = r.dq;

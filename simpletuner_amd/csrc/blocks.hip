@@ -96,8 +96,8 @@ extern "C" int st355_block_flux_single_bwd(void* stream, const st355_flux_single
   q.gemm(G(p->dhpre, 4 * D, p->wT_mlp, 4 * D, p->dn_mlp, D, M, D, 4 * D));
   // attention backward with the RoPE + RMSNorm backward in the dQ / dK kernels' epilogues: dq | dk | dv rows of the projection gradient
   if (q.ok())
-    q.run(st355_attn_bwd_rope(stream, p->Q, p->K, p->V, D, p->O, D, p->dO, D, p->lse2, p->key_bias, p->rrms, p->norm_q, p->norm_k, p->norm_q, p->norm_k, 0,
-                              p->cos_p, p->sin_p, p->dqkv, 3 * D, B, H, S, S, 128, p->scale, p->attn_ws));
+    q.run(st355_attn_bwd_rope_ds(stream, p->Q, p->K, p->V, D, p->O, D, p->dO, D, p->lse2, p->key_bias, p->rrms, p->norm_q, p->norm_k, p->norm_q, p->norm_k, 0,
+                                 p->cos_p, p->sin_p, p->dqkv, 3 * D, B, H, S, S, 128, p->scale, p->attn_ws, p->attn_ds, p->attn_ds_bytes > 0 ? (size_t)p->attn_ds_bytes : 0));
   // d norm_hidden = dqkv Wqkv (+ (dqkv sB) A) + d norm_hidden(mlp)
   if (p->K2) {
     st355_gemm_args u = G(p->dqkv, 3 * D, p->B_blk_T, 3 * D, p->U, p->K2, M, p->K2, 3 * D);
@@ -317,8 +317,9 @@ extern "C" int st355_block_flux_double_bwd(void* stream, const st355_flux_double
                p->gA_out, p->gB_out, p->accumulate, p->skinny_ws);
   // ---- attention (+ RoPE / RMSNorm backward in its epilogues): text positions < St carry the norm_added weights ----
   if (q.ok())
-    q.run(st355_attn_bwd_rope(stream, p->Q, p->K, p->V, D, p->O, D, p->dO, D, (const float*)p->lse2, (const float*)p->key_bias, (const float*)p->rrms, p->norm_added_q,
-                              p->norm_added_k, p->norm_q, p->norm_k, St, (const float*)p->cos_p, (const float*)p->sin_p, p->dqkv, 3 * D, B, H, S, S, 128, p->scale, p->attn_ws));
+    q.run(st355_attn_bwd_rope_ds(stream, p->Q, p->K, p->V, D, p->O, D, p->dO, D, (const float*)p->lse2, (const float*)p->key_bias, (const float*)p->rrms, p->norm_added_q,
+                                 p->norm_added_k, p->norm_q, p->norm_k, St, (const float*)p->cos_p, (const float*)p->sin_p, p->dqkv, 3 * D, B, H, S, S, 128, p->scale, p->attn_ws,
+                                 p->attn_ds, p->attn_ds_bytes > 0 ? (size_t)p->attn_ds_bytes : 0));
   // ---- input projections: the two streams' rows of the joint dqkv, in place ----
   const Rows dq_i = joint_rows(p->dqkv, 3 * D, St, S), dq_t = joint_rows(p->dqkv, 3 * D, 0, S);
   if (p->K2_qkv) {

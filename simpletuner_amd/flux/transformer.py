@@ -877,6 +877,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             mk = lambda c: torch.empty(B * S, c, dtype=BF16, device=dev)
             dx_out = mk(D)
             dxg_out = mk(D) if gprev is not None else None
+            ads = ops.attn_ds_scratch(dev, B, H, S, S, 128, env.key_bias, rope=True)     # the dS^T spill buffer where the library takes that route, else None
             ops.block_flux_single_bwd([t for t in lo.gA] if lo is not None else None, [t for t in lo.gB] if lo is not None else None,
                                       B=B, S=S, H=H, D=D, K2=lo.K2 if lo is not None else 0, k2_real=lo.k2_real if lo is not None else 0,
                                       n_targets=len(lo.targets) if lo is not None else 0, rank=lo.rank if lo is not None else 0, r_pad=lo.r_pad if lo is not None else 0,
@@ -887,7 +888,8 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                                       A_cat_T=lo.A_cat_T if lo is not None else None, B_blk_T=lo.B_blk_T if lo is not None else None,
                                       norm_q=blk.norm_q, norm_k=blk.norm_k, cos_p=env.cos_p, sin_p=env.sin_p, key_bias=env.key_bias, dx=dx, dxg=dxg,
                                       g=mk(D) if dxg is None else None, dO=mk(D), dhpre=mk(4 * D), dn_mlp=mk(D), dqkv=mk(3 * D),
-                                      U=mk(lo.K2) if lo is not None else None, dn=mk(D), dx_out=dx_out, dxg_out=dxg_out)
+                                      U=mk(lo.K2) if lo is not None else None, dn=mk(D), dx_out=dx_out, dxg_out=dxg_out,
+                                      attn_ds=ads, attn_ds_bytes=ops.attn_ds_bytes(ads))
             if lo is not None and self.grad_sync is not None:
                 self.grad_sync.ready(lo.flat_lo, lo.flat_hi)
             return dx_out, dxg_out, None, None
@@ -951,6 +953,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             lq, lo_ = blk.qkv.lora, blk.to_out.lora
             mk = lambda r, c: torch.empty(r, c, dtype=BF16, device=dev)
             d_img_out, d_txt_out = mk(B * Si, D), mk(B * St, D)
+            ads = ops.attn_ds_scratch(dev, B, H, S, S, 128, env.key_bias, rope=True)
             ops.block_flux_double_bwd(
                 {"gA_qkv": list(lq.gA) if lq is not None else None, "gB_qkv": list(lq.gB) if lq is not None else None,
                  "gA_out": list(lo_.gA) if lo_ is not None else None, "gB_out": list(lo_.gB) if lo_ is not None else None},
@@ -969,7 +972,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                 g_img=mk(B * Si, D), g_txt=mk(B * St, D), dh_img=mk(B * Si, 4 * D), dh_txt=mk(B * St, 4 * D), dn2_img=mk(B * Si, D), dn2_txt=mk(B * St, D),
                 dx1_img=mk(B * Si, D), dx1g_img=mk(B * Si, D), dx1_txt=mk(B * St, D), dx1g_txt=mk(B * St, D), dO=mk(B * S, D), dqkv=mk(B * S, 3 * D),
                 U_qkv=mk(B * Si, lq.K2) if lq is not None else None, U_out=mk(B * Si, lo_.K2) if lo_ is not None else None,
-                dn_img=mk(B * Si, D), dn_txt=mk(B * St, D), d_img_out=d_img_out, d_txt_out=d_txt_out)
+                dn_img=mk(B * Si, D), dn_txt=mk(B * St, D), d_img_out=d_img_out, d_txt_out=d_txt_out, attn_ds=ads, attn_ds_bytes=ops.attn_ds_bytes(ads))
             if self.grad_sync is not None:                     # the host-side order: to_out.0's adapters first, then to_q / to_k / to_v's
                 for lg in (lo_, lq):
                     if lg is not None:

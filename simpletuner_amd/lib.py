@@ -24,6 +24,7 @@ SYMBOLS = [
     "st355_ln_modulate_fwd", "st355_ln_modulate_bwd",
     "st355_qk_norm_rope_fwd", "st355_qk_norm_rope_bwd", "st355_qk_norm_wgrad_workspace", "st355_qk_norm_rope_bwd_wgrad", "st355_qk_rope_norm_bwd",
     "st355_attn_set_impl", "st355_attn_plan", "st355_attn_fwd", "st355_attn_fwd_vrows", "st355_attn_bwd_workspace", "st355_attn_bwd", "st355_attn_bwd_rope",
+    "st355_attn_bwd_ds_bytes", "st355_attn_set_ds", "st355_attn_bwd_ds", "st355_attn_bwd_rope_ds",
     "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_lion_step", "st355_lion_step_bf16", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
     "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
     "st355_soap_plan", "st355_soap_step", "st355_soap_eigh",
@@ -105,6 +106,7 @@ class FluxSingleBwdArgs(C.Structure):
         ("g", C.c_void_p), ("dO", C.c_void_p), ("dhpre", C.c_void_p), ("dn_mlp", C.c_void_p), ("dqkv", C.c_void_p), ("U", C.c_void_p), ("dn", C.c_void_p),
         ("gemm_ws", C.c_void_p), ("gemm_ws_bytes", C.c_int64), ("attn_ws", C.c_void_p), ("skinny_ws", C.c_void_p),
         ("dx_out", C.c_void_p), ("dxg_out", C.c_void_p),
+        ("attn_ds", C.c_void_p), ("attn_ds_bytes", C.c_int64),
     ]
 
 
@@ -150,6 +152,7 @@ class FluxDoubleBwdArgs(C.Structure):
         ("U_qkv", C.c_void_p), ("U_out", C.c_void_p), ("dn_img", C.c_void_p), ("dn_txt", C.c_void_p), ("gemm_ws", C.c_void_p),
         ("gemm_ws_bytes", C.c_int64),
         ("attn_ws", C.c_void_p), ("skinny_ws", C.c_void_p), ("d_img_out", C.c_void_p), ("d_txt_out", C.c_void_p),
+        ("attn_ds", C.c_void_p), ("attn_ds_bytes", C.c_int64),
     ]
 
 
@@ -332,6 +335,12 @@ def _declare(lib):
         "st355_attn_fwd_vrows": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, f32]),
         "st355_attn_bwd_rope": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp]),
         "st355_attn_bwd_workspace": (sz, [i32, i32, i32, i32, i32]),
+        "st355_attn_bwd_ds_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+        "st355_attn_set_ds": (C.c_int, [i32]),
+        "st355_attn_bwd_ds": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64,
+                                         i32, i32, i32, i32, i32, f32, vp, vp, sz]),
+        "st355_attn_bwd_rope_ds": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp,
+                                              vp, sz]),
         "st355_attn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64,
                                       i32, i32, i32, i32, i32, f32, vp]),
         "st355_adamw_ema_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, f32]),

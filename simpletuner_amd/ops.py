@@ -484,12 +484,18 @@ def attn_set_impl(fwd: int = -1, dq: int = -1, dkv: int = -1):
     return prev // 65536, (prev // 256) % 256, prev % 256
 
 
+def attn_set_ds(mode: int = -1) -> int:
+    """st355_attn_set_ds: the dS-spill attention backward (head_dim 128): 0 = never (the recompute kernels: A/B switch), 1 = wherever it is built, whatever the size
+    (tests), -1 = the library's size gate (default).  Returns the previous mode."""
+    return int(_l.load().st355_attn_set_ds(int(mode)))
+
+
 ATTN_ROUTE_KINDS = {10: "fwd64", 20: "fwd4", 30: "fwd4_bias", 40: "fwd4_res", 50: "fwd4_res_bias", 60: "fwd4_vrows", 70: "fwd4_vrows_bias",
                     100: "prep", 110: "prep_res", 120: "prep_dot", 130: "prep_res_dot",
                     200: "dkv4", 210: "dkv4_rope", 220: "dkv3", 230: "dkv3_rope", 240: "dkv2",
                     300: "dq64", 310: "dq64_rope", 320: "dq_tr", 330: "dq_tr_bias", 340: "dq", 350: "dq_bias", 360: "dq_tr_rope",
-                    370: "dq_tr_bias_rope"}      # ST355_ATTN_ROUTE_* (st355.h) + 0 / 1 / 2 for head_dim 64 / 96 / 128
-ATTN_PLAN_FLAGS = {"key_bias": 1, "vrows": 2, "O_res": 4, "Qt": 8, "Kt": 16, "rope": 32}
+                    370: "dq_tr_bias_rope", 250: "dkv4_ds", 260: "dkv4_rope_ds", 380: "dq_ds", 390: "dq_ds_rope"}      # ST355_ATTN_ROUTE_* (st355.h) + 0 / 1 / 2 for head_dim 64 / 96 / 128
+ATTN_PLAN_FLAGS = {"key_bias": 1, "vrows": 2, "O_res": 4, "Qt": 8, "Kt": 16, "rope": 32, "ds": 64}
 
 
 def attn_route_name(route: int) -> str:
@@ -497,11 +503,11 @@ def attn_route_name(route: int) -> str:
     return f"{ATTN_ROUTE_KINDS[kind]}<{(64, 96, 128)[hd]}>"
 
 
-def attn_plan(B, H, Sq, Sk, d, key_bias=False, vrows=False, O_res=False, Qt=False, Kt=False, rope=False):
+def attn_plan(B, H, Sq, Sk, d, key_bias=False, vrows=False, O_res=False, Qt=False, Kt=False, rope=False, ds=False):
     """st355_attn_plan: the kernels a forward + backward of this shape would run on now, without launching anything.  The keyword arguments say what the calls
-    are given (truthy: present).  Returns {"fwd", "prep", "dkv", "dq": route names such as "dq64<128>", "dq_tail": bool}."""
+    are given (truthy: present; ds: a large-enough dS^T spill buffer).  Returns {"fwd", "prep", "dkv", "dq": route names such as "dq64<128>", "dq_tail": bool}."""
     flags = 0
-    for k, v in (("key_bias", key_bias), ("vrows", vrows), ("O_res", O_res), ("Qt", Qt), ("Kt", Kt), ("rope", rope)):
+    for k, v in (("key_bias", key_bias), ("vrows", vrows), ("O_res", O_res), ("Qt", Qt), ("Kt", Kt), ("rope", rope), ("ds", ds)):
         if v is not None and v is not False:
             flags |= ATTN_PLAN_FLAGS[k]
     routes = (C.c_int32 * 5)()
@@ -887,13 +893,34 @@ def _attn_bwd_scratch(dev, B, H, S, Sp, d):
     return _scratch("attn_bwd", dev, _l.load().st355_attn_bwd_workspace(B, H, S, Sp, d))
 
 
+def attn_ds_scratch(dev, B, H, S, Sp, d, key_bias=None, rope=False):
+    """the dS^T spill buffer of the attention backward — allocated only where the library would take the spill route with one (st355_attn_plan decides; elsewhere
+    None: today's kernels run); one scratch per device under the retire-and-refuse rule of _scratch"""
+    if d != 128 or key_bias is not None or Sp != S:
+        return None
+    if not attn_plan(B, H, S, S, d, rope=rope, ds=True)["dq"].startswith("dq_ds"):
+        return None
+    return _scratch("attn_bwd_ds", dev, _l.load().st355_attn_bwd_ds_bytes(B, H, S, Sp, S, d))
+
+
+def attn_ds_bytes(ds) -> int:
+    return 0 if ds is None else ds.numel() * ds.element_size()
+
+
 # ST355_ATTN_TR=0: the engines build head-major Q^T / K^T copies and the backward reads them (dkv2 / dq); default: no copies, transposing LDS reads
 ATTN_TR = os.environ.get("ST355_ATTN_TR", "1") != "0"
 
 
-def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None):
+def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None, ds=None, ds_bytes=None):
+    """ds (a uint8 device tensor; ds_bytes: what the call is told it holds, default all of it): the caller's dS^T spill buffer -> st355_attn_bwd_ds"""
     L = _l.load()
     ws = _attn_bwd_scratch(Q.device, B, H, S, Sp, d)
+    if ds is not None:
+        _l.check(L.st355_attn_bwd_ds(_stream(), _ptr(Q), _ptr(K), _ptr(Qt), _ptr(Kt), _ptr(v_rows), _rows(v_rows, "v_rows"),
+                                     _ptr(O), _rows(O, "O"), _ptr(dO), _rows(dO, "dO"), _ptr(lse2), _ptr(key_bias),
+                                     _ptr(dQ), _ptr(dK), _ptr(dv_rows), _rows(dv_rows, "dv_rows"), B, H, S, Sp, d, scale, _ptr(ws), _ptr(ds),
+                                     attn_ds_bytes(ds) if ds_bytes is None else int(ds_bytes)), "attn_bwd_ds")
+        return
     if O_res is not None:          # delta = rowsum(dO * (O + O_res))
         _res_ok(O, O_res)
         _l.check(L.st355_attn_bwd_res(_stream(), _ptr(Q), _ptr(K), _ptr(Qt), _ptr(Kt), _ptr(v_rows), _rows(v_rows, "v_rows"),
@@ -906,12 +933,22 @@ def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d,
              "attn_bwd")
 
 
-def attn_bwd_rope(Q, K, v_rows, O, dO, lse2, rrms, wq_lo, wk_lo, wq_hi, wk_hi, split: int, cos_p, sin_p, dqkv, B, H, S, Sp, d, scale: float, key_bias=None):
+def attn_bwd_rope(Q, K, v_rows, O, dO, lse2, rrms, wq_lo, wk_lo, wq_hi, wk_hi, split: int, cos_p, sin_p, dqkv, B, H, S, Sp, d, scale: float, key_bias=None,
+                  ds=None, ds_bytes=None):
     """attention backward with the RoPE + RMSNorm backward fused into the dQ / dK epilogues (head_dim 128, after a fused QKV projection): dq, dk, dv are
-    written straight into the rows of the projection gradient dqkv [B*S, >= 3*H*d]; joint positions < split use the *_lo norm weights."""
+    written straight into the rows of the projection gradient dqkv [B*S, >= 3*H*d]; joint positions < split use the *_lo norm weights.
+    ds / ds_bytes: a dS^T spill buffer of the caller's (as attn_bwd); None: the shared scratch where the library would take the spill route."""
     L = _l.load()
     _chk(Q, BF16, "Q"); _chk(K, BF16, "K"); _chk(rrms, F32, "rrms"); _chk(dqkv, BF16, "dqkv"); _chk(cos_p, F32, "cos_p"); _chk(sin_p, F32, "sin_p")
     ws = _attn_bwd_scratch(Q.device, B, H, S, Sp, d)
+    if ds is None:
+        ds = attn_ds_scratch(Q.device, B, H, S, Sp, d, key_bias, rope=True)
+    if ds is not None:
+        _l.check(L.st355_attn_bwd_rope_ds(_stream(), _ptr(Q), _ptr(K), _ptr(v_rows), _rows(v_rows, "v_rows"), _ptr(O), _rows(O, "O"), _ptr(dO), _rows(dO, "dO"),
+                                          _ptr(lse2), _ptr(key_bias), _ptr(rrms), _ptr(wq_lo), _ptr(wk_lo), _ptr(wq_hi), _ptr(wk_hi), split, _ptr(cos_p), _ptr(sin_p),
+                                          _ptr(dqkv), _rows(dqkv, "dqkv"), B, H, S, Sp, d, scale, _ptr(ws), _ptr(ds),
+                                          attn_ds_bytes(ds) if ds_bytes is None else int(ds_bytes)), "attn_bwd_rope_ds")
+        return
     _l.check(L.st355_attn_bwd_rope(_stream(), _ptr(Q), _ptr(K), _ptr(v_rows), _rows(v_rows, "v_rows"), _ptr(O), _rows(O, "O"), _ptr(dO), _rows(dO, "dO"),
                                    _ptr(lse2), _ptr(key_bias), _ptr(rrms), _ptr(wq_lo), _ptr(wk_lo), _ptr(wq_hi), _ptr(wk_hi), split, _ptr(cos_p), _ptr(sin_p),
                                    _ptr(dqkv), _rows(dqkv, "dqkv"), B, H, S, Sp, d, scale, _ptr(ws)), "attn_bwd_rope")

@@ -4,6 +4,7 @@
 // second child checks its output against the r01 kernel launched directly) and st355_attn_bwd with and
 // without the pre-transposed Q^T / K^T copies (dkv2 + dq vs dkv3 + dq<TR>), per kernel class through the library's own hipEvent profiler, and checks
 // that the two backward paths agree bit for bit.
+// LAB_DS=1 [LAB_REPS=n]: only the dS-spill section (dkv4, dkv4_ds, dq64, dq_ds per launch at this shape; see there).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast tools/attn_lab.hip -o tools/attn_lab
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -191,6 +192,62 @@ int main(int argc, char** argv) {
     printf("  O, stale-max variant vs product kernel: rel-L2 %.3e, max |d| %.3e  %s\n", sqrt(hd / (hr + 1e-30)), hm, sqrt(hd / (hr + 1e-30)) < 4e-3 ? "within bf16 rounding" : "MISMATCH");
   }
   if (getenv("LAB_FWD_ONLY")) { printf("  (LAB_FWD_ONLY: backward skipped)\n"); return 0; }
+  // ---- LAB_DS=1: the dS-spill backward (dkv4_ds + dq_ds) against the recompute pair (dkv4 + dq64) of the same binary, alternated LAB_REPS times (default 5) so that the
+  // repeat-to-repeat spread of each pair is on the table next to their difference; FNV-1a checksums of dK / dV for both dK/dV bodies (must agree), dQ compared to rounding
+  if (getenv("LAB_DS")) {
+    if (d != 128 || S % 256 != 0) { printf("  (LAB_DS: head_dim 128 and S %% 256 == 0 only)\n"); return 0; }
+    const int reps = getenv("LAB_REPS") ? atoi(getenv("LAB_REPS")) : 5;
+    const size_t dsb = st355_attn_bwd_ds_bytes(B, H, S, Sp, S, d);
+    void* ds; CK(hipMalloc(&ds, dsb));
+    bf16 *dQa, *dKa, *dVa, *dQb, *dKb, *dVb;
+    CK(hipMalloc(&dQa, nh * 2)); CK(hipMalloc(&dKa, nh * 2)); CK(hipMalloc(&dVa, nr * 2)); CK(hipMalloc(&dQb, nh * 2)); CK(hipMalloc(&dKb, nh * 2)); CK(hipMalloc(&dVb, nr * 2));
+    g_attn_dq_impl = 64; g_attn_dkv_impl = 4;
+    double best[2] = {1e30, 1e30}, worst[2] = {0, 0}, sum_dkv[2] = {0, 0}, sum_dq[2] = {0, 0};
+    printf("  %-4s %-18s %12s %12s %12s\n", "rep", "pair", "dkv ms", "dq ms", "pair ms");
+    for (int rep = 0; rep < reps; rep++)
+      for (int mode = 0; mode < 2; mode++) {            // 0: dkv4 + dq64   1: dkv4_ds + dq_ds
+        st355_attn_set_ds(mode);
+        bf16 *dq_ = mode ? dQb : dQa, *dk_ = mode ? dKb : dKa, *dv_ = mode ? dVb : dVa;
+        RC(st355_attn_bwd_ds(st, Q, K, nullptr, nullptr, vrows, 3 * D, O, D, dO, D, lse2, nullptr, dq_, dk_, dv_, D, B, H, S, Sp, d, scale, ws, ds, dsb));
+        CK(hipStreamSynchronize(st));
+        st355_prof_reset(); st355_prof_enable(1);
+        for (int i = 0; i < iters; i++) RC(st355_attn_bwd_ds(st, Q, K, nullptr, nullptr, vrows, 3 * D, O, D, dO, D, lse2, nullptr, dq_, dk_, dv_, D, B, H, S, Sp, d, scale, ws, ds, dsb));
+        CK(hipStreamSynchronize(st));
+        st355_prof_enable(0);
+        double ms[16]; int64_t la[16]; double fl[16], by[16];
+        st355_prof_collect(ms, la, fl, by, 16); st355_prof_reset();
+        const double dkv = ms[3] / la[3], dq = ms[2] / la[2], pair = dkv + dq;
+        printf("  %-4d %-18s %12.4f %12.4f %12.4f\n", rep, mode ? "dkv4_ds + dq_ds" : "dkv4 + dq64", dkv, dq, pair);
+        if (pair < best[mode]) best[mode] = pair;
+        if (pair > worst[mode]) worst[mode] = pair;
+        sum_dkv[mode] += dkv; sum_dq[mode] += dq;
+      }
+    st355_attn_set_ds(-1);
+    for (int mode = 0; mode < 2; mode++)
+      printf("  %-18s mean dkv %.4f  dq %.4f  pair %.4f ms; pair min %.4f max %.4f (spread %.2f %%)\n", mode ? "dkv4_ds + dq_ds" : "dkv4 + dq64", sum_dkv[mode] / reps,
+             sum_dq[mode] / reps, (sum_dkv[mode] + sum_dq[mode]) / reps, best[mode], worst[mode], 100.0 * (worst[mode] - best[mode]) / best[mode]);
+    printf("  spill pair vs recompute pair: worst new %.4f ms, best old %.4f ms -> %s\n", worst[1], best[0], worst[1] < best[0] ? "FASTER beyond the spread" : "not faster beyond the spread");
+    unsigned short* hb = (unsigned short*)malloc(nh * 2 > nr * 2 ? nh * 2 : nr * 2);
+    struct { const char* n; const bf16* p; size_t cnt; } ck[] = {{"dK dkv4   ", dKa, nh}, {"dK dkv4_ds", dKb, nh}, {"dV dkv4   ", dVa, nr}, {"dV dkv4_ds", dVb, nr}};
+    unsigned long long f4[4];
+    for (int c = 0; c < 4; c++) {
+      CK(hipMemcpy(hb, ck[c].p, ck[c].cnt * 2, hipMemcpyDeviceToHost));
+      unsigned long long f = 1469598103934665603ull;
+      for (size_t i = 0; i < ck[c].cnt; i++) f = (f ^ hb[i]) * 1099511628211ull;
+      f4[c] = f;
+      printf("  checksum %s %016llx\n", ck[c].n, f);
+    }
+    printf("  dK / dV, spill body vs default body: %s\n", f4[0] == f4[1] && f4[2] == f4[3] ? "bit-identical" : "MISMATCH");
+    free(hb);
+    float* maxd; double *sd, *sr; CK(hipMalloc(&maxd, 4)); CK(hipMalloc(&sd, 8)); CK(hipMalloc(&sr, 8));
+    CK(hipMemsetAsync(maxd, 0, 4, st)); CK(hipMemsetAsync(sd, 0, 8, st)); CK(hipMemsetAsync(sr, 0, 8, st));
+    k_absdiff<<<2048, 256, 0, st>>>(dQb, dQa, (int64_t)nh, maxd, sd, sr);
+    float hm; double hd, hr;
+    CK(hipMemcpyAsync(&hm, maxd, 4, hipMemcpyDeviceToHost, st)); CK(hipMemcpyAsync(&hd, sd, 8, hipMemcpyDeviceToHost, st)); CK(hipMemcpyAsync(&hr, sr, 8, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    printf("  dQ, dq_ds vs dq64: rel-L2 %.3e, max |d| %.3e  %s\n", sqrt(hd / (hr + 1e-30)), hm, sqrt(hd / (hr + 1e-30)) < 6e-3 ? "within bf16 rounding" : "MISMATCH");
+    return 0;
+  }
   // ---- backward: with the transposed copies (dkv2 + dq) and without (dkv3 + dq<TR>) ----
   bf16* dQ3; CK(hipMalloc(&dQ3, nh * 2)); CK(hipMemsetAsync(dQ3, 0, nh * 2, st));
   if (getenv("LAB_DQ_TRACE")) { CK(hipMalloc(&g_attn_dq_trace, 4 * 128)); CK(hipMemsetAsync(g_attn_dq_trace, 0, 4 * 128, st)); }

@@ -1,6 +1,7 @@
 """kgen.dkv — instruction stream of k_attn_bwd_dkv4 (attention backward, dK / dV; head_dim 128; 8 waves x 32 keys, TWO waves per SIMD, 256 registers per wave).
 
   python -m tools.kgen.dkv        -> simpletuner_amd/csrc/gen/attn_dkv4_body.inc   (the text of one asm statement; see attention_bwd.hip)
+  DKV_DS=1 python -m tools.kgen.dkv   -> .../attn_dkv4_ds_body.inc   (the same stream + the dS^T spill stores for k_attn_bwd_dq_ds; see DS below)
 
 Why a hand-scheduled body at the SAME geometry as k_attn_bwd_dkv3 (64 keys per wave would need 256 accumulator registers + 128 operand registers: no
 budget holds it): dkv3 sits at the 256-register limit, so hipcc consumes its LDS fragments in pairs right behind their requests (sched_barrier pins) and
@@ -59,7 +60,20 @@ T = [10, 11, None, None, 12, 13, 14, 15]     # scratch v10..v15 (T[0], T[1]: DMA
 S_QP, S_GP, S_LP, S_DP = 40, 42, 44, 46      # global bases: Q head, dO head, lse row, delta row (64-bit)
 S_CNT, S_QQ0, S_M0, S_T0, S_T1, S_T2, S_SQ1, S_STQ = 48, 49, 50, 51, 52, 53, 54, 55
 
+S_DS = 56                                    # DKV_DS: the dS spill base of this (b, h) at the current query tile (64-bit, advanced by one 4-KiB block per tile)
+
 CAP = float(os.environ.get("DKV_CAP", "6"))
+# DKV_DS=1 (head_dim 128): the SPILL variant behind k_attn_bwd_dq_ds — after phase B of every 32-query block the packed dS registers (first half of the dP block: per lane two
+# runs of 8 consecutive queries of ONE key) go to global memory (bf16, unscaled) by two 16-byte vector stores woven into C's MFMA gaps.  Layout: FRAGMENT-major — per
+# (b h, 32-key block = wave, 64-query tile) one 4-KiB block [j = 2 qb + m][lane][8 queries], so every store instruction of a wave writes 1 KiB of whole cache lines.
+# (First version: key-major rows dS^T[key][query].  There a store instruction touches 32 rows x 32 bytes; measured at B8 H24 S4608: dK/dV 3.38 -> 4.15 ms, more than
+# the new dQ kernel gives back — profiles/attn_ds_route_ab.md.)  Nothing else changes: dK / dV are bit-identical to the default body.  The stores of a tile's second block stay in flight across the tile barrier (vmcnt counts loads and stores in issue
+# order: the counted wait retires every LDS-DMA of the next tile and leaves DKV_DS_KEEP stores outstanding; 0 = drain).  DKV_DS_NT=1: non-temporal stores.
+DS = os.environ.get("DKV_DS", "0") == "1"
+DS_KEEP = int(os.environ.get("DKV_DS_KEEP", "2"))
+DS_NT = os.environ.get("DKV_DS_NT", "0") == "1"
+assert not DS or HD == 128, "DKV_DS: head_dim 128 only"
+assert 0 <= DS_KEEP <= 2
 DBG = set(filter(None, os.environ.get("DKV_DBG", "").split(",")))
 
 
@@ -145,6 +159,16 @@ def c_groups(slot: int, qb: int, tail: list[list[str]], ph: int = 0) -> list[lis
     return groups
 
 
+def ds_stores(qb: int) -> list:
+    """DKV_DS: dS of query block qb (v[DPACC : DPACC + 7]: queries 32 qb + 16 m + 8 h + 0..7 of the lane's key in registers 4 m .. 4 m + 3) -> piece j = 2 qb + m (1 KiB, lane-linear)
+    of the (wave, query tile)'s 4-KiB block; the base moves on to the next query tile's block behind block 1's second store.  One filler per store: the weaver spreads them over C's gaps."""
+    nt = " nt" if DS_NT else ""
+    out = [[f"global_store_dwordx4 %[dsoff], {vr(DPACC + 4 * m, 4)}, s[{S_DS}:{S_DS + 1}] offset:{1024 * (2 * qb + m)}{nt}"] for m in range(2)]
+    if qb == 1:
+        out[1] += [f"s_add_u32 s{S_DS}, s{S_DS}, 4096", f"s_addc_u32 s{S_DS + 1}, s{S_DS + 1}, 0"]
+    return out
+
+
 def stage_ops(slot: int) -> list:
     """LDS-DMA of tile min(qt + 1, last) into `slot`: this wave's two Q pieces and two dO pieces (rows clamped to Sq - 1), waves 0 / 1 also the lse / delta row.
     S_QQ0 = first query of that tile, S_STQ = the same clamped for the padded statistics rows.  Returned as chunks for the weaver."""
@@ -188,6 +212,8 @@ def build() -> str:
     o(f"s_mov_b64 s[{S_GP}:{S_GP + 1}], %[gbase]")
     o(f"s_mov_b64 s[{S_LP}:{S_LP + 1}], %[lbase]")
     o(f"s_mov_b64 s[{S_DP}:{S_DP + 1}], %[dbase]")
+    if DS:
+        o(f"s_mov_b64 s[{S_DS}:{S_DS + 1}], %[dsbase]")
     o(f"s_sub_u32 s{S_SQ1}, %[sq], 1")
     o(f"s_lshl_b32 s{S_T0}, %[wv], 10")
     o(f"s_add_u32 s{S_T0}, s{S_T0}, %[lds]")                  # LDS address of this wave's first piece inside an image
@@ -231,8 +257,12 @@ def build() -> str:
         o("s_nop 11")
         st.extend(b)
         o("s_nop 1")
-        for g in cg:
-            st.extend(g)
+        if DS:                                                # store m rides behind the MFMAs that consume dS(m) at the earliest (gaps 1 and 3), never in front of B
+            sto = ds_stores(qb)
+            st.extend(weave_budget(cg, [([sto[0]], 1, 4 * NDT - 1), ([sto[1]], 3, 4 * NDT - 1)], CAP))
+        else:
+            for g in cg:
+                st.extend(g)
         if nxt is not None:                                   # the next block's chains start from its statistics: after C's last MFMA has taken P / dS
             st.extend(stat_request(nxt[0], nxt[1]))
 
@@ -250,7 +280,7 @@ def build() -> str:
         else:
             # block 1 must not request from the other slot before the barrier: its C tail carries nothing, the requests follow the barrier
             block(slot, 1, None)
-            o("s_waitcnt vmcnt(0)")
+            o(f"s_waitcnt vmcnt({DS_KEEP if DS else 0})")
             o("s_barrier")
             st.extend(stat_request(slot ^ 1, 0))
             st.extend(row_request(0, slot ^ 1, 0, PHASE[0]))
@@ -324,14 +354,14 @@ def build() -> str:
 
 
 def main() -> None:
-    name = "attn_dkv4_body.inc" if HD == 128 else f"attn_dkv4_hd{HD}_body.inc"
+    name = "attn_dkv4_ds_body.inc" if DS else "attn_dkv4_body.inc" if HD == 128 else f"attn_dkv4_hd{HD}_body.inc"
     out = os.environ.get("DKV_OUT") or os.path.join(os.path.dirname(__file__), "..", "..", "simpletuner_amd", "csrc", "gen", name)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     body = build()
     with open(out, "w") as f:
         f.write("// GENERATED by tools/kgen/dkv.py — do not edit; regenerate with  python -m tools.kgen.dkv\n")
         f.write(body)
-    if not os.environ.get("DKV_OUT") and HD == 128:
+    if not os.environ.get("DKV_OUT") and HD == 128 and not DS:       # (the spill variant owns the same registers: one clobber list)
         regs = [f'"v{i}"' for i in range(10, 128)] + [f'"a{i}"' for i in range(128)] + [f'"s{i}"' for i in range(40, 76)]
         with open(os.path.join(os.path.dirname(out), "attn_dkv4_clobbers.inc"), "w") as f:
             f.write("// GENERATED by tools/kgen/dkv.py — the registers the dkv4 body owns\n")

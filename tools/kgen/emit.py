@@ -6,6 +6,7 @@ statement (cdna_hip_programming.md §5.7), so the generator is responsible for
   * every s_waitcnt (LDS reads: lgkmcnt; LDS-DMA: vmcnt),
   * the gfx950 wait-state rules between dependent instructions (measured from hipcc's own output, /tmp probes of round 4):
         MFMA result -> any reader / overwriter other than the next MFMA accumulating into it ........ >= 12 states
+        VMEM store of more than 8 bytes -> any write of its data registers ............................ >= 2 states
         VALU (or v_accvgpr_write) result -> MFMA A / B / C operand ..................................... >= 2 states
         transcendental (v_exp_f32) result -> its consumer ................................................ >= 1 state
         s_mov m0 -> LDS-DMA .............................................................................. >= 1 state
@@ -104,6 +105,7 @@ def check_hazards(lines: list[str]) -> list[str]:
             reads_ab, reads_c = set(), set()
         else:
             kind, writes, reads, reads_ab, reads_c = "other", set(), set(), set(), set()
+        wide_store = opc in ("global_store_dwordx3", "global_store_dwordx4")     # its data registers (operand 1) are fetched up to two states behind the issue
         # look back
         dist = 0
         for pk, pw, pr, st in reversed(hist):
@@ -123,10 +125,12 @@ def check_hazards(lines: list[str]) -> list[str]:
                 need = 2
             elif pk == "trans" and kind in ("valu", "trans") and pw & reads:
                 need = 1
+            elif pk == "store16" and pw & writes:
+                need = 2
             if need and dist < need:
                 problems.append(f"line {ln}: '{line}' needs {need} states after a {pk} writing {sorted(pw & (reads | writes))[:2]} (has {dist})")
             dist += st
-        hist.append((kind, writes, reads, states(line)))
+        hist.append(("store16", regs_of(ops[1]), reads, states(line)) if wide_store else (kind, writes, reads, states(line)))
         if len(hist) > 40:
             hist.pop(0)
     return problems
