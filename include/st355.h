@@ -543,6 +543,35 @@ int st355_ig_head_bwd(void* stream, const void* xhat, const float* rstd, const v
 int st355_ig_wgrad(void* stream, const float* P, const float* db, const void* gamma, const void* beta, const void* W, int params_bf16, void* g_gamma, void* g_beta,
                    void* g_W, void* g_b, int N, int D, int accumulate);
 
+/* ---- NextLat (helpers/training/nextlat.py): the predictor LayerNorm(D, eps 1e-6) -> Linear(D -> 2D) -> GELU(erf) -> Linear(2D -> D) on rows 0 .. S-2 of one block's
+ * image-token output, against rows 1 .. S-1 (detached) ----
+ * fp32 arithmetic, bf16 only in memory, no atomics, fixed-order reductions (two calls give the same bits).  D % 8 == 0, D <= 4096, 16-byte aligned operands.
+ * params_bf16: the six parameters gamma, beta [D], W_up [2D, D], b_up [2D], W_down [D, 2D], b_down [D] (and their gradients) are bf16 (the full fine-tune's arenas)
+ * instead of fp32 (adapter arena).  The row pass (xhat, rstd) is st355_ig_head_fwd on the view h[:, :S-1]; the GEMMs are st355_gemm_bf16 / st355_gemm_tn_bf16.
+ * st355_nextlat_fold: W1f [2D, D] = bf16(gamma * W_up), W1fT [D, 2D] its transpose, c1 [2D] = bf16(W_up beta + b_up), Wd [D, 2D] = bf16(W_down), WdT [2D, D], bd [D].
+ * st355_gelu_erf_fwd: A = gelu_erf(U) over n bf16 elements (n % 8 == 0);  st355_gelu_erf_bwd: dU = dA * gelu_erf'(U) (dU may be dA).
+ * st355_nextlat_loss: pred [B * rows, D] compact bf16, target a [B, rows, D] view (row stride ld, batch stride bstride, elements).  mode 0: smooth-L1 (beta 1),
+ * mode 1: MSE.  pred is overwritten with psi = d(per-element loss) / d pred (clamp(pred - t, -1, 1) / 2 (pred - t)); *loss = the mean over B * rows * D.
+ * ws: st355_nextlat_loss_workspace(B * rows) bytes.
+ * st355_nextlat_ln_bwd_add: dx (a view like the target) = bf16(float(dx) + s * rstd * (g - mean_D(g) - xhat * mean_D(g * xhat))), g / xhat [B * rows, D] compact bf16,
+ * s = *scale_dev (ONE fp32 on the device).  Rows outside the view are not touched.
+ * st355_nextlat_wgrad_up: P1 [2D, D] bf16 = dU^T xhat, db1 [2D] fp32 = colsum(dU) -> g_W = s (P1 * gamma + db1 beta^T), g_b = s db1,
+ * g_gamma[d] = s sum_n W_up[n, d] P1[n, d], g_beta[d] = s sum_n W_up[n, d] db1[n] (no division by gamma).  ws: st355_nextlat_wgrad_workspace(D) bytes.
+ * st355_nextlat_wgrad_down: P2 [D, 2D] bf16 = psi^T A, db2 [D] fp32 = colsum(psi) -> g_W = s P2, g_b = s db2.
+ * accumulate != 0 adds to what the gradient tensors hold (gradient accumulation). */
+int st355_nextlat_fold(void* stream, const void* gamma, const void* beta, const void* W_up, const void* b_up, const void* W_down, const void* b_down, int params_bf16,
+                       void* W1f, void* W1fT, void* c1, void* Wd, void* WdT, void* bd, int D);
+int st355_gelu_erf_fwd(void* stream, const void* U, void* A, int64_t n);
+int st355_gelu_erf_bwd(void* stream, const void* U, const void* dA, void* dU, int64_t n);
+int64_t st355_nextlat_loss_workspace(int64_t n_rows);
+int st355_nextlat_loss(void* stream, void* pred, const void* target, int B, int rows, int D, int64_t ld, int64_t bstride, int mode, float* loss, void* ws);
+int st355_nextlat_ln_bwd_add(void* stream, const void* g, const void* xhat, const float* rstd, const float* scale_dev, void* dx, int B, int rows, int D, int64_t ld,
+                             int64_t bstride);
+int64_t st355_nextlat_wgrad_workspace(int D);
+int st355_nextlat_wgrad_up(void* stream, const void* P1, const float* db1, const void* gamma, const void* beta, const void* W_up, int params_bf16,
+                           const float* scale_dev, void* g_gamma, void* g_beta, void* g_W, void* g_b, int D, int accumulate, void* ws);
+int st355_nextlat_wgrad_down(void* stream, const void* P2, const float* db2, int params_bf16, const float* scale_dev, void* g_W, void* g_b, int D, int accumulate);
+
 /* LoRA operand packing (K12): from fp32 A[r,K], B[N,r] write the bf16 GEMM operands of ONE adapter into the (zero-initialised)
  * block-structured operands of a fused projection group with K2 padded low-rank columns and N_total outputs:
  *   A_cat   [K2,K]       rows  k2_off..k2_off+r-1      = A

@@ -4,6 +4,7 @@
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
+  * `nextlat_index` / `NextLatHead` / `NextLatTap`: the NextLat predictor's parameters, its forward tap (the state loss) and its backward;
   * `pad64` / `pad64_empty`: operands of the TN weight-gradient GEMM (contraction granule: 64 rows);
   * `ArenaModule`: every base parameter a view of ONE bf16 arena (two-pass construction), checkpoint load / save over the parameter names;
   * `FullGrads`: the per-backward helper of full-rank training — weight / bias gradients into the gradient arena, the modulation rows' reductions, the fused
@@ -295,6 +296,132 @@ def pad64(t):
     return o
 
 
+# ------------------------------------------------------------------------------------------------
+# NextLat (helpers/training/nextlat.py): a predictor LayerNorm(D, eps 1e-6) -> Linear(D -> 2D) -> GELU(erf) -> Linear(2D -> D) of token t + 1 from token t of one
+# block's image-token output
+# ------------------------------------------------------------------------------------------------
+NEXTLAT_NAMES = ("norm.weight", "norm.bias", "up.weight", "up.bias", "down.weight", "down.bias")          # under `nextlat_predictor.`: the reference module's names
+
+
+def nextlat_index(configured, n_blocks: int) -> int:
+    """nextlat.py:103-106 as it is: `int(configured or -1)`, negative = the last block — so None, 0 and -1 all name the last block, and block 0 cannot be chosen"""
+    c = int(configured or -1)
+    i = n_blocks - 1 if c < 0 else c
+    if not 0 <= i < n_blocks:
+        raise ValueError(f"nextlat_block_index must be within [-1, {n_blocks - 1}], got {c}.")
+    return i
+
+
+def nextlat_shapes(D: int):
+    return ((D,), (D,), (2 * D, D), (2 * D,), (D, 2 * D), (D,))
+
+
+@torch.no_grad()
+def nextlat_init_reference(params, D: int, generator=None):
+    """nextlat.py:78-83 on the six tensors (NEXTLAT_NAMES order, any dtype): LayerNorm affine (1, 0), `up` as nn.Linear's default (kaiming_uniform(a = sqrt 5) =
+    U(-1 / sqrt D, 1 / sqrt D) for weight and bias), `down` zero.  The one initialiser of every lay-out (adapter arena, base arena)."""
+    gamma, beta, W_up, b_up, W_down, b_down = params
+    bound = 1.0 / math.sqrt(D)
+    gamma.fill_(1.0); beta.zero_()
+    W_up.uniform_(-bound, bound, generator=generator); b_up.uniform_(-bound, bound, generator=generator)
+    W_down.zero_(); b_down.zero_()
+
+
+class NextLatHead:
+    """The predictor's six trainable tensors as views of the arena that trains (fp32 at the tail of the adapter arena, or bf16 inside the base parameter arena), their
+    gradient views, the [lo, hi) element range of the gradient arena they span, and the folded bf16 operands the GEMMs read (ops.nextlat_fold, once per forward)."""
+
+    def __init__(self, block: int, D: int, params, grads, flat_lo: int, flat_hi: int, device):
+        self.block, self.D = block, D
+        self.gamma, self.beta, self.W_up, self.b_up, self.W_down, self.b_down = params
+        self.g_gamma, self.g_beta, self.g_W_up, self.g_b_up, self.g_W_down, self.g_b_down = grads          # re-pointed by the owner when it switches gradient arenas
+        self.flat_lo, self.flat_hi = flat_lo, flat_hi
+        e = lambda *shp: torch.empty(*shp, dtype=BF16, device=device)
+        self.W1f, self.W1fT, self.c1 = e(2 * D, D), e(D, 2 * D), e(2 * D)
+        self.Wd, self.WdT, self.bd = e(D, 2 * D), e(2 * D, D), e(D)
+
+    @property
+    def params(self):
+        return (self.gamma, self.beta, self.W_up, self.b_up, self.W_down, self.b_down)
+
+    @property
+    def grads(self):
+        return (self.g_gamma, self.g_beta, self.g_W_up, self.g_b_up, self.g_W_down, self.g_b_down)
+
+    def init_reference(self, generator=None):
+        nextlat_init_reference(self.params, self.D, generator)
+
+    def fold(self):
+        ops.nextlat_fold(*self.params, self.W1f, self.W1fT, self.c1, self.Wd, self.WdT, self.bd)
+
+
+class NextLatTap:
+    """One per training forward (kept in its ctx).  `tap(g, view)` after block g of the saving forward — never in the recompute pass of a checkpointed segment — folds
+    the current parameters and runs the predictor on rows 0 .. S-2 of the block's image-token rows [B, S, D] against rows 1 .. S-1 (both read as the views they are):
+    `state_loss` (one fp32 on the device) is the mean smooth-L1 / MSE; xhat, rstd, U, A and psi = d loss / d pred (unscaled) stay for the backward.
+    `backward(d_state, dx_view)` right before block g's own backward fills the six gradient views and adds d loss / d h into rows 0 .. S-2 of the gradient with
+    respect to that block's output (dx_view None: the block lies below the first one that trains, only the predictor's gradients are wanted), then hands the
+    predictor's range to `sync`.  The target rows are detached (nextlat.py:146): nothing flows into them."""
+
+    def __init__(self, head: NextLatHead, mode: str = "smooth_l1"):
+        self.head, self.block, self.mode = head, head.block, mode
+        self.xhat = self.rstd = self.U = self.A = self.psi = self.state_loss = None
+        self.B = self.rows = 0
+
+    def tap(self, g: int, view):
+        if g != self.block:
+            return
+        B, S, D = view.shape
+        if S < 2:
+            raise ValueError("NextLat requires at least two hidden tokens to predict the next latent state.")          # nextlat.py:141-142
+        h, dev = self.head, view.device
+        rows = S - 1
+        M = B * rows
+        self.B, self.rows = B, rows
+        self.xhat, self.rstd = pad64_empty(M, D, dev), torch.empty(M, dtype=F32, device=dev)
+        self.U, self.A, self.psi = torch.empty(M, 2 * D, dtype=BF16, device=dev), pad64_empty(M, 2 * D, dev), pad64_empty(M, D, dev)
+        self.state_loss = torch.empty(1, dtype=F32, device=dev)
+        h.fold()
+        ops.nextlat_rows(view[:, :rows], self.xhat, self.rstd)
+        ops.gemm(self.xhat, h.W1f, bias=h.c1, out=self.U)
+        ops.gelu_erf(self.U, self.A)
+        ops.gemm(self.A, h.Wd, bias=h.bd, out=self.psi)                  # the prediction, overwritten with psi by the loss
+        ops.nextlat_loss(self.psi, view[:, 1:], self.mode, self.state_loss)
+
+    def state(self):
+        if self.state_loss is None:
+            raise RuntimeError(f"NextLat: block {self.block} was never reached by the forward")
+        return self.state_loss.view(())
+
+    def backward(self, d_state, dx_view, accumulate: bool = False, sync=None):
+        h = self.head
+        if d_state is None:                      # the state loss took no part in the loss
+            if not accumulate:
+                for g in h.grads:
+                    g.zero_()
+        else:
+            M, D, dev = self.B * self.rows, h.D, self.psi.device
+            # the chain is linear in psi: ONE device scalar carries the upstream gradient (nextlat_weight, the accumulation division) and the mean's 1 / (M D)
+            s = (d_state.detach().to(device=dev, dtype=F32).reshape(1) * (1.0 / (M * D))).contiguous()
+            dU = pad64_empty(M, 2 * D, dev)
+            ops.gemm(self.psi, h.WdT, out=dU)                             # dA = psi W_down
+            ops.gelu_erf_bwd(self.U, dU, dU)
+            db = torch.empty(3 * D, dtype=F32, device=dev)
+            db2, db1 = db[:D].view(1, D), db[D:].view(1, 2 * D)
+            ops.colsum_prod(self.psi, db2)
+            ops.nextlat_wgrad_down(ops.gemm_tn(pad64(self.psi), pad64(self.A)), db2.view(D), s, h.g_W_down, h.g_b_down, accumulate=accumulate)
+            ops.colsum_prod(dU, db1)
+            ops.nextlat_wgrad_up(ops.gemm_tn(pad64(dU), pad64(self.xhat)), db1.view(2 * D), h.gamma, h.beta, h.W_up, s, h.g_gamma, h.g_beta, h.g_W_up, h.g_b_up,
+                                 accumulate=accumulate)
+            if dx_view is not None:
+                g = torch.empty(M, D, dtype=BF16, device=dev)
+                ops.gemm(dU, h.W1fT, out=g)                               # g = dU W1f
+                ops.nextlat_ln_bwd_add(g, self.xhat, self.rstd, s, dx_view[:, :self.rows])
+        if sync is not None:
+            sync.ready(h.flat_lo, h.flat_hi)
+        self.xhat = self.rstd = self.U = self.A = self.psi = None
+
+
 def sincos_2d_hw(embed_dim: int, h: int, w: int, base_size: int, interpolation_scale: float) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed on a (h, w) grid: [h * w, embed_dim] fp32 (first half from the w coordinate, which varies fastest; sin then cos)"""
     gh = (torch.arange(h, dtype=torch.float32) / (h / base_size) / interpolation_scale).double()
@@ -350,8 +477,8 @@ class ArenaModule(nn.Module):
     def load_flat_state(self, state: Dict[str, torch.Tensor]):
         """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
         own = dict(self.named_parameters())
-        # (an Internal Guidance head is optional in a file: without one it keeps the reference's initial values)
-        missing = [k for k in own if k not in state and ".lora_" not in k and not k.startswith("internal_guidance_head.")]
+        # (an Internal Guidance head / a NextLat predictor is optional in a file: without one it keeps the reference's initial values)
+        missing = [k for k in own if k not in state and ".lora_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor."))]
         if missing:
             raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
         own.update(self._extra_state())

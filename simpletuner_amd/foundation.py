@@ -436,7 +436,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         full fine-tune exposes exactly its arena views; the VAE / ControlNet trunk never carry gradients"""
         if "lora" in str(getattr(self.config, "model_type", "lora")) and self.model is not None:
             for n, p_ in self.unwrap_model(self.model).named_parameters():
-                if ".lora_" not in n and not (n.startswith("internal_guidance_head.") and p_.dtype == torch.float32):      # (the head's fp32 masters train with the adapters)
+                if ".lora_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
                     p_.requires_grad_(False)
         elif str(getattr(self.config, "model_type", "lora")) == "full" and self.model is not None:
             # the reference leaves a full-rank model as diffusers loaded it — every parameter trainable — and `Trainer._get_trainable_parameters` collects
@@ -456,19 +456,65 @@ class ModelFoundation(ExplorativeModelingMixin):
 
     def post_model_load_setup(self):
         """common.py:3638 / 6704 (ImageModelFoundation).  The reference attaches its representation-alignment regularisers here (LayerSync, internal guidance,
-        NextLat, CREPA / U-REPA: hooks into a diffusers module's blocks).  LayerSync is built for the components that expose `set_layersync` (Flux, SD3: it needs
-        nothing outside the model); asking for any other is refused — defined here so that a reference flow calling it never reaches the reference's regulariser
-        initialisers through the MRO."""
-        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled", "nextlat_enabled"):
+        NextLat, CREPA / U-REPA: hooks into a diffusers module's blocks).  The three that need nothing outside the model are built for the components that expose
+        their setter: LayerSync (`set_layersync`: Flux, SD3), Internal Guidance (`set_internal_guidance`: SD3) and NextLat (`set_nextlat`: SD3).  The REPA family
+        needs an external vision encoder and is refused — defined here so that a reference flow calling it never reaches the reference's regulariser initialisers
+        through the MRO."""
+        for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled"):
             if getattr(self.config, flag, False):
-                raise NotImplementedError(f"{flag}: representation-alignment regularisers hook diffusers modules and are not built on the st355 path")
+                raise NotImplementedError(f"{flag}: the REPA regularisers align with an external vision encoder hooked into diffusers modules and are not built on the st355 path")
         self.layersync = None
         if getattr(self.config, "layersync_enabled", False):
             self._layersync_init()
         self.internal_guidance = None
         if getattr(self.config, "internal_guidance_enabled", False):
             self._internal_guidance_init()
+        self.nextlat = None
+        if getattr(self.config, "nextlat_enabled", False):
+            self._nextlat_init()
         return None
+
+    def _nextlat_init(self):
+        """common.py:5197-5220 `_init_nextlat_regularizer` + nextlat.py:95-116: the configuration checks in the reference's order and with its texts, then the
+        trained component is told which block output feeds the predictor (the predictor itself was laid out with the component's arenas)"""
+        cfg = self.config
+        if self.MODEL_TYPE is not ModelTypes.TRANSFORMER:
+            raise ValueError("NextLat is only supported for transformer model families.")
+        if str(getattr(cfg, "lora_type", "standard") or "standard").lower() == "lycoris":
+            raise ValueError("NextLat requires standard PEFT LoRA or full-model training so its predictor is optimized and saved.")
+        comp = self.get_trained_component()
+        if comp is None:
+            raise ValueError("NextLat requires an attached transformer component.")
+        comp = self.unwrap_model(comp)
+        if not hasattr(comp, "set_nextlat"):
+            raise NotImplementedError(f"nextlat_enabled: NextLat is not built for {self.NAME} on the st355 path (built: SD3)")
+        if not (getattr(comp, "lora_groups", None) or getattr(comp, "full", False)):
+            # an ordering requirement of this path, not one of the reference's checks: NextLat is set up once the arena that trains exists (adapters added, or the
+            # full fine-tune enabled); set-up ahead of it is refused by the flag's name, like every configuration this path does not take
+            raise NotImplementedError("nextlat_enabled: post_model_load_setup while the component has no trainable arena yet is not built on the st355 path — add the "
+                                      "LoRA adapters (or enable the full fine-tune) first, then set NextLat up")
+        weight = float(getattr(cfg, "nextlat_weight", None) or 0.0)
+        if weight <= 0:
+            raise ValueError("nextlat_weight must be greater than zero when NextLat is enabled.")
+        from .engine import nextlat_index
+        idx = nextlat_index(getattr(cfg, "nextlat_block_index", None), int(comp.config.num_layers))          # (the rule, the range check and its text live there)
+        state_loss = str(getattr(cfg, "nextlat_state_loss", None) or "smooth_l1")
+        if state_loss not in ("smooth_l1", "mse"):
+            raise ValueError("nextlat_state_loss must be 'smooth_l1' or 'mse'.")
+        kl = float(getattr(cfg, "nextlat_kl_weight", None) or 0.0)
+        if kl < 0:
+            raise ValueError("nextlat_kl_weight must be non-negative.")
+        if kl > 0:          # nextlat.py:171-173: no diffusion family puts a logits head into its model output, so the reference raises this at the first step
+            raise ValueError("nextlat_kl_weight requires model_output['nextlat_logits_head'].")
+        if getattr(cfg, "internal_guidance_enabled", False):
+            raise NotImplementedError("nextlat_enabled together with internal_guidance_enabled is not built on the st355 path (both heads claim the tail of the arena that trains)")
+        tc = getattr(cfg, "tread_config", None)
+        if tc and tc.get("routes", None):
+            raise NotImplementedError("nextlat_enabled with TREAD routing (the routed block's token rows are no longer neighbours in the sequence) is not built on the st355 path")
+        if getattr(getattr(self, "xm_config", None), "enabled", False):
+            raise NotImplementedError("nextlat_enabled with XM noise candidates is not built on the st355 path")
+        comp.set_nextlat(getattr(cfg, "nextlat_block_index", None), state_loss)
+        self.nextlat = SimpleNamespace(weight=weight, block_index=idx, state_loss=state_loss)
 
     def internal_guidance_block_index(self, n_blocks: int) -> int:
         """internal_guidance.py:194-197: `internal_guidance_block_index` as it is (0-based), default max(0, n_blocks // 4)"""
@@ -645,6 +691,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         # (a component whose working layout pads the adapter factors — PixArt's 72 -> 96 head lanes — hands out the true peft shapes itself)
         sd = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in src}
         sd.update(self._internal_guidance_head_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
+        sd.update(self._nextlat_predictor_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         return sd
 
     IG_PREFIX = "internal_guidance_head."          # internal_guidance.py:184 MODULE_NAME; in an adapter file under `transformer.`
@@ -659,6 +706,22 @@ class ModelFoundation(ExplorativeModelingMixin):
         own = dict(comp.named_parameters())
         out = {ModelFoundation.IG_PREFIX + nm: own[ModelFoundation.IG_PREFIX + nm].detach().to(dtype) for nm in ("norm.weight", "norm.bias", "proj.weight", "proj.bias")}
         out[ModelFoundation.IG_PREFIX + "block_index"] = torch.tensor(int(head.block), dtype=torch.int64)
+        return out
+
+    NEXTLAT_PREFIX = "nextlat_predictor."          # nextlat.py:93 MODULE_NAME; in an adapter file under `transformer.`
+
+    @staticmethod
+    def _nextlat_predictor_state(comp, dtype) -> dict:
+        """the NextLat predictor as the reference saves it with the adapter (common.py:924-937 `modules_to_save`; here: its module's state dict under
+        `nextlat_predictor.`, a layout not pinned against peft): the six tensors in the dtype the adapter tensors are saved in and `block_index` as an int64
+        scalar.  Empty when the component trains no predictor with its adapters."""
+        from .engine import NEXTLAT_NAMES
+        head = getattr(comp, "_nl", None)
+        if head is None or not getattr(comp, "lora_groups", None):
+            return {}
+        own = dict(comp.named_parameters())
+        out = {ModelFoundation.NEXTLAT_PREFIX + nm: own[ModelFoundation.NEXTLAT_PREFIX + nm].detach().to(dtype) for nm in NEXTLAT_NAMES}
+        out[ModelFoundation.NEXTLAT_PREFIX + "block_index"] = torch.tensor(int(head.block), dtype=torch.int64)
         return out
 
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = None     # common.py:524; Flux / SD3 / PixArt keep their `transformer.` prefix in ComfyUI files
@@ -683,7 +746,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         """writes `pytorch_lora_weights.safetensors` with diffusers' component prefix (`transformer.` / `unet.`), as the diffusers pipelines'
         save_lora_weights the reference calls (common.py:2072-2120); `layers` = {"<subfolder>_lora_layers": state} or nothing (= the trained
         component).  `config.lora_format == "comfyui"` converts the keys on the way out (ComfyUI / kohya names + one `.alpha` tensor per module); that export
-        DROPS an Internal Guidance head (`internal_guidance_head.*`: ComfyUI has no module to load it into) — keep the diffusers-format file to resume or to sample
+        DROPS an Internal Guidance head / a NextLat predictor (`internal_guidance_head.*`, `nextlat_predictor.*`: ComfyUI has no module to load them into) — keep the diffusers-format file to resume or to sample
         with the head."""
         import os
 
@@ -705,7 +768,7 @@ class ModelFoundation(ExplorativeModelingMixin):
                 flat[f"{prefix}.{k}"] = v.detach().to("cpu").contiguous()
         fmt = normalize_lora_format(getattr(self.config, "lora_format", None))
         if fmt == PEFTLoRAFormat.COMFYUI and not getattr(self, "NATIVE_COMFYUI_LORA_SUPPORT", False):
-            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k}
+            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k}
             flat = self._convert_lora_state_dict_to_comfyui(flat, adapter_metadata=meta or self._lora_adapter_metadata(), component_adapter_metadata=comp_meta)
             flat = {k: v.contiguous() for k, v in flat.items()}
         os.makedirs(output_dir, exist_ok=True)
@@ -761,23 +824,25 @@ class ModelFoundation(ExplorativeModelingMixin):
                 k0 = next(iter(bad))
                 raise ValueError(f"LoRA file alpha {bad[k0]} for {k0} differs from the configured lora_alpha {want}; set lora_alpha to match the file")
         own = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in comp.named_parameters() if ".lora_" in n}
-        # an Internal Guidance head travels with the adapter (diffusers-format files): read back strictly — every head tensor when a head is configured, and a file
-        # that carries one needs a component that has one
-        in_file = sorted(k for k in flat if self.IG_PREFIX in k)
-        head = getattr(comp, "_ig", None)
-        if in_file and (head is None or not getattr(comp, "lora_groups", None)):
-            raise ValueError(f"LoRA checkpoint carries an Internal Guidance head ({in_file[0]}, ...) but none is configured: set internal_guidance_enabled (and the "
-                             "file's internal_guidance_block_index) before loading it")
-        if head is not None and getattr(comp, "lora_groups", None) and fmt != PEFTLoRAFormat.DIFFUSERS:
-            raise ValueError("a ComfyUI-format LoRA file cannot carry the Internal Guidance head (the export drops it): load the diffusers-format file, or turn "
-                             "internal_guidance_enabled off to load the adapters alone")
-        if head is not None and getattr(comp, "lora_groups", None):
-            own.update({n: p for n, p in comp.named_parameters() if n.startswith(self.IG_PREFIX)})
-            bi = flat.get(prefix + self.IG_PREFIX + "block_index")
-            if bi is None:
-                raise KeyError(f"LoRA checkpoint is missing the Internal Guidance head's block index ({prefix}{self.IG_PREFIX}block_index)")
-            if int(bi.item()) != int(head.block):
-                raise ValueError(f"LoRA checkpoint's Internal Guidance head was trained on block {int(bi.item())}, the configured internal_guidance_block_index is {int(head.block)}")
+        # an Internal Guidance head / a NextLat predictor travels with the adapter (diffusers-format files): read back strictly — every tensor of it when one is
+        # configured, and a file that carries one needs a component that has one
+        for pre, attr, a, name, flag, key in ((self.IG_PREFIX, "_ig", "an", "Internal Guidance head", "internal_guidance_enabled", "internal_guidance_block_index"),
+                                              (self.NEXTLAT_PREFIX, "_nl", "a", "NextLat predictor", "nextlat_enabled", "nextlat_block_index")):
+            in_file = sorted(k for k in flat if pre in k)
+            head = getattr(comp, attr, None)
+            if in_file and (head is None or not getattr(comp, "lora_groups", None)):
+                raise ValueError(f"LoRA checkpoint carries {a} {name} ({in_file[0]}, ...) but none is configured: set {flag} (and the "
+                                 f"file's {key}) before loading it")
+            if head is not None and getattr(comp, "lora_groups", None) and fmt != PEFTLoRAFormat.DIFFUSERS:
+                raise ValueError(f"a ComfyUI-format LoRA file cannot carry the {name} (the export drops it): load the diffusers-format file, or turn "
+                                 f"{flag} off to load the adapters alone")
+            if head is not None and getattr(comp, "lora_groups", None):
+                own.update({n: p for n, p in comp.named_parameters() if n.startswith(pre)})
+                bi = flat.get(prefix + pre + "block_index")
+                if bi is None:
+                    raise KeyError(f"LoRA checkpoint is missing the {name}'s block index ({prefix}{pre}block_index)")
+                if int(bi.item()) != int(head.block):
+                    raise ValueError(f"LoRA checkpoint's {name} was trained on block {int(bi.item())}, the configured {key} is {int(head.block)}")
         missing = [k for k in own if prefix + k not in flat]
         if missing:
             raise KeyError(f"LoRA checkpoint is missing {len(missing)} adapter tensors, e.g. {missing[:3]}")
@@ -1244,6 +1309,16 @@ class ModelFoundation(ExplorativeModelingMixin):
             weighted = inter * ig.weight
             loss = loss + weighted
             logs.update(internal_guidance_loss=weighted.detach().item(), internal_guidance_unweighted_loss=inter.detach().item())
+        nl = getattr(self, "nextlat", None)
+        if nl is not None:
+            # common.py:6471-6475 / nextlat.py:134-156, between the Internal Guidance and LayerSync terms (the reference's order): weight * the state loss the
+            # engine's tap left on the device (model_output["nextlat_state_loss"]), the two logs as host floats
+            state = model_output.get("nextlat_state_loss") if isinstance(model_output, dict) else None
+            if state is None:
+                raise ValueError("NextLat is enabled but the model did not return a hidden-state buffer.")
+            nl_loss = state * nl.weight
+            loss = loss + nl_loss
+            logs.update(nextlat_loss=nl_loss.detach().item(), nextlat_state_loss=state.detach().item())
         ls = getattr(self, "layersync", None)
         if ls is not None:
             sim = model_output.get("layersync_similarity") if isinstance(model_output, dict) else None

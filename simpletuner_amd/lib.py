@@ -30,6 +30,8 @@ SYMBOLS = [
     "st355_soap_plan", "st355_soap_step", "st355_soap_eigh",
     "st355_layersync_fwd", "st355_layersync_inject",
     "st355_ig_fold", "st355_ig_head_fwd", "st355_ig_head_bwd", "st355_ig_wgrad",
+    "st355_nextlat_fold", "st355_gelu_erf_fwd", "st355_gelu_erf_bwd", "st355_nextlat_loss_workspace", "st355_nextlat_loss", "st355_nextlat_ln_bwd_add",
+    "st355_nextlat_wgrad_workspace", "st355_nextlat_wgrad_up", "st355_nextlat_wgrad_down",
     "st355_lora_pack",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
@@ -366,6 +368,15 @@ def _declare(lib):
         "st355_ig_head_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
         "st355_ig_head_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64]),
         "st355_ig_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32]),
+        "st355_nextlat_fold": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32]),
+        "st355_gelu_erf_fwd": (C.c_int, [vp, vp, vp, i64]),
+        "st355_gelu_erf_bwd": (C.c_int, [vp, vp, vp, vp, i64]),
+        "st355_nextlat_loss_workspace": (i64, [i64]),
+        "st355_nextlat_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, i64, i64, i32, vp, vp]),
+        "st355_nextlat_ln_bwd_add": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64]),
+        "st355_nextlat_wgrad_workspace": (i64, [i32]),
+        "st355_nextlat_wgrad_up": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
+        "st355_nextlat_wgrad_down": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32]),
         "st355_lora_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),

@@ -1299,6 +1299,193 @@ def ig_wgrad(xhat, dy, gamma, beta, W, g_gamma, g_beta, g_W, g_b, accumulate: bo
     return g_gamma, g_beta, g_W, g_b
 
 
+NEXTLAT_MODES = {"smooth_l1": 0, "mse": 1}          # nextlat.py:147-150 `nextlat_state_loss`
+
+
+def _al16(name: str, *ts):
+    for t in ts:
+        if t.data_ptr() % 16:
+            raise _l.St355Error(f"{name}: operands must be 16-byte aligned (a view that starts off a 16-byte boundary)")
+
+
+def _nextlat_params(name: str, gamma, beta, W_up, b_up, W_down, b_down):
+    """the predictor's six parameters (or their gradients): all fp32 (adapter arena) or all bf16 (full fine-tune arena), contiguous, 16-byte aligned, W_up [2D, D],
+    W_down [D, 2D].  Returns (D, bf16?)"""
+    ts = (gamma, beta, W_up, b_up, W_down, b_down)
+    dt = W_up.dtype
+    if dt not in (F32, BF16) or any(t.dtype != dt for t in ts):
+        raise _l.St355Error(f"{name}: the six predictor tensors must share one dtype, fp32 or bf16")
+    for t in ts:
+        _dev(t, name)
+    if W_up.dim() != 2 or W_up.shape[0] != 2 * W_up.shape[1]:
+        raise _l.St355Error(f"{name}: expected W_up [2D, D], got {tuple(W_up.shape)}")
+    D = W_up.shape[1]
+    if D % 8 or D > 4096:
+        raise _l.St355Error(f"{name}: D must be a multiple of 8, at most 4096 (got {D})")
+    if tuple(W_down.shape) != (D, 2 * D) or gamma.numel() != D or beta.numel() != D or b_up.numel() != 2 * D or b_down.numel() != D \
+            or not all(t.is_contiguous() for t in ts):
+        raise _l.St355Error(f"{name}: expected contiguous gamma [D], beta [D], W_up [2D, D], b_up [2D], W_down [D, 2D], b_down [D] with D = {D}")
+    _al16(name, *ts)
+    return D, int(dt == BF16)
+
+
+def _nextlat_scale(name: str, s):
+    if not torch.is_tensor(s):
+        raise _l.St355Error(f"{name}: the scale is ONE fp32 on the device, not a host number")
+    _chk(s, F32, "scale")
+    if s.numel() != 1:
+        raise _l.St355Error(f"{name}: the scale is ONE fp32 on the device")
+
+
+def nextlat_fold(gamma, beta, W_up, b_up, W_down, b_down, W1f, W1fT, c1, Wd, WdT, bd):
+    """NextLat predictor (st355_nextlat_fold): W1f [2D, D] = bf16(gamma * W_up), W1fT [D, 2D] its transpose, c1 [2D] = bf16(W_up beta + b_up), Wd [D, 2D] =
+    bf16(W_down), WdT [2D, D], bd [D] = bf16(b_down) — the operands of the predictor's four GEMMs, from the current parameters (fp32 or bf16).  Writes into the
+    tensors given."""
+    L = _l.load()
+    D, p16 = _nextlat_params("nextlat_fold", gamma, beta, W_up, b_up, W_down, b_down)
+    outs = (W1f, W1fT, c1, Wd, WdT, bd)
+    for t, nm in zip(outs, ("W1f", "W1fT", "c1", "Wd", "WdT", "bd")):
+        _chk(t, BF16, nm)
+    if tuple(W1f.shape) != (2 * D, D) or tuple(W1fT.shape) != (D, 2 * D) or c1.numel() != 2 * D or tuple(Wd.shape) != (D, 2 * D) or tuple(WdT.shape) != (2 * D, D) \
+            or bd.numel() != D or not all(t.is_contiguous() for t in outs):
+        raise _l.St355Error(f"nextlat_fold: expected contiguous W1f [2D, D], W1fT [D, 2D], c1 [2D], Wd [D, 2D], WdT [2D, D], bd [D] with D = {D}")
+    _al16("nextlat_fold", *outs)
+    _l.check(L.st355_nextlat_fold(_stream(), _ptr(gamma), _ptr(beta), _ptr(W_up), _ptr(b_up), _ptr(W_down), _ptr(b_down), p16, _ptr(W1f), _ptr(W1fT), _ptr(c1),
+                                  _ptr(Wd), _ptr(WdT), _ptr(bd), D), "nextlat_fold")
+    return outs
+
+
+def nextlat_rows(h, xhat, rstd):
+    """the predictor's row pass (st355_ig_head_fwd as it is): h a [B, rows, D] bf16 view (read once, no compact copy) -> xhat [B * rows, D] compact bf16 = LN(h) without
+    affine (centred variance, eps 1e-6), rstd [B * rows] fp32.  D % 64 == 0: xhat feeds the up projection's GEMM."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(h, "h")
+    _chk(xhat, BF16, "xhat"); _chk(rstd, F32, "rstd")
+    M = B * rows
+    if D % 64:
+        raise _l.St355Error(f"nextlat_rows: D must be a multiple of 64, the contraction granule of the up projection's GEMM (got {D}; the row kernel itself takes D % 8 == 0)")
+    if D > 4096 or ld % 8 or bs % 8:
+        raise _l.St355Error(f"nextlat_rows: the view's strides must be multiples of 8 elements, D at most 4096 (got D = {D}, strides {h.stride()})")
+    if tuple(xhat.shape) != (M, D) or not xhat.is_contiguous() or rstd.numel() != M or not rstd.is_contiguous():
+        raise _l.St355Error(f"nextlat_rows: expected contiguous xhat [{M}, {D}], rstd [{M}]")
+    _al16("nextlat_rows", h, xhat)
+    _l.check(L.st355_ig_head_fwd(_stream(), _ptr(h), _ptr(xhat), _ptr(rstd), B, rows, D, ld, bs), "nextlat_rows")
+    return xhat, rstd
+
+
+def _gelu_operands(name: str, *ts):
+    for t in ts:
+        _chk(t, BF16, name)
+    n = ts[0].numel()
+    if n == 0 or n % 8 or any(t.shape != ts[0].shape or not t.is_contiguous() for t in ts):
+        raise _l.St355Error(f"{name}: expected contiguous bf16 tensors of one shape, a multiple of 8 elements")
+    _al16(name, *ts)
+    return n
+
+
+def gelu_erf(U, A):
+    """A = gelu_erf(U) (st355_gelu_erf_fwd; the exact erf form of F.gelu), contiguous bf16, 8 elements per lane.  Writes into A."""
+    L = _l.load()
+    n = _gelu_operands("gelu_erf", U, A)
+    _l.check(L.st355_gelu_erf_fwd(_stream(), _ptr(U), _ptr(A), n), "gelu_erf_fwd")
+    return A
+
+
+def gelu_erf_bwd(U, dA, dU):
+    """dU = dA * gelu_erf'(U) (st355_gelu_erf_bwd); dU may be dA."""
+    L = _l.load()
+    n = _gelu_operands("gelu_erf_bwd", U, dA, dU)
+    _l.check(L.st355_gelu_erf_bwd(_stream(), _ptr(U), _ptr(dA), _ptr(dU), n), "gelu_erf_bwd")
+    return dU
+
+
+def nextlat_loss(pred, target, mode: str, loss):
+    """NextLat state loss (st355_nextlat_loss): pred [B * rows, D] compact bf16, target a [B, rows, D] bf16 view (the block output's rows 1 .. S-1).  mode
+    "smooth_l1" (beta 1) or "mse".  pred is OVERWRITTEN with psi = d(per-element loss) / d pred (clamp(pred - t, -1, 1) / 2 (pred - t)); loss (one fp32) = the mean
+    over B * rows * D, a two-stage fixed-order reduction."""
+    L = _l.load()
+    if mode not in NEXTLAT_MODES:
+        raise _l.St355Error("nextlat_loss: mode must be 'smooth_l1' or 'mse'")
+    B, rows, D, ld, bs = _token_view(target, "target")
+    _chk(pred, BF16, "pred"); _chk(loss, F32, "loss")
+    M = B * rows
+    if D % 8 or D > 4096 or ld % 8 or bs % 8:
+        raise _l.St355Error(f"nextlat_loss: D and the view's strides must be multiples of 8 elements, D at most 4096 (got D = {D}, strides {target.stride()})")
+    if tuple(pred.shape) != (M, D) or not pred.is_contiguous() or loss.numel() != 1:
+        raise _l.St355Error(f"nextlat_loss: expected contiguous pred [{M}, {D}] and one fp32 for the loss")
+    _al16("nextlat_loss", pred, target)
+    ws = _scratch("nextlat_loss", pred.device, L.st355_nextlat_loss_workspace(M))
+    _l.check(L.st355_nextlat_loss(_stream(), _ptr(pred), _ptr(target), B, rows, D, ld, bs, NEXTLAT_MODES[mode], _ptr(loss), _ptr(ws)), "nextlat_loss")
+    return loss
+
+
+def nextlat_ln_bwd_add(g, xhat, rstd, scale, dx):
+    """the predictor's LayerNorm backward into the dX chain (st355_nextlat_ln_bwd_add): dx, a [B, rows, D] bf16 view, = bf16(float(dx) + s * rstd * (g - mean(g) -
+    xhat * mean(g * xhat))); g / xhat [B * rows, D] compact bf16, s ONE fp32 on the device.  Rows outside the view are not touched."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(dx, "dx")
+    _chk(g, BF16, "g"); _chk(xhat, BF16, "xhat"); _chk(rstd, F32, "rstd")
+    _nextlat_scale("nextlat_ln_bwd_add", scale)
+    M = B * rows
+    if D % 8 or D > 4096 or ld % 8 or bs % 8:
+        raise _l.St355Error(f"nextlat_ln_bwd_add: D and the view's strides must be multiples of 8 elements, D at most 4096 (got D = {D}, strides {dx.stride()})")
+    if tuple(g.shape) != (M, D) or tuple(xhat.shape) != (M, D) or rstd.numel() != M or not (g.is_contiguous() and xhat.is_contiguous() and rstd.is_contiguous()):
+        raise _l.St355Error(f"nextlat_ln_bwd_add: expected contiguous g [{M}, {D}], xhat [{M}, {D}], rstd [{M}]")
+    _al16("nextlat_ln_bwd_add", g, xhat, dx)
+    _l.check(L.st355_nextlat_ln_bwd_add(_stream(), _ptr(g), _ptr(xhat), _ptr(rstd), _ptr(scale), _ptr(dx), B, rows, D, ld, bs), "nextlat_ln_bwd_add")
+    return dx
+
+
+def nextlat_wgrad_up(P1, db1, gamma, beta, W_up, scale, g_gamma, g_beta, g_W, g_b, accumulate: bool = False):
+    """gradients of the predictor's LayerNorm affine and up projection (st355_nextlat_wgrad_up) from P1 [2D, D] bf16 = dU^T xhat (gemm_tn) and db1 [2D] fp32 =
+    colsum(dU): g_W = s (P1 * gamma + db1 beta^T), g_b = s db1, g_gamma = s sum_n W_up * P1, g_beta = s sum_n W_up * db1.  Parameters and gradients share one
+    dtype (fp32 or bf16); accumulate adds to what the gradients hold."""
+    L = _l.load()
+    dt = W_up.dtype
+    ts = (gamma, beta, W_up, g_gamma, g_beta, g_W, g_b)
+    if dt not in (F32, BF16) or any(t.dtype != dt for t in ts):
+        raise _l.St355Error("nextlat_wgrad_up: parameters and gradients must share one dtype, fp32 or bf16")
+    _chk(P1, BF16, "P1"); _chk(db1, F32, "db1")
+    _nextlat_scale("nextlat_wgrad_up", scale)
+    for t in ts:
+        _dev(t, "nextlat_wgrad_up")
+    if W_up.dim() != 2 or W_up.shape[0] != 2 * W_up.shape[1]:
+        raise _l.St355Error(f"nextlat_wgrad_up: expected W_up [2D, D], got {tuple(W_up.shape)}")
+    D = W_up.shape[1]
+    if D % 8 or D > 4096:
+        raise _l.St355Error(f"nextlat_wgrad_up: D must be a multiple of 8, at most 4096 (got {D})")
+    if tuple(P1.shape) != (2 * D, D) or db1.numel() != 2 * D or tuple(g_W.shape) != (2 * D, D) or g_b.numel() != 2 * D or any(t.numel() != D for t in (gamma, beta, g_gamma, g_beta)) \
+            or not all(t.is_contiguous() for t in ts + (P1, db1)):
+        raise _l.St355Error(f"nextlat_wgrad_up: expected contiguous P1 [2D, D], db1 [2D] and parameters / gradients in the predictor's shapes with D = {D}")
+    _al16("nextlat_wgrad_up", P1, gamma, beta, W_up, g_W)
+    ws = _scratch("nextlat_wgrad", P1.device, L.st355_nextlat_wgrad_workspace(D))
+    _l.check(L.st355_nextlat_wgrad_up(_stream(), _ptr(P1), _ptr(db1), _ptr(gamma), _ptr(beta), _ptr(W_up), int(dt == BF16), _ptr(scale), _ptr(g_gamma), _ptr(g_beta),
+                                      _ptr(g_W), _ptr(g_b), D, 1 if accumulate else 0, _ptr(ws)), "nextlat_wgrad_up")
+    return g_gamma, g_beta, g_W, g_b
+
+
+def nextlat_wgrad_down(P2, db2, scale, g_W, g_b, accumulate: bool = False):
+    """gradients of the predictor's down projection (st355_nextlat_wgrad_down): g_W [D, 2D] = s P2 (P2 bf16 = psi^T A, gemm_tn), g_b [D] = s db2 (db2 fp32 =
+    colsum(psi)); the gradients fp32 or bf16; accumulate adds to what they hold."""
+    L = _l.load()
+    dt = g_W.dtype
+    if dt not in (F32, BF16) or g_b.dtype != dt:
+        raise _l.St355Error("nextlat_wgrad_down: the gradients must share one dtype, fp32 or bf16")
+    _chk(P2, BF16, "P2"); _chk(db2, F32, "db2"); _dev(g_W, "g_W"); _dev(g_b, "g_b")
+    _nextlat_scale("nextlat_wgrad_down", scale)
+    if g_W.dim() != 2 or g_W.shape[1] != 2 * g_W.shape[0]:
+        raise _l.St355Error(f"nextlat_wgrad_down: expected g_W [D, 2D], got {tuple(g_W.shape)}")
+    D = g_W.shape[0]
+    if D % 8 or D > 4096:
+        raise _l.St355Error(f"nextlat_wgrad_down: D must be a multiple of 8, at most 4096 (got {D})")
+    if tuple(P2.shape) != (D, 2 * D) or db2.numel() != D or g_b.numel() != D or not all(t.is_contiguous() for t in (P2, db2, g_W, g_b)):
+        raise _l.St355Error(f"nextlat_wgrad_down: expected contiguous P2 [D, 2D], db2 [D], g_W [D, 2D], g_b [D] with D = {D}")
+    _al16("nextlat_wgrad_down", P2, db2, g_W, g_b)
+    _l.check(L.st355_nextlat_wgrad_down(_stream(), _ptr(P2), _ptr(db2), int(dt == BF16), _ptr(scale), _ptr(g_W), _ptr(g_b), D, 1 if accumulate else 0),
+             "nextlat_wgrad_down")
+    return g_W, g_b
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

@@ -34,6 +34,9 @@ class SD3(ModelFoundation):
             import inspect
             n_layers = arch.get("num_layers", inspect.signature(SD3Transformer2DModel.__init__).parameters["num_layers"].default)          # (the constructor's own default)
             arch = dict(arch, internal_guidance_block_index=self.internal_guidance_block_index(int(n_layers)))
+        if getattr(self.config, "nextlat_enabled", False) and "nextlat_block_index" not in arch:
+            # NextLat: the predictor is laid out with the component's arenas; the constructor applies the reference's index rule (None / 0 / negative = last block)
+            arch = dict(arch, nextlat_block_index=getattr(self.config, "nextlat_block_index", None) or -1)
         self.model = SD3Transformer2DModel(device=self.accelerator.device, **arch)
         if state_dict is not None:
             self.model.load_flat_state(state_dict)
@@ -69,7 +72,7 @@ class SD3(ModelFoundation):
         )
         # further outputs travel by name; (a component that hands back a plain tuple has only its sample)
         out = {"model_prediction": res[0] if isinstance(res, tuple) else res.sample, "crepa_hidden_states": None, "hidden_states_buffer": None}
-        for k in ("layersync_similarity", "internal_guidance_prediction"):          # LayerSync / Internal Guidance: the training forward's further outputs
+        for k in ("layersync_similarity", "internal_guidance_prediction", "nextlat_state_loss"):          # LayerSync / Internal Guidance / NextLat: the training forward's further outputs
             if getattr(res, k, None) is not None:
                 out[k] = getattr(res, k)
         return out

@@ -24,8 +24,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraGroup, attach, compact, frozen,
-                      internal_guidance_index, internal_guidance_shapes, layersync_indices, pad64_empty, problems, rows_of, sincos_2d_hw)
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraGroup, NextLatHead, NextLatTap,
+                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty,
+                      problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -67,11 +68,17 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                  attention_head_dim: int = 64, num_attention_heads: int = 18, joint_attention_dim: int = 4096,
                  caption_projection_dim: int = 1152, pooled_projection_dim: int = 2048, out_channels: int = 16,
                  pos_embed_max_size: int = 96, dual_attention_layers: Tuple[int, ...] = (), qk_norm: Optional[str] = None,
-                 internal_guidance_block_index: Optional[int] = None, device=None, **_ignored):
+                 internal_guidance_block_index: Optional[int] = None, nextlat_block_index: Optional[int] = None, device=None, **_ignored):
         super().__init__()
         # Internal Guidance (set_internal_guidance): given here, the head's four tensors get their place in the base parameter arena (what a full fine-tune trains)
         self._ig_block = None if internal_guidance_block_index is None else internal_guidance_index(internal_guidance_block_index, num_layers)
         self._ig_arena, self._ig = None, None
+        # NextLat (set_nextlat): given here (the reference's rule: None / 0 / negative = the last block), the predictor's six tensors get their place in the base
+        # parameter arena
+        self._nl_block = None if nextlat_block_index is None else nextlat_index(nextlat_block_index, num_layers)
+        self._nl_arena, self._nl, self._nl_mode, self._nl_loaded = None, None, "smooth_l1", False
+        if self._ig_block is not None and self._nl_block is not None:
+            raise NotImplementedError("Internal Guidance together with NextLat is not built on the st355 path (both heads claim the tail of the arena that trains)")
         if patch_size != 2:
             raise ValueError("patch_size must be 2 (the patchify kernels are 2x2)")
         self.dual_layers = frozenset(int(i) for i in (dual_attention_layers or ()))
@@ -204,6 +211,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 self._reg("internal_guidance_head." + nm, frozen(t))
             if not self._counting:
                 self._ig_arena[0].fill_(1.0)
+        if self._nl_block is not None:         # the NextLat predictor, last in the arena (nextlat.py:78-83: LayerNorm (1, 0), `up` as nn.Linear's default, `down` zero)
+            self._nl_arena = tuple(e(*shp) for shp in nextlat_shapes(D))
+            for nm, t in zip(NEXTLAT_NAMES, self._nl_arena):
+                self._reg("nextlat_predictor." + nm, frozen(t))
+            if not self._counting:
+                self._nextlat_init_arena()
 
 
     # ------------------------------------------------------------------------------------------------
@@ -222,8 +235,22 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if self._ig_arena is not None:         # the head keeps the reference's initial values (registered last: the draws of every other parameter are unchanged)
             for t, v in zip(self._ig_arena, (1.0, 0.0, 0.0, 0.0)):
                 t.fill_(v)
+        if self._nl_arena is not None:         # (registered last as well)
+            self._nextlat_init_arena()
         c = self.config
         self.pos_embed.pos_embed.copy_(sincos_2d(self.D, c.pos_embed_max_size, c.sample_size // c.patch_size)[None].to(self.device_))
+
+    @torch.no_grad()
+    def _nextlat_init_arena(self):
+        """the reference's initial values for the arena's (bf16) predictor, from a generator of its own (the global one is left alone)"""
+        nextlat_init_reference(self._nl_arena, self.D, torch.Generator(device=self.device_).manual_seed(1729))
+        self._nl_loaded = False
+
+    @torch.no_grad()
+    def load_flat_state(self, state):
+        super().load_flat_state(state)
+        if self._nl_arena is not None and any(k.startswith("nextlat_predictor.") for k in state):
+            self._nl_loaded = True                   # add_lora_adapter takes the file's predictor as the masters' start
 
     @torch.no_grad()
     def prepare_for_training(self):
@@ -268,6 +295,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ig_lo = total                             # Internal Guidance: the head's fp32 masters follow the adapters in the same arena (one run for the optimizer)
         if self._ig_block is not None:
             total += sum(math.prod(shp) for shp in internal_guidance_shapes(D))
+        if self._nl_block is not None:            # NextLat: the predictor's fp32 masters likewise, from a 16-byte boundary (its kernels move 8 elements per lane)
+            nl_lo = total = (total + 7) // 8 * 8
+            total += sum(math.prod(shp) for shp in nextlat_shapes(D))
         total = (total + 7) // 8 * 8
         self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
         self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
@@ -305,6 +335,23 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if self._ig_arena is not None:
                 for dst, src in zip(ps, self._ig_arena):
                     dst.copy_(src)                   # a head that came with the loaded weights
+        if self._nl_block is not None:
+            assert off <= nl_lo
+            off = nl_lo
+            ps, gs = [], []
+            for nm, shp in zip(NEXTLAT_NAMES, nextlat_shapes(D)):
+                n = math.prod(shp)
+                pr = nn.Parameter(self.lora_flat[off:off + n].view(shp))
+                attach(self, "nextlat_predictor." + nm, pr)          # (replaces the frozen arena view of the same name, when there is one)
+                ps.append(pr.data); gs.append(self.lora_grad_flat[off:off + n].view(shp))
+                self._lora_params.append(pr)
+                off += n
+            self._nl = NextLatHead(self._nl_block, D, ps, gs, nl_lo, off, dev)
+            if self._nl_arena is not None and self._nl_loaded:
+                for dst, src in zip(ps, self._nl_arena):
+                    dst.copy_(src)                   # a predictor that came with the loaded weights
+            else:
+                self._nl.init_reference(gen)         # the reference's initial values, drawn in fp32 from the adapters' generator
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
@@ -644,6 +691,11 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ig = ctx.ig = InternalGuidanceTap(self._ig_head(), self.out_channels)
         elif want_ig:
             raise ValueError("The transformer does not have an internal_guidance_head.")          # internal_guidance.py:405
+        nl = None
+        if self._nl_block is not None and save:
+            if self._tread_router is not None:
+                raise NotImplementedError("NextLat under TREAD routing (the routed block's token rows are no longer neighbours in the sequence) is not built on the st355 path")
+            nl = ctx.nl = NextLatTap(self._nl_head(), self._nl_mode)
         rp, info, saved, env_cur = 0, None, None, env
         for (s0, n, ck) in ctx.segs:
             for bi in range(s0, s0 + n):
@@ -662,6 +714,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     ls.tap(bi, img.view(B, Si, D))
                 if ig is not None:                            # Internal Guidance: the head on this block's image-stream output (the recompute pass never taps)
                     ig.tap(bi, img.view(B, Si, D))
+                if nl is not None:                            # NextLat: the predictor on this block's image-stream output (the recompute pass never taps)
+                    nl.tap(bi, img.view(B, Si, D))
                 if info is not None and bi == routes[rp]["end_layer_idx"]:
                     full_seq = saved.clone()                                                        # TREADRouter.end_route(original_x=saved)
                     ops.scatter_rows(img.view(B, env_cur.Si, D), info.keep_i32(), full_seq.view(B, Si, D))
@@ -679,6 +733,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 ctx.n_out = n_out
         if ig is not None:
             ctx.ig_pred = ig.prediction(Hh, Ww)
+        if nl is not None:
+            ctx.nl_state = nl.state()
         return ops.unpatchify(out.view(B, Si, -1), self.out_channels, Hh, Ww, order=1), ctx
 
     def set_internal_guidance(self, block_index):
@@ -687,6 +743,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         adapter arena); a full fine-tune needs the constructor's `internal_guidance_block_index` (the head lives inside the base parameter arena, laid out once).
         A training forward then also returns the head's [B, 16, H, W] prediction and the backward takes its gradient at that block."""
         i = internal_guidance_index(block_index, len(self.blocks))
+        if self._nl_block is not None:
+            raise NotImplementedError("Internal Guidance together with NextLat is not built on the st355 path (both heads claim the tail of the arena that trains)")
         if self._ig is not None or self._ig_arena is not None:
             self._ig_block = i                        # the head exists: only the tap moves
             if self._ig is not None:
@@ -696,6 +754,34 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             raise RuntimeError("set_internal_guidance: the trainable arena is already laid out without the head — call it before add_lora_adapter(), or construct the "
                                "model with internal_guidance_block_index")
         self._ig_block = i
+
+    def set_nextlat(self, configured_index=None, state_loss: str = "smooth_l1"):
+        """NextLat (helpers/training/nextlat.py; the reference captures `layer_{i}` at sd3/transformer.py:872): the joint block whose image-stream output feeds the
+        predictor LayerNorm -> Linear(D -> 2D) -> GELU -> Linear(2D -> D), by the reference's rule (`int(configured or -1)`, negative = the last block: None, 0 and -1
+        all name the last block).  Call it before `add_lora_adapter` (the predictor's fp32 masters go to the tail of the adapter arena); a full fine-tune needs the
+        constructor's `nextlat_block_index` (the predictor lives inside the base parameter arena, laid out once).  A training forward then also returns the state
+        loss (mean smooth-L1 / MSE between the prediction from token t and token t + 1) and the backward takes its gradient at that block."""
+        if state_loss not in ops.NEXTLAT_MODES:
+            raise ValueError("nextlat_state_loss must be 'smooth_l1' or 'mse'.")
+        i = nextlat_index(configured_index, len(self.blocks))
+        if self._ig_block is not None:
+            raise NotImplementedError("Internal Guidance together with NextLat is not built on the st355 path (both heads claim the tail of the arena that trains)")
+        self._nl_mode = state_loss
+        if self._nl is not None or self._nl_arena is not None:
+            self._nl_block = i                        # the predictor exists: only the tap moves
+            if self._nl is not None:
+                self._nl.block = i
+            return
+        if self.lora_groups or self.full:
+            raise RuntimeError("set_nextlat: the trainable arena is already laid out without the predictor — call it before add_lora_adapter(), or construct the "
+                               "model with nextlat_block_index")
+        self._nl_block = i
+
+    def _nl_head(self) -> NextLatHead:
+        if self._nl is None:
+            raise RuntimeError("NextLat: no predictor is laid out for training (add_lora_adapter() after set_nextlat(), or enable_full_finetune() on a model "
+                               "constructed with nextlat_block_index)")
+        return self._nl
 
     def _ig_head(self) -> InternalGuidanceHead:
         if self._ig is None:
@@ -721,9 +807,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for bi in range(s0, s0 + n):
             img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, ctx.envs[bi], True)
 
-    def _engine_backward(self, ctx, dout, dsim=None, d_ig=None):
+    def _engine_backward(self, ctx, dout, dsim=None, d_ig=None, d_nl=None):
         """dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the dX chain at the student block's output; d_ig: upstream gradient of the
-        Internal Guidance prediction (set_internal_guidance), taken by the head's backward right before its block's own"""
+        Internal Guidance prediction (set_internal_guidance), taken by the head's backward right before its block's own; d_nl: upstream gradient of the NextLat
+        state loss (set_nextlat), likewise"""
         if not self._prepared:
             raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
         D, H, hd = self.D, self.H, self.hd
@@ -737,7 +824,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], rpb)
         d_txt = None
         del dn, dpk
-        ls, ig = getattr(ctx, "ls", None), getattr(ctx, "ig", None)
+        ls, ig, nl = getattr(ctx, "ls", None), getattr(ctx, "ig", None), getattr(ctx, "nl", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
@@ -745,6 +832,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 ls.inject(d_img.view(B, ctx.Si, D), dsim)
             if ig is not None and li == ig.block:
                 ig.backward(d_ig, d_img.view(B, ctx.Si, D), self.accumulate_lora_grads, self.grad_sync)
+            if nl is not None and li == nl.block:
+                nl.backward(d_nl, d_img.view(B, ctx.Si, D), self.accumulate_lora_grads, self.grad_sync)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -915,6 +1004,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             self._ig = InternalGuidanceHead(self._ig_block, self.D, self._ig_arena, (None,) * 4, lo, self.arena.numel(), self.device_)
             for attr, t in zip(("g_gamma", "g_beta", "g_W", "g_b"), self._ig_arena):
                 gview(self._ig, attr, t)
+        if self._nl_block is not None:                # NextLat: the predictor trains inside the base arena like every other parameter
+            if self._nl_arena is None:
+                raise RuntimeError("NextLat under a full fine-tune: construct the model with nextlat_block_index (the predictor lives inside the base parameter arena, "
+                                   "which is laid out once)")
+            lo = (self._nl_arena[0].data_ptr() - base) // 2
+            self._nl = NextLatHead(self._nl_block, self.D, self._nl_arena, (None,) * 6, lo, self.arena.numel(), self.device_)
+            for attr, t in zip(("g_gamma", "g_beta", "g_W_up", "g_b_up", "g_W_down", "g_b_down"), self._nl_arena):
+                gview(self._nl, attr, t)
         ps = sorted([p for n, p in self.named_parameters() if ".lora_" not in n], key=lambda p: p.data_ptr())
         for p in ps:
             p.requires_grad_(True)
@@ -948,7 +1045,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """training.grad_sync.hand_over_gradients: the arena just filled now belongs to autograd; the next backward takes the other one"""
         self._select_grad_arena(1 - self._grad_sel)
 
-    def _engine_backward_full(self, ctx, dout, dsim=None, d_ig=None):
+    def _engine_backward_full(self, ctx, dout, dsim=None, d_ig=None, d_nl=None):
         D, H, hd = self.D, self.H, self.hd
         B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
         dev = self.device_
@@ -992,7 +1089,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             sync.ready(self._head_arena_lo, self._head_arena_hi)             # proj_out gradients are final (an Internal Guidance head behind it: at its block)
         # the fused modulation matrix (a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
-        ls, ig = getattr(ctx, "ls", None), getattr(ctx, "ig", None)
+        ls, ig, nl = getattr(ctx, "ls", None), getattr(ctx, "ig", None), getattr(ctx, "nl", None)
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
@@ -1000,6 +1097,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 ls.inject(d_img.view(B, ctx.Si, D), dsim)
             if ig is not None and li == ig.block:
                 ig.backward(d_ig, d_img.view(B, ctx.Si, D), False, sync)
+            if nl is not None and li == nl.block:
+                nl.backward(d_nl, d_img.view(B, ctx.Si, D), False, sync)
             if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
                 r_info = ctx.route_end[li]
                 d_full = d_img
@@ -1143,47 +1242,51 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if timestep.ndim not in (1, 2):
             raise ValueError(f"timestep: expected [B] or tokenwise [B, S_img], got {tuple(timestep.shape)}")
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or getattr(self, "full", False))
-        sim = igp = None                                   # LayerSync / Internal Guidance: the training nodes return the similarity / the head's prediction as further outputs
+        sim = igp = nls = None                             # LayerSync / Internal Guidance / NextLat: the training nodes return the similarity / the head's prediction / the state loss as further outputs
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
         if need_grad and getattr(self, "full", False):
             out = _SD3FullFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._full_params)
-            out, sim, igp = _split_outputs(self, out)
+            out, sim, igp, nls = _split_outputs(self, out)
         elif need_grad:
             out = _SD3Fn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._lora_params)
-            out, sim, igp = _split_outputs(self, out)
+            out, sim, igp, nls = _split_outputs(self, out)
         else:
             with torch.no_grad():
                 out, ectx = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False,
                                                  want_ig=bool(return_internal_guidance))
                 igp = getattr(ectx, "ig_pred", None)            # sampling: the intermediate prediction next to the final one
-        extra = {k: v for k, v in (("layersync_similarity", sim), ("internal_guidance_prediction", igp)) if v is not None}
+        extra = {k: v for k, v in (("layersync_similarity", sim), ("internal_guidance_prediction", igp), ("nextlat_state_loss", nls)) if v is not None}
         if not return_dict:
-            return (out,) + tuple(extra.values())               # order: (out, sim, ig_pred)
+            return (out,) + tuple(extra.values())               # order: (out, sim, ig_pred, nextlat_state)
         return SimpleNamespace(sample=out, **extra)
 
 
 def _split_outputs(model, out):
-    """the training nodes' outputs: out, then the LayerSync similarity, then the Internal Guidance prediction, each only when its feature is on"""
+    """the training nodes' outputs: out, then the LayerSync similarity, then the Internal Guidance prediction, then the NextLat state loss, each only when its
+    feature is on"""
     if not isinstance(out, tuple):
-        return out, None, None
+        return out, None, None, None
     rest = list(out[1:])
     sim = rest.pop(0) if model._layersync is not None else None
     igp = rest.pop(0) if model._ig_block is not None else None
-    return out[0], sim, igp
+    nls = rest.pop(0) if model._nl_block is not None else None
+    return out[0], sim, igp, nls
 
 
 def _node_outputs(out, ctx):
-    extra = ([ctx.ls.sim] if getattr(ctx, "ls", None) is not None else []) + ([ctx.ig_pred] if getattr(ctx, "ig", None) is not None else [])
+    extra = ([ctx.ls.sim] if getattr(ctx, "ls", None) is not None else []) + ([ctx.ig_pred] if getattr(ctx, "ig", None) is not None else []) \
+        + ([ctx.nl_state] if getattr(ctx, "nl", None) is not None else [])
     return out if not extra else (out, *extra)
 
 
 def _node_grads(ctx, rest):
-    """(dsim, d_ig) from the gradients of the nodes' further outputs, in _node_outputs' order"""
+    """(dsim, d_ig, d_nl) from the gradients of the nodes' further outputs, in _node_outputs' order"""
     rest = list(rest)
     dsim = rest.pop(0) if getattr(ctx, "ls", None) is not None else None
     d_ig = rest.pop(0) if getattr(ctx, "ig", None) is not None else None
-    return dsim, d_ig
+    d_nl = rest.pop(0) if getattr(ctx, "nl", None) is not None else None
+    return dsim, d_ig, d_nl
 
 
 class _SD3Fn(torch.autograd.Function):

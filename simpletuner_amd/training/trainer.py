@@ -59,7 +59,8 @@ def default_config(**over) -> SimpleNamespace:
                gradient_accumulation_steps=1, train_batch_size=1, gradient_checkpointing=False, input_perturbation=0,
                offset_noise=False, seed=42, lora_init_b_std=0.0, layersync_enabled=False, layersync_student_block=None, layersync_teacher_block=None,
                layersync_lambda=None, internal_guidance_enabled=False, internal_guidance_loss_weight=0.5, internal_guidance_block_index=None,
-               validation_internal_guidance_scale=1.0)
+               validation_internal_guidance_scale=1.0, nextlat_enabled=False, nextlat_weight=None, nextlat_block_index=None, nextlat_state_loss=None,
+               nextlat_kl_weight=None)
     cfg.update(over)
     return SimpleNamespace(**cfg)
 
@@ -111,6 +112,9 @@ class Trainer:
             raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, st355-adamw = torch-adamw semantics)")
         if opt_name in ("muon", "soap") and getattr(config, "internal_guidance_enabled", False):
             raise NotImplementedError(f"optimizer '{opt_name}' with internal_guidance_enabled: the trainable arena then holds the head's 1-D tensors, which the "
+                                      "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
+        if opt_name in ("muon", "soap") and getattr(config, "nextlat_enabled", False):
+            raise NotImplementedError(f"optimizer '{opt_name}' with nextlat_enabled: the trainable arena then holds the predictor's 1-D tensors, which the "
                                       "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
         self._bf16_shadow = None
         if opt_name == "muon":
@@ -192,6 +196,11 @@ class Trainer:
                 raise NotImplementedError("hip_graph: Internal Guidance (internal_guidance_enabled) reads its logs on the host every step and cannot be captured")
             if getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
                 raise NotImplementedError("internal_guidance_enabled with XM noise candidates is not built on the st355 path")
+        if getattr(config, "nextlat_enabled", False):
+            if self._use_graph:
+                raise NotImplementedError("hip_graph: NextLat (nextlat_enabled) reads its logs on the host every step and cannot be captured")
+            if getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
+                raise NotImplementedError("nextlat_enabled with XM noise candidates is not built on the st355 path")
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
