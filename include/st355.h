@@ -581,6 +581,50 @@ int st355_nextlat_wgrad_down(void* stream, const void* P2, const float* db2, int
 int st355_lora_pack(void* stream, const float* A, const float* Bm, int r, int K, int N, float scale,
                     void* A_cat, void* A_cat_T, void* B_blk, void* B_blk_T, int K2, int k2_off, int N_total, int n_off);
 
+/* ---- LoRA dropout (peft `lora_dropout`; csrc/lora_dropout.hip): y = base(x) + (alpha / r) B A dropout(x).  The mask is never stored: a keep bit is a pure
+ * function of (key, call, stream, row, col), regenerated by the forward, every recompute pass and the two gradient kernels.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85); one call = 4 x 32 bits = eight 16-bit lanes
+ *              for the eight consecutive input columns of one row (K % 8 == 0: a group never straddles rows)
+ *   counter    c0, c1 = low / high word of the 64-bit group index (row * K + col) / 8;  c2 = the stream id;  c3 = *call
+ *   key        (key0, key1)
+ *   element    j = col % 8 of a group takes bits [16 (j % 2), 16 (j % 2) + 16) of output word j / 2 and is DROPPED iff that value < threshold
+ *   threshold  T = round(p * 65536), 1 .. 65535: the realised probability is p' = T / 65536;  scale = 1 / (1 - p') in fp32, applied to fp32 accumulators (never
+ *              to x), so dropped elements are exact zeros
+ *   row        the LOGICAL row of the Linear's input, b * rows + s inside its stream — whatever the operand's lay-out: compact (seg_rows = 0), or seg_rows-row
+ *              blocks seg_stride ROWS apart (a [B, rows, C] view of a joint buffer; any seg_rows that divides M).  The same logical problem gives the same bits
+ *   streams[g] the stream id of target g of a group (q / k / v share x but draw independent masks, as peft's per-module nn.Dropout)
+ *   call       ONE uint32 on the device: read through the pointer by every kernel, advanced by st355_lora_dropout_advance (a one-thread launch that belongs
+ *              to the step, so a captured step advances it on the device) */
+typedef struct st355_lora_drop {
+  uint32_t key0, key1;
+  uint32_t threshold;
+  float scale;
+  const uint32_t* call;
+  uint32_t streams[4];
+} st355_lora_drop;
+/* the keep bits of stream streams[0] as uint8 out[M, K] (tests and tools; never on the step) */
+int st355_lora_dropout_mask(void* stream, uint8_t* out, int64_t M, int64_t K, const st355_lora_drop* drop);
+/* *call += 1 */
+int st355_lora_dropout_advance(void* stream, uint32_t* call);
+/* T[m, g r_pad + r] = bf16(scale sum_k keep_g(m,k) x[m,k] A_cat[g r_pad + r, k]) for the G <= 4 targets of a group in ONE pass over x; the columns
+ * [G r_pad, K2) of T are zeroed.  x bf16 (row stride ldx), A_cat [K2, K] bf16 contiguous, T [M, >= K2] bf16 compact (row stride ldt); r_pad 32 / 64 / 128. */
+int st355_lora_down_drop(void* stream, const void* x, int64_t ldx, int64_t seg_rows, int64_t seg_stride, const void* A_cat, void* T, int64_t ldt,
+                         int64_t M, int K, int G, int r_pad, int K2, const st355_lora_drop* drop);
+/* dx[m, k] = bf16(float(dx[m, k]) + scale sum_g keep_g(m,k) sum_r U[m, g r_pad + r] A_cat_T[k, g r_pad + r]) in place.  dx bf16 (row stride ldd, segmented like
+ * x above), U [M, >= K2] bf16 compact (row stride ldu), A_cat_T [K, K2] bf16 contiguous. */
+int st355_lora_dx_drop(void* stream, void* dx, int64_t ldd, int64_t seg_rows, int64_t seg_stride, const void* U, int64_t ldu, const void* A_cat_T,
+                       int64_t M, int K, int G, int r_pad, int K2, const st355_lora_drop* drop);
+/* the masked st355_skinny_tn_seg: out[p*so_p + r*so_r] (+)= alpha scale sum_m keep(m,p) L[m,p] R[m,r] with stream streams[0] (L = the Linear's input x, P = K its
+ * column count).  seg_rows: any divisor of M (seg_l / seg_r in rows; 0 = that operand is compact).  workspace: st355_skinny_tn_workspace(M, P, Rn) bytes. */
+int st355_skinny_tn_drop(void* stream, const void* L, int64_t ldl, const void* R, int64_t ldr, float* out, int64_t so_p, int64_t so_r, int64_t M, int64_t P,
+                         int Rn, int r_used, float alpha, int accumulate, void* workspace, int64_t seg_rows, int64_t seg_l, int64_t seg_r,
+                         const st355_lora_drop* drop);
+/* the masked st355_skinny_tn_multi: column block g of R (32 columns) belongs to target g and sees x under streams[g]; ONE pass over L.
+ * workspace: st355_skinny_tn_workspace(M, P, 128) bytes. */
+int st355_skinny_tn_drop_multi(void* stream, const void* L, int64_t ldl, const void* R, int64_t ldr, float* const* outs, int nout, int64_t so_p, int64_t so_r,
+                               int64_t M, int64_t P, int r_used, float alpha, int accumulate, void* workspace, int64_t seg_rows, int64_t seg_l, int64_t seg_r,
+                               const st355_lora_drop* drop);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

@@ -6,6 +6,8 @@
 // group, lane 4i+s points at 4 contiguous bf16 of tile row i and lane j receives column j of the 4x16 block), so nothing is
 // transposed in memory.  r <= 64 makes this a bandwidth-class op (reads L once).  Deterministic: split-M partials + a
 // fixed-order reduce.  (k_skinny_tn is the first-generation fp32-VALU version, kept for A/B: ST355_SKINNY=1.)
+// lora_dropout.hip holds a masked copy of k_skinny_tn_mfma / k_skinny_reduce_multi (k_skinny_tn_drop / k_drop_reduce: pitches, fragment geometry, chunk rule and
+// reduce order are these): a change to the schedule here belongs there too.
 #include <stdlib.h>
 #include "common.h"
 

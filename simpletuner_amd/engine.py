@@ -1,6 +1,7 @@
 """Host code the engines share (flux/, sd3/, pixart/ transformer.py, unet/unet.py): nothing here knows a model family.
 
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
+  * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
@@ -45,11 +46,44 @@ def frozen(t: torch.Tensor) -> nn.Parameter:
     return nn.Parameter(t, requires_grad=False)
 
 
-class LoraGroup:
-    """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A x."""
+class LoraDropout:
+    """LoRA dropout (peft `lora_dropout`) of one trained component: y = base(x) + (alpha / r) B A dropout(x).  The mask is never stored: a keep bit is a pure
+    function of (key, call, stream, row, col) (st355_lora_drop in include/st355.h) that the forward, every recompute pass and the gradient kernels regenerate.
+      thr     T = round(p * 65536): an element is dropped iff its 16-bit lane < T; the realised probability is p' = T / 65536, the scale 1 / (1 - p')
+      key     (key0, key1) from the run's seed and the data-parallel rank: replicas draw different masks
+      call    ONE int32 on the device, read by the kernels through its pointer.  `advance()` — once per training forward of the component, never per recompute —
+              is a one-thread launch that belongs to the step: a captured step reads and advances the counter on the device, two replays use different masks.
+              A forward uses the value it advanced to, and so does its backward.  `calls` (host) mirrors the eager count for save / resume."""
 
-    def __init__(self, K: int, N_total: int, targets: List[Tuple[str, int, int]], rank: int, alpha: float, device):
+    def __init__(self, p: float, seed: int, rank: int, device, calls: int = 0):
+        self.p = float(p)
+        self.thr = ops.lora_dropout_threshold(p)
+        self.p_real = self.thr / 65536.0
+        seed, rank = int(seed), int(rank)
+        self.key0 = seed & 0xFFFFFFFF
+        self.key1 = ((seed >> 32) ^ (rank * 0x9E3779B9)) & 0xFFFFFFFF
+        self.call = torch.zeros(1, dtype=torch.int32, device=device)
+        self.set_calls(calls)
+
+    def set_calls(self, calls: int):
+        c = int(calls) & 0xFFFFFFFF
+        self.call.fill_(c - (1 << 32) if c >= (1 << 31) else c)           # the kernels read the 32 bits as unsigned
+
+    def calls(self) -> int:
+        return int(self.call.item()) & 0xFFFFFFFF
+
+    def advance(self):
+        ops.lora_dropout_advance(self.call)
+
+
+class LoraGroup:
+    """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A dropout(x): `streams` are the targets' mask
+    stream ids (their index in the component's ordered target list — q / k / v share x but draw independent masks, as peft's per-module nn.Dropout); `down` /
+    `grads` / `dx_add` take the component's LoraDropout state, None = no dropout (eval, p = 0): the unmasked routes."""
+
+    def __init__(self, K: int, N_total: int, targets: List[Tuple[str, int, int]], rank: int, alpha: float, device, streams=None):
         self.K, self.N_total, self.targets = K, N_total, targets
+        self.streams = list(range(len(targets))) if streams is None else list(streams)
         self.rank, self.scale = rank, alpha / rank
         # adapter columns inside the K-extension: 32 / 64 (one pass of the rank-space kernels), above 64 a multiple of 64 walked in 64-column slabs
         # (the reference's sd3.peft-lora example trains rank 128)
@@ -70,9 +104,31 @@ class LoraGroup:
             ops.lora_pack(self.A[g], self.B[g], self.scale, self.A_cat, self.A_cat_T, self.B_blk, self.B_blk_T,
                           k2_off=g * self.r_pad, n_off=n_off)
 
-    def grads(self, x, T, dy, U, accumulate: bool, sync=None):
+    def down(self, x, drop=None, out=None):
+        """T = x A_cat^T [M, K2] bf16 — under dropout T_g = scale (keep_g . x) A_g^T for every target in one pass over x.  x: compact [M, K] or a [B, rows, K]
+        view of a joint buffer (the mask follows the logical row b * rows + s either way)."""
+        if drop is None:
+            return ops.gemm(x, self.A_cat) if out is None else ops.gemm(x, self.A_cat, out=out)
+        self._drop_check()
+        return ops.lora_down_drop(x, self.A_cat, self.r_pad, self.streams, drop, out=out)
+
+    def dx_add(self, dx, U, drop):
+        """dx += scale sum_g keep_g . (U_g A_g): the adapter term of the projection's input gradient under dropout (the mask sits between U and A, so the term
+        cannot ride the K-extension of the dx GEMM); in place, before anything consumes dx"""
+        self._drop_check()
+        return ops.lora_dx_drop(dx, U, self.A_cat_T, self.r_pad, self.streams, drop)
+
+    def _drop_check(self):
+        if self.K % 8 or len(self.targets) > 4 or self.r_pad > 128:
+            raise NotImplementedError(f"lora_dropout: the adapters of {self.targets[0][0]} (in_features {self.K}, {len(self.targets)} targets, rank {self.rank}) are "
+                                      "outside the masked kernels (in_features % 8 == 0, at most 4 targets per input, rank <= 128); set --lora_dropout=0")
+
+    def grads(self, x, T, dy, U, accumulate: bool, sync=None, drop=None):
         """dB_g = s * dy_g^T T_g ; dA_g = U_g^T x   (rank-space backward: both products are [*, r]).  x: the projection's input, or — an input that only
-        exists as K segments (the single block's proj_out reads [attn | mlp] as a two-segment K loop) — a list of (segment, first input column)."""
+        exists as K segments (the single block's proj_out reads [attn | mlp] as a two-segment K loop) — a list of (segment, first input column).
+        drop: dA_g = scale U_g^T (keep_g . x) (T already carries the mask, dB is unchanged)."""
+        if drop is not None:
+            return self._grads_drop(x, T, dy, U, accumulate, sync, drop)
         segs = x if isinstance(x, (list, tuple)) else [(x, 0)]
         multi = len(segs) == 1 and 1 < len(self.targets) <= 4 and self.r_pad == 32 and U.shape[1] >= 128   # q / k / v share x: dA of all three in ONE pass over x
         cw = min(self.r_pad, 64)                                 # rank-space kernels take 32 or 64 adapter columns per pass
@@ -85,6 +141,23 @@ class LoraGroup:
                         ops.skinny_tn(xs, U[:, c0:c0 + cw], self.gA[g][s0:, k0:], 1, self.K, r_used, alpha=1.0, accumulate=accumulate)
         if multi:
             ops.skinny_tn_multi(x, U, self.gA, 1, self.K, self.rank, alpha=1.0, accumulate=accumulate)
+        if sync is not None:
+            sync.ready(self.flat_lo, self.flat_hi)
+
+    def _grads_drop(self, x, T, dy, U, accumulate: bool, sync, drop):
+        if isinstance(x, (list, tuple)):
+            raise NotImplementedError("lora_dropout: an input that only exists as K segments needs the logical column offset in the mask (not built)")
+        self._drop_check()
+        multi = 1 < len(self.targets) <= 4 and self.r_pad == 32 and U.shape[1] >= 128            # q / k / v share x: dA of all three in ONE pass over x
+        cw = min(self.r_pad, 64)
+        for g, (_, n_off, N) in enumerate(self.targets):
+            for s0 in range(0, self.rank, cw):
+                c0, r_used = g * self.r_pad + s0, min(cw, self.rank - s0)
+                ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], self.gB[g][:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=accumulate)
+                if not multi:
+                    ops.skinny_tn_drop(x, U[:, c0:c0 + cw], self.gA[g][s0:], 1, self.K, r_used, self.streams[g], drop, accumulate=accumulate)
+        if multi:
+            ops.skinny_tn_drop_multi(x, U, self.gA, 1, self.K, self.rank, self.streams, drop, accumulate=accumulate)
         if sync is not None:
             sync.ready(self.flat_lo, self.flat_hi)
 

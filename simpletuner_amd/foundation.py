@@ -474,6 +474,22 @@ class ModelFoundation(ExplorativeModelingMixin):
             self._nextlat_init()
         return None
 
+    LORA_DROPOUT_BUILT = False          # families whose engine draws the LoRA-dropout masks (SD3)
+
+    def lora_dropout_value(self) -> float:
+        """`lora_dropout` (the reference builds every standard LoRA with LoraConfig(lora_dropout=...): common.py:1094-1104) as the family's add_lora_adapter takes
+        it: 0.0 when absent; a full fine-tune and lora_type=lycoris ignore the flag, as the reference does; a standard LoRA of a family without the masked kernels
+        refuses a positive value by name — never a silently different computation."""
+        cfg = self.config
+        p = float(getattr(cfg, "lora_dropout", 0.0) or 0.0)
+        if "lora" not in str(getattr(cfg, "model_type", "lora")) or str(getattr(cfg, "lora_type", "standard") or "standard").lower() != "standard":
+            return 0.0
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"lora_dropout must lie in [0, 1), got {p}")
+        if p > 0.0 and not self.LORA_DROPOUT_BUILT:
+            raise NotImplementedError(f"lora_dropout={p}: LoRA dropout is not built for {self.NAME} on the st355 path (built: SD3); set --lora_dropout=0")
+        return p
+
     def _nextlat_init(self):
         """common.py:5197-5220 `_init_nextlat_regularizer` + nextlat.py:95-116: the configuration checks in the reference's order and with its texts, then the
         trained component is told which block output feeds the predictor (the predictor itself was laid out with the component's arenas)"""

@@ -33,6 +33,7 @@ SYMBOLS = [
     "st355_nextlat_fold", "st355_gelu_erf_fwd", "st355_gelu_erf_bwd", "st355_nextlat_loss_workspace", "st355_nextlat_loss", "st355_nextlat_ln_bwd_add",
     "st355_nextlat_wgrad_workspace", "st355_nextlat_wgrad_up", "st355_nextlat_wgrad_down",
     "st355_lora_pack",
+    "st355_lora_dropout_mask", "st355_lora_dropout_advance", "st355_lora_down_drop", "st355_lora_dx_drop", "st355_skinny_tn_drop", "st355_skinny_tn_drop_multi",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
     # UNet path (SDXL / SD1.5)
@@ -57,6 +58,11 @@ class St355Unavailable(RuntimeError):
 
 class St355Error(RuntimeError):
     pass
+
+
+class LoraDrop(C.Structure):
+    """st355_lora_drop (include/st355.h): the Philox key, the threshold, the scale, the device-resident call counter and the targets' stream ids"""
+    _fields_ = [("key0", C.c_uint32), ("key1", C.c_uint32), ("threshold", C.c_uint32), ("scale", C.c_float), ("call", C.c_void_p), ("streams", C.c_uint32 * 4)]
 
 
 class QkRope(C.Structure):
@@ -378,6 +384,12 @@ def _declare(lib):
         "st355_nextlat_wgrad_up": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
         "st355_nextlat_wgrad_down": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32]),
         "st355_lora_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32]),
+        "st355_lora_dropout_mask": (C.c_int, [vp, vp, i64, i64, C.POINTER(LoraDrop)]),
+        "st355_lora_dropout_advance": (C.c_int, [vp, vp]),
+        "st355_lora_down_drop": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(LoraDrop)]),
+        "st355_lora_dx_drop": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, i32, i32, i32, i32, C.POINTER(LoraDrop)]),
+        "st355_skinny_tn_drop": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, i32, f32, i32, vp, i64, i64, i64, C.POINTER(LoraDrop)]),
+        "st355_skinny_tn_drop_multi": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, i64, i64, i64, i64, i32, f32, i32, vp, i64, i64, i64, C.POINTER(LoraDrop)]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),
         "st355_comm_init": (C.c_int, [vp, vp, i32, i32]),

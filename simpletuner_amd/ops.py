@@ -767,6 +767,139 @@ def skinny_tn_multi(Lm, R, outs, so_p: int, so_r: int, r_used: int, alpha: float
 
 
 # ------------------------------------------------------------------------------------------------
+# LoRA dropout (csrc/lora_dropout.hip; st355_lora_drop in include/st355.h): the mask is regenerated from (key, call, stream, row, col), never stored
+# ------------------------------------------------------------------------------------------------
+def lora_dropout_threshold(p: float) -> int:
+    """T = round(p * 65536): an element is dropped iff its 16-bit lane < T, so the realised probability is p' = T / 65536 (0 < p < 1 is built)"""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"lora_dropout must lie in [0, 1), got {p}")
+    T = int(round(p * 65536.0))
+    if not 1 <= T <= 65535:
+        raise ValueError(f"lora_dropout={p} rounds to the threshold {T} / 65536: outside the 16-bit lanes of the mask generator")
+    return T
+
+
+def _drop_struct(drop, streams, name: str):
+    """`drop`: the component's dropout state — .thr (lora_dropout_threshold), .key0 / .key1 (32-bit words of the Philox key), .call (ONE int32 on the device, read
+    as uint32).  streams: the stream ids of the 1 .. 4 targets."""
+    if not 1 <= len(streams) <= 4:
+        raise _l.St355Error(f"{name}: 1 .. 4 targets share one input (got {len(streams)})")
+    call = drop.call
+    _chk(call, torch.int32, "call")
+    if call.numel() != 1:
+        raise _l.St355Error(f"{name}: the call counter is ONE int32 on the device")
+    st = _l.LoraDrop()
+    st.key0, st.key1, st.threshold = int(drop.key0) & 0xFFFFFFFF, int(drop.key1) & 0xFFFFFFFF, int(drop.thr)
+    st.scale = 1.0 / (1.0 - int(drop.thr) / 65536.0)
+    st.call = call.data_ptr()
+    for i in range(4):
+        st.streams[i] = int(streams[min(i, len(streams) - 1)]) & 0xFFFFFFFF
+    return st
+
+
+def _drop_rows(t, name: str):
+    """(M, cols, ld, seg_rows, seg_stride_rows) of a masked operand: 2-D row-major or a [B, rows, C] view (_seg); K % 8 and 16-byte rows are what one Philox
+    group per 16-byte chunk needs"""
+    M, K, ld, seg, seg_s = _seg(t, name)
+    if K % 8 or ld % 8 or t.data_ptr() % 16:
+        raise _l.St355Error(f"{name}: LoRA dropout needs K % 8 == 0 and 16-byte aligned rows (the mask is drawn per group of 8 input columns; got K = {K}, "
+                            f"row stride {ld})")
+    return M, K, ld, seg, seg_s
+
+
+def lora_dropout_advance(call):
+    """*call += 1: a one-thread launch that belongs to the step (a captured step advances the counter on the device)"""
+    _chk(call, torch.int32, "call")
+    _l.check(_l.load().st355_lora_dropout_advance(_stream(), _ptr(call)), "lora_dropout_advance")
+    return call
+
+
+def lora_dropout_mask(M: int, K: int, drop, stream: int):
+    """the keep bits of (key, call, stream) over an [M, K] input as uint8 (tests and tools; never on the step)"""
+    if K % 8 or M <= 0:
+        raise _l.St355Error(f"lora_dropout_mask: K must be a multiple of 8 (got {K})")
+    out = torch.empty(M, K, dtype=torch.uint8, device=drop.call.device)
+    st = _drop_struct(drop, [stream], "lora_dropout_mask")
+    _l.check(_l.load().st355_lora_dropout_mask(_stream(), _ptr(out), M, K, C.byref(st)), "lora_dropout_mask")
+    return out
+
+
+def lora_down_drop(x, A_cat, r_pad: int, streams, drop, out=None):
+    """T[m, g r_pad + r] = scale sum_k keep_g(m,k) x[m,k] A_cat[g r_pad + r, k] for the len(streams) targets of a group in ONE pass over x (bf16 T [M, K2], one
+    rounding; the K-extension consumes it as it does the unmasked product)"""
+    _chk(x, BF16, "x"); _chk(A_cat, BF16, "A_cat")
+    M, K, ldx, seg, seg_s = _drop_rows(x, "lora_down_drop: x")
+    K2 = A_cat.shape[0]
+    if A_cat.dim() != 2 or A_cat.shape[1] != K or not A_cat.is_contiguous():
+        raise _l.St355Error(f"lora_down_drop: expected contiguous A_cat [K2, {K}], got {tuple(A_cat.shape)}")
+    if r_pad not in (32, 64, 128) or len(streams) * r_pad > K2:
+        raise _l.St355Error(f"lora_down_drop: r_pad must be 32, 64 or 128 and the targets' columns fit K2 (got r_pad {r_pad}, {len(streams)} targets, K2 {K2})")
+    if out is None:
+        out = torch.empty(M, K2, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    if tuple(out.shape) != (M, K2):
+        raise _l.St355Error(f"lora_down_drop: expected out [{M}, {K2}], got {tuple(out.shape)}")
+    st = _drop_struct(drop, streams, "lora_down_drop")
+    _l.check(_l.load().st355_lora_down_drop(_stream(), _ptr(x), ldx, seg, seg_s, _ptr(A_cat), _ptr(out), _rows(out, "out"), M, K, len(streams), r_pad, K2,
+                                            C.byref(st)), "lora_down_drop")
+    return out
+
+
+def lora_dx_drop(dx, U, A_cat_T, r_pad: int, streams, drop):
+    """dx[m, k] += scale sum_g keep_g(m,k) sum_r U[m, g r_pad + r] A_cat_T[k, g r_pad + r], in place into a bf16 tensor or [B, rows, C] view (one rounding): the
+    adapter term of a projection's input gradient, which the mask keeps off the K-extension of the dx GEMM"""
+    _chk(dx, BF16, "dx"); _chk(U, BF16, "U"); _chk(A_cat_T, BF16, "A_cat_T")
+    M, K, ldd, seg, seg_s = _drop_rows(dx, "lora_dx_drop: dx")
+    K2 = A_cat_T.shape[1]
+    if A_cat_T.dim() != 2 or A_cat_T.shape[0] != K or not A_cat_T.is_contiguous():
+        raise _l.St355Error(f"lora_dx_drop: expected contiguous A_cat_T [{K}, K2], got {tuple(A_cat_T.shape)}")
+    if U.dim() != 2 or tuple(U.shape) != (M, K2) or U.data_ptr() % 16:
+        raise _l.St355Error(f"lora_dx_drop: expected U [{M}, {K2}], got {tuple(U.shape)}")
+    if r_pad not in (32, 64, 128) or len(streams) * r_pad > K2:
+        raise _l.St355Error(f"lora_dx_drop: r_pad must be 32, 64 or 128 and the targets' columns fit K2 (got r_pad {r_pad}, {len(streams)} targets, K2 {K2})")
+    st = _drop_struct(drop, streams, "lora_dx_drop")
+    _l.check(_l.load().st355_lora_dx_drop(_stream(), _ptr(dx), ldd, seg, seg_s, _ptr(U), _rows(U, "U"), _ptr(A_cat_T), M, K, len(streams), r_pad, K2, C.byref(st)),
+             "lora_dx_drop")
+    return dx
+
+
+def skinny_tn_drop(Lm, R, out, so_p: int, so_r: int, r_used: int, stream: int, drop, alpha: float = 1.0, accumulate: bool = False):
+    """skinny_tn with the LoRA-dropout mask of `stream` on Lm (the Linear's input): out[p*so_p + r*so_r] (+)= alpha scale sum_m keep(m,p) Lm[m,p] R[m,r]"""
+    L = _l.load()
+    _chk(Lm, BF16, "L"); _chk(R, BF16, "R"); _chk(out, F32, "out")
+    M, P, ldl, seg, seg_l = _drop_rows(Lm, "skinny_tn_drop: L")
+    Mr, Rn, ldr, sr, seg_r = _seg(R, "R")
+    if Mr != M:
+        raise _l.St355Error(f"skinny_tn_drop: L has {M} rows, R has {Mr}")
+    seg = _seg_join(seg, sr, "skinny_tn_drop")
+    ws = _skinny_scratch(Lm.device, M, P, Rn)
+    st = _drop_struct(drop, [stream], "skinny_tn_drop")
+    _l.check(L.st355_skinny_tn_drop(_stream(), _ptr(Lm), ldl, _ptr(R), ldr, _ptr(out), so_p, so_r, M, P, Rn, r_used, alpha, 1 if accumulate else 0, _ptr(ws),
+                                    seg, seg_l, seg_r, C.byref(st)), "skinny_tn_drop")
+    return out
+
+
+def skinny_tn_drop_multi(Lm, R, outs, so_p: int, so_r: int, r_used: int, streams, drop, alpha: float = 1.0, accumulate: bool = False):
+    """skinny_tn_multi with target g's mask (streams[g]) on Lm for column block g of R: the q / k / v adapters' dA in ONE pass over Lm"""
+    L = _l.load()
+    _chk(Lm, BF16, "L"); _chk(R, BF16, "R")
+    M, P, ldl, seg, seg_l = _drop_rows(Lm, "skinny_tn_drop_multi: L")
+    Mr, Rn, ldr, sr, seg_r = _seg(R, "R")
+    if Mr != M or Rn < 128 or not (1 <= len(outs) <= 4) or len(streams) != len(outs):
+        raise _l.St355Error(f"skinny_tn_drop_multi: L has {M} rows, R {Mr} x {Rn} (needs 128 columns), {len(outs)} outputs (1..4), {len(streams)} streams")
+    seg = _seg_join(seg, sr, "skinny_tn_drop_multi")
+    for o in outs:
+        _chk(o, F32, "out")
+    ws = _skinny_scratch(Lm.device, M, P, 128)
+    arr = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    st = _drop_struct(drop, streams, "skinny_tn_drop_multi")
+    _l.check(L.st355_skinny_tn_drop_multi(_stream(), _ptr(Lm), ldl, _ptr(R), ldr, arr, len(outs), so_p, so_r, M, P, r_used, alpha, 1 if accumulate else 0,
+                                          _ptr(ws), seg, seg_l, seg_r, C.byref(st)), "skinny_tn_drop_multi")
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------
 # AdaLN / RMSNorm + RoPE
 # ------------------------------------------------------------------------------------------------
 def ln_modulate_fwd(x, scale, shift, rows_per_batch: int, eps: float = 1e-6, out=None):

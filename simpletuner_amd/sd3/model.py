@@ -21,6 +21,7 @@ class SD3(ModelFoundation):
     MODEL_TYPE = ModelTypes.TRANSFORMER
     MODEL_CLASS = SD3Transformer2DModel
     MODEL_SUBFOLDER = "transformer"
+    LORA_DROPOUT_BUILT = True
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
     VAE_CONFIG = dict(latent_channels=16, scaling_factor=1.5305, shift_factor=0.0609, use_quant_conv=False)
@@ -50,7 +51,9 @@ class SD3(ModelFoundation):
         comp = self.unwrap_model(self.model)
         params = comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),
                                        targets="default", seed=int(getattr(self.config, "seed", 42) or 42) + 7,
-                                       init_b_std=float(getattr(self.config, "lora_init_b_std", 0.0)))
+                                       init_b_std=float(getattr(self.config, "lora_init_b_std", 0.0)),
+                                       dropout=self.lora_dropout_value(), dropout_seed=int(getattr(self.config, "seed", 42) or 42),
+                                       dropout_rank=int(getattr(self.accelerator, "process_index", 0) or 0))
         comp.prepare_for_training()
         return params
 

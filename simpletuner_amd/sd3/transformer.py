@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraGroup, NextLatHead, NextLatTap,
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
                       attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty,
                       problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
@@ -110,6 +110,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.pos_embed.register_buffer("pos_embed", torch.zeros(1, pos_embed_max_size * pos_embed_max_size, D, dtype=F32, device=dev))
 
         self.lora_groups: List[LoraGroup] = []
+        self.lora_dropout: Optional[LoraDropout] = None          # add_lora_adapter(dropout > 0): applies to training forwards only
         self.lora_flat: Optional[torch.Tensor] = None
         self.lora_grad_flat: Optional[torch.Tensor] = None
         self._lora_params: List[nn.Parameter] = []
@@ -265,15 +266,22 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     # ------------------------------------------------------------------------------------------------
     # LoRA (peft naming), sd3/model.py:122 DEFAULT_LORA_TARGET = to_k,to_q,to_v,to_out.0
     # ------------------------------------------------------------------------------------------------
-    def add_lora_adapter(self, rank: int = 32, alpha: Optional[float] = None, targets: str = "default", seed: int = 7, init_b_std: float = 0.0):
+    def add_lora_adapter(self, rank: int = 32, alpha: Optional[float] = None, targets: str = "default", seed: int = 7, init_b_std: float = 0.0,
+                         dropout: float = 0.0, dropout_seed: int = 0, dropout_rank: int = 0, dropout_calls: int = 0):
+        """dropout: peft's `lora_dropout` (0 <= p < 1) — y = base(x) + (alpha / r) B A dropout(x) in training forwards, every adapted Linear with its own mask stream
+        (its index in the ordered target list below); dropout_seed / dropout_rank make the mask key, dropout_calls is the call counter's start (engine.LoraDropout)"""
         alpha = float(rank if alpha is None else alpha)
+        dropout = float(dropout or 0.0)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"lora_dropout must lie in [0, 1), got {dropout}")
         D, dev = self.D, self.device_
         plan = []
         self.lora_groups = []
+        self.lora_dropout = LoraDropout(dropout, dropout_seed, dropout_rank, dev, dropout_calls) if dropout > 0.0 else None
 
         def group(lin, prefix, names, K):
             g = LoraGroup(K, lin.w.shape[0], [(prefix + n, j * (lin.w.shape[0] // len(names)), lin.w.shape[0] // len(names))
-                                              for j, n in enumerate(names)], rank, alpha, dev)
+                                              for j, n in enumerate(names)], rank, alpha, dev, streams=range(len(plan), len(plan) + len(names)))
             lin.lora = g
             self.lora_groups.append(g)
             for (name, n_off, N) in g.targets:
@@ -379,7 +387,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         B, Si, St, S, Sp, cos, sin, mod, scale, full = env.B, env.Si, env.St, env.S, env.Sp, env.cos, env.sin, env.mod, env.scale, env.full
         ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         rpb = 1 if env.rpb_i == 1 else Si     # rows of the image stream that share one modulation row: the sample's (inside a TREAD route: its kept) rows, or 1 under tokenwise timesteps
-        if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and img.is_contiguous() and txt.is_contiguous() and rpb == Si:
+        drop = getattr(env, "drop", None)      # LoRA dropout of this training forward (and of its recompute passes): the adapters' down projections draw masks
+        if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and img.is_contiguous() and txt.is_contiguous() and rpb == Si and drop is None:
             return self._block_fwd_c(blk, img, txt, env, save, ybuf)
 
         mi = env.mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
@@ -391,8 +400,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mt = mod[:, blk.mod_off_c:blk.mod_off_c + 6 * D]
             n_txt = ops.ln_modulate_fwd(txt, mt[:, D:2 * D], mt[:, :D], St)
         qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
-        T_img = ops.gemm(n_img, blk.qkv.lora.A_cat) if blk.qkv.lora is not None else None
-        T_txt = ops.gemm(n_txt, blk.add_qkv.lora.A_cat) if blk.add_qkv.lora is not None else None
+        T_img = blk.qkv.lora.down(n_img, drop) if blk.qkv.lora is not None else None
+        T_txt = blk.add_qkv.lora.down(n_txt, drop) if blk.add_qkv.lora is not None else None
         kw_i = dict(a2=T_img, b2=blk.qkv.lora.B_blk) if T_img is not None else {}
         kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_blk) if T_txt is not None else {}
         # the image stream (4096 rows per sample: tile-aligned) is ONE segmented problem over the joint buffer; the 154 text rows stay per sample
@@ -430,15 +439,21 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if B > 1 and St % 256:
             O_t = O_t.reshape(B * St, D)                                  # the text rows of the attention output, gathered once for both uses below
         if T_o is not None:
-            for pr in _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o), after):
-                ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
+            if drop is not None:
+                blk.to_out.lora.down(O_i, drop, out=T_o)                  # (the view as it is: the mask follows the logical row b * Si + s)
+            else:
+                for pr in _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o), after):
+                    ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
             kw_i.update(a2=T_o, b2=blk.to_out.lora.B_blk)
         probs = _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.w, bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
                                                 gate=mi[:, 2 * D:3 * D], rows_per_batch=rpb, **kw_i), after)
         if not blk.last:
             if T_ao is not None:
-                for pr in _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao), after):
-                    ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
+                if drop is not None:
+                    blk.to_add_out.lora.down(O_t, drop, out=T_ao)
+                else:
+                    for pr in _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao), after):
+                        ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
                 kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_blk)
             probs += _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.w, bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
                                                      aux_in=txt, gate=mt[:, 2 * D:3 * D], rows_per_batch=St, **kw_t), after)
@@ -452,7 +467,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mi9 = mod[:, blk.mod_off:blk.mod_off + 9 * D]                        # (dual blocks never run tokenwise: refused in _engine_forward)
             Sip = (Si + 63) // 64 * 64
             n2a = ops.ln_modulate_fwd(img, mi9[:, 7 * D:8 * D], mi9[:, 6 * D:7 * D], Si)
-            T2 = ops.gemm(n2a, blk.qkv2.lora.A_cat) if blk.qkv2.lora is not None else None
+            T2 = blk.qkv2.lora.down(n2a, drop) if blk.qkv2.lora is not None else None
             kwq = dict(a2=T2, b2=blk.qkv2.lora.B_blk) if T2 is not None else {}
             qkv2 = ops.gemm(n2a, blk.qkv2.w, bias=blk.qkv2.b, **kwq)
             Q2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); K2 = torch.empty_like(Q2)
@@ -469,7 +484,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             kw2 = dict(aux_out=ya2) if ya2 is not None else {}
             T_o2 = None
             if blk.to_out2.lora is not None:
-                T_o2 = ops.gemm(O2, blk.to_out2.lora.A_cat)
+                T_o2 = blk.to_out2.lora.down(O2, drop)
                 kw2.update(a2=T_o2, b2=blk.to_out2.lora.B_blk)
             x1b_img = ops.gemm(O2, blk.to_out2.w, bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si, **kw2)
             d2 = SimpleNamespace(n2a=n2a, qkv2=qkv2, T2=T2, Q2=Q2, K2=K2, Q2t=Q2t, K2t=K2t, O2=O2, lse2b=lse2b, ya2=ya2, T_o2=T_o2, Sip=Sip)
@@ -661,7 +676,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ctx.emb = SimpleNamespace(patches=patches, enc2d=enc2d, tproj=tproj, t1=t1, st1=st1, pooled=pooled_b, p1=p1, sp1=sp1, temb=temb, st=st)
         ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         scale = 1.0 / math.sqrt(hd)
-        env = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, mod=mod, mod_i=mod_i, rpb_i=rpb_i, scale=scale, full=full)
+        # LoRA dropout: training forwards only (validation sampling and eval() forwards are the p = 0 computation).  The call counter advances here, once per
+        # training forward — the blocks below, their recompute passes and the backward all read the value it advanced to
+        drop = self.lora_dropout if (save and self.training and not full and self.lora_groups) else None
+        if drop is not None:
+            drop.advance()
+        env = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, mod=mod, mod_i=mod_i, rpb_i=rpb_i, scale=scale, full=full, drop=drop)
         ctx.env, ctx.blocks, ctx.ck = env, [None] * len(self.blocks), {}
         # activation-checkpoint plan (sd3/transformer.py:716-833; training/checkpoint_plan.py): a checkpointed segment keeps only its input
         from ..training.checkpoint_plan import segments as _segments
@@ -844,7 +864,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mi = mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
             mt = mod[:, blk.mod_off_c:blk.mod_off_c + (2 if blk.last else 6) * D]
             rpb_i = rpb if rpb == 1 else Si             # (inside a TREAD route Si is the kept-token count)
-            if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous()) and rpb != 1:
+            drop = getattr(ctx.envs[li], "drop", None)      # LoRA dropout: the masked dA / dx kernels regenerate this forward's masks
+            acc_, gs_ = self.accumulate_lora_grads, self.grad_sync
+            if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous()) and rpb != 1 \
+                    and drop is None:
                 # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then the rank-space adapter gradients from the gradients it left behind
                 d_img, d_txt, G = self._block_bwd_c(blk, sv, ctx.envs[li], mod, cos, sin, d_img, d_txt, li != 0)
                 pairs = [(blk.to_out, G.U_o, sv.T_o, G.dx1g_i, 0, Si)]
@@ -881,18 +904,22 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 dx1_i, dxg2 = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dres=d_img, gate=mi9[:, 8 * D:9 * D], want_gated=True)
                 lo2, lq2 = blk.to_out2.lora, blk.qkv2.lora
                 U2 = ops.gemm(dxg2, lo2.B_blk_T) if lo2 is not None else None
-                dO2 = ops.gemm(dxg2, blk.to_out2.wT, **(dict(a2=U2, b2=lo2.A_cat_T) if U2 is not None else {}))
+                dO2 = ops.gemm(dxg2, blk.to_out2.wT, **(dict(a2=U2, b2=lo2.A_cat_T) if (U2 is not None and drop is None) else {}))
                 if lo2 is not None:
-                    lo2.grads(d2.O2, d2.T_o2, dxg2, U2, self.accumulate_lora_grads, self.grad_sync)
+                    if drop is not None:
+                        lo2.dx_add(dO2, U2, drop)
+                    lo2.grads(d2.O2, d2.T_o2, dxg2, U2, acc_, gs_, drop)
                 dqkv2 = torch.empty(B * Si, 3 * D, dtype=BF16, device=dev)
                 dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
                 ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
                 ops.qk_norm_rope_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, cos, sin, dqkv2, B, H, hd, Si, 0, Si)
                 Uq2 = ops.gemm(dqkv2, lq2.B_blk_T) if lq2 is not None else None
                 if li != 0:
-                    dn2a = ops.gemm(dqkv2, blk.qkv2.wT, **(dict(a2=Uq2, b2=lq2.A_cat_T) if Uq2 is not None else {}))
+                    dn2a = ops.gemm(dqkv2, blk.qkv2.wT, **(dict(a2=Uq2, b2=lq2.A_cat_T) if (Uq2 is not None and drop is None) else {}))
+                    if lq2 is not None and drop is not None:
+                        lq2.dx_add(dn2a, Uq2, drop)
                 if lq2 is not None:
-                    lq2.grads(d2.n2a, d2.T2, dqkv2, Uq2, self.accumulate_lora_grads, self.grad_sync)
+                    lq2.grads(d2.n2a, d2.T2, dqkv2, Uq2, acc_, gs_, drop)
                 dx1g_i = ops.scale_cols(dx1_i, mi[:, 2 * D:3 * D], Si)
                 del dxg2, dO2, dQ2, dK2, dqkv2, U2, Uq2, d2
             else:
@@ -903,20 +930,25 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             U_i = ops.gemm(dx1g_i, blk.to_out.lora.B_blk_T) if blk.to_out.lora is not None else None
             U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_blk_T) if (not blk.last and blk.to_add_out.lora is not None) else None
             after = []
-            kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T) if U_i is not None else {}
+            kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T) if (U_i is not None and drop is None) else {}
             probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S), **kw_i), after)
             if not blk.last:
-                kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T) if U_t is not None else {}
+                kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T) if (U_t is not None and drop is None) else {}
                 probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S), **kw_t), after)
             ops.gemm_grouped(probs)
             for f in after:
                 f()
+            if drop is not None:               # the adapter term of dO, masked, before the attention backward reads it (each stream's rows of the joint buffer in place)
+                if U_i is not None:
+                    blk.to_out.lora.dx_add(rows_of(dO, 0, Si, B, S), U_i, drop)
+                if U_t is not None:
+                    blk.to_add_out.lora.dx_add(rows_of(dO, Si, St, B, S), U_t, drop)
             pairs = [(blk.to_out, U_i, sv.T_o, dx1g_i, 0, Si)]
             if not blk.last:
                 pairs.append((blk.to_add_out, U_t, sv.T_ao, dx1g_t, Si, St))
             for (lin, U, T_, dxg, lo, rows) in pairs:
                 if lin.lora is not None:       # this stream's rows of the joint attention output: read in place when tile-aligned (image rows), else a compact copy
-                    lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
+                    lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, acc_, gs_, drop)
             del dx1g_i, dx1g_t, U_i, U_t
             dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
             dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
@@ -936,15 +968,19 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 if lin.lora is not None:
                     Us[name] = torch.empty(B * rows, lin.lora.B_blk_T.shape[0], dtype=BF16, device=dev)
                     ops.gemm(dq, lin.lora.B_blk_T, out=Us[name])
-                    kw = dict(a2=Us[name], b2=lin.lora.A_cat_T)
+                    kw = dict(a2=Us[name], b2=lin.lora.A_cat_T) if drop is None else {}
                 if not first:
                     dns.append(torch.empty(B * rows, D, dtype=BF16, device=dev))
                     probs.append(dict(a=dq, w=lin.wT, out=dns[-1], **kw))
             if probs:
                 ops.gemm_grouped(probs)
+            if drop is not None and not first:         # the adapter term of the norm inputs' gradients, masked, before the norm backward reads them
+                for (name, lin, dq, n_in, T_, rows), dn_ in zip(streams, dns):
+                    if lin.lora is not None:
+                        lin.lora.dx_add(dn_, Us[name], drop)
             for (name, lin, dq, n_in, T_, rows) in streams:
                 if lin.lora is not None:
-                    lin.lora.grads(n_in, T_, dq, Us[name], self.accumulate_lora_grads, self.grad_sync)
+                    lin.lora.grads(n_in, T_, dq, Us[name], acc_, gs_, drop)
             if not first:
                 d_img, _ = ops.ln_modulate_bwd(dns[0], sv.img, mi[:, D:2 * D], rpb_i, dres=dx1_i)
                 if dn2a is not None:             # the second reader of LN(img): attn2's modulated input (scale_msa2)

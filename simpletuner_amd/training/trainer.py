@@ -204,6 +204,8 @@ class Trainer:
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
+        # (LoRA dropout: the component's call counter starts where add_lora_adapter(dropout_calls=) put it — 0, the micro-step count of a fresh run; load_state
+        # restores it)
         self.last_loss = None          # device scalar, no host sync
         self.last_grad_norm = None
         self.last_grad_absmax = None
@@ -436,6 +438,9 @@ class Trainer:
         ts = {"global_step": self.state["global_step"], "epoch_step": self.state.get("epoch_step", 0), "epoch": self.state.get("epoch", 1),
               "exhausted_backends": list(self.state.get("exhausted_backends", [])), "repeats": dict(self.state.get("repeats", {})),
               "micro_step": self.state["micro_step"]}
+        drop = getattr(plug.get_trained_component(), "lora_dropout", None)
+        if drop is not None:                      # LoRA dropout: the mask sequence's position (the device-resident call counter), with the step counters
+            ts["lora_dropout_calls"] = drop.calls()
         if rank != 0:                                                                   # save_hooks.py:369-373: non-zero ranks write their own state file
             with open(os.path.join(checkpoint_dir, f"training_state-rank{rank}.json"), "w") as fh:
                 json.dump(ts, fh)
@@ -498,6 +503,9 @@ class Trainer:
             ts = json.load(fh)
         self.state.update({k: ts[k] for k in ("global_step", "epoch_step", "epoch", "exhausted_backends", "repeats") if k in ts})
         self.state["micro_step"] = int(ts.get("micro_step", self.state["global_step"] * self.config.gradient_accumulation_steps))
+        drop = getattr(comp, "lora_dropout", None)
+        if drop is not None:                      # a resumed run continues the mask sequence (a state file from before the counter: the micro-step count)
+            drop.set_calls(int(ts.get("lora_dropout_calls", self.state["micro_step"])))
         plug.load_flow_custom_timestep_state(checkpoint_dir, fallback_global_step=self.state["global_step"])
         for name in (f"random_states_{rank}.pkl", "random_states_0.pkl"):
             path = os.path.join(checkpoint_dir, name)
