@@ -513,6 +513,28 @@ int st355_soap_step(void* stream, const int64_t* plan_host, const int64_t* plan_
  * record field 10, unless NULL) — flip(eigh(.)) of :385-389.  A zero matrix gives the identity. */
 int st355_soap_eigh(void* stream, const int64_t* plan_host, const int64_t* plan_dev, const float* gg, float* q, float* evals);
 
+/* ---- Adafactor (torch.optim.Adafactor, _single_tensor_adafactor: no momentum, no relative step) over a bf16 or fp32 arena of tensors of any rank ----
+ * st355_adafactor_plan (host only): tensor i is batch[i] row-major matrices of [rows[i], cols[i]] (the LAST TWO dims; the leading dims multiplied
+ * out) at element offsets[i] of the arena (ascending, non-overlapping; the elements between tensors are never touched).  A 1-D tensor of k elements
+ * has rows = 0, cols = k, batch = 1.  Fills plan (ST355_ADAFACTOR_PLAN_HEADER + n * ST355_ADAFACTOR_PLAN_RECORD int64) and the workspace size in
+ * floats (also plan[6]; st355_adafactor_workspace_floats reads it back).  plan[3], plan[4], plan[5] = the lengths of the row_var, col_var and
+ * variance state buffers: sum batch * rows, sum batch * cols, sum of the 1-D lengths — packed, tensor after tensor, at record fields 6, 7, 8; inside
+ * a tensor row_var is [batch, rows] and col_var [batch, cols].  Record: 0 offset, 1 kind, 2 batch, 3 rows, 4 cols, 5 numel, 6-8 state offsets,
+ * 9 first tile, 10-11 tile counts, 12 first factor item, 13-15 workspace offsets. */
+#define ST355_ADAFACTOR_PLAN_HEADER 8
+#define ST355_ADAFACTOR_PLAN_RECORD 16
+int st355_adafactor_plan(const int64_t* offsets, const int64_t* batch, const int32_t* rows, const int32_t* cols, int n, int64_t* plan, int64_t* ws_floats);
+int64_t st355_adafactor_workspace_floats(const int64_t* plan_host);
+/* one step for every tensor of the plan, five launches (four when no tensor is a tiled matrix) whatever n is; no atomics, no host sync, no allocation;
+ * fixed summation orders (bit-identical run to run).  p, g: the arena in its dtype (elem_bytes 2 = bf16, 4 = fp32), n_arena elements; state fp32.
+ *   g' = grad_scale g;  alpha = max(eps2, ||p|| / sqrt(numel)) rho  (p before the decay);  matrices: row_var <- lerp(row_var, mean_cols g'^2, w),
+ *   col_var <- lerp(col_var, mean_rows g'^2, w), v = row_var col_var / max(mean_rows row_var, eps1);  1-D: variance <- lerp(variance, g'^2, w), v = variance;
+ *   u = g' / sqrt(max(v, eps1^2));  denom = max(1, ||u|| / (sqrt(numel) d));  p <- p (1 - lr_weight_decay) - (alpha / denom) u, rounded once (nearest even).
+ * w = one_minus_beta2 = step^beta2_decay and rho = min(lr, 1 / sqrt(step)) are computed by the caller in double; eps1 is given (never NULL here). */
+int st355_adafactor_step(void* stream, const int64_t* plan_host, const int64_t* plan_dev, void* p, const void* g, int elem_bytes, int64_t n_arena,
+                         float* row_var, float* col_var, float* variance, float* ws, int64_t ws_floats, float grad_scale, double one_minus_beta2,
+                         double rho, double eps1, double eps2, double d, double lr_weight_decay);
+
 /* ---- LayerSync (helpers/training/layersync.py): self-alignment of two block outputs, cosine per token row, F.normalize semantics x / max(|x|, 1e-12) ----
  * student, teacher: [B, rows, D] bf16 views with row stride ld and their own batch strides (elements), e.g. the image rows of a joint [B * S, D] buffer; the
  * teacher is a constant (detached).  Per row c = <s^, t^> -> cos_rows[B * rows] fp32; G[B * rows, D] bf16 (compact) = (t^ - c s^) / max(|s|, 1e-12) / (B * rows)

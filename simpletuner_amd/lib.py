@@ -28,6 +28,7 @@ SYMBOLS = [
     "st355_adamw_ema_step", "st355_adamw_ema_step_bf16", "st355_adamw_bf16_sr_step", "st355_lion_step", "st355_lion_step_bf16", "st355_ema_update", "st355_grad_norm", "st355_grad_norm_ws", "st355_grad_clamp", "st355_grad_clip_norm",
     "st355_muon_plan", "st355_muon_step", "st355_muon_orthogonalize",
     "st355_soap_plan", "st355_soap_step", "st355_soap_eigh",
+    "st355_adafactor_plan", "st355_adafactor_workspace_floats", "st355_adafactor_step",
     "st355_layersync_fwd", "st355_layersync_inject",
     "st355_ig_fold", "st355_ig_head_fwd", "st355_ig_head_bwd", "st355_ig_wgrad",
     "st355_nextlat_fold", "st355_gelu_erf_fwd", "st355_gelu_erf_bwd", "st355_nextlat_loss_workspace", "st355_nextlat_loss", "st355_nextlat_ln_bwd_add",
@@ -368,6 +369,9 @@ def _declare(lib):
         "st355_soap_plan": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "st355_soap_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32]),
         "st355_soap_eigh": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "st355_adafactor_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp]),
+        "st355_adafactor_workspace_floats": (i64, [vp]),
+        "st355_adafactor_step": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
         "st355_layersync_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, vp]),
         "st355_layersync_inject": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
         "st355_ig_fold": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32]),

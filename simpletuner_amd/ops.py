@@ -1313,6 +1313,76 @@ def soap_eigh(plan: SoapPlan, gg, q=None, evals=None):
     return q, evals
 
 
+def adafactor_factor_shape(shape):
+    """(batch, R, C) of a parameter shape as torch.optim.Adafactor factors it: the last two dims, the leading dims a batch; a 1-D tensor of k
+    elements is (1, 0, k)"""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or any(s < 1 for s in shape):
+        raise _l.St355Error(f"adafactor_plan: cannot take a tensor of shape {shape}")
+    if len(shape) == 1:
+        return 1, 0, shape[0]
+    batch = 1
+    for s in shape[:-2]:
+        batch *= s
+    return batch, shape[-2], shape[-1]
+
+
+class AdafactorPlan:
+    """st355_adafactor_plan for a fixed list of tensors of one arena (element offsets, shapes of any rank): the host plan and its device copy, made
+    once.  `rv_len`, `cv_len`, `var_len` are the lengths of the three fp32 state buffers; `rv_offsets[i]`, `cv_offsets[i]`, `var_offsets[i]` and
+    `factors[i]` = (batch, R, C) place tensor i's slices in them.  The workspace (`ws_floats`) comes from the scratch helper at every step."""
+
+    HEADER, RECORD = 8, 16
+
+    def __init__(self, offsets, shapes, device):
+        n = len(shapes)
+        if n == 0 or len(offsets) != n:
+            raise _l.St355Error("adafactor_plan: expected one offset per tensor shape")
+        L = _l.load()
+        self.factors = [adafactor_factor_shape(s) for s in shapes]
+        if any(max(f) >= 2 ** 31 for f in self.factors):
+            raise _l.St355Error("adafactor_plan: a dimension of 2^31 or more")
+        off = (C.c_int64 * n)(*[int(o) for o in offsets])
+        batch = (C.c_int64 * n)(*[f[0] for f in self.factors])
+        rows = (C.c_int32 * n)(*[f[1] for f in self.factors])
+        cols = (C.c_int32 * n)(*[f[2] for f in self.factors])
+        self.host = torch.zeros(self.HEADER + self.RECORD * n, dtype=torch.int64)
+        ws = C.c_int64(0)
+        _l.check(L.st355_adafactor_plan(off, batch, rows, cols, n, _ptr(self.host), C.byref(ws)), "adafactor_plan")
+        self.n = n
+        self.ws_floats = int(ws.value)
+        self.rv_len, self.cv_len, self.var_len = (int(self.host[i]) for i in (3, 4, 5))
+        rec = self.host[self.HEADER:].view(n, self.RECORD)
+        self.rv_offsets, self.cv_offsets, self.var_offsets = rec[:, 6].tolist(), rec[:, 7].tolist(), rec[:, 8].tolist()
+        self.end = int(rec[-1, 0] + rec[-1, 5])
+        self.dev = self.host.to(device)
+
+
+def adafactor_step(plan: AdafactorPlan, pflat, gflat, row_var, col_var, variance, step: int, lr: float, beta2_decay: float = -0.8, eps1: Optional[float] = None,
+                   eps2: float = 1e-3, d: float = 1.0, weight_decay: float = 0.0, grad_scale: float = 1.0):
+    """one torch.optim.Adafactor step over the arena (pflat, gflat: bf16 or fp32 flat, plan offsets into them; row_var, col_var, variance: the plan's
+    fp32 state buffers), in place.  `step` is the count AFTER this step (1 for the first).  eps1=None is torch's: the epsilon of the arena's dtype"""
+    L = _l.load()
+    if pflat.dtype not in (F32, BF16):
+        raise _l.St355Error(f"adafactor_step: the arena must be fp32 or bf16, got {pflat.dtype}")
+    _chk(pflat, pflat.dtype, "pflat"); _chk(gflat, pflat.dtype, "gflat")
+    if not pflat.is_contiguous() or not gflat.is_contiguous() or gflat.numel() != pflat.numel() or pflat.numel() < plan.end:
+        raise _l.St355Error(f"adafactor_step: pflat and gflat must be contiguous arenas of one length >= {plan.end}")
+    for t, nm, k in ((row_var, "row_var", plan.rv_len), (col_var, "col_var", plan.cv_len), (variance, "variance", plan.var_len)):
+        _chk(t, F32, nm)
+        if not t.is_contiguous() or t.numel() < k:
+            raise _l.St355Error(f"adafactor_step: {nm} must be a contiguous fp32 buffer of at least {k} elements")
+    if step < 1:
+        raise _l.St355Error("adafactor_step: step counts from 1")
+    if eps1 is None:
+        eps1 = torch.finfo(pflat.dtype).eps
+    ws = _scratch("adafactor", pflat.device, 4 * max(plan.ws_floats, 1))
+    _l.check(L.st355_adafactor_step(_stream(), _ptr(plan.host), _ptr(plan.dev), _ptr(pflat), _ptr(gflat), pflat.element_size(), pflat.numel(),
+                                    _ptr(row_var), _ptr(col_var), _ptr(variance), _ptr(ws), ws.numel() // 4, float(grad_scale),
+                                    float(step) ** beta2_decay, min(float(lr), 1.0 / float(step) ** 0.5), float(eps1), float(eps2), float(d),
+                                    float(lr) * float(weight_decay)), "adafactor_step")
+
+
 def _token_view(t, name: str):
     """a [B, rows, D] bf16 view with unit inner stride (e.g. the image rows of a joint [B * S, D] buffer): (B, rows, D, row stride, batch stride)"""
     _chk(t, BF16, name)

@@ -60,7 +60,7 @@ def _unpack_saved_state(opt: torch.optim.Optimizer, state_dict: dict):
 
 
 class _ArenaOptimizer(torch.optim.Optimizer):
-    """What the fused arena optimizers (AdamW, AdamWBF16, Lion, Muon, SOAP) share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
+    """What the fused arena optimizers (AdamW, AdamWBF16, Lion, Muon, SOAP, Adafactor) share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
     per-parameter state installed as views of them (`_flat[gi]`: ok, ps, n, one entry per declared buffer, the subclass's extras); a
     `load_state_dict` that copies a checkpoint INTO those buffers in the dtype each is kept in; and the test for the one-launch path.
     A subclass declares `_buffers`, adds its extras in `_group_extras` / `_load_extras`, and issues its `ops.*` calls in `step`."""
@@ -675,8 +675,115 @@ class St355Soap(_ArenaOptimizer):
         return loss
 
 
+# ---- Adafactor -------------------------------------------------------------------------------------------------------------------
+class St355Adafactor(_ArenaOptimizer):
+    """torch.optim.Adafactor — the reference's "torch-adafactor" entry (optimizer_param.py:154-163) — as ONE st355_adafactor_step call (five
+    launches) per parameter group, whatever the number of tensors.  The rule is `_single_tensor_adafactor` of the installed torch.
+
+    Same constructor and defaults; `foreach` is accepted and ignored, `maximize=True` and a tensor `lr` are refused.  Per-parameter state in torch's
+    layout: `step` (float scalar tensor), `row_var [..., R, 1]` and `col_var [..., 1, C]` for tensors of two or more dims (factored over the last
+    two, the leading dims a batch), `variance` like p for 1-D tensors — views of three flat buffers sized by the plan, fp32 also for bf16 parameters
+    (torch keeps them in bf16).  No state buffer has the arena's length.  Parameters must be fp32 or bf16 views of one contiguous arena; there is
+    no per-tensor path.  A `state_dict()` of torch.optim.Adafactor on the same shapes loads here, in either dtype."""
+
+    def __init__(self, params, lr=1e-2, beta2_decay: float = -0.8, eps=(None, 1e-3), d: float = 1.0, weight_decay: float = 0.0, *, foreach=None,
+                 maximize: bool = False):
+        if isinstance(lr, torch.Tensor):
+            raise NotImplementedError("torch-adafactor: a tensor lr is not built on the st355 path (the learning rate crosses the ABI as a host scalar)")
+        if maximize:
+            raise NotImplementedError("torch-adafactor: maximize=True is not built on the st355 path")
+        if not 0.0 <= lr:                                             # torch/optim/_adafactor.py:38-49, same texts
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 >= beta2_decay:
+            raise ValueError(f"beta2_decay should be <= 0 but is: {beta2_decay}")
+        if eps[0] is not None and not 0.0 <= eps[0]:
+            raise ValueError(f"epsilon1 should be >= 0 but is: {eps[0]}")
+        if not 0.0 <= eps[1]:
+            raise ValueError(f"epsilon2 should be >= 0 but is: {eps[1]}")
+        if not 1.0 <= d:
+            raise ValueError(f"Clipping threshold d should be >= 1 but is: {d}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight_decay should be >= 0 but is: {weight_decay}")
+        super().__init__(params, dict(lr=lr, beta2_decay=beta2_decay, eps=tuple(eps), d=d, weight_decay=weight_decay, foreach=foreach, maximize=False))
+        self.abi_calls = 0              # st355 calls issued by step(): one per parameter group, whatever the number of tensors
+
+    def _group_params(self, group):
+        return list(group["params"])
+
+    def _check_param(self, p):
+        if p.dtype not in (F32, torch.bfloat16):
+            raise NotImplementedError(f"torch-adafactor: parameters must be fp32 or bf16 on the st355 path, got {p.dtype}")
+        if p.dim() < 1 or p.numel() == 0:
+            raise NotImplementedError(f"torch-adafactor: a parameter of shape {tuple(p.shape)} is not built on the st355 path")
+
+    def _group_extras(self, gi, group, st):
+        ps = st["ps"]
+        if not st["ok"]:
+            raise NotImplementedError("torch-adafactor: the parameters of a group must be one contiguous run of one dtype (an st355 arena)")
+        base, esz, dev = ps[0].data_ptr(), ps[0].element_size(), ps[0].device
+        plan = st["plan"] = ops.AdafactorPlan([(p.data_ptr() - base) // esz for p in ps], [tuple(p.shape) for p in ps], dev)
+        st["row_var"] = torch.zeros(plan.rv_len, dtype=F32, device=dev)
+        st["col_var"] = torch.zeros(plan.cv_len, dtype=F32, device=dev)
+        st["variance"] = torch.zeros(plan.var_len, dtype=F32, device=dev)
+        st["step"] = 0
+        st["step_t"] = torch.tensor(0.0)    # torch's per-parameter `step` (a float scalar tensor): ONE tensor shared by the group's parameters, so a step is one host increment
+        for p, (batch, R, C), ro, co, vo in zip(ps, plan.factors, plan.rv_offsets, plan.cv_offsets, plan.var_offsets):
+            s = self.state[p]
+            s["step"] = st["step_t"]
+            if R == 0:
+                s["variance"] = st["variance"][vo:vo + C].view_as(p)
+            else:
+                s["row_var"] = st["row_var"][ro:ro + batch * R].view(*p.shape[:-1], 1)
+                s["col_var"] = st["col_var"][co:co + batch * C].view(*p.shape[:-2], 1, p.shape[-1])
+
+    def _load_extras(self, st, mine, old):
+        """the factors (or the variance) of one parameter, saved in either dtype, into the fp32 views; the step count is the group's"""
+        for key in ("row_var", "col_var", "variance"):
+            if (key in mine) != (old.get(key) is not None):
+                raise NotImplementedError(f"torch-adafactor: the saved state has {'a' if key not in mine else 'no'} '{key}' for a parameter of "
+                                          f"{'one dim' if 'variance' in mine else 'two or more dims'}")
+            if key in mine:
+                if tuple(old[key].shape) != tuple(mine[key].shape):
+                    raise ValueError(f"torch-adafactor: saved '{key}' of shape {tuple(old[key].shape)}, expected {tuple(mine[key].shape)}")
+                mine[key].copy_(old[key].to(device=mine[key].device, dtype=F32))
+        k = int(float(old["step"]))
+        if st.get("_loaded") and st["step"] != k:
+            raise NotImplementedError("torch-adafactor: the parameters of a group must share one step count (one fused call)")
+        st.update(step=k, _loaded=True)
+        st["step_t"].fill_(float(k))
+
+    def state_dict(self):
+        """every parameter gets its own copy of the shared `step` tensor: torch's class increments `step` once per parameter, so a state dict whose entries
+        shared one tensor would count a step N times there"""
+        base = super().state_dict()
+        base["state"] = {k: {**v, "step": v["step"].clone()} if "step" in v else v for k, v in base["state"].items()}
+        return base
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            if all(p.grad is None for p in group["params"]):
+                continue
+            st = self._group_flat(gi, group)
+            fused = self._fused_views(st, st["ps"])
+            if fused is None or fused[1].dtype != fused[0].dtype:
+                raise RuntimeError("St355Adafactor expects the gradients of every parameter of a group as one flat arena of the parameters' dtype (fused step)")
+            pflat, gflat, _ = fused
+            st["step"] += 1
+            eps1, eps2 = group["eps"]
+            ops.adafactor_step(st["plan"], pflat, gflat, st["row_var"], st["col_var"], st["variance"], st["step"], group["lr"], group["beta2_decay"],
+                               eps1, eps2, group["d"], group["weight_decay"], self.grad_scale)
+            self.abi_calls += 1
+            st["step_t"] += 1
+        return loss
+
+
 # what the reference's registry `optimizer_choices` holds for these names (optimizer_param.py:76-96 "st355-adamw"-style entry, the reference's own
-# "adamw_bf16", "muon" :432-447, "optimi-lion" :327-338 and "soap" :415-431), with the fused classes substituted
+# "adamw_bf16", "muon" :432-447, "optimi-lion" :327-338, "soap" :415-431 and "torch-adafactor" :154-163), with the fused classes substituted
 OPTIMIZER_CHOICE = {
     "st355-adamw": {
         "precision": "any",
@@ -705,6 +812,11 @@ OPTIMIZER_CHOICE = {
                              "max_precond_dim": 10000, "merge_dims": False, "precondition_1d": False, "normalize_grads": False,
                              "data_format": "channels_first", "correct_bias": True},
         "class": St355Soap,
+    },
+    "torch-adafactor": {
+        "precision": "any",
+        "default_settings": {"beta2_decay": -0.8, "eps": (None, 1e-3), "d": 1.0, "weight_decay": 0.0},
+        "class": St355Adafactor,
     },
 }
 
@@ -739,4 +851,8 @@ def optimizer_settings(name: str, config) -> dict:
     import copy
     settings = copy.deepcopy(OPTIMIZER_CHOICE[name].get("default_settings", {}))
     settings.update(parse_optimizer_config(config))
+    if name == "torch-adafactor" and ("eps1" in settings or "eps2" in settings):
+        # the registry's `eps` is a pair, which `k=v,k=v` cannot spell: eps1= / eps2= set its two halves (an explicit eps1 is used as given)
+        eps = tuple(settings["eps"])
+        settings["eps"] = (settings.pop("eps1", eps[0]), settings.pop("eps2", eps[1]))
     return settings

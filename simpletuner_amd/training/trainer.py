@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, St355Soap, flat_view, optimizer_settings
+from .optimizer import OPTIMIZER_CHOICE, St355Adafactor, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, St355Soap, flat_view, optimizer_settings
 
 
 class St355Accelerator:
@@ -108,8 +108,8 @@ class Trainer:
                        else [p for p in comp.parameters() if p.requires_grad])
         # optimizer_param.py:76-96 registry semantics: name -> class (+ default settings)
         opt_name = getattr(config, "optimizer", "st355-adamw")
-        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap"):   # never a silently different optimizer
-            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, st355-adamw = torch-adamw semantics)")
+        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap", "torch-adafactor"):   # never a silently different optimizer
+            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, torch-adafactor, st355-adamw = torch-adamw semantics)")
         if opt_name in ("muon", "soap") and getattr(config, "internal_guidance_enabled", False):
             raise NotImplementedError(f"optimizer '{opt_name}' with internal_guidance_enabled: the trainable arena then holds the head's 1-D tensors, which the "
                                       "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
@@ -142,6 +142,17 @@ class Trainer:
             self.optimizer = St355AdamWBF16(opt_params, lr=config.learning_rate, betas=(config.adam_beta1, config.adam_beta2),
                                             eps=OPTIMIZER_CHOICE["adamw_bf16"]["default_settings"]["eps"], weight_decay=config.adam_weight_decay,
                                             seed=int(getattr(config, "seed", 0) or 0))
+        elif opt_name == "torch-adafactor":
+            # every LoRA arena (2-D fp32) and the transformer full arenas (bf16; 1-D tensors and batched small matrices included).  No fused EMA: EMAModel.step
+            # runs after the step.  The UNet full fine-tune is refused: in the reference's layout its convolutions are [Cout, Cin, 3, 3], i.e. 3 x 3 factors on the
+            # untuned small-matrix path.  The class-name test is the one that fires for the real component (UNet2DConditionModel keeps a convolution as [Cout, 9 Cin]
+            # rows, so its parameters do not show the 3 x 3 shape — and would factor differently from the reference if they were stepped); the shape test
+            # catches a component that does expose checkpoint-shaped convolutions
+            unet = type(comp).__name__.startswith("UNet") or any(p.dim() == 4 and tuple(p.shape[-2:]) == (3, 3) for p in self.params)
+            if getattr(comp, "full", False) and unet:
+                raise NotImplementedError("optimizer 'torch-adafactor' is not built for the SDXL / SD 1.5 UNet full fine-tune: the reference factors its "
+                                          "[Cout, Cin, 3, 3] convolutions as 3 x 3 matrices, which only the untuned small-matrix path would serve")
+            self.optimizer = St355Adafactor(self.params, lr=config.learning_rate, **optimizer_settings("torch-adafactor", config))
         elif opt_name == "optimi-lion":
             # fp32 adapter arena or bf16 full-fine-tune arena (Kahan-compensated there), one launch either way; no override_lr_scheduler in the registry entry
             self.optimizer = St355Lion(self.params, lr=config.learning_rate, **optimizer_settings("optimi-lion", config))
