@@ -647,6 +647,25 @@ int st355_skinny_tn_drop_multi(void* stream, const void* L, int64_t ldl, const v
                                int64_t M, int64_t P, int r_used, float alpha, int accumulate, void* workspace, int64_t seg_rows, int64_t seg_l, int64_t seg_r,
                                const st355_lora_drop* drop);
 
+/* ---- DoRA (Liu et al. 2024; peft `use_dora`; csrc/dora.hip): V = W + s B A, norm_n = ||V[n, :]||_2 (detached), g_n = m_n / norm_n,
+ * y = g . (x W^T + s (x A^T) B^T) + b.  The row scale is folded into the GEMM operands once per forward; fp32 arithmetic, no atomics, fixed-order reductions. */
+/* One launch per adapter group (G <= 4 targets; target i owns rows [n_off[i], n_off[i] + n_cnt[i]) of the fused Linear, in rising order, and the slab
+ * [i r_pad, (i + 1) r_pad) of the K-extension; n_off / n_cnt are HOST arrays).  Reads W [N_total, K] bf16, A_cat_T [K, K2] and B_blk [N_total, K2] (the packed
+ * bf16 operands the forward multiplies with; B_blk carries s) and m [N_total] fp32; per row of a target writes
+ *   inv_norm[n] = 1 / norm_n, g[n] = m[n] / norm_n (fp32; init != 0: m[n] = norm_n is WRITTEN first, so g[n] = 1 exactly),
+ *   Wf = bf16(g . W) [N_total, K] and WfT [K, N_total] its transpose, Bf = bf16(g . B_blk) [N_total, K2] and BfT [K2, N_total].
+ * Rows outside every target are not touched.  K % 8 == 0, K2 % 64 == 0, r_pad 32 / 64 / 128, any n_cnt. */
+int st355_dora_fold(void* stream, const void* W, const void* A_cat_T, const void* B_blk, float* m, int init, float* inv_norm, float* g, void* Wf, void* WfT,
+                    void* Bf, void* BfT, int N_total, int K, int K2, int G, const int* n_off, const int* n_cnt, int r_pad);
+/* dm[n] (+)= inv_norm[n] sum_rows dy[row, n] y0[row, n].  dy bf16 (row stride ldd; compact, or seg_rows-row blocks seg_stride ROWS apart: a [B, rows, N] view of a
+ * joint buffer), y0 bf16 [M, N] (row stride ldy) = x W^T + s (x A^T) B^T recomputed by the backward.  Two stages: per 256-row chunk partial column sums into the
+ * workspace (st355_dora_dmag_workspace(M, N) bytes), then the chunks in order: a view and its compact copy give the same bits.  N % 8 == 0. */
+int64_t st355_dora_dmag_workspace(int64_t M, int N);
+int st355_dora_dmag(void* stream, const void* dy, int64_t ldd, int64_t seg_rows, int64_t seg_stride, const void* y0, int64_t ldy, const float* inv_norm, float* dm,
+                    int64_t M, int N, int accumulate, void* workspace);
+/* gB[n, r] (+)= g[n] P[n, r]: P [N, rank] fp32 contiguous = s dy^T T (st355_skinny_tn_seg, accumulate = 0), gB [N, rank] fp32 contiguous */
+int st355_dora_db_finish(void* stream, const float* P, const float* g, float* gB, int N, int rank, int accumulate);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

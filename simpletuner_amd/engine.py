@@ -2,6 +2,7 @@
 
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
   * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
+  * `LoraDora`: a group's DoRA state (magnitudes, the row scale, the folded GEMM operands);
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
@@ -14,7 +15,7 @@
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -76,6 +77,24 @@ class LoraDropout:
         ops.lora_dropout_advance(self.call)
 
 
+class LoraDora:
+    """DoRA (peft `use_dora`; Liu et al. 2024) of one LoraGroup: y = g . (x W^T + s (x A^T) B^T) + b with g = m / ||W + s B A||_row, the norm detached.  The row
+    scale is folded into the GEMM operands once per forward (LoraGroup.fold), so every GEMM route and epilogue runs as it is on the folded copies:
+      m / gm       the trainable magnitudes of the group's targets and their gradients, [N_total] fp32 views of the arenas
+      inv_norm, g  [N_total] fp32 of the last fold
+      Wf / WfT     bf16(g . W) and its transpose (what `lin.w` / `lin.wT` are to a plain LoRA);  Bf / BfT  bf16(g . B_blk) and its transpose
+    The folded copies double the adapted weights' memory; they live for the whole step."""
+
+    def __init__(self, group, lin, m, gm, flat_lo: int):
+        dev = lin.w.device
+        N, K, K2 = group.N_total, group.K, group.K2
+        self.lin, self.m, self.gm = lin, m, gm
+        self.flat_lo, self.flat_hi = flat_lo, flat_lo + N
+        self.inv_norm, self.g = torch.zeros(N, dtype=F32, device=dev), torch.zeros(N, dtype=F32, device=dev)
+        e = lambda *s: torch.empty(*s, dtype=BF16, device=dev)
+        self.Wf, self.WfT, self.Bf, self.BfT = e(N, K), e(K, N), e(N, K2), e(K2, N)
+
+
 class LoraGroup:
     """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A dropout(x): `streams` are the targets' mask
     stream ids (their index in the component's ordered target list — q / k / v share x but draw independent masks, as peft's per-module nn.Dropout); `down` /
@@ -98,6 +117,58 @@ class LoraGroup:
         self.gA: List[torch.Tensor] = []  # fp32 grad views
         self.gB: List[torch.Tensor] = []
         self.flat_lo = self.flat_hi = 0   # this group's [lo, hi) element range inside the flat gradient arena
+        self.dora: Optional[LoraDora] = None          # enable_dora(): the group's magnitudes and folded operands; None = plain LoRA (nothing allocated or launched)
+
+    # ---- DoRA ----
+    def enable_dora(self, lin, m, gm, flat_lo: int):
+        """m / gm: the group's magnitudes and their gradients, [N_total] fp32 views of the arenas (the targets' vectors back to back, from element flat_lo)"""
+        if self.K % 8 or len(self.targets) > 4 or self.r_pad > 128:
+            raise NotImplementedError(f"use_dora: the adapters of {self.targets[0][0]} (in_features {self.K}, {len(self.targets)} targets, rank {self.rank}) are "
+                                      "outside the fold kernel (in_features % 8 == 0, at most 4 targets per input, rank <= 128)")
+        self.dora = LoraDora(self, lin, m, gm, flat_lo)
+
+    def fold(self, init: bool = False):
+        """after pack(): g = m / ||W + s B A||_row from the packed operands, then W' = g . W, B_blk' = g . B_blk and their transposes (ops.dora_fold).  The folded
+        copies stay for the whole step: the forward, every recompute pass and the backward's dx / U products read them."""
+        d = self.dora
+        ops.dora_fold(d.lin.w, self.A_cat_T, self.B_blk, d.m, [(n_off, N) for (_, n_off, N) in self.targets], self.r_pad, d.inv_norm, d.g, d.Wf, d.WfT, d.Bf, d.BfT,
+                      init=init)
+
+    # the operands the GEMMs of an adapted Linear read: the folded ones under DoRA, else the Linear's own and the packed ones
+    def w_of(self, lin):
+        return lin.w if self.dora is None else self.dora.Wf
+
+    def wT_of(self, lin):
+        return lin.wT if self.dora is None else self.dora.WfT
+
+    @property
+    def B_fwd(self):
+        return self.B_blk if self.dora is None else self.dora.Bf
+
+    @property
+    def B_fwd_T(self):
+        return self.B_blk_T if self.dora is None else self.dora.BfT
+
+    def _grads_dora(self, x, T, dy, accumulate: bool, sync):
+        """dm = (1 / norm) sum_rows dy . y0 with y0 = x W^T + s (x A^T) B^T recomputed on the forward's GEMM route from the UNSCALED operands (no bias, no epilogue;
+        nothing saved), and dB_g = g . (s dy_g^T T_g): the unscaled product into scratch by skinny_tn, then the row scale (gradient accumulation rules out scaling
+        gB afterwards)"""
+        d = self.dora
+        if isinstance(x, (list, tuple)):
+            raise NotImplementedError("use_dora: an input that only exists as K segments is not built")
+        M = x.shape[0] * x.shape[1] if x.dim() == 3 else x.shape[0]
+        y0 = ops.dora_y0_scratch(T.device, M, self.N_total)
+        ops.gemm(x, d.lin.w, a2=T, b2=self.B_blk, out=y0)
+        ops.dora_dmag(dy, y0, d.inv_norm, d.gm, accumulate=accumulate)
+        cw = min(self.r_pad, 64)
+        for g, (_, n_off, N) in enumerate(self.targets):
+            P = ops.dora_db_scratch(T.device, N, self.rank)
+            for s0 in range(0, self.rank, cw):
+                c0, r_used = g * self.r_pad + s0, min(cw, self.rank - s0)
+                ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], P[:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=False)
+            ops.dora_db_finish(P, d.g[n_off:n_off + N], self.gB[g], accumulate=accumulate)
+        if sync is not None:
+            sync.ready(d.flat_lo, d.flat_hi)
 
     def pack(self):
         for g, (_, n_off, _) in enumerate(self.targets):
@@ -132,10 +203,14 @@ class LoraGroup:
         segs = x if isinstance(x, (list, tuple)) else [(x, 0)]
         multi = len(segs) == 1 and 1 < len(self.targets) <= 4 and self.r_pad == 32 and U.shape[1] >= 128   # q / k / v share x: dA of all three in ONE pass over x
         cw = min(self.r_pad, 64)                                 # rank-space kernels take 32 or 64 adapter columns per pass
+        dora = self.dora is not None          # DoRA: U = (g . dy) B_blk^T already carries the row scale, so dA is the product below as it is; dm and dB are not
+        if dora:
+            self._grads_dora(x, T, dy, accumulate, sync)
         for g, (_, n_off, N) in enumerate(self.targets):
             for s0 in range(0, self.rank, cw):
                 c0, r_used = g * self.r_pad + s0, min(cw, self.rank - s0)
-                ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], self.gB[g][:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=accumulate)
+                if not dora:
+                    ops.skinny_tn(dy[..., n_off:n_off + N], T[:, c0:c0 + cw], self.gB[g][:, s0:], self.rank, 1, r_used, alpha=self.scale, accumulate=accumulate)
                 if not multi:
                     for (xs, k0) in segs:
                         ops.skinny_tn(xs, U[:, c0:c0 + cw], self.gA[g][s0:, k0:], 1, self.K, r_used, alpha=1.0, accumulate=accumulate)

@@ -475,6 +475,32 @@ class ModelFoundation(ExplorativeModelingMixin):
         return None
 
     LORA_DROPOUT_BUILT = False          # families whose engine draws the LoRA-dropout masks (SD3)
+    DORA_BUILT = False                  # families whose engine folds the DoRA row scale (SD3)
+
+    def use_dora_value(self) -> bool:
+        """`use_dora` (the reference builds every standard LoRA with LoraConfig(use_dora=...): common.py:1094-1104) as the family's add_lora_adapter takes it:
+        False when absent; a full fine-tune and lora_type=lycoris ignore the flag, as the reference does; a standard LoRA of a family without the fold refuses it by
+        name, and so do the combinations that are not built — never a silently different computation."""
+        cfg = self.config
+        v = getattr(cfg, "use_dora", False)
+        on = v.strip().lower() in ("1", "true", "yes", "on") if isinstance(v, str) else bool(v)
+        if not on or "lora" not in str(getattr(cfg, "model_type", "lora")) or str(getattr(cfg, "lora_type", "standard") or "standard").lower() != "standard":
+            return False
+        if not self.DORA_BUILT:
+            raise NotImplementedError(f"use_dora: DoRA is not built for {self.NAME} on the st355 path (built: SD3); set --use_dora=false")
+        p = float(getattr(cfg, "lora_dropout", 0.0) or 0.0)
+        if p > 0.0:
+            raise NotImplementedError(f"use_dora with lora_dropout={p}: peft then feeds the dropped x to the base term of the DoRA correction, a different "
+                                      "computation that is not built on the st355 path; set --lora_dropout=0 or --use_dora=false")
+        opt = str(getattr(cfg, "optimizer", "") or "")
+        if opt in ("muon", "soap"):
+            raise NotImplementedError(f"use_dora with optimizer '{opt}': the trainable arena then holds the magnitudes' 1-D tensors, which the matrix optimizers do "
+                                      "not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion, torch-adafactor)")
+        from .training.lora_keys import PEFTLoRAFormat, normalize_lora_format
+        if normalize_lora_format(getattr(cfg, "lora_format", None)) == PEFTLoRAFormat.COMFYUI:
+            raise NotImplementedError("use_dora with lora_format=comfyui: the ComfyUI export of a DoRA adapter is not built on the st355 path; set "
+                                      "--lora_format=diffusers")
+        return True
 
     def lora_dropout_value(self) -> float:
         """`lora_dropout` (the reference builds every standard LoRA with LoraConfig(lora_dropout=...): common.py:1094-1104) as the family's add_lora_adapter takes
@@ -705,10 +731,13 @@ class ModelFoundation(ExplorativeModelingMixin):
         comp = component if component is not None else self.get_trained_component()
         src = comp.lora_state_dict().items() if hasattr(comp, "lora_state_dict") else ((n, p.detach()) for n, p in comp.named_parameters() if ".lora_" in n)
         # (a component whose working layout pads the adapter factors — PixArt's 72 -> 96 head lanes — hands out the true peft shapes itself)
-        sd = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in src}
+        # (a DoRA adapter's magnitudes: `<module>.lora_magnitude_vector.weight`, fp32 [out_features] — the spelling the reference's loader reads, adapter.py:170, 204-207)
+        sd = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.").replace(self.DORA_KEY + ".default.", self.DORA_KEY + "."): p for n, p in src}
         sd.update(self._internal_guidance_head_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         sd.update(self._nextlat_predictor_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         return sd
+
+    DORA_KEY = ".lora_magnitude_vector"            # peft's DoraLinearLayer parameter, per adapted module
 
     IG_PREFIX = "internal_guidance_head."          # internal_guidance.py:184 MODULE_NAME; in an adapter file under `transformer.`
 
@@ -783,6 +812,9 @@ class ModelFoundation(ExplorativeModelingMixin):
             for k, v in state.items():
                 flat[f"{prefix}.{k}"] = v.detach().to("cpu").contiguous()
         fmt = normalize_lora_format(getattr(self.config, "lora_format", None))
+        if fmt == PEFTLoRAFormat.COMFYUI and any(self.DORA_KEY in k for k in flat):
+            raise NotImplementedError("use_dora: the ComfyUI export of a DoRA adapter (its magnitude vectors) is not built on the st355 path; save with "
+                                      "--lora_format=diffusers")
         if fmt == PEFTLoRAFormat.COMFYUI and not getattr(self, "NATIVE_COMFYUI_LORA_SUPPORT", False):
             flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k}
             flat = self._convert_lora_state_dict_to_comfyui(flat, adapter_metadata=meta or self._lora_adapter_metadata(), component_adapter_metadata=comp_meta)
@@ -839,7 +871,17 @@ class ModelFoundation(ExplorativeModelingMixin):
             if bad:
                 k0 = next(iter(bad))
                 raise ValueError(f"LoRA file alpha {bad[k0]} for {k0} differs from the configured lora_alpha {want}; set lora_alpha to match the file")
-        own = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): p for n, p in comp.named_parameters() if ".lora_" in n}
+        own = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.").replace(self.DORA_KEY + ".default.", self.DORA_KEY + "."): p
+               for n, p in comp.named_parameters() if ".lora_" in n}
+        # DoRA: the magnitudes travel as `<module>.lora_magnitude_vector.weight` (also accepted: the key without `.weight`); a file and a component must agree
+        flat = {(k + ".weight" if k.endswith(self.DORA_KEY) else k): v for k, v in flat.items()}
+        file_dora, own_dora = any(self.DORA_KEY in k for k in flat), any(self.DORA_KEY in k for k in own)
+        if file_dora and not own_dora:
+            raise ValueError("LoRA checkpoint carries DoRA magnitude vectors (lora_magnitude_vector) but the adapter was built without them: set --use_dora=true "
+                             "before loading it")
+        if own_dora and not file_dora:
+            raise ValueError("use_dora is set but the LoRA checkpoint carries no DoRA magnitude vectors (lora_magnitude_vector): it is a plain LoRA file; set "
+                             "--use_dora=false to load it")
         # an Internal Guidance head / a NextLat predictor travels with the adapter (diffusers-format files): read back strictly — every tensor of it when one is
         # configured, and a file that carries one needs a component that has one
         for pre, attr, a, name, flag, key in ((self.IG_PREFIX, "_ig", "an", "Internal Guidance head", "internal_guidance_enabled", "internal_guidance_block_index"),

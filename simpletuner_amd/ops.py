@@ -900,6 +900,71 @@ def skinny_tn_drop_multi(Lm, R, outs, so_p: int, so_r: int, r_used: int, streams
 
 
 # ------------------------------------------------------------------------------------------------
+# DoRA (csrc/dora.hip): the row scale g = m / ||W + s B A|| folded into the GEMM operands once per forward, dm and the row-scaled dB of the backward
+# ------------------------------------------------------------------------------------------------
+def dora_fold(W, A_cat_T, B_blk, m, targets, r_pad: int, inv_norm, g, Wf, WfT, Bf, BfT, init: bool = False):
+    """One adapter group (st355_dora_fold): from the frozen W [N, K] and the packed bf16 operands the forward multiplies with (A_cat_T [K, K2], B_blk [N, K2], which
+    carries s) write inv_norm / g [N] fp32 (g = m / ||W + s B A||_row; init: m = the norm is written first, g = 1 exactly), Wf = bf16(g . W), WfT its transpose,
+    Bf = bf16(g . B_blk), BfT its transpose.  targets: [(n_off, N)] of the 1 .. 4 targets, rising; target i owns slab i of the K-extension."""
+    for t, nm in ((W, "W"), (A_cat_T, "A_cat_T"), (B_blk, "B_blk"), (Wf, "Wf"), (WfT, "WfT"), (Bf, "Bf"), (BfT, "BfT")):
+        _chk(t, BF16, nm)
+    for t, nm in ((m, "m"), (inv_norm, "inv_norm"), (g, "g")):
+        _chk(t, F32, nm)
+    if W.dim() != 2:
+        raise _l.St355Error(f"dora_fold: expected W [N, K], got {tuple(W.shape)}")
+    N, K = W.shape
+    K2 = B_blk.shape[1] if B_blk.dim() == 2 else -1
+    if tuple(A_cat_T.shape) != (K, K2) or tuple(B_blk.shape) != (N, K2) or tuple(Wf.shape) != (N, K) or tuple(WfT.shape) != (K, N) or tuple(Bf.shape) != (N, K2) \
+            or tuple(BfT.shape) != (K2, N) or any(t.numel() != N for t in (m, inv_norm, g)) \
+            or not all(t.is_contiguous() for t in (W, A_cat_T, B_blk, m, inv_norm, g, Wf, WfT, Bf, BfT)):
+        raise _l.St355Error(f"dora_fold: expected contiguous W [N, K], A_cat_T [K, K2], B_blk [N, K2], m / inv_norm / g [N], Wf [N, K], WfT [K, N], Bf [N, K2], BfT [K2, N] "
+                            f"(N = {N}, K = {K}, K2 = {K2})")
+    G = len(targets)
+    if not 1 <= G <= 4:
+        raise _l.St355Error(f"dora_fold: 1 .. 4 targets per group (got {G})")
+    n_off = (C.c_int32 * G)(*[int(o) for o, _ in targets])
+    n_cnt = (C.c_int32 * G)(*[int(n) for _, n in targets])
+    _l.check(_l.load().st355_dora_fold(_stream(), _ptr(W), _ptr(A_cat_T), _ptr(B_blk), _ptr(m), 1 if init else 0, _ptr(inv_norm), _ptr(g), _ptr(Wf), _ptr(WfT), _ptr(Bf),
+                                       _ptr(BfT), N, K, K2, G, n_off, n_cnt, int(r_pad)), "dora_fold")
+    return g
+
+
+def dora_y0_scratch(dev, M: int, N: int):
+    """[M, N] bf16 over the DoRA backward's scratch (the recomputed y0 = x W^T + s (x A^T) B^T of one adapted Linear; consumed by dora_dmag right away)"""
+    return _scratch("dora_y0", dev, 2 * M * N)[:2 * M * N].view(BF16).view(M, N)
+
+
+def dora_db_scratch(dev, N: int, rank: int):
+    """[N, rank] fp32 over the DoRA backward's second scratch (the unscaled s dy^T T of one target, consumed by dora_db_finish right away)"""
+    return _scratch("dora_db", dev, 4 * N * rank)[:4 * N * rank].view(F32).view(N, rank)
+
+
+def dora_dmag(dy, y0, inv_norm, dm, accumulate: bool = False):
+    """dm[n] (+)= inv_norm[n] sum_rows dy[row, n] y0[row, n] (st355_dora_dmag).  dy: compact [M, N] bf16 or a [B, rows, N] view of a joint buffer; y0 [M, N] bf16;
+    two-stage fixed-order reduction over 256-row chunks of the LOGICAL rows: a view and its compact copy give the same bits."""
+    L = _l.load()
+    _chk(dy, BF16, "dy"); _chk(y0, BF16, "y0"); _chk(inv_norm, F32, "inv_norm"); _chk(dm, F32, "dm")
+    M, N, ldd, seg, seg_s = _seg(dy, "dora_dmag: dy")
+    if y0.dim() != 2 or tuple(y0.shape) != (M, N) or inv_norm.numel() != N or dm.numel() != N or not (inv_norm.is_contiguous() and dm.is_contiguous()):
+        raise _l.St355Error(f"dora_dmag: expected y0 [{M}, {N}], contiguous inv_norm / dm [{N}]")
+    ldy = _rows(y0, "dora_dmag: y0")
+    if N % 8 or ldd % 8 or ldy % 8 or dy.data_ptr() % 16 or y0.data_ptr() % 16:
+        raise _l.St355Error(f"dora_dmag: N and the row strides must be multiples of 8, the operands 16-byte aligned (N = {N}, strides {ldd} / {ldy})")
+    ws = _scratch("dora_dmag", dy.device, L.st355_dora_dmag_workspace(M, N))
+    _l.check(L.st355_dora_dmag(_stream(), _ptr(dy), ldd, seg, seg_s, _ptr(y0), ldy, _ptr(inv_norm), _ptr(dm), M, N, 1 if accumulate else 0, _ptr(ws)), "dora_dmag")
+    return dm
+
+
+def dora_db_finish(P, g, gB, accumulate: bool = False):
+    """gB[n, :] (+)= g[n] P[n, :] (st355_dora_db_finish): P [N, rank] fp32 = s dy^T T from skinny_tn (accumulate=False), g [N] fp32, gB [N, rank] fp32"""
+    _chk(P, F32, "P"); _chk(g, F32, "g"); _chk(gB, F32, "gB")
+    if P.dim() != 2 or P.shape != gB.shape or g.numel() != P.shape[0] or not (P.is_contiguous() and gB.is_contiguous() and g.is_contiguous()):
+        raise _l.St355Error(f"dora_db_finish: expected contiguous P / gB [N, rank] and g [N], got {tuple(P.shape)}, {tuple(gB.shape)}, {tuple(g.shape)}")
+    _l.check(_l.load().st355_dora_db_finish(_stream(), _ptr(P), _ptr(g), _ptr(gB), P.shape[0], P.shape[1], 1 if accumulate else 0), "dora_db_finish")
+    return gB
+
+
+# ------------------------------------------------------------------------------------------------
 # AdaLN / RMSNorm + RoPE
 # ------------------------------------------------------------------------------------------------
 def ln_modulate_fwd(x, scale, shift, rows_per_batch: int, eps: float = 1e-6, out=None):

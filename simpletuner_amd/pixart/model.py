@@ -56,6 +56,7 @@ class PixartSigma(ModelFoundation):
             raise NotImplementedError("PixArt: a LoRA on the trunk together with the ControlNet branch is not built on the st355 path")
         comp = self.unwrap_model(self.model)
         self.lora_dropout_value()                 # (refuses lora_dropout > 0 by name: built for SD3)
+        self.use_dora_value()                     # (refuses use_dora by name: built for SD3)
         return comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),
                                      seed=int(getattr(self.config, "seed", 42) or 42) + 7, init_b_std=float(getattr(self.config, "lora_init_b_std", 0.0)))
 

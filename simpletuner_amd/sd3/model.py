@@ -22,6 +22,7 @@ class SD3(ModelFoundation):
     MODEL_CLASS = SD3Transformer2DModel
     MODEL_SUBFOLDER = "transformer"
     LORA_DROPOUT_BUILT = True
+    DORA_BUILT = True
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
     VAE_CONFIG = dict(latent_channels=16, scaling_factor=1.5305, shift_factor=0.0609, use_quant_conv=False)
@@ -53,7 +54,7 @@ class SD3(ModelFoundation):
                                        targets="default", seed=int(getattr(self.config, "seed", 42) or 42) + 7,
                                        init_b_std=float(getattr(self.config, "lora_init_b_std", 0.0)),
                                        dropout=self.lora_dropout_value(), dropout_seed=int(getattr(self.config, "seed", 42) or 42),
-                                       dropout_rank=int(getattr(self.accelerator, "process_index", 0) or 0))
+                                       dropout_rank=int(getattr(self.accelerator, "process_index", 0) or 0), dora=self.use_dora_value())
         comp.prepare_for_training()
         return params
 

@@ -40,6 +40,16 @@ def sincos_2d(embed_dim: int, grid_size: int, base_size: int, interpolation_scal
     return sincos_2d_hw(embed_dim, grid_size, grid_size, base_size, interpolation_scale)
 
 
+def _w(lin):
+    """the weight operand of an adapted Linear's forward GEMM: its own, or under DoRA the group's folded copy g . W"""
+    return lin.w if lin.lora is None else lin.lora.w_of(lin)
+
+
+def _wT(lin):
+    """likewise the K-major operand of its dgrad GEMM"""
+    return lin.wT if lin.lora is None else lin.lora.wT_of(lin)
+
+
 def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] = None):
     """one projection over the `rows`-row block of every sample as ONE problem: segmented operands when the block is tile-aligned (the 4096 image rows,
     engine.problems); otherwise (the 154 text rows) through compact copies of the joint-buffer operands — the rows are gathered before the
@@ -111,6 +121,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
 
         self.lora_groups: List[LoraGroup] = []
         self.lora_dropout: Optional[LoraDropout] = None          # add_lora_adapter(dropout > 0): applies to training forwards only
+        self.lora_dora = False                                   # add_lora_adapter(dora=True): part of the weight, applies to every forward
         self.lora_flat: Optional[torch.Tensor] = None
         self.lora_grad_flat: Optional[torch.Tensor] = None
         self._lora_params: List[nn.Parameter] = []
@@ -267,23 +278,32 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     # LoRA (peft naming), sd3/model.py:122 DEFAULT_LORA_TARGET = to_k,to_q,to_v,to_out.0
     # ------------------------------------------------------------------------------------------------
     def add_lora_adapter(self, rank: int = 32, alpha: Optional[float] = None, targets: str = "default", seed: int = 7, init_b_std: float = 0.0,
-                         dropout: float = 0.0, dropout_seed: int = 0, dropout_rank: int = 0, dropout_calls: int = 0):
+                         dropout: float = 0.0, dropout_seed: int = 0, dropout_rank: int = 0, dropout_calls: int = 0, dora: bool = False):
         """dropout: peft's `lora_dropout` (0 <= p < 1) — y = base(x) + (alpha / r) B A dropout(x) in training forwards, every adapted Linear with its own mask stream
-        (its index in the ordered target list below); dropout_seed / dropout_rank make the mask key, dropout_calls is the call counter's start (engine.LoraDropout)"""
+        (its index in the ordered target list below); dropout_seed / dropout_rank make the mask key, dropout_calls is the call counter's start (engine.LoraDropout).
+        dora: peft's `use_dora` — every adapted Linear gets a trainable magnitude vector m [out_features] (`<module>.lora_magnitude_vector.default.weight`, fp32, in
+        the adapter arena right behind all A / B tensors) and computes y = (m / ||W + s B A||_row) . (x W^T + s (x A^T) B^T) + b, the norm detached; m starts as the
+        norm of the freshly initialised adapter, so the first forward is the plain LoRA's (engine.LoraDora).  It applies to every forward, eval() included."""
         alpha = float(rank if alpha is None else alpha)
         dropout = float(dropout or 0.0)
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"lora_dropout must lie in [0, 1), got {dropout}")
+        if dora and dropout > 0.0:
+            raise NotImplementedError(f"use_dora with lora_dropout={dropout}: peft then feeds the dropped x to the base term of the DoRA correction, a different "
+                                      "computation that is not built on the st355 path; set --lora_dropout=0 or --use_dora=false")
         D, dev = self.D, self.device_
         plan = []
         self.lora_groups = []
         self.lora_dropout = LoraDropout(dropout, dropout_seed, dropout_rank, dev, dropout_calls) if dropout > 0.0 else None
+        self.lora_dora = bool(dora)
+        group_lins = []
 
         def group(lin, prefix, names, K):
             g = LoraGroup(K, lin.w.shape[0], [(prefix + n, j * (lin.w.shape[0] // len(names)), lin.w.shape[0] // len(names))
                                               for j, n in enumerate(names)], rank, alpha, dev, streams=range(len(plan), len(plan) + len(names)))
             lin.lora = g
             self.lora_groups.append(g)
+            group_lins.append(lin)
             for (name, n_off, N) in g.targets:
                 plan.append((g, name, N, K))
 
@@ -300,6 +320,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 if blk.to_add_out is not None:
                     group(blk.to_add_out, p, ["to_add_out"], D)
         total = sum(rank * K + N * rank for (_, _, N, K) in plan)
+        dora_lo = total                           # DoRA: the magnitudes follow all A / B tensors (flat_view of parameters and of gradients stays one run), before the heads
+        if dora:
+            total += sum(N for (_, _, N, _) in plan)
         ig_lo = total                             # Internal Guidance: the head's fp32 masters follow the adapters in the same arena (one run for the optimizer)
         if self._ig_block is not None:
             total += sum(math.prod(shp) for shp in internal_guidance_shapes(D))
@@ -328,6 +351,17 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
             g.flat_hi = off
             self._lora_params += [pa, pb]
+        if dora:
+            assert off == dora_lo
+            for g, lin in zip(self.lora_groups, group_lins):
+                g.enable_dora(lin, self.lora_flat[off:off + g.N_total], self.lora_grad_flat[off:off + g.N_total], off)
+                for (name, n_off, N) in g.targets:
+                    pm = nn.Parameter(self.lora_flat[off:off + N])
+                    attach(self, name + ".lora_magnitude_vector.default.weight", pm)
+                    self._lora_params.append(pm)
+                    off += N
+                g.pack()
+                g.fold(init=True)                    # m = ||W + s B A||_row of the fresh adapter (peft's DoraLinearLayer.update_layer): g = 1 at step 0
         if self._ig_block is not None:
             assert off == ig_lo
             ps, gs = [], []
@@ -388,7 +422,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         rpb = 1 if env.rpb_i == 1 else Si     # rows of the image stream that share one modulation row: the sample's (inside a TREAD route: its kept) rows, or 1 under tokenwise timesteps
         drop = getattr(env, "drop", None)      # LoRA dropout of this training forward (and of its recompute passes): the adapters' down projections draw masks
-        if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and img.is_contiguous() and txt.is_contiguous() and rpb == Si and drop is None:
+        if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and img.is_contiguous() and txt.is_contiguous() and rpb == Si and drop is None and not self.lora_dora:
             return self._block_fwd_c(blk, img, txt, env, save, ybuf)
 
         mi = env.mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
@@ -402,12 +436,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
         T_img = blk.qkv.lora.down(n_img, drop) if blk.qkv.lora is not None else None
         T_txt = blk.add_qkv.lora.down(n_txt, drop) if blk.add_qkv.lora is not None else None
-        kw_i = dict(a2=T_img, b2=blk.qkv.lora.B_blk) if T_img is not None else {}
-        kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_blk) if T_txt is not None else {}
+        kw_i = dict(a2=T_img, b2=blk.qkv.lora.B_fwd) if T_img is not None else {}
+        kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_fwd) if T_txt is not None else {}
         # the image stream (4096 rows per sample: tile-aligned) is ONE segmented problem over the joint buffer; the 154 text rows stay per sample
         after = []
-        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=blk.qkv.w, bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **kw_i), after)
-                         + _stream_problems(B, S, St, dict(a=n_txt, w=blk.add_qkv.w, bias=blk.add_qkv.b, out=rows_of(qkv, Si, St, B, S), **kw_t), after))
+        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=_w(blk.qkv), bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **kw_i), after)
+                         + _stream_problems(B, S, St, dict(a=n_txt, w=_w(blk.add_qkv), bias=blk.add_qkv.b, out=rows_of(qkv, Si, St, B, S), **kw_t), after))
         for f in after:
             f()
         Q = torch.empty(B, H, S, hd, dtype=BF16, device=dev); K = torch.empty_like(Q)
@@ -444,8 +478,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             else:
                 for pr in _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o), after):
                     ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-            kw_i.update(a2=T_o, b2=blk.to_out.lora.B_blk)
-        probs = _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.w, bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
+            kw_i.update(a2=T_o, b2=blk.to_out.lora.B_fwd)
+        probs = _stream_problems(B, S, Si, dict(a=O_i, w=_w(blk.to_out), bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
                                                 gate=mi[:, 2 * D:3 * D], rows_per_batch=rpb, **kw_i), after)
         if not blk.last:
             if T_ao is not None:
@@ -454,8 +488,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 else:
                     for pr in _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao), after):
                         ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-                kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_blk)
-            probs += _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.w, bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
+                kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_fwd)
+            probs += _stream_problems(B, S, St, dict(a=O_t, w=_w(blk.to_add_out), bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
                                                      aux_in=txt, gate=mt[:, 2 * D:3 * D], rows_per_batch=St, **kw_t), after)
         ops.gemm_grouped(probs)
         for f in after:
@@ -468,8 +502,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             Sip = (Si + 63) // 64 * 64
             n2a = ops.ln_modulate_fwd(img, mi9[:, 7 * D:8 * D], mi9[:, 6 * D:7 * D], Si)
             T2 = blk.qkv2.lora.down(n2a, drop) if blk.qkv2.lora is not None else None
-            kwq = dict(a2=T2, b2=blk.qkv2.lora.B_blk) if T2 is not None else {}
-            qkv2 = ops.gemm(n2a, blk.qkv2.w, bias=blk.qkv2.b, **kwq)
+            kwq = dict(a2=T2, b2=blk.qkv2.lora.B_fwd) if T2 is not None else {}
+            qkv2 = ops.gemm(n2a, _w(blk.qkv2), bias=blk.qkv2.b, **kwq)
             Q2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); K2 = torch.empty_like(Q2)
             mk2 = torch.zeros if Sip > Si else torch.empty
             Q2t = K2t = None
@@ -485,8 +519,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             T_o2 = None
             if blk.to_out2.lora is not None:
                 T_o2 = blk.to_out2.lora.down(O2, drop)
-                kw2.update(a2=T_o2, b2=blk.to_out2.lora.B_blk)
-            x1b_img = ops.gemm(O2, blk.to_out2.w, bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si, **kw2)
+                kw2.update(a2=T_o2, b2=blk.to_out2.lora.B_fwd)
+            x1b_img = ops.gemm(O2, _w(blk.to_out2), bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si, **kw2)
             d2 = SimpleNamespace(n2a=n2a, qkv2=qkv2, T2=T2, Q2=Q2, K2=K2, Q2t=Q2t, K2t=K2t, O2=O2, lse2b=lse2b, ya2=ya2, T_o2=T_o2, Sip=Sip)
             x1_img = x1b_img                       # what the MLP branch (and its residual) sees
         n2_i = ops.ln_modulate_fwd(x1_img, mi[:, 4 * D:5 * D], mi[:, 3 * D:4 * D], rpb)
@@ -633,6 +667,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         dev = self.device_
         for g in self.lora_groups:
             g.pack()
+            if g.dora is not None:          # DoRA: the row scale of the current A / B / m folded into W and B_blk, once per forward
+                g.fold()
         pos, cos, sin = self._tables(h, w, S, B)
         # ---- embeddings (sd3/transformer.py:623-700) ----
         patches = ops.patchify(latents, order=0).view(B * Si, 4 * C)
@@ -867,7 +903,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             drop = getattr(ctx.envs[li], "drop", None)      # LoRA dropout: the masked dA / dx kernels regenerate this forward's masks
             acc_, gs_ = self.accumulate_lora_grads, self.grad_sync
             if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous()) and rpb != 1 \
-                    and drop is None:
+                    and drop is None and not self.lora_dora:
                 # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then the rank-space adapter gradients from the gradients it left behind
                 d_img, d_txt, G = self._block_bwd_c(blk, sv, ctx.envs[li], mod, cos, sin, d_img, d_txt, li != 0)
                 pairs = [(blk.to_out, G.U_o, sv.T_o, G.dx1g_i, 0, Si)]
@@ -903,8 +939,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 d2, mi9 = sv.d2, mod[:, blk.mod_off:blk.mod_off + 9 * D]
                 dx1_i, dxg2 = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dres=d_img, gate=mi9[:, 8 * D:9 * D], want_gated=True)
                 lo2, lq2 = blk.to_out2.lora, blk.qkv2.lora
-                U2 = ops.gemm(dxg2, lo2.B_blk_T) if lo2 is not None else None
-                dO2 = ops.gemm(dxg2, blk.to_out2.wT, **(dict(a2=U2, b2=lo2.A_cat_T) if (U2 is not None and drop is None) else {}))
+                U2 = ops.gemm(dxg2, lo2.B_fwd_T) if lo2 is not None else None
+                dO2 = ops.gemm(dxg2, _wT(blk.to_out2), **(dict(a2=U2, b2=lo2.A_cat_T) if (U2 is not None and drop is None) else {}))
                 if lo2 is not None:
                     if drop is not None:
                         lo2.dx_add(dO2, U2, drop)
@@ -913,9 +949,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
                 ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
                 ops.qk_norm_rope_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, cos, sin, dqkv2, B, H, hd, Si, 0, Si)
-                Uq2 = ops.gemm(dqkv2, lq2.B_blk_T) if lq2 is not None else None
+                Uq2 = ops.gemm(dqkv2, lq2.B_fwd_T) if lq2 is not None else None
                 if li != 0:
-                    dn2a = ops.gemm(dqkv2, blk.qkv2.wT, **(dict(a2=Uq2, b2=lq2.A_cat_T) if (Uq2 is not None and drop is None) else {}))
+                    dn2a = ops.gemm(dqkv2, _wT(blk.qkv2), **(dict(a2=Uq2, b2=lq2.A_cat_T) if (Uq2 is not None and drop is None) else {}))
                     if lq2 is not None and drop is not None:
                         lq2.dx_add(dn2a, Uq2, drop)
                 if lq2 is not None:
@@ -927,14 +963,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             del g_i, dh_i, dn2_i
             # attention output projections -> dO rows of both streams (+ adapter grads); a context_pre_only block has no txt rows
             dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
-            U_i = ops.gemm(dx1g_i, blk.to_out.lora.B_blk_T) if blk.to_out.lora is not None else None
-            U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_blk_T) if (not blk.last and blk.to_add_out.lora is not None) else None
+            U_i = ops.gemm(dx1g_i, blk.to_out.lora.B_fwd_T) if blk.to_out.lora is not None else None
+            U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_fwd_T) if (not blk.last and blk.to_add_out.lora is not None) else None
             after = []
             kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T) if (U_i is not None and drop is None) else {}
-            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S), **kw_i), after)
+            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=_wT(blk.to_out), out=rows_of(dO, 0, Si, B, S), **kw_i), after)
             if not blk.last:
                 kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T) if (U_t is not None and drop is None) else {}
-                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S), **kw_t), after)
+                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=_wT(blk.to_add_out), out=rows_of(dO, Si, St, B, S), **kw_t), after)
             ops.gemm_grouped(probs)
             for f in after:
                 f()
@@ -967,11 +1003,11 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 kw = {}
                 if lin.lora is not None:
                     Us[name] = torch.empty(B * rows, lin.lora.B_blk_T.shape[0], dtype=BF16, device=dev)
-                    ops.gemm(dq, lin.lora.B_blk_T, out=Us[name])
+                    ops.gemm(dq, lin.lora.B_fwd_T, out=Us[name])
                     kw = dict(a2=Us[name], b2=lin.lora.A_cat_T) if drop is None else {}
                 if not first:
                     dns.append(torch.empty(B * rows, D, dtype=BF16, device=dev))
-                    probs.append(dict(a=dq, w=lin.wT, out=dns[-1], **kw))
+                    probs.append(dict(a=dq, w=_wT(lin), out=dns[-1], **kw))
             if probs:
                 ops.gemm_grouped(probs)
             if drop is not None and not first:         # the adapter term of the norm inputs' gradients, masked, before the norm backward reads them
