@@ -666,6 +666,28 @@ int st355_dora_dmag(void* stream, const void* dy, int64_t ldd, int64_t seg_rows,
 /* gB[n, r] (+)= g[n] P[n, r]: P [N, rank] fp32 contiguous = s dy^T T (st355_skinny_tn_seg, accumulate = 0), gB [N, rank] fp32 contiguous */
 int st355_dora_db_finish(void* stream, const float* P, const float* g, float* gB, int N, int rank, int accumulate);
 
+/* ---- Scheduled sampling with ReflexFlow (flow matching; common.py:6287-6318, scheduled_sampling/rollout.py:70-199; csrc/reflexflow.hip).  All tensors bf16
+ * [batch, per_sample] contiguous, per_sample % 8 == 0, batch < 65536.  Reductions run in two stages in a fixed order (bit-identical run to run), the second on
+ * the device; `workspace`: st355_reflexflow_workspace(batch, per_sample) bytes, 16-byte aligned. */
+int64_t st355_reflexflow_workspace(int64_t batch, int64_t per_sample);
+/* stats_out fp32 [batch, 4]: sum |clean - biased| (0 when clean / biased are NULL: they come together or not at all), sum p^2, sum tau^2, sum p tau with
+ * tau = noisy - latents; differences and products in fp32. */
+int st355_reflexflow_stats(void* stream, const void* pred, const void* noisy, const void* latents, const void* clean, const void* biased, float* stats_out,
+                           void* workspace, int64_t batch, int64_t per_sample);
+/* st355_cond_loss_masked (loss_type 0 / 1 / 2, huber_c [batch] NULL for l2, emask / mask_period, grad_scale) plus the ReflexFlow terms:
+ *   l_i <- l_i (1 + alpha e_i / max(stats[b, 0], 1e-6)), e = clean - biased (skipped when clean / biased are NULL or alpha == 0);  l_i <- l_i beta2;  the mask;
+ *   per_sample_out[b] = mean_i l_i + adr_out[b],  adr_out[b] = beta1 sum_i (p_i / pn - tau_i / tn)^2, pn = max(sqrt(stats[b, 1]), 1e-6), tn = max(sqrt(stats[b, 2]), 1e-6)
+ *   (unmasked; beta1 == 0: no term, noisy / latents may be NULL);  loss_out[0] = mean_b per_sample_out.
+ * dpred (bf16, may be NULL), rounded once = grad_scale d loss_out / d pred: the element term's gradient plus, for sqrt(stats[b, 1]) > 1e-6,
+ *   (2 beta1 / (batch pn)) [(u - th) - u (u . (u - th))], u = p / pn, th = tau / tn, u . (u - th) from the stats;  for a clamped norm 2 beta1 (u - th) / (batch 1e-6).
+ * adr_out may be NULL.  stats may be NULL when neither term needs them. */
+int st355_reflexflow_loss(void* stream, const void* pred, const void* target, const float* huber_c, int loss_type, const float* emask, int64_t mask_period,
+                          const void* noisy, const void* latents, const void* clean, const void* biased, const float* stats, float alpha, float beta1,
+                          float beta2, float* loss_out, float* per_sample_out, float* adr_out, void* dpred, void* workspace, int64_t batch,
+                          int64_t per_sample, float grad_scale);
+/* x[b, :] <- x[b, :] + dt[b] v[b, :] in place (the rollout's Euler update): dt fp32 [batch] on the device, fp32 arithmetic, one rounding.  x != v. */
+int st355_flow_euler_step(void* stream, void* x, const void* v, const float* dt, int64_t batch, int64_t per_sample);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

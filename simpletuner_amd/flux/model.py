@@ -51,6 +51,8 @@ class Flux(ModelFoundation):
     DEFAULT_MODEL_FLAVOUR = "dev"
     DEFAULT_LORA_TARGET = ["to_k", "to_q", "to_v", "to_out.0"]
     SUPPORTS_MUON_CLIP = True                                        # flux/model.py:50
+    # what _model_predict_single reads per sample (scheduled sampling's batch-1 forwards; `latents` for its shape)
+    ROLLOUT_BATCH_KEYS = ("latents", "prompt_embeds", "add_text_embeds", "encoder_attention_mask", "conditioning_packed_latents", "conditioning_ids")
 
     def convert_text_embed_for_pipeline(self, text_embedding: dict) -> dict:
         """flux/model.py:453-472: prompt / pooled embeddings (+ the text mask as `prompt_mask` only under flux_attention_masked_training)"""

@@ -292,6 +292,10 @@ class ModelFoundation(ExplorativeModelingMixin):
 
     # ---- prediction entry points; XM (off by default) expands the batch with K noise candidates first (flux/model.py:630-636, 940-946) ----
     def model_predict(self, prepared_batch: dict):
+        if prepared_batch.get("scheduled_sampling_plan") is not None and not prepared_batch.get("_scheduled_sampling_rolled"):
+            # a step loop that skips the rollout would train on the un-rolled batch with the plan's loss terms: refused, never a silently different computation
+            raise RuntimeError("scheduled_sampling_max_step_offset: the batch carries a scheduled_sampling_plan but the rollout has not run — call "
+                               "plugin.apply_scheduled_sampling_rollout(prepared_batch) between prepare_batch and model_predict (Trainer.train_step does)")
         return self._xm_wrapped(self._model_predict_single, prepared_batch)
 
     def controlnet_predict(self, prepared_batch: dict):
@@ -501,6 +505,61 @@ class ModelFoundation(ExplorativeModelingMixin):
             raise NotImplementedError("use_dora with lora_format=comfyui: the ComfyUI export of a DoRA adapter is not built on the st355 path; set "
                                       "--lora_format=diffusers")
         return True
+
+    ROLLOUT_BATCH_KEYS = None           # families with the scheduled-sampling rollout (Flux, SD3): the per-sample batch entries their model_predict reads
+
+    def scheduled_sampling_value(self):
+        """`scheduled_sampling_max_step_offset` / `scheduled_sampling_reflexflow` as the step takes them: (max offset, ReflexFlow on).  Applies the reference's
+        default-on rule (`_maybe_enable_reflexflow_default`, common.py:5376-5397: a positive offset on a flow-matching family sets the flag unless the user set it),
+        and refuses by the flag's name every configuration the rollout / the loss terms are not built for — never a silently different computation."""
+        cfg = self.config
+        try:
+            offset = float(getattr(cfg, "scheduled_sampling_max_step_offset", 0) or 0)
+        except Exception:
+            offset = 0.0
+        if (offset > 0 and getattr(cfg, "scheduled_sampling_reflexflow", None) is None and self.PREDICTION_TYPE is PredictionTypes.FLOW_MATCHING
+                and self.ROLLOUT_BATCH_KEYS is not None):
+            setattr(cfg, "scheduled_sampling_reflexflow", True)
+        reflex = bool(getattr(cfg, "scheduled_sampling_reflexflow", False))
+        if not (offset > 0 or reflex):
+            return 0, False
+        flag = f"scheduled_sampling_max_step_offset={getattr(cfg, 'scheduled_sampling_max_step_offset', 0)}" if offset > 0 else "scheduled_sampling_reflexflow"
+        if self.PREDICTION_TYPE is not PredictionTypes.FLOW_MATCHING or self.ROLLOUT_BATCH_KEYS is None:
+            raise NotImplementedError(f"{flag}: scheduled sampling is not built for {self.NAME} on the st355 path (built: Flux, SD3) — the epsilon / v rollout needs "
+                                      "skrample's samplers; unset scheduled_sampling_max_step_offset and scheduled_sampling_reflexflow")
+        if getattr(cfg, "hip_graph", False):
+            raise NotImplementedError(f"{flag} with hip_graph: the rollout is host-driven and its length is drawn per step, it cannot be captured")
+        tc = getattr(cfg, "tread_config", None)
+        if tc and (tc.get("routes", None) if isinstance(tc, dict) else getattr(tc, "routes", None)):
+            raise NotImplementedError(f"{flag} with TREAD routing: the reference's rollout forwards are training-mode forwards that route tokens, which the no-grad "
+                                      "route of the st355 path does not; not built")
+        # (as lora_dropout_value: a full fine-tune and lora_type=lycoris ignore lora_dropout, so no dropout would run there)
+        if (float(getattr(cfg, "lora_dropout", 0.0) or 0.0) > 0.0 and "lora" in str(getattr(cfg, "model_type", "lora"))
+                and str(getattr(cfg, "lora_type", "standard") or "standard").lower() == "standard"):
+            raise NotImplementedError(f"{flag} with lora_dropout={getattr(cfg, 'lora_dropout')}: the reference's rollout forwards are training-mode forwards that drop, "
+                                      "which the no-grad route of the st355 path does not; not built")
+        if getattr(cfg, "twinflow_enabled", False):
+            raise NotImplementedError(f"{flag} with twinflow_enabled: TwinFlow is not built on the st355 path")
+        if getattr(cfg, "controlnet", False):
+            raise NotImplementedError(f"{flag} with controlnet: the rollout through controlnet_predict is not built on the st355 path")
+        return int(offset), reflex
+
+    def _scheduled_sampling_refuse_tokenwise(self, batch: dict):
+        t = batch.get("timesteps")
+        if getattr(t, "ndim", 1) != 1:
+            raise NotImplementedError(f"scheduled_sampling_max_step_offset / scheduled_sampling_reflexflow with tokenwise timesteps {tuple(t.shape)}: the rollout "
+                                      "re-times whole samples and the ReflexFlow terms are per sample; not built on the st355 path")
+
+    def apply_scheduled_sampling_rollout(self, prepared_batch: dict) -> dict:
+        """trainer.py:6059 `apply_scheduled_sampling_rollout`, between prepare_batch and model_predict: a no-op without a plan"""
+        if not prepared_batch or prepared_batch.get("scheduled_sampling_plan") is None:
+            return prepared_batch
+        self.scheduled_sampling_value()
+        self._scheduled_sampling_refuse_tokenwise(prepared_batch)
+        from .scheduled_sampling import apply_flow_rollout
+        prepared_batch = apply_flow_rollout(self, prepared_batch, self.noise_schedule, self.config)
+        prepared_batch["_scheduled_sampling_rolled"] = True
+        return prepared_batch
 
     def lora_dropout_value(self) -> float:
         """`lora_dropout` (the reference builds every standard LoRA with LoraConfig(lora_dropout=...): common.py:1094-1104) as the family's add_lora_adapter takes
@@ -1233,6 +1292,15 @@ class ModelFoundation(ExplorativeModelingMixin):
             if self.PREDICTION_TYPE is PredictionTypes.V_PREDICTION:                  # get_velocity uses the un-perturbed noise (common.py:4649-4653)
                 batch["velocity_target"] = ops.ddpm_noise_mix(lat, noise, a, b, want_v=True)[1]
         batch.pop("noise_shape_ref", None)
+        ss_offset, ss_reflex = self.scheduled_sampling_value()                          # common.py:6013-6037: after the noisy latents exist
+        if ss_offset > 0 or ss_reflex:
+            self._scheduled_sampling_refuse_tokenwise(batch)
+        if ss_offset > 0 and batch.get("scheduled_sampling_plan") is None:              # (tests / parity runs inject a plan, like the noise)
+            from .scheduled_sampling import build_rollout_schedule, effective_probability, num_train_timesteps_of
+            batch["scheduled_sampling_plan"] = build_rollout_schedule(
+                num_train_timesteps=num_train_timesteps_of(self.noise_schedule), batch_size=lat.shape[0], max_step_offset=ss_offset, device=dev,
+                base_timesteps=batch["timesteps"], strategy=getattr(self.config, "scheduled_sampling_strategy", "uniform"),
+                apply_probability=effective_probability(self.config, state.get("global_step", 0)))
         return self.prepare_batch_conditions(batch=batch, state=state)
 
     def expand_sigmas(self, batch: dict) -> dict:
@@ -1262,7 +1330,7 @@ class ModelFoundation(ExplorativeModelingMixin):
             return prepared_batch["latents"]
         raise ValueError(f"Unknown prediction type {self.PREDICTION_TYPE}.")
 
-    def loss(self, prepared_batch: dict, model_output, apply_conditioning_mask: bool = True, _per_sample_only: bool = False, _row_weight=None):
+    def loss(self, prepared_batch: dict, model_output, apply_conditioning_mask: bool = True, _per_sample_only: bool = False, _row_weight=None, _logs=None):
         """common.py:6217-6430.  The two private switches serve XM (xm.py): `_per_sample_only` returns (weighted per-row losses [B] fp32, the row
         weights or None) without touching autograd; `_row_weight` replaces the row weights (it already carries the min-SNR factor)."""
         target = self.get_prediction_target(prepared_batch)
@@ -1293,9 +1361,37 @@ class ModelFoundation(ExplorativeModelingMixin):
                 p_, t_ = model_pred.detach().to(BF16), target.to(BF16)
                 per = ops.cond_loss(p_, t_, loss_type, huber_c, weight=weight, want_grad=False, emask=emask)[1]
             return per, weight
+        if self.PREDICTION_TYPE is PredictionTypes.FLOW_MATCHING and getattr(self.config, "scheduled_sampling_reflexflow", False):
+            self.scheduled_sampling_value()                                            # (the refusals, by the flag's name)
+            self._scheduled_sampling_refuse_tokenwise(prepared_batch)
+            return self._reflexflow_loss(prepared_batch, model_pred, target, loss_type, huber_c, emask, _logs)
         if loss_type == "l2" and emask is None:
             return _MSELossFn.apply(model_pred, target, weight)
         return _CondLossFn.apply(model_pred, target, loss_type, huber_c, weight, emask)
+
+    def _reflexflow_loss(self, prepared_batch: dict, model_pred, target, loss_type, huber_c, emask, logs=None):
+        """common.py:6287-6318 + 6426-6429, the flow-matching branch with `scheduled_sampling_reflexflow` truthy: the exposure weight from the rollout's cached
+        predictions (when both exist and alpha != 0), beta2, the mask, the per-sample mean, the ADR term against tau = noisy_latents - latents (post-rollout; present
+        with the flag alone, without a plan), the batch mean.  alpha / beta1 / beta2 are read with the reference's `or` idiom: alpha None / 0 -> 0, beta1 None / 0 -> 0,
+        beta2 None -> 1.  `logs` (a dict, loss_with_logs passes one): receives the ADR term's batch mean and the mean |exposure weight - 1| as device scalars."""
+        cfg = self.config
+        beta2 = getattr(cfg, "scheduled_sampling_reflexflow_beta2", 1.0)
+        beta2 = 1.0 if beta2 is None else float(beta2)
+        alpha = float(getattr(cfg, "scheduled_sampling_reflexflow_alpha", 1.0) or 0.0)
+        beta1 = float(getattr(cfg, "scheduled_sampling_reflexflow_beta1", 10.0) or 0.0)
+        clean, biased = prepared_batch.get("_reflexflow_clean_pred"), prepared_batch.get("_reflexflow_biased_pred")
+        if clean is None or biased is None:
+            clean = biased = None
+        noisy, latents = prepared_batch.get("noisy_latents"), prepared_batch.get("latents")
+        if noisy is None or latents is None:                                           # common.py:6308: the term needs both
+            beta1 = 0.0
+        loss, adr, stats = _ReflexFlowLossFn.apply(model_pred, target, noisy, latents, clean, biased, loss_type, huber_c, emask, alpha, beta1, beta2)
+        if logs is not None:
+            logs["reflexflow_adr"] = adr.mean()
+            if clean is not None and alpha != 0.0:
+                s_e = stats[:, 0]
+                logs["reflexflow_weight_deviation"] = (abs(alpha) * s_e / s_e.clamp_min(1e-6)).mean() / float(model_pred.numel() // model_pred.shape[0])
+        return loss
 
     def _conditioning_loss_mask(self, prepared_batch: dict, model_pred, apply_conditioning_mask: bool):
         """common.py:6402-6424: `loss_mask_type` (legacy: `conditioning_type`) "mask" multiplies the elementwise loss by the first channel of
@@ -1350,7 +1446,9 @@ class ModelFoundation(ExplorativeModelingMixin):
         k = model_output.get("xm_candidate_count") if isinstance(model_output, dict) else None
         if k:
             return self._xm_noise_loss_with_logs(prepared_batch, model_output, candidate_count=int(k), apply_conditioning_mask=apply_conditioning_mask)
-        return self.loss(prepared_batch, model_output, apply_conditioning_mask), None
+        logs = {}          # (ReflexFlow fills it with device scalars; read here as host floats, like auxiliary_loss's logs)
+        loss = self.loss(prepared_batch, model_output, apply_conditioning_mask, _logs=logs)
+        return loss, ({k: v.item() for k, v in logs.items()} or None)
 
     def auxiliary_loss(self, model_output, prepared_batch: dict, loss: torch.Tensor):
         """common.py:5364-5374 `_apply_layersync_regularizer`: loss - lambda * similarity, the two logs as host floats (layersync.py:55-58).  The similarity and its
@@ -1386,6 +1484,28 @@ class ModelFoundation(ExplorativeModelingMixin):
             loss = loss + ls_loss
             logs.update(layersync_loss=ls_loss.detach().item(), layersync_similarity=sim.detach().item())
         return loss, (logs or None)
+
+
+class _ReflexFlowLossFn(torch.autograd.Function):
+    """the ReflexFlow loss (ops.reflexflow_stats + ops.reflexflow_loss), gradient from the same kernel pass; also returns the ADR terms [B] and the stats [B, 4]"""
+
+    @staticmethod
+    def forward(ctx, pred, target, noisy, latents, clean, biased, loss_type, huber_c, emask, alpha, beta1, beta2):
+        to = lambda t: None if t is None else t.detach().to(BF16)
+        p_, n_, l_, c_, b_ = to(pred), to(noisy), to(latents), to(clean), to(biased)
+        if n_ is None or l_ is None:                     # (beta1 is 0 then: the kernels still take the operands' places)
+            n_ = l_ = p_
+        stats = ops.reflexflow_stats(p_, n_, l_, c_, b_)
+        loss, _per, adr, dpred = ops.reflexflow_loss(p_, to(target), n_, l_, stats, loss_type, huber_c, clean=c_, biased=b_, alpha=alpha, beta1=beta1, beta2=beta2,
+                                                     want_grad=True, emask=emask)
+        ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(adr, stats)
+        return loss.reshape(()), adr, stats
+
+    @staticmethod
+    def backward(ctx, g, _gadr, _gstats):
+        (dpred,) = ctx.saved_tensors
+        return ((dpred.float() * g).to(dpred.dtype) if g.numel() == 1 else dpred,) + (None,) * 11
 
 
 class _CondLossFn(torch.autograd.Function):

@@ -173,6 +173,93 @@ def cond_loss(pred, target, loss_type: str = "l2", huber_c=0.1, weight=None, wan
     return loss, per_sample, dpred
 
 
+def _rf_rows(ts, names):
+    """the [B, N] bf16 operands of the ReflexFlow ops: device tensors of one shape, N % 8 == 0, B < 65536; returns (contiguous tensors, B, N)"""
+    out = []
+    for t, name in zip(ts, names):
+        _chk(t, BF16, name)
+        if t.shape != ts[0].shape:
+            raise _l.St355Error(f"{name}: shape {tuple(t.shape)} differs from {names[0]}'s {tuple(ts[0].shape)}")
+        out.append(t.contiguous())
+    B = ts[0].shape[0]
+    N = ts[0].numel() // B
+    if N % 8 != 0 or not 0 < B < 65536:
+        raise _l.St355Error(f"{names[0]}: per-sample size {N} must be a multiple of 8 and the batch {B} below 65536")
+    return out, B, N
+
+
+def _rf_scratch(dev, B: int, N: int):
+    return _scratch("reflexflow", dev, _l.load().st355_reflexflow_workspace(B, N))
+
+
+def reflexflow_stats(pred, noisy, latents, clean=None, biased=None):
+    """fp32 [B, 4] per sample: sum |clean - biased| (0 without the pair), sum p^2, sum tau^2, sum p tau, tau = noisy - latents; fixed-order two-stage reduction"""
+    L = _l.load()
+    if (clean is None) != (biased is None):
+        raise _l.St355Error("reflexflow_stats: clean and biased come together or not at all")
+    pair = [clean, biased] if clean is not None else []
+    ts, B, N = _rf_rows([pred, noisy, latents] + pair, ["pred", "noisy", "latents", "clean", "biased"])
+    stats = torch.empty(B, 4, dtype=F32, device=pred.device)
+    ws = _rf_scratch(pred.device, B, N)
+    _l.check(L.st355_reflexflow_stats(_stream(), _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]) if pair else None, _ptr(ts[4]) if pair else None,
+                                      _ptr(stats), _ptr(ws), B, N), "reflexflow_stats")
+    return stats
+
+
+def reflexflow_loss(pred, target, noisy, latents, stats, loss_type: str = "l2", huber_c=0.1, clean=None, biased=None, alpha: float = 1.0, beta1: float = 10.0,
+                    beta2: float = 1.0, want_grad: bool = True, grad_scale: float = 1.0, emask=None):
+    """ops.cond_loss plus the ReflexFlow terms (common.py:6287-6318): the exposure weight 1 + alpha (clean - biased) / max(stats[:, 0], 1e-6) per element, beta2, the
+    mask, the per-sample mean, + beta1 * sum (p / |p| - tau / |tau|)^2 (norms clamped at 1e-6, from `stats` = reflexflow_stats(...)), the batch mean, and the fused
+    d(loss)/d(pred).  Returns (loss[1], per_sample[B], adr[B] (the term as added), dpred)."""
+    L = _l.load()
+    if (clean is None) != (biased is None):
+        raise _l.St355Error("reflexflow_loss: clean and biased come together or not at all")
+    pair = [clean, biased] if clean is not None else []
+    ts, B, N = _rf_rows([pred, target, noisy, latents] + pair, ["pred", "target", "noisy", "latents", "clean", "biased"])
+    _chk(stats, F32, "stats")
+    if tuple(stats.shape) != (B, 4) or not stats.is_contiguous():
+        raise _l.St355Error(f"stats: expected a contiguous fp32 [{B}, 4] tensor (reflexflow_stats), got {tuple(stats.shape)}")
+    dev = pred.device
+    loss = torch.empty(1, dtype=F32, device=dev)
+    per_sample = torch.empty(B, dtype=F32, device=dev)
+    adr = torch.empty(B, dtype=F32, device=dev)
+    dpred = torch.empty_like(ts[0]) if want_grad else None
+    if loss_type != "l2":
+        if not torch.is_tensor(huber_c):
+            huber_c = torch.full((B,), float(huber_c), dtype=F32, device=dev)
+        _chk(huber_c, F32, "huber_c")
+        huber_c = huber_c.contiguous()
+        if huber_c.numel() != B:
+            raise _l.St355Error(f"huber_c: expected {B} values, got {huber_c.numel()}")
+    else:
+        huber_c = None
+    period = 0
+    if emask is not None:
+        _chk(emask, F32, "emask")
+        emask = emask.reshape(B, -1).contiguous()
+        period = emask.shape[1]
+    ws = _rf_scratch(dev, B, N)
+    _l.check(L.st355_reflexflow_loss(_stream(), _ptr(ts[0]), _ptr(ts[1]), _ptr(huber_c), LOSS_TYPES[loss_type], _ptr(emask), period, _ptr(ts[2]), _ptr(ts[3]),
+                                     _ptr(ts[4]) if pair else None, _ptr(ts[5]) if pair else None, _ptr(stats), float(alpha), float(beta1), float(beta2),
+                                     _ptr(loss), _ptr(per_sample), _ptr(adr), _ptr(dpred), _ptr(ws), B, N, grad_scale), "reflexflow_loss")
+    return loss, per_sample, adr, dpred
+
+
+def flow_euler_step(x, v, dt):
+    """x[b] += dt[b] * v[b] in place (bf16 [B, ...] contiguous, dt fp32 [B] on the device): fp32 arithmetic, one rounding.  Returns x."""
+    L = _l.load()
+    _chk(x, BF16, "x"); _chk(v, BF16, "v"); _chk(dt, F32, "dt")
+    B = x.shape[0]
+    N = x.numel() // B
+    if not x.is_contiguous() or x.shape != v.shape or dt.numel() != B or N % 8 != 0:
+        raise _l.St355Error(f"flow_euler_step: x must be contiguous (it is updated in place), v of its shape, dt [{B}] and the per-sample size {N} a multiple of 8")
+    v = v.contiguous()
+    if v.data_ptr() == x.data_ptr():
+        raise _l.St355Error("flow_euler_step: x and v must be different buffers")
+    _l.check(L.st355_flow_euler_step(_stream(), _ptr(x), _ptr(v), _ptr(dt.contiguous()), B, N), "flow_euler_step")
+    return x
+
+
 def flux_pack(latents):
     L = _l.load()
     _chk(latents, BF16, "latents")

@@ -23,6 +23,7 @@ class SD3(ModelFoundation):
     MODEL_SUBFOLDER = "transformer"
     LORA_DROPOUT_BUILT = True
     DORA_BUILT = True
+    ROLLOUT_BATCH_KEYS = ("encoder_hidden_states", "add_text_embeds")          # what _model_predict_single reads per sample (scheduled sampling's batch-1 forwards)
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
     VAE_CONFIG = dict(latent_channels=16, scaling_factor=1.5305, shift_factor=0.0609, use_quant_conv=False)

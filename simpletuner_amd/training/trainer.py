@@ -212,6 +212,8 @@ class Trainer:
                 raise NotImplementedError("hip_graph: NextLat (nextlat_enabled) reads its logs on the host every step and cannot be captured")
             if getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
                 raise NotImplementedError("nextlat_enabled with XM noise candidates is not built on the st355 path")
+        if hasattr(self.model, "scheduled_sampling_value"):
+            self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
@@ -274,9 +276,12 @@ class Trainer:
             loss = self._graph_forward_backward(prepared)
             self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)
         else:
+            prepared = self.model.apply_scheduled_sampling_rollout(prepared)             # :6059 (a no-op without a plan)
             pred = self.model.model_predict(prepared)                                    # :7097 -> :6085
-            loss, _ = self.model.loss_with_logs(prepared, pred)
+            loss, loss_logs = self.model.loss_with_logs(prepared, pred)
             loss, self.last_aux_logs = self.model.auxiliary_loss(pred, prepared, loss)
+            if loss_logs and not (isinstance(pred, dict) and pred.get("xm_candidate_count")):      # ReflexFlow's logs, ahead of the regularisers' (XM's candidate logs stay where they were)
+                self.last_aux_logs = {**loss_logs, **(self.last_aux_logs or {})}
             if cfg.gradient_accumulation_steps > 1:
                 loss = loss / cfg.gradient_accumulation_steps
             self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)   # :7114 (C2)
