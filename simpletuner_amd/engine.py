@@ -3,6 +3,7 @@
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
   * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
   * `LoraDora`: a group's DoRA state (magnitudes, the row scale, the folded GEMM operands);
+  * `lin_w` / `lin_wT` / `lora_down` ... `lora_grads`: one adapter site of a block's forward / backward, phase by phase, a no-op without an adapter;
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
@@ -238,6 +239,46 @@ class LoraGroup:
 
 
 # ------------------------------------------------------------------------------------------------
+# one adapter site = a Linear (`lin.w`, `lin.wT`, `lin.lora`: its LoraGroup or None), phase by phase: the callers issue every site's down / up GEMM, then the
+# (grouped) base GEMM with the kwargs below, then the `lora_dx_finish`es, then the `lora_grads`.  Without an adapter (or with `lin` None) each does nothing.
+# ------------------------------------------------------------------------------------------------
+def lin_w(lin):
+    """the weight operand of an adapted Linear's forward GEMM: its own, or under DoRA the group's folded copy g . W"""
+    return lin.w if lin.lora is None else lin.lora.w_of(lin)
+
+
+def lin_wT(lin):
+    """likewise the K-major operand of its dgrad GEMM"""
+    return lin.wT if lin.lora is None else lin.lora.wT_of(lin)
+
+
+def lora_down(lin, x, drop=None, out=None):          # forward: T = x A_cat^T (LoraGroup.down)
+    return None if lin is None or lin.lora is None else lin.lora.down(x, drop, out=out)
+
+
+def lora_fwd_kw(lin, T) -> dict:                     # forward: the K-extension of the base GEMM, y += T B^T
+    return {} if T is None else dict(a2=T, b2=lin.lora.B_fwd)
+
+
+def lora_up(lin, dy, out=None):                      # backward: U = dy B [M, K2]
+    return None if lin is None or lin.lora is None else ops.gemm(dy, lin.lora.B_fwd_T, out=out)
+
+
+def lora_dx_kw(lin, U, drop) -> dict:                # backward: the K-extension of the dx GEMM, dx += U A — not under dropout: the mask sits between U and A
+    return dict(a2=U, b2=lin.lora.A_cat_T) if (U is not None and drop is None) else {}
+
+
+def lora_dx_finish(lin, dx, U, drop):                # backward, under dropout: that term, masked, added in place before anything consumes dx (LoraGroup.dx_add)
+    if U is not None and drop is not None:
+        lin.lora.dx_add(dx, U, drop)
+
+
+def lora_grads(lin, x, T, dy, U, accumulate: bool, sync=None, drop=None):          # backward: the adapter's own gradients (LoraGroup.grads)
+    if lin is not None and lin.lora is not None:
+        lin.lora.grads(x, T, dy, U, accumulate, sync, drop)
+
+
+# ------------------------------------------------------------------------------------------------
 # a stream's rows of a joint [B * S, C] buffer as GEMM operands
 # ------------------------------------------------------------------------------------------------
 def rows_of(joint, lo: int, rows: int, B: int, S: int):
@@ -299,9 +340,12 @@ class LayerSyncTap:
     G = d sim / d student (ops.layersync_fwd; the teacher is read as the view it is).  `inject(view, dsim)` right before the student block's own backward adds
     dsim * G to the gradient with respect to that block's output; dsim stays on the device (it carries -lambda, the accumulation division and any loss scale)."""
 
+    key = "layersync_similarity"
+
     def __init__(self, student: int, teacher: int):
         self.student, self.teacher = student, teacher
-        self.G = self.cos = self.sim = None
+        self.block = student                  # where the backward hooks in
+        self.G = self.cos = self.sim = self.output = None
 
     def tap(self, g: int, view):
         if g == self.student:
@@ -314,9 +358,16 @@ class LayerSyncTap:
             B, rows, D = view.shape
             ops.layersync_fwd(self.G.view(B, rows, D), view, self.G, self.cos, self.sim)
 
+    def finish(self, H: int, W: int):
+        self.output = self.sim
+        return self.output
+
     def inject(self, view, dsim):
         ops.layersync_inject(view, self.G, dsim.detach().to(F32))
         self.G = None
+
+    def backward(self, dsim, dx_view, accumulate: bool = False, sync=None):
+        self.inject(dx_view, dsim)            # nothing trains here: no gradients of its own to accumulate or hand to `sync`
 
 
 # ------------------------------------------------------------------------------------------------
@@ -370,9 +421,11 @@ class InternalGuidanceTap:
     right before block g's own backward fills the head's four gradient views and adds d loss / d h into the gradient with respect to that block's output
     (dx_view None: the block lies below the first one that trains, only the head's gradients are wanted), then hands the head's range to `sync`."""
 
+    key = "internal_guidance_prediction"
+
     def __init__(self, head: InternalGuidanceHead, channels: int = 16):
         self.head, self.block, self.channels = head, head.block, channels
-        self.xhat = self.rstd = self.y = None
+        self.xhat = self.rstd = self.y = self.output = None
         self.B = self.rows = 0
 
     def tap(self, g: int, view):
@@ -394,6 +447,10 @@ class InternalGuidanceTap:
             raise ValueError("Internal Guidance hidden-state token count does not match the diffusion target: "
                              f"tokens={self.rows}, patch_volume=4, spatial_shape=({H}, {W}).")
         return ops.unpatchify(self.y.view(self.B, self.rows, ops.IG_N), self.channels, H, W, order=1)
+
+    def finish(self, H: int, W: int):
+        self.output = self.prediction(H, W)
+        return self.output
 
     def backward(self, d_pred, dx_view, accumulate: bool = False, sync=None):
         h = self.head
@@ -511,9 +568,11 @@ class NextLatTap:
     respect to that block's output (dx_view None: the block lies below the first one that trains, only the predictor's gradients are wanted), then hands the
     predictor's range to `sync`.  The target rows are detached (nextlat.py:146): nothing flows into them."""
 
+    key = "nextlat_state_loss"
+
     def __init__(self, head: NextLatHead, mode: str = "smooth_l1"):
         self.head, self.block, self.mode = head, head.block, mode
-        self.xhat = self.rstd = self.U = self.A = self.psi = self.state_loss = None
+        self.xhat = self.rstd = self.U = self.A = self.psi = self.state_loss = self.output = None
         self.B = self.rows = 0
 
     def tap(self, g: int, view):
@@ -540,6 +599,10 @@ class NextLatTap:
         if self.state_loss is None:
             raise RuntimeError(f"NextLat: block {self.block} was never reached by the forward")
         return self.state_loss.view(())
+
+    def finish(self, H: int, W: int):
+        self.output = self.state()
+        return self.output
 
     def backward(self, d_state, dx_view, accumulate: bool = False, sync=None):
         h = self.head

@@ -25,8 +25,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
-                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty,
-                      problems, rows_of, sincos_2d_hw)
+                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lora_down, lora_dx_finish, lora_dx_kw,
+                      lora_fwd_kw, lora_grads, lora_up, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -38,16 +38,6 @@ _BLOCK_ABI = os.environ.get("ST355_BLOCK_ABI", "1") != "0"      # A/B switch: 0 
 def sincos_2d(embed_dim: int, grid_size: int, base_size: int, interpolation_scale: float = 1.0) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed: [grid_size^2, embed_dim] fp32 (w axis first, sin then cos per axis)"""
     return sincos_2d_hw(embed_dim, grid_size, grid_size, base_size, interpolation_scale)
-
-
-def _w(lin):
-    """the weight operand of an adapted Linear's forward GEMM: its own, or under DoRA the group's folded copy g . W"""
-    return lin.w if lin.lora is None else lin.lora.w_of(lin)
-
-
-def _wT(lin):
-    """likewise the K-major operand of its dgrad GEMM"""
-    return lin.wT if lin.lora is None else lin.lora.wT_of(lin)
 
 
 def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] = None):
@@ -70,7 +60,6 @@ def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] 
             q[k] = tmp
             after.append(lambda dst=v, src=tmp: dst.copy_(src.view(B, rows, -1)))      # scatter back into the joint rows
     return [q]
-
 
 
 class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
@@ -229,7 +218,6 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 self._reg("nextlat_predictor." + nm, frozen(t))
             if not self._counting:
                 self._nextlat_init_arena()
-
 
     # ------------------------------------------------------------------------------------------------
     # weights
@@ -422,7 +410,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         rpb = 1 if env.rpb_i == 1 else Si     # rows of the image stream that share one modulation row: the sample's (inside a TREAD route: its kept) rows, or 1 under tokenwise timesteps
         drop = getattr(env, "drop", None)      # LoRA dropout of this training forward (and of its recompute passes): the adapters' down projections draw masks
-        if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and img.is_contiguous() and txt.is_contiguous() and rpb == Si and drop is None and not self.lora_dora:
+        if self._c_entry_ok(blk, env, (img, txt), full=full, backward=False):
             return self._block_fwd_c(blk, img, txt, env, save, ybuf)
 
         mi = env.mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
@@ -434,14 +422,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mt = mod[:, blk.mod_off_c:blk.mod_off_c + 6 * D]
             n_txt = ops.ln_modulate_fwd(txt, mt[:, D:2 * D], mt[:, :D], St)
         qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
-        T_img = blk.qkv.lora.down(n_img, drop) if blk.qkv.lora is not None else None
-        T_txt = blk.add_qkv.lora.down(n_txt, drop) if blk.add_qkv.lora is not None else None
-        kw_i = dict(a2=T_img, b2=blk.qkv.lora.B_fwd) if T_img is not None else {}
-        kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_fwd) if T_txt is not None else {}
+        T_img, T_txt = lora_down(blk.qkv, n_img, drop), lora_down(blk.add_qkv, n_txt, drop)
         # the image stream (4096 rows per sample: tile-aligned) is ONE segmented problem over the joint buffer; the 154 text rows stay per sample
         after = []
-        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=_w(blk.qkv), bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **kw_i), after)
-                         + _stream_problems(B, S, St, dict(a=n_txt, w=_w(blk.add_qkv), bias=blk.add_qkv.b, out=rows_of(qkv, Si, St, B, S), **kw_t), after))
+        ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=lin_w(blk.qkv), bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **lora_fwd_kw(blk.qkv, T_img)), after)
+                         + _stream_problems(B, S, St, dict(a=n_txt, w=lin_w(blk.add_qkv), bias=blk.add_qkv.b, out=rows_of(qkv, Si, St, B, S),
+                                                           **lora_fwd_kw(blk.add_qkv, T_txt)), after))
         for f in after:
             f()
         Q = torch.empty(B, H, S, hd, dtype=BF16, device=dev); K = torch.empty_like(Q)
@@ -459,38 +445,32 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         del Vt
         x1_img = torch.empty(B * Si, D, dtype=BF16, device=dev)
         x1_txt = None if blk.last else torch.empty(B * St, D, dtype=BF16, device=dev)
-        T_o = torch.empty(B * Si, blk.to_out.lora.K2, dtype=BF16, device=dev) if blk.to_out.lora is not None else None
-        T_ao = (torch.empty(B * St, blk.to_add_out.lora.K2, dtype=BF16, device=dev)
-                if (not blk.last and blk.to_add_out.lora is not None) else None)
         ya_i, ya_t = ybuf(B * Si), (None if blk.last else ybuf(B * St))
         O_i, O_t = rows_of(O, 0, Si, B, S), rows_of(O, Si, St, B, S)
-        kw_i, kw_t = {}, {}
-        if ya_i is not None:
-            kw_i["aux_out"] = ya_i
-        if ya_t is not None:
-            kw_t["aux_out"] = ya_t
         after = []
         if B > 1 and St % 256:
             O_t = O_t.reshape(B * St, D)                                  # the text rows of the attention output, gathered once for both uses below
-        if T_o is not None:
+
+        def down_rows(lin, x, rows):
+            """lora_down over one stream's rows of the joint attention output: undropped, the plain GEMM in the operand form of the projection itself"""
+            if lin is None or lin.lora is None:
+                return None
+            T = torch.empty(B * rows, lin.lora.K2, dtype=BF16, device=dev)
             if drop is not None:
-                blk.to_out.lora.down(O_i, drop, out=T_o)                  # (the view as it is: the mask follows the logical row b * Si + s)
+                lora_down(lin, x, drop, out=T)                            # (the view as it is: the mask follows the logical row b * rows + s)
             else:
-                for pr in _stream_problems(B, S, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o), after):
+                for pr in _stream_problems(B, S, rows, dict(a=x, w=lin.lora.A_cat, out=T), after):
                     ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-            kw_i.update(a2=T_o, b2=blk.to_out.lora.B_fwd)
-        probs = _stream_problems(B, S, Si, dict(a=O_i, w=_w(blk.to_out), bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
-                                                gate=mi[:, 2 * D:3 * D], rows_per_batch=rpb, **kw_i), after)
+            return T
+
+        aux = lambda y: {} if y is None else dict(aux_out=y)
+        T_o = down_rows(blk.to_out, O_i, Si)
+        probs = _stream_problems(B, S, Si, dict(a=O_i, w=lin_w(blk.to_out), bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
+                                                gate=mi[:, 2 * D:3 * D], rows_per_batch=rpb, **aux(ya_i), **lora_fwd_kw(blk.to_out, T_o)), after)
+        T_ao = down_rows(blk.to_add_out, O_t, St)                         # (a context_pre_only block has no to_add_out)
         if not blk.last:
-            if T_ao is not None:
-                if drop is not None:
-                    blk.to_add_out.lora.down(O_t, drop, out=T_ao)
-                else:
-                    for pr in _stream_problems(B, S, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao), after):
-                        ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-                kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_fwd)
-            probs += _stream_problems(B, S, St, dict(a=O_t, w=_w(blk.to_add_out), bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
-                                                     aux_in=txt, gate=mt[:, 2 * D:3 * D], rows_per_batch=St, **kw_t), after)
+            probs += _stream_problems(B, S, St, dict(a=O_t, w=lin_w(blk.to_add_out), bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
+                                                     aux_in=txt, gate=mt[:, 2 * D:3 * D], rows_per_batch=St, **aux(ya_t), **lora_fwd_kw(blk.to_add_out, T_ao)), after)
         ops.gemm_grouped(probs)
         for f in after:
             f()
@@ -501,9 +481,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mi9 = mod[:, blk.mod_off:blk.mod_off + 9 * D]                        # (dual blocks never run tokenwise: refused in _engine_forward)
             Sip = (Si + 63) // 64 * 64
             n2a = ops.ln_modulate_fwd(img, mi9[:, 7 * D:8 * D], mi9[:, 6 * D:7 * D], Si)
-            T2 = blk.qkv2.lora.down(n2a, drop) if blk.qkv2.lora is not None else None
-            kwq = dict(a2=T2, b2=blk.qkv2.lora.B_fwd) if T2 is not None else {}
-            qkv2 = ops.gemm(n2a, _w(blk.qkv2), bias=blk.qkv2.b, **kwq)
+            T2 = lora_down(blk.qkv2, n2a, drop)
+            qkv2 = ops.gemm(n2a, lin_w(blk.qkv2), bias=blk.qkv2.b, **lora_fwd_kw(blk.qkv2, T2))
             Q2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); K2 = torch.empty_like(Q2)
             mk2 = torch.zeros if Sip > Si else torch.empty
             Q2t = K2t = None
@@ -515,20 +494,16 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ops.attn_fwd(Q2, K2, V2t, O2, lse2b, B, H, Si, Sip, hd, scale)
             del V2t
             ya2 = ybuf(B * Si)
-            kw2 = dict(aux_out=ya2) if ya2 is not None else {}
-            T_o2 = None
-            if blk.to_out2.lora is not None:
-                T_o2 = blk.to_out2.lora.down(O2, drop)
-                kw2.update(a2=T_o2, b2=blk.to_out2.lora.B_fwd)
-            x1b_img = ops.gemm(O2, _w(blk.to_out2), bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si, **kw2)
+            T_o2 = lora_down(blk.to_out2, O2, drop)
+            x1b_img = ops.gemm(O2, lin_w(blk.to_out2), bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si,
+                               **aux(ya2), **lora_fwd_kw(blk.to_out2, T_o2))
             d2 = SimpleNamespace(n2a=n2a, qkv2=qkv2, T2=T2, Q2=Q2, K2=K2, Q2t=Q2t, K2t=K2t, O2=O2, lse2b=lse2b, ya2=ya2, T_o2=T_o2, Sip=Sip)
             x1_img = x1b_img                       # what the MLP branch (and its residual) sees
         n2_i = ops.ln_modulate_fwd(x1_img, mi[:, 4 * D:5 * D], mi[:, 3 * D:4 * D], rpb)
         hpre_img = torch.empty(B * Si, 4 * D, dtype=BF16, device=dev)
         hpre_txt = x2_txt = n2_t = h_t = None
         yf_i, yf_t = ybuf(B * Si), (None if blk.last else ybuf(B * St))
-        kf_i = dict(aux_out=yf_i) if yf_i is not None else {}
-        kf_t = dict(aux_out=yf_t) if yf_t is not None else {}
+        kf_i, kf_t = aux(yf_i), aux(yf_t)
         if blk.last:
             h_i = ops.gemm(n2_i, blk.ff1.w, bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img)
             x2_img = ops.gemm(h_i, blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D],
@@ -557,6 +532,24 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if g is None:
             return 0, 0, None, None, None, None
         return g.K2, getattr(g, "k2_real", 0), g.A_cat, g.B_blk, g.A_cat_T, g.B_blk_T
+
+    def _c_entry_ok(self, blk, env, streams, *, full: bool, backward: bool, sv=None) -> bool:
+        """may this block go through its C entry (st355_block_sd3_joint_fwd / _bwd) instead of the host-sequenced form?  `streams`: the (img, txt) inputs of the
+        forward, the (d_img, d_txt | None) gradients of the backward.  Every form: the switch is on, a regular block (the entries know no attn2), the
+        transposing-LDS attention backward (the entries keep no head-major Q^T / K^T copies), contiguous streams (they take plain pointers).
+          forward                 one modulation row per sample (rpb == Si; tokenwise timesteps index it per token), no LoRA dropout and no DoRA (the entries
+                                  sequence neither the masked rank-space kernels nor the folded operands)
+          backward                the activations come from a forward that kept no Q^T / K^T (sv.Qt is None)
+          backward, LoRA          as the forward, the tokenwise test on the step's own rows-per-batch (rpb != 1)
+          backward, full          no trainable q / k RMSNorm weights (SD3.5): their gradients ride in the host form's RMSNorm backward pass"""
+        if not (_BLOCK_ABI and not blk.dual and ops.ATTN_TR and all(t is None or t.is_contiguous() for t in streams)):
+            return False
+        plain_lora = getattr(env, "drop", None) is None and not self.lora_dora
+        if not backward:
+            return (1 if env.rpb_i == 1 else env.Si) == env.Si and plain_lora
+        if not full:
+            return sv.Qt is None and env.rpb_i != 1 and plain_lora
+        return sv.Qt is None and blk.norm_q is None and blk.norm_k is None and blk.norm_added_q is None and blk.norm_added_k is None
 
     def _block_fwd_c(self, blk, img, txt, env, save: bool, ybuf):
         """_block_fwd through st355_block_sd3_joint_fwd: ONE C call sequences the launches of the host-side form below on the same operands —
@@ -657,6 +650,238 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         G.dq_t = G.c_txt if G.c_txt is not None else compact(rows_of(G.dqkv, Si, St, B, S), B, St)
         return d_img_out, d_txt_out, G
 
+    def _block_bwd(self, ctx, li: int, blk, sv, env, grads):
+        """frozen-base LoRA backward of one block (the block_bwd of _walk_blocks_bwd): (d_img, d_txt) with respect to its outputs -> with respect to its inputs,
+        and the adapters' gradients.  Block 0 stops at the adapters: the embedders below it are frozen."""
+        D, H, hd, dev = self.D, self.H, self.hd, self.device_
+        B, St, mod, cos, sin = ctx.B, ctx.St, ctx.mod, ctx.cos, ctx.sin
+        Si, S, Sp = env.Si, env.S, env.Sp                # (inside a TREAD route Si is the kept-token count)
+        scale = 1.0 / math.sqrt(hd)
+        d_img, d_txt = grads
+        grads.clear()
+        drop = getattr(env, "drop", None)      # LoRA dropout: the masked dA / dx kernels regenerate this forward's masks
+        acc_, gs_ = self.accumulate_lora_grads, self.grad_sync
+
+        def o_rows(lin, lo, rows):
+            """this stream's rows of the joint attention output as an adapter-gradient operand: read in place when tile-aligned (image rows), else a compact copy"""
+            return None if lin is None or lin.lora is None else compact(rows_of(sv.O, lo, rows, B, S), B, rows)
+
+        if self._c_entry_ok(blk, env, (d_img, d_txt), full=False, backward=True, sv=sv):
+            # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then the rank-space adapter gradients from the gradients it left behind
+            d_img, d_txt, G = self._block_bwd_c(blk, sv, env, mod, cos, sin, d_img, d_txt, li != 0)
+            lora_grads(blk.to_out, o_rows(blk.to_out, 0, Si), sv.T_o, G.dx1g_i, G.U_o, acc_, gs_)
+            lora_grads(blk.to_add_out, o_rows(blk.to_add_out, Si, St), sv.T_ao, G.dx1g_t, G.U_ao, acc_, gs_)
+            lora_grads(blk.qkv, sv.n_img, sv.T_img, G.dq_i, G.U_q, acc_, gs_)
+            lora_grads(blk.add_qkv, sv.n_txt, sv.T_txt, G.dq_t, G.U_a, acc_, gs_)
+            return d_img, d_txt
+        mi = ctx.mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
+        mt = mod[:, blk.mod_off_c:blk.mod_off_c + (2 if blk.last else 6) * D]
+        rpb_i = 1 if ctx.rpb_i == 1 else Si
+        g_i = ops.scale_cols(d_img, mi[:, 5 * D:6 * D], rpb_i)
+        if blk.last:
+            dh_i = ops.gemm(g_i, blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
+            dn2_i = ops.gemm(dh_i, blk.ff1.wT)
+            dx1_t = dx1g_t = None
+        else:
+            g_t = ops.scale_cols(d_txt, mt[:, 5 * D:6 * D], St)
+            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img),
+                                           dict(a=g_t, w=blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)])
+            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT), dict(a=dh_t, w=blk.ffc1.wT)])
+            dx1_t, dx1g_t = ops.ln_modulate_bwd(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dres=d_txt, gate=mt[:, 2 * D:3 * D], want_gated=True)
+            del g_t, dh_t, dn2_t
+        dn2a = None
+        if blk.dual:
+            # the MLP's LayerNorm read the stream AFTER the attn2 residual: its gated gradient feeds attn2's output projection, the un-gated one is the
+            # gradient of the stream after the joint-attention residual (dx1) — attn2 first, then the joint attention as for a regular block
+            d2, mi9 = sv.d2, mod[:, blk.mod_off:blk.mod_off + 9 * D]
+            dx1_i, dxg2 = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dres=d_img, gate=mi9[:, 8 * D:9 * D], want_gated=True)
+            U2 = lora_up(blk.to_out2, dxg2)
+            dO2 = ops.gemm(dxg2, lin_wT(blk.to_out2), **lora_dx_kw(blk.to_out2, U2, drop))
+            lora_dx_finish(blk.to_out2, dO2, U2, drop)
+            lora_grads(blk.to_out2, d2.O2, d2.T_o2, dxg2, U2, acc_, gs_, drop)
+            dqkv2 = torch.empty(B * Si, 3 * D, dtype=BF16, device=dev)
+            dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
+            ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
+            ops.qk_norm_rope_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, cos, sin, dqkv2, B, H, hd, Si, 0, Si)
+            Uq2 = lora_up(blk.qkv2, dqkv2)
+            if li != 0:
+                dn2a = ops.gemm(dqkv2, lin_wT(blk.qkv2), **lora_dx_kw(blk.qkv2, Uq2, drop))
+                lora_dx_finish(blk.qkv2, dn2a, Uq2, drop)
+            lora_grads(blk.qkv2, d2.n2a, d2.T2, dqkv2, Uq2, acc_, gs_, drop)
+            dx1g_i = ops.scale_cols(dx1_i, mi[:, 2 * D:3 * D], Si)
+            del dxg2, dO2, dQ2, dK2, dqkv2, U2, Uq2, d2
+        else:
+            dx1_i, dx1g_i = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], rpb_i, dres=d_img, gate=mi[:, 2 * D:3 * D], want_gated=True)
+        del g_i, dh_i, dn2_i
+        # attention output projections -> dO rows of both streams (+ adapter grads); a context_pre_only block has no txt rows (and no to_add_out)
+        dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
+        dO_i, dO_t = rows_of(dO, 0, Si, B, S), rows_of(dO, Si, St, B, S)
+        U_i, U_t = lora_up(blk.to_out, dx1g_i), lora_up(blk.to_add_out, dx1g_t)
+        after = []
+        probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=lin_wT(blk.to_out), out=dO_i, **lora_dx_kw(blk.to_out, U_i, drop)), after)
+        if not blk.last:
+            probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=lin_wT(blk.to_add_out), out=dO_t, **lora_dx_kw(blk.to_add_out, U_t, drop)), after)
+        ops.gemm_grouped(probs)
+        for f in after:
+            f()
+        lora_dx_finish(blk.to_out, dO_i, U_i, drop)               # the adapter term of dO, masked, before the attention backward reads it (the joint buffer's rows in place)
+        lora_dx_finish(blk.to_add_out, dO_t, U_t, drop)
+        lora_grads(blk.to_out, o_rows(blk.to_out, 0, Si), sv.T_o, dx1g_i, U_i, acc_, gs_, drop)
+        lora_grads(blk.to_add_out, o_rows(blk.to_add_out, Si, St), sv.T_ao, dx1g_t, U_t, acc_, gs_, drop)
+        del dx1g_i, dx1g_t, U_i, U_t, dO_i, dO_t
+        dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
+        dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
+        ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * D:], sv.O, dO, sv.lse2, dQ, dK, dqkv[:, 2 * D:], B, H, S, Sp, hd, scale)
+        ops.qk_norm_rope_bwd(dQ, dK, sv.qkv, blk.norm_q, blk.norm_k, cos, sin, dqkv, B, H, hd, Si, 0, S)
+        ops.qk_norm_rope_bwd(dQ, dK, sv.qkv, blk.norm_added_q, blk.norm_added_k, cos, sin, dqkv, B, H, hd, St, Si, S)
+        del dQ, dK, dO
+        # the two streams' rows of the joint dqkv: the image rows in place (segmented operands), the 154 text rows as a compact copy
+        sites = [(blk.qkv, compact(rows_of(dqkv, 0, Si, B, S), B, Si), sv.n_img, sv.T_img, Si),
+                 (blk.add_qkv, compact(rows_of(dqkv, Si, St, B, S), B, St), sv.n_txt, sv.T_txt, St)]
+        Us = [lora_up(lin, dq) for (lin, dq, _, _, _) in sites]
+        if li != 0:               # (block 0: frozen embedders below, only the adapter gradients remain)
+            dns = [torch.empty(B * rows, D, dtype=BF16, device=dev) for (_, _, _, _, rows) in sites]
+            ops.gemm_grouped([dict(a=dq, w=lin_wT(lin), out=dn_, **lora_dx_kw(lin, U, drop)) for (lin, dq, _, _, _), U, dn_ in zip(sites, Us, dns)])
+            for (lin, _, _, _, _), U, dn_ in zip(sites, Us, dns):      # the adapter term of the norm inputs' gradients, masked, before the norm backward reads them
+                lora_dx_finish(lin, dn_, U, drop)
+        for (lin, dq, n_in, T_, _), U in zip(sites, Us):
+            lora_grads(lin, n_in, T_, dq, U, acc_, gs_, drop)
+        if li != 0:
+            d_img, _ = ops.ln_modulate_bwd(dns[0], sv.img, mi[:, D:2 * D], rpb_i, dres=dx1_i)
+            if dn2a is not None:             # the second reader of LN(img): attn2's modulated input (scale_msa2)
+                d_img, _ = ops.ln_modulate_bwd(dn2a, sv.img, mod[:, blk.mod_off + 7 * D:blk.mod_off + 8 * D], Si, dres=d_img)
+            d_txt, _ = ops.ln_modulate_bwd(dns[1], sv.txt, mt[:, :D] if blk.last else mt[:, D:2 * D], St, dres=dx1_t)
+        return d_img, d_txt
+
+    def _block_bwd_full(self, ctx, fb, blk, sv, env, grads):
+        """full fine-tune backward of one block (the block_bwd of _walk_blocks_bwd): (d_img, d_txt) with respect to its outputs -> with respect to its inputs, and
+        every weight / bias / modulation gradient of the block (fb: the backward's FullGrads)"""
+        D, H, hd, dev = self.D, self.H, self.hd, self.device_
+        B, St, mod, cos, sin = ctx.B, ctx.St, ctx.mod, ctx.cos, ctx.sin
+        Si, S, Sp = env.Si, env.S, env.Sp                # (inside a TREAD route Si is the kept-token count)
+        scale = 1.0 / math.sqrt(hd)
+        dmod, wgrad = fb.dmod, fb.wgrad
+        d_img, d_txt = grads
+        grads.clear()
+
+        def qk_bwd(dQ_, dK_, qkv_, wq, wk, dqkv_, rows, pos0, S_, gq, gk):
+            """RMSNorm (+ identity RoPE) backward of one stream's q / k; with norm weights (SD3.5) also their gradients (sd3/transformer.py:155-165)"""
+            if wq is None and wk is None:
+                ops.qk_norm_rope_bwd(dQ_, dK_, qkv_, wq, wk, cos, sin, dqkv_, B, H, hd, rows, pos0, S_)
+            else:
+                ops.qk_norm_rope_bwd_wgrad(dQ_, dK_, qkv_, wq, wk, cos, sin, dqkv_, B, H, hd, rows, pos0, S_, gq, gk)
+
+        def grad_rows(t, lo, n, seg: bool = False):
+            """rows [lo, lo+n) of every batch element of a joint [B*S, C] buffer as a weight-gradient operand.  seg: in place — a [B, n, C] strided view, the
+            segmented-contraction form of st355_gemm_tn_seg_bf16 — when n is a whole number of 64-row K-tiles (the image rows of every bucket); else (the text
+            rows, and callers that also read the operand as a plain matrix) a compact copy, its row count zero-tailed to 64 (pad64 takes it as is)"""
+            if B == 1:
+                return t[lo:lo + n]
+            v = t.view(B, S, -1)[:, lo:lo + n]
+            if seg and n % 64 == 0 and n >= 128:
+                return v
+            o = pad64_empty(B * n, t.shape[1], dev)
+            o.view(B, n, -1).copy_(v)
+            return o
+
+        if self._c_entry_ok(blk, env, (d_img, d_txt), full=True, backward=True, sv=sv):
+            # the data path as ONE C entry point (st355_block_sd3_joint_bwd).  Every bias / modulation-shift / -scale / gate gradient of the block is written by the
+            # entry itself — the column sums ride in its scale_cols and LayerNorm-backward passes, csrc/stats.hip; only the weight gradients are left, taken from
+            # the gradients it kept
+            d_img, d_txt, G = self._block_bwd_c(blk, sv, env, mod, cos, sin, d_img, d_txt, True, dmod=dmod)
+            wgrad(blk.ff2, G.g_i, sv.h_i, bias=False)
+            wgrad(blk.ff1, G.dh_i, sv.n2_i, bias=False)
+            if not blk.last:
+                wgrad(blk.ffc2, G.g_t, sv.h_t, bias=False)
+                wgrad(blk.ffc1, G.dh_t, sv.n2_t, bias=False)
+            wgrad(blk.to_out, G.dx1g_i, grad_rows(sv.O, 0, Si, seg=True), bias=False)
+            if not blk.last:
+                wgrad(blk.to_add_out, G.dx1g_t, grad_rows(sv.O, Si, St), bias=False)
+            wgrad(blk.qkv, G.c_img if G.c_img is not None else grad_rows(G.dqkv, 0, Si, seg=True), sv.n_img, bias=False)       # (c_*: the compact copy the entry left)
+            wgrad(blk.add_qkv, G.c_txt if G.c_txt is not None else grad_rows(G.dqkv, Si, St), sv.n_txt, bias=False)
+            return d_img, d_txt
+        mi = mod[:, blk.mod_off:blk.mod_off + 6 * D]; dmi = dmod[:, blk.mod_off:blk.mod_off + 6 * D]
+        nct = 2 if blk.last else 6
+        mt = mod[:, blk.mod_off_c:blk.mod_off_c + nct * D]; dmt = dmod[:, blk.mod_off_c:blk.mod_off_c + nct * D]
+        # ---- MLP branch (host-sequenced form: SD3.5 dual-attention blocks, trainable q / k norms, ST355_BLOCK_ABI=0).  Every modulation / gate / bias
+        # gradient rides in the pass that streams its operands — the same fused entry points the C block sequences (csrc/stats.hip) ----
+        g_i = ops.scale_cols_stats(d_img, mi[:, 5 * D:6 * D], Si, y_branch=sv.yf_i, d_gate=dmi[:, 5 * D:6 * D], d_bias=blk.ff2.gb)     # + d gate_mlp, d b_ff2
+        wgrad(blk.ff2, g_i, sv.h_i, bias=False)
+        dh_i = ops.gemm(g_i, blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
+        wgrad(blk.ff1, dh_i, sv.n2_i, bias=False)
+        dn2_i = ops.gemm(dh_i, blk.ff1.wT)
+        dn2a = None
+        if blk.dual:
+            d2 = sv.d2
+            mi9 = mod[:, blk.mod_off:blk.mod_off + 9 * D]; dmi9 = dmod[:, blk.mod_off:blk.mod_off + 9 * D]
+            # + d shift_mlp, d scale_mlp, d gate_msa2 = sum d x1 * y_attn2, d b_to_out2 = sum gate_msa2 * d x1
+            dx1_i, dxg2 = ops.ln_modulate_bwd_stats(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dmi[:, 3 * D:4 * D], dmi[:, 4 * D:5 * D], dres=d_img,
+                                                    gate=mi9[:, 8 * D:9 * D], y_branch=d2.ya2, d_gate=dmi9[:, 8 * D:9 * D], d_bias=blk.to_out2.gb, want_gated=True)
+            ops.colsum_rows(dh_i, Si, Si, B, blk.ff1.gb)
+            wgrad(blk.to_out2, dxg2, d2.O2, bias=False)
+            dO2 = ops.gemm(dxg2, blk.to_out2.wT)
+            dqkv2 = torch.empty(B * Si, 3 * D, dtype=BF16, device=dev)
+            dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
+            ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
+            qk_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, dqkv2, Si, 0, Si, blk.g_norm_q2, blk.g_norm_k2)
+            wgrad(blk.qkv2, dqkv2, d2.n2a)
+            dn2a = ops.gemm(dqkv2, blk.qkv2.wT)
+            dx1g_i = ops.scale_cols_stats(dx1_i, mi[:, 2 * D:3 * D], Si, y_branch=sv.ya_i, d_gate=dmi[:, 2 * D:3 * D], d_bias=blk.to_out.gb)   # + d gate_msa, d b_to_out
+            del dxg2, dO2, dQ2, dK2, dqkv2, d2
+        else:
+            # + d shift_mlp, d scale_mlp, d gate_msa = sum d x1 * y_attn, d b_to_out = sum gate_msa * d x1
+            dx1_i, dx1g_i = ops.ln_modulate_bwd_stats(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dmi[:, 3 * D:4 * D], dmi[:, 4 * D:5 * D], dres=d_img,
+                                                      gate=mi[:, 2 * D:3 * D], y_branch=sv.ya_i, d_gate=dmi[:, 2 * D:3 * D], d_bias=blk.to_out.gb, want_gated=True)
+            ops.colsum_rows(dh_i, Si, Si, B, blk.ff1.gb)
+        del g_i, dh_i, dn2_i
+        dx1_t = dx1g_t = None
+        if not blk.last:
+            g_t = ops.scale_cols_stats(d_txt, mt[:, 5 * D:6 * D], St, y_branch=sv.yf_t, d_gate=dmt[:, 5 * D:6 * D], d_bias=blk.ffc2.gb)
+            wgrad(blk.ffc2, g_t, sv.h_t, bias=False)
+            dh_t = ops.gemm(g_t, blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)
+            wgrad(blk.ffc1, dh_t, sv.n2_t, bias=False)
+            dn2_t = ops.gemm(dh_t, blk.ffc1.wT)
+            dx1_t, dx1g_t = ops.ln_modulate_bwd_stats(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dmt[:, 3 * D:4 * D], dmt[:, 4 * D:5 * D], dres=d_txt,
+                                                      gate=mt[:, 2 * D:3 * D], y_branch=sv.ya_t, d_gate=dmt[:, 2 * D:3 * D], d_bias=blk.to_add_out.gb, want_gated=True)
+            ops.colsum_rows(dh_t, St, St, B, blk.ffc1.gb)
+            del g_t, dh_t, dn2_t
+        # ---- attention output projections ----
+        O_i = grad_rows(sv.O, 0, Si)
+        wgrad(blk.to_out, dx1g_i, O_i, bias=False)
+        dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
+        after = []
+        probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S)), after)
+        if not blk.last:
+            probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S)), after)
+        ops.gemm_grouped(probs)
+        for f in after:
+            f()
+        if not blk.last:
+            wgrad(blk.to_add_out, dx1g_t, grad_rows(sv.O, Si, St), bias=False)
+        del dx1g_i, dx1g_t, O_i
+        # ---- attention ----
+        dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
+        dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
+        ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * D:], sv.O, dO, sv.lse2, dQ, dK, dqkv[:, 2 * D:], B, H, S, Sp, hd, scale)
+        qk_bwd(dQ, dK, sv.qkv, blk.norm_q, blk.norm_k, dqkv, Si, 0, S, blk.g_norm_q, blk.g_norm_k)
+        qk_bwd(dQ, dK, sv.qkv, blk.norm_added_q, blk.norm_added_k, dqkv, St, Si, S, blk.g_norm_added_q, blk.g_norm_added_k)
+        del dQ, dK, dO
+        ops.colsum_rows(dqkv, Si, S, B, blk.qkv.gb)                    # d b_qkv / d b_add_qkv: each stream's rows of the joint dqkv, summed in place
+        ops.colsum_rows(dqkv[Si:], St, S, B, blk.add_qkv.gb)
+        dq_i, dq_t = grad_rows(dqkv, 0, Si), grad_rows(dqkv, Si, St)
+        wgrad(blk.qkv, dq_i, sv.n_img, bias=False)
+        wgrad(blk.add_qkv, dq_t, sv.n_txt, bias=False)
+        dn_i, dn_t = ops.gemm_grouped([dict(a=dq_i, w=blk.qkv.wT), dict(a=dq_t, w=blk.add_qkv.wT)])
+        d_img, _ = ops.ln_modulate_bwd_stats(dn_i, sv.img, mi[:, D:2 * D], Si, dmi[:, :D], dmi[:, D:2 * D], dres=dx1_i)      # + d shift_msa, d scale_msa
+        if dn2a is not None:                  # the second reader of LN(img): attn2's modulated input (shift_msa2, scale_msa2)
+            d_img, _ = ops.ln_modulate_bwd_stats(dn2a, sv.img, mod[:, blk.mod_off + 7 * D:blk.mod_off + 8 * D], Si, dmi9[:, 6 * D:7 * D], dmi9[:, 7 * D:8 * D],
+                                                 dres=d_img)
+        if blk.last:                          # AdaLayerNormContinuous: chunks (scale, shift)
+            d_txt, _ = ops.ln_modulate_bwd_stats(dn_t, sv.txt, mt[:, :D], St, dmt[:, D:2 * D], dmt[:, :D], dres=None)
+        else:
+            d_txt, _ = ops.ln_modulate_bwd_stats(dn_t, sv.txt, mt[:, D:2 * D], St, dmt[:, :D], dmt[:, D:2 * D], dres=dx1_t)
+        return d_img, d_txt
+
     def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False, want_ig: bool = False):
         D, H, hd = self.D, self.H, self.hd
         B, C, Hh, Ww = latents.shape
@@ -710,7 +935,6 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ctx = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, mod=mod, mod_i=mod_i, rpb_i=rpb_i, blocks=[], C=C, Hh=Hh, Ww=Ww)
         if full and save:
             ctx.emb = SimpleNamespace(patches=patches, enc2d=enc2d, tproj=tproj, t1=t1, st1=st1, pooled=pooled_b, p1=p1, sp1=sp1, temb=temb, st=st)
-        ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         scale = 1.0 / math.sqrt(hd)
         # LoRA dropout: training forwards only (validation sampling and eval() forwards are the p = 0 computation).  The call counter advances here, once per
         # training forward — the blocks below, their recompute passes and the backward all read the value it advanced to
@@ -733,25 +957,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             from ..training.checkpoint_plan import per_block as _per_block
             ctx.segs = _per_block(len(self.blocks), bool(self.gradient_checkpointing), self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride)
         ctx.envs, ctx.route_start, ctx.route_end = [env] * len(self.blocks), {}, {}
-        ls = None
-        if save and self._layersync is not None:
-            if self._tread_router is not None:
-                raise NotImplementedError("LayerSync under TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
-            if tokenwise:
-                raise NotImplementedError("LayerSync with tokenwise timesteps is not built on the st355 path")
-            ls = ctx.ls = LayerSyncTap(*self._layersync)
-        ig = None
-        if self._ig_block is not None and (save or want_ig):
-            if save and self._tread_router is not None:
-                raise NotImplementedError("Internal Guidance under TREAD routing (the routed block's token count no longer matches the diffusion target) is not built on the st355 path")
-            ig = ctx.ig = InternalGuidanceTap(self._ig_head(), self.out_channels)
-        elif want_ig:
-            raise ValueError("The transformer does not have an internal_guidance_head.")          # internal_guidance.py:405
-        nl = None
-        if self._nl_block is not None and save:
-            if self._tread_router is not None:
-                raise NotImplementedError("NextLat under TREAD routing (the routed block's token rows are no longer neighbours in the sequence) is not built on the st355 path")
-            nl = ctx.nl = NextLatTap(self._nl_head(), self._nl_mode)
+        ctx.taps = self._make_taps(save, want_ig, tokenwise)
         rp, info, saved, env_cur = 0, None, None, env
         for (s0, n, ck) in ctx.segs:
             for bi in range(s0, s0 + n):
@@ -766,12 +972,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     ctx.ck[s0] = (img, txt)
                 ctx.envs[bi] = env_cur
                 img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, env_cur, save and not ck)
-                if ls is not None:                            # LayerSync: the block's image-stream output (the recompute pass, _recompute_segment, never taps)
-                    ls.tap(bi, img.view(B, Si, D))
-                if ig is not None:                            # Internal Guidance: the head on this block's image-stream output (the recompute pass never taps)
-                    ig.tap(bi, img.view(B, Si, D))
-                if nl is not None:                            # NextLat: the predictor on this block's image-stream output (the recompute pass never taps)
-                    nl.tap(bi, img.view(B, Si, D))
+                for tap in ctx.taps:                          # each on this block's image-stream output (the recompute pass, _recompute_segment, never taps)
+                    tap.tap(bi, img.view(B, Si, D))
                 if info is not None and bi == routes[rp]["end_layer_idx"]:
                     full_seq = saved.clone()                                                        # TREADRouter.end_route(original_x=saved)
                     ops.scatter_rows(img.view(B, env_cur.Si, D), info.keep_i32(), full_seq.view(B, Si, D))
@@ -787,11 +989,31 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ctx.x_img_final = img
             if full:
                 ctx.n_out = n_out
-        if ig is not None:
-            ctx.ig_pred = ig.prediction(Hh, Ww)
-        if nl is not None:
-            ctx.nl_state = nl.state()
+        for tap in ctx.taps:
+            tap.finish(Hh, Ww)
         return ops.unpatchify(out.view(B, Si, -1), self.out_channels, Hh, Ww, order=1), ctx
+
+    def _make_taps(self, save: bool, want_ig: bool, tokenwise: bool) -> list:
+        """the per-forward taps of the configured regularisers, in their launch order: LayerSync, Internal Guidance, NextLat (engine.py: `tap` after every block of
+        the saving forward, `finish` after the output head, `backward` right before the backward of block `tap.block`; `key` names the extra output)"""
+        taps, routed = [], self._tread_router is not None
+        if save and self._layersync is not None:
+            if routed:
+                raise NotImplementedError("LayerSync under TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
+            if tokenwise:
+                raise NotImplementedError("LayerSync with tokenwise timesteps is not built on the st355 path")
+            taps.append(LayerSyncTap(*self._layersync))
+        if self._ig_block is not None and (save or want_ig):
+            if save and routed:
+                raise NotImplementedError("Internal Guidance under TREAD routing (the routed block's token count no longer matches the diffusion target) is not built on the st355 path")
+            taps.append(InternalGuidanceTap(self._ig_head(), self.out_channels))
+        elif want_ig:
+            raise ValueError("The transformer does not have an internal_guidance_head.")          # internal_guidance.py:405
+        if self._nl_block is not None and save:
+            if routed:
+                raise NotImplementedError("NextLat under TREAD routing (the routed block's token rows are no longer neighbours in the sequence) is not built on the st355 path")
+            taps.append(NextLatTap(self._nl_head(), self._nl_mode))
+        return taps
 
     def set_internal_guidance(self, block_index):
         """Internal Guidance (helpers/training/internal_guidance.py; the reference captures `layer_{i}` at sd3/transformer.py:872): the 0-based joint block whose
@@ -863,170 +1085,46 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for bi in range(s0, s0 + n):
             img, txt, ctx.blocks[bi] = self._block_fwd(self.blocks[bi], img, txt, ctx.envs[bi], True)
 
-    def _engine_backward(self, ctx, dout, dsim=None, d_ig=None, d_nl=None):
-        """dsim: upstream gradient of the LayerSync similarity (set_layersync), added into the dX chain at the student block's output; d_ig: upstream gradient of the
-        Internal Guidance prediction (set_internal_guidance), taken by the head's backward right before its block's own; d_nl: upstream gradient of the NextLat
-        state loss (set_nextlat), likewise"""
-        if not self._prepared:
-            raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
-        D, H, hd = self.D, self.H, self.hd
-        B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
-        dev = self.device_
-        scale = 1.0 / math.sqrt(hd)
-        dpk = ops.patchify(dout.to(BF16).contiguous(), order=1).view(B * Si, -1)
-        mod_i, rpb = ctx.mod_i, ctx.rpb_i          # the image stream's modulation rows: per sample, or per token under tokenwise timesteps (rows_per_batch = 1)
-        mo = mod_i[:, self.mod_off_out:self.mod_off_out + 2 * D]
-        dn = ops.gemm(dpk, self.l_out.wT)
-        d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], rpb)
-        d_txt = None
-        del dn, dpk
-        ls, ig, nl = getattr(ctx, "ls", None), getattr(ctx, "ig", None), getattr(ctx, "nl", None)
+    def _walk_blocks_bwd(self, ctx, grads, d_taps, taps_kw, block_bwd):
+        """the backward walk over the block stack, last block first.  `grads` = [d_img, d_txt] above the last block on entry (d_txt None: the last block is
+        context_pre_only), below block 0 on return — a list, here and towards the callee, so that no caller's frame keeps a gradient alive that its consumer is
+        done with.  Per block: recompute its checkpointed segment when its activations are gone; the taps' backwards (d_taps: the upstream gradient of each of
+        ctx.taps' outputs, taps_kw: (accumulate, sync)) add into d_img at their blocks; a TREAD route is entered at its END — the routed blocks see only the kept
+        tokens' gradient rows — and left at its START, where the skipped tokens keep the gradient they had at the route's end;
+        `block_bwd(li, blk, sv, env, grads) -> (d_img, d_txt)` does the block's own work: it EMPTIES `grads` as it takes the two, and `sv` (popped from ctx.blocks)
+        dies with the call."""
+        B, D = ctx.B, self.D
+        d_full = None
         for li in range(len(self.blocks) - 1, -1, -1):
             if ctx.blocks[li] is None:
                 self._recompute_segment(ctx, li)
-            if ls is not None and li == ls.student:
-                ls.inject(d_img.view(B, ctx.Si, D), dsim)
-            if ig is not None and li == ig.block:
-                ig.backward(d_ig, d_img.view(B, ctx.Si, D), self.accumulate_lora_grads, self.grad_sync)
-            if nl is not None and li == nl.block:
-                nl.backward(d_nl, d_img.view(B, ctx.Si, D), self.accumulate_lora_grads, self.grad_sync)
-            if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
-                r_info = ctx.route_end[li]
-                d_full = d_img
-                d_img = ops.gather_rows(d_full.view(B, ctx.Si, D), r_info.keep_i32()).view(-1, D)
-            Si, S, Sp = ctx.envs[li].Si, ctx.envs[li].S, ctx.envs[li].Sp
-            blk, sv = self.blocks[li], ctx.blocks[li]
+            for tap, d in zip(ctx.taps, d_taps):
+                if li == tap.block:
+                    tap.backward(d, grads[0].view(B, ctx.Si, D), *taps_kw)
+            if li in ctx.route_end:
+                d_full = grads[0]
+                grads[0] = ops.gather_rows(d_full.view(B, ctx.Si, D), ctx.route_end[li].keep_i32()).view(-1, D)
+            env, sv = ctx.envs[li], ctx.blocks[li]
             ctx.blocks[li] = None
-            mi = mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
-            mt = mod[:, blk.mod_off_c:blk.mod_off_c + (2 if blk.last else 6) * D]
-            rpb_i = rpb if rpb == 1 else Si             # (inside a TREAD route Si is the kept-token count)
-            drop = getattr(ctx.envs[li], "drop", None)      # LoRA dropout: the masked dA / dx kernels regenerate this forward's masks
-            acc_, gs_ = self.accumulate_lora_grads, self.grad_sync
-            if _BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous()) and rpb != 1 \
-                    and drop is None and not self.lora_dora:
-                # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then the rank-space adapter gradients from the gradients it left behind
-                d_img, d_txt, G = self._block_bwd_c(blk, sv, ctx.envs[li], mod, cos, sin, d_img, d_txt, li != 0)
-                pairs = [(blk.to_out, G.U_o, sv.T_o, G.dx1g_i, 0, Si)]
-                if not blk.last:
-                    pairs.append((blk.to_add_out, G.U_ao, sv.T_ao, G.dx1g_t, Si, St))
-                for (lin, U, T_, dxg, lo, rows) in pairs:
-                    if lin.lora is not None:
-                        lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
-                for (lin, dq, n_in, T_, U) in ((blk.qkv, G.dq_i, sv.n_img, sv.T_img, G.U_q), (blk.add_qkv, G.dq_t, sv.n_txt, sv.T_txt, G.U_a)):
-                    if lin.lora is not None:
-                        lin.lora.grads(n_in, T_, dq, U, self.accumulate_lora_grads, self.grad_sync)
-                del sv, G
-                if li in ctx.route_start and d_img is not None:
-                    ops.scatter_rows(d_img.view(B, Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
-                    d_img, d_full = d_full, None
-                continue
-            g_i = ops.scale_cols(d_img, mi[:, 5 * D:6 * D], rpb_i)
-            if blk.last:
-                dh_i = ops.gemm(g_i, blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
-                dn2_i = ops.gemm(dh_i, blk.ff1.wT)
-                dx1_t = dx1g_t = None
-            else:
-                g_t = ops.scale_cols(d_txt, mt[:, 5 * D:6 * D], St)
-                dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img),
-                                               dict(a=g_t, w=blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)])
-                dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT), dict(a=dh_t, w=blk.ffc1.wT)])
-                dx1_t, dx1g_t = ops.ln_modulate_bwd(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dres=d_txt, gate=mt[:, 2 * D:3 * D], want_gated=True)
-                del g_t, dh_t, dn2_t
-            dn2a = None
-            if blk.dual:
-                # the MLP's LayerNorm read the stream AFTER the attn2 residual: its gated gradient feeds attn2's output projection, the un-gated one is the
-                # gradient of the stream after the joint-attention residual (dx1) — attn2 first, then the joint attention as for a regular block
-                d2, mi9 = sv.d2, mod[:, blk.mod_off:blk.mod_off + 9 * D]
-                dx1_i, dxg2 = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dres=d_img, gate=mi9[:, 8 * D:9 * D], want_gated=True)
-                lo2, lq2 = blk.to_out2.lora, blk.qkv2.lora
-                U2 = ops.gemm(dxg2, lo2.B_fwd_T) if lo2 is not None else None
-                dO2 = ops.gemm(dxg2, _wT(blk.to_out2), **(dict(a2=U2, b2=lo2.A_cat_T) if (U2 is not None and drop is None) else {}))
-                if lo2 is not None:
-                    if drop is not None:
-                        lo2.dx_add(dO2, U2, drop)
-                    lo2.grads(d2.O2, d2.T_o2, dxg2, U2, acc_, gs_, drop)
-                dqkv2 = torch.empty(B * Si, 3 * D, dtype=BF16, device=dev)
-                dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
-                ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
-                ops.qk_norm_rope_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, cos, sin, dqkv2, B, H, hd, Si, 0, Si)
-                Uq2 = ops.gemm(dqkv2, lq2.B_fwd_T) if lq2 is not None else None
-                if li != 0:
-                    dn2a = ops.gemm(dqkv2, _wT(blk.qkv2), **(dict(a2=Uq2, b2=lq2.A_cat_T) if (Uq2 is not None and drop is None) else {}))
-                    if lq2 is not None and drop is not None:
-                        lq2.dx_add(dn2a, Uq2, drop)
-                if lq2 is not None:
-                    lq2.grads(d2.n2a, d2.T2, dqkv2, Uq2, acc_, gs_, drop)
-                dx1g_i = ops.scale_cols(dx1_i, mi[:, 2 * D:3 * D], Si)
-                del dxg2, dO2, dQ2, dK2, dqkv2, U2, Uq2, d2
-            else:
-                dx1_i, dx1g_i = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], rpb_i, dres=d_img, gate=mi[:, 2 * D:3 * D], want_gated=True)
-            del g_i, dh_i, dn2_i
-            # attention output projections -> dO rows of both streams (+ adapter grads); a context_pre_only block has no txt rows
-            dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
-            U_i = ops.gemm(dx1g_i, blk.to_out.lora.B_fwd_T) if blk.to_out.lora is not None else None
-            U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_fwd_T) if (not blk.last and blk.to_add_out.lora is not None) else None
-            after = []
-            kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T) if (U_i is not None and drop is None) else {}
-            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=_wT(blk.to_out), out=rows_of(dO, 0, Si, B, S), **kw_i), after)
-            if not blk.last:
-                kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T) if (U_t is not None and drop is None) else {}
-                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=_wT(blk.to_add_out), out=rows_of(dO, Si, St, B, S), **kw_t), after)
-            ops.gemm_grouped(probs)
-            for f in after:
-                f()
-            if drop is not None:               # the adapter term of dO, masked, before the attention backward reads it (each stream's rows of the joint buffer in place)
-                if U_i is not None:
-                    blk.to_out.lora.dx_add(rows_of(dO, 0, Si, B, S), U_i, drop)
-                if U_t is not None:
-                    blk.to_add_out.lora.dx_add(rows_of(dO, Si, St, B, S), U_t, drop)
-            pairs = [(blk.to_out, U_i, sv.T_o, dx1g_i, 0, Si)]
-            if not blk.last:
-                pairs.append((blk.to_add_out, U_t, sv.T_ao, dx1g_t, Si, St))
-            for (lin, U, T_, dxg, lo, rows) in pairs:
-                if lin.lora is not None:       # this stream's rows of the joint attention output: read in place when tile-aligned (image rows), else a compact copy
-                    lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, acc_, gs_, drop)
-            del dx1g_i, dx1g_t, U_i, U_t
-            dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
-            dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
-            ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * D:], sv.O, dO, sv.lse2, dQ, dK, dqkv[:, 2 * D:], B, H, S, Sp, hd, scale)
-            ops.qk_norm_rope_bwd(dQ, dK, sv.qkv, blk.norm_q, blk.norm_k, cos, sin, dqkv, B, H, hd, Si, 0, S)
-            ops.qk_norm_rope_bwd(dQ, dK, sv.qkv, blk.norm_added_q, blk.norm_added_k, cos, sin, dqkv, B, H, hd, St, Si, S)
-            del dQ, dK, dO
-            first = li == 0
-            # the two streams' rows of the joint dqkv: the image rows in place (segmented operands), the 154 text rows as a compact copy
-            dq_i = compact(rows_of(dqkv, 0, Si, B, S), B, Si); dq_t = compact(rows_of(dqkv, Si, St, B, S), B, St)
-            streams = [("img", blk.qkv, dq_i, sv.n_img, sv.T_img, Si), ("txt", blk.add_qkv, dq_t, sv.n_txt, sv.T_txt, St)]
-            if first:
-                streams = [s_ for s_ in streams if s_[1].lora is not None]     # frozen embedders: only adapter grads remain
-            probs, Us, dns = [], {}, []
-            for (name, lin, dq, n_in, T_, rows) in streams:
-                kw = {}
-                if lin.lora is not None:
-                    Us[name] = torch.empty(B * rows, lin.lora.B_blk_T.shape[0], dtype=BF16, device=dev)
-                    ops.gemm(dq, lin.lora.B_fwd_T, out=Us[name])
-                    kw = dict(a2=Us[name], b2=lin.lora.A_cat_T) if drop is None else {}
-                if not first:
-                    dns.append(torch.empty(B * rows, D, dtype=BF16, device=dev))
-                    probs.append(dict(a=dq, w=_wT(lin), out=dns[-1], **kw))
-            if probs:
-                ops.gemm_grouped(probs)
-            if drop is not None and not first:         # the adapter term of the norm inputs' gradients, masked, before the norm backward reads them
-                for (name, lin, dq, n_in, T_, rows), dn_ in zip(streams, dns):
-                    if lin.lora is not None:
-                        lin.lora.dx_add(dn_, Us[name], drop)
-            for (name, lin, dq, n_in, T_, rows) in streams:
-                if lin.lora is not None:
-                    lin.lora.grads(n_in, T_, dq, Us[name], acc_, gs_, drop)
-            if not first:
-                d_img, _ = ops.ln_modulate_bwd(dns[0], sv.img, mi[:, D:2 * D], rpb_i, dres=dx1_i)
-                if dn2a is not None:             # the second reader of LN(img): attn2's modulated input (scale_msa2)
-                    d_img, _ = ops.ln_modulate_bwd(dn2a, sv.img, mod[:, blk.mod_off + 7 * D:blk.mod_off + 8 * D], Si, dres=d_img)
-                c_scale = mt[:, :D] if blk.last else mt[:, D:2 * D]
-                d_txt, _ = ops.ln_modulate_bwd(dns[1], sv.txt, c_scale, St, dres=dx1_t)
-            del dqkv, sv, dns
-            if li in ctx.route_start and d_img is not None:   # ... and leaves it at its START: skipped tokens keep the gradient they had at the route's end
-                ops.scatter_rows(d_img.view(B, Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
-                d_img, d_full = d_full, None
+            grads[:] = block_bwd(li, self.blocks[li], sv, env, grads)
+            del sv
+            # (a LoRA block 0 through its C entry returns no input gradients — the embedders are frozen: then there is nothing to scatter)
+            if li in ctx.route_start and grads[0] is not None:
+                ops.scatter_rows(grads[0].view(B, env.Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
+                grads[0], d_full = d_full, None
+
+    def _engine_backward(self, ctx, dout, *d_taps):
+        """d_taps: the upstream gradients of the taps' outputs, in ctx.taps' order (LayerSync's similarity, the Internal Guidance prediction, the NextLat state
+        loss); each tap's backward takes its own right before its block's own backward"""
+        if not self._prepared:
+            raise RuntimeError("call prepare_for_training() after loading weights (builds the K-major dgrad operands)")
+        D = self.D
+        dpk = ops.patchify(dout.to(BF16).contiguous(), order=1).view(ctx.B * ctx.Si, -1)
+        mo = ctx.mod_i[:, self.mod_off_out:self.mod_off_out + 2 * D]       # the image stream's modulation rows: per sample, or per token under tokenwise timesteps
+        dn = ops.gemm(dpk, self.l_out.wT)
+        grads = [ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], ctx.rpb_i)[0], None]
+        del dn, dpk
+        self._walk_blocks_bwd(ctx, grads, d_taps, (self.accumulate_lora_grads, self.grad_sync), lambda li, *a: self._block_bwd(ctx, li, *a))
         return None
 
     # ------------------------------------------------------------------------------------------------
@@ -1117,183 +1215,40 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """training.grad_sync.hand_over_gradients: the arena just filled now belongs to autograd; the next backward takes the other one"""
         self._select_grad_arena(1 - self._grad_sel)
 
-    def _engine_backward_full(self, ctx, dout, dsim=None, d_ig=None, d_nl=None):
-        D, H, hd = self.D, self.H, self.hd
-        B, Si, St, S, Sp, mod, cos, sin = ctx.B, ctx.Si, ctx.St, ctx.S, ctx.Sp, ctx.mod, ctx.cos, ctx.sin
-        dev = self.device_
-        scale = 1.0 / math.sqrt(hd)
+    def _engine_backward_full(self, ctx, dout, *d_taps):
+        """d_taps: as in _engine_backward"""
+        D, B, Si, mod = self.D, ctx.B, ctx.Si, ctx.mod
         self._refresh_transposed()
         sync = self.grad_sync
-        fb = FullGrads(self, B, dev, sync, self._blocks_arena_lo, ctx.emb.st)
-        dmod, wgrad = fb.dmod, fb.wgrad
-
-        def qk_bwd(dQ_, dK_, qkv_, wq, wk, dqkv_, rows, pos0, S_, gq, gk):
-            """RMSNorm (+ identity RoPE) backward of one stream's q / k; with norm weights (SD3.5) also their gradients (sd3/transformer.py:155-165)"""
-            if wq is None and wk is None:
-                ops.qk_norm_rope_bwd(dQ_, dK_, qkv_, wq, wk, cos, sin, dqkv_, B, H, hd, rows, pos0, S_)
-            else:
-                ops.qk_norm_rope_bwd_wgrad(dQ_, dK_, qkv_, wq, wk, cos, sin, dqkv_, B, H, hd, rows, pos0, S_, gq, gk)
-
-        def grad_rows(t, lo, n, seg: bool = False):
-            """rows [lo, lo+n) of every batch element of a joint [B*S, C] buffer as a weight-gradient operand.  seg: in place — a [B, n, C] strided view, the
-            segmented-contraction form of st355_gemm_tn_seg_bf16 — when n is a whole number of 64-row K-tiles (the image rows of every bucket); else (the text
-            rows, and callers that also read the operand as a plain matrix) a compact copy, its row count zero-tailed to 64 (pad64 takes it as is)"""
-            if B == 1:
-                return t[lo:lo + n]
-            v = t.view(B, S, -1)[:, lo:lo + n]
-            if seg and n % 64 == 0 and n >= 128:
-                return v
-            o = pad64_empty(B * n, t.shape[1], dev)
-            o.view(B, n, -1).copy_(v)
-            return o
-
+        fb = FullGrads(self, B, self.device_, sync, self._blocks_arena_lo, ctx.emb.st)
         # ---- head ----
         dpk = ops.patchify(dout.to(BF16).contiguous(), order=1).view(B * Si, -1)
         mo = mod[:, self.mod_off_out:self.mod_off_out + 2 * D]
-        dmo = dmod[:, self.mod_off_out:self.mod_off_out + 2 * D]
-        wgrad(self.l_out, dpk, ctx.n_out)
+        dmo = fb.dmod[:, self.mod_off_out:self.mod_off_out + 2 * D]
+        fb.wgrad(self.l_out, dpk, ctx.n_out)
         dn = ops.gemm(dpk, self.l_out.wT)
         fb.mod_grads(dn, ctx.x_img_final, Si, 1, 0, dmo)                        # AdaLayerNormContinuous: (scale, shift)
-        d_img, _ = ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], Si)
-        d_txt = None
+        grads = [ops.ln_modulate_bwd(dn, ctx.x_img_final, mo[:, :D], Si)[0], None]
         del dn, dpk
         if sync is not None:
             sync.ready(self._head_arena_lo, self._head_arena_hi)             # proj_out gradients are final (an Internal Guidance head behind it: at its block)
         # the fused modulation matrix (a third of SD3-Medium's parameters, 1.35 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
-        ls, ig, nl = getattr(ctx, "ls", None), getattr(ctx, "ig", None), getattr(ctx, "nl", None)
-        for li in range(len(self.blocks) - 1, -1, -1):
-            if ctx.blocks[li] is None:
-                self._recompute_segment(ctx, li)
-            if ls is not None and li == ls.student:
-                ls.inject(d_img.view(B, ctx.Si, D), dsim)
-            if ig is not None and li == ig.block:
-                ig.backward(d_ig, d_img.view(B, ctx.Si, D), False, sync)
-            if nl is not None and li == nl.block:
-                nl.backward(d_nl, d_img.view(B, ctx.Si, D), False, sync)
-            if li in ctx.route_end:                       # backward enters a TREAD route at its END: the routed blocks see only the kept tokens' gradient rows
-                r_info = ctx.route_end[li]
-                d_full = d_img
-                d_img = ops.gather_rows(d_full.view(B, ctx.Si, D), r_info.keep_i32()).view(-1, D)
-            Si, S, Sp = ctx.envs[li].Si, ctx.envs[li].S, ctx.envs[li].Sp
-            blk, sv = self.blocks[li], ctx.blocks[li]
-            ctx.blocks[li] = None
+
+        def block_bwd(li, blk, sv, env, grads):
             if li + 1 < len(self.blocks):
                 nb = self.blocks[li + 1]
                 if sync is not None:
                     sync.ready(nb.arena_lo, nb.arena_hi)                      # the block processed last iteration: its slice can go out
                 fb.mod_rows_grad(nb.mod_off)                                     # ... and so can its rows of the modulation matrix
-            mi = mod[:, blk.mod_off:blk.mod_off + 6 * D]; dmi = dmod[:, blk.mod_off:blk.mod_off + 6 * D]
-            nct = 2 if blk.last else 6
-            mt = mod[:, blk.mod_off_c:blk.mod_off_c + nct * D]; dmt = dmod[:, blk.mod_off_c:blk.mod_off_c + nct * D]
-            if (_BLOCK_ABI and not blk.dual and ops.ATTN_TR and sv.Qt is None and d_img.is_contiguous() and (d_txt is None or d_txt.is_contiguous())
-                    and blk.norm_q is None and blk.norm_k is None and blk.norm_added_q is None and blk.norm_added_k is None):
-                # the data path as ONE C entry point (st355_block_sd3_joint_bwd), then every weight / bias / modulation gradient of the block from the gradients
-                # it left behind (SD3.5's trainable q / k norm weights take the host-side form: their gradient rides in the RMSNorm backward pass)
-                # (every bias / modulation-shift / -scale / gate gradient of the block is written by the entry itself — the column sums ride in its scale_cols and
-                # LayerNorm-backward passes, csrc/stats.hip; only the weight gradients are left, taken from the gradients it kept)
-                d_img, d_txt, G = self._block_bwd_c(blk, sv, ctx.envs[li], mod, cos, sin, d_img, d_txt, True, dmod=dmod)
-                wgrad(blk.ff2, G.g_i, sv.h_i, bias=False)
-                wgrad(blk.ff1, G.dh_i, sv.n2_i, bias=False)
-                if not blk.last:
-                    wgrad(blk.ffc2, G.g_t, sv.h_t, bias=False)
-                    wgrad(blk.ffc1, G.dh_t, sv.n2_t, bias=False)
-                wgrad(blk.to_out, G.dx1g_i, grad_rows(sv.O, 0, Si, seg=True), bias=False)
-                if not blk.last:
-                    wgrad(blk.to_add_out, G.dx1g_t, grad_rows(sv.O, Si, St), bias=False)
-                wgrad(blk.qkv, G.c_img if G.c_img is not None else grad_rows(G.dqkv, 0, Si, seg=True), sv.n_img, bias=False)       # (c_*: the compact copy the entry left)
-                wgrad(blk.add_qkv, G.c_txt if G.c_txt is not None else grad_rows(G.dqkv, Si, St), sv.n_txt, bias=False)
-                del sv, G
-                if li in ctx.route_start:
-                    ops.scatter_rows(d_img.view(B, Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
-                    d_img, d_full = d_full, None
-                continue
-            # ---- MLP branch (host-sequenced form: SD3.5 dual-attention blocks, trainable q / k norms, TREAD, ST355_BLOCK_ABI=0).  Every modulation / gate / bias
-            # gradient rides in the pass that streams its operands — the same fused entry points the C block sequences (csrc/stats.hip) ----
-            g_i = ops.scale_cols_stats(d_img, mi[:, 5 * D:6 * D], Si, y_branch=sv.yf_i, d_gate=dmi[:, 5 * D:6 * D], d_bias=blk.ff2.gb)     # + d gate_mlp, d b_ff2
-            wgrad(blk.ff2, g_i, sv.h_i, bias=False)
-            dh_i = ops.gemm(g_i, blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
-            wgrad(blk.ff1, dh_i, sv.n2_i, bias=False)
-            dn2_i = ops.gemm(dh_i, blk.ff1.wT)
-            dn2a = None
-            if blk.dual:
-                d2 = sv.d2
-                mi9 = mod[:, blk.mod_off:blk.mod_off + 9 * D]; dmi9 = dmod[:, blk.mod_off:blk.mod_off + 9 * D]
-                # + d shift_mlp, d scale_mlp, d gate_msa2 = sum d x1 * y_attn2, d b_to_out2 = sum gate_msa2 * d x1
-                dx1_i, dxg2 = ops.ln_modulate_bwd_stats(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dmi[:, 3 * D:4 * D], dmi[:, 4 * D:5 * D], dres=d_img,
-                                                        gate=mi9[:, 8 * D:9 * D], y_branch=d2.ya2, d_gate=dmi9[:, 8 * D:9 * D], d_bias=blk.to_out2.gb, want_gated=True)
-                ops.colsum_rows(dh_i, Si, Si, B, blk.ff1.gb)
-                wgrad(blk.to_out2, dxg2, d2.O2, bias=False)
-                dO2 = ops.gemm(dxg2, blk.to_out2.wT)
-                dqkv2 = torch.empty(B * Si, 3 * D, dtype=BF16, device=dev)
-                dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
-                ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
-                qk_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, dqkv2, Si, 0, Si, blk.g_norm_q2, blk.g_norm_k2)
-                wgrad(blk.qkv2, dqkv2, d2.n2a)
-                dn2a = ops.gemm(dqkv2, blk.qkv2.wT)
-                dx1g_i = ops.scale_cols_stats(dx1_i, mi[:, 2 * D:3 * D], Si, y_branch=sv.ya_i, d_gate=dmi[:, 2 * D:3 * D], d_bias=blk.to_out.gb)   # + d gate_msa, d b_to_out
-                del dxg2, dO2, dQ2, dK2, dqkv2, d2
-            else:
-                # + d shift_mlp, d scale_mlp, d gate_msa = sum d x1 * y_attn, d b_to_out = sum gate_msa * d x1
-                dx1_i, dx1g_i = ops.ln_modulate_bwd_stats(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dmi[:, 3 * D:4 * D], dmi[:, 4 * D:5 * D], dres=d_img,
-                                                          gate=mi[:, 2 * D:3 * D], y_branch=sv.ya_i, d_gate=dmi[:, 2 * D:3 * D], d_bias=blk.to_out.gb, want_gated=True)
-                ops.colsum_rows(dh_i, Si, Si, B, blk.ff1.gb)
-            del g_i, dh_i, dn2_i
-            dx1_t = dx1g_t = None
-            if not blk.last:
-                g_t = ops.scale_cols_stats(d_txt, mt[:, 5 * D:6 * D], St, y_branch=sv.yf_t, d_gate=dmt[:, 5 * D:6 * D], d_bias=blk.ffc2.gb)
-                wgrad(blk.ffc2, g_t, sv.h_t, bias=False)
-                dh_t = ops.gemm(g_t, blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)
-                wgrad(blk.ffc1, dh_t, sv.n2_t, bias=False)
-                dn2_t = ops.gemm(dh_t, blk.ffc1.wT)
-                dx1_t, dx1g_t = ops.ln_modulate_bwd_stats(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dmt[:, 3 * D:4 * D], dmt[:, 4 * D:5 * D], dres=d_txt,
-                                                          gate=mt[:, 2 * D:3 * D], y_branch=sv.ya_t, d_gate=dmt[:, 2 * D:3 * D], d_bias=blk.to_add_out.gb, want_gated=True)
-                ops.colsum_rows(dh_t, St, St, B, blk.ffc1.gb)
-                del g_t, dh_t, dn2_t
-            # ---- attention output projections ----
-            O_i = grad_rows(sv.O, 0, Si)
-            wgrad(blk.to_out, dx1g_i, O_i, bias=False)
-            dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
-            after = []
-            probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, 0, Si, B, S)), after)
-            if not blk.last:
-                probs += _stream_problems(B, S, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, Si, St, B, S)), after)
-            ops.gemm_grouped(probs)
-            for f in after:
-                f()
-            if not blk.last:
-                wgrad(blk.to_add_out, dx1g_t, grad_rows(sv.O, Si, St), bias=False)
-            del dx1g_i, dx1g_t, O_i
-            # ---- attention ----
-            dqkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
-            dQ = torch.empty(B, H, S, hd, dtype=BF16, device=dev); dK = torch.empty_like(dQ)
-            ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * D:], sv.O, dO, sv.lse2, dQ, dK, dqkv[:, 2 * D:], B, H, S, Sp, hd, scale)
-            qk_bwd(dQ, dK, sv.qkv, blk.norm_q, blk.norm_k, dqkv, Si, 0, S, blk.g_norm_q, blk.g_norm_k)
-            qk_bwd(dQ, dK, sv.qkv, blk.norm_added_q, blk.norm_added_k, dqkv, St, Si, S, blk.g_norm_added_q, blk.g_norm_added_k)
-            del dQ, dK, dO
-            ops.colsum_rows(dqkv, Si, S, B, blk.qkv.gb)                    # d b_qkv / d b_add_qkv: each stream's rows of the joint dqkv, summed in place
-            ops.colsum_rows(dqkv[Si:], St, S, B, blk.add_qkv.gb)
-            dq_i, dq_t = grad_rows(dqkv, 0, Si), grad_rows(dqkv, Si, St)
-            wgrad(blk.qkv, dq_i, sv.n_img, bias=False)
-            wgrad(blk.add_qkv, dq_t, sv.n_txt, bias=False)
-            dn_i, dn_t = ops.gemm_grouped([dict(a=dq_i, w=blk.qkv.wT), dict(a=dq_t, w=blk.add_qkv.wT)])
-            d_img, _ = ops.ln_modulate_bwd_stats(dn_i, sv.img, mi[:, D:2 * D], Si, dmi[:, :D], dmi[:, D:2 * D], dres=dx1_i)      # + d shift_msa, d scale_msa
-            if dn2a is not None:                  # the second reader of LN(img): attn2's modulated input (shift_msa2, scale_msa2)
-                d_img, _ = ops.ln_modulate_bwd_stats(dn2a, sv.img, mod[:, blk.mod_off + 7 * D:blk.mod_off + 8 * D], Si, dmi9[:, 6 * D:7 * D], dmi9[:, 7 * D:8 * D],
-                                                     dres=d_img)
-            if blk.last:                          # AdaLayerNormContinuous: chunks (scale, shift)
-                d_txt, _ = ops.ln_modulate_bwd_stats(dn_t, sv.txt, mt[:, :D], St, dmt[:, D:2 * D], dmt[:, :D], dres=None)
-            else:
-                d_txt, _ = ops.ln_modulate_bwd_stats(dn_t, sv.txt, mt[:, D:2 * D], St, dmt[:, :D], dmt[:, D:2 * D], dres=dx1_t)
-            del dqkv, sv, dn_i, dn_t, dq_i, dq_t
-            if li in ctx.route_start:
-                ops.scatter_rows(d_img.view(B, Si, D), ctx.route_start[li].keep_i32(), d_full.view(B, ctx.Si, D))
-                d_img, d_full = d_full, None
-        Si, S, Sp = ctx.Si, ctx.S, ctx.Sp
+            return self._block_bwd_full(ctx, fb, blk, sv, env, grads)
+
+        self._walk_blocks_bwd(ctx, grads, d_taps, (False, sync), block_bwd)
+        d_img, d_txt = grads
         # ---- embedders ----
         em = ctx.emb
-        wgrad(self.l_patch, d_img, em.patches)                              # PatchEmbed conv == GEMM on the patches; the position table is a buffer
-        wgrad(self.l_ctx, d_txt, em.enc2d)
+        fb.wgrad(self.l_patch, d_img, em.patches)                           # PatchEmbed conv == GEMM on the patches; the position table is a buffer
+        fb.wgrad(self.l_ctx, d_txt, em.enc2d)
         dtemb = fb.mod_linear_bwd(em.temb)          # (+ block 0's modulation rows: every other block's went out behind the block after it)
         fb.mlp_bwd(self.l_t1, self.l_t2, em.tproj, em.t1, em.st1, dtemb)
         fb.mlp_bwd(self.l_p1, self.l_p2, em.pooled, em.p1, em.sp1, dtemb)
@@ -1314,51 +1269,27 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if timestep.ndim not in (1, 2):
             raise ValueError(f"timestep: expected [B] or tokenwise [B, S_img], got {tuple(timestep.shape)}")
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or getattr(self, "full", False))
-        sim = igp = nls = None                             # LayerSync / Internal Guidance / NextLat: the training nodes return the similarity / the head's prediction / the state loss as further outputs
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
-        if need_grad and getattr(self, "full", False):
-            out = _SD3FullFn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._full_params)
-            out, sim, igp, nls = _split_outputs(self, out)
-        elif need_grad:
-            out = _SD3Fn.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *self._lora_params)
-            out, sim, igp, nls = _split_outputs(self, out)
+        if need_grad:      # the training nodes return every tap's output (the similarity / the head's prediction / the state loss) behind the prediction, in the taps' order
+            node, params = (_SD3FullFn, self._full_params) if getattr(self, "full", False) else (_SD3Fn, self._lora_params)
+            out = node.apply(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, *params)
+            out, *rest = out if isinstance(out, tuple) else (out,)
+            extra = dict(zip(self._node_keys, rest))
         else:
             with torch.no_grad():
                 out, ectx = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False,
                                                  want_ig=bool(return_internal_guidance))
-                igp = getattr(ectx, "ig_pred", None)            # sampling: the intermediate prediction next to the final one
-        extra = {k: v for k, v in (("layersync_similarity", sim), ("internal_guidance_prediction", igp), ("nextlat_state_loss", nls)) if v is not None}
+                extra = {tap.key: tap.output for tap in ectx.taps}      # sampling: the intermediate prediction next to the final one
         if not return_dict:
-            return (out,) + tuple(extra.values())               # order: (out, sim, ig_pred, nextlat_state)
+            return (out,) + tuple(extra.values())
         return SimpleNamespace(sample=out, **extra)
 
 
-def _split_outputs(model, out):
-    """the training nodes' outputs: out, then the LayerSync similarity, then the Internal Guidance prediction, then the NextLat state loss, each only when its
-    feature is on"""
-    if not isinstance(out, tuple):
-        return out, None, None, None
-    rest = list(out[1:])
-    sim = rest.pop(0) if model._layersync is not None else None
-    igp = rest.pop(0) if model._ig_block is not None else None
-    nls = rest.pop(0) if model._nl_block is not None else None
-    return out[0], sim, igp, nls
-
-
-def _node_outputs(out, ctx):
-    extra = ([ctx.ls.sim] if getattr(ctx, "ls", None) is not None else []) + ([ctx.ig_pred] if getattr(ctx, "ig", None) is not None else []) \
-        + ([ctx.nl_state] if getattr(ctx, "nl", None) is not None else [])
-    return out if not extra else (out, *extra)
-
-
-def _node_grads(ctx, rest):
-    """(dsim, d_ig, d_nl) from the gradients of the nodes' further outputs, in _node_outputs' order"""
-    rest = list(rest)
-    dsim = rest.pop(0) if getattr(ctx, "ls", None) is not None else None
-    d_ig = rest.pop(0) if getattr(ctx, "ig", None) is not None else None
-    d_nl = rest.pop(0) if getattr(ctx, "nl", None) is not None else None
-    return dsim, d_ig, d_nl
+def _node_outputs(model, out, ctx):
+    """what a training node returns: the prediction, then every tap's output; `model._node_keys` names them for `forward`"""
+    model._node_keys = [tap.key for tap in ctx.taps]
+    return (out, *(tap.output for tap in ctx.taps)) if ctx.taps else out
 
 
 class _SD3Fn(torch.autograd.Function):
@@ -1368,14 +1299,14 @@ class _SD3Fn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *lora_params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True)
         fctx.model, fctx.ectx = model, ctx
-        return _node_outputs(out, ctx)
+        return _node_outputs(model, out, ctx)
 
     @staticmethod
     def backward(fctx, dout, *rest):
         model = fctx.model
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout, *_node_grads(fctx.ectx, rest))
+        model._engine_backward(fctx.ectx, dout, *rest)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()
@@ -1397,7 +1328,7 @@ class _SD3FullFn(torch.autograd.Function):
     def forward(fctx, model, latents, enc, pooled, timestep, *params):
         out, ctx = model._engine_forward(latents.detach().to(BF16), enc.detach().to(BF16), pooled.detach(), timestep.detach(), save=True, full=True)
         fctx.model, fctx.ectx = model, ctx
-        return _node_outputs(out, ctx)
+        return _node_outputs(model, out, ctx)
 
     @staticmethod
     def backward(fctx, dout, *rest):
@@ -1405,7 +1336,7 @@ class _SD3FullFn(torch.autograd.Function):
         model._pick_grad_arena()
         if model.grad_sync is not None:
             model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout, *_node_grads(fctx.ectx, rest))
+        model._engine_backward_full(fctx.ectx, dout, *rest)
         fctx.ectx = None
         if model.grad_sync is not None:
             model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world

@@ -2,8 +2,8 @@
 
     python tools/launch_trace.py OUT.txt [extra pytest arguments]
 
-Runs the engine tests that execute against tests/ops_emulator.py (`-m "not gpu"`, the -k expression below) with every emulated `ops` wrapper wrapped: before
-it runs, one line goes to OUT.txt — the wrapper's name and its arguments bound to the wrapper's signature (defaults filled in), tensors as dtype / shape /
+Runs the engine tests that execute against tests/ops_emulator.py (`-m "not gpu"`, the -k expression below) with every emulated `ops` wrapper wrapped, and
+every stand-in that the feature reference modules (tests/*_ref.py: `STAND_INS`, LayerSync's two) install on top of them: before it runs, one line goes to OUT.txt — the wrapper's name and its arguments bound to the wrapper's signature (defaults filled in), tensors as dtype / shape /
 stride, scalars by value.  An output the wrapper would allocate itself (`out=None`) is written as the tensor it returns, so who allocates a temporary does
 not show; what the C entry point receives does.  `### <nodeid>` opens every test.  Run it at two commits and compare the files (`cmp`, `sha256sum`): the host
 layer launches the same stream exactly when they are identical.  Worker processes a test spawns (the gloo replicas) are not traced; the single-process
@@ -75,6 +75,15 @@ class LaunchTrace:
             return ops
 
         EMU.install = install
+        # the features' stand-ins, installed on top of the emulator by their modules' own `install` (which read these at call time): wrapped in place
+        from tests import dora_ref, internal_guidance_ref, layersync_ref, lora_dropout_ref, nextlat_ref, reflexflow_ref
+        for mod in (layersync_ref, nextlat_ref, internal_guidance_ref, lora_dropout_ref, dora_ref, reflexflow_ref):
+            table = getattr(mod, "STAND_INS", None) or {}
+            for name, fn in table.items():
+                if inspect.isfunction(fn):
+                    table[name] = self.wrap(name, fn)
+        for name in ("layersync_fwd", "layersync_inject"):
+            setattr(layersync_ref, name, self.wrap(name, getattr(layersync_ref, name)))
 
     def pytest_runtest_setup(self, item):
         self.f.write(f"### {item.nodeid}\n")
