@@ -2174,6 +2174,8 @@ def vae_encode(table: VaeEncoderTable, x):
 def tokens_to_grid(tokens, B: int, H: int, W: int, residual=None):
     L = _l.load()
     _chk(tokens, BF16, "tokens")
+    if tokens.shape[0] != B * H * W or not tokens.is_contiguous():          # st355_tokens_to_grid takes no row stride
+        raise _l.St355Error("tokens_to_grid: tokens must be a dense [B*H*W, C] tensor")
     g = _grid_out(B, H, W, tokens.shape[1], tokens.device)
     _l.check(L.st355_tokens_to_grid(_stream(), _ptr(tokens), _ptr(residual), _ptr(g), B, H, W, tokens.shape[1]), "tokens_to_grid")
     return g
@@ -2229,6 +2231,8 @@ def groupnorm_bwd(dy, x, gamma, beta, stats, B: int, H: int, W: int, groups: int
     L = _l.load()
     _chk(dy, BF16, "dy"); _chk(x, BF16, "x"); _chk(stats, F32, "stats")
     Cn = x.shape[1]
+    if dy_tokens and (tuple(dy.shape) != (B * H * W, Cn) or not dy.is_contiguous()):          # st355_groupnorm_bwd takes no row stride
+        raise _l.St355Error("groupnorm_bwd: dy_tokens must be a dense [B*H*W, C] tensor")
     dx = _grid_out(B, H, W, Cn, x.device)
     _l.check(L.st355_groupnorm_bwd(_stream(), _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dadd), _ptr(dx), _ptr(dgamma), _ptr(dbeta),
                                    B, H, W, Cn, groups, 1 if silu else 0, 1 if dy_tokens else 0, 1 if accumulate_params else 0,

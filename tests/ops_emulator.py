@@ -10,7 +10,8 @@ the oracle's autograd — the GPU parity tests remain the proof for the kernels 
 
 Covered: the GEMM family and its epilogues, the TN weight-gradient GEMM, token-axis reductions, AdaLN / LayerNorm / GroupNorm / RMSNorm + RoPE forward and backward,
 self- and cross-attention, the grid-buffer convolution path of the UNet / VAE (conv-as-GEMM, im2col, up / down sampling), GEGLU, rank-space LoRA products, noising,
-the fused losses, AdamW (+ EMA), gradient norm / clipping — 66 wrappers (`_EMULATED`).  Nothing in the product imports this module; the product has no CPU path (ops.* raise
+the fused losses, AdamW (+ EMA), gradient norm / clipping — 75 wrappers (`_EMULATED`), each held to its kernel's fp64 bound by tests/emulator_cases.py
+(tests/test_ops_emulator_bounds_cpu.py here, tests/test_ops_emulator_bounds_gpu.py on the MI355X).  Nothing in the product imports this module; the product has no CPU path (ops.* raise
 on host tensors; tests/test_product_isolation_cpu.py).  NOT emulated: the block-level C entry points (st355_block_flux_*, st355_vae_encode), the fp8 Linears and AdamWBF16's
 stochastic rounding — tests switch those paths off, exactly like the A/B env switches do.  The fused QKV projection epilogue (ST355_EPI_QK_NORM_ROPE) and the attention
 backward with its RoPE / RMSNorm epilogues ARE emulated: that is Flux's default host path at head_dim 128 with tile-aligned streams.
@@ -291,7 +292,7 @@ def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, a2=None, b2=None, aux_out
     elif epilogue == EPI_GELU:
         if aux_out is not None:
             _put(aux_out, acc)                      # the pre-activation, for the backward
-        val = _gelu(acc)
+        val = _gelu(acc if aux_out is None else _flat(aux_out))          # with aux_out the kernel activates the pre-activation AS STORED (gemm.hip; gemm_bounds.epi_gelu_of_stored)
     elif epilogue == EPI_MUL_GELU_GRAD:
         _need(aux_in is not None, "gemm: EPI_MUL_GELU_GRAD needs aux_in (the saved pre-activation)")
         val = acc * _gelu_grad(_flat(aux_in))
@@ -531,22 +532,39 @@ def cond_loss(pred, target, loss_type="l2", huber_c=0.1, weight=None, want_grad=
     return _loss_common(pred, target, weight, emask, want_grad, grad_scale, lambda d: k * (torch.sqrt(d * d + c * c) - c), lambda d: k * d / torch.sqrt(d * d + c * c))
 
 
+def _f32(x):
+    """the fp32 value a float argument takes when it crosses the C ABI"""
+    return float(torch.tensor(float(x), dtype=F32))
+
+
+def _ema_one(shadow, p_stored, omd):
+    """ema_one (optim.hip): s - omd (s - p), the difference materialised in the shadow dtype; fp64 arithmetic, one rounding at the store"""
+    d = (shadow.double() - p_stored.double()).to(shadow.dtype).double()
+    shadow.copy_((shadow.double() - omd * d).to(shadow.dtype))
+
+
 def adamw_ema_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, grad_scale=1.0, ema=None, ema_decay=0.0, p_bf16=None):
-    """torch.optim.AdamW's single-tensor order of operations over a flat arena (fp32 p / g, or bf16 p / g with fp32 moments), optional fused EMA"""
+    """adam_one (optim.hip; torch.optim.AdamW's single-tensor order of operations) over a flat arena (fp32 p / g, or bf16 p / g with fp32 moments), optional
+    fused EMA of the parameter AS STORED and bf16 mirror.  The scalars are the fp32 values the C ABI receives, step_size and sqrt(bc2) come from double arithmetic
+    on those (make_adam); the element arithmetic runs in fp64 with one rounding at each store, which keeps every output inside the kernel's fp32 bound
+    (tests/step_bounds.py adamw)"""
     _need(step >= 1 and p.dim() == 1 and p.is_contiguous() and g.is_contiguous(), "adamw_ema_step: flat contiguous arenas, step >= 1")
     _need(p.dtype in (F32, BF16) and g.dtype == p.dtype and m.dtype == F32 and v.dtype == F32, "adamw_ema_step: dtypes")
     _need(p.dtype == F32 or p.numel() % 8 == 0, "adamw_ema_step_bf16: n must be a multiple of 8")
-    gf = g.float() * grad_scale
-    pf = p.float() * (1.0 - lr * weight_decay)
-    m.add_((gf - m) * (1.0 - beta1))
-    v.mul_(beta2).add_((1.0 - beta2) * gf * gf)
-    bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    pf = pf - (lr / bc1) * (m / (v.sqrt() / math.sqrt(bc2) + eps))
+    lr, b1, b2, eps, wd, gs = (_f32(x) for x in (lr, beta1, beta2, eps, weight_decay, grad_scale))
+    step_size, bc2_sqrt = _f32(lr / (1.0 - b1 ** step)), _f32(math.sqrt(1.0 - b2 ** step))
+    omd = float(torch.tensor(1.0, dtype=F32) - torch.tensor(float(ema_decay), dtype=F32))
+    gf = g.double() * gs
+    pf = p.double() * (1.0 - lr * wd)
+    m1 = m.double() + (gf - m.double()) * (1.0 - b1)
+    v1 = v.double() * b2 + (1.0 - b2) * gf * gf
+    pf = pf - step_size * (m1 / (v1.sqrt() / bc2_sqrt + eps))
+    m.copy_(m1.float()); v.copy_(v1.float())
     p.copy_(pf.to(p.dtype))
     if ema is not None:
-        ema.copy_((ema.float() - (1.0 - ema_decay) * (ema.float() - p.float()).to(ema.dtype).float()).to(ema.dtype))      # (s - p) materialised in the shadow dtype, as k_ema
+        _ema_one(ema, p, omd)
     if p_bf16 is not None:
-        p_bf16.copy_(pf.to(BF16))
+        p_bf16.copy_(p.to(BF16))          # one RNE of the stored parameter
 
 
 def adamw_bf16_sr_step(p, g, m, v, shift, step, lr, beta1, beta2, eps, seg_end=None, seg_decay=None, rand_bits=None, seed=0, offset=0, grad_scale=1.0):
@@ -571,10 +589,9 @@ def adamw_bf16_sr_step(p, g, m, v, shift, step, lr, beta1, beta2, eps, seg_end=N
 
 
 def ema_update(shadow, param, decay):
-    """s -= (1 - d) (s - p), the difference materialised in the parameter dtype (ema.py:423)"""
+    """s -= (1 - d) (s - p), the difference materialised in the parameter dtype (ema.py:423); 1 - d in fp32, as st355_ema_update forms it"""
     _need(shadow.dtype == param.dtype, "ema_update: dtype mismatch")
-    diff = (shadow.float() - param.float()).to(shadow.dtype)
-    shadow.copy_((shadow.float() - (1.0 - decay) * diff.float()).to(shadow.dtype))
+    _ema_one(shadow, param, float(torch.tensor(1.0, dtype=F32) - torch.tensor(float(decay), dtype=F32)))
 
 
 def grad_norm(g):
@@ -712,7 +729,7 @@ def ln_modulate_bwd(dy, x, scale, rows_per_batch, dres=None, gate=None, eps=1e-6
     dxg = None
     if want_gated:
         _chk(gate, BF16, "gate"); _rows(gate, "gate")
-        dxg = (dx * _per_batch(gate, rows, rows_per_batch)).to(BF16)
+        dxg = (dst.float() * _per_batch(gate, rows, rows_per_batch)).to(BF16)          # gate * dx AS STORED (k_ln_mod_bwd; norm_bounds.mul_stored)
     return dst, dxg
 
 
@@ -996,7 +1013,7 @@ def grid_to_nchw(g, B, Cn, H, W):
 
 def tokens_to_grid(tokens, B, H, W, residual=None):
     _chk(tokens, BF16, "tokens"); _rows(tokens, "tokens")
-    _need(tokens.shape[0] == B * H * W, "tokens_to_grid: rows")
+    _need(tokens.shape[0] == B * H * W and tokens.is_contiguous(), "tokens_to_grid: dense [B*H*W, C] tokens (st355_tokens_to_grid takes no row stride)")
     img = tokens.float().reshape(B, H, W, -1)
     if residual is not None:
         img = img + _interior(residual, B, H, W)
@@ -1106,6 +1123,7 @@ def groupnorm_bwd(dy, x, gamma, beta, stats, B, H, W, groups=32, silu=True, dy_t
     _chk(stats, F32, "stats")
     xi = _interior(x, B, H, W)
     Cn = xi.shape[-1]
+    _need(not dy_tokens or (dy.is_contiguous() and tuple(dy.shape) == (B * H * W, Cn)), "groupnorm_bwd: dy_tokens is a dense [B*H*W, C] tensor (st355_groupnorm_bwd takes no row stride)")
     d = dy.float().reshape(B, H, W, Cn) if dy_tokens else _interior(dy, B, H, W)
     mean, rstd = stats[..., 0][:, None, None, :], stats[..., 1][:, None, None, :]
     xhat = (xi - mean) * rstd
@@ -1404,7 +1422,7 @@ def block_sd3_joint_bwd(**a):
                A.gb_add_qkv, A.dn_txt, A.txt, 1 if last else 0, 0 if last else 1, not last)
 
 
-_EMULATED = ("qk_rope", "attn_fwd_vrows", "attn_bwd_rope", "qk_rope_norm_bwd", "grid_rows", "grid_zeros", "grid_from_nchw", "grid_to_nchw", "tokens_to_grid", "grid_to_tokens", "conv", "conv_wgrad", "im2col3x3", "col2im3x3", "upsample2x",
+_EMULATED = ("qk_rope", "heads", "attn_fwd_vrows", "attn_bwd_rope", "qk_rope_norm_bwd", "grid_rows", "grid_zeros", "grid_from_nchw", "grid_to_nchw", "tokens_to_grid", "grid_to_tokens", "conv", "conv_wgrad", "im2col3x3", "col2im3x3", "upsample2x",
              "upsample2x_bwd", "groupnorm_fwd", "groupnorm_bwd", "layernorm_fwd", "layernorm_bwd", "layernorm_param_grads", "geglu_fwd", "geglu_bwd", "softmax_rows_",
              "softmax_rows_bwd_", "attn_cross_fwd", "attn_cross_bwd", "head_split", "head_merge", "gelu_tanh", "gemm", "gemm_grouped", "gemm_tn", "colsum_prod", "transpose", "skinny_tn", "skinny_tn_multi", "lora_pack", "flow_noise_mix", "ddpm_noise_mix", "flux_pack", "flux_unpack", "mse_loss", "cond_loss", "adamw_ema_step", "adamw_bf16_sr_step", "ema_update", "grad_norm", "grad_clamp_", "grad_clip_norm_", "timestep_proj", "patchify", "unpatchify", "silu", "silu_bwd",
              "add", "scale_cols", "scale_cols_stats", "colsum_rows", "ln_modulate_bwd_stats", "gather_rows", "scatter_rows", "ln_modulate_fwd", "ln_modulate_bwd", "layer_norm_xhat", "qk_norm_rope_fwd", "qk_norm_rope_bwd",
