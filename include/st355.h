@@ -666,6 +666,30 @@ int st355_dora_dmag(void* stream, const void* dy, int64_t ldd, int64_t seg_rows,
 /* gB[n, r] (+)= g[n] P[n, r]: P [N, rank] fp32 contiguous = s dy^T T (st355_skinny_tn_seg, accumulate = 0), gB [N, rank] fp32 contiguous */
 int st355_dora_db_finish(void* stream, const float* P, const float* g, float* gB, int N, int rank, int accumulate);
 
+/* ---- LyCORIS LoKr (`algo: lokr`, both factors full; csrc/lokr.hip): for a target W [N, K] with N = ol ok, K = im in: dW = s kron(w1, w2),
+ * dW[i ok + k, j in + l] = s w1[i, j] w2[k, l] (w1 [ol, im], w2 [ok, in], fp32), y = x bf16(W + dW)^T + b.  fp32 arithmetic, no atomics, fixed-order two-stage
+ * reductions (two calls give the same bits).  ol, im <= 16; ok % 8 == 0, in % 8 == 0. */
+/* One launch per fused projection (G <= 4 targets; target g owns rows [n_off[g], n_off[g] + n_cnt[g]) of W [N_total, K], in rising order; n_off / n_cnt / ol / im
+ * and the three pointer tables are HOST arrays).  Writes Wf = bf16(fmaf(s w1[i, j], w2[k, l], float(W))) [N_total, K] (s w1 rounded to fp32 first), WfT [K, N_total]
+ * its transpose and w2b[g] = bf16(w2[g]) [ok, in].  Rows outside every target are copied.  s = 0 gives Wf == W bit for bit. */
+int st355_lokr_fold(void* stream, const void* W, void* Wf, void* WfT, int N_total, int K, int G, const int* n_off, const int* n_cnt, const int* ol, const int* im,
+                    const float* const* w1, const float* const* w2, void* const* w2b, float s);
+/* dP[m, j ok + k] = bf16(sum_i w1[i, j] dy[m, n_off + i ok + k]) (fp32 fma chain in rising i, one rounding).  dy bf16 (row stride ldd; compact, or seg_rows-row
+ * blocks seg_stride ROWS apart: a [B, rows, C] view of a joint buffer), dP bf16 [M, im ok] contiguous.  n_off % 8 == 0, ldd % 8 == 0. */
+int st355_lokr_mix(void* stream, const void* dy, int64_t ldd, int64_t seg_rows, int64_t seg_stride, int n_off, const float* w1, int ol, int im, int ok, void* dP,
+                   int64_t M);
+/* out[ok, in] (+)= alpha dP.view(M im, ok)^T x.view(M im, in), fp32 contiguous.  dP bf16 [M im, ok] contiguous; x bf16 rows of im * in columns (row stride ldx,
+ * compact or segmented as above).  64 x 64 output tiles (128 x 128 where ok and in are multiples of 128) x slices of the contraction on the MFMA into the workspace (st355_lokr_dw2_workspace(M im, ok, in) bytes),
+ * then the slices in order. */
+int64_t st355_lokr_dw2_workspace(int64_t rows, int ok, int in_);
+int st355_lokr_dw2(void* stream, const void* dP, const void* x, int64_t ldx, int64_t seg_rows, int64_t seg_stride, int im, float* out, int64_t M, int ok, int in_,
+                   float alpha, int accumulate, void* workspace);
+/* out[ol, im] (+)= alpha sum_{m, k} dy[m, n_off + i ok + k] P[m, j ok + k], fp32 contiguous.  dy as for the mix, P bf16 [M, im ok] contiguous.  One 16 x 16 fp32
+ * tile per wave over a slice of m into the workspace (st355_lokr_dw1_workspace(M) bytes), then the waves in order. */
+int64_t st355_lokr_dw1_workspace(int64_t M);
+int st355_lokr_dw1(void* stream, const void* dy, int64_t ldd, int64_t seg_rows, int64_t seg_stride, int n_off, const void* P, float* out, int64_t M, int ol, int im,
+                   int ok, float alpha, int accumulate, void* workspace);
+
 /* ---- Scheduled sampling with ReflexFlow (flow matching; common.py:6287-6318, scheduled_sampling/rollout.py:70-199; csrc/reflexflow.hip).  All tensors bf16
  * [batch, per_sample] contiguous, per_sample % 8 == 0, batch < 65536.  Reductions run in two stages in a fixed order (bit-identical run to run), the second on
  * the device; `workspace`: st355_reflexflow_workspace(batch, per_sample) bytes, 16-byte aligned. */

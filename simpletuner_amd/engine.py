@@ -1,6 +1,7 @@
 """Host code the engines share (flux/, sd3/, pixart/ transformer.py, unet/unet.py): nothing here knows a model family.
 
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
+  * `lokr_factorization` / `LokrGroup`: the LyCORIS LoKr adapters of such a group (the Kronecker delta folded into the GEMM operands, the structured gradients);
   * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
   * `LoraDora`: a group's DoRA state (magnitudes, the row scale, the folded GEMM operands);
   * `lin_w` / `lin_wT` / `lora_down` ... `lora_grads`: one adapter site of a block's forward / backward, phase by phase, a no-op without an adapter;
@@ -184,6 +185,10 @@ class LoraGroup:
         self._drop_check()
         return ops.lora_down_drop(x, self.A_cat, self.r_pad, self.streams, drop, out=out)
 
+    def up(self, dy, out=None):
+        """U = dy B_blk [M, K2] bf16: the adapter term of the backward's dx and the left operand of dA"""
+        return ops.gemm(dy, self.B_fwd_T, out=out)
+
     def dx_add(self, dx, U, drop):
         """dx += scale sum_g keep_g . (U_g A_g): the adapter term of the projection's input gradient under dropout (the mask sits between U and A, so the term
         cannot ride the K-extension of the dx GEMM); in place, before anything consumes dx"""
@@ -238,6 +243,122 @@ class LoraGroup:
             sync.ready(self.flat_lo, self.flat_hi)
 
 
+def lokr_factorization(dim: int, factor: int = -1) -> Tuple[int, int]:
+    """LyCORIS' factor rule: (m, n) with m <= n and m * n = dim.  A positive factor that divides dim gives (factor, dim // factor), sorted.  Otherwise (a negative
+    factor means dim) m steps from 1 through the divisors of dim while m + n does not grow, m <= factor and m < n; the last accepted pair, sorted."""
+    dim, factor = int(dim), int(factor)
+    if factor > 0 and dim % factor == 0:
+        return tuple(sorted((factor, dim // factor)))
+    if factor < 0:
+        factor = dim
+    m, n = 1, dim
+    while m < n:
+        nm = m + 1
+        while dim % nm:
+            nm += 1
+        nn_ = dim // nm
+        if nm + nn_ > m + n or nm > factor:
+            break
+        m, n = nm, nn_
+    return (m, n) if m <= n else (n, m)
+
+
+@torch.no_grad()
+def lokr_init_norm(W, w2, scale: float, generator=None):
+    """the reference's `init_lokr_norm` start of one w2 (helpers/training/peft_init.py): a standard normal draw of w2's shape, rescaled first to the frozen weight's
+    norm, then to its standard deviation, then shifted to its mean — in that order, the statistics taken on the fp32 image of the weight — and multiplied by `scale`"""
+    z = torch.randn(w2.shape, dtype=w2.dtype, device=w2.device, generator=generator)
+    Wd = W.to(F32)          # (the reference takes the weight through Tensor.dequantize(), which hands a bf16 weight back as fp32)
+    norm, mean, std = (f().to(w2.dtype) for f in (Wd.norm, Wd.mean, Wd.std))
+    z = z * (norm / z.norm())
+    z = z * (std / z.std())
+    z = z - z.mean() + mean
+    w2.copy_(z * scale)
+
+
+class LokrGroup:
+    """LyCORIS LoKr adapters (`algo: lokr`, both factors full) of the projections that share one input (one fused GEMM), beside LoraGroup and answering the same
+    adapter-site calls.  Target g owns rows [n_off, n_off + N) of the fused W [N_total, K]: dW_g = s kron(w1_g, w2_g) with w1 [ol, im], w2 [ok, in],
+    (ol, ok) = lokr_factorization(N, factor), (im, in) = lokr_factorization(K, factor).  The forward is the merged-weight one: `fold(mult)` — once per engine
+    forward, never in a recompute pass — writes Wf = bf16(W + dW), its transpose and the bf16 copy of every w2; `w_of` / `wT_of` hand the folded copies to every
+    GEMM of the forward, of the recompute passes and of the backward's dx.  There is no rank-space side path: `down` / `up` return nothing, so the K-extension
+    keyword helpers stay empty.  The folded copies double the adapted weights' memory; they live for the whole step."""
+
+    K2 = 0          # no K-extension
+    dora = None
+    scale = 1.0     # (the adapter scale a LoraGroup carries in alpha / r lives in `s`, set by every fold)
+
+    def __init__(self, lin, targets: List[Tuple[str, int, int]], factors: List[int], device):
+        N_total, K = lin.w.shape
+        self.lin, self.K, self.N_total, self.targets = lin, K, N_total, targets
+        self.shapes = []                        # per target (ol, ok, im, in)
+        for (name, n_off, N), f in zip(targets, factors):
+            (ol, ok), (im, in_) = lokr_factorization(N, f), lokr_factorization(K, f)
+            self.shapes.append((ol, ok, im, in_))
+        self.check(targets, self.shapes, factors)
+        e = lambda *s: torch.empty(*s, dtype=BF16, device=device)
+        self.Wf, self.WfT = e(N_total, K), e(K, N_total)
+        self.w2b = [e(ok, in_) for (_, ok, _, in_) in self.shapes]
+        self.w1: List[torch.Tensor] = []        # fp32 params (views into the flat arena), filled by the owner
+        self.w2: List[torch.Tensor] = []
+        self.g1: List[torch.Tensor] = []        # fp32 grad views
+        self.g2: List[torch.Tensor] = []
+        self.flat_lo = self.flat_hi = 0
+        self.s = 1.0                            # the scale of the last fold: what the backward's gradients carry
+
+    @staticmethod
+    def check(targets, shapes, factors):
+        """the shapes the kernels and the P GEMM route take, refused by name with the factor to choose"""
+        if len(targets) > 4:
+            raise NotImplementedError(f"lycoris lokr: {len(targets)} targets on one input ({targets[0][0]}); the fold kernel takes at most 4")
+        for (name, _, N), (ol, ok, im, in_), f in zip(targets, shapes, factors):
+            if ol > 16 or im > 16:
+                raise NotImplementedError(f"lycoris lokr: factor={f} gives {name} a w1 of [{ol}, {im}]; the kernels take w1 sides up to 16 — set factor to a divisor "
+                                          f"of {N} and {in_ * im} that is at most 16")
+            if ok % 8 or in_ % 64:
+                raise NotImplementedError(f"lycoris lokr: factor={f} splits {name} [{N}, {im * in_}] into w2 [{ok}, {in_}]; the gradient route needs ok % 8 == 0 and "
+                                          f"in % 64 == 0 — choose a factor for which in_features / factor is a multiple of 64 (e.g. factor=8 or factor=4)")
+
+    def fold(self, mult: float = 1.0):
+        self.s = float(mult)
+        ops.lokr_fold(self.lin.w, [(n_off, N, w1, w2, w2b) for (_, n_off, N), w1, w2, w2b in zip(self.targets, self.w1, self.w2, self.w2b)], self.s, self.Wf, self.WfT)
+
+    def pack(self):
+        pass
+
+    def w_of(self, lin):
+        return self.Wf
+
+    def wT_of(self, lin):
+        return self.WfT
+
+    def down(self, x, drop=None, out=None):
+        return None
+
+    def up(self, dy, out=None):
+        return None
+
+    def grads(self, x, T, dy, U, accumulate: bool, sync=None, drop=None):
+        """per target: dP = mix(dy), dw2 = s dP^T x, P = x.view(M im, in) w2^T on the GEMM route into scratch, dw1 = s sum dy . P — no [N, K] gradient is formed.
+        x: the projection's input, compact [M, K] or a [B, rows, K] view of a joint buffer; dy likewise over the fused projection's N_total columns."""
+        if isinstance(x, (list, tuple)):
+            raise NotImplementedError("lycoris lokr: an input that only exists as K segments is not built")
+        if x.dim() == 2 and not x.is_contiguous():
+            x = x.contiguous()
+        M = x.shape[0] * x.shape[1] if x.dim() == 3 else x.shape[0]
+        dev = x.device
+        for g, ((_, n_off, N), (ol, ok, im, in_)) in enumerate(zip(self.targets, self.shapes)):
+            dP = ops.lokr_scratch("dp", dev, M, im * ok)
+            ops.lokr_mix(dy, n_off, self.w1[g], ok, dP)
+            ops.lokr_dw2(dP, x, im, self.g2[g], alpha=self.s, accumulate=accumulate)
+            P = ops.lokr_scratch("p", dev, M, im * ok)
+            xv = x.view(M * im, in_) if x.dim() == 2 else x.unflatten(-1, (im, in_)).flatten(1, 2)
+            ops.gemm(xv, self.w2b[g], out=P.view(M * im, ok))
+            ops.lokr_dw1(dy, n_off, P, self.g1[g], ok, alpha=self.s, accumulate=accumulate)
+        if sync is not None:
+            sync.ready(self.flat_lo, self.flat_hi)
+
+
 # ------------------------------------------------------------------------------------------------
 # one adapter site = a Linear (`lin.w`, `lin.wT`, `lin.lora`: its LoraGroup or None), phase by phase: the callers issue every site's down / up GEMM, then the
 # (grouped) base GEMM with the kwargs below, then the `lora_dx_finish`es, then the `lora_grads`.  Without an adapter (or with `lin` None) each does nothing.
@@ -261,7 +382,7 @@ def lora_fwd_kw(lin, T) -> dict:                     # forward: the K-extension 
 
 
 def lora_up(lin, dy, out=None):                      # backward: U = dy B [M, K2]
-    return None if lin is None or lin.lora is None else ops.gemm(dy, lin.lora.B_fwd_T, out=out)
+    return None if lin is None or lin.lora is None else lin.lora.up(dy, out)
 
 
 def lora_dx_kw(lin, U, drop) -> dict:                # backward: the K-extension of the dx GEMM, dx += U A — not under dropout: the mask sits between U and A
@@ -689,7 +810,7 @@ class ArenaModule(nn.Module):
         """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
         own = dict(self.named_parameters())
         # (an Internal Guidance head / a NextLat predictor is optional in a file: without one it keeps the reference's initial values)
-        missing = [k for k in own if k not in state and ".lora_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor."))]
+        missing = [k for k in own if k not in state and ".lora_" not in k and ".lokr_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor."))]
         if missing:
             raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
         own.update(self._extra_state())
@@ -704,7 +825,7 @@ class ArenaModule(nn.Module):
     def diffusers_state_dict(self) -> Dict[str, torch.Tensor]:
         """{diffusers checkpoint key: tensor} of the base parameters (the parameter names ARE the checkpoint keys) + `_extra_state()`: what `save_pretrained`
         writes (training/trainer.py save_state)"""
-        sd = {k: v.detach() for k, v in self.named_parameters() if ".lora_" not in k}
+        sd = {k: v.detach() for k, v in self.named_parameters() if ".lora_" not in k and ".lokr_" not in k}
         sd.update({k: v.detach() for k, v in self._extra_state().items()})
         return sd
 
@@ -713,7 +834,7 @@ class ArenaModule(nn.Module):
         """seed-deterministic random init on device, same distribution family as the oracle's init_params (benchmarks)."""
         g = torch.Generator(device=self.device_).manual_seed(seed)
         for name, p in self.named_parameters():
-            if ".lora_" in name:
+            if ".lora_" in name or ".lokr_" in name:
                 continue
             if "norm_q" in name or "norm_k" in name or "norm_added" in name:
                 p.data.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g, device=self.device_))

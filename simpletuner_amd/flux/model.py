@@ -96,6 +96,7 @@ class Flux(ModelFoundation):
         if getattr(self.config, "model_type", "lora") != "lora":
             raise RuntimeError("model_type == 'full' trains every transformer parameter: call enable_full_finetune() instead of add_lora_adapter()")
         targets = self._lora_target_set()
+        self.lycoris_value()                      # (refuses lora_type=lycoris by name: built for SD3)
         self.lora_dropout_value()                 # (refuses lora_dropout > 0 by name: built for SD3)
         self.use_dora_value()                     # (refuses use_dora by name: built for SD3)
         params = self.unwrap_model(self.model).add_lora_adapter(rank=int(self.config.lora_rank),

@@ -440,7 +440,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         full fine-tune exposes exactly its arena views; the VAE / ControlNet trunk never carry gradients"""
         if "lora" in str(getattr(self.config, "model_type", "lora")) and self.model is not None:
             for n, p_ in self.unwrap_model(self.model).named_parameters():
-                if ".lora_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
+                if ".lora_" not in n and ".lokr_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
                     p_.requires_grad_(False)
         elif str(getattr(self.config, "model_type", "lora")) == "full" and self.model is not None:
             # the reference leaves a full-rank model as diffusers loaded it — every parameter trainable — and `Trainer._get_trainable_parameters` collects
@@ -505,6 +505,71 @@ class ModelFoundation(ExplorativeModelingMixin):
             raise NotImplementedError("use_dora with lora_format=comfyui: the ComfyUI export of a DoRA adapter is not built on the st355 path; set "
                                       "--lora_format=diffusers")
         return True
+
+    LYCORIS_BUILT = False               # families whose engine folds the LoKr delta (SD3)
+    LYCORIS_CLASSES = ("Attention", "FeedForward")          # the `target_module` entries with adapter sites
+    _lycoris_alpha_logged = False
+
+    def lycoris_value(self):
+        """`lora_type=lycoris` (the reference hands `lycoris_config` to LyCORIS' create_lycoris: trainer.py:3390-3440) as the family's add_lora_adapter takes it: None
+        for a standard LoRA or a full fine-tune; a family without the fold refuses the flag by name (it would otherwise train a standard LoRA under it); for SD3 the
+        parsed JSON — {factors: {module class: factor}, multiplier, linear_dim, linear_alpha, init_norm, validation_strength} — with every option that is not built
+        refused by its key and the value to set, never a silently different adapter."""
+        cfg = self.config
+        if "lora" not in str(getattr(cfg, "model_type", "lora")) or str(getattr(cfg, "lora_type", "standard") or "standard").lower() != "lycoris":
+            return None
+        if not self.LYCORIS_BUILT:
+            raise NotImplementedError(f"lora_type=lycoris: LyCORIS adapters are not built for {self.NAME} on the st355 path (built: SD3); set --lora_type=standard")
+        src = getattr(cfg, "lycoris_config", None)
+        if isinstance(src, dict):
+            lc = dict(src)
+        elif src:
+            import json
+            with open(src, "r") as f:
+                lc = json.load(f)
+        else:
+            raise ValueError("lora_type=lycoris needs lycoris_config: the path of the LyCORIS JSON (algo, multiplier, linear_dim, linear_alpha, factor, apply_preset)")
+        refuse = lambda key, val, to: NotImplementedError(f"lycoris_config {key}={val}: not built on the st355 path (built: algo=lokr with both factors full, merged-weight "
+                                                          f"forward); set {to}")
+        algo = str(lc.get("algo", "lokr")).lower()
+        if algo != "lokr":
+            raise refuse("algo", algo, '"algo": "lokr"')
+        for k in ("decompose_both", "use_tucker", "use_scalar", "weight_decompose", "rs_lora", "train_norm", "bypass_mode"):
+            if lc.get(k):
+                raise refuse(k, "true", f'"{k}": false')
+        for k in ("dropout", "rank_dropout", "module_dropout"):
+            if float(lc.get(k, 0.0) or 0.0) > 0.0:
+                raise refuse(k, lc[k], f'"{k}": 0')
+        from .training.lora_keys import PEFTLoRAFormat, normalize_lora_format
+        if normalize_lora_format(getattr(cfg, "lora_format", None)) == PEFTLoRAFormat.COMFYUI:
+            raise NotImplementedError("lora_type=lycoris with lora_format=comfyui: the ComfyUI export of a LoKr adapter is not built on the st355 path; set "
+                                      "--lora_format=diffusers")
+        if getattr(cfg, "init_lora", None):
+            raise NotImplementedError(f"lora_type=lycoris with init_lora={cfg.init_lora}: starting a LoKr adapter from a file through init_lora is not built on the st355 "
+                                      "path; unset --init_lora (resume_from_checkpoint restores the adapter)")
+        preset = lc.get("apply_preset") or {}
+        classes = list(preset.get("target_module", self.LYCORIS_CLASSES))
+        for c in classes:
+            if c not in self.LYCORIS_CLASSES:
+                raise NotImplementedError(f"lycoris_config apply_preset.target_module entry {c!r}: not built for {self.NAME} on the st355 path; set target_module to a "
+                                          f"subset of {list(self.LYCORIS_CLASSES)}")
+        amap = preset.get("module_algo_map") or {}
+        factors = {}
+        for c in classes:
+            sub = amap.get(c) or {}
+            if str(sub.get("algo", algo)).lower() != "lokr":
+                raise refuse(f"apply_preset.module_algo_map.{c}.algo", sub["algo"], '"algo": "lokr"')
+            factors[c] = int(sub.get("factor", lc.get("factor", -1)))
+        linear_dim, linear_alpha = int(lc.get("linear_dim", 4)), lc.get("linear_alpha", None)
+        if linear_alpha is not None and float(linear_alpha) != float(linear_dim) and not ModelFoundation._lycoris_alpha_logged:
+            ModelFoundation._lycoris_alpha_logged = True
+            import logging
+            logging.getLogger(__name__).info("lycoris lokr: both factors are full matrices, so LyCORIS sets alpha = linear_dim and the scale is the multiplier; "
+                                             "linear_alpha=%s has no effect", linear_alpha)
+        init_norm = getattr(cfg, "init_lokr_norm", None)
+        return dict(factors=factors, multiplier=float(lc.get("multiplier", 1.0)), linear_dim=linear_dim, linear_alpha=linear_alpha,
+                    init_norm=None if init_norm in (None, False) else float(init_norm),
+                    validation_strength=float(getattr(cfg, "validation_lycoris_strength", 1.0) or 1.0))
 
     ROLLOUT_BATCH_KEYS = None           # families with the scheduled-sampling rollout (Flux, SD3): the per-sample batch entries their model_predict reads
 
@@ -857,6 +922,14 @@ class ModelFoundation(ExplorativeModelingMixin):
         from safetensors.torch import save_file
 
         from .training.lora_keys import PEFTLoRAFormat, normalize_lora_format
+        if not layers and getattr(self.unwrap_model(self.get_trained_component()), "lora_lokr", False):
+            if normalize_lora_format(getattr(self.config, "lora_format", None)) == PEFTLoRAFormat.COMFYUI:
+                raise NotImplementedError("lora_type=lycoris with lora_format=comfyui: the ComfyUI export of a LoKr adapter is not built on the st355 path; save with "
+                                          "--lora_format=diffusers")
+            os.makedirs(output_dir, exist_ok=True)
+            path = os.path.join(output_dir, self.LORA_WEIGHT_NAME)
+            save_file({k: v.detach().to("cpu").contiguous() for k, v in self.lokr_state_dict().items()}, path, metadata={"format": "pt"})
+            return path
         if not any(k.endswith("_lora_layers") for k in layers):
             layers = dict(layers, **{f"{self.MODEL_SUBFOLDER}_lora_layers": self.lora_state_dict()})
         flat, meta, comp_meta = {}, {}, {}
@@ -883,6 +956,50 @@ class ModelFoundation(ExplorativeModelingMixin):
         save_file(flat, path, metadata={"format": "pt"})
         return path
 
+    LYCORIS_PREFIX = "lycoris_"                    # LyCORIS' module naming: `lycoris_` + the module path with '.' -> '_'
+    LOKR_KEYS = (".lokr_w1", ".lokr_w2")
+
+    def lokr_state_dict(self, component=None) -> dict:
+        """a LoKr adapter as a LyCORIS file holds it: per adapted module `lycoris_<module path, '.' -> '_'>.lokr_w1`, `.lokr_w2` (fp32) and `.alpha` (a scalar,
+        = linear_dim: with both factors full LyCORIS sets alpha = linear_dim).  The lay-out is restated from LyCORIS' naming rule, not pinned against the package."""
+        comp = self.unwrap_model(component if component is not None else self.get_trained_component())
+        sd = {}
+        for n, p in comp.named_parameters():
+            for key in self.LOKR_KEYS:
+                if n.endswith(key):
+                    mod = self.LYCORIS_PREFIX + n[:-len(key)].replace(".", "_")
+                    sd[mod + key] = p.detach()
+                    sd[mod + ".alpha"] = torch.tensor(float(getattr(comp, "lokr_linear_dim", 10000)), dtype=torch.float32)
+        return sd
+
+    def _load_lokr_weights(self, comp, flat: dict):
+        """strict both ways: every factor of the component is in the file with its shape, and the file holds nothing else"""
+        own = {}
+        for n, p in comp.named_parameters():
+            for key in self.LOKR_KEYS:
+                if n.endswith(key):
+                    own[self.LYCORIS_PREFIX + n[:-len(key)].replace(".", "_") + key] = p
+        alphas = {k[:-len(key)] + ".alpha" for k in own for key in self.LOKR_KEYS if k.endswith(key)}
+        missing = [k for k in list(own) + sorted(alphas) if k not in flat]
+        if missing:
+            raise KeyError(f"LyCORIS checkpoint is missing {len(missing)} adapter tensors, e.g. {missing[:3]}")
+        extra = [k for k in flat if k not in own and k not in alphas]
+        if extra:
+            raise KeyError(f"LyCORIS checkpoint holds {len(extra)} tensors the adapter has no place for, e.g. {extra[:3]}; the lycoris_config (target_module) must match "
+                           "the one the file was trained with")
+        for k, p in own.items():
+            if tuple(flat[k].shape) != tuple(p.shape):
+                raise ValueError(f"LyCORIS checkpoint tensor {k} has shape {tuple(flat[k].shape)}, the adapter's is {tuple(p.shape)}: the lycoris_config factor must match "
+                                 "the one the file was trained with")
+        want = float(getattr(comp, "lokr_linear_dim", 10000))
+        for k in sorted(alphas):
+            if float(flat[k]) != want:
+                raise ValueError(f"LyCORIS checkpoint alpha {float(flat[k])} ({k}) differs from the configured linear_dim {want}; set linear_dim to match the file")
+        with torch.no_grad():
+            for k, p in own.items():
+                p.copy_(flat[k].to(device=p.device, dtype=p.dtype))
+        return comp
+
     def _kohya_name_map(self) -> dict:
         """kohya module name -> this component's module path, built forwards from the adapters that exist (the underscore-joined kohya spelling
         cannot be split back into a dotted path on its own)"""
@@ -906,6 +1023,15 @@ class ModelFoundation(ExplorativeModelingMixin):
         comp = self.get_trained_component()
         flat = load_file(os.path.join(input_dir, self.LORA_WEIGHT_NAME))
         prefix = f"{self.MODEL_SUBFOLDER}."
+        file_lokr, own_lokr = any(k.endswith(self.LOKR_KEYS) for k in flat), bool(getattr(self.unwrap_model(comp), "lora_lokr", False))
+        if file_lokr and not own_lokr:
+            raise ValueError("LoRA checkpoint carries LyCORIS LoKr factors (lokr_w1 / lokr_w2) but the adapter was built as a standard LoRA: set --lora_type=lycoris "
+                             "(and lycoris_config) before loading it")
+        if own_lokr and not file_lokr:
+            raise ValueError("lora_type=lycoris is set but the checkpoint carries no LoKr factors (lokr_w1 / lokr_w2): it is a standard LoRA file; set "
+                             "--lora_type=standard to load it")
+        if own_lokr:
+            return self._load_lokr_weights(self.unwrap_model(comp), flat)
         fmt = normalize_lora_format(getattr(self.config, "lora_format", None))
         if fmt == PEFTLoRAFormat.DIFFUSERS and self.AUTO_LORA_FORMAT_DETECTION and detect_state_dict_format(flat) == PEFTLoRAFormat.COMFYUI:
             fmt = PEFTLoRAFormat.COMFYUI

@@ -36,6 +36,7 @@ SYMBOLS = [
     "st355_lora_pack",
     "st355_lora_dropout_mask", "st355_lora_dropout_advance", "st355_lora_down_drop", "st355_lora_dx_drop", "st355_skinny_tn_drop", "st355_skinny_tn_drop_multi",
     "st355_dora_fold", "st355_dora_dmag_workspace", "st355_dora_dmag", "st355_dora_db_finish",
+    "st355_lokr_fold", "st355_lokr_mix", "st355_lokr_dw2_workspace", "st355_lokr_dw2", "st355_lokr_dw1_workspace", "st355_lokr_dw1",
     "st355_reflexflow_workspace", "st355_reflexflow_stats", "st355_reflexflow_loss", "st355_flow_euler_step",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
@@ -400,6 +401,13 @@ def _declare(lib):
         "st355_dora_dmag_workspace": (i64, [i64, i32]),
         "st355_dora_dmag": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, vp, i64, i32, i32, vp]),
         "st355_dora_db_finish": (C.c_int, [vp, vp, vp, vp, i32, i32, i32]),
+        "st355_lokr_fold": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), f32]),
+        "st355_lokr_mix": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, i32, i32, i32, vp, i64]),
+        "st355_lokr_dw2_workspace": (i64, [i64, i32, i32]),
+        "st355_lokr_dw2": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp, i64, i32, i32, f32, i32, vp]),
+        "st355_lokr_dw1_workspace": (i64, [i64]),
+        "st355_lokr_dw1": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, vp, i64, i32, i32, i32, f32, i32, vp]),
         "st355_reflexflow_workspace": (i64, [i64, i64]),
         "st355_reflexflow_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
         "st355_reflexflow_loss": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, i64, i64, f32]),

@@ -1052,6 +1052,82 @@ def dora_db_finish(P, g, gB, accumulate: bool = False):
 
 
 # ------------------------------------------------------------------------------------------------
+# LyCORIS LoKr (csrc/lokr.hip): dW = s kron(w1, w2) folded into the GEMM operands once per forward; the structured gradients of w1 / w2 in the backward
+# ------------------------------------------------------------------------------------------------
+def lokr_fold(W, targets, s: float, Wf, WfT):
+    """One fused projection (st355_lokr_fold): Wf = bf16(W + s kron(w1, w2)) on every target's row slab, WfT its transpose, and the bf16 copy of every w2.
+    targets: 1 .. 4 of (n_off, N, w1 [ol, im] fp32, w2 [ok, in] fp32, w2b [ok, in] bf16) in rising row order; rows outside every target are copied."""
+    for t, nm in ((W, "W"), (Wf, "Wf"), (WfT, "WfT")):
+        _chk(t, BF16, nm)
+    if W.dim() != 2:
+        raise _l.St355Error(f"lokr_fold: expected W [N, K], got {tuple(W.shape)}")
+    N, K = W.shape
+    if not (W.is_contiguous() and Wf.is_contiguous() and WfT.is_contiguous()) or tuple(Wf.shape) != (N, K) or tuple(WfT.shape) != (K, N):
+        raise _l.St355Error(f"lokr_fold: expected contiguous W / Wf [N, K] and WfT [K, N], got {tuple(W.shape)}, {tuple(Wf.shape)}, {tuple(WfT.shape)}")
+    G = len(targets)
+    if not 1 <= G <= 4:
+        raise _l.St355Error(f"lokr_fold: 1 .. 4 targets per projection (got {G})")
+    i32a, vpa = C.c_int32 * G, C.c_void_p * G
+    n_off, n_cnt, ol, im, p1, p2, pb = i32a(), i32a(), i32a(), i32a(), vpa(), vpa(), vpa()
+    for g, (off, n, w1, w2, w2b) in enumerate(targets):
+        _chk(w1, F32, "w1"); _chk(w2, F32, "w2"); _chk(w2b, BF16, "w2b")
+        if w1.dim() != 2 or w2.dim() != 2 or not (w1.is_contiguous() and w2.is_contiguous() and w2b.is_contiguous()) or w2b.shape != w2.shape \
+                or w1.shape[0] * w2.shape[0] != n or w1.shape[1] * w2.shape[1] != K:
+            raise _l.St355Error(f"lokr_fold: target {g}: expected contiguous w1 [ol, im], w2 / w2b [ok, in] with ol * ok = {n} and im * in = {K}, got "
+                                f"{tuple(w1.shape)}, {tuple(w2.shape)}, {tuple(w2b.shape)}")
+        n_off[g], n_cnt[g], ol[g], im[g], p1[g], p2[g], pb[g] = int(off), int(n), w1.shape[0], w1.shape[1], w1.data_ptr(), w2.data_ptr(), w2b.data_ptr()
+    _l.check(_l.load().st355_lokr_fold(_stream(), _ptr(W), _ptr(Wf), _ptr(WfT), N, K, G, n_off, n_cnt, ol, im, p1, p2, pb, float(s)), "lokr_fold")
+    return Wf
+
+
+def lokr_scratch(which: str, dev, M: int, cols: int):
+    """[M, cols] bf16 over one of the LoKr backward's scratch buffers ("dp": the mixed gradient, "p": x.view(M im, in) w2^T; each consumed right away)"""
+    return _scratch("lokr_" + which, dev, 2 * M * cols)[:2 * M * cols].view(BF16).view(M, cols)
+
+
+def lokr_mix(dy, n_off: int, w1, ok: int, out):
+    """out[m, j ok + k] = bf16(sum_i w1[i, j] dy[m, n_off + i ok + k]) (st355_lokr_mix).  dy: compact [M, C] bf16 or a [B, rows, C] view of a joint buffer;
+    w1 [ol, im] fp32; out [M, im ok] bf16 contiguous."""
+    _chk(dy, BF16, "lokr_mix: dy"); _chk(w1, F32, "lokr_mix: w1"); _chk(out, BF16, "lokr_mix: out")
+    M, Cn, ldd, seg, seg_s = _seg(dy, "lokr_mix: dy")
+    if w1.dim() != 2 or not w1.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (M, w1.shape[1] * ok) or n_off + w1.shape[0] * ok > Cn:
+        raise _l.St355Error(f"lokr_mix: expected contiguous w1 [ol, im] and out [{M}, im * {ok}], the slab inside dy's {Cn} columns; got {tuple(w1.shape)}, "
+                            f"{tuple(out.shape)}, n_off {n_off}")
+    _l.check(_l.load().st355_lokr_mix(_stream(), _ptr(dy), ldd, seg, seg_s, int(n_off), _ptr(w1), w1.shape[0], w1.shape[1], int(ok), _ptr(out), M), "lokr_mix")
+    return out
+
+
+def lokr_dw2(dP, x, im: int, out, alpha: float = 1.0, accumulate: bool = False):
+    """out[ok, in] (+)= alpha dP.view(M im, ok)^T x.view(M im, in) (st355_lokr_dw2).  dP [M, im ok] bf16 contiguous; x: compact [M, im in] bf16 or a
+    [B, rows, im in] view of a joint buffer; out fp32 contiguous."""
+    L = _l.load()
+    _chk(dP, BF16, "lokr_dw2: dP"); _chk(x, BF16, "lokr_dw2: x"); _chk(out, F32, "lokr_dw2: out")
+    M, K, ldx, seg, seg_s = _seg(x, "lokr_dw2: x")
+    if out.dim() != 2 or not out.is_contiguous() or not dP.is_contiguous() or dP.dim() != 2:
+        raise _l.St355Error("lokr_dw2: expected contiguous dP [M, im * ok] and out [ok, in]")
+    ok, in_ = out.shape
+    if tuple(dP.shape) != (M, im * ok) or K != im * in_:
+        raise _l.St355Error(f"lokr_dw2: expected dP [{M}, {im * ok}] and x with {im * in_} columns, got {tuple(dP.shape)} and {K}")
+    ws = _scratch("lokr_dw2", x.device, L.st355_lokr_dw2_workspace(M * im, ok, in_))
+    _l.check(L.st355_lokr_dw2(_stream(), _ptr(dP), _ptr(x), ldx, seg, seg_s, int(im), _ptr(out), M, ok, in_, float(alpha), 1 if accumulate else 0, _ptr(ws)), "lokr_dw2")
+    return out
+
+
+def lokr_dw1(dy, n_off: int, P, out, ok: int, alpha: float = 1.0, accumulate: bool = False):
+    """out[i, j] (+)= alpha sum_{m, k} dy[m, n_off + i ok + k] P[m, j ok + k] (st355_lokr_dw1).  dy as for lokr_mix; P [M, im ok] bf16 contiguous; out [ol, im] fp32."""
+    L = _l.load()
+    _chk(dy, BF16, "lokr_dw1: dy"); _chk(P, BF16, "lokr_dw1: P"); _chk(out, F32, "lokr_dw1: out")
+    M, Cn, ldd, seg, seg_s = _seg(dy, "lokr_dw1: dy")
+    if out.dim() != 2 or not out.is_contiguous() or not P.is_contiguous() or tuple(P.shape) != (M, out.shape[1] * ok) or n_off + out.shape[0] * ok > Cn:
+        raise _l.St355Error(f"lokr_dw1: expected contiguous out [ol, im] and P [{M}, im * {ok}], the slab inside dy's {Cn} columns; got {tuple(out.shape)}, "
+                            f"{tuple(P.shape)}, n_off {n_off}")
+    ws = _scratch("lokr_dw1", dy.device, L.st355_lokr_dw1_workspace(M))
+    _l.check(L.st355_lokr_dw1(_stream(), _ptr(dy), ldd, seg, seg_s, int(n_off), _ptr(P), _ptr(out), M, out.shape[0], out.shape[1], int(ok), float(alpha),
+                              1 if accumulate else 0, _ptr(ws)), "lokr_dw1")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # AdaLN / RMSNorm + RoPE
 # ------------------------------------------------------------------------------------------------
 def ln_modulate_fwd(x, scale, shift, rows_per_batch: int, eps: float = 1e-6, out=None):

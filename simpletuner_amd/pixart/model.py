@@ -55,6 +55,7 @@ class PixartSigma(ModelFoundation):
         if self.controlnet is not None:
             raise NotImplementedError("PixArt: a LoRA on the trunk together with the ControlNet branch is not built on the st355 path")
         comp = self.unwrap_model(self.model)
+        self.lycoris_value()                      # (refuses lora_type=lycoris by name: built for SD3)
         self.lora_dropout_value()                 # (refuses lora_dropout > 0 by name: built for SD3)
         self.use_dora_value()                     # (refuses use_dora by name: built for SD3)
         return comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),

@@ -54,6 +54,7 @@ class StableDiffusion1(ModelFoundation):
 
     def add_lora_adapter(self):
         comp = self.unwrap_model(self.model)
+        self.lycoris_value()                      # (refuses lora_type=lycoris by name: built for SD3)
         self.lora_dropout_value()                 # (refuses lora_dropout > 0 by name: built for SD3)
         self.use_dora_value()                     # (refuses use_dora by name: built for SD3)
         return comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),

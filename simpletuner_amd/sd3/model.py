@@ -23,6 +23,7 @@ class SD3(ModelFoundation):
     MODEL_SUBFOLDER = "transformer"
     LORA_DROPOUT_BUILT = True
     DORA_BUILT = True
+    LYCORIS_BUILT = True
     ROLLOUT_BATCH_KEYS = ("encoder_hidden_states", "add_text_embeds")          # what _model_predict_single reads per sample (scheduled sampling's batch-1 forwards)
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
@@ -51,11 +52,29 @@ class SD3(ModelFoundation):
         if getattr(self.config, "model_type", "lora") != "lora":
             raise RuntimeError("model_type == 'full' trains every transformer parameter: call enable_full_finetune() (or freeze_components()) instead of add_lora_adapter()")
         comp = self.unwrap_model(self.model)
+        if str(getattr(self.config, "lora_type", "standard") or "standard").lower() == "lycoris":
+            return self._add_lycoris_adapter(comp)
         params = comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),
                                        targets="default", seed=int(getattr(self.config, "seed", 42) or 42) + 7,
                                        init_b_std=float(getattr(self.config, "lora_init_b_std", 0.0)),
                                        dropout=self.lora_dropout_value(), dropout_seed=int(getattr(self.config, "seed", 42) or 42),
                                        dropout_rank=int(getattr(self.accelerator, "process_index", 0) or 0), dora=self.use_dora_value())
+        comp.prepare_for_training()
+        return params
+
+    def _add_lycoris_adapter(self, comp):
+        """`lora_type=lycoris`: LoKr adapters on the Attention / FeedForward Linears from the JSON named by `lycoris_config` (ModelFoundation.lycoris_value).  The
+        standard-LoRA-only flags keep their treatment (lora_dropout / use_dora ignored); Internal Guidance / NextLat raise the reference's ValueError first."""
+        cfg = self.config
+        if getattr(cfg, "internal_guidance_enabled", False):
+            raise ValueError("Internal Guidance requires standard PEFT LoRA or full-model training so its auxiliary head is optimized and saved.")
+        if getattr(cfg, "nextlat_enabled", False):
+            raise ValueError("NextLat requires standard PEFT LoRA or full-model training so its predictor is optimized and saved.")
+        lc = self.lycoris_value()
+        params = comp.add_lokr_adapter(factors=lc["factors"], multiplier=lc["multiplier"], seed=int(getattr(cfg, "seed", 42) or 42) + 7, init_norm=lc["init_norm"],
+                                       linear_dim=lc["linear_dim"])
+        comp.lokr_validation_strength = lc["validation_strength"]
+        self.lycoris = lc
         comp.prepare_for_training()
         return params
 

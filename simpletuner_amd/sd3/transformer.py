@@ -24,8 +24,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
-                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lora_down, lora_dx_finish, lora_dx_kw,
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
+                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
                       lora_fwd_kw, lora_grads, lora_up, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
@@ -111,6 +111,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.lora_groups: List[LoraGroup] = []
         self.lora_dropout: Optional[LoraDropout] = None          # add_lora_adapter(dropout > 0): applies to training forwards only
         self.lora_dora = False                                   # add_lora_adapter(dora=True): part of the weight, applies to every forward
+        self.lora_lokr = False                                   # add_lokr_adapter(): LyCORIS LoKr, part of the weight, applies to every forward
+        self.lokr_multiplier, self.lokr_validation_strength = 1.0, 1.0
         self.lora_flat: Optional[torch.Tensor] = None
         self.lora_grad_flat: Optional[torch.Tensor] = None
         self._lora_params: List[nn.Parameter] = []
@@ -385,6 +387,90 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
+    # LyCORIS LoKr (`lora_type=lycoris`, `algo: lokr`): engine.LokrGroup on the Attention and FeedForward Linears
+    # ------------------------------------------------------------------------------------------------
+    LOKR_CLASSES = ("Attention", "FeedForward")
+
+    def add_lokr_adapter(self, factors: Optional[Dict[str, int]] = None, multiplier: float = 1.0, seed: int = 7, init_norm: Optional[float] = None,
+                         linear_dim: Optional[int] = None):
+        """factors: {"Attention": factor, "FeedForward": factor} — the module classes that get adapters (LyCORIS' `target_module`) and their `factor`.  Every Linear of a
+        selected class gets w1 [ol, im] and w2 [ok, in] (`<module>.lokr_w1` / `<module>.lokr_w2`, fp32, back to back in the adapter arena in target order) and
+        computes y = x bf16(W + multiplier kron(w1, w2))^T + b in every forward, eval() included.  w1 ~ U(-1 / sqrt(im), 1 / sqrt(im)) and w2 = 0: the first
+        forward is the base model's bit for bit.  init_norm (the `init_lokr_norm` value): w1 = 1 and w2 a normal draw rescaled to the frozen weight's norm, std and
+        mean, times the value.  linear_dim: LyCORIS' rank bound — a value that would make any w2 low-rank is refused."""
+        factors = dict(factors if factors is not None else {"Attention": 10, "FeedForward": 4})
+        for k in factors:
+            if k not in self.LOKR_CLASSES:
+                raise NotImplementedError(f"lycoris lokr: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
+        if self._ig_block is not None or self._nl_block is not None:
+            raise NotImplementedError("lycoris lokr with an Internal Guidance head / a NextLat predictor is not built on the st355 path")
+        dev = self.device_
+        self.lora_groups, self.lora_dropout, self.lora_dora, self.lora_lokr = [], None, False, True
+        self.lokr_multiplier = float(multiplier)
+        self.lokr_linear_dim = 10000 if linear_dim is None else int(linear_dim)          # what an adapter file records as `alpha`
+        plan = []
+
+        def group(lin, prefix, names, factor):
+            n_each = lin.w.shape[0] // len(names)
+            g = LokrGroup(lin, [(prefix + n, j * n_each, n_each) for j, n in enumerate(names)], [factor] * len(names), dev)
+            lin.lora = g
+            self.lora_groups.append(g)
+            plan.append(g)
+
+        fa, ff = factors.get("Attention"), factors.get("FeedForward")
+        for i, blk in enumerate(self.blocks):
+            p = f"transformer_blocks.{i}."
+            if fa is not None:
+                group(blk.qkv, p + "attn.", ["to_q", "to_k", "to_v"], fa)
+                group(blk.to_out, p + "attn.", ["to_out.0"], fa)
+                group(blk.add_qkv, p + "attn.", ["add_q_proj", "add_k_proj", "add_v_proj"], fa)
+                if blk.to_add_out is not None:
+                    group(blk.to_add_out, p + "attn.", ["to_add_out"], fa)
+                if blk.dual:
+                    group(blk.qkv2, p + "attn2.", ["to_q", "to_k", "to_v"], fa)
+                    group(blk.to_out2, p + "attn2.", ["to_out.0"], fa)
+            if ff is not None:
+                group(blk.ff1, p, ["ff.net.0.proj"], ff)
+                group(blk.ff2, p, ["ff.net.2"], ff)
+                if blk.ffc1 is not None:
+                    group(blk.ffc1, p, ["ff_context.net.0.proj"], ff)
+                    group(blk.ffc2, p, ["ff_context.net.2"], ff)
+        if linear_dim is not None:          # LyCORIS keeps w2 a full matrix only while linear_dim >= max(ok, in) / 2; below that it trains a low-rank pair
+            for g in plan:
+                for (name, _, _), (ol, ok, im, in_) in zip(g.targets, g.shapes):
+                    if linear_dim < max(ok, in_) / 2:
+                        raise NotImplementedError(f"lycoris_config linear_dim={linear_dim}: {name} would get a low-rank w2 ([{ok}, {in_}] needs linear_dim >= "
+                                                  f"{max(ok, in_) // 2}), which is not built on the st355 path; set \"linear_dim\": 10000 (full matrices)")
+        total = sum(ol * im + ok * in_ for g in plan for (ol, ok, im, in_) in g.shapes)
+        total = (total + 7) // 8 * 8
+        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
+        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(seed)
+        off = 0
+        self._lora_params = []
+        for g in plan:
+            g.flat_lo = off
+            for (name, n_off, N), (ol, ok, im, in_) in zip(g.targets, g.shapes):
+                views = []
+                for shp in ((ol, im), (ok, in_)):
+                    n = shp[0] * shp[1]
+                    views.append((self.lora_flat[off:off + n].view(shp), self.lora_grad_flat[off:off + n].view(shp)))
+                    off += n
+                (w1, g1), (w2, g2) = views
+                if init_norm is None:
+                    bound = 1.0 / math.sqrt(im)
+                    w1.copy_((torch.rand(ol, im, generator=gen, device=dev) * 2 - 1) * bound)
+                else:
+                    w1.fill_(1.0)
+                    lokr_init_norm(g.lin.w[n_off:n_off + N], w2, float(init_norm), gen)
+                p1, p2 = nn.Parameter(w1), nn.Parameter(w2)
+                attach(self, name + ".lokr_w1", p1); attach(self, name + ".lokr_w2", p2)
+                g.w1.append(p1.data); g.w2.append(p2.data); g.g1.append(g1); g.g2.append(g2)
+                self._lora_params += [p1, p2]
+            g.flat_hi = off
+        return self._lora_params
+
+    # ------------------------------------------------------------------------------------------------
     def _tables(self, h: int, w: int, S: int, B: int):
         """cropped position table expanded over the batch ([B*h*w, D] bf16) and identity RoPE tables (SD3 has no RoPE)"""
         key = (h, w, S, B)
@@ -453,7 +539,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
 
         def down_rows(lin, x, rows):
             """lora_down over one stream's rows of the joint attention output: undropped, the plain GEMM in the operand form of the projection itself"""
-            if lin is None or lin.lora is None:
+            if lin is None or lin.lora is None or not lin.lora.K2:          # (a LoKr group has no rank-space side path)
                 return None
             T = torch.empty(B * rows, lin.lora.K2, dtype=BF16, device=dev)
             if drop is not None:
@@ -505,19 +591,19 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         yf_i, yf_t = ybuf(B * Si), (None if blk.last else ybuf(B * St))
         kf_i, kf_t = aux(yf_i), aux(yf_t)
         if blk.last:
-            h_i = ops.gemm(n2_i, blk.ff1.w, bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img)
-            x2_img = ops.gemm(h_i, blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D],
+            h_i = ops.gemm(n2_i, lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img)
+            x2_img = ops.gemm(h_i, lin_w(blk.ff2), bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D],
                               rows_per_batch=rpb, **kf_i)
         else:
             n2_t = ops.ln_modulate_fwd(x1_txt, mt[:, 4 * D:5 * D], mt[:, 3 * D:4 * D], St)
             hpre_txt = torch.empty(B * St, 4 * D, dtype=BF16, device=dev)
-            h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=blk.ff1.w, bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img),
-                                         dict(a=n2_t, w=blk.ffc1.w, bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt)])
+            h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img),
+                                         dict(a=n2_t, w=lin_w(blk.ffc1), bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt)])
             x2_img, x2_txt = ops.gemm_grouped([
-                dict(a=h_i, w=blk.ff2.w, bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D], rows_per_batch=rpb, **kf_i),
-                dict(a=h_t, w=blk.ffc2.w, bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt, gate=mt[:, 5 * D:6 * D], rows_per_batch=St, **kf_t)])
+                dict(a=h_i, w=lin_w(blk.ff2), bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D], rows_per_batch=rpb, **kf_i),
+                dict(a=h_t, w=lin_w(blk.ffc2), bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt, gate=mt[:, 5 * D:6 * D], rows_per_batch=St, **kf_t)])
         if save:
-            sv = SimpleNamespace(img=img, txt=txt, n_img=n_img, n_txt=n_txt if (T_txt is not None or full) else None, qkv=qkv, Q=Q, K=K,
+            sv = SimpleNamespace(img=img, txt=txt, n_img=n_img, n_txt=n_txt if (blk.add_qkv.lora is not None or full) else None, qkv=qkv, Q=Q, K=K,
                                  Qt=Qt, Kt=Kt, O=O, lse2=lse2, x1_img=x1_img, x1_txt=x1_txt, hpre_img=hpre_img,
                                  hpre_txt=hpre_txt, T_img=T_img, T_txt=T_txt, T_o=T_o, T_ao=T_ao, d2=d2)
             if full:    # a full fine-tune also needs every Linear's input (weight gradients) and the un-gated branch outputs (gate gradients)
@@ -544,7 +630,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
           backward, full          no trainable q / k RMSNorm weights (SD3.5): their gradients ride in the host form's RMSNorm backward pass"""
         if not (_BLOCK_ABI and not blk.dual and ops.ATTN_TR and all(t is None or t.is_contiguous() for t in streams)):
             return False
-        plain_lora = getattr(env, "drop", None) is None and not self.lora_dora
+        plain_lora = getattr(env, "drop", None) is None and not self.lora_dora and not self.lora_lokr
         if not backward:
             return (1 if env.rpb_i == 1 else env.Si) == env.Si and plain_lora
         if not full:
@@ -678,15 +764,25 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         mt = mod[:, blk.mod_off_c:blk.mod_off_c + (2 if blk.last else 6) * D]
         rpb_i = 1 if ctx.rpb_i == 1 else Si
         g_i = ops.scale_cols(d_img, mi[:, 5 * D:6 * D], rpb_i)
+
+        def ff_grads(l1, l2, x1, m6, rpb_, hpre, g_, dh_):
+            """the adapter gradients of a feed-forward pair (LoKr's FeedForward sites): its gradient operands are recomputed, nothing is saved for them — the
+            modulated LayerNorm rows as the forward made them, the activated rows from the kept pre-activation"""
+            if l1.lora is not None:
+                lora_grads(l1, ops.ln_modulate_fwd(x1, m6[:, 4 * D:5 * D], m6[:, 3 * D:4 * D], rpb_), None, dh_, None, acc_, gs_, drop)
+            if l2.lora is not None:
+                lora_grads(l2, ops.gelu_tanh(hpre), None, g_, None, acc_, gs_, drop)
+
         if blk.last:
-            dh_i = ops.gemm(g_i, blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
-            dn2_i = ops.gemm(dh_i, blk.ff1.wT)
+            dh_i = ops.gemm(g_i, lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
+            dn2_i = ops.gemm(dh_i, lin_wT(blk.ff1))
             dx1_t = dx1g_t = None
         else:
             g_t = ops.scale_cols(d_txt, mt[:, 5 * D:6 * D], St)
-            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img),
-                                           dict(a=g_t, w=blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)])
-            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT), dict(a=dh_t, w=blk.ffc1.wT)])
+            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img),
+                                           dict(a=g_t, w=lin_wT(blk.ffc2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)])
+            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=lin_wT(blk.ff1)), dict(a=dh_t, w=lin_wT(blk.ffc1))])
+            ff_grads(blk.ffc1, blk.ffc2, sv.x1_txt, mt, St, sv.hpre_txt, g_t, dh_t)
             dx1_t, dx1g_t = ops.ln_modulate_bwd(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dres=d_txt, gate=mt[:, 2 * D:3 * D], want_gated=True)
             del g_t, dh_t, dn2_t
         dn2a = None
@@ -712,6 +808,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             del dxg2, dO2, dQ2, dK2, dqkv2, U2, Uq2, d2
         else:
             dx1_i, dx1g_i = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], rpb_i, dres=d_img, gate=mi[:, 2 * D:3 * D], want_gated=True)
+        ff_grads(blk.ff1, blk.ff2, sv.x1_img, mi, rpb_i, sv.hpre_img, g_i, dh_i)
         del g_i, dh_i, dn2_i
         # attention output projections -> dO rows of both streams (+ adapter grads); a context_pre_only block has no txt rows (and no to_add_out)
         dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
@@ -894,6 +991,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             g.pack()
             if g.dora is not None:          # DoRA: the row scale of the current A / B / m folded into W and B_blk, once per forward
                 g.fold()
+        if self.lora_lokr:                  # LoKr: W + s kron(w1, w2) of the current factors, once per forward (eval() forwards: times the validation strength)
+            mult = self.lokr_multiplier * (1.0 if self.training else self.lokr_validation_strength)
+            for g in self.lora_groups:
+                g.fold(mult)
         pos, cos, sin = self._tables(h, w, S, B)
         # ---- embeddings (sd3/transformer.py:623-700) ----
         patches = ops.patchify(latents, order=0).view(B * Si, 4 * C)
@@ -1182,7 +1283,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             self._nl = NextLatHead(self._nl_block, self.D, self._nl_arena, (None,) * 6, lo, self.arena.numel(), self.device_)
             for attr, t in zip(("g_gamma", "g_beta", "g_W_up", "g_b_up", "g_W_down", "g_b_down"), self._nl_arena):
                 gview(self._nl, attr, t)
-        ps = sorted([p for n, p in self.named_parameters() if ".lora_" not in n], key=lambda p: p.data_ptr())
+        ps = sorted([p for n, p in self.named_parameters() if ".lora_" not in n and ".lokr_" not in n], key=lambda p: p.data_ptr())
         for p in ps:
             p.requires_grad_(True)
         self._full_params = ps

@@ -40,6 +40,7 @@ class SDXL(ModelFoundation):
     def add_lora_adapter(self):
         """peft LoRA on DEFAULT_LORA_TARGET (to_k,to_q,to_v,to_out.0 of every attn1 / attn2): the "SDXL-LoRA" workload of BASELINE.json's metric"""
         comp = self.unwrap_model(self.model)
+        self.lycoris_value()                      # (refuses lora_type=lycoris by name: built for SD3)
         self.lora_dropout_value()                 # (refuses lora_dropout > 0 by name: built for SD3)
         self.use_dora_value()                     # (refuses use_dora by name: built for SD3)
         return comp.add_lora_adapter(rank=int(self.config.lora_rank), alpha=getattr(self.config, "lora_alpha", None),
