@@ -863,6 +863,32 @@ def mod_grads(D: int, dn, x_in, rows: int, k_shift: int, k_scale: int, dm, xhat=
 
 
 # ------------------------------------------------------------------------------------------------
+# the backward of the one autograd node per network (flux/transformer.py::_FluxFn / _FluxFullFn, sd3/transformer.py::_SD3Fn / _SD3FullFn)
+# ------------------------------------------------------------------------------------------------
+def node_backward(fctx, full: bool, *d_outs):
+    """Runs the model's hand-written backward on the node's kept context between the gradient exchange's begin / finish, then hands autograd a private flat
+    copy (one copy per step) so that .grad never aliases the arena the next backward overwrites; the per-parameter gradients returned stay views of ONE
+    contiguous buffer, which the fused optimizer / RCCL all-reduce exploit.  full: the bf16 gradient arena and `_full_params`, else the adapters' fp32 one."""
+    model = fctx.model
+    if model.grad_sync is not None:
+        model.grad_sync.begin()
+    (model._engine_backward_full if full else model._engine_backward)(fctx.ectx, *d_outs)
+    fctx.ectx = None
+    if model.grad_sync is not None:
+        model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world
+    from .training.grad_sync import hand_over_gradients
+    model._last_grad_flat = gflat = hand_over_gradients(model, model.grad_arena if full else model.lora_grad_flat)
+    if full:
+        return tuple(gflat[off:off + n].view_as(p) for (off, n), p in zip(model._full_offsets, model._full_params))
+    grads, off = [], 0
+    for p in model._lora_params:
+        n = p.numel()
+        grads.append(gflat[off:off + n].view_as(p))
+        off += n
+    return tuple(grads)
+
+
+# ------------------------------------------------------------------------------------------------
 # full-rank training: what one backward shares between the families
 # ------------------------------------------------------------------------------------------------
 class FullGrads:

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, mod_grads, pad64, problems, rows_of
+from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, lora_up, mod_grads, node_backward, pad64, problems, rows_of
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_QK_NORM_ROPE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -45,6 +45,16 @@ _TRANSPOSED_COPIES = os.environ.get("ST355_ATTN_BWD_T") == "1"      # A/B switch
 
 def _block_abi_ok() -> bool:
     return _BLOCK_ABI
+
+
+def _ext_fwd(lg, T) -> dict:
+    """the K-extension of an adapted Linear's forward GEMM: [x | T] [W | sB]^T with T = x A^T; nothing without an adapter (lg: its LoraGroup or None)"""
+    return dict(a2=T, b2=lg.B_blk, k2_real=lg.k2_real) if lg is not None else {}
+
+
+def _ext_bwd(lg, U) -> dict:
+    """its backward mirror, on the dgrad GEMM: dx = dy W + (dy sB) A with U = dy sB"""
+    return dict(a2=U, b2=lg.A_cat_T, k2_real=lg.k2_real) if lg is not None else {}
 
 
 class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
@@ -347,19 +357,13 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
     # ------------------------------------------------------------------------------------------------
     def _lin_fwd(self, lin, x, **kw):
         """y = x W^T + b (+ LoRA K-extension).  Returns (y, T) where T = x A^T (kept for the rank-space backward)."""
-        T = None
-        if lin.lora is not None:
-            T = ops.gemm(x, lin.lora.A_cat)
-            kw.update(a2=T, b2=lin.lora.B_blk, k2_real=lin.lora.k2_real)
-        return ops.gemm(x, lin.w, bias=lin.b, **kw), T
+        T = ops.gemm(x, lin.lora.A_cat) if lin.lora is not None else None
+        return ops.gemm(x, lin.w, bias=lin.b, **kw, **_ext_fwd(lin.lora, T)), T
 
     def _lin_bwd(self, lin, dy, x=None, T=None, **kw):
         """dx = dy W (+ LoRA K-extension (dy sB) A); also writes the adapter gradients when the projection has one."""
-        U = None
-        if lin.lora is not None:
-            U = ops.gemm(dy, lin.lora.B_blk_T)
-            kw.update(a2=U, b2=lin.lora.A_cat_T, k2_real=lin.lora.k2_real)
-        dx = ops.gemm(dy, lin.wT, **kw)
+        U = ops.gemm(dy, lin.lora.B_blk_T) if lin.lora is not None else None
+        dx = ops.gemm(dy, lin.wT, **kw, **_ext_bwd(lin.lora, U))
         if lin.lora is not None:
             lin.lora.grads(x, T, dy, U, self.accumulate_lora_grads, self.grad_sync)
         return dx
@@ -465,8 +469,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         n_txt = ops.ln_modulate_fwd(txt, mt[:, D:2 * D], mt[:, :D], St)
         T_img = ops.gemm(n_img, blk.qkv.lora.A_cat) if blk.qkv.lora is not None else None
         T_txt = ops.gemm(n_txt, blk.add_qkv.lora.A_cat) if blk.add_qkv.lora is not None else None
-        kw_t = dict(a2=T_txt, b2=blk.add_qkv.lora.B_blk, k2_real=blk.add_qkv.lora.k2_real) if T_txt is not None else {}
-        kw_i = dict(a2=T_img, b2=blk.qkv.lora.B_blk, k2_real=blk.qkv.lora.k2_real) if T_img is not None else {}
+        kw_t, kw_i = _ext_fwd(blk.add_qkv.lora, T_txt), _ext_fwd(blk.qkv.lora, T_img)
         O = torch.empty(B * S, D, dtype=BF16, device=dev); lse2 = torch.empty(B, H, S, dtype=F32, device=dev)
         qkv = V = rrms = Qt = Kt = None
         if fused:
@@ -508,11 +511,11 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         if T_o is not None:
             for pr in problems(B, Si, dict(a=O_i, w=blk.to_out.lora.A_cat, out=T_o)):
                 ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-            kw_i.update(a2=T_o, b2=blk.to_out.lora.B_blk, k2_real=blk.to_out.lora.k2_real)
+            kw_i.update(_ext_fwd(blk.to_out.lora, T_o))
         if T_ao is not None:
             for pr in problems(B, St, dict(a=O_t, w=blk.to_add_out.lora.A_cat, out=T_ao)):
                 ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-            kw_t.update(a2=T_ao, b2=blk.to_add_out.lora.B_blk, k2_real=blk.to_add_out.lora.k2_real)
+            kw_t.update(_ext_fwd(blk.to_add_out.lora, T_ao))
         ops.gemm_grouped(problems(B, Si, dict(a=O_i, w=blk.to_out.w, bias=blk.to_out.b, out=x1_img, epilogue=EPI_GATE_RESIDUAL, aux_in=img,
                                                       gate=mi[:, 2 * D:3 * D], rows_per_batch=rpi, **kw_i))
                          + problems(B, St, dict(a=O_t, w=blk.to_add_out.w, bias=blk.to_add_out.b, out=x1_txt, epilogue=EPI_GATE_RESIDUAL,
@@ -522,17 +525,16 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         n2_t = ops.ln_modulate_fwd(x1_txt, mt[:, 4 * D:5 * D], mt[:, 3 * D:4 * D], St)
         hpre_img = torch.empty(B * Si, 4 * D, dtype=BF16, device=dev); hpre_txt = torch.empty(B * St, 4 * D, dtype=BF16, device=dev)
         # '+ffs' adapters (flux/model.py:1272-1301): the same K-extension as the attention projections' — T = x A^T first, then [x | T] [W | sB]^T in the projection's launch
-        ext = lambda lg, T_: dict(a2=T_, b2=lg.B_blk, k2_real=lg.k2_real) if lg is not None else {}
         T_f1 = ops.gemm(n2_i, blk.ff1.lora.A_cat) if blk.ff1.lora is not None else None
         T_c1 = ops.gemm(n2_t, blk.ffc1.lora.A_cat) if blk.ffc1.lora is not None else None
-        h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=blk.ff1.w, bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img, **ext(blk.ff1.lora, T_f1)),
-                                     dict(a=n2_t, w=blk.ffc1.w, bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt, **ext(blk.ffc1.lora, T_c1))])
+        h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=blk.ff1.w, bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img, **_ext_fwd(blk.ff1.lora, T_f1)),
+                                     dict(a=n2_t, w=blk.ffc1.w, bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt, **_ext_fwd(blk.ffc1.lora, T_c1))])
         T_f2 = ops.gemm(h_i, blk.ff2.lora.A_cat) if blk.ff2.lora is not None else None
         T_c2 = ops.gemm(h_t, blk.ffc2.lora.A_cat) if blk.ffc2.lora is not None else None
         x = x2_img = x2_txt = None
         kf_i = dict(aux_out=yf_i) if yf_i is not None else {}
         kf_t = dict(aux_out=yf_t) if yf_t is not None else {}
-        kf_i.update(ext(blk.ff2.lora, T_f2)); kf_t.update(ext(blk.ffc2.lora, T_c2))
+        kf_i.update(_ext_fwd(blk.ff2.lora, T_f2)); kf_t.update(_ext_fwd(blk.ffc2.lora, T_c2))
         if bi == len(self.double) - 1:
             # the last double block's MLP down-projections write the joint [txt || img] sequence of the single blocks in place
             # (flux/transformer.py:1332 `torch.cat`): one problem per (stream, sample), no concat pass
@@ -608,8 +610,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         hpre = torch.empty(B * S, 4 * D, dtype=BF16, device=dev)
         lm, lp = blk.proj_mlp.lora, blk.proj_out.lora
         T_m = ops.gemm(n, lm.A_cat) if lm is not None else None
-        hact = ops.gemm(n, blk.proj_mlp.w, bias=blk.proj_mlp.b, epilogue=EPI_GELU, aux_out=hpre,
-                        **(dict(a2=T_m, b2=lm.B_blk, k2_real=lm.k2_real) if lm is not None else {}))
+        hact = ops.gemm(n, blk.proj_mlp.w, bias=blk.proj_mlp.b, epilogue=EPI_GELU, aux_out=hpre, **_ext_fwd(lm, T_m))
         # cat[attn, mlp] @ Wout^T is a two-segment K loop: no [B,S,5D] concat buffer is ever materialised
         y = torch.empty(B * S, D, dtype=BF16, device=dev) if keep_y else None          # the un-gated branch output (gate gradient)
         x_in, T_p = x, None
@@ -689,14 +690,12 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         em.temb, em.st = temb, ops.silu(temb)
         ml = self.mod_lora
         T_mod = ops.gemm(em.st, ml.A_cat) if ml is not None else None
-        mod = ops.gemm(em.st, self.mod_w, bias=self.mod_b, **(dict(a2=T_mod, b2=ml.B_blk, k2_real=ml.k2_real) if ml is not None else {}))   # [B, mod_total]: every block's modulation at once
+        mod = ops.gemm(em.st, self.mod_w, bias=self.mod_b, **_ext_fwd(ml, T_mod))   # [B, mod_total]: every block's modulation at once
         if tokenwise:
             xoff = self.single[0].mod_off if self.single else self.mod_off_out          # the single blocks' and norm_out's columns follow the double blocks'
             mod_x = torch.cat([mod[:, None, xoff:].expand(B, St, self.mod_total - xoff), mod_img.view(B, Si, -1)[:, :, xoff:]], dim=1).reshape(B * S, self.mod_total - xoff)
         env = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, cos_p=cos_p, sin_p=sin_p, mod=mod, scale=1.0 / math.sqrt(hd), key_bias=key_bias,
                               full=bool(full), tokenwise=tokenwise, mod_img=mod_img, mod_x=mod_x, xoff=xoff)
-        segs_d = self._checkpoint_segments(len(self.double)) if save else [(i, 1, False) for i in range(len(self.double))]
-        segs_s = self._checkpoint_segments(len(self.single)) if save else [(i, 1, False) for i in range(len(self.single))]
         # TREAD routing (flux/transformer.py:1101-1133, 1211-1241 double blocks, 1394-1486 single blocks; training/tread.py): only while training; between a route's
         # two blocks the IMAGE stream is a per-sample subset of its tokens, the text tokens all stay.  Layer indices run over double + single blocks.  Under
         # routing the reference drops the segmented checkpoint form for the per-block one (:1144-1157 `not use_routing`).
@@ -709,12 +708,17 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             raise NotImplementedError("TREAD routing with flux_lora_target='ai-toolkit' (modulation-row gradients over routed token subsets) is not built on the st355 path")
         if routes and full:
             raise NotImplementedError("TREAD routing under full-rank Flux training is not built on the st355 path (LoRA training routes)")
-        if routes:
+        # the checkpoint plan (start, count, checkpointed) is made per stack, so no segment straddles the two; everything in the context — segments, kept segment
+        # inputs `ck`, saved activations `blocks`, per-block `envs`, routes — is indexed by the GLOBAL block index, double blocks first
+        if not save:
+            plan = lambda n: [(i, 1, False) for i in range(n)]
+        elif routes:
             from ..training.checkpoint_plan import per_block as _per_block
-            gc_, iv_, sd_ = bool(self.gradient_checkpointing), self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride
-            segs_d, segs_s = _per_block(nd, gc_, iv_, sd_), _per_block(ns, gc_, iv_, sd_)
-        ctx = SimpleNamespace(env=env, dbl={}, sgl={}, segs_d=segs_d, segs_s=segs_s, ck_d={}, ck_s={}, env_d=[env] * nd, env_s=[env] * ns,
-                              route_start={}, route_end={})
+            plan = lambda n: _per_block(n, bool(self.gradient_checkpointing), self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride)
+        else:
+            plan = self._checkpoint_segments
+        segs_d, segs_s = plan(nd), [(nd + s0, n, ck) for (s0, n, ck) in plan(ns)]
+        ctx = SimpleNamespace(env=env, blocks=[None] * (nd + ns), segs=segs_d + segs_s, ck={}, envs=[env] * (nd + ns), route_start={}, route_end={})
         rt = SimpleNamespace(ptr=0, info=None, saved=None, env=env)          # the open route: its mask, the full image stream at its start, the routed env
 
         def start_route(img_full, g):
@@ -748,7 +752,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         x = None
         # nothing below the first block that carries an adapter is differentiated (add_lora_adapter: 'tiny' / 'nano' start at single block 7): those blocks keep
         # no activations and no checkpoint inputs
-        stop = 0 if full else getattr(self, "_bwd_stop", 0)
+        stop = ctx.stop = 0 if full else getattr(self, "_bwd_stop", 0)
         ls = None
         if save and self._layersync is not None:
             self._layersync_refusals(stop, tokenwise)
@@ -759,12 +763,10 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                 if starts(bi):
                     img = start_route(img, bi)
                 if ck and bi == s0 and save and s0 + n - 1 >= stop:
-                    ctx.ck_d[s0] = (img, txt)                 # a checkpointed segment keeps only its input; its blocks are re-run in backward
-                ctx.env_d[bi] = rt.env
-                img, txt, x, sv = self._double_fwd(bi, img, txt, rt.env, save and not ck and bi >= stop)
-                if sv is not None:
-                    ctx.dbl[bi] = sv
-                if ls is not None:                            # LayerSync: the block's image-token output (the last double block wrote the joint sequence)
+                    ctx.ck[s0] = (img, txt)                   # a checkpointed segment keeps only its input; its blocks are re-run in backward
+                ctx.envs[bi] = rt.env
+                img, txt, x, ctx.blocks[bi] = self._double_fwd(bi, img, txt, rt.env, save and not ck and bi >= stop)
+                if ls is not None:                           # LayerSync: the block's image-token output (the last double block wrote the joint sequence)
                     ls.tap(bi, img.view(B, Si, D) if x is None else rows_of(x, St, Si, B, S))
                 if ends(bi):
                     if x is not None:                         # the last double block wrote the joint [txt || kept img] sequence: re-open it
@@ -780,18 +782,15 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         del img, txt
         # ---- single blocks ----
         for (s0, n, ck) in segs_s:
-            for bi in range(s0, s0 + n):
-                g = nd + bi
+            for g in range(s0, s0 + n):
                 if starts(g):
                     xv = x.view(B, S, D)
                     t_part = xv[:, :St]
                     x = torch.cat([t_part, start_route(xv[:, St:].contiguous().view(-1, D), g).view(B, -1, D)], dim=1).reshape(-1, D)
-                if ck and bi == s0 and save and nd + s0 + n - 1 >= stop:
-                    ctx.ck_s[s0] = x
-                ctx.env_s[bi] = rt.env
-                x, sv = self._single_fwd(bi, x, rt.env, save and not ck and g >= stop)
-                if sv is not None:
-                    ctx.sgl[bi] = sv
+                if ck and g == s0 and save and s0 + n - 1 >= stop:
+                    ctx.ck[s0] = x
+                ctx.envs[g] = rt.env
+                x, ctx.blocks[g] = self._single_fwd(g - nd, x, rt.env, save and not ck and g >= stop)
                 if ls is not None:
                     ls.tap(g, rows_of(x, St, Si, B, S))
                 if ends(g):
@@ -908,7 +907,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             del U_p
         if lm is not None:
             U_m = ops.gemm(dhpre, lm.B_blk_T)
-            dn_mlp = ops.gemm(dhpre, blk.proj_mlp.wT, a2=U_m, b2=lm.A_cat_T, k2_real=lm.k2_real)
+            dn_mlp = ops.gemm(dhpre, blk.proj_mlp.wT, **_ext_bwd(lm, U_m))
             lm.grads(sv.n, sv.T_m, dhpre, U_m, self.accumulate_lora_grads, self.grad_sync)
             del U_m
         else:
@@ -988,16 +987,14 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT), dict(a=dh_t, w=blk.ffc1.wT)])
         else:
             # dx = dy W + (dy sB) A as a K-extension of the dgrad launch (U = dy sB first); then the rank-space adapter gradients dB = s dy^T T, dA = U^T x
-            back = lambda lg, dy: ops.gemm(dy, lg.B_blk_T) if lg is not None else None
-            ext = lambda lg, U_: dict(a2=U_, b2=lg.A_cat_T, k2_real=lg.k2_real) if lg is not None else {}
-            U_f2, U_c2 = back(blk.ff2.lora, g_i), back(blk.ffc2.lora, g_t)
-            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img, **ext(blk.ff2.lora, U_f2)),
-                                           dict(a=g_t, w=blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt, **ext(blk.ffc2.lora, U_c2))])
+            U_f2, U_c2 = lora_up(blk.ff2, g_i), lora_up(blk.ffc2, g_t)
+            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=blk.ff2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img, **_ext_bwd(blk.ff2.lora, U_f2)),
+                                           dict(a=g_t, w=blk.ffc2.wT, epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt, **_ext_bwd(blk.ffc2.lora, U_c2))])
             for (lg, x_in, T_, dy, U_) in ((blk.ff2.lora, ff.h_i, ff.T_f2, g_i, U_f2), (blk.ffc2.lora, ff.h_t, ff.T_c2, g_t, U_c2)):
                 if lg is not None:
                     lg.grads(x_in, T_, dy, U_, self.accumulate_lora_grads, self.grad_sync)
-            U_f1, U_c1 = back(blk.ff1.lora, dh_i), back(blk.ffc1.lora, dh_t)
-            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT, **ext(blk.ff1.lora, U_f1)), dict(a=dh_t, w=blk.ffc1.wT, **ext(blk.ffc1.lora, U_c1))])
+            U_f1, U_c1 = lora_up(blk.ff1, dh_i), lora_up(blk.ffc1, dh_t)
+            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=blk.ff1.wT, **_ext_bwd(blk.ff1.lora, U_f1)), dict(a=dh_t, w=blk.ffc1.wT, **_ext_bwd(blk.ffc1.lora, U_c1))])
             for (lg, x_in, T_, dy, U_) in ((blk.ff1.lora, ff.n2_i, ff.T_f1, dh_i, U_f1), (blk.ffc1.lora, ff.n2_t, ff.T_c1, dh_t, U_c1)):
                 if lg is not None:
                     lg.grads(x_in, T_, dy, U_, self.accumulate_lora_grads, self.grad_sync)
@@ -1013,12 +1010,9 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             ops.colsum_prod(dx1_t, dmt[:, 2 * D:3 * D], b=sv.ya_t, rows_per_batch=St)
         # attention output projections: dO rows of both streams (+ adapter grads)
         dO = torch.empty(B * S, D, dtype=BF16, device=dev)
-        U_i = ops.gemm(dx1g_i, blk.to_out.lora.B_blk_T) if blk.to_out.lora is not None else None
-        U_t = ops.gemm(dx1g_t, blk.to_add_out.lora.B_blk_T) if blk.to_add_out.lora is not None else None
-        kw_i = dict(a2=U_i, b2=blk.to_out.lora.A_cat_T, k2_real=blk.to_out.lora.k2_real) if U_i is not None else {}
-        kw_t = dict(a2=U_t, b2=blk.to_add_out.lora.A_cat_T, k2_real=blk.to_add_out.lora.k2_real) if U_t is not None else {}
-        ops.gemm_grouped(problems(B, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, St, Si, B, S), **kw_i))
-                         + problems(B, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, 0, St, B, S), **kw_t)))
+        U_i, U_t = lora_up(blk.to_out, dx1g_i), lora_up(blk.to_add_out, dx1g_t)
+        ops.gemm_grouped(problems(B, Si, dict(a=dx1g_i, w=blk.to_out.wT, out=rows_of(dO, St, Si, B, S), **_ext_bwd(blk.to_out.lora, U_i)))
+                         + problems(B, St, dict(a=dx1g_t, w=blk.to_add_out.wT, out=rows_of(dO, 0, St, B, S), **_ext_bwd(blk.to_add_out.lora, U_t))))
         for (lin, U, T_, dxg, lo, rows) in ((blk.to_out, U_i, sv.T_o, dx1g_i, St, Si), (blk.to_add_out, U_t, sv.T_ao, dx1g_t, 0, St)):
             if lin.lora is not None:       # dA = U^T O over this stream's rows of the joint attention output, read in place
                 lin.lora.grads(compact(rows_of(sv.O, lo, rows, B, S), B, rows), T_, dxg, U, self.accumulate_lora_grads, self.grad_sync)
@@ -1034,15 +1028,13 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             streams = [s_ for s_ in streams if s_[1].lora is not None]   # frozen embedders: only adapter grads remain to compute
         probs, Us, dns = [], {}, []
         for (name, lin, dq, n_in, T_, rows) in streams:
-            kw = {}
             if lin.lora is not None:
                 Us[name] = torch.empty(B * rows, lin.lora.B_blk_T.shape[0], dtype=BF16, device=dev)
                 for pr in problems(B, rows, dict(a=dq, w=lin.lora.B_blk_T, out=Us[name])):
                     ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
-                kw = dict(a2=Us[name], b2=lin.lora.A_cat_T, k2_real=lin.lora.k2_real)
             if not last:
                 dns.append(torch.empty(B * rows, D, dtype=BF16, device=dev))
-                probs += problems(B, rows, dict(a=dq, w=lin.wT, out=dns[-1], **kw))
+                probs += problems(B, rows, dict(a=dq, w=lin.wT, out=dns[-1], **_ext_bwd(lin.lora, Us.get(name))))
         if probs:
             ops.gemm_grouped(probs)
         for (name, lin, dq, n_in, T_, rows) in streams:
@@ -1055,6 +1047,76 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_img, _ = ops.ln_modulate_bwd(dns[0], sv.img, mi[:, D:2 * D], rpi, dres=dx1_i)
         d_txt, _ = ops.ln_modulate_bwd(dns[1], sv.txt, mt[:, D:2 * D], St, dres=dx1_t)
         return d_img, d_txt
+
+    def _recompute_segment(self, ctx, g: int):
+        """backward reached block `g` of a checkpointed segment: re-run the segment's forward from its kept input (same kernels, same order: the activations are
+        bit-identical to the ones a plain forward keeps).  In a segment that straddles the stop block the blocks below it are re-run (their outputs feed the ones
+        above) but keep nothing — the backward returns at `ctx.stop`."""
+        nd = len(self.double)
+        s0, n = next((a, c) for (a, c, ck) in ctx.segs if ck and a <= g < a + c)
+        state = ctx.ck.pop(s0)                       # (img, txt) of a double-stack segment, the joint x of a single-stack one
+        for bi in range(s0, s0 + n):
+            if bi < nd:
+                *state, _, ctx.blocks[bi] = self._double_fwd(bi, *state, ctx.envs[bi], bi >= ctx.stop)
+            else:
+                state, ctx.blocks[bi] = self._single_fwd(bi - nd, state, ctx.envs[bi], bi >= ctx.stop)
+
+    @staticmethod
+    def _split_joint(dx, env):
+        """the joint gradient [txt || img] as the two stream-major ones [d_img, d_txt]"""
+        dxv = dx.view(env.B, env.S, -1)
+        return [dxv[:, env.St:].reshape(env.B * env.Si, -1), dxv[:, :env.St].reshape(env.B * env.St, -1)]
+
+    def _walk_blocks_bwd(self, ctx, grads, dsim, taps_kw, single_bwd, double_bwd):
+        """the backward walk over both stacks, last block first, down to `ctx.stop` (see sd3/transformer.py::_walk_blocks_bwd).  `grads` holds the gradient in one
+        of two forms: joint [dx, dxg] (rows [txt || img]; dxg = dx pre-gated for the next single block, or None) above a single block — the form it has on
+        entry — and stream-major [d_img, d_txt] above a double block; on return it is the gradient below block 0.  A list, and the block's activations in the
+        one-element list `acts`, so that no frame here keeps either alive once the callee has taken it.  Per block: recompute its checkpointed segment when its
+        activations are gone; enter / leave a TREAD route; LayerSync (dsim: the upstream gradient of the similarity, taps_kw: (accumulate, sync)) adds into the
+        image rows at the student block's output; then `single_bwd(li, acts, env, grads) -> (dx, dxg, d_txt, d_img)` / `double_bwd(li, acts, env, grads) ->
+        (d_img, d_txt)` do the block's own work, li counting within the stack."""
+        env, D, nd = ctx.env, self.D, len(self.double)
+        B, St = env.B, env.St
+        ls = getattr(ctx, "ls", None)
+        joint, d_full = True, None
+
+        def img_rows():          # the image stream's rows of the gradient [B, rows, D], in place (rows: the kept tokens inside a route)
+            return grads[0].view(B, -1, D)[:, St:] if joint else grads[0].view(B, -1, D)
+
+        def put_img_rows(t):     # ... replaced by t [B, rows', D]; the joint form is rebuilt around its text rows, and its pre-gated copy is gone
+            grads[:] = [torch.cat([grads[0].view(B, -1, D)[:, :St], t], dim=1).reshape(-1, D), None] if joint else [t.reshape(-1, D), grads[1]]
+
+        for g in range(nd + len(self.single) - 1, -1, -1):
+            if ctx.blocks[g] is None:
+                self._recompute_segment(ctx, g)
+            if joint and g < nd:          # the single-to-double boundary, unless single block 0 already handed the gradient back stream-major
+                grads[:], joint = self._split_joint(grads[0], env), False
+            # TREAD: the backward enters a route at its END block (the routed blocks see only the kept tokens' gradient rows; the skipped tokens' gradient stays in
+            # d_full) and leaves it at its START block (the kept rows go back into d_full: the gradient of the full stream at the route's start)
+            if g in ctx.route_end:
+                d_full = img_rows().contiguous()
+                put_img_rows(ops.gather_rows(d_full, ctx.route_end[g].keep_i32()))
+            if ls is not None and g == ls.student:
+                ls.backward(dsim, img_rows(), *taps_kw)
+                if joint:
+                    grads[1] = None       # the pre-gated copy of dx is stale: _single_bwd / the block entry point gate the new dx themselves
+            acts = [ctx.blocks[g]]
+            ctx.blocks[g] = None
+            if g < nd:
+                grads[:] = double_bwd(g, acts, ctx.envs[g], grads)
+            else:
+                out = single_bwd(g - nd, acts, ctx.envs[g], grads)
+                joint = out[0] is not None
+                grads[:] = out[:2] if joint else (out[3], out[2])
+                del out
+            if g == ctx.stop and g > 0:          # nothing below the first block that carries an adapter is differentiated
+                ctx.blocks, ctx.ck = [], {}
+                return
+            # (block 0 of a LoRA run returns no input gradients — the embedders are frozen: then there is nothing to scatter)
+            if g in ctx.route_start and grads[0] is not None:
+                ops.scatter_rows(img_rows().contiguous(), ctx.route_start[g].keep_i32(), d_full)
+                put_img_rows(d_full)
+                d_full = None
 
     def _engine_backward(self, ctx, dout, dsim=None):
         """hand-written backward for frozen-base (LoRA) training: dX chain + rank-space adapter gradients.  Checkpointed segments are re-run from
@@ -1079,76 +1141,14 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             ops.ln_modulate_bwd(dn[b * Si:(b + 1) * Si], ctx.x_final[b * S + St:(b + 1) * S], mo[b:b + 1, :D], Si, out=dx[b * S + St:(b + 1) * S])
         del dn
         ctx.x_final = None
-        # ---- single blocks, reversed ----
-        # TREAD: the backward enters a route at its END block (the routed blocks see only the kept tokens' gradient rows; the skipped tokens' gradient stays in
-        # d_full) and leaves it at its START block (the kept rows go back into d_full: the gradient of the full stream at the route's start)
-        nd = len(self.double)
-        stop = getattr(self, "_bwd_stop", 0)          # global index of the first block with an adapter (add_lora_adapter)
-        dxg = d_txt = d_img = d_full = None
-        keep_of = lambda info: info.keep_i32()
-        ls = getattr(ctx, "ls", None)
-        for (s0, n, ck) in reversed(ctx.segs_s):
-            if ck:
-                # a segment that straddles the stop block: blocks below it are re-run (their outputs feed the ones above) but keep nothing — the backward returns at `stop`
-                xr = ctx.ck_s.pop(s0)
-                for bi in range(s0, s0 + n):
-                    xr, sv = self._single_fwd(bi, xr, ctx.env_s[bi], nd + bi >= stop)
-                    if nd + bi >= stop:
-                        ctx.sgl[bi] = sv
-                del xr
-            for li in range(s0 + n - 1, s0 - 1, -1):
-                g, e = nd + li, ctx.env_s[li]
-                if g in ctx.route_end:
-                    dxv = dx.view(B, S, D)
-                    d_full = dxv[:, St:].contiguous()
-                    dx = torch.cat([dxv[:, :St], ops.gather_rows(d_full, keep_of(ctx.route_end[g]))], dim=1).reshape(-1, D)
-                    dxg = None
-                if ls is not None and g == ls.student:
-                    ls.inject(rows_of(dx, St, Si, B, S), dsim)
-                    dxg = None                               # the pre-gated copy of dx is stale: _single_bwd / the block entry point gate the new dx themselves
-                dx, dxg, d_txt, d_img = self._single_bwd(li, ctx.sgl.pop(li), dx, dxg, e)
-                if g == stop and g > 0:
-                    ctx.sgl.clear(); ctx.dbl.clear(); ctx.ck_s.clear(); ctx.ck_d.clear()
-                    return None
-                if g in ctx.route_start:
-                    if dx is None:                               # single block 0 under double blocks: its input gradient came back stream-major
-                        ops.scatter_rows(d_img.view(B, e.Si, D), keep_of(ctx.route_start[g]), d_full)
-                        d_img, d_full = d_full.view(-1, D), None
-                    else:
-                        dxv = dx.view(B, e.S, D)
-                        ops.scatter_rows(dxv[:, St:].contiguous(), keep_of(ctx.route_start[g]), d_full)
-                        dx = torch.cat([dxv[:, :St], d_full], dim=1).reshape(B * S, D)
-                        dxg, d_full = None, None
-        # ---- split the joint gradient (only when there was no single block to do it) ----
-        if not self.single:
-            d_txt = dx.view(B, S, D)[:, :St].reshape(B * St, D); d_img = dx.view(B, S, D)[:, St:].reshape(B * Si, D)
-        # ---- double blocks, reversed ----
-        for (s0, n, ck) in reversed(ctx.segs_d):
-            if ck:
-                ir, tr = ctx.ck_d.pop(s0)
-                for bi in range(s0, s0 + n):
-                    ir, tr, _, sv = self._double_fwd(bi, ir, tr, ctx.env_d[bi], bi >= stop)
-                    if bi >= stop:
-                        ctx.dbl[bi] = sv
-                del ir, tr
-            for li in range(s0 + n - 1, s0 - 1, -1):
-                e = ctx.env_d[li]
-                if li in ctx.route_end:
-                    d_full = d_img.view(B, Si, D)
-                    d_img = ops.gather_rows(d_full, keep_of(ctx.route_end[li])).view(-1, D)
-                if ls is not None and li == ls.student:      # (the last double block: single block 0 handed its input gradient back stream-major)
-                    ls.inject(d_img.view(B, Si, D), dsim)
-                d_img, d_txt = self._double_bwd(li, ctx.dbl.pop(li), d_img, d_txt, e)
-                if li == stop and li > 0:
-                    ctx.dbl.clear(); ctx.ck_d.clear()
-                    return None
-                if li in ctx.route_start and d_img is not None:
-                    ops.scatter_rows(d_img.view(B, e.Si, D), keep_of(ctx.route_start[li]), d_full)
-                    d_img, d_full = d_full.reshape(-1, D), None
+        grads = [dx, None]
+        del dx
+        self._walk_blocks_bwd(ctx, grads, dsim, (self.accumulate_lora_grads, self.grad_sync),
+                              lambda li, acts, e, g: self._single_bwd(li, acts.pop(), *g, e), lambda li, acts, e, g: self._double_bwd(li, acts.pop(), *g, e))
         lx = self.l_x.lora
         if lx is not None:          # 'all+ffs+embedder': dy of x_embedder = the image stream's gradient at block 0's input; its own input (the packed latents) needs none
-            if d_img is None:       # no double block: the image rows of the joint gradient at single block 0's input
-                d_img = dx.view(B, S, D)[:, St:].reshape(B * Si, D)
+            # (no double block: the image rows of the joint gradient at single block 0's input)
+            d_img = grads[0] if self.double else grads[0].view(B, S, D)[:, St:].reshape(B * Si, D)
             U_x = ops.gemm(d_img, lx.B_blk_T)
             lx.grads(ctx.x2d, ctx.T_x, d_img, U_x, self.accumulate_lora_grads, self.grad_sync)
         ml = self.mod_lora
@@ -1306,39 +1306,26 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             sync.ready(self._head_arena_lo, self.grad_arena.numel())        # proj_out gradients are final
         # the fused modulation matrix (3.2 B of Flux.1-dev's 11.9 B parameters, 6.5 GB of gradient) gets its gradient rows block by block (FullGrads.mod_rows_grad)
         fb.mod_rows_grad(self.mod_off_out)                   # norm_out's (scale, shift) rows: final since mod_grads above
-        ls, nd = getattr(ctx, "ls", None), len(self.double)         # LayerSync: dsim * G enters at the student block's output (see _engine_backward)
-        # ---- single blocks, reversed ----
-        for (s0, n, ck) in reversed(ctx.segs_s):
-            if ck:
-                xr = ctx.ck_s.pop(s0)
-                for bi in range(s0, s0 + n):
-                    xr, ctx.sgl[bi] = self._single_fwd(bi, xr, ctx.env_s[bi], True)
-                del xr
-            for li in range(s0 + n - 1, s0 - 1, -1):
-                if ls is not None and nd + li == ls.student:
-                    ls.inject(rows_of(dx, St, Si, B, S), dsim)
-                dx = self._single_bwd_full(li, ctx.sgl.pop(li), dx, ctx.env_s[li], fb)
-                if sync is not None:
-                    sync.ready(self.single[li].arena_lo, self.single[li].arena_hi)
-                fb.mod_rows_grad(self.single[li].mod_off)
-        # ---- split the joint gradient [txt || img] ----
-        dxv = dx.view(B, S, D)
-        d_txt, d_img = dxv[:, :St].reshape(B * St, D), dxv[:, St:].reshape(B * Si, D)
-        del dx, dxv
-        # ---- double blocks, reversed ----
-        for (s0, n, ck) in reversed(ctx.segs_d):
-            if ck:
-                ir, tr = ctx.ck_d.pop(s0)
-                for bi in range(s0, s0 + n):
-                    ir, tr, _, ctx.dbl[bi] = self._double_fwd(bi, ir, tr, ctx.env_d[bi], True)
-                del ir, tr
-            for li in range(s0 + n - 1, s0 - 1, -1):
-                if ls is not None and li == ls.student:
-                    ls.inject(d_img.view(B, Si, D), dsim)
-                d_img, d_txt = self._double_bwd_full(li, ctx.dbl.pop(li), d_img, d_txt, ctx.env_d[li], fb)
-                if sync is not None:
-                    sync.ready(self.double[li].arena_lo, self.double[li].arena_hi)
-                fb.mod_rows_grad(self.double[li].mod_off)
+        def handed_over(blk):          # the block's parameter gradients are final: its arena slice can go out, and so can its rows of the modulation matrix
+            if sync is not None:
+                sync.ready(blk.arena_lo, blk.arena_hi)
+            fb.mod_rows_grad(blk.mod_off)
+
+        def single_bwd(li, acts, e, g):
+            dx_in = self._single_bwd_full(li, acts.pop(), g.pop(0), e, fb)
+            handed_over(self.single[li])
+            return dx_in, None, None, None
+
+        def double_bwd(li, acts, e, g):
+            d_in = self._double_bwd_full(li, acts.pop(), g.pop(0), g.pop(0), e, fb)
+            handed_over(self.double[li])
+            return d_in
+
+        grads = [dx, None]
+        del dx
+        self._walk_blocks_bwd(ctx, grads, dsim, (False, sync), single_bwd, double_bwd)
+        d_img, d_txt = grads if self.double else self._split_joint(grads[0], env)
+        del grads
         # ---- embedders ----
         em = ctx.emb
         fb.wgrad(self.l_x, d_img, em.x2d)
@@ -1435,25 +1422,7 @@ class _FluxFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout, dsim=None):
-        model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout, dsim)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_scale_from_sync = model.grad_sync.finish()   # all slices reduced (SUM); optimizer folds 1/world
-        # hand autograd a private flat copy (one 4 B/param copy) so .grad never aliases the arena the next backward overwrites;
-        # the per-parameter grads stay views of ONE contiguous buffer, which the fused optimizer / RCCL all-reduce exploit.
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.lora_grad_flat)
-        model._last_grad_flat = gflat
-        grads, off = [], 0
-        for p in model._lora_params:
-            n = p.numel()
-            grads.append(gflat[off:off + n].view_as(p))
-            off += n
-        return (None,) * 9 + tuple(grads)
-
+        return (None,) * 9 + node_backward(fctx, False, dout, dsim)
 
 class _FluxFullFn(torch.autograd.Function):
     """full-rank training: one autograd node; backward fills the bf16 gradient arena and hands autograd views of a private copy"""
@@ -1467,15 +1436,4 @@ class _FluxFullFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout, dsim=None):
-        model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout, dsim)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.grad_arena)
-        model._last_grad_flat = gflat
-        grads = [gflat[off:off + n].view_as(p) for (off, n), p in zip(model._full_offsets, model._full_params)]
-        return (None,) * 9 + tuple(grads)
+        return (None,) * 9 + node_backward(fctx, True, dout, dsim)

@@ -26,7 +26,7 @@ import torch.nn as nn
 from .. import ops
 from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
                       attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
-                      lora_fwd_kw, lora_grads, lora_up, nextlat_index, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
+                      lora_fwd_kw, lora_grads, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -1404,23 +1404,7 @@ class _SD3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout, *rest):
-        model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout, *rest)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_scale_from_sync = model.grad_sync.finish()
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.lora_grad_flat)
-        model._last_grad_flat = gflat
-        grads, off = [], 0
-        for p in model._lora_params:
-            n = p.numel()
-            grads.append(gflat[off:off + n].view_as(p))
-            off += n
-        return (None,) * 5 + tuple(grads)
-
+        return (None,) * 5 + node_backward(fctx, False, dout, *rest)
 
 class _SD3FullFn(torch.autograd.Function):
     """full fine-tune: one autograd node; backward fills the bf16 gradient arena and hands autograd views of a private copy"""
@@ -1433,16 +1417,5 @@ class _SD3FullFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout, *rest):
-        model = fctx.model
-        model._pick_grad_arena()
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward_full(fctx.ectx, dout, *rest)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.grad_arena)
-        model._last_grad_flat = gflat
-        grads = [gflat[off:off + n].view_as(p) for (off, n), p in zip(model._full_offsets, model._full_params)]
-        return (None,) * 5 + tuple(grads)
+        fctx.model._pick_grad_arena()
+        return (None,) * 5 + node_backward(fctx, True, dout, *rest)
