@@ -902,7 +902,7 @@ class FullGrads:
         self.dmod = torch.zeros(B, model.mod_total, dtype=F32, device=dev)
         self.st_p = self._pad_batch(st)
         self._tmp_b = {}
-        self.mw_lo = (model.mod_w.data_ptr() - model.arena.data_ptr()) // 2
+        self.mw_lo = (model.mod_w.data_ptr() - model.arena.data_ptr()) // model.arena.element_size()
         self.mw_hi = self.mw_lo + model.mod_total * model.D
         self.mod_in_front = 0 <= self.mw_lo and self.mw_hi <= front_hi
         self.mod_rows_lo = model.mod_total                # rows [mod_rows_lo, mod_total) of dW_mod are written (and handed over)

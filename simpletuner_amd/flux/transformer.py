@@ -1182,7 +1182,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         base = self.arena.data_ptr()
 
         def gview(t):
-            off = (t.data_ptr() - base) // 2
+            off = (t.data_ptr() - base) // t.element_size()
             return self.grad_arena[off:off + t.numel()].view(t.shape)
 
         for l in self._all_linears():
@@ -1197,7 +1197,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         for p in ps:
             p.requires_grad_(True)
         self._full_params = ps
-        self._full_offsets = [((p.data_ptr() - base) // 2, p.numel()) for p in ps]
+        self._full_offsets = [((p.data_ptr() - base) // p.element_size(), p.numel()) for p in ps]
         self.prepare_for_training()
         return ps
 

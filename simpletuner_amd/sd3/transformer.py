@@ -1252,7 +1252,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self._grad_views = ([], [])          # per arena: (owner, attribute, view) of every gradient view the backward writes through
 
         def gview(owner, attr, t):
-            off = (t.data_ptr() - base) // 2
+            off = (t.data_ptr() - base) // t.element_size()
             for k in (0, 1):
                 self._grad_views[k].append((owner, attr, None if t is None else self._grad_arenas[k][off:off + t.numel()].view(t.shape)))
             setattr(owner, attr, self._grad_views[0][-1][2])
@@ -1271,7 +1271,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if self._ig_arena is None:
                 raise RuntimeError("Internal Guidance under a full fine-tune: construct the model with internal_guidance_block_index (the head lives inside the base "
                                    "parameter arena, which is laid out once)")
-            lo = (self._ig_arena[0].data_ptr() - base) // 2
+            lo = (self._ig_arena[0].data_ptr() - base) // self.arena.element_size()
             self._ig = InternalGuidanceHead(self._ig_block, self.D, self._ig_arena, (None,) * 4, lo, self.arena.numel(), self.device_)
             for attr, t in zip(("g_gamma", "g_beta", "g_W", "g_b"), self._ig_arena):
                 gview(self._ig, attr, t)
@@ -1279,7 +1279,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if self._nl_arena is None:
                 raise RuntimeError("NextLat under a full fine-tune: construct the model with nextlat_block_index (the predictor lives inside the base parameter arena, "
                                    "which is laid out once)")
-            lo = (self._nl_arena[0].data_ptr() - base) // 2
+            lo = (self._nl_arena[0].data_ptr() - base) // self.arena.element_size()
             self._nl = NextLatHead(self._nl_block, self.D, self._nl_arena, (None,) * 6, lo, self.arena.numel(), self.device_)
             for attr, t in zip(("g_gamma", "g_beta", "g_W_up", "g_b_up", "g_W_down", "g_b_down"), self._nl_arena):
                 gview(self._nl, attr, t)
@@ -1287,7 +1287,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for p in ps:
             p.requires_grad_(True)
         self._full_params = ps
-        self._full_offsets = [((p.data_ptr() - base) // 2, p.numel()) for p in ps]
+        self._full_offsets = [((p.data_ptr() - base) // p.element_size(), p.numel()) for p in ps]
         self.prepare_for_training()
         for l in (self.l_t2, self.l_p2):
             l.wT = l.w.t().contiguous()

@@ -356,7 +356,7 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
             p.requires_grad_(True)
         self._full_params = ps
         base = self.arena.data_ptr()
-        self._full_offsets = [((p.data_ptr() - base) // 2, p.numel()) for p in ps]
+        self._full_offsets = [((p.data_ptr() - base) // p.element_size(), p.numel()) for p in ps]
         self._alloc_transposed()
         return ps
 
