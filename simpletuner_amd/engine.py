@@ -1,6 +1,7 @@
 """Host code the engines share (flux/, sd3/, pixart/ transformer.py, unet/unet.py): nothing here knows a model family.
 
   * `attach` / `frozen` / `LoraGroup`: parameters under dotted checkpoint names, the adapters of projections that share an input;
+  * `AdapterArena` / `lora_pairs`: the ONE fp32 arena of everything trained beside the base (two-phase: plan, build), the A / B pairs of a plan laid out and drawn;
   * `lokr_factorization` / `LokrGroup`: the LyCORIS LoKr adapters of such a group (the Kronecker delta folded into the GEMM operands, the structured gradients);
   * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
   * `LoraDora`: a group's DoRA state (magnitudes, the row scale, the folded GEMM operands);
@@ -17,6 +18,7 @@
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -47,6 +49,62 @@ def attach(root: nn.Module, dotted: str, param: nn.Parameter):
 
 def frozen(t: torch.Tensor) -> nn.Parameter:
     return nn.Parameter(t, requires_grad=False)
+
+
+class AdapterArena:
+    """The lay-out of everything a model trains beside its frozen base: ONE fp32 arena `model.lora_flat` and its twin `model.lora_grad_flat` (one optimizer launch, one
+    exchange over slices of it).  `add` plans a tensor and returns its slot, `lo` / `hi` known at once; `build` allocates both arenas (the total rounded up to 8),
+    fills every slot's `p` / `g` (parameter / gradient view), attaches one nn.Parameter per slot in `add` order and publishes `model._lora_params` and
+    `model._lora_offsets` [(lo, n)] — what the node's backward cuts the flat gradient by."""
+
+    def __init__(self, model, dev):
+        self.model, self.dev, self.slots, self.end = model, dev, [], 0
+
+    def add(self, name: str, shape, align: int = 1):
+        lo = (self.end + align - 1) // align * align
+        self.end = lo + math.prod(shape)
+        self.slots.append(SimpleNamespace(name=name, shape=tuple(shape), lo=lo, hi=self.end, p=None, g=None))
+        return self.slots[-1]
+
+    def build(self, seed: int) -> torch.Generator:
+        """-> the device generator the initial values are drawn from, seeded"""
+        m, total = self.model, (self.end + 7) // 8 * 8
+        m.lora_flat, m.lora_grad_flat = torch.zeros(total, dtype=F32, device=self.dev), torch.zeros(total, dtype=F32, device=self.dev)
+        m._lora_params, m._lora_offsets = [], [(s.lo, s.hi - s.lo) for s in self.slots]
+        for s in self.slots:
+            par = nn.Parameter(m.lora_flat[s.lo:s.hi].view(s.shape))
+            attach(m, s.name, par)          # (replaces a frozen base-arena view of the same name, when there is one: the heads)
+            s.p, s.g = par.data, m.lora_grad_flat[s.lo:s.hi].view(s.shape)
+            m._lora_params.append(par)
+        return torch.Generator(device=self.dev).manual_seed(seed)
+
+
+def lora_pairs(arena: AdapterArena, plan, rank: int, init_b_std: float, fan_in: Optional[int] = None, pad=None, divide: bool = False):
+    """Plans lora_A [rank, K] / lora_B [N, rank] (peft names) of every (group, name, N, K) of `plan`, pair by pair, and sets the groups' `flat_lo` / `flat_hi`.
+    Returns `draw(gen)` for after `arena.build()`: A ~ U(-1, 1) / sqrt(fan_in or K) (kaiming_uniform(a = sqrt 5), peft's default for lora_A), then B ~ N(0, init_b_std)
+    if init_b_std > 0 — both drawn at the full shape — and the groups' A / B / gA / gB lists.  pad: a boolean mask of a padded axis' lanes, zeroed in an A whose K
+    and a B whose N is that axis.  divide: the draw is divided by sqrt(K), not multiplied by its reciprocal (the last bit differs)."""
+    pairs = []
+    for (g, name, N, K) in plan:
+        sa, sb = arena.add(name + ".lora_A.default.weight", (rank, K)), arena.add(name + ".lora_B.default.weight", (N, rank))
+        if not g.flat_hi:
+            g.flat_lo = sa.lo
+        g.flat_hi = sb.hi
+        pairs.append((g, sa, sb))
+
+    def draw(gen):
+        for g, sa, sb in pairs:
+            (N, _), (_, K) = sb.shape, sa.shape
+            u = torch.rand(rank, K, generator=gen, device=arena.dev) * 2 - 1
+            sa.p.copy_(u / math.sqrt(K) if divide else u * (1.0 / math.sqrt(fan_in or K)))
+            if init_b_std > 0:
+                sb.p.copy_(torch.randn(N, rank, generator=gen, device=arena.dev) * init_b_std)
+            if pad is not None and K == pad.numel():
+                sa.p[:, pad] = 0
+            if pad is not None and N == pad.numel():
+                sb.p[pad] = 0
+            g.A.append(sa.p); g.B.append(sb.p); g.gA.append(sa.g); g.gB.append(sb.g)
+    return draw
 
 
 class LoraDropout:
@@ -863,29 +921,32 @@ def mod_grads(D: int, dn, x_in, rows: int, k_shift: int, k_scale: int, dm, xhat=
 
 
 # ------------------------------------------------------------------------------------------------
-# the backward of the one autograd node per network (flux/transformer.py::_FluxFn / _FluxFullFn, sd3/transformer.py::_SD3Fn / _SD3FullFn)
+# the backward of the one autograd node per network (_FluxFn / _FluxFullFn, _SD3Fn / _SD3FullFn, _PixArtLoraFn / _CtrlFn, _UNetFn)
 # ------------------------------------------------------------------------------------------------
-def node_backward(fctx, full: bool, *d_outs):
+def node_backward(fctx, full: bool, *d_outs, run=None, whole: bool = False, covered: bool = False, cut=None):
     """Runs the model's hand-written backward on the node's kept context between the gradient exchange's begin / finish, then hands autograd a private flat
     copy (one copy per step) so that .grad never aliases the arena the next backward overwrites; the per-parameter gradients returned stay views of ONE
-    contiguous buffer, which the fused optimizer / RCCL all-reduce exploit.  full: the bf16 gradient arena and `_full_params`, else the adapters' fp32 one."""
+    contiguous buffer, which the fused optimizer / RCCL all-reduce exploit.  full: the bf16 gradient arena and `_full_params`, else the adapters' fp32 one.
+    run: what runs the backward on (context, *d_outs), the model's `_engine_backward[_full]` by default.  whole: the arena is handed to the exchange in one piece
+    after the backward (nothing reported itself ready).  covered: refuse an exchange that did not take every element.  cut: the (parameters, [(offset, n)]) the
+    flat gradient is cut by, else `_full_params` / `_lora_params` and their offsets."""
     model = fctx.model
-    if model.grad_sync is not None:
-        model.grad_sync.begin()
-    (model._engine_backward_full if full else model._engine_backward)(fctx.ectx, *d_outs)
+    sync = model.grad_sync
+    if sync is not None:
+        sync.begin()
+    (run or (model._engine_backward_full if full else model._engine_backward))(fctx.ectx, *d_outs)
     fctx.ectx = None
-    if model.grad_sync is not None:
-        model.grad_scale_from_sync = model.grad_sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world
+    arena = model.grad_arena if full else model.lora_grad_flat
+    if sync is not None:
+        if whole:
+            sync.ready(0, arena.numel())
+        model.grad_scale_from_sync = sync.finish()   # every slice reduced (SUM over replicas); the optimizer folds 1/world
+        if covered and (sent := sum(hi - lo for lo, hi in sync.launched_slices)) != arena.numel():
+            raise RuntimeError(f"gradient sync covered {sent} of {arena.numel()} elements: a parameter's gradient was never reported ready")
     from .training.grad_sync import hand_over_gradients
-    model._last_grad_flat = gflat = hand_over_gradients(model, model.grad_arena if full else model.lora_grad_flat)
-    if full:
-        return tuple(gflat[off:off + n].view_as(p) for (off, n), p in zip(model._full_offsets, model._full_params))
-    grads, off = [], 0
-    for p in model._lora_params:
-        n = p.numel()
-        grads.append(gflat[off:off + n].view_as(p))
-        off += n
-    return tuple(grads)
+    model._last_grad_flat = gflat = hand_over_gradients(model, arena)
+    params, offsets = cut or ((model._full_params, model._full_offsets) if full else (model._lora_params, model._lora_offsets))
+    return tuple(gflat[off:off + n].view_as(p) for (off, n), p in zip(offsets, params))
 
 
 # ------------------------------------------------------------------------------------------------

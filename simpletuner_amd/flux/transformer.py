@@ -29,7 +29,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ArenaModule, FullGrads, LayerSyncTap, LoraGroup, attach, compact, frozen, layersync_indices, lora_up, mod_grads, node_backward, pad64, problems, rows_of
+from ..engine import (AdapterArena, ArenaModule, FullGrads, LayerSyncTap, LoraGroup, compact, frozen, layersync_indices, lora_pairs, lora_up, mod_grads, node_backward, pad64,
+                      problems, rows_of)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_QK_NORM_ROPE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -295,29 +296,9 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         carries = [any(l.lora is not None for l in (b.qkv, b.add_qkv, b.to_out, b.to_add_out, b.ff1, b.ff2, b.ffc1, b.ffc2)) for b in self.double] \
             + [any(l.lora is not None for l in (b.qkv, b.proj_mlp, b.proj_out)) for b in self.single]
         self._bwd_stop = carries.index(True) if True in carries else 0
-        total = sum(rank * K + N * rank for (_, _, N, K) in plan)
-        total = (total + 7) // 8 * 8
-        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
-        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
-        gen = torch.Generator(device=dev).manual_seed(seed)
-        off = 0
-        self._lora_params = []
-        for (g, name, N, K) in plan:
-            if not g.A:
-                g.flat_lo = off
-            g.flat_hi = off + rank * K + N * rank
-            a = self.lora_flat[off:off + rank * K].view(rank, K); ga = self.lora_grad_flat[off:off + rank * K].view(rank, K)
-            off += rank * K
-            b = self.lora_flat[off:off + N * rank].view(N, rank); gb = self.lora_grad_flat[off:off + N * rank].view(N, rank)
-            off += N * rank
-            bound = 1.0 / math.sqrt(K)   # kaiming_uniform(a=sqrt(5)) on [r,K] (peft default for lora_A)
-            a.copy_((torch.rand(rank, K, generator=gen, device=dev) * 2 - 1) * bound)
-            if init_b_std > 0:
-                b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
-            pa, pb = nn.Parameter(a), nn.Parameter(b)
-            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
-            g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
-            self._lora_params += [pa, pb]
+        arena = AdapterArena(self, dev)
+        draw = lora_pairs(arena, plan, rank, init_b_std)
+        draw(arena.build(seed))
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import LoraGroup, attach, frozen, mod_grads, pad64, sincos_2d_hw
+from ..engine import AdapterArena, LoraGroup, attach, frozen, lora_pairs, mod_grads, node_backward, pad64, sincos_2d_hw
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -176,34 +176,10 @@ class PixArtTransformer2DModel(nn.Module):
                 self.lora_groups.append(g)
                 for (name, _, N) in g.targets:
                     plan.append((g, name, N, g.K))
-        total = (sum(rank * K + N * rank for (_, _, N, K) in plan) + 7) // 8 * 8
-        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
-        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
-        gen = torch.Generator(device=dev).manual_seed(seed)
-        off = 0
-        self._lora_params = []
-        pad_rows = torch.zeros(H, HP, dtype=torch.bool, device=dev); pad_rows[:, hd:] = True          # the pad lanes of a head-padded axis
-        pad_rows = pad_rows.reshape(-1)
-        for (g, name, N, K) in plan:
-            if not g.A:
-                g.flat_lo = off
-            a = self.lora_flat[off:off + rank * K].view(rank, K); ga = self.lora_grad_flat[off:off + rank * K].view(rank, K)
-            off += rank * K
-            b = self.lora_flat[off:off + N * rank].view(N, rank); gb = self.lora_grad_flat[off:off + N * rank].view(N, rank)
-            off += N * rank
-            g.flat_hi = off
-            k_true = D                                                           # kaiming_uniform(a=sqrt(5)) on the TRUE [r, in_features] (peft default for lora_A)
-            a.copy_((torch.rand(rank, K, generator=gen, device=dev) * 2 - 1) * (1.0 / math.sqrt(k_true)))
-            if K == Dp:
-                a[:, pad_rows] = 0
-            if init_b_std > 0:
-                b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
-                if N == Dp:
-                    b[pad_rows] = 0
-            pa, pb = nn.Parameter(a), nn.Parameter(b)
-            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
-            g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
-            self._lora_params += [pa, pb]
+        pad = torch.zeros(H, HP, dtype=torch.bool, device=dev); pad[:, hd:] = True          # the pad lanes of a head-padded axis
+        arena = AdapterArena(self, dev)
+        draw = lora_pairs(arena, plan, rank, init_b_std, fan_in=D, pad=pad.reshape(-1))          # the bound from the TRUE [r, in_features] (peft's default for lora_A)
+        draw(arena.build(seed))
         return self._lora_params
 
     def lora_state_dict(self) -> Dict[str, torch.Tensor]:
@@ -713,22 +689,7 @@ class _PixArtLoraFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout):
-        model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward_lora(fctx.ectx, dout)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_scale_from_sync = model.grad_sync.finish()
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.lora_grad_flat)
-        model._last_grad_flat = gflat
-        grads, off = [], 0
-        for p in model._lora_params:
-            n = p.numel()
-            grads.append(gflat[off:off + n].view_as(p))
-            off += n
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 6 + node_backward(fctx, False, dout, run=fctx.model._engine_backward_lora)
 
 
 class PixArtSigmaControlNetTransformerModel(CheckpointPlanMixin, nn.Module):
@@ -912,16 +873,5 @@ class _CtrlFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout):
-        model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        model._engine_backward(fctx.ectx, dout)
-        fctx.ectx = None
-        if model.grad_sync is not None:
-            model.grad_sync.ready(0, model.grad_arena.numel())
-            model.grad_scale_from_sync = model.grad_sync.finish()
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, model.grad_arena)
-        model._last_grad_flat = gflat
-        grads = [gflat[off:off + n].view_as(p) for (off, n), p in zip(model._offsets, model._params)]
-        return (None,) * 7 + tuple(grads)
+        model = fctx.model          # the bf16 adapter arena goes to the exchange in one piece after the backward
+        return (None,) * 7 + node_backward(fctx, True, dout, run=model._engine_backward, whole=True, cut=(model._params, model._offsets))

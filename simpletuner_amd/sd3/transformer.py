@@ -24,9 +24,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, NextLatTap,
-                      attach, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
-                      lora_fwd_kw, lora_grads, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, AdapterArena, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead,
+                      NextLatTap, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
+                      lora_fwd_kw, lora_grads, lora_pairs, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -309,79 +309,33 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                 group(blk.add_qkv, p, ["add_q_proj", "add_k_proj", "add_v_proj"], D)
                 if blk.to_add_out is not None:
                     group(blk.to_add_out, p, ["to_add_out"], D)
-        total = sum(rank * K + N * rank for (_, _, N, K) in plan)
-        dora_lo = total                           # DoRA: the magnitudes follow all A / B tensors (flat_view of parameters and of gradients stays one run), before the heads
-        if dora:
-            total += sum(N for (_, _, N, _) in plan)
-        ig_lo = total                             # Internal Guidance: the head's fp32 masters follow the adapters in the same arena (one run for the optimizer)
-        if self._ig_block is not None:
-            total += sum(math.prod(shp) for shp in internal_guidance_shapes(D))
-        if self._nl_block is not None:            # NextLat: the predictor's fp32 masters likewise, from a 16-byte boundary (its kernels move 8 elements per lane)
-            nl_lo = total = (total + 7) // 8 * 8
-            total += sum(math.prod(shp) for shp in nextlat_shapes(D))
-        total = (total + 7) // 8 * 8
-        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
-        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
-        gen = torch.Generator(device=dev).manual_seed(seed)
-        off = 0
-        self._lora_params = []
-        for (g, name, N, K) in plan:
-            if not g.A:
-                g.flat_lo = off
-            a = self.lora_flat[off:off + rank * K].view(rank, K); ga = self.lora_grad_flat[off:off + rank * K].view(rank, K)
-            off += rank * K
-            b = self.lora_flat[off:off + N * rank].view(N, rank); gb = self.lora_grad_flat[off:off + N * rank].view(N, rank)
-            off += N * rank
-            bound = 1.0 / math.sqrt(K)
-            a.copy_((torch.rand(rank, K, generator=gen, device=dev) * 2 - 1) * bound)
-            if init_b_std > 0:
-                b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
-            pa, pb = nn.Parameter(a), nn.Parameter(b)
-            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
-            g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
-            g.flat_hi = off
-            self._lora_params += [pa, pb]
-        if dora:
-            assert off == dora_lo
-            for g, lin in zip(self.lora_groups, group_lins):
-                g.enable_dora(lin, self.lora_flat[off:off + g.N_total], self.lora_grad_flat[off:off + g.N_total], off)
-                for (name, n_off, N) in g.targets:
-                    pm = nn.Parameter(self.lora_flat[off:off + N])
-                    attach(self, name + ".lora_magnitude_vector.default.weight", pm)
-                    self._lora_params.append(pm)
-                    off += N
-                g.pack()
-                g.fold(init=True)                    # m = ||W + s B A||_row of the fresh adapter (peft's DoraLinearLayer.update_layer): g = 1 at step 0
-        if self._ig_block is not None:
-            assert off == ig_lo
-            ps, gs = [], []
-            for nm, shp in zip(IG_NAMES, internal_guidance_shapes(D)):
-                n = math.prod(shp)
-                pr = nn.Parameter(self.lora_flat[off:off + n].view(shp))
-                attach(self, "internal_guidance_head." + nm, pr)          # (replaces the frozen arena view of the same name, when there is one)
-                ps.append(pr.data); gs.append(self.lora_grad_flat[off:off + n].view(shp))
-                self._lora_params.append(pr)
-                off += n
-            self._ig = InternalGuidanceHead(self._ig_block, D, ps, gs, ig_lo, off, dev)
+        arena = AdapterArena(self, dev)
+        draw = lora_pairs(arena, plan, rank, init_b_std)
+        # DoRA: the magnitudes follow all A / B tensors (flat_view of parameters and of gradients stays one run), before the heads
+        mags = [[arena.add(name + ".lora_magnitude_vector.default.weight", (N,)) for (name, _, N) in g.targets] for g in self.lora_groups] if dora else []
+        # Internal Guidance, then NextLat: the heads' fp32 masters follow the adapters in the same arena (one run for the optimizer), the predictor from a 16-byte
+        # boundary (its kernels move 8 elements per lane)
+        ig = [arena.add("internal_guidance_head." + nm, shp) for nm, shp in zip(IG_NAMES, internal_guidance_shapes(D))] if self._ig_block is not None else []
+        nl = [arena.add("nextlat_predictor." + nm, shp, align=1 if k else 8) for k, (nm, shp) in enumerate(zip(NEXTLAT_NAMES, nextlat_shapes(D)))] \
+            if self._nl_block is not None else []
+        gen = arena.build(seed)
+        draw(gen)
+        for g, lin, ms in zip(self.lora_groups, group_lins, mags):
+            lo, hi = ms[0].lo, ms[-1].hi
+            g.enable_dora(lin, self.lora_flat[lo:hi], self.lora_grad_flat[lo:hi], lo)
+            g.pack()
+            g.fold(init=True)                    # m = ||W + s B A||_row of the fresh adapter (peft's DoraLinearLayer.update_layer): g = 1 at step 0
+        if ig:
+            self._ig = InternalGuidanceHead(self._ig_block, D, [s.p for s in ig], [s.g for s in ig], ig[0].lo, ig[-1].hi, dev)
             self._ig.init_reference()
             if self._ig_arena is not None:
-                for dst, src in zip(ps, self._ig_arena):
-                    dst.copy_(src)                   # a head that came with the loaded weights
-        if self._nl_block is not None:
-            assert off <= nl_lo
-            off = nl_lo
-            ps, gs = [], []
-            for nm, shp in zip(NEXTLAT_NAMES, nextlat_shapes(D)):
-                n = math.prod(shp)
-                pr = nn.Parameter(self.lora_flat[off:off + n].view(shp))
-                attach(self, "nextlat_predictor." + nm, pr)          # (replaces the frozen arena view of the same name, when there is one)
-                ps.append(pr.data); gs.append(self.lora_grad_flat[off:off + n].view(shp))
-                self._lora_params.append(pr)
-                off += n
-            self._nl = NextLatHead(self._nl_block, D, ps, gs, nl_lo, off, dev)
+                for s, src in zip(ig, self._ig_arena):
+                    s.p.copy_(src)               # a head that came with the loaded weights
+        if nl:
+            self._nl = NextLatHead(self._nl_block, D, [s.p for s in nl], [s.g for s in nl], nl[0].lo, nl[-1].hi, dev)
             if self._nl_arena is not None and self._nl_loaded:
-                for dst, src in zip(ps, self._nl_arena):
-                    dst.copy_(src)                   # a predictor that came with the loaded weights
+                for s, src in zip(nl, self._nl_arena):
+                    s.p.copy_(src)               # a predictor that came with the loaded weights
             else:
                 self._nl.init_reference(gen)         # the reference's initial values, drawn in fp32 from the adapters' generator
         return self._lora_params
@@ -441,33 +395,19 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     if linear_dim < max(ok, in_) / 2:
                         raise NotImplementedError(f"lycoris_config linear_dim={linear_dim}: {name} would get a low-rank w2 ([{ok}, {in_}] needs linear_dim >= "
                                                   f"{max(ok, in_) // 2}), which is not built on the st355 path; set \"linear_dim\": 10000 (full matrices)")
-        total = sum(ol * im + ok * in_ for g in plan for (ol, ok, im, in_) in g.shapes)
-        total = (total + 7) // 8 * 8
-        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
-        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
-        gen = torch.Generator(device=dev).manual_seed(seed)
-        off = 0
-        self._lora_params = []
-        for g in plan:
-            g.flat_lo = off
-            for (name, n_off, N), (ol, ok, im, in_) in zip(g.targets, g.shapes):
-                views = []
-                for shp in ((ol, im), (ok, in_)):
-                    n = shp[0] * shp[1]
-                    views.append((self.lora_flat[off:off + n].view(shp), self.lora_grad_flat[off:off + n].view(shp)))
-                    off += n
-                (w1, g1), (w2, g2) = views
+        arena = AdapterArena(self, dev)
+        slots = [[(arena.add(name + ".lokr_w1", (ol, im)), arena.add(name + ".lokr_w2", (ok, in_))) for (name, _, _), (ol, ok, im, in_) in zip(g.targets, g.shapes)] for g in plan]
+        gen = arena.build(seed)
+        for g, pairs in zip(plan, slots):
+            g.flat_lo, g.flat_hi = pairs[0][0].lo, pairs[-1][1].hi
+            for (name, n_off, N), (s1, s2) in zip(g.targets, pairs):
                 if init_norm is None:
-                    bound = 1.0 / math.sqrt(im)
-                    w1.copy_((torch.rand(ol, im, generator=gen, device=dev) * 2 - 1) * bound)
+                    ol, im = s1.shape
+                    s1.p.copy_((torch.rand(ol, im, generator=gen, device=dev) * 2 - 1) * (1.0 / math.sqrt(im)))
                 else:
-                    w1.fill_(1.0)
-                    lokr_init_norm(g.lin.w[n_off:n_off + N], w2, float(init_norm), gen)
-                p1, p2 = nn.Parameter(w1), nn.Parameter(w2)
-                attach(self, name + ".lokr_w1", p1); attach(self, name + ".lokr_w2", p2)
-                g.w1.append(p1.data); g.w2.append(p2.data); g.g1.append(g1); g.g2.append(g2)
-                self._lora_params += [p1, p2]
-            g.flat_hi = off
+                    s1.p.fill_(1.0)
+                    lokr_init_norm(g.lin.w[n_off:n_off + N], s2.p, float(init_norm), gen)
+                g.w1.append(s1.p); g.w2.append(s2.p); g.g1.append(s1.g); g.g2.append(s2.g)
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------

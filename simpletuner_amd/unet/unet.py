@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import LoraGroup, attach, frozen, pad64
+from ..engine import AdapterArena, LoraGroup, attach, frozen, lora_pairs, node_backward, pad64
 from ..ops import EPI_ADD, EPI_GEGLU, EPI_GEGLU_GRAD, EPI_HEADS, EPI_NONE
 from ..training.checkpoint_plan import CheckpointPlanMixin
 
@@ -407,27 +407,9 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
         for i, blk in enumerate(self.up):
             for j, t in enumerate(blk.attns):
                 tr(t, f"up_blocks.{i}.attentions.{j}.")
-        total = (sum(rank * K + N * rank for (_, _, N, K) in plan) + 7) // 8 * 8
-        self.lora_flat = torch.zeros(total, dtype=F32, device=dev)
-        self.lora_grad_flat = torch.zeros(total, dtype=F32, device=dev)
-        gen = torch.Generator(device=dev).manual_seed(seed)
-        off = 0
-        self._lora_params = []
-        for (g, name, N, K) in plan:
-            if not g.A:
-                g.flat_lo = off
-            a = self.lora_flat[off:off + rank * K].view(rank, K); ga = self.lora_grad_flat[off:off + rank * K].view(rank, K)
-            off += rank * K
-            b = self.lora_flat[off:off + N * rank].view(N, rank); gb = self.lora_grad_flat[off:off + N * rank].view(N, rank)
-            off += N * rank
-            a.copy_((torch.rand(rank, K, generator=gen, device=dev) * 2 - 1) / math.sqrt(K))
-            if init_b_std > 0:
-                b.copy_(torch.randn(N, rank, generator=gen, device=dev) * init_b_std)
-            pa, pb = nn.Parameter(a), nn.Parameter(b)
-            attach(self, name + ".lora_A.default.weight", pa); attach(self, name + ".lora_B.default.weight", pb)
-            g.A.append(pa.data); g.B.append(pb.data); g.gA.append(ga); g.gB.append(gb)
-            g.flat_hi = off
-            self._lora_params += [pa, pb]
+        arena = AdapterArena(self, dev)
+        draw = lora_pairs(arena, plan, rank, init_b_std, divide=True)
+        draw(arena.build(seed))
         self._alloc_transposed()
         self._refresh_transposed()                       # frozen base: the K-major copies are built once
         return self._lora_params
@@ -989,34 +971,17 @@ class _UNetFn(torch.autograd.Function):
         has_add = model.config.addition_embed_type == "text_time"
         out, tape = model._engine_forward(sample.detach(), timestep.detach(), ehs.detach(), te.detach() if has_add else None,
                                           ti.detach() if has_add else None, save=True)
-        fctx.model, fctx.tape, fctx.out = model, tape, out
+        fctx.model, fctx.ectx, fctx.out = model, tape, out
         return out
 
     @staticmethod
     def backward(fctx, dout):
         model = fctx.model
-        if model.grad_sync is not None:
-            model.grad_sync.begin()
-        if model.full:
-            model._refresh_transposed()
-        fctx.tape.backward(fctx.out, dout.contiguous())
-        fctx.tape = None
-        arena = model.grad_arena if model.full else model.lora_grad_flat
-        if model.grad_sync is not None:
-            if not model.full:
-                model.grad_sync.ready(0, arena.numel())          # LoRA: one small all-reduce after the backward
-            model.grad_scale_from_sync = model.grad_sync.finish()
-            sent = sum(hi - lo for lo, hi in model.grad_sync.launched_slices)
-            if sent != arena.numel():
-                raise RuntimeError(f"gradient sync covered {sent} of {arena.numel()} elements: a parameter's gradient was never reported ready")
-        from ..training.grad_sync import hand_over_gradients
-        gflat = hand_over_gradients(model, arena)
-        model._last_grad_flat = gflat
-        if model.full:
-            grads = [gflat[off:off + n].view_as(p) for (off, n), p in zip(model._full_offsets, model._full_params)]
-        else:
-            grads, off = [], 0
-            for p in model._lora_params:
-                grads.append(gflat[off:off + p.numel()].view_as(p))
-                off += p.numel()
-        return (None,) * 6 + tuple(grads)
+
+        def run(tape, dout):
+            if model.full:
+                model._refresh_transposed()
+            tape.backward(fctx.out, dout.contiguous())
+
+        # LoRA: one small all-reduce of the whole arena after the backward
+        return (None,) * 6 + node_backward(fctx, model.full, dout, run=run, whole=not model.full, covered=True)
