@@ -712,6 +712,36 @@ int st355_reflexflow_loss(void* stream, const void* pred, const void* target, co
 /* x[b, :] <- x[b, :] + dt[b] v[b, :] in place (the rollout's Euler update): dt fp32 [batch] on the device, fp32 arithmetic, one rounding.  x != v. */
 int st355_flow_euler_step(void* stream, void* x, const void* v, const float* dt, int64_t batch, int64_t per_sample);
 
+/* ---- Flow-DPO preference training (distillation_method=flow_dpo; helpers/distillation/flow_dpo/distiller.py; csrc/flow_dpo.hip).  policy / ref: bf16
+ * [2 pairs, per_sample] contiguous, rows [0, pairs) the preferred samples, [pairs, 2 pairs) the rejected ones; target_w / target_l: bf16 [pairs, per_sample];
+ * emask: fp32 [pairs, mask_period] (element i of a sample reads emask[b, i % mask_period]; 16-byte aligned, mask_period % 8 == 0 dividing per_sample) or NULL.
+ * per_sample % 8 == 0, pairs < 32768.  Reductions run in two stages in a fixed order (bit-identical run to run), the second on the device; `workspace`:
+ * st355_flow_dpo_workspace(pairs, per_sample) bytes, 16-byte aligned. */
+int64_t st355_flow_dpo_workspace(int64_t pairs, int64_t per_sample);
+/* stats_out fp32 [pairs, 9]: sum m (pw - tw)^2, sum m (pl - tl)^2, sum m (rw - tw)^2, sum m (rl - tl)^2 (the four errors, for the logs), sum (pw - rw)^2,
+ * sum (pl - rl)^2 (the anchor, unmasked), sum m, and the two advantages accumulated element by element: sum m (rw - pw)(rw + pw - 2 tw) and
+ * sum m (pl - rl)(pl + rl - 2 tl). */
+int st355_flow_dpo_stats(void* stream, const void* policy, const void* ref, const void* target_w, const void* target_l, const float* emask, int64_t mask_period,
+                         float* stats_out, void* workspace, int64_t pairs, int64_t per_sample);
+/* One workgroup over the stats.  nu_b = 1 (norm_type 0, sum), 1 / per_sample (1, mean; 2, masked_mean, without a mask), 1 / max(stats[b, 6], 1) (2 with a mask);
+ * margin_b = nu_b (stats[b, 7] + stats[b, 8]);  absmean = mean_b |margin_b|.  auto_beta: ema_state[0] <- ema_state[1] ? decay ema + (1 - decay) absmean : absmean,
+ * ema_state[1] <- 1, beta = clamp(auto_num / max(ema, eps), beta_min, beta_max); else the given beta.  logit_b = beta margin_b / 2;
+ * dpo = -mean_b log sigma(logit_b) (log sigma(x) = min(x, 0) - log1p(exp(-|x|)));  anchor = anchor_alpha (mean (pw - rw)^2 + mean (pl - rl)^2) / 2;
+ * loss_out[0] = dpo loss_weight + anchor;  pair_out fp32 [pairs, 4] = (margin, logit, c = loss_weight beta sigma(-logit) / (2 pairs), nu).
+ * logs_out fp32 [16]: dpo, beta, mean margin, mean preferred advantage, mean rejected advantage, the four mean errors (policy preferred, policy rejected,
+ * reference preferred, reference rejected), 100 mean [margin < 0], mean sigma(-logit), loss_out + sft_weight original_loss[0] (original_loss may be NULL),
+ * anchor, absmean, ema, original_loss[0].
+ * mode 0: all of it.  mode 1: nu, the margins and absmean_io[0] only, the EMA untouched (the rank mean of absmean_io follows, outside).  mode 2: all of it with
+ * absmean_io[0] as given. */
+int st355_flow_dpo_head(void* stream, const float* stats, int norm_type, int has_mask, int mode, float* absmean_io, float* ema_state, int auto_beta, float beta,
+                        float auto_num, float decay, float beta_min, float beta_max, float eps, float loss_weight, float anchor_alpha, const float* original_loss,
+                        float sft_weight, float* pair_out, float* loss_out, float* logs_out, int64_t pairs, int64_t per_sample);
+/* dpred bf16 [2 pairs, per_sample], rounded once = s d loss_out / d policy, s = grad_scale (* grad_scale_dev[0] when given: the upstream gradient on the device):
+ *   preferred rows  s [ 2 c_b nu_b m (p - tw) + anchor_alpha (p - r) / (pairs per_sample)],  rejected rows  s [-2 c_b nu_b m (p - tl) + anchor_alpha (p - r) / (pairs per_sample)].
+ * ref may be NULL when anchor_alpha == 0. */
+int st355_flow_dpo_grad(void* stream, const void* policy, const void* ref, const void* target_w, const void* target_l, const float* emask, int64_t mask_period,
+                        const float* pair, void* dpred, int64_t pairs, int64_t per_sample, float anchor_alpha, float grad_scale, const float* grad_scale_dev);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

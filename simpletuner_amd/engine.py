@@ -18,6 +18,7 @@
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -904,6 +905,49 @@ class ArenaModule(nn.Module):
 
     def trainable_parameters(self):
         return list(self._full_params) if self.full else list(self._lora_params)
+
+    # ---- adapters off / on (peft's names: the reference's distillers call them on the trained component) ----
+    def disable_lora(self):
+        """Take every LoRA group off its site: the engine forward then launches exactly the base model's sequence (no down projection, an empty K-extension, the
+        block-level entry points get NULL adapter operands) and, with no group left, neither packs nor drops.  Meant for no-grad forwards between training
+        forwards (Flow-DPO's reference model); `enable_lora()` puts the same groups back.  DoRA and LoKr fold their adapters into the weights and are refused."""
+        if getattr(self, "_lora_off", None) is not None:
+            return
+        if getattr(self, "lora_dora", False) or getattr(self, "lora_lokr", False):
+            raise NotImplementedError("disable_lora: switching a DoRA / LoKr adapter off (its fold lives in the weights) is not built on the st355 path")
+        sites = [(l, l.lora) for l in self._all_linears() if getattr(l, "lora", None) is not None]
+        mod = getattr(self, "mod_lora", None)
+        if len(sites) + (mod is not None) != len(self.lora_groups):
+            raise RuntimeError(f"disable_lora: {len(self.lora_groups)} adapter groups but {len(sites) + (mod is not None)} sites found")
+        self._lora_off = (sites, self.lora_groups, mod, getattr(self, "lora_dropout", None))
+        for l, _ in sites:
+            l.lora = None
+        self.lora_groups = []
+        if mod is not None:
+            self.mod_lora = None
+        if hasattr(self, "lora_dropout"):
+            self.lora_dropout = None
+
+    def enable_lora(self):
+        off, self._lora_off = getattr(self, "_lora_off", None), None
+        if off is None:
+            return
+        sites, groups, mod, drop = off
+        for l, g in sites:
+            l.lora = g
+        self.lora_groups = groups
+        if mod is not None:
+            self.mod_lora = mod
+        if hasattr(self, "lora_dropout"):
+            self.lora_dropout = drop
+
+    @contextmanager
+    def lora_disabled(self):
+        self.disable_lora()
+        try:
+            yield self
+        finally:
+            self.enable_lora()
 
     def _refresh_transposed(self):
         """W^T follows the weights (2 B read + 2 B write per parameter per step: ~12 ms for Flux.1-dev's 12 B parameters, ~1 ms for SD3-Medium)"""

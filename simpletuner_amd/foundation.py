@@ -631,6 +631,10 @@ class ModelFoundation(ExplorativeModelingMixin):
         it: 0.0 when absent; a full fine-tune and lora_type=lycoris ignore the flag, as the reference does; a standard LoRA of a family without the masked kernels
         refuses a positive value by name — never a silently different computation."""
         cfg = self.config
+        if getattr(cfg, "distillation_method", None):          # safety_check.py:23-49: a distillation method trains its adapters without dropout
+            from .flow_dpo import adapter_dropout_override, method_of
+            if method_of(cfg) is not None:
+                adapter_dropout_override(cfg)
         p = float(getattr(cfg, "lora_dropout", 0.0) or 0.0)
         if "lora" not in str(getattr(cfg, "model_type", "lora")) or str(getattr(cfg, "lora_type", "standard") or "standard").lower() != "standard":
             return 0.0

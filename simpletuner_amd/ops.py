@@ -260,6 +260,110 @@ def flow_euler_step(x, v, dt):
     return x
 
 
+FLOW_DPO_NORMS = {"sum": 0, "mean": 1, "masked_mean": 2}
+FLOW_DPO_LOGS = ("flow_dpo_loss", "flow_dpo_beta", "flow_dpo_margin", "flow_dpo_win_adv", "flow_dpo_lose_adv", "flow_dpo_policy_win_err",
+                 "flow_dpo_policy_lose_err", "flow_dpo_ref_win_err", "flow_dpo_ref_lose_err", "flow_dpo_negative_margin_pct", "flow_dpo_gradient_factor", "total",
+                 "flow_dpo_anchor_loss", "flow_dpo_margin_abs", "flow_dpo_margin_ema", "original_loss")          # the entries of flow_dpo_head's log vector, in order
+
+
+def _fd_rows(policy, ref, target_w, target_l, emask):
+    """the operands of the Flow-DPO ops: policy / ref bf16 [2B, ...], the targets bf16 [B, ...] of the same per-sample shape, emask fp32 [B, period] or None;
+    returns (contiguous tensors, B, N, emask, period)"""
+    _chk(policy, BF16, "policy"); _chk(target_w, BF16, "target_w"); _chk(target_l, BF16, "target_l")
+    if ref is not None:
+        _chk(ref, BF16, "ref")
+        if ref.shape != policy.shape:
+            raise _l.St355Error(f"ref: shape {tuple(ref.shape)} differs from policy's {tuple(policy.shape)}")
+    if policy.shape[0] % 2 != 0 or target_w.shape != target_l.shape or target_w.shape[0] * 2 != policy.shape[0] or target_w.shape[1:] != policy.shape[1:]:
+        raise _l.St355Error(f"flow_dpo: policy [2B, ...] {tuple(policy.shape)} needs targets [B, ...], got {tuple(target_w.shape)} / {tuple(target_l.shape)}")
+    B = target_w.shape[0]
+    N = target_w.numel() // B
+    if N % 8 != 0 or not 0 < B < 32768:
+        raise _l.St355Error(f"flow_dpo: per-sample size {N} must be a multiple of 8 and the pair count {B} below 32768")
+    period = 0
+    if emask is not None:
+        _chk(emask, F32, "emask")
+        emask = emask.reshape(B, -1).contiguous()
+        period = emask.shape[1]
+        if period % 8 != 0 or N % period != 0:
+            raise _l.St355Error(f"emask: period {period} must be a multiple of 8 dividing the per-sample size {N}")
+    return [policy.contiguous(), None if ref is None else ref.contiguous(), target_w.contiguous(), target_l.contiguous()], B, N, emask, period
+
+
+def flow_dpo_stats(policy, ref, target_w, target_l, emask=None):
+    """fp32 [B, 9] per pair (rows [0, B) of policy / ref: preferred, [B, 2B): rejected): the four masked errors (policy preferred, policy rejected, reference
+    preferred, reference rejected), the two anchor sums sum (p - r)^2, the mask sum, and the preferred / rejected advantages accumulated element by element;
+    fixed-order two-stage reduction"""
+    L = _l.load()
+    ts, B, N, emask, period = _fd_rows(policy, ref, target_w, target_l, emask)
+    if ts[1] is None:
+        raise _l.St355Error("flow_dpo_stats: the reference prediction is required")
+    stats = torch.empty(B, 9, dtype=F32, device=policy.device)
+    ws = _scratch("flow_dpo", policy.device, L.st355_flow_dpo_workspace(B, N))
+    _l.check(L.st355_flow_dpo_stats(_stream(), _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]), _ptr(emask), period, _ptr(stats), _ptr(ws), B, N), "flow_dpo_stats")
+    return stats
+
+
+def flow_dpo_head(stats, per_sample: int, norm_type: str = "sum", has_mask: bool = False, beta: float = 1.0, loss_weight: float = 1.0, anchor_alpha: float = 0.0,
+                  ema_state=None, auto_num: float = 0.0, decay: float = 0.99, beta_min=None, beta_max=None, eps: float = 1e-6, original_loss=None,
+                  sft_weight: float = 0.0, reduce_absmean=None):
+    """The one-workgroup head over flow_dpo_stats' [B, 9]: nu, the margins, beta (auto-beta when `ema_state`, fp32 [2] on the device = (ema, initialised), is
+    given: it is updated in place; auto_num = -2 logit(target)), the logits, the loss and the per-pair coefficients.  reduce_absmean: a callable that averages
+    the device scalar mean_b |margin_b| over the ranks in place (world size > 1), run between the head's two launches.  Returns (loss[1], pair [B, 4] = (margin,
+    logit, c, nu), logs fp32 [16] in the order of FLOW_DPO_LOGS)."""
+    L = _l.load()
+    _chk(stats, F32, "stats")
+    if stats.dim() != 2 or stats.shape[1] != 9 or not stats.is_contiguous():
+        raise _l.St355Error(f"stats: expected a contiguous fp32 [B, 9] tensor (flow_dpo_stats), got {tuple(stats.shape)}")
+    B, dev = stats.shape[0], stats.device
+    auto = ema_state is not None
+    if auto:
+        _chk(ema_state, F32, "ema_state")
+        if ema_state.numel() != 2 or not ema_state.is_contiguous():
+            raise _l.St355Error("ema_state: expected a contiguous fp32 [2] tensor (ema, initialised)")
+    if original_loss is not None:
+        _chk(original_loss, F32, "original_loss")
+    loss = torch.empty(1, dtype=F32, device=dev)
+    pair = torch.empty(B, 4, dtype=F32, device=dev)
+    logs = torch.empty(16, dtype=F32, device=dev)
+    absmean = torch.empty(1, dtype=F32, device=dev)
+    inf = float("inf")
+
+    def launch(mode):
+        _l.check(L.st355_flow_dpo_head(_stream(), _ptr(stats), FLOW_DPO_NORMS[norm_type], int(bool(has_mask)), mode, _ptr(absmean), _ptr(ema_state), int(auto),
+                                       float(beta), float(auto_num), float(decay), -inf if beta_min is None else float(beta_min),
+                                       inf if beta_max is None else float(beta_max), float(eps), float(loss_weight), float(anchor_alpha), _ptr(original_loss),
+                                       float(sft_weight), _ptr(pair), _ptr(loss), _ptr(logs), B, int(per_sample)), "flow_dpo_head")
+
+    if auto and reduce_absmean is not None:
+        launch(1)
+        reduce_absmean(absmean)
+        launch(2)
+    else:
+        launch(0)
+    return loss, pair, logs
+
+
+def flow_dpo_grad(policy, ref, target_w, target_l, pair, emask=None, anchor_alpha: float = 0.0, grad_scale: float = 1.0, upstream=None):
+    """d loss / d policy, bf16 [2B, ...] in one write: +-2 c_b nu_b m (p - t) + anchor_alpha (p - r) / (B n), times grad_scale (and the device scalar `upstream`)"""
+    L = _l.load()
+    ts, B, N, emask, period = _fd_rows(policy, ref, target_w, target_l, emask)
+    _chk(pair, F32, "pair")
+    if tuple(pair.shape) != (B, 4) or not pair.is_contiguous():
+        raise _l.St355Error(f"pair: expected a contiguous fp32 [{B}, 4] tensor (flow_dpo_head), got {tuple(pair.shape)}")
+    if float(anchor_alpha) != 0.0 and ts[1] is None:
+        raise _l.St355Error("flow_dpo_grad: the anchor term (anchor_alpha != 0) needs the reference prediction")
+    if upstream is not None:
+        _chk(upstream, F32, "upstream")
+        upstream = upstream.reshape(-1).contiguous()
+        if upstream.numel() != 1:
+            raise _l.St355Error("upstream: expected one fp32 device scalar")
+    dpred = torch.empty_like(ts[0])
+    _l.check(L.st355_flow_dpo_grad(_stream(), _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]), _ptr(emask), period, _ptr(pair), _ptr(dpred), B, N,
+                                   float(anchor_alpha), float(grad_scale), _ptr(upstream)), "flow_dpo_grad")
+    return dpred
+
+
 def flux_pack(latents):
     L = _l.load()
     _chk(latents, BF16, "latents")

@@ -214,6 +214,10 @@ class Trainer:
                 raise NotImplementedError("nextlat_enabled with XM noise candidates is not built on the st355 path")
         if hasattr(self.model, "scheduled_sampling_value"):
             self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
+        self.distiller = None
+        if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Flow-DPO (every other method is refused by name)
+            from ..flow_dpo import create_distiller
+            self.distiller = create_distiller(self.model)
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
@@ -275,6 +279,18 @@ class Trainer:
         if self._use_graph:
             loss = self._graph_forward_backward(prepared)
             self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)
+        elif self.distiller is not None:
+            # Flow-DPO (trainer.py:6432-6434, 6109-6132): the distiller's prepare_batch, ONE training forward over the doubled batch (preferred rows, then
+            # rejected), the plugin's own loss on the preferred rows, then the distill loss (its reference forward runs inside, adapters off, no grad)
+            prepared = self.distiller.prepare_batch(prepared, self.model, self.state)
+            pred = self.model.model_predict(self.distiller.policy_batch(prepared))
+            loss, self.last_aux_logs = self.distiller.compute_distill_loss(prepared, pred, self.distiller.original_loss(prepared, pred))
+            loss, gen_logs = self.distiller.generator_loss_step(prepared, pred, loss)
+            self.last_aux_logs.update(gen_logs)
+            if cfg.gradient_accumulation_steps > 1:
+                loss = loss / cfg.gradient_accumulation_steps
+            self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)
+            acc.backward(loss)
         else:
             prepared = self.model.apply_scheduled_sampling_rollout(prepared)             # :6059 (a no-op without a plan)
             pred = self.model.model_predict(prepared)                                    # :7097 -> :6085
