@@ -742,6 +742,20 @@ int st355_flow_dpo_head(void* stream, const float* stats, int norm_type, int has
 int st355_flow_dpo_grad(void* stream, const void* policy, const void* ref, const void* target_w, const void* target_l, const float* emask, int64_t mask_period,
                         const float* pair, void* dpred, int64_t pairs, int64_t per_sample, float anchor_alpha, float grad_scale, const float* grad_scale_dev);
 
+/* ---- Diff2Flow flow-matching loss of the epsilon / v families (diff2flow_enabled + diff2flow_loss; diff2flow/bridge.py, common.py:6231-6248; csrc/diff2flow.hip).
+ * pred: bf16 [batch, per_sample] with a per-sample stride of pred_stride elements (>= per_sample: read in place); noisy / tau: bf16 [batch, per_sample] contiguous;
+ * timesteps: int64 [batch] on the device; table: fp32 [table_len, 2] on the device, (sqrt(1/a), sqrt(1/a - 1)) for mode 0 (epsilon), (sqrt(a), sqrt(1 - a)) for
+ * mode 1 (v), gathered in the kernel at clamp(timesteps[b], 0, table_len - 1); weight: fp32 [batch] or NULL; emask: fp32 [batch, mask_period], mask_period dividing
+ * per_sample, or NULL.  With (c0, c1) the pair:  z = c0 x - c1 p;  mode 0: f = p - z, k = 1 + c1;  mode 1: f = (c0 p + c1 x) - z, k = c0 + c1;  d = f - tau;
+ *   per_sample_out[b] = weight[b] mean_i(d_i^2 m_i),  loss_out[0] = mean_b per_sample_out[b],  dpred (bf16 compact, one rounding, may be NULL) = grad_scale d loss / d pred
+ *   = 2 grad_scale k weight[b] d m / (batch per_sample).
+ * 16 bytes per lane where per_sample, pred_stride and mask_period are multiples of 8 and the pointers 16-byte aligned, else the same walk with scalar accesses.
+ * The reduction runs in two stages in a fixed order (bit-identical run to run), the second on the device; `workspace`: st355_diff2flow_workspace bytes. */
+int64_t st355_diff2flow_workspace(int64_t batch, int64_t per_sample);
+int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred_stride, const void* noisy, const void* tau, const int64_t* timesteps, const float* table,
+                         int table_len, int mode, const float* weight, const float* emask, int64_t mask_period, float* loss_out, float* per_sample_out,
+                         void* dpred, void* workspace, int64_t batch, int64_t per_sample, float grad_scale);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

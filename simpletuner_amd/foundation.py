@@ -1110,6 +1110,8 @@ class ModelFoundation(ExplorativeModelingMixin):
         if self.PREDICTION_TYPE is not PredictionTypes.FLOW_MATCHING:
             self.noise_schedule = DDPMSchedule(prediction_type=self.PREDICTION_TYPE.value, device=self.accelerator.device,
                                                rescale_betas_zero_snr=bool(getattr(self.config, "rescale_betas_zero_snr", False)))
+            if getattr(self.config, "diff2flow_enabled", False):
+                self.diff2flow_value()                               # common.py:563-564: the bridge (and its refusals) when the schedule is set up
         else:
             from .sampling import FlowMatchEulerDiscreteScheduler, fix_flow_match_euler_schedule_bounds
             self.noise_schedule = fix_flow_match_euler_schedule_bounds(
@@ -1118,6 +1120,15 @@ class ModelFoundation(ExplorativeModelingMixin):
 
     def flow_matching_target_direction(self) -> float:
         return 1.0
+
+    def diff2flow_value(self):
+        """`diff2flow_enabled` as the step takes it (setup_diff2flow_bridge, common.py:4558-4574): the Diff2FlowBridge over the training schedule on an epsilon / v
+        family with the flag set, else None — on a flow-matching family the flag (and `diff2flow_loss`) does nothing.  diffusers' DDPM schedule always carries
+        alphas_cumprod; a schedule without it switches the flag off with the reference's warning.  Refuses, by the flags' names, what the tables cannot carry."""
+        if not getattr(self.config, "diff2flow_enabled", False) or self.PREDICTION_TYPE not in (PredictionTypes.EPSILON, PredictionTypes.V_PREDICTION):
+            return None
+        from .diff2flow import resolve_bridge
+        return resolve_bridge(self)
 
     # ---- sigma / timestep sampling (common.py:4994-5090) ----
     def sample_flow_sigmas(self, batch: dict, state: dict):
@@ -1421,6 +1432,14 @@ class ModelFoundation(ExplorativeModelingMixin):
             batch["noisy_latents"] = noisy
             if self.PREDICTION_TYPE is PredictionTypes.V_PREDICTION:                  # get_velocity uses the un-perturbed noise (common.py:4649-4653)
                 batch["velocity_target"] = ops.ddpm_noise_mix(lat, noise, a, b, want_v=True)[1]
+            if getattr(self.config, "diff2flow_enabled", False) and self.diff2flow_value() is not None:
+                # common.py:5952-5955: noise - latents from the UN-perturbed noise, in the weight dtype, one rounding (the target output of the flow noising pass)
+                # (the zero sigmas are held per batch size: no fill launch per step.  The pass still writes a noisy output nobody reads — a target-only mode
+                # of the noising kernel is the follow-up)
+                zeros = self.__dict__.setdefault("_diff2flow_zero_sigmas", {})
+                if (bsz, str(dev)) not in zeros:
+                    zeros[(bsz, str(dev))] = torch.zeros(bsz, dtype=torch.float32, device=dev)
+                batch["flow_target"] = ops.flow_noise_mix(lat, zeros[(bsz, str(dev))], noise=noise)[1]
         batch.pop("noise_shape_ref", None)
         ss_offset, ss_reflex = self.scheduled_sampling_value()                          # common.py:6013-6037: after the noisy latents exist
         if ss_offset > 0 or ss_reflex:
@@ -1467,6 +1486,10 @@ class ModelFoundation(ExplorativeModelingMixin):
         model_pred = model_output["model_prediction"]
         if target is None:
             raise ValueError("Target is None. Cannot compute loss.")
+        if getattr(self.config, "diff2flow_loss", False):                             # common.py:6231-6248: before loss_type / snr_gamma / snr_weight are read
+            bridge = self.diff2flow_value()
+            if bridge is not None:
+                return self._diff2flow_loss(prepared_batch, model_pred, bridge, apply_conditioning_mask, _per_sample_only, _row_weight)
         loss_type = getattr(self.config, "loss_type", "l2")
         if loss_type not in ("l2", "huber", "smooth_l1"):
             raise NotImplementedError(f"Unsupported Loss Type {loss_type}")
@@ -1498,6 +1521,29 @@ class ModelFoundation(ExplorativeModelingMixin):
         if loss_type == "l2" and emask is None:
             return _MSELossFn.apply(model_pred, target, weight)
         return _CondLossFn.apply(model_pred, target, loss_type, huber_c, weight, emask)
+
+    def _diff2flow_loss(self, prepared_batch: dict, model_pred, bridge, apply_conditioning_mask: bool, per_sample_only: bool = False, row_weight=None):
+        """common.py:6231-6248 + 6402-6429 (xm_mixin.py:175-192 for the two XM passes): the prediction converted to a flow-matching field at the noisy latents and
+        the timestep, held to `flow_target` = noise - latents by a plain squared error, then the mask, the per-sample mean and the batch mean — one pass of
+        ops.diff2flow_loss, the coefficient pair gathered on the device.  loss_type, snr_gamma and snr_weight are not read on this branch (logged once): the
+        base row weight is None."""
+        bridge.log_ignored_once(self.config)
+        dev = model_pred.device
+        tau = prepared_batch.get("flow_target")
+        if tau is None:                                                                # get_flow_target (common.py:4660-4666)
+            lat = prepared_batch["latents"]
+            tau = ops.flow_noise_mix(lat, torch.zeros(lat.shape[0], dtype=torch.float32, device=lat.device), noise=prepared_batch["noise"])[1]
+        emask = self._conditioning_loss_mask(prepared_batch, model_pred, apply_conditioning_mask)      # common.py:6402-6424
+        noisy = prepared_batch["noisy_latents"].to(device=dev, dtype=BF16)
+        tau = tau.to(device=dev, dtype=BF16)
+        t = prepared_batch["timesteps"].to(device=dev).long()
+        table, mode = bridge.table(self.PREDICTION_TYPE.value), bridge.mode(self.PREDICTION_TYPE.value)
+        weight = None if row_weight is None else row_weight.to(device=dev, dtype=torch.float32).contiguous()
+        if per_sample_only:
+            with torch.no_grad():
+                per = ops.diff2flow_loss(model_pred.detach().to(BF16), noisy, tau, t, table, mode, weight=weight, want_grad=False, emask=emask)[1]
+            return per, None
+        return _Diff2FlowLossFn.apply(model_pred, noisy, tau, t, table, mode, weight, emask)
 
     def _reflexflow_loss(self, prepared_batch: dict, model_pred, target, loss_type, huber_c, emask, logs=None):
         """common.py:6287-6318 + 6426-6429, the flow-matching branch with `scheduled_sampling_reflexflow` truthy: the exposure weight from the rollout's cached
@@ -1636,6 +1682,22 @@ class _ReflexFlowLossFn(torch.autograd.Function):
     def backward(ctx, g, _gadr, _gstats):
         (dpred,) = ctx.saved_tensors
         return ((dpred.float() * g).to(dpred.dtype) if g.numel() == 1 else dpred,) + (None,) * 11
+
+
+class _Diff2FlowLossFn(torch.autograd.Function):
+    """the Diff2Flow loss (ops.diff2flow_loss), gradient from the same kernel pass; the prediction is read in place (PixArt's leading channel half)"""
+
+    @staticmethod
+    def forward(ctx, pred, noisy, tau, timesteps, table, mode, weight=None, emask=None):
+        loss, _per, dpred = ops.diff2flow_loss(pred.detach().to(BF16), noisy, tau, timesteps, table, mode, weight=weight, want_grad=True, emask=emask)
+        ctx.save_for_backward(dpred)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        # g is the upstream scalar (1.0, or the loss scale); fold it without a host sync
+        return ((dpred.float() * g).to(dpred.dtype) if g.numel() == 1 else dpred,) + (None,) * 7
 
 
 class _CondLossFn(torch.autograd.Function):

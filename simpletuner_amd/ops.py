@@ -260,6 +260,62 @@ def flow_euler_step(x, v, dt):
     return x
 
 
+DIFF2FLOW_MODES = {"epsilon": 0, "v_prediction": 1}
+
+
+def _d2f_rows(pred, noisy, tau, timesteps, table, weight, emask):
+    """the operands of the Diff2Flow loss: pred bf16 [B, ...] whose per-sample block is dense (a leading-channel slice of a wider output is read in place through
+    its batch stride), noisy / tau bf16 of its shape, timesteps int64 [B], table fp32 [T, 2], weight fp32 [B] or None, emask fp32 [B, period] or None;
+    returns (pred, contiguous noisy, tau, timesteps, table, emask, B, N, pred stride, period)"""
+    _chk(pred, BF16, "pred"); _chk(noisy, BF16, "noisy"); _chk(tau, BF16, "tau"); _chk(table, F32, "table")
+    _chk(timesteps, torch.int64, "timesteps")
+    if noisy.shape != pred.shape or tau.shape != pred.shape:
+        raise _l.St355Error(f"diff2flow_loss: noisy {tuple(noisy.shape)} and tau {tuple(tau.shape)} must have pred's shape {tuple(pred.shape)}")
+    B = pred.shape[0]
+    N = pred.numel() // B if B else 0
+    if N <= 0 or not 0 < B < 65536:
+        raise _l.St355Error(f"pred: the batch {B} must lie in [1, 65535] and the per-sample size {N} be positive")
+    if not pred[0].is_contiguous() or (B > 1 and pred.stride(0) < N):
+        pred = pred.contiguous()                                          # (an inner-strided view; the models' predictions never are)
+    stride = pred.stride(0) if B > 1 else N
+    if timesteps.numel() != B:
+        raise _l.St355Error(f"timesteps: expected {B} values, got {timesteps.numel()}")
+    if table.dim() != 2 or table.shape[1] != 2 or table.shape[0] < 1 or not table.is_contiguous():
+        raise _l.St355Error(f"table: expected a contiguous fp32 [T, 2] tensor, got {tuple(table.shape)}")
+    if weight is not None:
+        _chk(weight, F32, "weight")
+        if weight.numel() != B:
+            raise _l.St355Error(f"weight: expected {B} values, got {weight.numel()}")
+        weight = weight.contiguous()
+    period = 0
+    if emask is not None:
+        _chk(emask, F32, "emask")
+        emask = emask.reshape(B, -1).contiguous()
+        period = emask.shape[1]
+        if period <= 0 or N % period != 0:
+            raise _l.St355Error(f"emask: period {period} must divide the per-sample size {N}")
+    return pred, noisy.contiguous(), tau.contiguous(), timesteps.reshape(-1).contiguous(), table, weight, emask, B, N, stride, period
+
+
+def diff2flow_loss(pred, noisy, tau, timesteps, table, mode: str = "epsilon", weight=None, want_grad: bool = True, grad_scale: float = 1.0, emask=None):
+    """The Diff2Flow loss (bridge.py + common.py:6231-6248, 6402-6429) in one pass.  With (c0, c1) = table[clamp(timesteps[b], 0, T - 1)] — (sqrt(1/a), sqrt(1/a - 1))
+    for mode "epsilon", (sqrt(a), sqrt(1 - a)) for "v_prediction" — gathered on the device:  z = c0 x - c1 p;  f = p - z  (epsilon)  or  (c0 p + c1 x) - z  (v);
+    (f - tau)^2 [* emask] -> per-sample mean [* weight] -> batch mean, and the fused d(loss)/d(pred) (compact bf16, one rounding).  pred may be a leading-channel
+    slice of a wider output: it is read in place.  Returns (loss[1], per_sample[B], dpred)."""
+    L = _l.load()
+    if mode not in DIFF2FLOW_MODES:
+        raise _l.St355Error(f"diff2flow_loss: mode must be one of {sorted(DIFF2FLOW_MODES)}, got {mode!r}")
+    pred, noisy, tau, timesteps, table, weight, emask, B, N, stride, period = _d2f_rows(pred, noisy, tau, timesteps, table, weight, emask)
+    dev = pred.device
+    loss = torch.empty(1, dtype=F32, device=dev)
+    per_sample = torch.empty(B, dtype=F32, device=dev)
+    dpred = torch.empty(pred.shape, dtype=BF16, device=dev) if want_grad else None
+    ws = _scratch("diff2flow", dev, L.st355_diff2flow_workspace(B, N))
+    _l.check(L.st355_diff2flow_loss(_stream(), _ptr(pred), stride, _ptr(noisy), _ptr(tau), _ptr(timesteps), _ptr(table), table.shape[0], DIFF2FLOW_MODES[mode],
+                                    _ptr(weight), _ptr(emask), period, _ptr(loss), _ptr(per_sample), _ptr(dpred), _ptr(ws), B, N, grad_scale), "diff2flow_loss")
+    return loss, per_sample, dpred
+
+
 FLOW_DPO_NORMS = {"sum": 0, "mean": 1, "masked_mean": 2}
 FLOW_DPO_LOGS = ("flow_dpo_loss", "flow_dpo_beta", "flow_dpo_margin", "flow_dpo_win_adv", "flow_dpo_lose_adv", "flow_dpo_policy_win_err",
                  "flow_dpo_policy_lose_err", "flow_dpo_ref_win_err", "flow_dpo_ref_lose_err", "flow_dpo_negative_margin_pct", "flow_dpo_gradient_factor", "total",
