@@ -756,6 +756,19 @@ int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred_stride, co
                          int table_len, int mode, const float* weight, const float* emask, int64_t mask_period, float* loss_out, float* per_sample_out,
                          void* dpred, void* workspace, int64_t batch, int64_t per_sample, float grad_scale);
 
+/* ---- T-LoRA (lora_type=lycoris, `algo: tlora`; csrc/tlora.hip): y_b = base(x_b) + s (mask_b . (x_b A^T)) B^T, mask_b = the first r_b rank columns of sample b.
+ * st355_tlora_mask zeroes, in place, the inactive rank columns of a rank-space operand of a LoraGroup (T = x A_cat^T, U = dy B_blk_T): t is bf16 with M logical
+ * rows of row stride ld (compact when seg_rows == 0, else segments of seg_rows rows seg_stride ROWS apart, as the LoRA-dropout kernels take them), G targets of r_pad
+ * columns each from column 0.  Column g r_pad + j of row m becomes +0 iff j >= r_active(m / rows_per_sample), for g < G and j < rank; the padding columns
+ * [rank, r_pad) of every target and the columns from G r_pad on are neither read nor written, and survivors are never read.
+ *   r_active(b) = ranks_table[clamp(trunc(timesteps[b]), 0, T)]     timesteps: [B] on the device, fp32 / bf16 / int64 (ts_kind); ranks_table: int32 [T + 1] on the device
+ * Nothing is read on the host.  r_pad: 32 or a multiple of 64; G <= 4; 1 <= rank <= r_pad; ld % 8 == 0 and t 16-byte aligned; M == B * rows_per_sample. */
+#define ST355_TS_F32 0
+#define ST355_TS_BF16 1
+#define ST355_TS_I64 2
+int st355_tlora_mask(void* stream, void* t, int64_t ld, int64_t seg_rows, int64_t seg_stride, int64_t M, int64_t rows_per_sample, int G, int r_pad, int rank,
+                     const void* timesteps, int ts_kind, int64_t B, const int32_t* ranks_table, int T);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

@@ -5,6 +5,7 @@
   * `lokr_factorization` / `LokrGroup`: the LyCORIS LoKr adapters of such a group (the Kronecker delta folded into the GEMM operands, the structured gradients);
   * `LoraDropout`: a component's LoRA-dropout state (threshold, Philox key, the device-resident call counter);
   * `LoraDora`: a group's DoRA state (magnitudes, the row scale, the folded GEMM operands);
+  * `tlora_active_rank` / `TLora`: T-LoRA's timestep -> active-rank rule, a component's state (the device table) and one forward's binding of it to the timesteps;
   * `lin_w` / `lin_wT` / `lora_down` ... `lora_grads`: one adapter site of a block's forward / backward, phase by phase, a no-op without an adapter;
   * `rows_of` / `problems` / `compact`: a stream's rows of a joint [B * S, C] buffer as GEMM operands;
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
@@ -156,6 +157,34 @@ class LoraDora:
         self.Wf, self.WfT, self.Bf, self.BfT = e(N, K), e(K, N), e(N, K2), e(K2, N)
 
 
+def tlora_active_rank(t: int, T: int, R: int, Rmin: int, alpha: float) -> int:
+    """T-LoRA's active rank at integer timestep t (the reference's documentation/experimental/T_LORA.md, "How the masking works internally"), in Python floats
+    in exactly this order: r = min(R, int(((T - t) / T) ** alpha * (R - Rmin)) + Rmin)"""
+    return min(R, int(((T - t) / T) ** alpha * (R - Rmin)) + Rmin)
+
+
+class TLora:
+    """T-LoRA (LyCORIS `algo: tlora`) of one trained component: every adapted Linear computes y_b = base(x_b) + s (mask_b . (x_b A^T)) B^T with mask_b the first
+    r_b rank columns, r_b = tlora_active_rank(int(timestep_b)).  `table`: int32 [T + 1] on the device, built here once — the mask kernel gathers from it with the
+    device timestep (no host read: a captured step replays with whatever timesteps its static input holds).  `at(timesteps)` binds one forward's [B] timesteps:
+    the object the adapter-site helpers take as `tl`; the recompute passes and the backward of that forward use the same one, so every pass regenerates the
+    same mask."""
+
+    def __init__(self, R: int, Rmin: int, alpha: float, T: int, device):
+        self.R, self.Rmin, self.alpha, self.T = int(R), int(Rmin), float(alpha), int(T)
+        if not 1 <= self.Rmin <= self.R:
+            raise ValueError(f"tlora_min_rank must lie in [1, linear_dim = {self.R}], got {self.Rmin}")
+        if not self.alpha > 0.0:
+            raise ValueError(f"tlora_alpha must be positive, got {self.alpha}")
+        if self.T < 1:
+            raise ValueError(f"num_train_timesteps must be positive, got {self.T}")
+        self.ranks = [tlora_active_rank(t, self.T, self.R, self.Rmin, self.alpha) for t in range(self.T + 1)]
+        self.table = torch.tensor(self.ranks, dtype=torch.int32).to(device)
+
+    def at(self, timesteps):
+        return SimpleNamespace(table=self.table, timesteps=timesteps)
+
+
 class LoraGroup:
     """LoRA adapters of the projections that share one input (one fused GEMM).  peft semantics: y += (alpha/r) B A dropout(x): `streams` are the targets' mask
     stream ids (their index in the component's ordered target list — q / k / v share x but draw independent masks, as peft's per-module nn.Dropout); `down` /
@@ -236,17 +265,25 @@ class LoraGroup:
             ops.lora_pack(self.A[g], self.B[g], self.scale, self.A_cat, self.A_cat_T, self.B_blk, self.B_blk_T,
                           k2_off=g * self.r_pad, n_off=n_off)
 
-    def down(self, x, drop=None, out=None):
+    def down(self, x, drop=None, out=None, tl=None):
         """T = x A_cat^T [M, K2] bf16 — under dropout T_g = scale (keep_g . x) A_g^T for every target in one pass over x.  x: compact [M, K] or a [B, rows, K]
-        view of a joint buffer (the mask follows the logical row b * rows + s either way)."""
+        view of a joint buffer (the mask follows the logical row b * rows + s either way).  tl: T-LoRA — the inactive rank columns of every sample are zeroed
+        right behind the product."""
         if drop is None:
-            return ops.gemm(x, self.A_cat) if out is None else ops.gemm(x, self.A_cat, out=out)
+            T = ops.gemm(x, self.A_cat) if out is None else ops.gemm(x, self.A_cat, out=out)
+            return T if tl is None else self.tlora_mask(T, tl)
         self._drop_check()
         return ops.lora_down_drop(x, self.A_cat, self.r_pad, self.streams, drop, out=out)
 
-    def up(self, dy, out=None):
-        """U = dy B_blk [M, K2] bf16: the adapter term of the backward's dx and the left operand of dA"""
-        return ops.gemm(dy, self.B_fwd_T, out=out)
+    def up(self, dy, out=None, tl=None):
+        """U = dy B_blk [M, K2] bf16: the adapter term of the backward's dx and the left operand of dA (tl: T-LoRA's mask, as on T)"""
+        U = ops.gemm(dy, self.B_fwd_T, out=out)
+        return U if tl is None else self.tlora_mask(U, tl)
+
+    def tlora_mask(self, t, tl):
+        """T-LoRA: zeroes the rank columns >= r_b of sample b's rows of a rank-space operand [B * rows, K2] in place (ops.tlora_mask) — always launched, whatever
+        the ranks are: nothing here depends on device data"""
+        return ops.tlora_mask(t, self.r_pad, self.rank, len(self.targets), t.shape[0] // tl.timesteps.numel(), tl.table, tl.timesteps)
 
     def dx_add(self, dx, U, drop):
         """dx += scale sum_g keep_g . (U_g A_g): the adapter term of the projection's input gradient under dropout (the mask sits between U and A, so the term
@@ -391,10 +428,10 @@ class LokrGroup:
     def wT_of(self, lin):
         return self.WfT
 
-    def down(self, x, drop=None, out=None):
+    def down(self, x, drop=None, out=None, tl=None):
         return None
 
-    def up(self, dy, out=None):
+    def up(self, dy, out=None, tl=None):
         return None
 
     def grads(self, x, T, dy, U, accumulate: bool, sync=None, drop=None):
@@ -432,16 +469,16 @@ def lin_wT(lin):
     return lin.wT if lin.lora is None else lin.lora.wT_of(lin)
 
 
-def lora_down(lin, x, drop=None, out=None):          # forward: T = x A_cat^T (LoraGroup.down)
-    return None if lin is None or lin.lora is None else lin.lora.down(x, drop, out=out)
+def lora_down(lin, x, drop=None, out=None, tl=None):          # forward: T = x A_cat^T (LoraGroup.down; tl: T-LoRA's rank mask on it)
+    return None if lin is None or lin.lora is None else lin.lora.down(x, drop, out=out, tl=tl)
 
 
 def lora_fwd_kw(lin, T) -> dict:                     # forward: the K-extension of the base GEMM, y += T B^T
     return {} if T is None else dict(a2=T, b2=lin.lora.B_fwd)
 
 
-def lora_up(lin, dy, out=None):                      # backward: U = dy B [M, K2]
-    return None if lin is None or lin.lora is None else lin.lora.up(dy, out)
+def lora_up(lin, dy, out=None, tl=None):             # backward: U = dy B [M, K2] (tl: T-LoRA's rank mask on it)
+    return None if lin is None or lin.lora is None else lin.lora.up(dy, out, tl=tl)
 
 
 def lora_dx_kw(lin, U, drop) -> dict:                # backward: the K-extension of the dx GEMM, dx += U A — not under dropout: the mask sits between U and A

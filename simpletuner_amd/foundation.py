@@ -532,7 +532,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         refuse = lambda key, val, to: NotImplementedError(f"lycoris_config {key}={val}: not built on the st355 path (built: algo=lokr with both factors full, merged-weight "
                                                           f"forward); set {to}")
         algo = str(lc.get("algo", "lokr")).lower()
-        if algo != "lokr":
+        if algo not in ("lokr", "tlora"):
             raise refuse("algo", algo, '"algo": "lokr"')
         for k in ("decompose_both", "use_tucker", "use_scalar", "weight_decompose", "rs_lora", "train_norm", "bypass_mode"):
             if lc.get(k):
@@ -557,9 +557,15 @@ class ModelFoundation(ExplorativeModelingMixin):
         factors = {}
         for c in classes:
             sub = amap.get(c) or {}
-            if str(sub.get("algo", algo)).lower() != "lokr":
+            sub_algo = str(sub.get("algo", algo)).lower()
+            if sub_algo not in ("lokr", "tlora"):
                 raise refuse(f"apply_preset.module_algo_map.{c}.algo", sub["algo"], '"algo": "lokr"')
+            if sub_algo != algo:
+                raise NotImplementedError(f"lycoris_config apply_preset.module_algo_map.{c}.algo={sub_algo} beside algo={algo}: one component that mixes lokr and tlora "
+                                          "adapters is not built on the st355 path; set the same algo for every module class")
             factors[c] = int(sub.get("factor", lc.get("factor", -1)))
+        if algo == "tlora":
+            return self._tlora_value(lc, classes, amap)
         linear_dim, linear_alpha = int(lc.get("linear_dim", 4)), lc.get("linear_alpha", None)
         if linear_alpha is not None and float(linear_alpha) != float(linear_dim) and not ModelFoundation._lycoris_alpha_logged:
             ModelFoundation._lycoris_alpha_logged = True
@@ -570,6 +576,36 @@ class ModelFoundation(ExplorativeModelingMixin):
         return dict(factors=factors, multiplier=float(lc.get("multiplier", 1.0)), linear_dim=linear_dim, linear_alpha=linear_alpha,
                     init_norm=None if init_norm in (None, False) else float(init_norm),
                     validation_strength=float(getattr(cfg, "validation_lycoris_strength", 1.0) or 1.0))
+
+    def _tlora_value(self, lc: dict, classes, amap: dict) -> dict:
+        """`algo: tlora` of lycoris_value: {algo, classes, multiplier, linear_dim, linear_alpha, min_rank, alpha, num_train_timesteps, validation_strength}.
+        multiplier, linear_dim and linear_alpha go through int(), as the reference's create_lycoris call site does (trainer.py:3410-3412); the mask settings are
+        `tlora_min_rank` (default 1) and `tlora_alpha` (default 1.0) of the JSON, T is the noise schedule's num_train_timesteps."""
+        cfg = self.config
+        for c in classes:
+            for k in ("linear_dim", "linear_alpha", "tlora_min_rank", "tlora_alpha"):
+                if k in (amap.get(c) or {}) and (k not in lc or amap[c][k] != lc[k]):
+                    raise NotImplementedError(f"lycoris_config apply_preset.module_algo_map.{c}.{k}={amap[c][k]}: a per-class {k} is not built on the st355 path (one "
+                                              f"rank table per component); set \"{k}\" at the top level only")
+        linear_dim = int(lc.get("linear_dim", 4))
+        linear_alpha = int(lc.get("linear_alpha", 1))
+        min_rank, alpha = int(lc.get("tlora_min_rank", 1)), float(lc.get("tlora_alpha", 1.0))
+        if not 1 <= min_rank <= linear_dim:
+            raise ValueError(f"lycoris_config tlora_min_rank={min_rank}: must lie in [1, linear_dim = {linear_dim}]; set \"tlora_min_rank\" inside that range")
+        if not alpha > 0.0:
+            raise ValueError(f"lycoris_config tlora_alpha={alpha}: must be positive; set \"tlora_alpha\" above 0")
+        from .scheduled_sampling import num_train_timesteps_of
+        return dict(algo="tlora", classes=list(classes), multiplier=int(lc.get("multiplier", 1.0)), linear_dim=linear_dim, linear_alpha=linear_alpha,
+                    min_rank=min_rank, alpha=alpha, num_train_timesteps=num_train_timesteps_of(getattr(self, "noise_schedule", None)),
+                    validation_strength=float(getattr(cfg, "validation_lycoris_strength", 1.0) or 1.0))
+
+    def _tlora_of_component(self):
+        """the trained component's engine.TLora state, None without a T-LoRA adapter (or before the component exists)"""
+        try:
+            comp = self.get_trained_component()
+        except Exception:
+            comp = None
+        return getattr(self.unwrap_model(comp), "lora_tlora", None) if comp is not None else None
 
     ROLLOUT_BATCH_KEYS = None           # families with the scheduled-sampling rollout (Flux, SD3): the per-sample batch entries their model_predict reads
 
@@ -603,6 +639,9 @@ class ModelFoundation(ExplorativeModelingMixin):
                 and str(getattr(cfg, "lora_type", "standard") or "standard").lower() == "standard"):
             raise NotImplementedError(f"{flag} with lora_dropout={getattr(cfg, 'lora_dropout')}: the reference's rollout forwards are training-mode forwards that drop, "
                                       "which the no-grad route of the st355 path does not; not built")
+        if self._tlora_of_component() is not None:
+            raise NotImplementedError(f"{flag} with lycoris algo=tlora: the reference's rollout forwards run without the timestep rank mask, which every forward of a "
+                                      "T-LoRA component of the st355 path applies; not built")
         if getattr(cfg, "twinflow_enabled", False):
             raise NotImplementedError(f"{flag} with twinflow_enabled: TwinFlow is not built on the st355 path")
         if getattr(cfg, "controlnet", False):
@@ -926,6 +965,14 @@ class ModelFoundation(ExplorativeModelingMixin):
         from safetensors.torch import save_file
 
         from .training.lora_keys import PEFTLoRAFormat, normalize_lora_format
+        if not layers and getattr(self.unwrap_model(self.get_trained_component()), "lora_tlora", None) is not None:
+            if normalize_lora_format(getattr(self.config, "lora_format", None)) == PEFTLoRAFormat.COMFYUI:
+                raise NotImplementedError("lora_type=lycoris with lora_format=comfyui: the ComfyUI export of a T-LoRA adapter is not built on the st355 path; save with "
+                                          "--lora_format=diffusers")
+            os.makedirs(output_dir, exist_ok=True)
+            path = os.path.join(output_dir, self.LORA_WEIGHT_NAME)
+            save_file({k: v.detach().to("cpu").contiguous() for k, v in self.tlora_state_dict().items()}, path, metadata={"format": "pt"})
+            return path
         if not layers and getattr(self.unwrap_model(self.get_trained_component()), "lora_lokr", False):
             if normalize_lora_format(getattr(self.config, "lora_format", None)) == PEFTLoRAFormat.COMFYUI:
                 raise NotImplementedError("lora_type=lycoris with lora_format=comfyui: the ComfyUI export of a LoKr adapter is not built on the st355 path; save with "
@@ -1004,6 +1051,50 @@ class ModelFoundation(ExplorativeModelingMixin):
                 p.copy_(flat[k].to(device=p.device, dtype=p.dtype))
         return comp
 
+    TLORA_KEYS = (".lora_down.weight", ".lora_up.weight")
+
+    def tlora_state_dict(self, component=None) -> dict:
+        """a T-LoRA adapter as a LyCORIS file holds a LoCon module: per adapted module `lycoris_<module path, '.' -> '_'>.lora_down.weight` [r, in],
+        `.lora_up.weight` [out, r] (fp32) and `.alpha` (a scalar = linear_alpha).  The lay-out is restated from LyCORIS' naming rule, not pinned against the package."""
+        comp = self.unwrap_model(component if component is not None else self.get_trained_component())
+        sd = {}
+        for n, p in comp.named_parameters():
+            for key in self.TLORA_KEYS:
+                if n.endswith(key):
+                    mod = self.LYCORIS_PREFIX + n[:-len(key)].replace(".", "_")
+                    sd[mod + key] = p.detach()
+                    sd[mod + ".alpha"] = torch.tensor(float(comp.tlora_linear_alpha), dtype=torch.float32)
+        return sd
+
+    def _load_tlora_weights(self, comp, flat: dict):
+        """strict both ways: every matrix of the component is in the file with its shape, the file holds nothing else, and every alpha is the configured one"""
+        own = {}
+        for n, p in comp.named_parameters():
+            for key in self.TLORA_KEYS:
+                if n.endswith(key):
+                    own[self.LYCORIS_PREFIX + n[:-len(key)].replace(".", "_") + key] = p
+        alphas = {k[:-len(key)] + ".alpha" for k in own for key in self.TLORA_KEYS if k.endswith(key)}
+        missing = [k for k in list(own) + sorted(alphas) if k not in flat]
+        if missing:
+            raise KeyError(f"LyCORIS checkpoint is missing {len(missing)} adapter tensors, e.g. {missing[:3]}; the lycoris_config (target_module) must match the one "
+                           "the file was trained with")
+        extra = [k for k in flat if k not in own and k not in alphas]
+        if extra:
+            raise KeyError(f"LyCORIS checkpoint holds {len(extra)} tensors the adapter has no place for, e.g. {extra[:3]}; the lycoris_config (target_module) must match "
+                           "the one the file was trained with")
+        for k, p in own.items():
+            if tuple(flat[k].shape) != tuple(p.shape):
+                raise ValueError(f"LyCORIS checkpoint tensor {k} has shape {tuple(flat[k].shape)}, the adapter's is {tuple(p.shape)}: the lycoris_config linear_dim must "
+                                 "match the one the file was trained with")
+        want = float(comp.tlora_linear_alpha)
+        for k in sorted(alphas):
+            if float(flat[k]) != want:
+                raise ValueError(f"LyCORIS checkpoint alpha {float(flat[k])} ({k}) differs from the configured linear_alpha {want}; set linear_alpha to match the file")
+        with torch.no_grad():
+            for k, p in own.items():
+                p.copy_(flat[k].to(device=p.device, dtype=p.dtype))
+        return comp
+
     def _kohya_name_map(self) -> dict:
         """kohya module name -> this component's module path, built forwards from the adapters that exist (the underscore-joined kohya spelling
         cannot be split back into a dotted path on its own)"""
@@ -1027,6 +1118,22 @@ class ModelFoundation(ExplorativeModelingMixin):
         comp = self.get_trained_component()
         flat = load_file(os.path.join(input_dir, self.LORA_WEIGHT_NAME))
         prefix = f"{self.MODEL_SUBFOLDER}."
+        file_tlora = any(k.startswith(self.LYCORIS_PREFIX) and k.endswith(self.TLORA_KEYS) for k in flat)
+        own_tlora = getattr(self.unwrap_model(comp), "lora_tlora", None) is not None
+        if own_tlora and any(k.endswith(self.LOKR_KEYS) for k in flat):
+            raise ValueError("lycoris_config algo=tlora is set but the checkpoint carries LyCORIS LoKr factors (lokr_w1 / lokr_w2): set \"algo\": \"lokr\" in the "
+                             "lycoris_config to load it")
+        if file_tlora and not own_tlora:
+            if getattr(self.unwrap_model(comp), "lora_lokr", False):
+                raise ValueError("lycoris_config algo=lokr is set but the checkpoint carries LyCORIS low-rank pairs (lora_down / lora_up: a T-LoRA file): set "
+                                 "\"algo\": \"tlora\" in the lycoris_config to load it")
+            raise ValueError("LoRA checkpoint carries LyCORIS low-rank pairs (lycoris_*.lora_down / lora_up: a T-LoRA file) but the adapter was built as a standard "
+                             "LoRA: set --lora_type=lycoris (and a lycoris_config with \"algo\": \"tlora\") before loading it")
+        if own_tlora and not file_tlora:
+            raise ValueError("lycoris_config algo=tlora is set but the checkpoint carries no LyCORIS low-rank pairs (lycoris_*.lora_down / lora_up): it is a standard "
+                             "LoRA file; set --lora_type=standard to load it")
+        if own_tlora:
+            return self._load_tlora_weights(self.unwrap_model(comp), flat)
         file_lokr, own_lokr = any(k.endswith(self.LOKR_KEYS) for k in flat), bool(getattr(self.unwrap_model(comp), "lora_lokr", False))
         if file_lokr and not own_lokr:
             raise ValueError("LoRA checkpoint carries LyCORIS LoKr factors (lokr_w1 / lokr_w2) but the adapter was built as a standard LoRA: set --lora_type=lycoris "

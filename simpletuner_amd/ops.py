@@ -1111,6 +1111,26 @@ def lora_dx_drop(dx, U, A_cat_T, r_pad: int, streams, drop):
     return dx
 
 
+_TS_KINDS = {F32: 0, BF16: 1, torch.int64: 2}          # ST355_TS_*
+
+
+def tlora_mask(t, r_pad: int, rank: int, G: int, rows_per_sample: int, ranks_table, timesteps):
+    """T-LoRA (csrc/tlora.hip): zeroes, in place, column g r_pad + j of row m of the rank-space operand t (bf16 [M, >= G r_pad] or a [B, rows, C] view) iff
+    j >= ranks_table[clamp(trunc(timesteps[m // rows_per_sample]), 0, T)], for g < G and j < rank.  timesteps: [B] on the device, fp32 / bf16 / int64;
+    ranks_table: int32 [T + 1] on the device.  Nothing is read on the host."""
+    _chk(t, BF16, "tlora_mask: t"); _chk(ranks_table, torch.int32, "tlora_mask: ranks_table"); _dev(timesteps, "tlora_mask: timesteps")
+    M, cols, ld, seg, seg_s = _seg(t, "tlora_mask: t")
+    if timesteps.dtype not in _TS_KINDS or timesteps.dim() != 1 or not timesteps.is_contiguous():
+        raise _l.St355Error(f"tlora_mask: timesteps must be a contiguous [B] tensor of fp32 / bf16 / int64, got {timesteps.dtype} {tuple(timesteps.shape)}")
+    if ranks_table.dim() != 1 or not ranks_table.is_contiguous() or ranks_table.numel() < 2:
+        raise _l.St355Error(f"tlora_mask: ranks_table must be a contiguous int32 [T + 1], got {tuple(ranks_table.shape)}")
+    if cols < G * r_pad:
+        raise _l.St355Error(f"tlora_mask: {G} targets of {r_pad} columns do not fit the operand's {cols} columns")
+    _l.check(_l.load().st355_tlora_mask(_stream(), _ptr(t), ld, seg, seg_s, M, int(rows_per_sample), int(G), int(r_pad), int(rank), _ptr(timesteps),
+                                        _TS_KINDS[timesteps.dtype], timesteps.numel(), _ptr(ranks_table), ranks_table.numel() - 1), "tlora_mask")
+    return t
+
+
 def skinny_tn_drop(Lm, R, out, so_p: int, so_r: int, r_used: int, stream: int, drop, alpha: float = 1.0, accumulate: bool = False):
     """skinny_tn with the LoRA-dropout mask of `stream` on Lm (the Linear's input): out[p*so_p + r*so_r] (+)= alpha scale sum_m keep(m,p) Lm[m,p] R[m,r]"""
     L = _l.load()

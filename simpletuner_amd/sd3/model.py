@@ -63,7 +63,7 @@ class SD3(ModelFoundation):
         return params
 
     def _add_lycoris_adapter(self, comp):
-        """`lora_type=lycoris`: LoKr adapters on the Attention / FeedForward Linears from the JSON named by `lycoris_config` (ModelFoundation.lycoris_value).  The
+        """`lora_type=lycoris`: LoKr (or, `algo: tlora`, T-LoRA) adapters on the Attention / FeedForward Linears from the JSON named by `lycoris_config` (ModelFoundation.lycoris_value).  The
         standard-LoRA-only flags keep their treatment (lora_dropout / use_dora ignored); Internal Guidance / NextLat raise the reference's ValueError first."""
         cfg = self.config
         if getattr(cfg, "internal_guidance_enabled", False):
@@ -71,8 +71,12 @@ class SD3(ModelFoundation):
         if getattr(cfg, "nextlat_enabled", False):
             raise ValueError("NextLat requires standard PEFT LoRA or full-model training so its predictor is optimized and saved.")
         lc = self.lycoris_value()
-        params = comp.add_lokr_adapter(factors=lc["factors"], multiplier=lc["multiplier"], seed=int(getattr(cfg, "seed", 42) or 42) + 7, init_norm=lc["init_norm"],
-                                       linear_dim=lc["linear_dim"])
+        seed = int(getattr(cfg, "seed", 42) or 42) + 7
+        if lc.get("algo") == "tlora":          # T-LoRA: low-rank pairs with the timestep rank mask on the same site list
+            params = comp.add_tlora_adapter(classes=lc["classes"], linear_dim=lc["linear_dim"], linear_alpha=lc["linear_alpha"], multiplier=lc["multiplier"],
+                                            min_rank=lc["min_rank"], alpha=lc["alpha"], num_train_timesteps=lc["num_train_timesteps"], seed=seed)
+        else:
+            params = comp.add_lokr_adapter(factors=lc["factors"], multiplier=lc["multiplier"], seed=seed, init_norm=lc["init_norm"], linear_dim=lc["linear_dim"])
         comp.lokr_validation_strength = lc["validation_strength"]
         self.lycoris = lc
         comp.prepare_for_training()

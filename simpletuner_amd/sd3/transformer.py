@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, AdapterArena, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead,
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, AdapterArena, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
                       NextLatTap, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
                       lora_fwd_kw, lora_grads, lora_pairs, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
@@ -112,7 +112,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.lora_dropout: Optional[LoraDropout] = None          # add_lora_adapter(dropout > 0): applies to training forwards only
         self.lora_dora = False                                   # add_lora_adapter(dora=True): part of the weight, applies to every forward
         self.lora_lokr = False                                   # add_lokr_adapter(): LyCORIS LoKr, part of the weight, applies to every forward
-        self.lokr_multiplier, self.lokr_validation_strength = 1.0, 1.0
+        self.lokr_multiplier, self.lokr_validation_strength = 1.0, 1.0          # (the validation strength is `validation_lycoris_strength`: LoKr's and T-LoRA's)
+        self.lora_tlora: Optional[TLora] = None                  # add_tlora_adapter(): LyCORIS T-LoRA, a per-sample rank mask from the timestep in every forward
+        self.tlora_multiplier = 1
         self.lora_flat: Optional[torch.Tensor] = None
         self.lora_grad_flat: Optional[torch.Tensor] = None
         self._lora_params: List[nn.Parameter] = []
@@ -411,6 +413,71 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
+    # LyCORIS T-LoRA (`lora_type=lycoris`, `algo: tlora`): engine.LoraGroup + engine.TLora on the LoKr site list
+    # ------------------------------------------------------------------------------------------------
+    TLORA_MAX_DIM = 128          # the largest rank the rank-space kernels are exercised at (LoraGroup walks ranks above 64 in 64-column slabs)
+
+    def add_tlora_adapter(self, classes=("Attention", "FeedForward"), linear_dim: int = 4, linear_alpha: int = 1, multiplier: int = 1, min_rank: int = 1,
+                          alpha: float = 1.0, num_train_timesteps: int = 1000, seed: int = 7):
+        """classes: the module classes that get adapters (LyCORIS' `target_module`), on add_lokr_adapter's site list.  Every Linear of a selected class gets
+        down [r, in] and up [out, r] (`<module>.lora_down.weight` / `<module>.lora_up.weight`, fp32, pair by pair in the adapter arena in target order; r = linear_dim)
+        and computes, for sample b,  y_b = x_b W^T + bias + multiplier (linear_alpha / r) (mask_b . (x_b down^T)) up^T  in every forward, eval() included (there the
+        multiplier is times `lokr_validation_strength`), mask_b = the first r_b rank columns, r_b = engine.tlora_active_rank(int(timestep_b), num_train_timesteps,
+        r, min_rank, alpha).  LyCORIS' LoCon start: down ~ U(-1 / sqrt(in), 1 / sqrt(in)) (kaiming_uniform(a = sqrt 5)), up = 0 — the first forward is the base
+        model's bit for bit.  multiplier, linear_dim and linear_alpha are taken through int(), as the reference does."""
+        classes = list(classes)
+        for k in classes:
+            if k not in self.LOKR_CLASSES:
+                raise NotImplementedError(f"lycoris tlora: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
+        if self._ig_block is not None or self._nl_block is not None:
+            raise NotImplementedError("lycoris tlora with an Internal Guidance head / a NextLat predictor is not built on the st355 path")
+        rank, a, mult = int(linear_dim), int(linear_alpha), int(multiplier)
+        if not 1 <= rank <= self.TLORA_MAX_DIM:
+            raise NotImplementedError(f"lycoris_config linear_dim={rank}: the rank-space kernels of the st355 path take 1 <= linear_dim <= {self.TLORA_MAX_DIM}; set "
+                                      f"\"linear_dim\" inside that range")
+        dev = self.device_
+        state = TLora(rank, min_rank, alpha, num_train_timesteps, dev)          # (refuses tlora_min_rank / tlora_alpha outside their ranges)
+        self.lora_groups, self.lora_dropout, self.lora_dora, self.lora_lokr, self.lora_tlora = [], None, False, False, state
+        self.tlora_multiplier, self.tlora_linear_alpha = mult, a
+        plan = []
+
+        def group(lin, prefix, names):
+            n_each = lin.w.shape[0] // len(names)
+            g = LoraGroup(lin.w.shape[1], lin.w.shape[0], [(prefix + n, j * n_each, n_each) for j, n in enumerate(names)], rank, float(a), dev)
+            g.tlora_scale = g.scale            # alpha / r; `scale` itself is set by every forward: times the multiplier (eval(): and the validation strength)
+            g.scale = mult * g.tlora_scale
+            lin.lora = g
+            self.lora_groups.append(g)
+            plan.append(g)
+
+        for i, blk in enumerate(self.blocks):
+            p = f"transformer_blocks.{i}."
+            if "Attention" in classes:
+                group(blk.qkv, p + "attn.", ["to_q", "to_k", "to_v"])
+                group(blk.to_out, p + "attn.", ["to_out.0"])
+                group(blk.add_qkv, p + "attn.", ["add_q_proj", "add_k_proj", "add_v_proj"])
+                if blk.to_add_out is not None:
+                    group(blk.to_add_out, p + "attn.", ["to_add_out"])
+                if blk.dual:
+                    group(blk.qkv2, p + "attn2.", ["to_q", "to_k", "to_v"])
+                    group(blk.to_out2, p + "attn2.", ["to_out.0"])
+            if "FeedForward" in classes:
+                group(blk.ff1, p, ["ff.net.0.proj"])
+                group(blk.ff2, p, ["ff.net.2"])
+                if blk.ffc1 is not None:
+                    group(blk.ffc1, p, ["ff_context.net.0.proj"])
+                    group(blk.ffc2, p, ["ff_context.net.2"])
+        arena = AdapterArena(self, dev)
+        slots = [[(arena.add(name + ".lora_down.weight", (rank, g.K)), arena.add(name + ".lora_up.weight", (N, rank))) for (name, _, N) in g.targets] for g in plan]
+        gen = arena.build(seed)
+        for g, pairs in zip(plan, slots):
+            g.flat_lo, g.flat_hi = pairs[0][0].lo, pairs[-1][1].hi
+            for sd, su in pairs:
+                sd.p.copy_((torch.rand(rank, g.K, generator=gen, device=dev) * 2 - 1) * (1.0 / math.sqrt(g.K)))
+                g.A.append(sd.p); g.B.append(su.p); g.gA.append(sd.g); g.gB.append(su.g)
+        return self._lora_params
+
+    # ------------------------------------------------------------------------------------------------
     def _tables(self, h: int, w: int, S: int, B: int):
         """cropped position table expanded over the batch ([B*h*w, D] bf16) and identity RoPE tables (SD3 has no RoPE)"""
         key = (h, w, S, B)
@@ -436,6 +503,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ybuf = (lambda rows: torch.empty(rows, D, dtype=BF16, device=dev)) if (full and save) else (lambda rows: None)
         rpb = 1 if env.rpb_i == 1 else Si     # rows of the image stream that share one modulation row: the sample's (inside a TREAD route: its kept) rows, or 1 under tokenwise timesteps
         drop = getattr(env, "drop", None)      # LoRA dropout of this training forward (and of its recompute passes): the adapters' down projections draw masks
+        tl = getattr(env, "tl", None)          # T-LoRA: this forward's timesteps bound to the rank table — every down projection is masked per sample behind its product
         if self._c_entry_ok(blk, env, (img, txt), full=full, backward=False):
             return self._block_fwd_c(blk, img, txt, env, save, ybuf)
 
@@ -448,7 +516,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mt = mod[:, blk.mod_off_c:blk.mod_off_c + 6 * D]
             n_txt = ops.ln_modulate_fwd(txt, mt[:, D:2 * D], mt[:, :D], St)
         qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
-        T_img, T_txt = lora_down(blk.qkv, n_img, drop), lora_down(blk.add_qkv, n_txt, drop)
+        T_img, T_txt = lora_down(blk.qkv, n_img, drop, tl=tl), lora_down(blk.add_qkv, n_txt, drop, tl=tl)
         # the image stream (4096 rows per sample: tile-aligned) is ONE segmented problem over the joint buffer; the 154 text rows stay per sample
         after = []
         ops.gemm_grouped(_stream_problems(B, S, Si, dict(a=n_img, w=lin_w(blk.qkv), bias=blk.qkv.b, out=rows_of(qkv, 0, Si, B, S), **lora_fwd_kw(blk.qkv, T_img)), after)
@@ -487,6 +555,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             else:
                 for pr in _stream_problems(B, S, rows, dict(a=x, w=lin.lora.A_cat, out=T), after):
                     ops.gemm(pr.pop("a"), pr.pop("w"), **pr)
+                if tl is not None:
+                    lin.lora.tlora_mask(T, tl)
             return T
 
         aux = lambda y: {} if y is None else dict(aux_out=y)
@@ -507,7 +577,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             mi9 = mod[:, blk.mod_off:blk.mod_off + 9 * D]                        # (dual blocks never run tokenwise: refused in _engine_forward)
             Sip = (Si + 63) // 64 * 64
             n2a = ops.ln_modulate_fwd(img, mi9[:, 7 * D:8 * D], mi9[:, 6 * D:7 * D], Si)
-            T2 = lora_down(blk.qkv2, n2a, drop)
+            T2 = lora_down(blk.qkv2, n2a, drop, tl=tl)
             qkv2 = ops.gemm(n2a, lin_w(blk.qkv2), bias=blk.qkv2.b, **lora_fwd_kw(blk.qkv2, T2))
             Q2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); K2 = torch.empty_like(Q2)
             mk2 = torch.zeros if Sip > Si else torch.empty
@@ -520,7 +590,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             ops.attn_fwd(Q2, K2, V2t, O2, lse2b, B, H, Si, Sip, hd, scale)
             del V2t
             ya2 = ybuf(B * Si)
-            T_o2 = lora_down(blk.to_out2, O2, drop)
+            T_o2 = lora_down(blk.to_out2, O2, drop, tl=tl)
             x1b_img = ops.gemm(O2, lin_w(blk.to_out2), bias=blk.to_out2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi9[:, 8 * D:9 * D], rows_per_batch=Si,
                                **aux(ya2), **lora_fwd_kw(blk.to_out2, T_o2))
             d2 = SimpleNamespace(n2a=n2a, qkv2=qkv2, T2=T2, Q2=Q2, K2=K2, Q2t=Q2t, K2t=K2t, O2=O2, lse2b=lse2b, ya2=ya2, T_o2=T_o2, Sip=Sip)
@@ -530,22 +600,31 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         hpre_txt = x2_txt = n2_t = h_t = None
         yf_i, yf_t = ybuf(B * Si), (None if blk.last else ybuf(B * St))
         kf_i, kf_t = aux(yf_i), aux(yf_t)
+        # the feed-forward Linears' rank-space adapters (T-LoRA's FeedForward sites; nothing for a LoKr group or without an adapter): T = x A^T, masked, then the
+        # K-extension of the projection's own launch, in front of its GELU / gated-residual epilogue
+        T_f1 = T_f2 = T_c1 = T_c2 = None
         if blk.last:
-            h_i = ops.gemm(n2_i, lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img)
+            T_f1 = lora_down(blk.ff1, n2_i, drop, tl=tl)
+            h_i = ops.gemm(n2_i, lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img, **lora_fwd_kw(blk.ff1, T_f1))
+            T_f2 = lora_down(blk.ff2, h_i, drop, tl=tl)
             x2_img = ops.gemm(h_i, lin_w(blk.ff2), bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D],
-                              rows_per_batch=rpb, **kf_i)
+                              rows_per_batch=rpb, **kf_i, **lora_fwd_kw(blk.ff2, T_f2))
         else:
             n2_t = ops.ln_modulate_fwd(x1_txt, mt[:, 4 * D:5 * D], mt[:, 3 * D:4 * D], St)
             hpre_txt = torch.empty(B * St, 4 * D, dtype=BF16, device=dev)
-            h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img),
-                                         dict(a=n2_t, w=lin_w(blk.ffc1), bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt)])
+            T_f1, T_c1 = lora_down(blk.ff1, n2_i, drop, tl=tl), lora_down(blk.ffc1, n2_t, drop, tl=tl)
+            h_i, h_t = ops.gemm_grouped([dict(a=n2_i, w=lin_w(blk.ff1), bias=blk.ff1.b, epilogue=EPI_GELU, aux_out=hpre_img, **lora_fwd_kw(blk.ff1, T_f1)),
+                                         dict(a=n2_t, w=lin_w(blk.ffc1), bias=blk.ffc1.b, epilogue=EPI_GELU, aux_out=hpre_txt, **lora_fwd_kw(blk.ffc1, T_c1))])
+            T_f2, T_c2 = lora_down(blk.ff2, h_i, drop, tl=tl), lora_down(blk.ffc2, h_t, drop, tl=tl)
             x2_img, x2_txt = ops.gemm_grouped([
-                dict(a=h_i, w=lin_w(blk.ff2), bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D], rows_per_batch=rpb, **kf_i),
-                dict(a=h_t, w=lin_w(blk.ffc2), bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt, gate=mt[:, 5 * D:6 * D], rows_per_batch=St, **kf_t)])
+                dict(a=h_i, w=lin_w(blk.ff2), bias=blk.ff2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_img, gate=mi[:, 5 * D:6 * D], rows_per_batch=rpb, **kf_i,
+                     **lora_fwd_kw(blk.ff2, T_f2)),
+                dict(a=h_t, w=lin_w(blk.ffc2), bias=blk.ffc2.b, epilogue=EPI_GATE_RESIDUAL, aux_in=x1_txt, gate=mt[:, 5 * D:6 * D], rows_per_batch=St, **kf_t,
+                     **lora_fwd_kw(blk.ffc2, T_c2))])
         if save:
             sv = SimpleNamespace(img=img, txt=txt, n_img=n_img, n_txt=n_txt if (blk.add_qkv.lora is not None or full) else None, qkv=qkv, Q=Q, K=K,
                                  Qt=Qt, Kt=Kt, O=O, lse2=lse2, x1_img=x1_img, x1_txt=x1_txt, hpre_img=hpre_img,
-                                 hpre_txt=hpre_txt, T_img=T_img, T_txt=T_txt, T_o=T_o, T_ao=T_ao, d2=d2)
+                                 hpre_txt=hpre_txt, T_img=T_img, T_txt=T_txt, T_o=T_o, T_ao=T_ao, d2=d2, T_f1=T_f1, T_f2=T_f2, T_c1=T_c1, T_c2=T_c2)
             if full:    # a full fine-tune also needs every Linear's input (weight gradients) and the un-gated branch outputs (gate gradients)
                 sv.n2_i, sv.n2_t, sv.h_i, sv.h_t, sv.ya_i, sv.ya_t, sv.yf_i, sv.yf_t = n2_i, n2_t, h_i, h_t, ya_i, ya_t, yf_i, yf_t
             return x2_img, x2_txt, sv
@@ -570,7 +649,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
           backward, full          no trainable q / k RMSNorm weights (SD3.5): their gradients ride in the host form's RMSNorm backward pass"""
         if not (_BLOCK_ABI and not blk.dual and ops.ATTN_TR and all(t is None or t.is_contiguous() for t in streams)):
             return False
-        plain_lora = getattr(env, "drop", None) is None and not self.lora_dora and not self.lora_lokr
+        # (T-LoRA: the entries fuse the unmasked rank-space products and know no feed-forward adapter sites)
+        plain_lora = getattr(env, "drop", None) is None and not self.lora_dora and not self.lora_lokr and self.lora_tlora is None
         if not backward:
             return (1 if env.rpb_i == 1 else env.Si) == env.Si and plain_lora
         if not full:
@@ -686,6 +766,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         d_img, d_txt = grads
         grads.clear()
         drop = getattr(env, "drop", None)      # LoRA dropout: the masked dA / dx kernels regenerate this forward's masks
+        tl = getattr(env, "tl", None)          # T-LoRA: every U = dy B is masked as its T was (the same timesteps: the same mask)
         acc_, gs_ = self.accumulate_lora_grads, self.grad_sync
 
         def o_rows(lin, lo, rows):
@@ -705,24 +786,34 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         rpb_i = 1 if ctx.rpb_i == 1 else Si
         g_i = ops.scale_cols(d_img, mi[:, 5 * D:6 * D], rpb_i)
 
-        def ff_grads(l1, l2, x1, m6, rpb_, hpre, g_, dh_):
-            """the adapter gradients of a feed-forward pair (LoKr's FeedForward sites): its gradient operands are recomputed, nothing is saved for them — the
-            modulated LayerNorm rows as the forward made them, the activated rows from the kept pre-activation"""
+        def ff_grads(l1, l2, x1, m6, rpb_, hpre, g_, dh_, T1=None, T2=None, U1=None, U2=None):
+            """the adapter gradients of a feed-forward pair (LoKr's and T-LoRA's FeedForward sites): the Linears' inputs are recomputed, nothing is saved for them —
+            the modulated LayerNorm rows as the forward made them, the activated rows from the kept pre-activation.  T1 / T2: the forward's masked down projections
+            (T-LoRA keeps them: [M, K2] each), U1 / U2: the masked up products of the dx GEMMs above; None for a LoKr group."""
             if l1.lora is not None:
-                lora_grads(l1, ops.ln_modulate_fwd(x1, m6[:, 4 * D:5 * D], m6[:, 3 * D:4 * D], rpb_), None, dh_, None, acc_, gs_, drop)
+                lora_grads(l1, ops.ln_modulate_fwd(x1, m6[:, 4 * D:5 * D], m6[:, 3 * D:4 * D], rpb_), T1, dh_, U1, acc_, gs_, drop)
             if l2.lora is not None:
-                lora_grads(l2, ops.gelu_tanh(hpre), None, g_, None, acc_, gs_, drop)
+                lora_grads(l2, ops.gelu_tanh(hpre), T2, g_, U2, acc_, gs_, drop)
 
+        # (the feed-forward dx GEMMs take the rank-space adapter term as their K-extension: U = dy B masked, then dx += U A in front of the epilogue; nothing for a
+        # LoKr group or without an adapter)
+        U_f1 = U_f2 = None
         if blk.last:
-            dh_i = ops.gemm(g_i, lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img)
-            dn2_i = ops.gemm(dh_i, lin_wT(blk.ff1))
+            U_f2 = lora_up(blk.ff2, g_i, tl=tl)
+            dh_i = ops.gemm(g_i, lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img, **lora_dx_kw(blk.ff2, U_f2, drop))
+            U_f1 = lora_up(blk.ff1, dh_i, tl=tl)
+            dn2_i = ops.gemm(dh_i, lin_wT(blk.ff1), **lora_dx_kw(blk.ff1, U_f1, drop))
             dx1_t = dx1g_t = None
         else:
             g_t = ops.scale_cols(d_txt, mt[:, 5 * D:6 * D], St)
-            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img),
-                                           dict(a=g_t, w=lin_wT(blk.ffc2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt)])
-            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=lin_wT(blk.ff1)), dict(a=dh_t, w=lin_wT(blk.ffc1))])
-            ff_grads(blk.ffc1, blk.ffc2, sv.x1_txt, mt, St, sv.hpre_txt, g_t, dh_t)
+            U_f2, U_c2 = lora_up(blk.ff2, g_i, tl=tl), lora_up(blk.ffc2, g_t, tl=tl)
+            dh_i, dh_t = ops.gemm_grouped([dict(a=g_i, w=lin_wT(blk.ff2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_img, **lora_dx_kw(blk.ff2, U_f2, drop)),
+                                           dict(a=g_t, w=lin_wT(blk.ffc2), epilogue=EPI_MUL_GELU_GRAD, aux_in=sv.hpre_txt, **lora_dx_kw(blk.ffc2, U_c2, drop))])
+            U_f1, U_c1 = lora_up(blk.ff1, dh_i, tl=tl), lora_up(blk.ffc1, dh_t, tl=tl)
+            dn2_i, dn2_t = ops.gemm_grouped([dict(a=dh_i, w=lin_wT(blk.ff1), **lora_dx_kw(blk.ff1, U_f1, drop)),
+                                             dict(a=dh_t, w=lin_wT(blk.ffc1), **lora_dx_kw(blk.ffc1, U_c1, drop))])
+            ff_grads(blk.ffc1, blk.ffc2, sv.x1_txt, mt, St, sv.hpre_txt, g_t, dh_t, getattr(sv, "T_c1", None), getattr(sv, "T_c2", None), U_c1, U_c2)
+            del U_c1, U_c2
             dx1_t, dx1g_t = ops.ln_modulate_bwd(dn2_t, sv.x1_txt, mt[:, 4 * D:5 * D], St, dres=d_txt, gate=mt[:, 2 * D:3 * D], want_gated=True)
             del g_t, dh_t, dn2_t
         dn2a = None
@@ -731,7 +822,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             # gradient of the stream after the joint-attention residual (dx1) — attn2 first, then the joint attention as for a regular block
             d2, mi9 = sv.d2, mod[:, blk.mod_off:blk.mod_off + 9 * D]
             dx1_i, dxg2 = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], Si, dres=d_img, gate=mi9[:, 8 * D:9 * D], want_gated=True)
-            U2 = lora_up(blk.to_out2, dxg2)
+            U2 = lora_up(blk.to_out2, dxg2, tl=tl)
             dO2 = ops.gemm(dxg2, lin_wT(blk.to_out2), **lora_dx_kw(blk.to_out2, U2, drop))
             lora_dx_finish(blk.to_out2, dO2, U2, drop)
             lora_grads(blk.to_out2, d2.O2, d2.T_o2, dxg2, U2, acc_, gs_, drop)
@@ -739,7 +830,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             dQ2 = torch.empty(B, H, Si, hd, dtype=BF16, device=dev); dK2 = torch.empty_like(dQ2)
             ops.attn_bwd(d2.Q2, d2.K2, d2.Q2t, d2.K2t, d2.qkv2[:, 2 * D:], d2.O2, dO2, d2.lse2b, dQ2, dK2, dqkv2[:, 2 * D:], B, H, Si, d2.Sip, hd, scale)
             ops.qk_norm_rope_bwd(dQ2, dK2, d2.qkv2, blk.norm_q2, blk.norm_k2, cos, sin, dqkv2, B, H, hd, Si, 0, Si)
-            Uq2 = lora_up(blk.qkv2, dqkv2)
+            Uq2 = lora_up(blk.qkv2, dqkv2, tl=tl)
             if li != 0:
                 dn2a = ops.gemm(dqkv2, lin_wT(blk.qkv2), **lora_dx_kw(blk.qkv2, Uq2, drop))
                 lora_dx_finish(blk.qkv2, dn2a, Uq2, drop)
@@ -748,12 +839,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             del dxg2, dO2, dQ2, dK2, dqkv2, U2, Uq2, d2
         else:
             dx1_i, dx1g_i = ops.ln_modulate_bwd(dn2_i, sv.x1_img, mi[:, 4 * D:5 * D], rpb_i, dres=d_img, gate=mi[:, 2 * D:3 * D], want_gated=True)
-        ff_grads(blk.ff1, blk.ff2, sv.x1_img, mi, rpb_i, sv.hpre_img, g_i, dh_i)
-        del g_i, dh_i, dn2_i
+        ff_grads(blk.ff1, blk.ff2, sv.x1_img, mi, rpb_i, sv.hpre_img, g_i, dh_i, getattr(sv, "T_f1", None), getattr(sv, "T_f2", None), U_f1, U_f2)
+        del g_i, dh_i, dn2_i, U_f1, U_f2
         # attention output projections -> dO rows of both streams (+ adapter grads); a context_pre_only block has no txt rows (and no to_add_out)
         dO = (torch.zeros if blk.last else torch.empty)(B * S, D, dtype=BF16, device=dev)
         dO_i, dO_t = rows_of(dO, 0, Si, B, S), rows_of(dO, Si, St, B, S)
-        U_i, U_t = lora_up(blk.to_out, dx1g_i), lora_up(blk.to_add_out, dx1g_t)
+        U_i, U_t = lora_up(blk.to_out, dx1g_i, tl=tl), lora_up(blk.to_add_out, dx1g_t, tl=tl)
         after = []
         probs = _stream_problems(B, S, Si, dict(a=dx1g_i, w=lin_wT(blk.to_out), out=dO_i, **lora_dx_kw(blk.to_out, U_i, drop)), after)
         if not blk.last:
@@ -775,7 +866,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         # the two streams' rows of the joint dqkv: the image rows in place (segmented operands), the 154 text rows as a compact copy
         sites = [(blk.qkv, compact(rows_of(dqkv, 0, Si, B, S), B, Si), sv.n_img, sv.T_img, Si),
                  (blk.add_qkv, compact(rows_of(dqkv, Si, St, B, S), B, St), sv.n_txt, sv.T_txt, St)]
-        Us = [lora_up(lin, dq) for (lin, dq, _, _, _) in sites]
+        Us = [lora_up(lin, dq, tl=tl) for (lin, dq, _, _, _) in sites]
         if li != 0:               # (block 0: frozen embedders below, only the adapter gradients remain)
             dns = [torch.empty(B * rows, D, dtype=BF16, device=dev) for (_, _, _, _, rows) in sites]
             ops.gemm_grouped([dict(a=dq, w=lin_wT(lin), out=dn_, **lora_dx_kw(lin, U, drop)) for (lin, dq, _, _, _), U, dn_ in zip(sites, Us, dns)])
@@ -927,6 +1018,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         S = Si + St
         Sp = (S + 63) // 64 * 64
         dev = self.device_
+        if self.lora_tlora is not None:     # T-LoRA: the adapter scale of this forward is multiplier (alpha / r), in eval() forwards times the validation strength
+            mult = self.tlora_multiplier * (1.0 if self.training else self.lokr_validation_strength)
+            for g in self.lora_groups:
+                g.scale = mult * g.tlora_scale
         for g in self.lora_groups:
             g.pack()
             if g.dora is not None:          # DoRA: the row scale of the current A / B / m folded into W and B_blk, once per forward
@@ -982,7 +1077,16 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         drop = self.lora_dropout if (save and self.training and not full and self.lora_groups) else None
         if drop is not None:
             drop.advance()
-        env = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, mod=mod, mod_i=mod_i, rpb_i=rpb_i, scale=scale, full=full, drop=drop)
+        # T-LoRA: the [B] timesteps stay on the device — as the component received them when the mask kernel reads that dtype, else their fp32 image (exact for
+        # every integer step) — bound to the rank table for this forward, its recompute passes and its backward; every forward of the component, eval() included
+        tl = None
+        if self.lora_tlora is not None and self.lora_groups and not full:
+            if tokenwise:
+                raise NotImplementedError("lycoris tlora with tokenwise timesteps: the active rank is a function of ONE timestep per sample (the reference's int(t) over "
+                                          "a [B, S] list fails too); not built on the st355 path")
+            direct = timestep.device == dev and timestep.dtype in (F32, BF16, torch.int64) and timestep.is_contiguous()
+            tl = self.lora_tlora.at(timestep.reshape(-1) if direct else t32)
+        env = SimpleNamespace(B=B, Si=Si, St=St, S=S, Sp=Sp, cos=cos, sin=sin, mod=mod, mod_i=mod_i, rpb_i=rpb_i, scale=scale, full=full, drop=drop, tl=tl)
         ctx.env, ctx.blocks, ctx.ck = env, [None] * len(self.blocks), {}
         # activation-checkpoint plan (sd3/transformer.py:716-833; training/checkpoint_plan.py): a checkpointed segment keeps only its input
         from ..training.checkpoint_plan import segments as _segments

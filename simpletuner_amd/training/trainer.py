@@ -200,6 +200,10 @@ class Trainer:
             raise NotImplementedError("hip_graph: gradient_accumulation_steps == 1 only")
         if self._use_graph and getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
             raise NotImplementedError("hip_graph: XM noise candidates read their logs on the host every step and cannot be captured")
+        tlora = getattr(comp, "lora_tlora", None)
+        if tlora is not None and getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
+            raise NotImplementedError("lycoris algo=tlora with XM noise candidates: the candidate forwards would need the rank mask of the candidate's own timestep; not "
+                                      "built on the st355 path")
         if self._use_graph and getattr(config, "layersync_enabled", False):
             raise NotImplementedError("hip_graph: LayerSync (layersync_enabled) reads its logs on the host every step and cannot be captured")
         if getattr(config, "internal_guidance_enabled", False):
@@ -473,6 +477,9 @@ class Trainer:
         drop = getattr(plug.get_trained_component(), "lora_dropout", None)
         if drop is not None:                      # LoRA dropout: the mask sequence's position (the device-resident call counter), with the step counters
             ts["lora_dropout_calls"] = drop.calls()
+        tlora = getattr(plug.get_trained_component(), "lora_tlora", None)
+        if tlora is not None:                     # T-LoRA: the three mask settings, so that a resumed run can hold its config against them
+            ts["tlora"] = {"min_rank": tlora.Rmin, "alpha": tlora.alpha, "num_train_timesteps": tlora.T}
         if rank != 0:                                                                   # save_hooks.py:369-373: non-zero ranks write their own state file
             with open(os.path.join(checkpoint_dir, f"training_state-rank{rank}.json"), "w") as fh:
                 json.dump(ts, fh)
@@ -535,6 +542,13 @@ class Trainer:
             ts = json.load(fh)
         self.state.update({k: ts[k] for k in ("global_step", "epoch_step", "epoch", "exhausted_backends", "repeats") if k in ts})
         self.state["micro_step"] = int(ts.get("micro_step", self.state["global_step"] * self.config.gradient_accumulation_steps))
+        tlora = getattr(comp, "lora_tlora", None)
+        if tlora is not None and "tlora" in ts:   # T-LoRA: a resumed run trains under the mask the checkpoint was trained under
+            own = {"min_rank": tlora.Rmin, "alpha": tlora.alpha, "num_train_timesteps": tlora.T}
+            diff = [f"{k}: checkpoint {ts['tlora'].get(k)}, configured {v}" for k, v in own.items() if ts["tlora"].get(k) != v]
+            if diff:
+                raise ValueError("the checkpoint was trained under other T-LoRA mask settings (" + "; ".join(diff) + "): set tlora_min_rank / tlora_alpha in the "
+                                 "lycoris_config (and the noise schedule's num_train_timesteps) to the checkpoint's values")
         drop = getattr(comp, "lora_dropout", None)
         if drop is not None:                      # a resumed run continues the mask sequence (a state file from before the counter: the micro-step count)
             drop.set_calls(int(ts.get("lora_dropout_calls", self.state["micro_step"])))
