@@ -769,6 +769,30 @@ int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred_stride, co
 int st355_tlora_mask(void* stream, void* t, int64_t ld, int64_t seg_rows, int64_t seg_stride, int64_t M, int64_t rows_per_sample, int G, int r_pad, int rank,
                      const void* timesteps, int ts_kind, int64_t B, const int32_t* ranks_table, int T);
 
+/* ---- Self-Flow (CREPA with crepa_feature_source=self_flow; helpers/training/crepa.py, common.py `_prepare_image_crepa_self_flow_batch`; csrc/self_flow.hip) ----
+ * fp32 arithmetic, no atomics, fixed-order reductions (two calls give the same bits), nothing read on the host.
+ * st355_self_flow_views: latents / noise [B, C, H, W] (bf16 when in_bf16, else fp32; each sample contiguous, samples lat_bstride / noise_bstride ELEMENTS apart),
+ * sigma / sigma_alt / timesteps / timesteps_alt [B] fp32, uniforms [B, H/p, W/p] fp32, on the device.  Token (i, j) of sample b is masked iff uniforms[b, i, j] < ratio:
+ *   noisy_student[b, c, y, x] = (1 - s) latents + s noise,  s = masked(y / p, x / p) ? sigma_alt[b] : sigma[b]        (one rounding to the input dtype)
+ *   noisy_teacher[b, c, y, x] = (1 - sT) latents + sT noise, sT = min(sigma[b], sigma_alt[b])
+ *   token_timesteps[b, i (W/p) + j] = masked ? timesteps_alt[b] : timesteps[b];   sigma_teacher[b] = sT;   timestep_teacher[b] = min(timesteps[b], timesteps_alt[b])
+ * sigma_grid: NULL, or [B, H, W] fp32 that receives s.  Outputs are contiguous.  H % p != 0 or W % p != 0, a ratio outside [0, 0.5], C H W not a multiple of
+ * 8 (bf16) / 4 (fp32) elements and operands off a 16-byte boundary are refused.
+ * The projector LayerNorm(D, eps 1e-5) -> Linear(D -> D), parameters fp32, D % 8 == 0, D <= 4096, 16-byte aligned operands:
+ * st355_self_flow_fold: Wf [D, D] = bf16(gamma * W), WfT its transpose, c [D] = bf16(W beta + b).
+ * st355_self_flow_rows: h a [B, rows, D] bf16 view (row stride ld, batch stride bstride, elements) -> xhat [B * rows, D] compact bf16 (centred variance), rstd fp32.
+ * st355_self_flow_wgrad: P [D, D] bf16 = G^T xhat, db [D] fp32 = colsum(G), s = *scale_dev (ONE fp32 on the device) -> g_W = s (P * gamma + db beta^T), g_b = s db,
+ * g_gamma[d] = s sum_n W[n, d] P[n, d], g_beta[d] = s sum_n W[n, d] db[n]; accumulate != 0 adds to what the gradients hold.  ws: st355_self_flow_wgrad_workspace(D) bytes. */
+int st355_self_flow_views(void* stream, const void* latents, const void* noise, int in_bf16, int64_t lat_bstride, int64_t noise_bstride, const float* sigma,
+                          const float* sigma_alt, const float* timesteps, const float* timesteps_alt, const float* uniforms, float ratio, int patch,
+                          void* noisy_student, void* noisy_teacher, float* token_timesteps, float* sigma_teacher, float* timestep_teacher, float* sigma_grid, int B,
+                          int C, int H, int W);
+int st355_self_flow_fold(void* stream, const float* gamma, const float* beta, const float* W, const float* b, void* Wf, void* WfT, void* c, int D);
+int st355_self_flow_rows(void* stream, const void* h, void* xhat, float* rstd, int B, int rows, int D, int64_t ld, int64_t bstride);
+int64_t st355_self_flow_wgrad_workspace(int D);
+int st355_self_flow_wgrad(void* stream, const void* P, const float* db, const float* gamma, const float* beta, const float* W, const float* scale_dev, float* g_gamma,
+                          float* g_beta, float* g_W, float* g_b, int D, int accumulate, void* ws);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

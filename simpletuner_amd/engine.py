@@ -11,6 +11,8 @@
   * `layersync_indices` / `LayerSyncTap`: the LayerSync regulariser's forward taps and the injection of its gradient into the dX chain;
   * `internal_guidance_index` / `InternalGuidanceHead` / `InternalGuidanceTap`: the Internal Guidance head's parameters, its forward tap and its backward;
   * `nextlat_index` / `NextLatHead` / `NextLatTap`: the NextLat predictor's parameters, its forward tap (the state loss) and its backward;
+  * `self_flow_indices` / `SelfFlowHead` / `SelfFlowTap` / `CaptureTap`: Self-Flow's projector, its forward tap (the alignment to the EMA teacher's features) and its
+    backward, and the teacher forward's capture tap; `ArenaModule.teacher_values`: the adapter operands packed from another flat buffer (the EMA shadow);
   * `pad64` / `pad64_empty`: operands of the TN weight-gradient GEMM (contraction granule: 64 rows);
   * `ArenaModule`: every base parameter a view of ONE bf16 arena (two-pass construction), checkpoint load / save over the parameter names;
   * `FullGrads`: the per-backward helper of full-rank training — weight / bias gradients into the gradient arena, the modulation rows' reductions, the fused
@@ -850,6 +852,151 @@ class NextLatTap:
         self.xhat = self.rstd = self.U = self.A = self.psi = None
 
 
+# ------------------------------------------------------------------------------------------------
+# Self-Flow (helpers/training/crepa.py with crepa_feature_source=self_flow): a projector LayerNorm(D, eps 1e-5) -> Linear(D -> D) of one student block's image-token
+# output, aligned by cosine to a deeper block of the EMA teacher's forward on the cleaner view
+# ------------------------------------------------------------------------------------------------
+SELF_FLOW_NAMES = ("0.weight", "0.bias", "1.weight", "1.bias")          # under `crepa_projector.`: the reference's nn.Sequential(LayerNorm, Linear)
+
+
+def self_flow_indices(student_block, teacher_block, n_blocks: int):
+    """validated 0-based (student, teacher) block indices, used as they are (`layer_{i}` of the hidden-state buffer); the two forwards are separate, so neither
+    bounds the other"""
+    if student_block is None:
+        raise ValueError("crepa_block_index must be set when CREPA is enabled.")                                    # crepa.py `attach_to_model`
+    if teacher_block is None:
+        raise ValueError("CREPA self_flow mode requires crepa_teacher_block_index to be set.")                      # common.py `_validate_crepa_configuration`
+    s, t = int(student_block), int(teacher_block)
+    for key, i in (("crepa_block_index", s), ("crepa_teacher_block_index", t)):
+        if not 0 <= i < n_blocks:
+            raise ValueError(f"{key} must be within [0, {n_blocks - 1}], got {i}.")
+    return s, t
+
+
+def self_flow_shapes(D: int):
+    return ((D,), (D,), (D, D), (D,))
+
+
+class SelfFlowHead:
+    """The projector's four trainable tensors as fp32 views at the tail of the adapter arena, their gradient views, the [lo, hi) element range of the gradient arena
+    they span, and the folded bf16 operands the GEMMs read (ops.self_flow_fold, once per training forward)."""
+
+    def __init__(self, block: int, teacher_block: int, D: int, params, grads, flat_lo: int, flat_hi: int, device):
+        self.block, self.teacher_block, self.D = block, teacher_block, D
+        self.gamma, self.beta, self.W, self.b = params
+        self.g_gamma, self.g_beta, self.g_W, self.g_b = grads
+        self.flat_lo, self.flat_hi = flat_lo, flat_hi
+        e = lambda *shp: torch.empty(*shp, dtype=BF16, device=device)
+        self.Wf, self.WfT, self.c = e(D, D), e(D, D), e(D)
+
+    @property
+    def params(self):
+        return (self.gamma, self.beta, self.W, self.b)
+
+    @property
+    def grads(self):
+        return (self.g_gamma, self.g_beta, self.g_W, self.g_b)
+
+    @torch.no_grad()
+    def init_reference(self, generator=None):
+        """crepa.py `attach_to_model`: nn.LayerNorm's (1, 0) and nn.Linear's default — kaiming_uniform(a = sqrt 5) = U(-1 / sqrt D, 1 / sqrt D) for the weight, the same
+        bound for the bias — drawn in fp32, weight first, from the generator given: the adapters' own (seeded by add_lora_adapter's `seed`), behind every A / B draw"""
+        bound = 1.0 / math.sqrt(self.D)
+        self.gamma.fill_(1.0); self.beta.zero_()
+        self.W.uniform_(-bound, bound, generator=generator); self.b.uniform_(-bound, bound, generator=generator)
+
+    def fold(self):
+        ops.self_flow_fold(self.gamma, self.beta, self.W, self.b, self.Wf, self.WfT, self.c)
+
+
+class CaptureTap:
+    """The teacher forward's tap (no-grad, works with save=False): `tap(g, view)` at block `block` leaves a compact bf16 copy of its image-token rows [B, rows, D] in
+    `output`.  `stop`: the forward may end behind that block — nothing else of it is read."""
+
+    key = "crepa_hidden_states"
+    stop = True
+
+    def __init__(self, block: int):
+        self.block, self.output = block, None
+
+    def tap(self, g: int, view):
+        if g == self.block:
+            self.output = torch.empty(view.shape, dtype=BF16, device=view.device)
+            self.output.copy_(view)
+
+    def finish(self, H: int, W: int):
+        if self.output is None:
+            raise ValueError(f"CREPA self_flow mode requested teacher layer {self.block} but the teacher forward did not return hidden states.")      # common.py:5359-5362
+        return self.output
+
+    def backward(self, d, dx_view, accumulate: bool = False, sync=None):
+        raise RuntimeError("CaptureTap: the teacher forward has no backward")
+
+
+class SelfFlowTap:
+    """One per training forward (kept in its ctx).  `tap(g, view)` after the student block of the saving forward — never in the recompute pass of a checkpointed
+    segment — folds the current parameters and runs xhat / rstd (ops.self_flow_rows), proj = xhat Wf^T + c (ops.gemm) and the cosine against the teacher features
+    handed in (ops.layersync_fwd: `sim` = the mean over all B * rows tokens — the reference's mean of per-sample means, every sample having the same token count —
+    and G = d sim / d proj written over proj).  `backward(dsim, dx_view)` right before that block's own backward: P = G^T xhat, db = colsum(G), the four gradient
+    views (ops.self_flow_wgrad; dsim, ONE device scalar, carries -weight and the accumulation division), g = G Wf added through the LayerNorm backward into the
+    gradient with respect to the block's output (ops.nextlat_ln_bwd_add), then the projector's range goes to `sync`.  `cutoff`: the scheduler's weight is 0 — the
+    similarity took no part in the loss: nothing is launched, the gradient views are zeroed."""
+
+    key = "crepa_similarity"
+
+    def __init__(self, head: SelfFlowHead, teacher):
+        self.head, self.block, self.teacher = head, head.block, teacher
+        self.xhat = self.rstd = self.G = self.cos = self.sim = self.output = None
+        self.B = self.rows = 0
+        self.cutoff = False
+
+    def tap(self, g: int, view):
+        if g != self.block:
+            return
+        B, rows, D = view.shape
+        h, dev, t = self.head, view.device, self.teacher
+        if t is None:
+            raise ValueError("CREPA self_flow feature mode requires teacher features from the model.")              # crepa.py `compute_loss`
+        if t.dim() != 3 or tuple(t.shape) != (B, rows, D):
+            raise ValueError(f"CREPA self_flow: teacher features {tuple(t.shape)} do not match the student block's image tokens {(B, rows, D)}")
+        M = B * rows
+        self.B, self.rows = B, rows
+        self.xhat, self.rstd = pad64_empty(M, D, dev), torch.empty(M, dtype=F32, device=dev)
+        self.G = pad64_empty(M, D, dev)
+        self.cos, self.sim = torch.empty(M, dtype=F32, device=dev), torch.empty((), dtype=F32, device=dev)
+        h.fold()
+        ops.self_flow_rows(view, self.xhat, self.rstd)
+        ops.gemm(self.xhat, h.Wf, bias=h.c, out=self.G)                   # the projection, overwritten with G by the cosine pass
+        ops.layersync_fwd(self.G.view(B, rows, D), t.detach(), self.G, self.cos, self.sim)
+        self.teacher = None
+
+    def finish(self, H: int, W: int):
+        if self.sim is None:
+            raise RuntimeError(f"Self-Flow: block {self.block} was never reached by the forward")
+        self.output = self.sim
+        return self.output
+
+    def backward(self, dsim, dx_view, accumulate: bool = False, sync=None):
+        h = self.head
+        if dsim is None or self.cutoff:          # the similarity took no part in the loss
+            if not accumulate:
+                for g in h.grads:
+                    g.zero_()
+        else:
+            M, D, dev = self.B * self.rows, h.D, self.G.device
+            s = dsim.detach().to(device=dev, dtype=F32).reshape(1).contiguous()
+            db = torch.empty(1, D, dtype=F32, device=dev)
+            ops.colsum_prod(self.G, db)
+            ops.self_flow_wgrad(ops.gemm_tn(pad64(self.G), pad64(self.xhat)), db.view(D), h.gamma, h.beta, h.W, s, *h.grads, accumulate=accumulate)
+            if dx_view is not None:
+                g = torch.empty(M, D, dtype=BF16, device=dev)
+                ops.gemm(self.G, h.WfT, out=g)                            # g = G Wf
+                ops.nextlat_ln_bwd_add(g, self.xhat, self.rstd, s, dx_view)
+        if sync is not None:
+            sync.ready(h.flat_lo, h.flat_hi)
+        self.xhat = self.rstd = self.G = None
+
+
 def sincos_2d_hw(embed_dim: int, h: int, w: int, base_size: int, interpolation_scale: float) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed on a (h, w) grid: [h * w, embed_dim] fp32 (first half from the w coordinate, which varies fastest; sin then cos)"""
     gh = (torch.arange(h, dtype=torch.float32) / (h / base_size) / interpolation_scale).double()
@@ -906,7 +1053,7 @@ class ArenaModule(nn.Module):
         """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
         own = dict(self.named_parameters())
         # (an Internal Guidance head / a NextLat predictor is optional in a file: without one it keeps the reference's initial values)
-        missing = [k for k in own if k not in state and ".lora_" not in k and ".lokr_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor."))]
+        missing = [k for k in own if k not in state and ".lora_" not in k and ".lokr_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector."))]
         if missing:
             raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
         own.update(self._extra_state())
@@ -985,6 +1132,33 @@ class ArenaModule(nn.Module):
             yield self
         finally:
             self.enable_lora()
+
+    @contextmanager
+    def teacher_values(self, flat):
+        """Inside: the adapters' GEMM operands (LoraGroup.pack) are built from `flat` — an fp32 buffer laid out like `lora_flat`, e.g. the EMA's `shadow_flat` —
+        instead of the masters: every group's A / B lists point at the same offsets of `flat`, and every forward packs from what they point at.  On exit the lists
+        point at the masters again and the operands are rebuilt from them.  The masters are never written (no store / copy_to / restore round trip).  Standard LoRA
+        groups only: DoRA, LoKr and T-LoRA fold further state into their operands and are refused."""
+        groups = list(getattr(self, "lora_groups", None) or [])
+        if not groups or getattr(self, "lora_flat", None) is None:
+            raise RuntimeError("teacher_values: the component has no adapter arena (add_lora_adapter() first)")
+        if getattr(self, "lora_dora", False) or getattr(self, "lora_lokr", False) or getattr(self, "lora_tlora", None) is not None or not all(type(g) is LoraGroup for g in groups):
+            raise NotImplementedError("teacher_values: only standard LoRA groups pack from a flat buffer (DoRA / LoKr / T-LoRA fold further state) on the st355 path")
+        base = self.lora_flat
+        if flat.dtype != F32 or flat.device != base.device or flat.dim() != 1 or not flat.is_contiguous():
+            raise ValueError("teacher_values: expected a contiguous 1-D fp32 buffer on the adapters' device")
+        view = lambda t: flat[(t.data_ptr() - base.data_ptr()) // 4:][:t.numel()].view(t.shape)
+        if max(g.flat_hi for g in groups) > flat.numel():
+            raise ValueError(f"teacher_values: the buffer holds {flat.numel()} elements, the adapters end at {max(g.flat_hi for g in groups)}")
+        kept = [(g.A, g.B) for g in groups]
+        try:
+            for g in groups:
+                g.A, g.B = [view(t) for t in g.A], [view(t) for t in g.B]
+            yield self
+        finally:
+            for g, (A, B) in zip(groups, kept):
+                g.A, g.B = A, B
+                g.pack()
 
     def _refresh_transposed(self):
         """W^T follows the weights (2 B read + 2 B write per parameter per step: ~12 ms for Flux.1-dev's 12 B parameters, ~1 ms for SD3-Medium)"""

@@ -440,7 +440,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         full fine-tune exposes exactly its arena views; the VAE / ControlNet trunk never carry gradients"""
         if "lora" in str(getattr(self.config, "model_type", "lora")) and self.model is not None:
             for n, p_ in self.unwrap_model(self.model).named_parameters():
-                if ".lora_" not in n and ".lokr_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
+                if ".lora_" not in n and ".lokr_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
                     p_.requires_grad_(False)
         elif str(getattr(self.config, "model_type", "lora")) == "full" and self.model is not None:
             # the reference leaves a full-rank model as diffusers loaded it — every parameter trainable — and `Trainer._get_trainable_parameters` collects
@@ -464,9 +464,14 @@ class ModelFoundation(ExplorativeModelingMixin):
         their setter: LayerSync (`set_layersync`: Flux, SD3), Internal Guidance (`set_internal_guidance`: SD3) and NextLat (`set_nextlat`: SD3).  The REPA family
         needs an external vision encoder and is refused — defined here so that a reference flow calling it never reaches the reference's regulariser initialisers
         through the MRO."""
+        self.self_flow = None
         for flag in ("crepa_enabled", "irepa_enabled", "urepa_enabled"):
             if getattr(self.config, flag, False):
+                if flag == "crepa_enabled" and self._crepa_source() == "self_flow":
+                    continue          # Self-Flow needs nothing outside the model: the EMA copy of the same model is the teacher (`set_self_flow`: SD3)
                 raise NotImplementedError(f"{flag}: the REPA regularisers align with an external vision encoder hooked into diffusers modules and are not built on the st355 path")
+        if getattr(self.config, "crepa_enabled", False):
+            self._self_flow_init()
         self.layersync = None
         if getattr(self.config, "layersync_enabled", False):
             self._layersync_init()
@@ -682,6 +687,87 @@ class ModelFoundation(ExplorativeModelingMixin):
         if p > 0.0 and not self.LORA_DROPOUT_BUILT:
             raise NotImplementedError(f"lora_dropout={p}: LoRA dropout is not built for {self.NAME} on the st355 path (built: SD3); set --lora_dropout=0")
         return p
+
+    def _crepa_source(self) -> str:
+        """crepa.py `CrepaFeatureSource.from_config` (its ValueErrors included); imported only under `crepa_enabled`"""
+        from .self_flow import feature_source
+        return feature_source(self.config)
+
+    SELF_FLOW_BUILT = False             # families whose engine runs the teacher capture and the alignment tap (SD3)
+
+    def _self_flow_init(self):
+        """common.py `_validate_crepa_configuration` + crepa.py `attach_to_model`: the reference's checks with its texts, then what this path does not take, refused
+        by the flag's name; the component was told its blocks when it was built (`set_self_flow`, ahead of the adapter arena)"""
+        from .self_flow import WeightSchedule, mask_ratio, validate
+        cfg = self.config
+        validate(cfg, self.NAME, True)
+        if getattr(cfg, "crepa_block_index", None) is None:
+            raise ValueError("crepa_block_index must be set when CREPA is enabled.")
+        comp = self.get_trained_component()
+        comp = None if comp is None else self.unwrap_model(comp)
+        if not self.SELF_FLOW_BUILT or comp is None or not hasattr(comp, "set_self_flow"):
+            raise NotImplementedError(f"crepa_enabled: Self-Flow (crepa_feature_source=self_flow) is not built for {self.NAME} on the st355 path (built: SD3 LoRA)")
+        no = lambda what: NotImplementedError(f"crepa_enabled (self_flow) {what} is not built on the st355 path")
+        if "lora" not in str(getattr(cfg, "model_type", "lora")):
+            raise no("under a full fine-tune (tokenwise timesteps need per-token modulation gradients)")
+        if str(getattr(cfg, "lora_type", "standard") or "standard").lower() != "standard":
+            raise no("with lora_type=lycoris (LoKr / T-LoRA: the teacher forward packs standard LoRA operands from the EMA shadow; T-LoRA refuses tokenwise timesteps)")
+        if any(getattr(b, "dual", False) for b in getattr(comp, "blocks", ())):
+            raise no("with SD3.5 dual-attention blocks (they refuse tokenwise timesteps)")
+        if getattr(cfg, "use_dora", False):
+            raise no("with use_dora (the DoRA fold does not take the EMA shadow)")
+        if float(getattr(cfg, "lora_dropout", 0.0) or 0.0) > 0.0:
+            raise no(f"with lora_dropout={getattr(cfg, 'lora_dropout')} (the teacher forward is a no-grad forward that does not drop)")
+        for flag, name in (("layersync_enabled", "LayerSync"), ("internal_guidance_enabled", "Internal Guidance"), ("nextlat_enabled", "NextLat")):
+            if getattr(cfg, flag, False):
+                raise no(f"together with {flag} ({name} refuses tokenwise timesteps or claims the same arena tail)")
+        if getattr(cfg, "hip_graph", False):
+            raise NotImplementedError("hip_graph: Self-Flow (crepa_enabled) reads its similarity on the host every step and cannot be captured")
+        tc = getattr(cfg, "tread_config", None)
+        if tc and (tc.get("routes", None) if isinstance(tc, dict) else getattr(tc, "routes", None)):
+            raise no("with TREAD routing (tokenwise timesteps under a route)")
+        if getattr(getattr(self, "xm_config", None), "enabled", False):
+            raise ValueError(f"{self.NAME} XM noise-candidate training is not compatible with CREPA self-flow.")
+        try:
+            ss = float(getattr(cfg, "scheduled_sampling_max_step_offset", 0) or 0) > 0 or bool(getattr(cfg, "scheduled_sampling_reflexflow", False))
+        except Exception:
+            ss = False
+        if ss:
+            raise no("with scheduled sampling / ReflexFlow (scheduled_sampling_max_step_offset, scheduled_sampling_reflexflow: the rollout re-times whole samples)")
+        if getattr(cfg, "distillation_method", None):
+            raise no(f"with distillation_method={getattr(cfg, 'distillation_method')} (Flow-DPO doubles the batch with per-sample timesteps)")
+        if getattr(cfg, "mixflow_enabled", False) is True:
+            raise no("with mixflow_enabled (MixFlow re-draws the per-sample sigmas the views are built from)")
+        if not getattr(comp, "lora_groups", None) or getattr(comp, "_sf", None) is None:
+            # an ordering requirement of this path: the projector lives at the tail of the adapter arena, which add_lora_adapter lays out after load_model told the
+            # component its blocks
+            raise NotImplementedError("crepa_enabled: post_model_load_setup while the component has no adapter arena with the projector yet is not built on the st355 "
+                                      "path — load_model, then add the LoRA adapters, then set Self-Flow up")
+        comp.set_self_flow(cfg.crepa_block_index, cfg.crepa_teacher_block_index)          # (the projector exists: validates, and moves the taps)
+        self.self_flow = SimpleNamespace(block_index=int(cfg.crepa_block_index), teacher_block_index=int(cfg.crepa_teacher_block_index), mask_ratio=mask_ratio(cfg),
+                                         schedule=WeightSchedule(cfg, int(getattr(cfg, "max_train_steps", 0) or 0)), patch_size=int(getattr(comp.config, "patch_size", 2)))
+
+    def _self_flow_views(self, batch: dict, state: dict, lat, noise, sig):
+        """common.py `_prepare_image_crepa_self_flow_batch` on one kernel pass (ops.self_flow_views): a second (sigma, timestep) draw, the token mask's uniforms, then
+        the student's mixed view with its [B, S_img] timesteps and the teacher's cleaner homogeneous view.  Nothing is read on the host."""
+        sf, dev = self.self_flow, lat.device
+        f32 = lambda t: t.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        t0 = f32(batch["timesteps"])
+        alt_s, alt_t = batch.get("crepa_alt_sigmas"), batch.get("crepa_alt_timesteps")          # (tests / parity runs inject the draws, like the noise)
+        if alt_s is None or alt_t is None:
+            alt_s, alt_t = self.sample_flow_sigmas(batch=batch, state=state)
+        B, _, H, W = lat.shape
+        p = sf.patch_size
+        u = batch.get("crepa_self_flow_uniforms")
+        if u is None:
+            u = torch.rand(B, max(H // p, 1), max(W // p, 1), device=dev, dtype=torch.float32)
+        noisy_s, noisy_t, tok, sig_T, t_T, _ = ops.self_flow_views(lat, noise, sig, f32(alt_s), t0, f32(alt_t), u.to(device=dev, dtype=torch.float32).contiguous(),
+                                                                   sf.mask_ratio, p)
+        batch["noisy_latents"], batch["timesteps"] = noisy_s, tok
+        batch["sigmas"] = None          # (the reference leaves the student's [B, 1, H, W] sigma grid here; nothing reads it on this path, so it is not written)
+        batch["crepa_teacher_noisy_latents"], batch["crepa_teacher_timesteps"], batch["crepa_teacher_sigmas"] = noisy_t, t_T, sig_T
+        batch["crepa_global_step"] = int(state.get("global_step", 0))
+        return batch
 
     def _nextlat_init(self):
         """common.py:5197-5220 `_init_nextlat_regularizer` + nextlat.py:95-116: the configuration checks in the reference's order and with its texts, then the
@@ -902,6 +988,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         sd = {n.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.").replace(self.DORA_KEY + ".default.", self.DORA_KEY + "."): p for n, p in src}
         sd.update(self._internal_guidance_head_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         sd.update(self._nextlat_predictor_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
+        sd.update(self._self_flow_projector_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         return sd
 
     DORA_KEY = ".lora_magnitude_vector"            # peft's DoraLinearLayer parameter, per adapted module
@@ -938,6 +1025,19 @@ class ModelFoundation(ExplorativeModelingMixin):
 
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = None     # common.py:524; Flux / SD3 / PixArt keep their `transformer.` prefix in ComfyUI files
     AUTO_LORA_FORMAT_DETECTION = False                  # flux/model.py:56: a diffusers-configured run still recognises a ComfyUI file on load
+
+    SELF_FLOW_PREFIX = "crepa_projector."          # crepa.py `attach_to_model`: setattr(model, "crepa_projector", nn.Sequential(LayerNorm, Linear)); under `transformer.` in a file
+
+    @staticmethod
+    def _self_flow_projector_state(comp, dtype) -> dict:
+        """Self-Flow's projector as the reference saves it with the adapter (common.py:924-937 `get_lora_save_layers` names `crepa_projector` among the
+        `modules_to_save`; here: the nn.Sequential's state dict under `crepa_projector.`, the route of the two heads above): `0.weight`, `0.bias`, `1.weight`,
+        `1.bias` in the dtype the adapter tensors are saved in.  Empty when the component trains no projector."""
+        from .engine import SELF_FLOW_NAMES
+        if getattr(comp, "_sf", None) is None or not getattr(comp, "lora_groups", None):
+            return {}
+        own = dict(comp.named_parameters())
+        return {ModelFoundation.SELF_FLOW_PREFIX + nm: own[ModelFoundation.SELF_FLOW_PREFIX + nm].detach().to(dtype) for nm in SELF_FLOW_NAMES}
 
     def _lora_adapter_metadata(self) -> dict:
         """what peft records for the adapter (LoraConfig r / lora_alpha): alpha defaults to the rank (common.py:1049-1128)"""
@@ -999,7 +1099,7 @@ class ModelFoundation(ExplorativeModelingMixin):
             raise NotImplementedError("use_dora: the ComfyUI export of a DoRA adapter (its magnitude vectors) is not built on the st355 path; save with "
                                       "--lora_format=diffusers")
         if fmt == PEFTLoRAFormat.COMFYUI and not getattr(self, "NATIVE_COMFYUI_LORA_SUPPORT", False):
-            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k}
+            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k and self.SELF_FLOW_PREFIX not in k}
             flat = self._convert_lora_state_dict_to_comfyui(flat, adapter_metadata=meta or self._lora_adapter_metadata(), component_adapter_metadata=comp_meta)
             flat = {k: v.contiguous() for k, v in flat.items()}
         os.makedirs(output_dir, exist_ok=True)
@@ -1181,17 +1281,20 @@ class ModelFoundation(ExplorativeModelingMixin):
         # an Internal Guidance head / a NextLat predictor travels with the adapter (diffusers-format files): read back strictly — every tensor of it when one is
         # configured, and a file that carries one needs a component that has one
         for pre, attr, a, name, flag, key in ((self.IG_PREFIX, "_ig", "an", "Internal Guidance head", "internal_guidance_enabled", "internal_guidance_block_index"),
-                                              (self.NEXTLAT_PREFIX, "_nl", "a", "NextLat predictor", "nextlat_enabled", "nextlat_block_index")):
+                                              (self.NEXTLAT_PREFIX, "_nl", "a", "NextLat predictor", "nextlat_enabled", "nextlat_block_index"),
+                                              (self.SELF_FLOW_PREFIX, "_sf", "a", "Self-Flow projector", "crepa_enabled", None)):
             in_file = sorted(k for k in flat if pre in k)
             head = getattr(comp, attr, None)
             if in_file and (head is None or not getattr(comp, "lora_groups", None)):
                 raise ValueError(f"LoRA checkpoint carries {a} {name} ({in_file[0]}, ...) but none is configured: set {flag} (and the "
-                                 f"file's {key}) before loading it")
+                                 f"file's {key or 'crepa_block_index'}) before loading it")
             if head is not None and getattr(comp, "lora_groups", None) and fmt != PEFTLoRAFormat.DIFFUSERS:
                 raise ValueError(f"a ComfyUI-format LoRA file cannot carry the {name} (the export drops it): load the diffusers-format file, or turn "
                                  f"{flag} off to load the adapters alone")
             if head is not None and getattr(comp, "lora_groups", None):
                 own.update({n: p for n, p in comp.named_parameters() if n.startswith(pre)})
+                if key is None:          # (the reference's nn.Sequential projector carries no block index)
+                    continue
                 bi = flat.get(prefix + pre + "block_index")
                 if bi is None:
                     raise KeyError(f"LoRA checkpoint is missing the {name}'s block index ({prefix}{pre}block_index)")
@@ -1502,7 +1605,10 @@ class ModelFoundation(ExplorativeModelingMixin):
             batch["input_noise"] = input_noise
             batch["noisy_latents"] = noisy
             batch["flow_target"] = target      # n - x (common.py:4610-4611), consumed by get_prediction_target
-            self.expand_sigmas(batch)
+            if getattr(self, "self_flow", None) is not None and torch.is_grad_enabled():          # Self-Flow (common.py:5974-5976); evaluation batches stay homogeneous
+                self._self_flow_views(batch, state, lat, input_noise, sig)
+            else:
+                self.expand_sigmas(batch)
         else:
             # DDPM families (common.py:5983-6002): discrete timesteps (segmented selection when bsz > 1, custom_schedule.py:18-58), noise =
             # randn_like(latents) (or injected), x_t = sqrt(acp_t) x + sqrt(1 - acp_t) n in fp32 then cast (DDPMScheduler.add_noise)
@@ -1758,6 +1864,23 @@ class ModelFoundation(ExplorativeModelingMixin):
             nl_loss = state * nl.weight
             loss = loss + nl_loss
             logs.update(nextlat_loss=nl_loss.detach().item(), nextlat_state_loss=state.detach().item())
+        sf = getattr(self, "self_flow", None)
+        if sf is not None and isinstance(model_output, dict) and (model_output.get("crepa_similarity") is not None or torch.is_grad_enabled()):
+            # common.py:6850-6881 / crepa.py `compute_loss` (self_flow, image mode: one frame, so the alignment score IS the self similarity): -w * sim with w from
+            # the scheduler on this step's similarity — ONE host read; w == 0 (cutoff) adds nothing to the loss and switches the tap's backward off
+            sim = model_output.get("crepa_similarity")
+            if sim is None:
+                raise ValueError("CREPA is enabled but no intermediate hidden states were provided.")
+            score = sim.detach().item()
+            w = sf.schedule.weight(int(prepared_batch.get("crepa_global_step", 0)), similarity=score)
+            if w == 0:
+                self.unwrap_model(self.get_trained_component()).self_flow_cutoff()
+                logs.update(crepa_loss=0.0, crepa_alignment_score=score, crepa_similarity_self=score, crepa_weight=0.0, crepa_cutoff=True)
+            else:
+                loss = loss + (-sim * w)
+                logs.update(crepa_loss=-score * w, crepa_alignment_score=score, crepa_similarity_self=score, crepa_weight=w, crepa_cutoff=False)
+            if sf.schedule.ema is not None:
+                logs["crepa_alignment_score_ema"] = sf.schedule.ema
         ls = getattr(self, "layersync", None)
         if ls is not None:
             sim = model_output.get("layersync_similarity") if isinstance(model_output, dict) else None

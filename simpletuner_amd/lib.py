@@ -41,6 +41,7 @@ SYMBOLS = [
     "st355_flow_dpo_workspace", "st355_flow_dpo_stats", "st355_flow_dpo_head", "st355_flow_dpo_grad",
     "st355_diff2flow_workspace", "st355_diff2flow_loss",
     "st355_tlora_mask",
+    "st355_self_flow_views", "st355_self_flow_fold", "st355_self_flow_rows", "st355_self_flow_wgrad_workspace", "st355_self_flow_wgrad",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
     # UNet path (SDXL / SD1.5)
@@ -422,6 +423,11 @@ def _declare(lib):
         "st355_diff2flow_workspace": (i64, [i64, i64]),
         "st355_diff2flow_loss": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i64, i64, f32]),
         "st355_tlora_mask": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, vp, i32]),
+        "st355_self_flow_views": (C.c_int, [vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
+        "st355_self_flow_fold": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+        "st355_self_flow_rows": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
+        "st355_self_flow_wgrad_workspace": (i64, [i32]),
+        "st355_self_flow_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),
         "st355_comm_init": (C.c_int, [vp, vp, i32, i32]),

@@ -2097,6 +2097,132 @@ def nextlat_wgrad_down(P2, db2, scale, g_W, g_b, accumulate: bool = False):
     return g_W, g_b
 
 
+def _sf_vec(t, name: str):
+    """a [B] fp32 device vector of Self-Flow's views pass"""
+    _chk(t, F32, name)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise _l.St355Error(f"self_flow_views: {name} must be a contiguous [B] fp32 tensor, got {tuple(t.shape)}")
+
+
+def self_flow_views(latents, noise, sigma, sigma_alt, timesteps, timesteps_alt, uniforms, ratio: float, patch: int = 2, want_sigma_grid: bool = False, out=None):
+    """Self-Flow's two views in ONE streaming pass (st355_self_flow_views; common.py `_prepare_image_crepa_self_flow_batch`): latents / noise [B, C, H, W], both bf16 or
+    both fp32 (each sample contiguous; the batch stride may be larger), sigma / sigma_alt / timesteps / timesteps_alt [B] fp32 and uniforms [B, H/p, W/p] fp32 on the
+    device.  A token is masked iff its uniform < ratio.  Returns (noisy_student, noisy_teacher, token_timesteps [B, (H/p)(W/p)] fp32, sigma_teacher [B] fp32,
+    timestep_teacher [B] fp32, sigma_grid [B, 1, H, W] fp32 or None).  fp32 arithmetic, one rounding per output element, nothing read on the host.  out: the first
+    five outputs preallocated (contiguous, 16-byte aligned views), else they are allocated here."""
+    L = _l.load()
+    if latents.dtype not in (BF16, F32) or noise.dtype != latents.dtype:
+        raise _l.St355Error(f"self_flow_views: latents and noise must share one dtype, bf16 or fp32 (got {latents.dtype}, {noise.dtype})")
+    _dev(latents, "latents"); _dev(noise, "noise")
+    if latents.dim() != 4 or noise.shape != latents.shape:
+        raise _l.St355Error(f"self_flow_views: expected latents and noise [B, C, H, W] of one shape, got {tuple(latents.shape)} and {tuple(noise.shape)}")
+    B, Cc, H, W = latents.shape
+    patch = int(patch)
+    if patch < 1 or H % patch or W % patch:
+        raise _l.St355Error(f"self_flow_views: H % patch_size != 0 or W % patch_size != 0 (H = {H}, W = {W}, patch_size = {patch}): the reference's repeat_interleave "
+                            "and slice are not a defined computation there")
+    if not 0.0 <= float(ratio) <= 0.5:
+        raise _l.St355Error(f"self_flow_views: the mask ratio must lie in [0, 0.5] (got {ratio})")
+    for t, nm in ((latents, "latents"), (noise, "noise")):
+        if not t[0].is_contiguous() or (B > 1 and t.stride(0) < Cc * H * W):
+            raise _l.St355Error(f"self_flow_views: every sample of {nm} must be contiguous, samples at least C * H * W elements apart (strides {t.stride()})")
+    for t, nm in ((sigma, "sigma"), (sigma_alt, "sigma_alt"), (timesteps, "timesteps"), (timesteps_alt, "timesteps_alt")):
+        _sf_vec(t, nm)
+        if t.numel() != B:
+            raise _l.St355Error(f"self_flow_views: {nm} has {t.numel()} entries for a batch of {B}")
+    _chk(uniforms, F32, "uniforms")
+    if tuple(uniforms.shape) != (B, H // patch, W // patch) or not uniforms.is_contiguous():
+        raise _l.St355Error(f"self_flow_views: expected contiguous uniforms [{B}, {H // patch}, {W // patch}], got {tuple(uniforms.shape)}")
+    vec = 8 if latents.dtype == BF16 else 4
+    lbs, nbs = (latents.stride(0), noise.stride(0)) if B > 1 else (Cc * H * W, Cc * H * W)
+    if (Cc * H * W) % vec or lbs % vec or nbs % vec:
+        raise _l.St355Error(f"self_flow_views: C * H * W and the batch strides must be multiples of {vec} elements (16 bytes per lane), got {Cc * H * W}, {lbs}, {nbs}")
+    _al16("self_flow_views", latents, noise)
+    dev = latents.device
+    ntok = (H // patch) * (W // patch)
+    if out is None:
+        noisy_s, noisy_t = torch.empty(B, Cc, H, W, dtype=latents.dtype, device=dev), torch.empty(B, Cc, H, W, dtype=latents.dtype, device=dev)
+        tok = torch.empty(B, ntok, dtype=F32, device=dev)
+        sig_T, t_T = torch.empty(B, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev)
+    else:
+        noisy_s, noisy_t, tok, sig_T, t_T = out
+        for t, shp, dt in ((noisy_s, (B, Cc, H, W), latents.dtype), (noisy_t, (B, Cc, H, W), latents.dtype), (tok, (B, ntok), F32), (sig_T, (B,), F32), (t_T, (B,), F32)):
+            _chk(t, dt, "out")
+            if tuple(t.shape) != shp or not t.is_contiguous():
+                raise _l.St355Error(f"self_flow_views: expected a contiguous output of shape {shp}, got {tuple(t.shape)} (strides {t.stride()})")
+        _al16("self_flow_views", noisy_s, noisy_t)
+    grid = torch.empty(B, 1, H, W, dtype=F32, device=dev) if want_sigma_grid else None
+    _l.check(L.st355_self_flow_views(_stream(), _ptr(latents), _ptr(noise), int(latents.dtype == BF16), lbs, nbs, _ptr(sigma), _ptr(sigma_alt), _ptr(timesteps),
+                                     _ptr(timesteps_alt), _ptr(uniforms), float(ratio), patch, _ptr(noisy_s), _ptr(noisy_t), _ptr(tok), _ptr(sig_T), _ptr(t_T), _ptr(grid),
+                                     B, Cc, H, W), "self_flow_views")
+    return noisy_s, noisy_t, tok, sig_T, t_T, grid
+
+
+def _sf_params(name: str, gamma, beta, W, b):
+    """the projector's four fp32 parameters (or their gradients): contiguous, 16-byte aligned, W [D, D].  Returns D"""
+    ts = (gamma, beta, W, b)
+    for t in ts:
+        _chk(t, F32, name)
+    if W.dim() != 2 or W.shape[0] != W.shape[1]:
+        raise _l.St355Error(f"{name}: expected W [D, D], got {tuple(W.shape)}")
+    D = W.shape[1]
+    if D % 8 or D > 4096:
+        raise _l.St355Error(f"{name}: D must be a multiple of 8, at most 4096 (got {D})")
+    if any(t.numel() != D for t in (gamma, beta, b)) or not all(t.is_contiguous() for t in ts):
+        raise _l.St355Error(f"{name}: expected contiguous gamma [D], beta [D], W [D, D], b [D] with D = {D}")
+    _al16(name, gamma, beta, W)
+    return D
+
+
+def self_flow_fold(gamma, beta, W, b, Wf, WfT, c):
+    """Self-Flow projector (st355_self_flow_fold): Wf [D, D] = bf16(gamma * W), WfT its transpose, c [D] = bf16(W beta + b) — the operands of the projection
+    proj = xhat Wf^T + c and of the backward's g = G Wf, from the current fp32 parameters.  Writes into the tensors given."""
+    L = _l.load()
+    D = _sf_params("self_flow_fold", gamma, beta, W, b)
+    for t, nm in ((Wf, "Wf"), (WfT, "WfT"), (c, "c")):
+        _chk(t, BF16, nm)
+    if tuple(Wf.shape) != (D, D) or tuple(WfT.shape) != (D, D) or c.numel() != D or not (Wf.is_contiguous() and WfT.is_contiguous() and c.is_contiguous()):
+        raise _l.St355Error(f"self_flow_fold: expected contiguous Wf [D, D], WfT [D, D], c [D] with D = {D}")
+    _al16("self_flow_fold", Wf, WfT)
+    _l.check(L.st355_self_flow_fold(_stream(), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b), _ptr(Wf), _ptr(WfT), _ptr(c), D), "self_flow_fold")
+    return Wf, WfT, c
+
+
+def self_flow_rows(h, xhat, rstd):
+    """the projector's row pass (st355_self_flow_rows): h a [B, rows, D] bf16 view (read once, no compact copy) -> xhat [B * rows, D] compact bf16 = LN(h) without
+    affine (centred variance, nn.LayerNorm's default eps 1e-5), rstd [B * rows] fp32.  D % 64 == 0: xhat feeds the projection's GEMM."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(h, "h")
+    _chk(xhat, BF16, "xhat"); _chk(rstd, F32, "rstd")
+    M = B * rows
+    if D % 64:
+        raise _l.St355Error(f"self_flow_rows: D must be a multiple of 64, the contraction granule of the projection's GEMM (got {D}; the row kernel itself takes D % 8 == 0)")
+    if D > 4096 or ld % 8 or bs % 8:
+        raise _l.St355Error(f"self_flow_rows: the view's strides must be multiples of 8 elements, D at most 4096 (got D = {D}, strides {h.stride()})")
+    if tuple(xhat.shape) != (M, D) or not xhat.is_contiguous() or rstd.numel() != M or not rstd.is_contiguous():
+        raise _l.St355Error(f"self_flow_rows: expected contiguous xhat [{M}, {D}], rstd [{M}]")
+    _al16("self_flow_rows", h, xhat)
+    _l.check(L.st355_self_flow_rows(_stream(), _ptr(h), _ptr(xhat), _ptr(rstd), B, rows, D, ld, bs), "self_flow_rows")
+    return xhat, rstd
+
+
+def self_flow_wgrad(P, db, gamma, beta, W, scale, g_gamma, g_beta, g_W, g_b, accumulate: bool = False):
+    """gradients of the projector (st355_self_flow_wgrad) from P [D, D] bf16 = G^T xhat (gemm_tn) and db [D] fp32 = colsum(G): g_W = s (P * gamma + db beta^T),
+    g_b = s db, g_gamma = s sum_n W * P, g_beta = s sum_n W * db; s ONE fp32 on the device.  accumulate adds to what the gradients hold."""
+    L = _l.load()
+    D = _sf_params("self_flow_wgrad", gamma, beta, W, g_b)
+    _sf_params("self_flow_wgrad", g_gamma, g_beta, g_W, g_b)
+    _chk(P, BF16, "P"); _chk(db, F32, "db")
+    _nextlat_scale("self_flow_wgrad", scale)
+    if tuple(P.shape) != (D, D) or db.numel() != D or tuple(g_W.shape) != (D, D) or not (P.is_contiguous() and db.is_contiguous()):
+        raise _l.St355Error(f"self_flow_wgrad: expected contiguous P [D, D] bf16, db [D] fp32 and gradients in the projector's shapes with D = {D}")
+    _al16("self_flow_wgrad", P)
+    ws = _scratch("self_flow_wgrad", P.device, L.st355_self_flow_wgrad_workspace(D))
+    _l.check(L.st355_self_flow_wgrad(_stream(), _ptr(P), _ptr(db), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(scale), _ptr(g_gamma), _ptr(g_beta), _ptr(g_W), _ptr(g_b), D,
+                                     1 if accumulate else 0, _ptr(ws)), "self_flow_wgrad")
+    return g_gamma, g_beta, g_W, g_b
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

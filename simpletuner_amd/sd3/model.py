@@ -24,6 +24,7 @@ class SD3(ModelFoundation):
     LORA_DROPOUT_BUILT = True
     DORA_BUILT = True
     LYCORIS_BUILT = True
+    SELF_FLOW_BUILT = True
     ROLLOUT_BATCH_KEYS = ("encoder_hidden_states", "add_text_embeds")          # what _model_predict_single reads per sample (scheduled sampling's batch-1 forwards)
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
@@ -42,6 +43,11 @@ class SD3(ModelFoundation):
             # NextLat: the predictor is laid out with the component's arenas; the constructor applies the reference's index rule (None / 0 / negative = last block)
             arch = dict(arch, nextlat_block_index=getattr(self.config, "nextlat_block_index", None) or -1)
         self.model = SD3Transformer2DModel(device=self.accelerator.device, **arch)
+        if getattr(self.config, "crepa_enabled", False) and not getattr(self.config, "irepa_enabled", False) and self._crepa_source() == "self_flow" \
+                and "lora" in str(getattr(self.config, "model_type", "lora")):
+            # Self-Flow: the projector goes to the tail of the adapter arena, so the component learns its blocks ahead of add_lora_adapter (post_model_load_setup
+            # repeats the checks in the reference's order and refuses what this path does not take)
+            self.model.set_self_flow(getattr(self.config, "crepa_block_index", None), getattr(self.config, "crepa_teacher_block_index", None))
         if state_dict is not None:
             self.model.load_flat_state(state_dict)
         else:
@@ -90,6 +96,9 @@ class SD3(ModelFoundation):
         """sd3/model.py:540-570"""
         self._require_per_sample_timesteps(prepared_batch, tokenwise_ok=True)      # [B] or tokenwise [B, S_img], handed through unchanged (sd3/model.py:542)
         dev = self.accelerator.device
+        extra = {}
+        if getattr(self, "self_flow", None) is not None and torch.is_grad_enabled() and prepared_batch.get("crepa_teacher_noisy_latents") is not None:
+            extra["crepa_teacher_features"] = self._self_flow_teacher_features(prepared_batch)          # the teacher forward first, then the training forward with the tap
         res = self.model(
             hidden_states=prepared_batch["noisy_latents"].to(device=dev, dtype=BF16),
             timestep=prepared_batch["timesteps"].to(device=dev, dtype=torch.float32),
@@ -97,13 +106,35 @@ class SD3(ModelFoundation):
             pooled_projections=prepared_batch["add_text_embeds"].to(device=dev, dtype=BF16),
             return_dict=True,
             **({"return_internal_guidance": True} if prepared_batch.get("return_internal_guidance") else {}),          # sampling with validation_internal_guidance_scale != 1
+            **extra,
         )
         # further outputs travel by name; (a component that hands back a plain tuple has only its sample)
         out = {"model_prediction": res[0] if isinstance(res, tuple) else res.sample, "crepa_hidden_states": None, "hidden_states_buffer": None}
-        for k in ("layersync_similarity", "internal_guidance_prediction", "nextlat_state_loss"):          # LayerSync / Internal Guidance / NextLat: the training forward's further outputs
+        for k in ("layersync_similarity", "internal_guidance_prediction", "nextlat_state_loss", "crepa_similarity"):          # LayerSync / Internal Guidance / NextLat / Self-Flow: the training forward's further outputs
             if getattr(res, k, None) is not None:
                 out[k] = getattr(res, k)
         return out
+
+
+    def _self_flow_teacher_features(self, prepared_batch: dict):
+        """common.py `_run_crepa_teacher_forward`: the EMA teacher's forward on the cleaner homogeneous view — no grad, the adapter operands packed from the EMA's
+        flat shadow (ArenaModule.teacher_values: the masters are never written, unlike the reference's store / copy_to / restore), the image rows of block
+        `crepa_teacher_block_index` copied out; the forward ends behind that block."""
+        ema = getattr(self, "ema_model", None)
+        if ema is None or not getattr(self.config, "use_ema", False):
+            raise ValueError("EMA teacher weights are required but unavailable; enable use_ema or allow fallback.")          # common.py:5294-5295
+        shadow = getattr(ema, "shadow_flat", None)
+        if shadow is None:
+            raise NotImplementedError("crepa_enabled (self_flow): the EMA shadow is not one flat buffer over the adapter arena; not built on the st355 path")
+        dev = self.accelerator.device
+        comp = self.unwrap_model(self.model)
+        with torch.no_grad(), comp.teacher_values(shadow):
+            res = comp(hidden_states=prepared_batch["crepa_teacher_noisy_latents"].to(device=dev, dtype=BF16),
+                       timestep=prepared_batch["crepa_teacher_timesteps"].to(device=dev, dtype=torch.float32),
+                       encoder_hidden_states=prepared_batch["encoder_hidden_states"].to(device=dev, dtype=BF16),
+                       pooled_projections=prepared_batch["add_text_embeds"].to(device=dev, dtype=BF16), return_dict=True,
+                       crepa_capture_block_index=self.self_flow.teacher_block_index)
+        return res.crepa_hidden_states
 
 
 ModelRegistry.register("sd3", SD3)

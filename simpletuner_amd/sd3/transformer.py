@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, AdapterArena, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, SELF_FLOW_NAMES, AdapterArena, CaptureTap, SelfFlowHead, SelfFlowTap, self_flow_indices, self_flow_shapes, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
                       NextLatTap, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
                       lora_fwd_kw, lora_grads, lora_pairs, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
@@ -126,6 +126,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self.gradient_checkpointing_segment_stride = None
         self._tread_router, self._tread_routes = None, None
         self._layersync = None           # set_layersync(): 0-based (student, teacher) joint-block indices
+        # Self-Flow (set_self_flow): the 0-based student / teacher blocks, the projector at the tail of the adapter arena, the teacher features of the next training forward
+        self._sf_block, self._sf_teacher_block, self._sf, self._sf_feats, self._sf_tap = None, None, None, None, None
         self.grad_sync = None
         self._last_grad_flat = None
         self.full = False
@@ -320,6 +322,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ig = [arena.add("internal_guidance_head." + nm, shp) for nm, shp in zip(IG_NAMES, internal_guidance_shapes(D))] if self._ig_block is not None else []
         nl = [arena.add("nextlat_predictor." + nm, shp, align=1 if k else 8) for k, (nm, shp) in enumerate(zip(NEXTLAT_NAMES, nextlat_shapes(D)))] \
             if self._nl_block is not None else []
+        # Self-Flow: the projector's fp32 masters likewise (it excludes the two heads above), from a 16-byte boundary
+        sf = [arena.add("crepa_projector." + nm, shp, align=1 if k else 8) for k, (nm, shp) in enumerate(zip(SELF_FLOW_NAMES, self_flow_shapes(D)))] \
+            if self._sf_block is not None else []
+        if sf and dora:
+            raise NotImplementedError("crepa_enabled (self_flow) with use_dora: the teacher forward packs the adapters from the EMA shadow, which the DoRA fold does not "
+                                      "take; not built on the st355 path")
         gen = arena.build(seed)
         draw(gen)
         for g, lin, ms in zip(self.lora_groups, group_lins, mags):
@@ -340,6 +348,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     s.p.copy_(src)               # a predictor that came with the loaded weights
             else:
                 self._nl.init_reference(gen)         # the reference's initial values, drawn in fp32 from the adapters' generator
+        if sf:
+            self._sf = SelfFlowHead(self._sf_block, self._sf_teacher_block, D, [s.p for s in sf], [s.g for s in sf], sf[0].lo, sf[-1].hi, dev)
+            self._sf.init_reference(gen)             # nn.LayerNorm / nn.Linear defaults, drawn in fp32 from the adapters' generator behind every A / B draw
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
@@ -358,8 +369,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for k in factors:
             if k not in self.LOKR_CLASSES:
                 raise NotImplementedError(f"lycoris lokr: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
-        if self._ig_block is not None or self._nl_block is not None:
-            raise NotImplementedError("lycoris lokr with an Internal Guidance head / a NextLat predictor is not built on the st355 path")
+        if self._ig_block is not None or self._nl_block is not None or self._sf_block is not None:
+            raise NotImplementedError("lycoris lokr with an Internal Guidance head / a NextLat predictor / a Self-Flow projector is not built on the st355 path")
         dev = self.device_
         self.lora_groups, self.lora_dropout, self.lora_dora, self.lora_lokr = [], None, False, True
         self.lokr_multiplier = float(multiplier)
@@ -429,8 +440,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for k in classes:
             if k not in self.LOKR_CLASSES:
                 raise NotImplementedError(f"lycoris tlora: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
-        if self._ig_block is not None or self._nl_block is not None:
-            raise NotImplementedError("lycoris tlora with an Internal Guidance head / a NextLat predictor is not built on the st355 path")
+        if self._ig_block is not None or self._nl_block is not None or self._sf_block is not None:
+            raise NotImplementedError("lycoris tlora with an Internal Guidance head / a NextLat predictor / a Self-Flow projector is not built on the st355 path")
         rank, a, mult = int(linear_dim), int(linear_alpha), int(multiplier)
         if not 1 <= rank <= self.TLORA_MAX_DIM:
             raise NotImplementedError(f"lycoris_config linear_dim={rank}: the rank-space kernels of the st355 path take 1 <= linear_dim <= {self.TLORA_MAX_DIM}; set "
@@ -1010,7 +1021,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             d_txt, _ = ops.ln_modulate_bwd_stats(dn_t, sv.txt, mt[:, D:2 * D], St, dmt[:, :D], dmt[:, D:2 * D], dres=dx1_t)
         return d_img, d_txt
 
-    def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False, want_ig: bool = False):
+    def _engine_forward(self, latents, enc, pooled, timestep, save: bool, full: bool = False, want_ig: bool = False, capture: Optional[int] = None):
         D, H, hd = self.D, self.H, self.hd
         B, C, Hh, Ww = latents.shape
         h, w = Hh // 2, Ww // 2
@@ -1102,10 +1113,11 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             from ..training.checkpoint_plan import per_block as _per_block
             ctx.segs = _per_block(len(self.blocks), bool(self.gradient_checkpointing), self.gradient_checkpointing_interval, self.gradient_checkpointing_segment_stride)
         ctx.envs, ctx.route_start, ctx.route_end = [env] * len(self.blocks), {}, {}
-        ctx.taps = self._make_taps(save, want_ig, tokenwise)
+        ctx.taps = self._make_taps(save, want_ig, tokenwise, capture)
         rp, info, saved, env_cur = 0, None, None, env
+        last = capture if capture is not None else len(self.blocks) - 1          # a capture forward (Self-Flow's teacher) ends behind the captured block
         for (s0, n, ck) in ctx.segs:
-            for bi in range(s0, s0 + n):
+            for bi in range(s0, min(s0 + n, last + 1)):
                 if rp < len(routes) and info is None and bi == routes[rp]["start_layer_idx"]:
                     info = self._tread_router.get_mask(img.view(B, Si, D), mask_ratio=routes[rp]["selection_ratio"], force_keep=getattr(self, "_force_keep_mask", None))
                     saved = img
@@ -1126,6 +1138,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
                     info, saved, env_cur, rp = None, None, env, rp + 1
         if info is not None:
             raise ValueError("TREAD route does not end inside the block stack (end_layer_idx)")
+        if capture is not None:
+            for tap in ctx.taps:
+                tap.finish(Hh, Ww)
+            return None, ctx
         # ---- output head: AdaLayerNormContinuous (scale, shift), proj_out, unpatchify "nhwpqc->nchpwq" ----
         mo = mod_i[:, self.mod_off_out:self.mod_off_out + 2 * D]
         n_out = ops.ln_modulate_fwd(img, mo[:, :D], mo[:, D:2 * D], rpb_i)
@@ -1138,10 +1154,14 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             tap.finish(Hh, Ww)
         return ops.unpatchify(out.view(B, Si, -1), self.out_channels, Hh, Ww, order=1), ctx
 
-    def _make_taps(self, save: bool, want_ig: bool, tokenwise: bool) -> list:
+    def _make_taps(self, save: bool, want_ig: bool, tokenwise: bool, capture: Optional[int] = None) -> list:
         """the per-forward taps of the configured regularisers, in their launch order: LayerSync, Internal Guidance, NextLat (engine.py: `tap` after every block of
         the saving forward, `finish` after the output head, `backward` right before the backward of block `tap.block`; `key` names the extra output)"""
         taps, routed = [], self._tread_router is not None
+        if capture is not None:                    # Self-Flow's teacher forward: no-grad, nothing kept, one block's image rows copied out
+            if save or not 0 <= int(capture) < len(self.blocks):
+                raise ValueError(f"crepa_capture_block_index must name a block in [0, {len(self.blocks) - 1}] of a no-grad forward, got {capture}")
+            return [CaptureTap(int(capture))]
         if save and self._layersync is not None:
             if routed:
                 raise NotImplementedError("LayerSync under TREAD routing (the student and the teacher block would see different token subsets) is not built on the st355 path")
@@ -1158,7 +1178,41 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if routed:
                 raise NotImplementedError("NextLat under TREAD routing (the routed block's token rows are no longer neighbours in the sequence) is not built on the st355 path")
             taps.append(NextLatTap(self._nl_head(), self._nl_mode))
+        if self._sf_block is not None and save:
+            if routed:
+                raise NotImplementedError("crepa_enabled (self_flow) under TREAD routing (the student's routed block and the teacher's would see different token subsets) is "
+                                          "not built on the st355 path")
+            if self._sf is None:
+                raise RuntimeError("Self-Flow: no projector is laid out for training (add_lora_adapter() after set_self_flow())")
+            self._sf_tap = SelfFlowTap(self._sf, self._sf_feats)
+            self._sf_feats = None
+            taps.append(self._sf_tap)
         return taps
+
+    def set_self_flow(self, student_block, teacher_block):
+        """Self-Flow (CREPA with crepa_feature_source=self_flow; the reference captures `layer_{i}` at sd3/transformer.py:872): the 0-based joint block whose
+        image-stream output feeds the projector LayerNorm -> Linear(D -> D), and the block of the EMA teacher's forward it is aligned to.  Call it before
+        `add_lora_adapter` (the projector's fp32 masters go to the tail of the adapter arena).  A training forward then takes `crepa_teacher_features` — what a no-grad
+        forward with `crepa_capture_block_index=teacher_block` inside `teacher_values(shadow)` returned as `crepa_hidden_states` — and also returns the mean cosine
+        `crepa_similarity`; the backward takes its gradient at the student block.  LoRA only: a full fine-tune refuses tokenwise timesteps."""
+        s_, t_ = self_flow_indices(student_block, teacher_block, len(self.blocks))
+        if self._ig_block is not None or self._nl_block is not None or self._layersync is not None:
+            raise NotImplementedError("crepa_enabled (self_flow) together with LayerSync / Internal Guidance / NextLat is not built on the st355 path (they refuse tokenwise "
+                                      "timesteps or claim the same arena tail)")
+        if self.full or any(b.dual for b in self.blocks):
+            raise NotImplementedError("crepa_enabled (self_flow) needs tokenwise timesteps, which a full fine-tune and the SD3.5 dual-attention blocks refuse on the st355 path")
+        if self._sf is not None:
+            self._sf_block, self._sf_teacher_block = s_, t_           # the projector exists: only the taps move
+            self._sf.block, self._sf.teacher_block = s_, t_
+            return
+        if self.lora_groups:
+            raise RuntimeError("set_self_flow: the trainable arena is already laid out without the projector — call it before add_lora_adapter()")
+        self._sf_block, self._sf_teacher_block = s_, t_
+
+    def self_flow_cutoff(self):
+        """the scheduler's weight of the forward just run is 0: its similarity takes no part in the loss, so the tap's backward launches nothing"""
+        if self._sf_tap is not None:
+            self._sf_tap.cutoff = True
 
     def set_internal_guidance(self, block_index):
         """Internal Guidance (helpers/training/internal_guidance.py; the reference captures `layer_{i}` at sd3/transformer.py:872): the 0-based joint block whose
@@ -1166,6 +1220,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         adapter arena); a full fine-tune needs the constructor's `internal_guidance_block_index` (the head lives inside the base parameter arena, laid out once).
         A training forward then also returns the head's [B, 16, H, W] prediction and the backward takes its gradient at that block."""
         i = internal_guidance_index(block_index, len(self.blocks))
+        if self._sf_block is not None:
+            raise NotImplementedError("crepa_enabled (self_flow) together with Internal Guidance is not built on the st355 path (both claim the tail of the arena that trains)")
         if self._nl_block is not None:
             raise NotImplementedError("Internal Guidance together with NextLat is not built on the st355 path (both heads claim the tail of the arena that trains)")
         if self._ig is not None or self._ig_arena is not None:
@@ -1187,6 +1243,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if state_loss not in ops.NEXTLAT_MODES:
             raise ValueError("nextlat_state_loss must be 'smooth_l1' or 'mse'.")
         i = nextlat_index(configured_index, len(self.blocks))
+        if self._sf_block is not None:
+            raise NotImplementedError("crepa_enabled (self_flow) together with NextLat is not built on the st355 path (both claim the tail of the arena that trains)")
         if self._ig_block is not None:
             raise NotImplementedError("Internal Guidance together with NextLat is not built on the st355 path (both heads claim the tail of the arena that trains)")
         self._nl_mode = state_loss
@@ -1217,6 +1275,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """LayerSync (helpers/training/layersync.py; the reference captures at sd3/transformer.py:872): 0-based joint-block indices.  A training forward then also
         returns the mean cosine between the two blocks' image-stream outputs (teacher detached) and the backward adds its gradient into the dX chain at the
         student block."""
+        if self._sf_block is not None:
+            raise NotImplementedError("crepa_enabled (self_flow) together with LayerSync is not built on the st355 path (LayerSync refuses tokenwise timesteps)")
         self._layersync = layersync_indices(student_idx, teacher_idx, len(self.blocks))
 
     def set_router(self, router, routes):
@@ -1404,7 +1464,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     # public forward (reference signature: sd3/transformer.py:560-575)
     # ------------------------------------------------------------------------------------------------
     def forward(self, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None, block_controlnet_hidden_states=None,
-                joint_attention_kwargs=None, return_dict: bool = True, force_keep_mask=None, return_internal_guidance: bool = False, **unsupported):
+                joint_attention_kwargs=None, return_dict: bool = True, force_keep_mask=None, return_internal_guidance: bool = False,
+                crepa_capture_block_index: Optional[int] = None, crepa_teacher_features=None, **unsupported):
         self._force_keep_mask = force_keep_mask            # TREAD: tokens that may never be routed away (sd3/transformer.py:571, 699-703)
         if block_controlnet_hidden_states is not None:
             raise NotImplementedError("SD3 ControlNet residuals are not wired to the st355 path yet")
@@ -1414,6 +1475,12 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if timestep.ndim not in (1, 2):
             raise ValueError(f"timestep: expected [B] or tokenwise [B, S_img], got {tuple(timestep.shape)}")
         need_grad = torch.is_grad_enabled() and (len(self._lora_params) > 0 or getattr(self, "full", False))
+        if crepa_capture_block_index is not None:          # Self-Flow's teacher forward: always no-grad, returns `crepa_hidden_states` and no sample
+            need_grad = False
+        if crepa_teacher_features is not None:             # Self-Flow's training forward: the features its tap aligns to
+            if self._sf_block is None or not need_grad:
+                raise ValueError("crepa_teacher_features: only a training forward of a component with set_self_flow() takes teacher features")
+            self._sf_feats = crepa_teacher_features
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
         if need_grad:      # the training nodes return every tap's output (the similarity / the head's prediction / the state loss) behind the prediction, in the taps' order
@@ -1424,7 +1491,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         else:
             with torch.no_grad():
                 out, ectx = self._engine_forward(hidden_states.to(BF16), encoder_hidden_states.to(BF16), pooled_projections, timestep, save=False,
-                                                 want_ig=bool(return_internal_guidance))
+                                                 want_ig=bool(return_internal_guidance), capture=crepa_capture_block_index)
                 extra = {tap.key: tap.output for tap in ectx.taps}      # sampling: the intermediate prediction next to the final one
         if not return_dict:
             return (out,) + tuple(extra.values())

@@ -60,7 +60,7 @@ def default_config(**over) -> SimpleNamespace:
                offset_noise=False, seed=42, lora_init_b_std=0.0, layersync_enabled=False, layersync_student_block=None, layersync_teacher_block=None,
                layersync_lambda=None, internal_guidance_enabled=False, internal_guidance_loss_weight=0.5, internal_guidance_block_index=None,
                validation_internal_guidance_scale=1.0, nextlat_enabled=False, nextlat_weight=None, nextlat_block_index=None, nextlat_state_loss=None,
-               nextlat_kl_weight=None)
+               nextlat_kl_weight=None, crepa_enabled=False)
     cfg.update(over)
     return SimpleNamespace(**cfg)
 
@@ -115,6 +115,9 @@ class Trainer:
                                       "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
         if opt_name in ("muon", "soap") and getattr(config, "nextlat_enabled", False):
             raise NotImplementedError(f"optimizer '{opt_name}' with nextlat_enabled: the trainable arena then holds the predictor's 1-D tensors, which the "
+                                      "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
+        if opt_name in ("muon", "soap") and getattr(config, "crepa_enabled", False):
+            raise NotImplementedError(f"optimizer '{opt_name}' with crepa_enabled: the trainable arena then holds the projector's 1-D tensors, which the "
                                       "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
         self._bf16_shadow = None
         if opt_name == "muon":
@@ -182,6 +185,10 @@ class Trainer:
                                                                             or self.accelerator.num_processes == 1)
         if self.accelerator.num_processes > 1:
             sync_module_states(comp)                                     # replicas start from rank 0's weights (DDP construction semantics)
+            if self.ema_model is not None:                               # ... and so does every replica's shadow (Self-Flow forwards through it: one teacher on all ranks)
+                with torch.no_grad():
+                    for s_, p_ in zip(self.ema_model.shadow_params, self.params):
+                        s_.copy_(p_.data.to(s_.dtype))
         # ST355_COMM_SINGLE_RANK=1 under an initialised process group of ONE rank: the exchange is set up and issued anyway (GradSync.single_rank_exchange) — how a
         # 1-GPU box runs this step's collectives over RCCL itself; a 1-rank SUM changes nothing, so the step's numbers are those of the plain single-process step
         single_rank = self.accelerator.num_processes == 1 and dist.is_available() and dist.is_initialized() and _os.environ.get("ST355_COMM_SINGLE_RANK", "0") not in ("", "0")
@@ -216,6 +223,10 @@ class Trainer:
                 raise NotImplementedError("hip_graph: NextLat (nextlat_enabled) reads its logs on the host every step and cannot be captured")
             if getattr(getattr(model_plugin, "xm_config", None), "enabled", False):
                 raise NotImplementedError("nextlat_enabled with XM noise candidates is not built on the st355 path")
+        if getattr(config, "crepa_enabled", False):
+            if self._use_graph:
+                raise NotImplementedError("hip_graph: Self-Flow (crepa_enabled) reads its similarity on the host every step and cannot be captured")
+            self.model.ema_model = self.ema_model          # Self-Flow's teacher: the plugin packs the adapters from the EMA's flat shadow (common.py `_ema_teacher_weights_context`)
         if hasattr(self.model, "scheduled_sampling_value"):
             self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
         self.distiller = None
