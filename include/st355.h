@@ -793,6 +793,23 @@ int64_t st355_self_flow_wgrad_workspace(int D);
 int st355_self_flow_wgrad(void* stream, const void* P, const float* db, const float* gamma, const float* beta, const float* W, const float* scale_dev, float* g_gamma,
                           float* g_beta, float* g_W, float* g_b, int D, int accumulate, void* ws);
 
+/* ---- TwinFlow (twinflow_enabled; common.py `_twinflow_rcgm_target` / `_compute_twinflow_losses`, custom_schedule.py `TwinFlowScheduler`; csrc/twinflow.hip) ----
+ * bf16 tensors [batch, per_sample] contiguous, 16-byte aligned, per_sample % 8 == 0; fp32 arithmetic, one rounding per store, no atomics, nothing read on the host.
+ * st355_twinflow_rcgm_step: with h = t_next[b] - t_prev[b] (fp32 [batch] on the device):  x[b, :] <- x + h fc (bf16, in place; x != fc) and
+ *   acc[b, :] <- (first ? 0 : acc) + (-h) fc (fp32 [batch, per_sample]), one pass over fc.
+ * st355_twinflow_loss: t' = target + ratio (cond - uncond) (cond / uncond NULL together: t' = target), d = pred - t', r = d - acc:
+ *   loss_out[0] = mean clamp(r, -clamp, clamp)^2, loss_out[1] = mean d^2, plain means over all batch * per_sample elements, reduced in two stages in a fixed order
+ *   (bit-identical run to run);  dpred (bf16, may be NULL) = grad_scale (2 / (batch per_sample)) (clamp(r) + d), rounded once.  batch < 65536, clamp >= 0.
+ *   workspace: st355_twinflow_workspace(batch, per_sample) bytes, 16-byte aligned.
+ * st355_twinflow_ucgm_step: x <- (1 - s_next) (x - s_cur v) + s_next ((x + (1 - s_cur) v) sqrt(1 - rho) + noise sqrt(rho)) in place over n elements (n % 8 == 0);
+ *   rho in [0, 1]; noise (bf16) may be NULL when rho == 0. */
+int64_t st355_twinflow_workspace(int64_t batch, int64_t per_sample);
+int st355_twinflow_rcgm_step(void* stream, void* x, float* acc, const void* fc, const float* t_prev, const float* t_next, int first, int64_t batch,
+                             int64_t per_sample);
+int st355_twinflow_loss(void* stream, const void* pred, const void* target, const float* acc, const void* cond, const void* uncond, float ratio, float clamp,
+                        float* loss_out, void* dpred, void* workspace, int64_t batch, int64_t per_sample, float grad_scale);
+int st355_twinflow_ucgm_step(void* stream, void* x, const void* v, const void* noise, float s_cur, float s_next, float rho, int64_t n);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

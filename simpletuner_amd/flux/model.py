@@ -85,6 +85,9 @@ class Flux(ModelFoundation):
     # ---- loading (common.py:3400 load_model).  Checkpoints are absent offline: synthetic init or a provided state dict ----
     def load_model(self, state_dict=None, **arch):
         self.model = FluxTransformer2DModel(device=self.accelerator.device, **arch)
+        if state_dict is not None and getattr(self.config, "twinflow_enabled", False):
+            from ..twinflow import drop_sign_embedding          # TwinFlow: a zero time-sign table adds nothing under LoRA and is dropped, a trained one is refused
+            state_dict = drop_sign_embedding(state_dict)
         if state_dict is not None:
             self.model.load_flat_state(state_dict)
         else:

@@ -252,6 +252,8 @@ class ModelFoundation(ExplorativeModelingMixin):
         self._noise_step = 0            # noising passes issued (diagnostic)
         self._noise_offset = 0          # CUMULATIVE Philox counter position: every pass consumes its own, non-overlapping counter range whatever its shape
         self.xm_config = ExplorativeModelingConfig.from_config(config)     # common.py:578
+        if getattr(config, "twinflow_enabled", False):                     # common.py:601 `_validate_twinflow_config`, then what this path does not take
+            self.twinflow_value()
 
     # ---- latent encode seam (common.py:2653-2772, foundation_mixins.py:66-79) ----
     @classmethod
@@ -613,6 +615,18 @@ class ModelFoundation(ExplorativeModelingMixin):
         return getattr(self.unwrap_model(comp), "lora_tlora", None) if comp is not None else None
 
     ROLLOUT_BATCH_KEYS = None           # families with the scheduled-sampling rollout (Flux, SD3): the per-sample batch entries their model_predict reads
+
+    def twinflow_value(self) -> bool:
+        """`twinflow_enabled` as the step takes it: False when absent (nothing is imported then); else the reference's checks with its texts
+        (`_validate_twinflow_config`, common.py:5105-5140) and every configuration the teacher forwards / the kernels are not built for refused by the flag's name
+        and the value to set (twinflow.refuse_unbuilt) — never a silently different computation.  Built: the flow-matching families with the rollout's batch
+        keys (SD3, Flux), model_type=lora, standard LoRA."""
+        if not getattr(self.config, "twinflow_enabled", False):
+            return False
+        from .twinflow import refuse_unbuilt
+        flow = self.PREDICTION_TYPE is PredictionTypes.FLOW_MATCHING
+        refuse_unbuilt(self.config, self.NAME, flow, flow and self.ROLLOUT_BATCH_KEYS is not None)
+        return True
 
     def scheduled_sampling_value(self):
         """`scheduled_sampling_max_step_offset` / `scheduled_sampling_reflexflow` as the step takes them: (max offset, ReflexFlow on).  Applies the reference's
@@ -1609,6 +1623,9 @@ class ModelFoundation(ExplorativeModelingMixin):
                 self._self_flow_views(batch, state, lat, input_noise, sig)
             else:
                 self.expand_sigmas(batch)
+                if getattr(self.config, "twinflow_enabled", False) and self.twinflow_value():          # common.py:5979-5980, after the noisy latents exist
+                    from .twinflow import prepare_metadata
+                    prepare_metadata(batch)
         else:
             # DDPM families (common.py:5983-6002): discrete timesteps (segmented selection when bsz > 1, custom_schedule.py:18-58), noise =
             # randn_like(latents) (or injected), x_t = sqrt(acp_t) x + sqrt(1 - acp_t) n in fp32 then cast (DDPMScheduler.add_noise)
@@ -1843,6 +1860,13 @@ class ModelFoundation(ExplorativeModelingMixin):
         """common.py:5364-5374 `_apply_layersync_regularizer`: loss - lambda * similarity, the two logs as host floats (layersync.py:55-58).  The similarity and its
         gradient come from the engine (model_output["layersync_similarity"]); the `.item()` reads happen here, outside it."""
         logs = {}
+        if getattr(self.config, "twinflow_enabled", False) and self.twinflow_value():
+            # common.py:6448-6459, ahead of every regulariser (the reference's order): the RCGM base term + the real-velocity term on the training prediction, the
+            # teacher's forwards and the two logs' ONE host read inside twinflow.compute_losses
+            from .twinflow import compute_losses
+            twin, twin_logs = compute_losses(self, prepared_batch, model_output.get("model_prediction") if isinstance(model_output, dict) else None)
+            loss = loss + twin
+            logs.update(twin_logs)
         ig = getattr(self, "internal_guidance", None)
         if ig is not None:
             # common.py:6461-6469 / internal_guidance.py:229-254, before the LayerSync term (the reference's order): weight * the plugin's own loss() on the head's

@@ -260,6 +260,71 @@ def flow_euler_step(x, v, dt):
     return x
 
 
+def twinflow_rcgm_step(x, acc, fc, t_prev, t_next, first: bool):
+    """One step of TwinFlow's RCGM teacher integration, in place: x[b] += (t_next[b] - t_prev[b]) fc[b] (bf16, fp32 arithmetic, one rounding) and
+    acc[b] = (0 if first else acc[b]) + (t_prev[b] - t_next[b]) fc[b] (fp32), one pass over fc.  t_prev / t_next: fp32 [B] on the device.  Returns (x, acc)."""
+    L = _l.load()
+    _chk(x, BF16, "x"); _chk(fc, BF16, "fc"); _chk(acc, F32, "acc"); _chk(t_prev, F32, "t_prev"); _chk(t_next, F32, "t_next")
+    B = x.shape[0]
+    N = x.numel() // B
+    if not x.is_contiguous() or not acc.is_contiguous() or x.shape != fc.shape or acc.shape != x.shape or t_prev.numel() != B or t_next.numel() != B or N % 8 != 0:
+        raise _l.St355Error(f"twinflow_rcgm_step: x and acc must be contiguous (they are updated in place), fc and acc of x's shape, t_prev / t_next [{B}] and the "
+                            f"per-sample size {N} a multiple of 8")
+    fc = fc.contiguous()
+    if fc.data_ptr() == x.data_ptr():
+        raise _l.St355Error("twinflow_rcgm_step: x and fc must be different buffers")
+    _l.check(L.st355_twinflow_rcgm_step(_stream(), _ptr(x), _ptr(acc), _ptr(fc), _ptr(t_prev.contiguous()), _ptr(t_next.contiguous()), 1 if first else 0, B, N),
+             "twinflow_rcgm_step")
+    return x, acc
+
+
+def twinflow_loss(pred, target, acc, cond=None, uncond=None, ratio: float = 0.0, clamp: float = 1.0, want_grad: bool = True, grad_scale: float = 1.0):
+    """TwinFlow's two terms on the training prediction (common.py `_compute_twinflow_losses`): t' = target + ratio (cond - uncond), r = pred - acc - t';
+    losses[0] = mean clamp(r, +-clamp)^2 (the RCGM base term: the target is detached), losses[1] = mean (pred - t')^2 (real velocity), plain means over the whole
+    tensor, fixed-order two-stage reduction; dpred = grad_scale (2 / N) (clamp(r) + (pred - t')) from the same pass.  Returns (losses fp32 [2], dpred or None)."""
+    L = _l.load()
+    if (cond is None) != (uncond is None):
+        raise _l.St355Error("twinflow_loss: cond and uncond come together or not at all")
+    pair = [cond, uncond] if cond is not None else []
+    ts, B, N = _rf_rows([pred, target] + pair, ["pred", "target", "cond", "uncond"])
+    _chk(acc, F32, "acc")
+    if acc.shape != pred.shape or not acc.is_contiguous():
+        raise _l.St355Error(f"acc: expected a contiguous fp32 tensor of pred's shape {tuple(pred.shape)}, got {tuple(acc.shape)}")
+    if not float(clamp) >= 0.0:
+        raise _l.St355Error(f"twinflow_loss: the clamp ({clamp}) must not be negative")
+    dev = pred.device
+    losses = torch.empty(2, dtype=F32, device=dev)
+    dpred = torch.empty_like(ts[0]) if want_grad else None
+    ws = _scratch("twinflow", dev, L.st355_twinflow_workspace(B, N))
+    _l.check(L.st355_twinflow_loss(_stream(), _ptr(ts[0]), _ptr(ts[1]), _ptr(acc), _ptr(ts[2]) if pair else None, _ptr(ts[3]) if pair else None, float(ratio),
+                                   float(clamp), _ptr(losses), _ptr(dpred), _ptr(ws), B, N, float(grad_scale)), "twinflow_loss")
+    return losses, dpred
+
+
+def twinflow_ucgm_step(x, v, s_cur: float, s_next: float, rho: float = 0.0, noise=None):
+    """The UCGM sampler's step (custom_schedule.py `TwinFlowScheduler.step`), in place on bf16 x:
+    x <- (1 - s_next) (x - s_cur v) + s_next ((x + (1 - s_cur) v) sqrt(1 - rho) + noise sqrt(rho)); noise may be None when rho == 0.  Returns x."""
+    L = _l.load()
+    _chk(x, BF16, "x"); _chk(v, BF16, "v")
+    n = x.numel()
+    if not x.is_contiguous() or x.shape != v.shape or n % 8 != 0 or n == 0:
+        raise _l.St355Error(f"twinflow_ucgm_step: x must be contiguous (it is updated in place), v of its shape and the element count {n} a positive multiple of 8")
+    if not 0.0 <= float(rho) <= 1.0:
+        raise _l.St355Error(f"twinflow_ucgm_step: rho ({rho}) must lie in [0, 1]")
+    v = v.contiguous()
+    if noise is not None:
+        _chk(noise, BF16, "noise")
+        if noise.shape != x.shape:
+            raise _l.St355Error(f"noise: shape {tuple(noise.shape)} differs from x's {tuple(x.shape)}")
+        noise = noise.contiguous()
+    elif float(rho) != 0.0:
+        raise _l.St355Error("twinflow_ucgm_step: rho > 0 needs noise")
+    if v.data_ptr() == x.data_ptr() or (noise is not None and noise.data_ptr() == x.data_ptr()):
+        raise _l.St355Error("twinflow_ucgm_step: x, v and noise must be different buffers")
+    _l.check(L.st355_twinflow_ucgm_step(_stream(), _ptr(x), _ptr(v), _ptr(noise), float(s_cur), float(s_next), float(rho), n), "twinflow_ucgm_step")
+    return x
+
+
 DIFF2FLOW_MODES = {"epsilon": 0, "v_prediction": 1}
 
 

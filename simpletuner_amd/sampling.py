@@ -17,6 +17,7 @@ latents live on; the model call inside the loop is the same HIP forward the trai
 """
 from __future__ import annotations
 
+import logging
 import math
 from types import SimpleNamespace
 from typing import Callable, List, Optional, Sequence
@@ -287,7 +288,14 @@ def sample_images(plugin, prompt_embeds: torch.Tensor, pooled: Optional[torch.Te
     x = x.to(device=dev, dtype=torch.bfloat16)
     from .foundation import PredictionTypes
     flow = plugin.PREDICTION_TYPE is PredictionTypes.FLOW_MATCHING
-    if scheduler is None:
+    twinflow = bool(getattr(plugin.config, "twinflow_enabled", False)) and plugin.twinflow_value()
+    if twinflow:
+        # validation.py:2963-2976, 4720-4731: TwinFlow bakes the guidance in during training — its own UCGM sampler (TwinFlowScheduler, stochast_ratio = 1.0) for
+        # `twinflow_target_step_count` steps at guidance 0, whatever the caller asked for
+        from .twinflow import settings as twinflow_settings, ucgm_sample
+        num_inference_steps, guidance_scale = twinflow_settings(plugin.config)["target_step_count"], 0.0
+        logging.getLogger(__name__).info("TwinFlow validation: %d steps, guidance_scale=0.0", num_inference_steps)
+    if scheduler is None and not twinflow:
         if flow:
             scheduler = FlowMatchEulerDiscreteScheduler(shift=float(getattr(plugin.config, "flow_schedule_shift", 3.0) or 1.0))
         else:
@@ -336,7 +344,9 @@ def sample_images(plugin, prompt_embeds: torch.Tensor, pooled: Optional[torch.Te
             out = (inter + ig_scale * (out.float() - inter)).to(xt.dtype)
         return cfg_combine(out, float(guidance_scale)) if do_cfg else out
 
-    if flow:
+    if twinflow:
+        x = ucgm_sample(predict, x, num_inference_steps, stochast_ratio=1.0, generator=generator)
+    elif flow:
         x = flow_match_euler_sample(predict, x, scheduler, num_inference_steps, mu=mu)
     else:
         x = ddim_sample(predict, x, scheduler, num_inference_steps)

@@ -48,6 +48,9 @@ class SD3(ModelFoundation):
             # Self-Flow: the projector goes to the tail of the adapter arena, so the component learns its blocks ahead of add_lora_adapter (post_model_load_setup
             # repeats the checks in the reference's order and refuses what this path does not take)
             self.model.set_self_flow(getattr(self.config, "crepa_block_index", None), getattr(self.config, "crepa_teacher_block_index", None))
+        if state_dict is not None and getattr(self.config, "twinflow_enabled", False):
+            from ..twinflow import drop_sign_embedding          # TwinFlow: a zero time-sign table adds nothing under LoRA and is dropped, a trained one is refused
+            state_dict = drop_sign_embedding(state_dict)
         if state_dict is not None:
             self.model.load_flat_state(state_dict)
         else:

@@ -227,6 +227,9 @@ class Trainer:
             if self._use_graph:
                 raise NotImplementedError("hip_graph: Self-Flow (crepa_enabled) reads its similarity on the host every step and cannot be captured")
             self.model.ema_model = self.ema_model          # Self-Flow's teacher: the plugin packs the adapters from the EMA's flat shadow (common.py `_ema_teacher_weights_context`)
+        if getattr(config, "twinflow_enabled", False) and hasattr(self.model, "twinflow_value"):
+            self.model.twinflow_value()                                  # TwinFlow: the reference's checks, then the refusals by the flag's name
+            self.model.ema_model = self.ema_model                        # its teacher: the plugin packs the adapters from the EMA's flat shadow
         if hasattr(self.model, "scheduled_sampling_value"):
             self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
         self.distiller = None
