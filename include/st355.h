@@ -810,6 +810,20 @@ int st355_twinflow_loss(void* stream, const void* pred, const void* target, cons
                         float* loss_out, void* dpred, void* workspace, int64_t batch, int64_t per_sample, float grad_scale);
 int st355_twinflow_ucgm_step(void* stream, void* x, const void* v, const void* noise, float s_cur, float s_next, float rho, int64_t n);
 
+/* ---- Evaluation loss (eval_steps_interval / eval_epoch_interval; validation.py `Evaluation`, trainer.py `_prepare_custom_timestep_batch`; csrc/eval_loss.hip) ----
+ * K timesteps of the same `batch` samples stacked along the batch axis.  bf16 tensors contiguous, 16-byte aligned, per_sample % 8 == 0, 1 <= k <= 64; fp32
+ * arithmetic, one rounding per store, no atomics, nothing read on the host.
+ * st355_eval_flow_views: out[j, b, :] = (1 - sigma[j]) latents[b, :] + sigma[j] noise[b, :] for j < k (sigma fp32 [k] on the device; out bf16 [k, batch, per_sample],
+ *   overlapping neither input).  latents and noise are read once; slab j is bit-identical to st355_flow_noise_mix called with sigma[j] for every row.
+ * st355_eval_loss: for every slab j of pred [k, batch, per_sample] against the one target [batch, per_sample]: loss_type 0 = l2, 1 = huber, 2 = smooth_l1 (the element
+ *   formulas of st355_cond_loss; huber_c fp32 [k * batch], NULL for l2), per_sample[j, b] = the sample's mean, loss[j] = the mean of per_sample[j, :].  Reduced in two
+ *   stages in a fixed order whose shape follows from batch and per_sample alone: loss[j] and per_sample[j, :] do not depend on k or on j (bit for bit).  `loss` may
+ *   point into a larger device table.  batch < 65536.  workspace: st355_eval_loss_workspace(batch, per_sample, k) bytes. */
+int64_t st355_eval_loss_workspace(int64_t batch, int64_t per_sample, int64_t k);
+int st355_eval_flow_views(void* stream, const void* latents, const void* noise, const float* sigma, void* out, int64_t batch, int64_t per_sample, int64_t k);
+int st355_eval_loss(void* stream, const void* pred, const void* target, int loss_type, const float* huber_c, float* per_sample, float* loss, void* workspace,
+                    int64_t batch, int64_t per_sample_n, int64_t k);
+
 /* ==== UNet path (SDXL / SD1.5: sdxl/model.py:350-367, sd1x/model.py:224-270 call diffusers' UNet2DConditionModel — un-vendored) ==== */
 /* "grid buffer": [st355_conv_grid_rows(B,H,W), C] bf16 — position (b,y,x) of the zero-bordered (H+2)x(W+2) image b at row
  * (b*(H+2)+y)*(W+2)+x; border positions hold ZERO; 64 zero rows follow the last image.  Kernels keep the border zero and never write the

@@ -1602,6 +1602,7 @@ class ModelFoundation(ExplorativeModelingMixin):
                 batch["mixflow_slowdown_factors"], batch["mixflow_interpolation_sigmas"] = slow, sig
             given = batch.get("noise")          # tests / parity runs inject the reference's noise; else Philox in-kernel
             seed = int(getattr(self.config, "seed", 42) or 0) + 1_000_003 * int(getattr(self.accelerator, "process_index", 0))
+            seed = self.__dict__.get("_eval_noise_seed", seed)          # the evaluation pass's own noise stream (training/evaluation.py sets and removes it)
             per_call = (lat.numel() + 3) // 4
             noisy, target, noise = ops.flow_noise_mix(lat, sig, noise=given, seed=seed, offset=self._noise_offset)
             self._noise_step += 1

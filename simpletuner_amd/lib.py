@@ -43,6 +43,7 @@ SYMBOLS = [
     "st355_tlora_mask",
     "st355_self_flow_views", "st355_self_flow_fold", "st355_self_flow_rows", "st355_self_flow_wgrad_workspace", "st355_self_flow_wgrad",
     "st355_twinflow_workspace", "st355_twinflow_rcgm_step", "st355_twinflow_loss", "st355_twinflow_ucgm_step",
+    "st355_eval_loss_workspace", "st355_eval_flow_views", "st355_eval_loss",
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
     # UNet path (SDXL / SD1.5)
@@ -433,6 +434,9 @@ def _declare(lib):
         "st355_twinflow_rcgm_step": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i64, i64]),
         "st355_twinflow_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i64, i64, f32]),
         "st355_twinflow_ucgm_step": (C.c_int, [vp, vp, vp, vp, f32, f32, f32, i64]),
+        "st355_eval_loss_workspace": (i64, [i64, i64, i64]),
+        "st355_eval_flow_views": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64]),
+        "st355_eval_loss": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, i64, i64, i64]),
         "st355_workspace_bytes": (i64, [i32, vp, i32]),
         "st355_comm_unique_id": (C.c_int, [vp]),
         "st355_comm_init": (C.c_int, [vp, vp, i32, i32]),

@@ -325,6 +325,80 @@ def twinflow_ucgm_step(x, v, s_cur: float, s_next: float, rho: float = 0.0, nois
     return x
 
 
+EVAL_MAX_STACK = 64
+
+
+def eval_flow_views(latents, noise, sigma, out=None):
+    """The evaluation pass's noisy rows for K timesteps of the same samples: out[k, b] = (1 - sigma[k]) latents[b] + sigma[k] noise[b] (bf16 [K, B, ...]; sigma fp32
+    [K] on the device, 1 <= K <= 64), latents and noise read once.  Slab k is bit-identical to flow_noise_mix(latents, sigma[k] for every row, noise=noise)[0].
+    `out`: a contiguous bf16 tensor of K * latents.numel() elements to write into (overlapping neither input), else allocated.  Returns out."""
+    L = _l.load()
+    _chk(latents, BF16, "latents"); _chk(noise, BF16, "noise"); _chk(sigma, F32, "sigma")
+    B = latents.shape[0]
+    N = latents.numel() // max(B, 1)
+    K = sigma.numel()
+    if noise.shape != latents.shape:
+        raise _l.St355Error(f"noise: shape {tuple(noise.shape)} differs from latents' {tuple(latents.shape)}")
+    if B <= 0 or N <= 0 or N % 8 != 0:
+        raise _l.St355Error(f"eval_flow_views: the per-sample size {N} must be a positive multiple of 8 and the batch {B} positive")
+    if not 1 <= K <= EVAL_MAX_STACK or sigma.dim() != 1:
+        raise _l.St355Error(f"sigma: expected a 1-D tensor of 1 to {EVAL_MAX_STACK} values, got shape {tuple(sigma.shape)}")
+    latents, noise, sigma = latents.contiguous(), noise.contiguous(), sigma.contiguous()
+    if out is None:
+        out = torch.empty((K,) + tuple(latents.shape), dtype=BF16, device=latents.device)
+    else:
+        _chk(out, BF16, "out")
+        if not out.is_contiguous() or out.numel() != K * latents.numel():
+            raise _l.St355Error(f"out: expected a contiguous bf16 tensor of {K * latents.numel()} elements, got shape {tuple(out.shape)} stride {out.stride()}")
+        lo, hi = out.data_ptr(), out.data_ptr() + 2 * out.numel()
+        for t in (latents, noise):
+            if t.data_ptr() < hi and lo < t.data_ptr() + 2 * t.numel():
+                raise _l.St355Error("eval_flow_views: out must not overlap latents or noise")
+    _l.check(L.st355_eval_flow_views(_stream(), _ptr(latents), _ptr(noise), _ptr(sigma), _ptr(out), B, N, K), "eval_flow_views")
+    return out
+
+
+def eval_loss(pred, target, loss_type: str = "l2", huber_c=0.1, loss_out=None):
+    """The evaluation loss of K stacked timesteps: pred bf16 [K, B, ...] against the ONE target bf16 [B, ...] — the l2 / huber / smooth_l1 element loss, the per-sample
+    mean, the batch mean, per slab (what cond_loss computes for each slab alone, without gradient, mask or weights).  huber_c: float or fp32 device tensor of K * B
+    values.  `loss_out`: a contiguous fp32 [K] view to write the K losses into (a row segment of a device-resident result table), else allocated.  The values do not
+    depend on K or on a slab's position.  Returns (loss [K], per_sample [K, B])."""
+    L = _l.load()
+    _chk(pred, BF16, "pred"); _chk(target, BF16, "target")
+    if loss_type not in LOSS_TYPES:
+        raise _l.St355Error(f"eval_loss: loss_type {loss_type!r} is not one of {sorted(LOSS_TYPES)}")
+    if pred.dim() != target.dim() + 1 or tuple(pred.shape[1:]) != tuple(target.shape):
+        raise _l.St355Error(f"pred: expected shape [K, {', '.join(str(s) for s in target.shape)}], got {tuple(pred.shape)}")
+    K, B = pred.shape[0], target.shape[0]
+    N = target.numel() // max(B, 1)
+    if not 1 <= K <= EVAL_MAX_STACK:
+        raise _l.St355Error(f"eval_loss: the timestep count {K} must lie in [1, {EVAL_MAX_STACK}]")
+    if N <= 0 or N % 8 != 0 or not 0 < B < 65536:
+        raise _l.St355Error(f"eval_loss: per-sample size {N} must be a positive multiple of 8 and the batch {B} below 65536")
+    pred, target = pred.contiguous(), target.contiguous()
+    dev = pred.device
+    if loss_type != "l2":
+        if not torch.is_tensor(huber_c):
+            huber_c = torch.full((K * B,), float(huber_c), dtype=F32, device=dev)
+        _chk(huber_c, F32, "huber_c")
+        huber_c = huber_c.contiguous()
+        if huber_c.numel() != K * B:
+            raise _l.St355Error(f"huber_c: expected {K * B} values, got {huber_c.numel()}")
+    else:
+        huber_c = None
+    if loss_out is None:
+        loss_out = torch.empty(K, dtype=F32, device=dev)
+    else:
+        _chk(loss_out, F32, "loss_out")
+        if not loss_out.is_contiguous() or loss_out.numel() != K:
+            raise _l.St355Error(f"loss_out: expected a contiguous fp32 view of {K} values, got shape {tuple(loss_out.shape)} stride {loss_out.stride()}")
+    per_sample = torch.empty(K, B, dtype=F32, device=dev)
+    ws = _scratch("eval_loss", dev, L.st355_eval_loss_workspace(B, N, K))
+    _l.check(L.st355_eval_loss(_stream(), _ptr(pred), _ptr(target), LOSS_TYPES[loss_type], _ptr(huber_c), _ptr(per_sample), _ptr(loss_out), _ptr(ws), B, N, K),
+             "eval_loss")
+    return loss_out, per_sample
+
+
 DIFF2FLOW_MODES = {"epsilon": 0, "v_prediction": 1}
 
 

@@ -98,7 +98,7 @@ def _diffusers_config(comp) -> dict:
 
 
 class Trainer:
-    def __init__(self, config, model_plugin, accelerator: Optional[St355Accelerator] = None, lr_lambda: Optional[Callable] = None):
+    def __init__(self, config, model_plugin, accelerator: Optional[St355Accelerator] = None, lr_lambda: Optional[Callable] = None, eval_sets=None):
         self.config = config
         self.accelerator = accelerator or model_plugin.accelerator
         self.model = model_plugin
@@ -236,6 +236,18 @@ class Trainer:
         if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Flow-DPO (every other method is refused by name)
             from ..flow_dpo import create_distiller
             self.distiller = create_distiller(self.model)
+        # evaluation loss (trainer.py:7480-7495): built only when an interval is set and eval_loss_disable is false — otherwise nothing is imported, allocated or launched.
+        # `eval_sets`: {name: re-iterable of raw batches}, the seam of the reference's _type="eval" backends
+        self.evaluation = None
+        self.last_eval_logs = None     # {"loss/val/<name>": float} of the eval that ran after the last step of train(), else None; a logger merges it with last_aux_logs
+        self.last_eval_table = None    # {name: {timestep: [one loss per eval batch]}} of the last eval
+        self.eval_history = []         # (global_step, logs) of every eval train() ran
+        if not getattr(config, "eval_loss_disable", False) and any(getattr(config, f, None) not in (None, "", "None", 0, 0.0, False)
+                                                                   for f in ("eval_steps_interval", "eval_epoch_interval")):
+            from . import evaluation as _ev
+            if _ev.schedule_configured(config):
+                _ev.refuse_unbuilt(config, self.model, eval_sets)
+                self.evaluation = _ev.Evaluation(config, self.accelerator, eval_sets)
         self._graphs = {}
         self._graph_warm = {}
         self.state = {"global_step": 0, "micro_step": 0}
@@ -581,10 +593,25 @@ class Trainer:
             plug._noise_offset = int(rng.get("st355_noise_offset", 0))
             break
 
+    def evaluate(self) -> dict:
+        """One evaluation-loss pass over the eval sets with the training weights (the reference swaps in no EMA copy): {"loss/val/<name>": mean over all (timestep,
+        batch) entries}; `last_eval_table` keeps the per-dataset, per-timestep losses.  Ranks other than the main one return {} and issue no collective.  Training's
+        random streams, noise counters and round-robin cursor are where they were afterwards."""
+        if self.evaluation is None or not self.accelerator.is_main_process:
+            return {}
+        table = self.evaluation.execute_eval(self.model, self.evaluation.noise_scheduler_of(self.model))
+        self.last_eval_table = table
+        self.last_eval_logs = self.evaluation.generate_tracker_table(table) if table else {}
+        return self.last_eval_logs
+
     def train(self, batches: Iterable[dict], max_steps: int):
         losses = []
         for i, b in enumerate(batches):
             if i >= max_steps:
                 break
             losses.append(self.train_step(b))
+            if self.evaluation is not None:                                              # trainer.py:7480-7495: after the step
+                self.last_eval_logs = None
+                if self.evaluation.would_evaluate(self.state):
+                    self.eval_history.append((self.state["global_step"], self.evaluate()))
         return losses
