@@ -793,7 +793,30 @@ int64_t st355_self_flow_wgrad_workspace(int D);
 int st355_self_flow_wgrad(void* stream, const void* P, const float* db, const float* gamma, const float* beta, const float* W, const float* scale_dev, float* g_gamma,
                           float* g_beta, float* g_W, float* g_b, int D, int accumulate, void* ws);
 
-/* ---- TwinFlow (twinflow_enabled; common.py `_twinflow_rcgm_target` / `_compute_twinflow_losses`, custom_schedule.py `TwinFlowScheduler`; csrc/twinflow.hip) ----
+/* ---- Self-Transcendence (distillation_method=self_transcendence; helpers/distillation/self_transcendence/distiller.py; csrc/self_transcendence.hip) ----
+ * The projector Linear(D -> Hp) -> SiLU -> Linear(Hp -> Hp) -> SiLU -> Linear(Hp -> D), parameters fp32; fp32 arithmetic, one rounding per store, no atomics, every
+ * reduction in a fixed order, nothing read on the host.  D, Hp, P3 % 8 == 0, 16-byte aligned operands.
+ * st355_st_fold: ONE launch: W1h [Hp, D] = bf16(W1) and W1T [D, Hp], W2h / W2T [Hp, Hp], the first P3 <= D rows of W3h [D, Hp] = bf16(W3[:P3]) and the compact
+ *   W3T [Hp, P3], b1h / b2h [Hp], the first P3 of b3h.  Nothing behind row P3 of W3h / element P3 of b3h is written.
+ * st355_st_vae_loss: pred [B S, P] compact bf16, P = C (H / gh) (W / gw), gh gw == S; column (c, a, e) of token (i, j) is compared with
+ *   target[b, c, i ph + a, j pw + e] (bf16 when target_bf16, else fp32; samples target_bstride ELEMENTS apart, each contiguous), read in place.
+ * st355_st_cfg_loss: pred [B S, D] compact bf16 against u + cfg_scale (c - u) formed in fp32; cond / uncond: [B, S, D] bf16 views (row stride ld, batch stride bstride).
+ *   Both: per_sample[b] = mean_{S, P} (pred - t)^2; sample b is active iff tmin <= sigma[b] <= tmax (fp32 on the device); stats[0] = the mean of the active
+ *   samples' means (0 when none), stats[1] = their count, stats[2] = 1 / (count S P) (0 when none); pred <- G = bf16(2 (pred - t)) of an active sample, 0 otherwise.
+ *   ws: st355_st_loss_workspace(B, S P) bytes.
+ * st355_st_wgrad: g_W [R, Cc] fp32 = s P (P bf16 from gemm_tn), g_b [R] = s db (db fp32 from colsum_prod), s = *scale_dev; accumulate != 0 adds.
+ * st355_st_dx_add: dx (a [B, rows, D] bf16 view: row stride ld, batch stride bstride) = bf16(float(dx) + s g), g [B rows, D] compact bf16. */
+int st355_st_fold(void* stream, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, void* W1h, void* W1T, void* b1h,
+                  void* W2h, void* W2T, void* b2h, void* W3h, void* W3T, void* b3h, int D, int Hp, int P3);
+int64_t st355_st_loss_workspace(int B, int64_t per_sample_elems);
+int st355_st_vae_loss(void* stream, void* pred, const void* target, int target_bf16, int64_t target_bstride, const float* sigma, float tmin, float tmax, int B, int S,
+                      int C, int H, int W, int gh, int gw, float* per_sample, float* stats, void* ws);
+int st355_st_cfg_loss(void* stream, void* pred, const void* cond, const void* uncond, int64_t ld, int64_t bstride, float cfg_scale, const float* sigma, float tmin,
+                      float tmax, int B, int S, int D, float* per_sample, float* stats, void* ws);
+int st355_st_wgrad(void* stream, const void* P, const float* db, const float* scale_dev, float* g_W, float* g_b, int R, int Cc, int accumulate);
+int st355_st_dx_add(void* stream, const void* g, const float* scale_dev, void* dx, int B, int rows, int D, int64_t ld, int64_t bstride);
+
+/* ---- TwinFlow(twinflow_enabled; common.py `_twinflow_rcgm_target` / `_compute_twinflow_losses`, custom_schedule.py `TwinFlowScheduler`; csrc/twinflow.hip) ----
  * bf16 tensors [batch, per_sample] contiguous, 16-byte aligned, per_sample % 8 == 0; fp32 arithmetic, one rounding per store, no atomics, nothing read on the host.
  * st355_twinflow_rcgm_step: with h = t_next[b] - t_prev[b] (fp32 [batch] on the device):  x[b, :] <- x + h fc (bf16, in place; x != fc) and
  *   acc[b, :] <- (first ? 0 : acc) + (-h) fc (fp32 [batch, per_sample]), one pass over fc.

@@ -997,6 +997,176 @@ class SelfFlowTap:
         self.xhat = self.rstd = self.G = None
 
 
+# ------------------------------------------------------------------------------------------------
+# Self-Transcendence (helpers/distillation/self_transcendence/distiller.py): a projector Linear(D -> Hp) -> SiLU -> Linear(Hp -> Hp) -> SiLU -> Linear(Hp -> D) of one
+# shallow block's image-token output, trained by a masked per-sample MSE to the patchified diffusion target (stage `vae`) or to the frozen teacher's feature-space
+# CFG target (stage `self`)
+# ------------------------------------------------------------------------------------------------
+ST_NAMES = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias")      # under `self_transcendence_projector.`: the reference module's names
+
+
+def self_transcendence_indices(student_block, teacher_block, n_blocks: int):
+    """0-based (student, teacher or None) block indices, used as they are (`layer_{i}` of the hidden-state buffer); the reference finds no `layer_{i}` past the last
+    block at the first step — here that is refused when the blocks are named"""
+    s = int(student_block)
+    t = None if teacher_block is None else int(teacher_block)
+    for key, i in (("student_block", s), ("teacher_block", t)):
+        if i is not None and not 0 <= i < n_blocks:
+            raise ValueError(f"Self-Transcendence {key} must be within [0, {n_blocks - 1}], got {i}.")
+    return s, t
+
+
+def self_transcendence_shapes(D: int, Hp: int):
+    return ((Hp, D), (Hp,), (Hp, Hp), (Hp,), (D, Hp), (D,))
+
+
+def self_transcendence_grid(source_shape, token_count: int):
+    """distiller.py `_factor_grid` for a 2-D latent: the shape itself when it holds exactly the tokens (patch 1), else the divisor pair (gh, gw) with gh | H, gw | W
+    and gh gw == token_count whose aspect ratio is closest to H / W (the first such pair on a tie)"""
+    H, W = (int(v) for v in source_shape)
+    token_count = int(token_count)
+    if H * W == token_count:
+        return (H, W)
+    cands = [(f, token_count // f) for f in range(1, token_count + 1) if token_count % f == 0 and H % f == 0 and W % (token_count // f) == 0]
+    if not cands:
+        raise ValueError(f"Self-Transcendence could not map {token_count} tokens onto latent spatial shape {(H, W)}.")
+    return min(cands, key=lambda p: abs((p[0] / p[1]) - (H / W)))
+
+
+class SelfTranscendenceHead:
+    """The projector's six trainable tensors as fp32 views at the tail of the adapter arena, their gradient views, the [lo, hi) element range of the gradient arena
+    they span, and the bf16 operands the GEMMs read (ops.st_fold, once per training forward; the last Linear's as wide as the columns that are read)."""
+
+    def __init__(self, block: int, D: int, Hp: int, params, grads, flat_lo: int, flat_hi: int, device):
+        self.block, self.D, self.Hp = block, D, Hp
+        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = params
+        self.g_W1, self.g_b1, self.g_W2, self.g_b2, self.g_W3, self.g_b3 = grads
+        self.flat_lo, self.flat_hi = flat_lo, flat_hi
+        e = lambda *shp: torch.empty(*shp, dtype=BF16, device=device)
+        self.W1h, self.W1T, self.b1h = e(Hp, D), e(D, Hp), e(Hp)
+        self.W2h, self.W2T, self.b2h = e(Hp, Hp), e(Hp, Hp), e(Hp)
+        self.W3h, self.W3T, self.b3h = e(D, Hp), None, e(D)
+
+    @property
+    def params(self):
+        return (self.W1, self.b1, self.W2, self.b2, self.W3, self.b3)
+
+    @property
+    def grads(self):
+        return (self.g_W1, self.g_b1, self.g_W2, self.g_b2, self.g_W3, self.g_b3)
+
+    @torch.no_grad()
+    def init_reference(self, generator=None):
+        """nn.Linear's default for the three layers — kaiming_uniform(a = sqrt 5) = U(-1 / sqrt fan_in, 1 / sqrt fan_in) for the weight, the same bound for the bias —
+        drawn in fp32, layer by layer, weight first, from the generator given: the adapters' own, behind every A / B draw"""
+        for W, b in ((self.W1, self.b1), (self.W2, self.b2), (self.W3, self.b3)):
+            bound = 1.0 / math.sqrt(W.shape[1])
+            W.uniform_(-bound, bound, generator=generator); b.uniform_(-bound, bound, generator=generator)
+
+    def fold(self, P3: int):
+        if self.W3T is None or self.W3T.shape[1] != P3:
+            self.W3T = torch.empty(self.Hp, P3, dtype=BF16, device=self.W3h.device)
+        ops.st_fold(*self.params, self.W1h, self.W1T, self.b1h, self.W2h, self.W2T, self.b2h, self.W3h, self.W3T, self.b3h)
+
+
+class SelfTranscendenceTap:
+    """One per training forward (kept in its ctx).  `tap(g, view)` after the student block of the saving forward — never in the recompute pass of a checkpointed
+    segment — folds the current parameters and runs the projector on the block's image-token rows [B, S, D]: X (a compact copy) -> U1 = X W1^T + b1 -> A1 = silu ->
+    U2 = A1 W2^T + b2 -> A2 = silu -> pred = A2 W3[:P]^T + b3[:P] (ops.gemm / ops.silu; P = the columns that are read: the patch size of the diffusion target in
+    stage `vae` — a thin GEMM, the reference computes all D columns and discards the rest — and D in stage `self`), then the masked per-sample MSE (ops.st_vae_loss
+    against `target` [B, C, H, W] read in place / ops.st_cfg_loss against the teacher's [2B, S, D] capture): `stats` = (guide loss, active count, 1 / (count S P)) on
+    the device, G = d (sum of the active samples' squared errors) / d pred written over pred.  `backward(d, dx_view)` right before that block's own backward: the
+    chain is linear in G, so ONE device scalar s = d * stats[2] carries the upstream gradient (the weight, the accumulation division) and the normaliser; the three
+    Linears' gradients from gemm_tn / colsum_prod through ops.st_wgrad, dX = dU1 W1 added into the gradient with respect to the block's output (ops.st_dx_add;
+    dx_view None: the block lies below the first one that trains), then the projector's range goes to `sync`.  `off`: the weight is 0 (stop_step reached) — nothing
+    is launched, the output is a constant 0 and the gradient views are zeroed."""
+
+    key = "self_transcendence_guide_loss"
+
+    def __init__(self, head: SelfTranscendenceHead, stage: str, target, sigmas, tmin: float, tmax: float, cfg_scale: float = 1.0, off: bool = False):
+        self.head, self.block, self.stage, self.off = head, head.block, stage, off
+        self.target, self.sigmas, self.tmin, self.tmax, self.cfg_scale = target, sigmas, float(tmin), float(tmax), float(cfg_scale)
+        self.X = self.U1 = self.A1 = self.U2 = self.A2 = self.G = self.stats = self.per_sample = self.output = None
+        self.B = self.rows = self.P = 0
+
+    def tap(self, g: int, view):
+        if g != self.block or self.off:
+            return
+        B, S, D = view.shape
+        h, dev, t = self.head, view.device, self.target
+        if t is None or self.sigmas is None:
+            raise ValueError("Self-Transcendence: the training forward needs `self_transcendence_target` and `self_transcendence_sigmas`")
+        if self.stage == "vae":
+            if t.dim() != 4 or t.shape[0] != B:
+                raise ValueError(f"Self-Transcendence VAE guidance does not support latent shape {tuple(t.shape)}.")       # distiller.py `_vae_target_tokens`
+            grid = self_transcendence_grid(t.shape[2:], S)
+            P = t.shape[1] * (t.shape[2] // grid[0]) * (t.shape[3] // grid[1])
+            if P > D:
+                raise ValueError(f"Self-Transcendence: the diffusion target has {P} values per token, the projector's output only {D}")
+        else:
+            if t.dim() != 3 or tuple(t.shape) != (2 * B, S, D):
+                raise ValueError(f"Self-Transcendence student and teacher shapes differ: student={(B, S, D)}, teacher={tuple(t.shape)}.")
+            P = D
+        if D % 64 or h.Hp % 64 or P % 64:
+            raise NotImplementedError(f"distillation_method=self_transcendence: D, projector_hidden_dim and the target's values per token must be multiples of 64, the "
+                                      f"contraction granule of the GEMMs (got {D}, {h.Hp}, {P}); not built on the st355 path")
+        M = B * S
+        self.B, self.rows, self.P = B, S, P
+        self.X = pad64_empty(M, D, dev)
+        self.X.view(B, S, D).copy_(view)
+        self.U1, self.U2 = torch.empty(M, h.Hp, dtype=BF16, device=dev), torch.empty(M, h.Hp, dtype=BF16, device=dev)
+        self.G = pad64_empty(M, P, dev)
+        self.stats, self.per_sample = torch.empty(3, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev)
+        sig = self.sigmas.detach().to(device=dev, dtype=F32).reshape(B, -1)[:, 0].contiguous()
+        h.fold(P)
+        ops.gemm(self.X, h.W1h, bias=h.b1h, out=self.U1)
+        self.A1 = ops.silu(self.U1)
+        ops.gemm(self.A1, h.W2h, bias=h.b2h, out=self.U2)
+        self.A2 = ops.silu(self.U2)
+        ops.gemm(self.A2, h.W3h[:P], bias=h.b3h[:P], out=self.G)          # the prediction, overwritten with G by the loss
+        if self.stage == "vae":
+            ops.st_vae_loss(self.G, t.detach(), grid, sig, self.tmin, self.tmax, self.per_sample, self.stats)
+        else:
+            ops.st_cfg_loss(self.G, t.detach(), self.cfg_scale, sig, self.tmin, self.tmax, self.per_sample, self.stats)
+        self.target = self.sigmas = None
+
+    def finish(self, H: int, W: int):
+        if self.off:
+            self.output = torch.zeros((), dtype=F32, device=self.head.W1.device)
+        elif self.stats is None:
+            raise RuntimeError(f"Self-Transcendence: block {self.block} was never reached by the forward")
+        else:
+            self.output = self.stats[0]
+        return self.output
+
+    def backward(self, d, dx_view, accumulate: bool = False, sync=None):
+        h = self.head
+        if d is None or self.off:                # the guide loss took no part in the loss
+            if not accumulate:
+                for g in h.grads:
+                    g.zero_()
+        else:
+            M, D, Hp, P, dev = self.B * self.rows, h.D, h.Hp, self.P, self.G.device
+            s = (d.detach().to(device=dev, dtype=F32).reshape(1) * self.stats[2:3]).contiguous()
+            db = torch.empty(1, P + 2 * Hp, dtype=F32, device=dev)
+            db3, db2, db1 = db[:, :P], db[:, P:P + Hp], db[:, P + Hp:]
+            ops.colsum_prod(self.G, db3)
+            ops.st_wgrad(ops.gemm_tn(pad64(self.G), pad64(self.A2)), db3.view(P), s, h.g_W3[:P], h.g_b3[:P], accumulate=accumulate)
+            if P < D and not accumulate:         # the columns that are not read: the reference computes and discards them, their gradients are zero
+                h.g_W3[P:].zero_(); h.g_b3[P:].zero_()
+            dU2 = ops.silu_bwd(self.U2, ops.gemm(self.G, h.W3T))              # dA2 = G W3[:P]
+            ops.colsum_prod(dU2, db2)
+            ops.st_wgrad(ops.gemm_tn(pad64(dU2), pad64(self.A1)), db2.view(Hp), s, h.g_W2, h.g_b2, accumulate=accumulate)
+            dU1 = ops.silu_bwd(self.U1, ops.gemm(dU2, h.W2T))                 # dA1 = dU2 W2
+            ops.colsum_prod(dU1, db1)
+            ops.st_wgrad(ops.gemm_tn(pad64(dU1), pad64(self.X)), db1.view(Hp), s, h.g_W1, h.g_b1, accumulate=accumulate)
+            if dx_view is not None:
+                ops.st_dx_add(ops.gemm(dU1, h.W1T), s, dx_view)               # dX = dU1 W1
+        if sync is not None:
+            sync.ready(h.flat_lo, h.flat_hi)
+        self.X = self.U1 = self.A1 = self.U2 = self.A2 = self.G = None
+
+
 def sincos_2d_hw(embed_dim: int, h: int, w: int, base_size: int, interpolation_scale: float) -> torch.Tensor:
     """diffusers get_2d_sincos_pos_embed on a (h, w) grid: [h * w, embed_dim] fp32 (first half from the w coordinate, which varies fastest; sin then cos)"""
     gh = (torch.arange(h, dtype=torch.float32) / (h / base_size) / interpolation_scale).double()
@@ -1053,7 +1223,7 @@ class ArenaModule(nn.Module):
         """copy a {checkpoint name: tensor} dict into the fused buffers (names = diffusers state-dict keys)"""
         own = dict(self.named_parameters())
         # (an Internal Guidance head / a NextLat predictor is optional in a file: without one it keeps the reference's initial values)
-        missing = [k for k in own if k not in state and ".lora_" not in k and ".lokr_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector."))]
+        missing = [k for k in own if k not in state and ".lora_" not in k and ".lokr_" not in k and not k.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector.", "self_transcendence_projector."))]
         if missing:
             raise KeyError(f"missing weights: {missing[:5]} ... ({len(missing)})")
         own.update(self._extra_state())

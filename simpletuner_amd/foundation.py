@@ -442,7 +442,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         full fine-tune exposes exactly its arena views; the VAE / ControlNet trunk never carry gradients"""
         if "lora" in str(getattr(self.config, "model_type", "lora")) and self.model is not None:
             for n, p_ in self.unwrap_model(self.model).named_parameters():
-                if ".lora_" not in n and ".lokr_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
+                if ".lora_" not in n and ".lokr_" not in n and not (n.startswith(("internal_guidance_head.", "nextlat_predictor.", "crepa_projector.", "self_transcendence_projector.")) and p_.dtype == torch.float32):      # (the heads' fp32 masters train with the adapters)
                     p_.requires_grad_(False)
         elif str(getattr(self.config, "model_type", "lora")) == "full" and self.model is not None:
             # the reference leaves a full-rank model as diffusers loaded it — every parameter trainable — and `Trainer._get_trainable_parameters` collects
@@ -689,7 +689,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         it: 0.0 when absent; a full fine-tune and lora_type=lycoris ignore the flag, as the reference does; a standard LoRA of a family without the masked kernels
         refuses a positive value by name — never a silently different computation."""
         cfg = self.config
-        if getattr(cfg, "distillation_method", None):          # safety_check.py:23-49: a distillation method trains its adapters without dropout
+        if getattr(cfg, "distillation_method", None):          # safety_check.py:23-49: a distillation method trains its adapters without dropout (self_transcendence included)
             from .flow_dpo import adapter_dropout_override, method_of
             if method_of(cfg) is not None:
                 adapter_dropout_override(cfg)
@@ -1003,6 +1003,7 @@ class ModelFoundation(ExplorativeModelingMixin):
         sd.update(self._internal_guidance_head_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         sd.update(self._nextlat_predictor_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         sd.update(self._self_flow_projector_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
+        sd.update(self._self_transcendence_projector_state(comp, next(iter(sd.values())).dtype if sd else torch.float32))
         return sd
 
     DORA_KEY = ".lora_magnitude_vector"            # peft's DoraLinearLayer parameter, per adapted module
@@ -1052,6 +1053,19 @@ class ModelFoundation(ExplorativeModelingMixin):
             return {}
         own = dict(comp.named_parameters())
         return {ModelFoundation.SELF_FLOW_PREFIX + nm: own[ModelFoundation.SELF_FLOW_PREFIX + nm].detach().to(dtype) for nm in SELF_FLOW_NAMES}
+
+    ST_PREFIX = "self_transcendence_projector."          # distiller.py PROJECTOR_NAME; under `transformer.` in a file
+
+    @staticmethod
+    def _self_transcendence_projector_state(comp, dtype) -> dict:
+        """Self-Transcendence's projector as the reference saves it with the adapter (common.py:924-937 `get_lora_save_layers` names
+        `self_transcendence_projector` among the `modules_to_save`; here: the module's state dict under that name): `net.{0,2,4}.{weight,bias}` in the dtype the
+        adapter tensors are saved in.  Empty when the component trains no projector."""
+        from .engine import ST_NAMES
+        if getattr(comp, "_st", None) is None or not getattr(comp, "lora_groups", None):
+            return {}
+        own = dict(comp.named_parameters())
+        return {ModelFoundation.ST_PREFIX + nm: own[ModelFoundation.ST_PREFIX + nm].detach().to(dtype) for nm in ST_NAMES}
 
     def _lora_adapter_metadata(self) -> dict:
         """what peft records for the adapter (LoraConfig r / lora_alpha): alpha defaults to the rank (common.py:1049-1128)"""
@@ -1113,7 +1127,7 @@ class ModelFoundation(ExplorativeModelingMixin):
             raise NotImplementedError("use_dora: the ComfyUI export of a DoRA adapter (its magnitude vectors) is not built on the st355 path; save with "
                                       "--lora_format=diffusers")
         if fmt == PEFTLoRAFormat.COMFYUI and not getattr(self, "NATIVE_COMFYUI_LORA_SUPPORT", False):
-            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k and self.SELF_FLOW_PREFIX not in k}
+            flat = {k: v for k, v in flat.items() if self.IG_PREFIX not in k and self.NEXTLAT_PREFIX not in k and self.SELF_FLOW_PREFIX not in k and self.ST_PREFIX not in k}
             flat = self._convert_lora_state_dict_to_comfyui(flat, adapter_metadata=meta or self._lora_adapter_metadata(), component_adapter_metadata=comp_meta)
             flat = {k: v.contiguous() for k, v in flat.items()}
         os.makedirs(output_dir, exist_ok=True)
@@ -1296,12 +1310,13 @@ class ModelFoundation(ExplorativeModelingMixin):
         # configured, and a file that carries one needs a component that has one
         for pre, attr, a, name, flag, key in ((self.IG_PREFIX, "_ig", "an", "Internal Guidance head", "internal_guidance_enabled", "internal_guidance_block_index"),
                                               (self.NEXTLAT_PREFIX, "_nl", "a", "NextLat predictor", "nextlat_enabled", "nextlat_block_index"),
-                                              (self.SELF_FLOW_PREFIX, "_sf", "a", "Self-Flow projector", "crepa_enabled", None)):
+                                              (self.SELF_FLOW_PREFIX, "_sf", "a", "Self-Flow projector", "crepa_enabled", None),
+                                              (self.ST_PREFIX, "_st", "a", "Self-Transcendence projector", "distillation_method=self_transcendence", None)):
             in_file = sorted(k for k in flat if pre in k)
             head = getattr(comp, attr, None)
             if in_file and (head is None or not getattr(comp, "lora_groups", None)):
                 raise ValueError(f"LoRA checkpoint carries {a} {name} ({in_file[0]}, ...) but none is configured: set {flag} (and the "
-                                 f"file's {key or 'crepa_block_index'}) before loading it")
+                                 f"file's {key or ('student_block' if attr == '_st' else 'crepa_block_index')}) before loading it")
             if head is not None and getattr(comp, "lora_groups", None) and fmt != PEFTLoRAFormat.DIFFUSERS:
                 raise ValueError(f"a ComfyUI-format LoRA file cannot carry the {name} (the export drops it): load the diffusers-format file, or turn "
                                  f"{flag} off to load the adapters alone")

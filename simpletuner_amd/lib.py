@@ -42,6 +42,7 @@ SYMBOLS = [
     "st355_diff2flow_workspace", "st355_diff2flow_loss",
     "st355_tlora_mask",
     "st355_self_flow_views", "st355_self_flow_fold", "st355_self_flow_rows", "st355_self_flow_wgrad_workspace", "st355_self_flow_wgrad",
+    "st355_st_fold", "st355_st_loss_workspace", "st355_st_vae_loss", "st355_st_cfg_loss", "st355_st_wgrad", "st355_st_dx_add",
     "st355_twinflow_workspace", "st355_twinflow_rcgm_step", "st355_twinflow_loss", "st355_twinflow_ucgm_step",
     "st355_eval_loss_workspace", "st355_eval_flow_views", "st355_eval_loss",
     "st355_workspace_bytes",
@@ -430,6 +431,12 @@ def _declare(lib):
         "st355_self_flow_rows": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
         "st355_self_flow_wgrad_workspace": (i64, [i32]),
         "st355_self_flow_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+        "st355_st_fold": (C.c_int, [vp] * 16 + [i32, i32, i32]),
+        "st355_st_loss_workspace": (i64, [i32, i64]),
+        "st355_st_vae_loss": (C.c_int, [vp, vp, vp, i32, i64, vp, f32, f32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "st355_st_cfg_loss": (C.c_int, [vp, vp, vp, vp, i64, i64, f32, vp, f32, f32, i32, i32, i32, vp, vp, vp]),
+        "st355_st_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32]),
+        "st355_st_dx_add": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64]),
         "st355_twinflow_workspace": (i64, [i64, i64]),
         "st355_twinflow_rcgm_step": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i64, i64]),
         "st355_twinflow_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i64, i64, f32]),

@@ -2362,6 +2362,133 @@ def self_flow_wgrad(P, db, gamma, beta, W, scale, g_gamma, g_beta, g_W, g_b, acc
     return g_gamma, g_beta, g_W, g_b
 
 
+# ------------------------------------------------------------------------------------------------
+# Self-Transcendence (csrc/self_transcendence.hip): the projector Linear(D -> Hp) -> SiLU -> Linear(Hp -> Hp) -> SiLU -> Linear(Hp -> D) and its masked per-sample MSE
+# ------------------------------------------------------------------------------------------------
+def _st_params(name: str, W1, b1, W2, b2, W3, b3):
+    """the projector's six fp32 parameters (or their gradients): contiguous, W1 [Hp, D], W2 [Hp, Hp], W3 [D, Hp].  Returns (D, Hp)"""
+    ts = (W1, b1, W2, b2, W3, b3)
+    for t in ts:
+        _chk(t, F32, name)
+    if W1.dim() != 2 or W2.dim() != 2 or W3.dim() != 2:
+        raise _l.St355Error(f"{name}: expected W1 [Hp, D], W2 [Hp, Hp], W3 [D, Hp]")
+    Hp, D = W1.shape
+    if D % 8 or Hp % 8 or D > 16384 or Hp > 16384:
+        raise _l.St355Error(f"{name}: D and Hp must be multiples of 8, at most 16384 (got D = {D}, Hp = {Hp})")
+    if tuple(W2.shape) != (Hp, Hp) or tuple(W3.shape) != (D, Hp) or b1.numel() != Hp or b2.numel() != Hp or b3.numel() != D or not all(t.is_contiguous() for t in ts):
+        raise _l.St355Error(f"{name}: expected contiguous W1 [Hp, D], b1 [Hp], W2 [Hp, Hp], b2 [Hp], W3 [D, Hp], b3 [D] with D = {D}, Hp = {Hp}")
+    _al16(name, *ts)
+    return D, Hp
+
+
+def st_fold(W1, b1, W2, b2, W3, b3, W1h, W1T, b1h, W2h, W2T, b2h, W3h, W3T, b3h):
+    """Self-Transcendence projector (st355_st_fold): ONE launch turns the six fp32 masters into the bf16 GEMM operands: W1h [Hp, D] and W1T [D, Hp], W2h / W2T
+    [Hp, Hp], b1h / b2h [Hp], and — P3 = W3T.shape[1] <= D, the columns of the projection that are read — the first P3 rows of W3h [D, Hp], the compact
+    W3T [Hp, P3] and the first P3 of b3h [D].  Nothing behind row P3 of W3h / element P3 of b3h is written.  Writes into the tensors given."""
+    L = _l.load()
+    D, Hp = _st_params("st_fold", W1, b1, W2, b2, W3, b3)
+    outs = (W1h, W1T, b1h, W2h, W2T, b2h, W3h, W3T, b3h)
+    for t in outs:
+        _chk(t, BF16, "st_fold")
+    P3 = W3T.shape[1] if W3T.dim() == 2 else 0
+    if P3 <= 0 or P3 % 8 or P3 > D:
+        raise _l.St355Error(f"st_fold: W3T [Hp, P3] must have 0 < P3 <= D columns, a multiple of 8 (got {tuple(W3T.shape)})")
+    if not all(t.is_contiguous() for t in outs) or tuple(W1h.shape) != (Hp, D) or tuple(W1T.shape) != (D, Hp) or tuple(W2h.shape) != (Hp, Hp) \
+            or tuple(W2T.shape) != (Hp, Hp) or tuple(W3h.shape) != (D, Hp) or tuple(W3T.shape) != (Hp, P3) or b1h.numel() != Hp or b2h.numel() != Hp or b3h.numel() != D:
+        raise _l.St355Error(f"st_fold: expected contiguous W1h [Hp, D], W1T [D, Hp], b1h [Hp], W2h [Hp, Hp], W2T [Hp, Hp], b2h [Hp], W3h [D, Hp], W3T [Hp, P3], b3h [D] "
+                            f"with D = {D}, Hp = {Hp}")
+    _al16("st_fold", *outs)
+    _l.check(L.st355_st_fold(_stream(), *(_ptr(t) for t in (W1, b1, W2, b2, W3, b3)), *(_ptr(t) for t in outs), D, Hp, P3), "st_fold")
+    return outs
+
+
+def _st_loss_operands(name: str, pred, sigmas, tmin, tmax, B: int, S: int, Pc: int, per_sample, stats):
+    _chk(pred, BF16, "pred"); _chk(sigmas, F32, "sigmas"); _chk(per_sample, F32, "per_sample"); _chk(stats, F32, "stats")
+    if not float(tmin) <= float(tmax):
+        raise _l.St355Error(f"{name}: the timestep range must satisfy min <= max (got {tmin}, {tmax})")
+    if tuple(pred.shape) != (B * S, Pc) or not pred.is_contiguous() or Pc % 8:
+        raise _l.St355Error(f"{name}: expected contiguous pred [{B * S}, {Pc}] bf16 with a multiple of 8 columns, got {tuple(pred.shape)}")
+    if sigmas.numel() != B or per_sample.numel() != B or stats.numel() != 3 or not (sigmas.is_contiguous() and per_sample.is_contiguous() and stats.is_contiguous()):
+        raise _l.St355Error(f"{name}: expected contiguous sigmas [{B}], per_sample [{B}] and stats [3] fp32")
+    if B > 4096:
+        raise _l.St355Error(f"{name}: at most 4096 samples (got {B})")
+    _al16(name, pred)
+
+
+def st_vae_loss(pred, target, grid, sigmas, tmin: float, tmax: float, per_sample, stats):
+    """Self-Transcendence stage `vae` (st355_st_vae_loss): pred [B * S, P] compact bf16 against the diffusion target [B, C, H, W] (bf16 or fp32) read in place on the
+    gh x gw token grid (grid = (gh, gw), gh * gw == S; P = C (H / gh) (W / gw), columns in (c, a, e) order).  per_sample [B] = the per-sample means of (pred - t)^2;
+    sample b is active iff tmin <= sigmas[b] <= tmax (on the device); stats [3] = (the mean of the active samples' means or 0, their count, 1 / (count S P) or 0);
+    pred <- G = 2 (pred - t) of an active sample, exactly 0 otherwise.  Nothing is read on the host."""
+    L = _l.load()
+    _dev(target, "target")
+    if target.dtype not in (BF16, F32) or target.dim() != 4:
+        raise _l.St355Error(f"st_vae_loss: expected the target [B, C, H, W] in bf16 or fp32, got {tuple(target.shape)} {target.dtype}")
+    B, Cc, H, W = target.shape
+    gh, gw = (int(v) for v in grid)
+    if gh <= 0 or gw <= 0 or H % gh or W % gw:
+        raise _l.St355Error(f"st_vae_loss: the token grid {(gh, gw)} does not divide the latent shape {(H, W)}")
+    S, P = gh * gw, Cc * (H // gh) * (W // gw)
+    if not target[0].is_contiguous() or (B > 1 and target.stride(0) < Cc * H * W):
+        raise _l.St355Error(f"st_vae_loss: every sample of the target must be contiguous, samples at least C * H * W elements apart (strides {target.stride()})")
+    _st_loss_operands("st_vae_loss", pred, sigmas, tmin, tmax, B, S, P, per_sample, stats)
+    ws = _scratch("st_loss", pred.device, L.st355_st_loss_workspace(B, S * P))
+    _l.check(L.st355_st_vae_loss(_stream(), _ptr(pred), _ptr(target), int(target.dtype == BF16), target.stride(0) if B > 1 else Cc * H * W, _ptr(sigmas), float(tmin),
+                                 float(tmax), B, S, Cc, H, W, gh, gw, _ptr(per_sample), _ptr(stats), _ptr(ws)), "st_vae_loss")
+    return stats
+
+
+def st_cfg_loss(pred, capture, cfg_scale: float, sigmas, tmin: float, tmax: float, per_sample, stats):
+    """Self-Transcendence stage `self` (st355_st_cfg_loss): pred [B * S, D] compact bf16 against u + cfg_scale (c - u) formed in fp32, c = capture[:B], u = capture[B:]
+    of the teacher's [2B, S, D] bf16 capture (a view: unit inner stride, strides multiples of 8).  Outputs as st_vae_loss."""
+    L = _l.load()
+    B2, S, D, ld, bs = _token_view(capture, "capture")
+    if B2 % 2 or B2 == 0:
+        raise _l.St355Error(f"st_cfg_loss: the capture holds the conditional rows, then the unconditional rows: an even batch (got {B2})")
+    B = B2 // 2
+    if D % 8 or ld % 8 or bs % 8 or (B2 > 1 and bs < S * ld):
+        raise _l.St355Error(f"st_cfg_loss: D and the capture's strides must be multiples of 8 elements (got D = {D}, strides {capture.stride()})")
+    _st_loss_operands("st_cfg_loss", pred, sigmas, tmin, tmax, B, S, D, per_sample, stats)
+    cond, unc = capture[:B], capture[B:]
+    _al16("st_cfg_loss", cond, unc)
+    ws = _scratch("st_loss", pred.device, L.st355_st_loss_workspace(B, S * D))
+    _l.check(L.st355_st_cfg_loss(_stream(), _ptr(pred), _ptr(cond), _ptr(unc), ld, bs, float(cfg_scale), _ptr(sigmas), float(tmin), float(tmax), B, S, D,
+                                 _ptr(per_sample), _ptr(stats), _ptr(ws)), "st_cfg_loss")
+    return stats
+
+
+def st_wgrad(P, db, scale, g_W, g_b, accumulate: bool = False):
+    """gradients of one of the projector's Linears (st355_st_wgrad): g_W [R, Cc] fp32 = s P (P bf16 = dY^T A, gemm_tn), g_b [R] fp32 = s db (db fp32 = colsum(dY),
+    colsum_prod); s ONE fp32 on the device (the upstream gradient times the loss kernel's normaliser).  accumulate adds to what the gradients hold."""
+    L = _l.load()
+    _chk(P, BF16, "P"); _chk(db, F32, "db"); _chk(g_W, F32, "g_W"); _chk(g_b, F32, "g_b")
+    _nextlat_scale("st_wgrad", scale)
+    if P.dim() != 2 or P.shape[1] % 8:
+        raise _l.St355Error(f"st_wgrad: expected P [R, Cc] with Cc a multiple of 8, got {tuple(P.shape)}")
+    R, Cc = P.shape
+    if tuple(g_W.shape) != (R, Cc) or db.numel() != R or g_b.numel() != R or not all(t.is_contiguous() for t in (P, db, g_W, g_b)):
+        raise _l.St355Error(f"st_wgrad: expected contiguous P [{R}, {Cc}] bf16, db [{R}] fp32, g_W [{R}, {Cc}], g_b [{R}] fp32")
+    _al16("st_wgrad", P, g_W)
+    _l.check(L.st355_st_wgrad(_stream(), _ptr(P), _ptr(db), _ptr(scale), _ptr(g_W), _ptr(g_b), R, Cc, 1 if accumulate else 0), "st_wgrad")
+    return g_W, g_b
+
+
+def st_dx_add(g, scale, dx):
+    """the projector's input gradient into the dX chain (st355_st_dx_add): dx, a [B, rows, D] bf16 view, = bf16(float(dx) + s g), g [B * rows, D] compact bf16,
+    s ONE fp32 on the device.  In place."""
+    L = _l.load()
+    B, rows, D, ld, bs = _token_view(dx, "dx")
+    _chk(g, BF16, "g")
+    _nextlat_scale("st_dx_add", scale)
+    if D % 8 or ld % 8 or bs % 8 or (B > 1 and bs < rows * ld):
+        raise _l.St355Error(f"st_dx_add: D and the view's strides must be multiples of 8 elements (got D = {D}, strides {dx.stride()})")
+    if tuple(g.shape) != (B * rows, D) or not g.is_contiguous():
+        raise _l.St355Error(f"st_dx_add: expected contiguous g [{B * rows}, {D}]")
+    _al16("st_dx_add", g, dx)
+    _l.check(L.st355_st_dx_add(_stream(), _ptr(g), _ptr(scale), _ptr(dx), B, rows, D, ld, bs), "st_dx_add")
+    return dx
+
+
 def lora_pack(A, Bm, scale: float, A_cat, A_cat_T, B_blk, B_blk_T, k2_off: int = 0, n_off: int = 0):
     """write one adapter (A [r,K], B [N,r], fp32) into the block-structured bf16 operands of a fused projection group"""
     L = _l.load()

@@ -25,6 +25,7 @@ class SD3(ModelFoundation):
     DORA_BUILT = True
     LYCORIS_BUILT = True
     SELF_FLOW_BUILT = True
+    SELF_TRANSCENDENCE_BUILT = True
     ROLLOUT_BATCH_KEYS = ("encoder_hidden_states", "add_text_embeds")          # what _model_predict_single reads per sample (scheduled sampling's batch-1 forwards)
     LATENT_CHANNEL_COUNT = 16
     COMFYUI_LORA_PRESERVE_COMPONENT_PREFIXES = {"transformer"}      # sd3/model.py:117
@@ -48,6 +49,16 @@ class SD3(ModelFoundation):
             # Self-Flow: the projector goes to the tail of the adapter arena, so the component learns its blocks ahead of add_lora_adapter (post_model_load_setup
             # repeats the checks in the reference's order and refuses what this path does not take)
             self.model.set_self_flow(getattr(self.config, "crepa_block_index", None), getattr(self.config, "crepa_teacher_block_index", None))
+        if getattr(self.config, "distillation_method", None):
+            from ..flow_dpo import method_of
+            if method_of(self.config) == "self_transcendence" and str(getattr(self.config, "model_type", "lora")) == "lora" \
+                    and str(getattr(self.config, "lora_type", "standard") or "standard").lower() == "standard":
+                # Self-Transcendence: the projector goes to the tail of the adapter arena, so the component learns its settings ahead of add_lora_adapter (the
+                # distiller repeats the checks in the reference's order and refuses what this path does not take)
+                from ..self_transcendence import settings_of
+                s = settings_of(self.config)
+                self.model.set_self_transcendence(s["stage"], s["student_block"], s["teacher_block"], s["projector_hidden_dim"], s["timestep_min"],
+                                                  s["timestep_max"], s["cfg_scale"])
         if state_dict is not None and getattr(self.config, "twinflow_enabled", False):
             from ..twinflow import drop_sign_embedding          # TwinFlow: a zero time-sign table adds nothing under LoRA and is dropped, a trained one is refused
             state_dict = drop_sign_embedding(state_dict)
@@ -102,6 +113,11 @@ class SD3(ModelFoundation):
         extra = {}
         if getattr(self, "self_flow", None) is not None and torch.is_grad_enabled() and prepared_batch.get("crepa_teacher_noisy_latents") is not None:
             extra["crepa_teacher_features"] = self._self_flow_teacher_features(prepared_batch)          # the teacher forward first, then the training forward with the tap
+        st = getattr(self, "self_transcendence", None)
+        if st is not None and prepared_batch.get("self_transcendence_capture_block") is not None:
+            extra["crepa_capture_block_index"] = prepared_batch["self_transcendence_capture_block"]     # Self-Transcendence's teacher forward (no grad, ends behind the block)
+        elif st is not None and torch.is_grad_enabled():
+            extra.update(st.forward_inputs(self, prepared_batch))                                      # (stage `self`: the teacher forward first, as Self-Flow does)
         res = self.model(
             hidden_states=prepared_batch["noisy_latents"].to(device=dev, dtype=BF16),
             timestep=prepared_batch["timesteps"].to(device=dev, dtype=torch.float32),
@@ -113,7 +129,8 @@ class SD3(ModelFoundation):
         )
         # further outputs travel by name; (a component that hands back a plain tuple has only its sample)
         out = {"model_prediction": res[0] if isinstance(res, tuple) else res.sample, "crepa_hidden_states": None, "hidden_states_buffer": None}
-        for k in ("layersync_similarity", "internal_guidance_prediction", "nextlat_state_loss", "crepa_similarity"):          # LayerSync / Internal Guidance / NextLat / Self-Flow: the training forward's further outputs
+        for k in ("layersync_similarity", "internal_guidance_prediction", "nextlat_state_loss", "crepa_similarity", "self_transcendence_guide_loss") \
+                + (("crepa_hidden_states",) if "crepa_capture_block_index" in extra else ()):          # LayerSync / Internal Guidance / NextLat / Self-Flow: the training forward's further outputs
             if getattr(res, k, None) is not None:
                 out[k] = getattr(res, k)
         return out

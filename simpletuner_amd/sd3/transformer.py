@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, SELF_FLOW_NAMES, AdapterArena, CaptureTap, SelfFlowHead, SelfFlowTap, self_flow_indices, self_flow_shapes, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
+from ..engine import (IG_NAMES, NEXTLAT_NAMES, SELF_FLOW_NAMES, ST_NAMES, SelfTranscendenceHead, SelfTranscendenceTap, self_transcendence_indices, self_transcendence_shapes, AdapterArena, CaptureTap, SelfFlowHead, SelfFlowTap, self_flow_indices, self_flow_shapes, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
                       NextLatTap, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
                       lora_fwd_kw, lora_grads, lora_pairs, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
@@ -128,6 +128,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         self._layersync = None           # set_layersync(): 0-based (student, teacher) joint-block indices
         # Self-Flow (set_self_flow): the 0-based student / teacher blocks, the projector at the tail of the adapter arena, the teacher features of the next training forward
         self._sf_block, self._sf_teacher_block, self._sf, self._sf_feats, self._sf_tap = None, None, None, None, None
+        # Self-Transcendence (set_self_transcendence): its settings, the projector at the tail of the adapter arena, the (target, sigmas) of the next training forward
+        self._st_cfg, self._st, self._st_in = None, None, None
         self.grad_sync = None
         self._last_grad_flat = None
         self.full = False
@@ -325,6 +327,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         # Self-Flow: the projector's fp32 masters likewise (it excludes the two heads above), from a 16-byte boundary
         sf = [arena.add("crepa_projector." + nm, shp, align=1 if k else 8) for k, (nm, shp) in enumerate(zip(SELF_FLOW_NAMES, self_flow_shapes(D)))] \
             if self._sf_block is not None else []
+        # Self-Transcendence: the projector's fp32 masters likewise (it excludes every head above)
+        st = [arena.add("self_transcendence_projector." + nm, shp, align=1 if k else 8)
+              for k, (nm, shp) in enumerate(zip(ST_NAMES, self_transcendence_shapes(D, self._st_cfg.hidden_dim)))] if self._st_cfg is not None else []
         if sf and dora:
             raise NotImplementedError("crepa_enabled (self_flow) with use_dora: the teacher forward packs the adapters from the EMA shadow, which the DoRA fold does not "
                                       "take; not built on the st355 path")
@@ -351,6 +356,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if sf:
             self._sf = SelfFlowHead(self._sf_block, self._sf_teacher_block, D, [s.p for s in sf], [s.g for s in sf], sf[0].lo, sf[-1].hi, dev)
             self._sf.init_reference(gen)             # nn.LayerNorm / nn.Linear defaults, drawn in fp32 from the adapters' generator behind every A / B draw
+        if st:
+            self._st = SelfTranscendenceHead(self._st_cfg.student_block, D, self._st_cfg.hidden_dim, [s.p for s in st], [s.g for s in st], st[0].lo, st[-1].hi, dev)
+            self._st.init_reference(gen)             # nn.Linear's defaults, drawn in fp32 from the adapters' generator behind every A / B draw
         return self._lora_params
 
     # ------------------------------------------------------------------------------------------------
@@ -369,6 +377,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for k in factors:
             if k not in self.LOKR_CLASSES:
                 raise NotImplementedError(f"lycoris lokr: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
+        if self._st_cfg is not None:
+            raise ValueError("Self-Transcendence supports full-model and standard PEFT LoRA training; LyCORIS is not supported.")
         if self._ig_block is not None or self._nl_block is not None or self._sf_block is not None:
             raise NotImplementedError("lycoris lokr with an Internal Guidance head / a NextLat predictor / a Self-Flow projector is not built on the st355 path")
         dev = self.device_
@@ -440,6 +450,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         for k in classes:
             if k not in self.LOKR_CLASSES:
                 raise NotImplementedError(f"lycoris tlora: target_module entry {k!r} is not built on the st355 path (built: {', '.join(self.LOKR_CLASSES)})")
+        if self._st_cfg is not None:
+            raise ValueError("Self-Transcendence supports full-model and standard PEFT LoRA training; LyCORIS is not supported.")
         if self._ig_block is not None or self._nl_block is not None or self._sf_block is not None:
             raise NotImplementedError("lycoris tlora with an Internal Guidance head / a NextLat predictor / a Self-Flow projector is not built on the st355 path")
         rank, a, mult = int(linear_dim), int(linear_alpha), int(multiplier)
@@ -1187,7 +1199,54 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             self._sf_tap = SelfFlowTap(self._sf, self._sf_feats)
             self._sf_feats = None
             taps.append(self._sf_tap)
+        if self._st_cfg is not None and save:
+            c = self._st_cfg
+            if routed:
+                raise NotImplementedError("distillation_method=self_transcendence under TREAD routing (the routed block's token count no longer matches the target's) is "
+                                          "not built on the st355 path")
+            if tokenwise:
+                raise NotImplementedError("distillation_method=self_transcendence with tokenwise timesteps is not built on the st355 path")
+            if self._st is None:
+                raise RuntimeError("Self-Transcendence: no projector is laid out for training (add_lora_adapter() after set_self_transcendence())")
+            target, sigmas = self._st_in or (None, None)
+            self._st_in = None
+            taps.append(SelfTranscendenceTap(self._st, c.stage, target, sigmas, c.timestep_min, c.timestep_max, c.cfg_scale, off=c.off))
         return taps
+
+    def set_self_transcendence(self, stage: str, student_block, teacher_block=None, hidden_dim: int = 2048, timestep_min: float = 0.4, timestep_max: float = 0.7,
+                               cfg_scale: float = 30.0):
+        """Self-Transcendence (helpers/distillation/self_transcendence/distiller.py; the reference reads `layer_{i}` of the hidden-state buffer filled at
+        sd3/transformer.py:872): the 0-based joint block whose image-stream output feeds the projector Linear(D -> hidden_dim) -> SiLU -> Linear -> SiLU ->
+        Linear(hidden_dim -> D), and — stage `self` — the block of the frozen teacher's forward it is trained to.  Call it before `add_lora_adapter` (the projector's
+        fp32 masters go to the tail of the adapter arena).  A training forward then takes `self_transcendence_target` (stage `vae`: the diffusion target
+        [B, C, H, W]; stage `self`: what a no-grad forward at batch 2B — conditional rows, then unconditional — with `crepa_capture_block_index=teacher_block` inside
+        `teacher_values(snapshot)` returned as `crepa_hidden_states`) and `self_transcendence_sigmas` [B], and also returns the masked per-sample MSE
+        `self_transcendence_guide_loss`; the backward takes its gradient at the student block.  `self_transcendence_off(True)`: the weight is 0 from here on —
+        the tap launches nothing.  LoRA only."""
+        if stage not in ("vae", "self"):
+            raise ValueError("Self-Transcendence stage must be either 'vae' or 'self'.")
+        s_, t_ = self_transcendence_indices(student_block, teacher_block, len(self.blocks))
+        if stage == "self" and t_ is None:
+            raise ValueError("Self-Transcendence self stage requires teacher_block.")
+        if self._ig_block is not None or self._nl_block is not None or self._sf_block is not None or self._layersync is not None:
+            raise NotImplementedError("distillation_method=self_transcendence together with LayerSync / Internal Guidance / NextLat / Self-Flow is not built on the st355 "
+                                      "path (they claim the same arena tail)")
+        if self.full:
+            raise NotImplementedError("distillation_method=self_transcendence under a full fine-tune is not built on the st355 path (built: SD3 LoRA)")
+        cfg = SimpleNamespace(stage=stage, student_block=s_, teacher_block=t_, hidden_dim=int(hidden_dim), timestep_min=float(timestep_min),
+                              timestep_max=float(timestep_max), cfg_scale=float(cfg_scale), off=False)
+        if self._st is not None:
+            if cfg.hidden_dim != self._st.Hp:
+                raise RuntimeError(f"set_self_transcendence: the projector is laid out with projector_hidden_dim={self._st.Hp}, not {cfg.hidden_dim}")
+            self._st_cfg, self._st.block = cfg, s_          # the projector exists: only the tap and its settings move
+            return
+        if self.lora_groups:
+            raise RuntimeError("set_self_transcendence: the trainable arena is already laid out without the projector — call it before add_lora_adapter()")
+        self._st_cfg = cfg
+
+    def self_transcendence_off(self, off: bool = True):
+        """stop_step reached: the guide loss takes no part from here on — the tap launches nothing, returns a constant 0 and zeroes the projector's gradient views"""
+        self._st_cfg.off = bool(off)
 
     def set_self_flow(self, student_block, teacher_block):
         """Self-Flow (CREPA with crepa_feature_source=self_flow; the reference captures `layer_{i}` at sd3/transformer.py:872): the 0-based joint block whose
@@ -1196,6 +1255,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         forward with `crepa_capture_block_index=teacher_block` inside `teacher_values(shadow)` returned as `crepa_hidden_states` — and also returns the mean cosine
         `crepa_similarity`; the backward takes its gradient at the student block.  LoRA only: a full fine-tune refuses tokenwise timesteps."""
         s_, t_ = self_flow_indices(student_block, teacher_block, len(self.blocks))
+        if self._st_cfg is not None:
+            raise NotImplementedError("distillation_method=self_transcendence together with Self-Flow is not built on the st355 path (both claim the tail of the arena that trains)")
         if self._ig_block is not None or self._nl_block is not None or self._layersync is not None:
             raise NotImplementedError("crepa_enabled (self_flow) together with LayerSync / Internal Guidance / NextLat is not built on the st355 path (they refuse tokenwise "
                                       "timesteps or claim the same arena tail)")
@@ -1220,6 +1281,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         adapter arena); a full fine-tune needs the constructor's `internal_guidance_block_index` (the head lives inside the base parameter arena, laid out once).
         A training forward then also returns the head's [B, 16, H, W] prediction and the backward takes its gradient at that block."""
         i = internal_guidance_index(block_index, len(self.blocks))
+        if self._st_cfg is not None:
+            raise NotImplementedError("distillation_method=self_transcendence together with LayerSync / Internal Guidance / NextLat / Self-Flow is not built on the st355 "
+                                      "path (they claim the same arena tail)")
         if self._sf_block is not None:
             raise NotImplementedError("crepa_enabled (self_flow) together with Internal Guidance is not built on the st355 path (both claim the tail of the arena that trains)")
         if self._nl_block is not None:
@@ -1243,6 +1307,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         if state_loss not in ops.NEXTLAT_MODES:
             raise ValueError("nextlat_state_loss must be 'smooth_l1' or 'mse'.")
         i = nextlat_index(configured_index, len(self.blocks))
+        if self._st_cfg is not None:
+            raise NotImplementedError("distillation_method=self_transcendence together with LayerSync / Internal Guidance / NextLat / Self-Flow is not built on the st355 "
+                                      "path (they claim the same arena tail)")
         if self._sf_block is not None:
             raise NotImplementedError("crepa_enabled (self_flow) together with NextLat is not built on the st355 path (both claim the tail of the arena that trains)")
         if self._ig_block is not None:
@@ -1275,6 +1342,9 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         """LayerSync (helpers/training/layersync.py; the reference captures at sd3/transformer.py:872): 0-based joint-block indices.  A training forward then also
         returns the mean cosine between the two blocks' image-stream outputs (teacher detached) and the backward adds its gradient into the dX chain at the
         student block."""
+        if self._st_cfg is not None:
+            raise NotImplementedError("distillation_method=self_transcendence together with LayerSync / Internal Guidance / NextLat / Self-Flow is not built on the st355 "
+                                      "path (they claim the same arena tail)")
         if self._sf_block is not None:
             raise NotImplementedError("crepa_enabled (self_flow) together with LayerSync is not built on the st355 path (LayerSync refuses tokenwise timesteps)")
         self._layersync = layersync_indices(student_idx, teacher_idx, len(self.blocks))
@@ -1465,7 +1535,8 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
     # ------------------------------------------------------------------------------------------------
     def forward(self, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None, block_controlnet_hidden_states=None,
                 joint_attention_kwargs=None, return_dict: bool = True, force_keep_mask=None, return_internal_guidance: bool = False,
-                crepa_capture_block_index: Optional[int] = None, crepa_teacher_features=None, **unsupported):
+                crepa_capture_block_index: Optional[int] = None, crepa_teacher_features=None, self_transcendence_target=None, self_transcendence_sigmas=None,
+                **unsupported):
         self._force_keep_mask = force_keep_mask            # TREAD: tokens that may never be routed away (sd3/transformer.py:571, 699-703)
         if block_controlnet_hidden_states is not None:
             raise NotImplementedError("SD3 ControlNet residuals are not wired to the st355 path yet")
@@ -1481,6 +1552,10 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             if self._sf_block is None or not need_grad:
                 raise ValueError("crepa_teacher_features: only a training forward of a component with set_self_flow() takes teacher features")
             self._sf_feats = crepa_teacher_features
+        if self_transcendence_target is not None or self_transcendence_sigmas is not None:          # Self-Transcendence's training forward: what its tap is trained to
+            if self._st_cfg is None or not need_grad:
+                raise ValueError("self_transcendence_target: only a training forward of a component with set_self_transcendence() takes a target")
+            self._st_in = (self_transcendence_target, self_transcendence_sigmas)
         if need_grad and not self._prepared and not getattr(self, "full", False):
             self.prepare_for_training()      # K-major dgrad operands went stale (new weights / replica start-state broadcast): rebuild lazily
         if need_grad:      # the training nodes return every tap's output (the similarity / the head's prediction / the state loss) behind the prediction, in the taps' order

@@ -233,9 +233,16 @@ class Trainer:
         if hasattr(self.model, "scheduled_sampling_value"):
             self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
         self.distiller = None
-        if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Flow-DPO (every other method is refused by name)
-            from ..flow_dpo import create_distiller
+        self._self_transcendence = False
+        if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Self-Transcendence, Flow-DPO (every other method is refused by name)
+            from ..flow_dpo import create_distiller, method_of
+            if method_of(config) == "self_transcendence":
+                from ..self_transcendence import create_distiller
+                self._self_transcendence = True
             self.distiller = create_distiller(self.model)
+            if self._self_transcendence:
+                self.model.self_transcendence = self.distiller           # the plugin's training forward asks it what the tap is trained to
+        self._loop_step = None         # the training loop's own step counter (trainer.py:6876, 6955): what a distiller's pre_training_step is handed
         # evaluation loss (trainer.py:7480-7495): built only when an interval is set and eval_loss_disable is false — otherwise nothing is imported, allocated or launched.
         # `eval_sets`: {name: re-iterable of raw batches}, the seam of the reference's _type="eval" backends
         self.evaluation = None
@@ -309,6 +316,21 @@ class Trainer:
         if self._use_graph:
             loss = self._graph_forward_backward(prepared)
             self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)
+        elif self._self_transcendence:
+            # Self-Transcendence (trainer.py:7000, 6119-6131): pre_training_step with the loop's own counter, the plain step's forward (the projector runs at its
+            # block, inside it), the plugin's loss and auxiliary_loss, then the distill loss
+            self._loop_step = (self.state["global_step"] if self._loop_step is None else self._loop_step) + 1
+            self.distiller.pre_training_step(self.model, self._loop_step)
+            pred = self.model.model_predict(prepared)
+            loss, loss_logs = self.model.loss_with_logs(prepared, pred)
+            self.distiller.prepare_model_output(pred)
+            loss, self.last_aux_logs = self.model.auxiliary_loss(pred, prepared, loss)
+            loss, distill_logs = self.distiller.compute_distill_loss(prepared, pred, loss)
+            self.last_aux_logs = {**(loss_logs or {}), **(self.last_aux_logs or {}), **distill_logs}
+            if cfg.gradient_accumulation_steps > 1:
+                loss = loss / cfg.gradient_accumulation_steps
+            self.last_loss = gather_sample_weighted_scalar(loss, prepared["latents"].shape[0], acc)
+            acc.backward(loss)
         elif self.distiller is not None:
             # Flow-DPO (trainer.py:6432-6434, 6109-6132): the distiller's prepare_batch, ONE training forward over the doubled batch (preferred rows, then
             # rejected), the plugin's own loss on the preferred rows, then the distill loss (its reference forward runs inside, adapters off, no grad)
@@ -568,6 +590,7 @@ class Trainer:
             ts = json.load(fh)
         self.state.update({k: ts[k] for k in ("global_step", "epoch_step", "epoch", "exhausted_backends", "repeats") if k in ts})
         self.state["micro_step"] = int(ts.get("micro_step", self.state["global_step"] * self.config.gradient_accumulation_steps))
+        self._loop_step = None                    # (the loop's own counter restarts from the loaded global step, trainer.py:6876)
         tlora = getattr(comp, "lora_tlora", None)
         if tlora is not None and "tlora" in ts:   # T-LoRA: a resumed run trains under the mask the checkpoint was trained under
             own = {"min_rank": tlora.Rmin, "alpha": tlora.alpha, "num_train_timesteps": tlora.T}
