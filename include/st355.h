@@ -756,6 +756,31 @@ int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred_stride, co
                          int table_len, int mode, const float* weight, const float* emask, int64_t mask_period, float* loss_out, float* per_sample_out,
                          void* dpred, void* workspace, int64_t batch, int64_t per_sample, float grad_scale);
 
+/* ---- LCM distillation of the epsilon / v families (distillation_method=lcm; helpers/distillation/lcm/__init__.py, DDPM branch; csrc/lcm.hip) and its sampler.
+ * sched: fp32 [sched_len, 2] = (sqrt(acp_t), sqrt(1 - acp_t)); prev: fp32 [prev_len, 2] = (sqrt(acp_prev_i), sqrt(1 - acp_prev_i)) of the DDIM solver; index / start /
+ * timesteps: int64 [batch] on the device; every gather is clamped to its table.  mode 0 (epsilon): x0 = (x - s p) / a, eps = p; mode 1 (v): x0 = a x - s p,
+ * eps = a p + s x.  Scalings of a timestep t, S = timestep_scaling t: c_skip = 0.25 / (S^2 + 0.25), c_out = S / sqrt(S^2 + 0.25).  All arithmetic fp32.  16 bytes per
+ * lane where per_sample is a multiple of 8 and the pointers 16-byte aligned, else the same walk with scalar accesses.
+ *   st355_lcm_solver_step: x_s bf16 [batch, per_sample]; teacher_pair bf16 [2 batch, per_sample], conditional rows first; w fp32 [batch].  p = p_u + w (p_c - p_u);
+ *     x_prev = prev[index].0 x0 + prev[index].1 eps at (x_s, sched[start]), written as fp32 (x_prev32) and, rounded once, as bf16 (x_prev16).
+ *   st355_lcm_target: target (fp32) = c_skip(t) x_prev32 + c_out(t) x0(pred_t bf16 at (x_prev32, sched[t])); rows with t = 0 get x_prev32 exactly.
+ *   st355_lcm_loss: m = c_skip(start) x_s + c_out(start) x0(pred at (x_s, sched[start])), d = m - target (fp32); loss_type 0 (l2): d^2, 1 (huber): sqrt(d^2 + c^2) - c;
+ *     per_sample_out[b] = mean_i, loss_out[0] = mean_b per_sample_out[b]; dpred (bf16, one rounding, may be NULL) = grad_scale g(d) c_out(start) (dx0/dp) /
+ *     (batch per_sample), g = 2 d or d / sqrt(d^2 + c^2), dx0/dp = -s / a or -s.  The reduction runs in two stages in a fixed order (bit-identical run to run), the
+ *     second on the device; `workspace`: st355_lcm_workspace bytes.
+ *   st355_lcm_sample_step: one LCMScheduler step over `total` elements, every sample at timestep t: denoised = c_skip(t) x + c_out(t) x0(pred at (x, sched[t]));
+ *     out (bf16) = sched[t_next].0 denoised + sched[t_next].1 noise, or denoised on the last step (t_next < 0; noise may then be NULL). */
+int64_t st355_lcm_workspace(int64_t batch, int64_t per_sample);
+int st355_lcm_solver_step(void* stream, const void* x_s, const void* teacher_pair, const float* w, const int64_t* index, const int64_t* start, const float* sched,
+                          int sched_len, const float* prev, int prev_len, int mode, float* x_prev32, void* x_prev16, int64_t batch, int64_t per_sample);
+int st355_lcm_target(void* stream, const float* x_prev32, const void* pred_t, const int64_t* timesteps, const float* sched, int sched_len, int mode,
+                     float timestep_scaling, float* target, int64_t batch, int64_t per_sample);
+int st355_lcm_loss(void* stream, const void* pred, const void* x_s, const float* target, const int64_t* start, const float* sched, int sched_len, int mode,
+                   float timestep_scaling, int loss_type, float huber_c, float* loss_out, float* per_sample_out, void* dpred, void* workspace, int64_t batch,
+                   int64_t per_sample, float grad_scale);
+int st355_lcm_sample_step(void* stream, const void* x, const void* pred, const void* noise, const float* sched, int sched_len, int mode, float timestep_scaling,
+                          int64_t t, int64_t t_next, void* out, int64_t total);
+
 /* ---- T-LoRA (lora_type=lycoris, `algo: tlora`; csrc/tlora.hip): y_b = base(x_b) + s (mask_b . (x_b A^T)) B^T, mask_b = the first r_b rank columns of sample b.
  * st355_tlora_mask zeroes, in place, the inactive rank columns of a rank-space operand of a LoraGroup (T = x A_cat^T, U = dy B_blk_T): t is bf16 with M logical
  * rows of row stride ld (compact when seg_rows == 0, else segments of seg_rows rows seg_stride ROWS apart, as the LoRA-dropout kernels take them), G targets of r_pad

@@ -40,6 +40,7 @@ SYMBOLS = [
     "st355_reflexflow_workspace", "st355_reflexflow_stats", "st355_reflexflow_loss", "st355_flow_euler_step",
     "st355_flow_dpo_workspace", "st355_flow_dpo_stats", "st355_flow_dpo_head", "st355_flow_dpo_grad",
     "st355_diff2flow_workspace", "st355_diff2flow_loss",
+    "st355_lcm_workspace", "st355_lcm_solver_step", "st355_lcm_target", "st355_lcm_loss", "st355_lcm_sample_step",
     "st355_tlora_mask",
     "st355_self_flow_views", "st355_self_flow_fold", "st355_self_flow_rows", "st355_self_flow_wgrad_workspace", "st355_self_flow_wgrad",
     "st355_st_fold", "st355_st_loss_workspace", "st355_st_vae_loss", "st355_st_cfg_loss", "st355_st_wgrad", "st355_st_dx_add",
@@ -425,6 +426,11 @@ def _declare(lib):
         "st355_flow_dpo_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, f32, f32, vp]),
         "st355_diff2flow_workspace": (i64, [i64, i64]),
         "st355_diff2flow_loss": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i64, i64, f32]),
+        "st355_lcm_workspace": (i64, [i64, i64]),
+        "st355_lcm_solver_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, i64, i64]),
+        "st355_lcm_target": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, f32, vp, i64, i64]),
+        "st355_lcm_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, f32, vp, vp, vp, vp, i64, i64, f32]),
+        "st355_lcm_sample_step": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, f32, i64, i64, vp, i64]),
         "st355_tlora_mask": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, vp, i32]),
         "st355_self_flow_views": (C.c_int, [vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
         "st355_self_flow_fold": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),

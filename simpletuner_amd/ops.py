@@ -455,6 +455,114 @@ def diff2flow_loss(pred, noisy, tau, timesteps, table, mode: str = "epsilon", we
     return loss, per_sample, dpred
 
 
+LCM_MODES = DIFF2FLOW_MODES
+LCM_LOSSES = {"l2": 0, "huber": 1}
+
+
+def _lcm_rows(name, mode, tensors, index_like, tables):
+    """the operands of the LCM kernels: `tensors` (name, tensor, dtype, rows per sample-batch) of one [B, ...] shape (the teacher pair has 2B rows), `index_like` int64 [B]
+    vectors, `tables` contiguous fp32 [len, 2]; returns (B, N) and the tensors made contiguous, in order"""
+    if mode not in LCM_MODES:
+        raise _l.St355Error(f"{name}: mode must be one of {sorted(LCM_MODES)}, got {mode!r}")
+    lead = tensors[0][1]
+    B = lead.shape[0]
+    N = lead.numel() // B if B else 0
+    if N <= 0 or not 0 < B < 32768:
+        raise _l.St355Error(f"{name}: the batch {B} must lie in [1, 32767] and the per-sample size {N} be positive")
+    out = []
+    for nm, t, dt, mult in tensors:
+        _chk(t, dt, nm)
+        if t.shape[0] != mult * B or t.numel() != mult * B * N:
+            raise _l.St355Error(f"{name}: {nm} {tuple(t.shape)} must hold {mult * B} rows of {N} elements")
+        out.append(t.contiguous())
+    for nm, t in index_like:
+        _chk(t, torch.int64, nm)
+        if t.numel() != B:
+            raise _l.St355Error(f"{name}: {nm}: expected {B} values, got {t.numel()}")
+        out.append(t.reshape(-1).contiguous())
+    for nm, t in tables:
+        _chk(t, F32, nm)
+        if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1 or not t.is_contiguous():
+            raise _l.St355Error(f"{name}: {nm}: expected a contiguous fp32 [len, 2] tensor, got {tuple(t.shape)}")
+    return (B, N), out
+
+
+def lcm_solver_step(x_s, teacher_pair, w, index, start, sched, prev, mode: str = "epsilon"):
+    """The teacher's DDIM solver step of LCM distillation (lcm/__init__.py:229-252) in one pass.  teacher_pair bf16 [2B, ...]: the conditional predictions, then the
+    unconditional ones; p = p_u + w (p_c - p_u); x0 / eps of p at (x_s, sched[start]) by `mode`; x_prev = prev[index].0 x0 + prev[index].1 eps.  Returns (x_prev fp32,
+    x_prev bf16), both of x_s's shape."""
+    L = _l.load()
+    (B, N), (x_s, teacher_pair, index, start) = _lcm_rows("lcm_solver_step", mode, [("x_s", x_s, BF16, 1), ("teacher_pair", teacher_pair, BF16, 2)],
+                                                          [("index", index), ("start", start)], [("sched", sched), ("prev", prev)])
+    _chk(w, F32, "w")
+    if w.numel() != B:
+        raise _l.St355Error(f"lcm_solver_step: w: expected {B} values, got {w.numel()}")
+    w = w.reshape(-1).contiguous()
+    x32 = torch.empty(x_s.shape, dtype=F32, device=x_s.device)
+    x16 = torch.empty(x_s.shape, dtype=BF16, device=x_s.device)
+    _l.check(L.st355_lcm_solver_step(_stream(), _ptr(x_s), _ptr(teacher_pair), _ptr(w), _ptr(index), _ptr(start), _ptr(sched), sched.shape[0], _ptr(prev), prev.shape[0],
+                                     LCM_MODES[mode], _ptr(x32), _ptr(x16), B, N), "lcm_solver_step")
+    return x32, x16
+
+
+def lcm_target(x_prev32, pred_t, timesteps, sched, mode: str = "epsilon", timestep_scaling: float = 10.0):
+    """The consistency target (lcm/__init__.py:262-263): c_skip(t) x_prev + c_out(t) x0(pred_t at (x_prev, sched[t])), fp32; rows with t = 0 return x_prev exactly."""
+    L = _l.load()
+    (B, N), (x_prev32, pred_t, timesteps) = _lcm_rows("lcm_target", mode, [("x_prev32", x_prev32, F32, 1), ("pred_t", pred_t, BF16, 1)], [("timesteps", timesteps)],
+                                                      [("sched", sched)])
+    target = torch.empty(x_prev32.shape, dtype=F32, device=x_prev32.device)
+    _l.check(L.st355_lcm_target(_stream(), _ptr(x_prev32), _ptr(pred_t), _ptr(timesteps), _ptr(sched), sched.shape[0], LCM_MODES[mode], float(timestep_scaling),
+                                _ptr(target), B, N), "lcm_target")
+    return target
+
+
+def lcm_loss(pred, x_s, target, start, sched, mode: str = "epsilon", timestep_scaling: float = 10.0, loss_type: str = "l2", huber_c: float = 0.001,
+             want_grad: bool = True, grad_scale: float = 1.0):
+    """The LCM consistency loss (lcm/__init__.py:282-327) and its gradient in one pass: m = c_skip(start) x_s + c_out(start) x0(pred at (x_s, sched[start]));
+    l2: mean (m - target)^2, huber: mean sqrt((m - target)^2 + c^2) - c.  Returns (loss[1], per_sample[B], dpred bf16 or None)."""
+    L = _l.load()
+    if loss_type not in LCM_LOSSES:
+        raise _l.St355Error(f"lcm_loss: loss_type must be one of {sorted(LCM_LOSSES)}, got {loss_type!r}")
+    (B, N), (pred, x_s, target, start) = _lcm_rows("lcm_loss", mode, [("pred", pred, BF16, 1), ("x_s", x_s, BF16, 1), ("target", target, F32, 1)], [("start", start)],
+                                                   [("sched", sched)])
+    dev = pred.device
+    loss = torch.empty(1, dtype=F32, device=dev)
+    per_sample = torch.empty(B, dtype=F32, device=dev)
+    dpred = torch.empty(pred.shape, dtype=BF16, device=dev) if want_grad else None
+    ws = _scratch("lcm", dev, L.st355_lcm_workspace(B, N))
+    _l.check(L.st355_lcm_loss(_stream(), _ptr(pred), _ptr(x_s), _ptr(target), _ptr(start), _ptr(sched), sched.shape[0], LCM_MODES[mode], float(timestep_scaling),
+                              LCM_LOSSES[loss_type], float(huber_c), _ptr(loss), _ptr(per_sample), _ptr(dpred), _ptr(ws), B, N, grad_scale), "lcm_loss")
+    return loss, per_sample, dpred
+
+
+def lcm_sample_step(x, pred, noise, sched, t: int, t_next: int, mode: str = "epsilon", timestep_scaling: float = 10.0):
+    """One LCMScheduler step: denoised = c_skip(t) x + c_out(t) x0(pred at (x, sched[t])); returns sched[t_next].0 denoised + sched[t_next].1 noise, or denoised on
+    the last step (t_next < 0, noise None).  bf16 in, bf16 out (one rounding)."""
+    L = _l.load()
+    if mode not in LCM_MODES:
+        raise _l.St355Error(f"lcm_sample_step: mode must be one of {sorted(LCM_MODES)}, got {mode!r}")
+    _chk(x, BF16, "x"); _chk(pred, BF16, "pred"); _chk(sched, F32, "sched")
+    if pred.shape != x.shape or x.numel() == 0:
+        raise _l.St355Error(f"lcm_sample_step: pred {tuple(pred.shape)} must have x's shape {tuple(x.shape)}")
+    if sched.dim() != 2 or sched.shape[1] != 2 or not sched.is_contiguous():
+        raise _l.St355Error(f"lcm_sample_step: sched: expected a contiguous fp32 [T, 2] tensor, got {tuple(sched.shape)}")
+    t_next = int(t_next)
+    if t_next >= 0:
+        if noise is None:
+            raise _l.St355Error("lcm_sample_step: every step but the last (t_next < 0) needs its noise")
+        _chk(noise, BF16, "noise")
+        if noise.shape != x.shape:
+            raise _l.St355Error(f"lcm_sample_step: noise {tuple(noise.shape)} must have x's shape {tuple(x.shape)}")
+        noise = noise.contiguous()
+    else:
+        noise = None
+    x, pred = x.contiguous(), pred.contiguous()
+    out = torch.empty_like(x)
+    _l.check(L.st355_lcm_sample_step(_stream(), _ptr(x), _ptr(pred), _ptr(noise), _ptr(sched), sched.shape[0], LCM_MODES[mode], float(timestep_scaling), int(t), t_next,
+                                     _ptr(out), x.numel()), "lcm_sample_step")
+    return out
+
+
 FLOW_DPO_NORMS = {"sum": 0, "mean": 1, "masked_mean": 2}
 FLOW_DPO_LOGS = ("flow_dpo_loss", "flow_dpo_beta", "flow_dpo_margin", "flow_dpo_win_adv", "flow_dpo_lose_adv", "flow_dpo_policy_win_err",
                  "flow_dpo_policy_lose_err", "flow_dpo_ref_win_err", "flow_dpo_ref_lose_err", "flow_dpo_negative_margin_pct", "flow_dpo_gradient_factor", "total",

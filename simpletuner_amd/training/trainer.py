@@ -234,11 +234,13 @@ class Trainer:
             self.model.scheduled_sampling_value()                        # scheduled sampling / ReflexFlow: the default-on rule, and the refusals by the flag's name
         self.distiller = None
         self._self_transcendence = False
-        if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Self-Transcendence, Flow-DPO (every other method is refused by name)
+        if getattr(config, "distillation_method", None):                 # trainer.py:init_distillation: Self-Transcendence, Flow-DPO, LCM (every other method is refused by name)
             from ..flow_dpo import create_distiller, method_of
             if method_of(config) == "self_transcendence":
                 from ..self_transcendence import create_distiller
                 self._self_transcendence = True
+            elif method_of(config) == "lcm":
+                from ..lcm import create_distiller
             self.distiller = create_distiller(self.model)
             if self._self_transcendence:
                 self.model.self_transcendence = self.distiller           # the plugin's training forward asks it what the tap is trained to

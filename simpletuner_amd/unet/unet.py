@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import math
 import os
+from contextlib import contextmanager
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -413,6 +414,37 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
         self._alloc_transposed()
         self._refresh_transposed()                       # frozen base: the K-major copies are built once
         return self._lora_params
+
+    def disable_lora(self):
+        """Take every LoRA group off its linear (engine.ArenaModule.disable_lora's semantics): with every `lin.lora` None and `lora_groups` empty the forward neither
+        packs nor projects down, and launches exactly the base model's sequence.  Meant for no-grad forwards between training forwards (LCM's teacher);
+        `enable_lora()` puts the same groups back on the same linears."""
+        if getattr(self, "_lora_off", None) is not None:
+            return
+        sites = [(l, l.lora) for l in self._all_layers() if getattr(l, "lora", None) is not None]
+        if len(sites) != len(self.lora_groups):
+            raise RuntimeError(f"disable_lora: {len(self.lora_groups)} adapter groups but {len(sites)} sites found")
+        self._lora_off = (sites, self.lora_groups)
+        for l, _ in sites:
+            l.lora = None
+        self.lora_groups = []
+
+    def enable_lora(self):
+        off, self._lora_off = getattr(self, "_lora_off", None), None
+        if off is None:
+            return
+        sites, groups = off
+        for l, g in sites:
+            l.lora = g
+        self.lora_groups = groups
+
+    @contextmanager
+    def lora_disabled(self):
+        self.disable_lora()
+        try:
+            yield self
+        finally:
+            self.enable_lora()
 
     def _is_down(self, l):
         return any(blk.down is l for blk in self.down)

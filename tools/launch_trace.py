@@ -76,8 +76,8 @@ class LaunchTrace:
 
         EMU.install = install
         # the features' stand-ins, installed on top of the emulator by their modules' own `install` (which read these at call time): wrapped in place
-        from tests import diff2flow_ref, dora_ref, flow_dpo_ref, internal_guidance_ref, layersync_ref, lora_dropout_ref, nextlat_ref, reflexflow_ref, self_flow_ref, tlora_ref, twinflow_ref
-        for mod in (layersync_ref, nextlat_ref, internal_guidance_ref, lora_dropout_ref, dora_ref, reflexflow_ref, flow_dpo_ref, diff2flow_ref, tlora_ref, self_flow_ref, twinflow_ref):
+        from tests import diff2flow_ref, dora_ref, flow_dpo_ref, internal_guidance_ref, layersync_ref, lcm_ref, lora_dropout_ref, nextlat_ref, reflexflow_ref, self_flow_ref, tlora_ref, twinflow_ref
+        for mod in (layersync_ref, nextlat_ref, internal_guidance_ref, lora_dropout_ref, dora_ref, reflexflow_ref, flow_dpo_ref, diff2flow_ref, tlora_ref, self_flow_ref, twinflow_ref, lcm_ref):
             table = getattr(mod, "STAND_INS", None) or {}
             for name, fn in table.items():
                 if inspect.isfunction(fn):
