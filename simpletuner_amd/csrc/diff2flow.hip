@@ -10,22 +10,13 @@
 // stride or the mask period is no multiple of 8 (or a pointer is not 16-byte aligned) the same walk runs with scalar loads and stores, the n % 8 tail included.
 // The reduction runs in two stages in a fixed order — stage 1: `parts` workgroups per sample, each lane a strided run of 8-element groups, lane tree, then the wave
 // partials in wave order; stage 2, on the device: the `parts` partials in index order — so every output repeats bit for bit.  No atomics.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define D2F_THREADS OP_THREADS
 
-// partial workgroups per sample: the op_blocks grid (at most 2048 workgroups of 256) divided among the samples
-static inline int d2f_parts(int64_t batch, int64_t per_sample) {
-  int64_t p = cdiv64(cdiv64(per_sample, 8), D2F_THREADS);
-  const int64_t cap = (256 * 8) / batch;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
 extern "C" int64_t st355_diff2flow_workspace(int64_t batch, int64_t per_sample) {
   if (batch <= 0 || per_sample <= 0) return 0;
-  return (int64_t)sizeof(float) * batch * d2f_parts(batch, per_sample);
+  return (int64_t)sizeof(float) * batch * sample_parts(batch, per_sample);
 }
 
 struct D2fArgs {
@@ -55,39 +46,28 @@ __global__ void __launch_bounds__(D2F_THREADS) k_d2f_loss(const D2fArgs a) {
   const float w = a.weight ? a.weight[b] : 1.f;
   const float k = MODE == 0 ? 1.f + c1 : c0 + c1;
   const float gcoef = a.dscale * w * k;
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int64_t i = (int64_t)blockIdx.x * D2F_THREADS + threadIdx.x; i < groups; i += (int64_t)gridDim.x * D2F_THREADS) {
     const int64_t e0 = i * 8;
     const int cnt = (n - e0) >= 8 ? 8 : (int)(n - e0);
-    bf16x8 pv, xv, tv, dv;
-    float mk[8];
-    if (VEC) {
-      pv = *(const bf16x8*)(p_ + e0);
-      xv = *(const bf16x8*)(x_ + e0);
-      tv = *(const bf16x8*)(t_ + e0);
-      if (em) {
-        const int64_t off = e0 % a.mask_period;
-        const f32x4 m0 = *(const f32x4*)(em + off), m1 = *(const f32x4*)(em + off + 4);
+    float pv[8], xv[8], tv[8], mk[8], dv[8];
+    load8<VEC>(p_, e0, cnt, pv);
+    load8<VEC>(x_, e0, cnt, xv);
+    load8<VEC>(t_, e0, cnt, tv);
+    if (em) {
+      if (VEC) {
+        ld8(em + e0 % a.mask_period, mk);
+      } else {                                                    // (a scalar group may wrap around the period)
 #pragma unroll
-        for (int j = 0; j < 4; j++) { mk[j] = m0[j]; mk[j + 4] = m1[j]; }
+        for (int j = 0; j < 8; j++) mk[j] = j < cnt ? em[(e0 + j) % a.mask_period] : 0.f;
       }
     } else {
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const bool in = j < cnt;
-        pv[j] = in ? p_[e0 + j] : f2bf(0.f);
-        xv[j] = in ? x_[e0 + j] : f2bf(0.f);
-        tv[j] = in ? t_[e0 + j] : f2bf(0.f);
-        if (em) mk[j] = in ? em[(e0 + j) % a.mask_period] : 0.f;
-      }
-    }
-    if (!em) {
 #pragma unroll
       for (int j = 0; j < 8; j++) mk[j] = 1.f;
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      const float p = bf2f(pv[j]), x = bf2f(xv[j]);
+      const float p = pv[j], x = xv[j];
       const float z = c0 * x - c1 * p;
       float f;
       if (MODE == 0) {
@@ -96,34 +76,19 @@ __global__ void __launch_bounds__(D2F_THREADS) k_d2f_loss(const D2fArgs a) {
         const float e = c0 * p + c1 * x;
         f = e - z;
       }
-      const float d = f - bf2f(tv[j]);
-      if (VEC || j < cnt) acc += d * d * mk[j];
-      dv[j] = f2bf(gcoef * d * mk[j]);
+      const float d = f - tv[j];
+      if (VEC || j < cnt) acc[0] += d * d * mk[j];
+      dv[j] = gcoef * d * mk[j];
     }
-    if (d_) {
-      if (VEC) {
-        *(bf16x8*)(d_ + e0) = dv;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          if (j < cnt) d_[e0 + j] = dv[j];
-      }
-    }
+    if (d_) store8<VEC>(d_, e0, cnt, dv);
   }
-  acc = wave_sum(acc);
-  __shared__ float red[D2F_THREADS / WAVE];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < D2F_THREADS / WAVE; i++) s += red[i];
-    a.ws[(int64_t)b * gridDim.x + blockIdx.x] = s;
-  }
+  block_reduce<1>(acc, a.ws, b);
 }
 
 // stage 2, one workgroup: per sample the partials in index order -> per_sample[b] = weight[b] * sum / n; then the batch mean in sample order
-__global__ void __launch_bounds__(D2F_THREADS) k_d2f_finish(const float* __restrict__ ws, const float* __restrict__ weight, float* __restrict__ loss,
-                                                           float* __restrict__ per_sample_out, int B, int parts, float inv_per_sample) {
+// (weight == nullptr, lcm's loss: s * 1.f * inv is s * inv exactly)
+__global__ void __launch_bounds__(D2F_THREADS) k_sample_mean_finish(const float* __restrict__ ws, const float* __restrict__ weight, float* __restrict__ loss,
+                                                                   float* __restrict__ per_sample_out, int B, int parts, float inv_per_sample) {
   for (int b = threadIdx.x; b < B; b += D2F_THREADS) {
     float s = 0.f;
     for (int p = 0; p < parts; p++) s += ws[(int64_t)b * parts + p];
@@ -135,6 +100,11 @@ __global__ void __launch_bounds__(D2F_THREADS) k_d2f_finish(const float* __restr
     for (int b = 0; b < B; b++) s += per_sample_out[b];
     loss[0] = s / (float)B;
   }
+}
+
+// declared in feature_common.h: st355_lcm_loss (lcm.hip) launches it too, with weight == nullptr
+void sample_mean_finish(hipStream_t st, const float* ws, const float* weight, float* loss, float* per_sample_out, int B, int parts, float inv_per_sample) {
+  hipLaunchKernelGGL(k_sample_mean_finish, dim3(1), dim3(D2F_THREADS), 0, st, ws, weight, loss, per_sample_out, B, parts, inv_per_sample);
 }
 
 extern "C" int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred_stride, const void* noisy, const void* tau, const int64_t* timesteps,
@@ -150,7 +120,7 @@ extern "C" int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred
   ST_REQUIRE(dpred != pred, "diff2flow_loss: dpred and pred must be different buffers");
   const bool vec = per_sample % 8 == 0 && pred_stride % 8 == 0 && (((uintptr_t)pred | (uintptr_t)noisy | (uintptr_t)tau | (uintptr_t)dpred) & 15) == 0 &&
                    (!emask || (mask_period % 8 == 0 && ((uintptr_t)emask & 15) == 0));
-  const int parts = d2f_parts(batch, per_sample);
+  const int parts = sample_parts(batch, per_sample);
   const double n = (double)batch * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 12.0 * n, (6.0 + (emask ? 4.0 : 0.0) + (dpred ? 2.0 : 0.0)) * n);
   D2fArgs a;
@@ -166,7 +136,6 @@ extern "C" int st355_diff2flow_loss(void* stream, const void* pred, int64_t pred
     if (vec) hipLaunchKernelGGL((k_d2f_loss<1, true>), grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((k_d2f_loss<1, false>), grid, block, 0, (hipStream_t)stream, a);
   }
-  hipLaunchKernelGGL(k_d2f_finish, dim3(1), block, 0, (hipStream_t)stream, (const float*)workspace, weight, loss_out, per_sample_out, (int)batch, parts,
-                     1.0f / (float)per_sample);
+  sample_mean_finish((hipStream_t)stream, (const float*)workspace, weight, loss_out, per_sample_out, (int)batch, parts, 1.0f / (float)per_sample);
   return st355_check_launch("diff2flow_loss");
 }

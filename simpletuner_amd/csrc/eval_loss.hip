@@ -11,23 +11,15 @@
 // (k, b): lane tree, then the wave partials in wave order; stage 2, one workgroup per k: thread b sums sample b's partials in part order, thread 0 the B sample means
 // in sample order.  `parts` follows from B and n alone and no workgroup sees another slab, so loss[k] and per_sample[k, :] have the same bits whatever K is and
 // wherever the slab sits in the chunk.  No atomics, nothing read on the host.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define EL_THREADS OP_THREADS
 #define EL_MAX_K 64
 
-// partial workgroups per sample: the op_blocks grid (at most 2048 workgroups of 256) divided among the B samples of ONE slab
-static inline int el_parts(int64_t batch, int64_t per_sample) {
-  int64_t p = cdiv64(per_sample >> 3, EL_THREADS);
-  const int64_t cap = (256 * 8) / batch;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
+// (sample_parts over the B samples of ONE slab)
 extern "C" int64_t st355_eval_loss_workspace(int64_t batch, int64_t per_sample, int64_t k) {
   if (batch <= 0 || per_sample <= 0 || k <= 0) return 0;
-  return (int64_t)sizeof(float) * k * batch * el_parts(batch, per_sample);
+  return (int64_t)sizeof(float) * k * batch * sample_parts(batch, per_sample);
 }
 
 // ---- views ----------------------------------------------------------------------------------------------------------------------------------------
@@ -77,7 +69,6 @@ extern "C" int st355_eval_flow_views(void* stream, const void* latents, const vo
 template <int TYPE>
 __global__ void __launch_bounds__(EL_THREADS) k_eval_loss(const bf16* __restrict__ pred, const bf16* __restrict__ target, const float* __restrict__ huber_c,
                                                          float* __restrict__ ws, int64_t per_sample) {
-  __shared__ float red[EL_THREADS / WAVE];
   const int b = blockIdx.y, k = blockIdx.z, B = gridDim.y;
   const int64_t vecs = per_sample >> 3;
   const bf16* p = pred + ((int64_t)k * B + b) * per_sample;
@@ -88,25 +79,18 @@ __global__ void __launch_bounds__(EL_THREADS) k_eval_loss(const bf16* __restrict
     c2 = c * c;
     if (TYPE == 1) scale = 2.f * c;
   }
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int64_t i = (int64_t)blockIdx.x * EL_THREADS + threadIdx.x; i < vecs; i += (int64_t)gridDim.x * EL_THREADS) {
     const bf16x8 pv = *(const bf16x8*)(p + i * 8);
     const bf16x8 tv = *(const bf16x8*)(t + i * 8);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const float df = bf2f(pv[j]) - bf2f(tv[j]);
-      if (TYPE == 0) acc += df * df;
-      else acc += scale * (sqrtf(df * df + c2) - c);
+      if (TYPE == 0) acc[0] += df * df;
+      else acc[0] += scale * (sqrtf(df * df + c2) - c);
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int w = 0; w < EL_THREADS / WAVE; w++) s += red[w];
-    ws[((int64_t)k * B + b) * gridDim.x + blockIdx.x] = s;
-  }
+  block_reduce<1>(acc, ws, (int64_t)k * B + b);
 }
 
 // stage 2, grid = (K): thread b (strided over the samples) sums sample (k, b)'s partials in part order and writes per_sample[k, b] = sum / n; then thread 0 sums the B
@@ -137,7 +121,7 @@ extern "C" int st355_eval_loss(void* stream, const void* pred, const void* targe
              (long)per_sample_n, (long)batch);
   ST_REQUIRE(k >= 1 && k <= EL_MAX_K, "eval_loss: the timestep count (%ld) must lie in [1, %d]", (long)k, EL_MAX_K);
   ST_REQUIRE(((uintptr_t)pred & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)workspace & 3) == 0, "eval_loss: pred and target must be 16-byte aligned");
-  const int parts = el_parts(batch, per_sample_n);
+  const int parts = sample_parts(batch, per_sample_n);
   const double n = (double)batch * per_sample_n;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, (loss_type ? 6.0 : 3.0) * k * n, 2.0 * (k + 1) * n);
   const dim3 grid(parts, (unsigned)batch, (unsigned)k);

@@ -11,23 +11,15 @@
 // order n loses every digit of a margin that is small against them.  stats and grad stream 16 bytes per lane; the reductions run in two stages in a fixed order —
 // stage 1: `parts` workgroups per pair, each lane a strided run of vectors, lane tree, then the wave partials in wave order; stage 2, on the device: the `parts`
 // partials in index order — so every output repeats bit for bit, and nothing is read on the host.  No atomics.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define FD_THREADS OP_THREADS
 #define FD_NS 9          // E_pw, E_pl, E_rw, E_rl, A_w, A_l, mask sum, adv_w, adv_l
 
-// partial workgroups per pair: the op_blocks grid (at most 2048 workgroups of 256) divided among the pairs
-static inline int fd_parts(int64_t pairs, int64_t per_sample) {
-  int64_t p = cdiv64(per_sample >> 3, FD_THREADS);
-  const int64_t cap = (256 * 8) / pairs;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
+// (sample_parts with the pairs as its samples)
 extern "C" int64_t st355_flow_dpo_workspace(int64_t pairs, int64_t per_sample) {
   if (pairs <= 0 || per_sample <= 0) return 0;
-  return (int64_t)sizeof(float) * FD_NS * pairs * fd_parts(pairs, per_sample);
+  return (int64_t)sizeof(float) * FD_NS * pairs * sample_parts(pairs, per_sample);
 }
 
 __device__ __forceinline__ void fd_load_mask(const float* __restrict__ em, int64_t i, int64_t period, float (&mk)[8]) {
@@ -47,7 +39,6 @@ __device__ __forceinline__ void fd_load_mask(const float* __restrict__ em, int64
 __global__ void __launch_bounds__(FD_THREADS) k_fd_stats(const bf16* __restrict__ policy, const bf16* __restrict__ ref, const bf16* __restrict__ tw,
                                                         const bf16* __restrict__ tl, const float* __restrict__ emask, int64_t mask_period, float* __restrict__ ws,
                                                         int64_t pairs, int64_t per_sample) {
-  __shared__ float red[FD_NS][FD_THREADS / WAVE];
   const int b = blockIdx.y;
   const int64_t win = (int64_t)b * per_sample, lose = ((int64_t)b + pairs) * per_sample, vecs = per_sample >> 3;
   const float* em = emask ? emask + (int64_t)b * mask_period : nullptr;
@@ -78,17 +69,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_fd_stats(const bf16* __restrict_
       acc[8] += m * (dl * ((pl + rl) - 2.f * t2));
     }
   }
-#pragma unroll
-  for (int k = 0; k < FD_NS; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < FD_NS) {
-    float s = 0.f;
-    for (int w = 0; w < FD_THREADS / WAVE; w++) s += red[threadIdx.x][w];
-    ws[((int64_t)b * gridDim.x + blockIdx.x) * FD_NS + threadIdx.x] = s;
-  }
+  block_reduce<FD_NS>(acc, ws, b);
 }
 
 // stage 2: stats[b, k] = the partials of (b, k) in index order.  grid = B, 64 threads (FD_NS used)
@@ -110,7 +91,7 @@ extern "C" int st355_flow_dpo_stats(void* stream, const void* policy, const void
   ST_REQUIRE(per_sample > 0 && per_sample % 8 == 0 && pairs > 0 && pairs < 32768, "flow_dpo_stats: bad shape (per_sample %ld must be a multiple of 8, pairs %ld < 32768)",
              (long)per_sample, (long)pairs);
   ST_REQUIRE(fd_mask_ok(emask, mask_period, per_sample), "flow_dpo_stats: element mask period must be a multiple of 8 dividing per_sample (16-byte aligned)");
-  const int parts = fd_parts(pairs, per_sample);
+  const int parts = sample_parts(pairs, per_sample);
   const double n = (double)pairs * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 30.0 * n, 12.0 * n);
   float* ws = (float*)workspace;

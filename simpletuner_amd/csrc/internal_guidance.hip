@@ -8,18 +8,12 @@
 //   st355_ig_wgrad     from P = dy^T xhat [64, D] fp32 (st355_skinny_tn_seg) and db = sum_m dy: dW = P * gamma + db beta^T, and the LayerNorm affine's gradients by
 //                      contracting with the UNFOLDED W instead of dividing g by gamma (gamma may be 0): sum_m dn * xhat = sum_n W[n, :] * P[n, :] and
 //                      sum_m dn = sum_n W[n, :] * db[n] with dn = dy W — exact identities, so no per-block partial column sums leave the backward kernel.
-#include "common.h"
+#include "feature_common.h"
 
 #define IG_N 64                       // output features of the head (16 latent channels x 2 x 2 patch)
-#define IG_EPS 1e-6f
-#define IG_ROWS_PER_BLOCK 4           // forward: one wave per row
-#define IG_PASS_COLS 512              // 64 lanes x 8 bf16
-#define IG_MAX_PASSES 8               // D <= 4096
+#define IG_MAX_D (ROW_PASS_COLS * ROW_MAX_PASSES)          // the row pass keeps a row in registers: D <= 4096
 #define IG_BWD_ROWS 16                // backward: token rows per wave (one MFMA tile); a workgroup's 4 waves share the staged W'^T chunk
 #define IG_BWD_WAVES 4
-
-template <typename T> __device__ __forceinline__ float ig_ld(const T* p, int64_t i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void ig_st(T* p, int64_t i, float v, int accumulate) { p[i] = (T)(accumulate ? (float)p[i] + v : v); }
 
 // one block per output feature n: W'[n, :], W'^T[:, n] and c[n] = sum_d W[n, d] beta[d] + b[n] (thread-strided partials, butterfly per wave, the 4 wave sums in order)
 template <typename T>
@@ -29,23 +23,23 @@ __global__ void __launch_bounds__(256) k_ig_fold(const T* __restrict__ gamma, co
   const int n = blockIdx.x;
   float a = 0.f;
   for (int d = threadIdx.x; d < D; d += 256) {
-    const float w = ig_ld(W, (int64_t)n * D + d);
-    const bf16 f = f2bf(w * ig_ld(gamma, d));
+    const float w = ld(W, (int64_t)n * D + d);
+    const bf16 f = f2bf(w * ld(gamma, d));
     Wf[(int64_t)n * D + d] = f;
     WfT[(int64_t)d * IG_N + n] = f;
-    a = fmaf(w, ig_ld(beta, d), a);
+    a = fmaf(w, ld(beta, d), a);
   }
   a = wave_sum(a);
   if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x >> 6] = a;
   __syncthreads();
-  if (threadIdx.x == 0) c[n] = f2bf(((part[0] + part[1]) + (part[2] + part[3])) + ig_ld(b, n));
+  if (threadIdx.x == 0) c[n] = f2bf(((part[0] + part[1]) + (part[2] + part[3])) + ld(b, n));
 }
 
 extern "C" int st355_ig_fold(void* stream, const void* gamma, const void* beta, const void* W, const void* b, int params_bf16, void* Wf, void* WfT, void* c, int N,
                              int D) {
   ST_REQUIRE(gamma && beta && W && b && Wf && WfT && c, "ig_fold: bad args");
   ST_REQUIRE(N == IG_N, "ig_fold: the head has %d output features (got %d)", IG_N, N);
-  ST_REQUIRE(D > 0 && D % 8 == 0 && D <= IG_PASS_COLS * IG_MAX_PASSES, "ig_fold: D must be a multiple of 8, at most %d (got %d)", IG_PASS_COLS * IG_MAX_PASSES, D);
+  ST_REQUIRE(D > 0 && D % 8 == 0 && D <= IG_MAX_D, "ig_fold: D must be a multiple of 8, at most %d (got %d)", IG_MAX_D, D);
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 3.0 * N * D, 8.0 * N * D);
   if (params_bf16)
     hipLaunchKernelGGL(k_ig_fold<bf16>, dim3(IG_N), dim3(256), 0, (hipStream_t)stream, (const bf16*)gamma, (const bf16*)beta, (const bf16*)W, (const bf16*)b, (bf16*)Wf,
@@ -56,71 +50,15 @@ extern "C" int st355_ig_fold(void* stream, const void* gamma, const void* beta, 
   return st355_check_launch("ig_fold");
 }
 
-// NP = passes over the row (3 at D = 1536, 6 at D = 3072); a lane keeps its 8 * NP elements (packed bf16) between the two reductions and the store
-template <int NP>
-__global__ void __launch_bounds__(IG_ROWS_PER_BLOCK* WAVE) k_ig_head_fwd(const bf16* __restrict__ h, bf16* __restrict__ xhat, float* __restrict__ rstd, int rows, int D,
-                                                                         int64_t n_rows, int64_t ld, int64_t bstride, float inv_d) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t row = (int64_t)blockIdx.x * IG_ROWS_PER_BLOCK + (threadIdx.x >> 6);
-  if (row >= n_rows) return;                                      // wave-uniform: the last block may be partly empty
-  const bf16* hp = h + (row / rows) * bstride + (row % rows) * ld;
-  bf16x8 v[NP];
-  float s = 0.f;
-#pragma unroll
-  for (int p = 0; p < NP; p++) {
-    const int c = p * IG_PASS_COLS + lane * 8;
-    if (c < D) {                                                  // guarded tail: D % 512 != 0 (D % 8 == 0 keeps a lane's 8 columns together)
-      v[p] = *(const bf16x8*)(hp + c);
-#pragma unroll
-      for (int j = 0; j < 8; j++) s += bf2f(v[p][j]);
-    }
-  }
-  const float mean = wave_sum(s) * inv_d;                         // xor butterfly: every lane holds the same bits
-  float q = 0.f;
-#pragma unroll
-  for (int p = 0; p < NP; p++) {
-    if (p * IG_PASS_COLS + lane * 8 < D) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const float d = bf2f(v[p][j]) - mean;
-        q = fmaf(d, d, q);
-      }
-    }
-  }
-  const float rs = 1.f / sqrtf(wave_sum(q) * inv_d + IG_EPS);     // centred: no E[x^2] - mean^2 cancellation on a row of large offset
-  if (lane == 0) rstd[row] = rs;
-  bf16* xp = xhat + row * (int64_t)D;
-#pragma unroll
-  for (int p = 0; p < NP; p++) {
-    const int c = p * IG_PASS_COLS + lane * 8;
-    if (c < D) {
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; j++) o[j] = f2bf((bf2f(v[p][j]) - mean) * rs);
-      *(bf16x8*)(xp + c) = o;
-    }
-  }
-}
-
+// the row pass: k_rows_fwd of feature_common.h with the head's eps 1e-6
 extern "C" int st355_ig_head_fwd(void* stream, const void* h, void* xhat, float* rstd, int B, int rows, int D, int64_t ld, int64_t bstride) {
   ST_REQUIRE(h && xhat && rstd && B > 0 && rows > 0 && D > 0, "ig_head_fwd: bad args");
-  ST_REQUIRE(D % 8 == 0 && D <= IG_PASS_COLS * IG_MAX_PASSES, "ig_head_fwd: D must be a multiple of 8, at most %d (got %d)", IG_PASS_COLS * IG_MAX_PASSES, D);
+  ST_REQUIRE(D % 8 == 0 && D <= IG_MAX_D, "ig_head_fwd: D must be a multiple of 8, at most %d (got %d)", IG_MAX_D, D);
   ST_REQUIRE(ld >= D && ld % 8 == 0 && bstride % 8 == 0 && bstride >= 0, "ig_head_fwd: strides must be multiples of 8 elements, ld >= D");
   ST_REQUIRE(((uintptr_t)h | (uintptr_t)xhat) % 16 == 0, "ig_head_fwd: operands must be 16-byte aligned");
   const int64_t n = (int64_t)B * rows;
-  const dim3 grid((unsigned)cdiv64(n, IG_ROWS_PER_BLOCK)), block(IG_ROWS_PER_BLOCK * WAVE);
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 6.0 * n * D, 4.0 * n * D);
-#define IG_LAUNCH(NP_) \
-  hipLaunchKernelGGL(k_ig_head_fwd<NP_>, grid, block, 0, (hipStream_t)stream, (const bf16*)h, (bf16*)xhat, rstd, rows, D, n, ld, bstride, (float)(1.0 / (double)D))
-  switch ((D + IG_PASS_COLS - 1) / IG_PASS_COLS) {
-    case 1: IG_LAUNCH(1); break;
-    case 2: IG_LAUNCH(2); break;
-    case 3: IG_LAUNCH(3); break;
-    case 4: IG_LAUNCH(4); break;
-    case 5: case 6: IG_LAUNCH(6); break;
-    default: IG_LAUNCH(8); break;
-  }
-#undef IG_LAUNCH
+  rows_fwd_launch<RowEps1e6>((hipStream_t)stream, (const bf16*)h, (bf16*)xhat, rstd, rows, D, n, ld, bstride);
   return st355_check_launch("ig_head_fwd");
 }
 
@@ -232,7 +170,7 @@ extern "C" int st355_ig_head_bwd(void* stream, const void* xhat, const float* rs
                                  int64_t ld, int64_t bstride) {
   ST_REQUIRE(xhat && rstd && dy && WfT && dx && B > 0 && rows > 0 && D > 0, "ig_head_bwd: bad args");
   ST_REQUIRE(N == IG_N, "ig_head_bwd: the head has %d output features (got %d)", IG_N, N);
-  ST_REQUIRE(D % 8 == 0 && D <= IG_PASS_COLS * IG_MAX_PASSES, "ig_head_bwd: D must be a multiple of 8, at most %d (got %d)", IG_PASS_COLS * IG_MAX_PASSES, D);
+  ST_REQUIRE(D % 8 == 0 && D <= IG_MAX_D, "ig_head_bwd: D must be a multiple of 8, at most %d (got %d)", IG_MAX_D, D);
   ST_REQUIRE(ld >= D && ld % 8 == 0 && bstride % 8 == 0 && bstride >= 0, "ig_head_bwd: strides must be multiples of 8 elements, ld >= D");
   ST_REQUIRE(((uintptr_t)xhat | (uintptr_t)dy | (uintptr_t)WfT | (uintptr_t)dx) % 16 == 0, "ig_head_bwd: operands must be 16-byte aligned");
   const int64_t n = (int64_t)B * rows;
@@ -252,15 +190,15 @@ __global__ void __launch_bounds__(256) k_ig_wgrad(const float* __restrict__ P, c
   __shared__ float sg[8][IG_WG_COLS], sb[8][IG_WG_COLS];
   const int col = threadIdx.x & (IG_WG_COLS - 1), ng = threadIdx.x >> 5;
   const int d = blockIdx.x * IG_WG_COLS + col;
-  if (blockIdx.x == 0 && threadIdx.x < IG_N) ig_st(g_b, threadIdx.x, db[threadIdx.x], accumulate);
+  if (blockIdx.x == 0 && threadIdx.x < IG_N) st(g_b, threadIdx.x, db[threadIdx.x], accumulate);
   float dg = 0.f, dbe = 0.f;
   if (d < D) {
-    const float ga = ig_ld(gamma, d), be = ig_ld(beta, d);
+    const float ga = ld(gamma, d), be = ld(beta, d);
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       const int n = ng * 8 + i;
-      const float p = P[(int64_t)n * D + d], w = ig_ld(W, (int64_t)n * D + d), s = db[n];
-      ig_st(g_W, (int64_t)n * D + d, fmaf(p, ga, s * be), accumulate);
+      const float p = P[(int64_t)n * D + d], w = ld(W, (int64_t)n * D + d), s = db[n];
+      st(g_W, (int64_t)n * D + d, fmaf(p, ga, s * be), accumulate);
       dg = fmaf(w, p, dg);
       dbe = fmaf(w, s, dbe);
     }
@@ -271,8 +209,8 @@ __global__ void __launch_bounds__(256) k_ig_wgrad(const float* __restrict__ P, c
     float a = 0.f, c = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; k++) { a += sg[k][col]; c += sb[k][col]; }
-    ig_st(g_gamma, d, a, accumulate);
-    ig_st(g_beta, d, c, accumulate);
+    st(g_gamma, d, a, accumulate);
+    st(g_beta, d, c, accumulate);
   }
 }
 
@@ -280,7 +218,7 @@ extern "C" int st355_ig_wgrad(void* stream, const float* P, const float* db, con
                               void* g_beta, void* g_W, void* g_b, int N, int D, int accumulate) {
   ST_REQUIRE(P && db && gamma && beta && W && g_gamma && g_beta && g_W && g_b, "ig_wgrad: bad args");
   ST_REQUIRE(N == IG_N, "ig_wgrad: the head has %d output features (got %d)", IG_N, N);
-  ST_REQUIRE(D > 0 && D % 8 == 0 && D <= IG_PASS_COLS * IG_MAX_PASSES, "ig_wgrad: D must be a multiple of 8, at most %d (got %d)", IG_PASS_COLS * IG_MAX_PASSES, D);
+  ST_REQUIRE(D > 0 && D % 8 == 0 && D <= IG_MAX_D, "ig_wgrad: D must be a multiple of 8, at most %d (got %d)", IG_MAX_D, D);
   const dim3 grid((unsigned)((D + IG_WG_COLS - 1) / IG_WG_COLS)), block(256);
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 6.0 * N * D, 12.0 * N * D);
   if (params_bf16)

@@ -17,22 +17,13 @@
 // gather.  16 bytes per lane where the per-sample size is a multiple of 8 and the pointers are 16-byte aligned, else the same walk with scalar accesses, the n % 8 tail
 // included.  The loss reduction runs in two stages in a fixed order — stage 1: `parts` workgroups per sample, lane tree, wave partials in wave order; stage 2, on the
 // device: the partials in index order — so every output repeats bit for bit.  No atomics.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define LCM_THREADS OP_THREADS
 
-// workgroups per sample: the op_blocks grid (at most 2048 workgroups of 256) divided among the samples
-static inline int lcm_parts(int64_t batch, int64_t per_sample) {
-  int64_t p = cdiv64(cdiv64(per_sample, 8), LCM_THREADS);
-  const int64_t cap = (256 * 8) / batch;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
 extern "C" int64_t st355_lcm_workspace(int64_t batch, int64_t per_sample) {
   if (batch <= 0 || per_sample <= 0) return 0;
-  return (int64_t)sizeof(float) * batch * lcm_parts(batch, per_sample);
+  return (int64_t)sizeof(float) * batch * sample_parts(batch, per_sample);
 }
 
 __device__ __forceinline__ int64_t lcm_clamp(int64_t t, int len) { return t < 0 ? 0 : (t > len - 1 ? len - 1 : t); }
@@ -53,60 +44,6 @@ __device__ __forceinline__ float lcm_x0(float x, float p, float a, float s) {
 template <int MODE>
 __device__ __forceinline__ float lcm_eps(float x, float p, float a, float s) {
   return MODE == 0 ? p : a * p + s * x;
-}
-
-// 8 elements from e0 of a bf16 / fp32 row: one (two) 16-byte access(es), or `cnt` scalar ones (the rest zero)
-template <bool VEC>
-__device__ __forceinline__ void lcm_load(const bf16* __restrict__ src, int64_t e0, int cnt, float (&v)[8]) {
-  if (VEC) {
-    const bf16x8 r = *(const bf16x8*)(src + e0);
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = bf2f(r[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = j < cnt ? bf2f(src[e0 + j]) : 0.f;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void lcm_load(const float* __restrict__ src, int64_t e0, int cnt, float (&v)[8]) {
-  if (VEC) {
-    const f32x4 r0 = *(const f32x4*)(src + e0), r1 = *(const f32x4*)(src + e0 + 4);
-#pragma unroll
-    for (int j = 0; j < 4; j++) { v[j] = r0[j]; v[j + 4] = r1[j]; }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = j < cnt ? src[e0 + j] : 0.f;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void lcm_store(bf16* __restrict__ dst, int64_t e0, int cnt, const float (&v)[8]) {
-  if (VEC) {
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = f2bf(v[j]);
-    *(bf16x8*)(dst + e0) = r;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-      if (j < cnt) dst[e0 + j] = f2bf(v[j]);
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void lcm_store(float* __restrict__ dst, int64_t e0, int cnt, const float (&v)[8]) {
-  if (VEC) {
-    f32x4 r0, r1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) { r0[j] = v[j]; r1[j] = v[j + 4]; }
-    *(f32x4*)(dst + e0) = r0;
-    *(f32x4*)(dst + e0 + 4) = r1;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-      if (j < cnt) dst[e0 + j] = v[j];
-  }
 }
 
 // ---- the solver step: CFG combine, x0 / eps, DDIM step.  grid = (parts, B) ----
@@ -138,16 +75,16 @@ __global__ void __launch_bounds__(LCM_THREADS) k_lcm_solver(const LcmSolverArgs 
     const int64_t e0 = i * 8;
     const int cnt = (n - e0) >= 8 ? 8 : (int)(n - e0);
     float xv[8], cv[8], uv[8], ov[8];
-    lcm_load<VEC>(x_, e0, cnt, xv);
-    lcm_load<VEC>(pc_, e0, cnt, cv);
-    lcm_load<VEC>(pu_, e0, cnt, uv);
+    load8<VEC>(x_, e0, cnt, xv);
+    load8<VEC>(pc_, e0, cnt, cv);
+    load8<VEC>(pu_, e0, cnt, uv);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const float p = uv[j] + w * (cv[j] - uv[j]);
       ov[j] = ap * lcm_x0<MODE>(xv[j], p, al, sg) + sp * lcm_eps<MODE>(xv[j], p, al, sg);
     }
-    lcm_store<VEC>(o32, e0, cnt, ov);
-    lcm_store<VEC>(o16, e0, cnt, ov);
+    store8<VEC>(o32, e0, cnt, ov);
+    store8<VEC>(o16, e0, cnt, ov);
   }
 }
 
@@ -163,7 +100,7 @@ extern "C" int st355_lcm_solver_step(void* stream, const void* x_s, const void* 
   LcmSolverArgs a;
   a.x = (const bf16*)x_s; a.pair = (const bf16*)teacher_pair; a.w = w; a.index = index; a.start = start; a.sched = sched; a.prev = prev; a.out32 = x_prev32;
   a.out16 = (bf16*)x_prev16; a.per_sample = per_sample; a.batch = batch; a.sched_len = sched_len; a.prev_len = prev_len;
-  const dim3 grid(lcm_parts(batch, per_sample), (unsigned)batch), block(LCM_THREADS);
+  const dim3 grid(sample_parts(batch, per_sample), (unsigned)batch), block(LCM_THREADS);
   if (mode == 0) {
     if (vec) hipLaunchKernelGGL((k_lcm_solver<0, true>), grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((k_lcm_solver<0, false>), grid, block, 0, (hipStream_t)stream, a);
@@ -201,11 +138,11 @@ __global__ void __launch_bounds__(LCM_THREADS) k_lcm_target(const LcmTargetArgs 
     const int64_t e0 = i * 8;
     const int cnt = (n - e0) >= 8 ? 8 : (int)(n - e0);
     float xv[8], pv[8], ov[8];
-    lcm_load<VEC>(x_, e0, cnt, xv);
-    lcm_load<VEC>(p_, e0, cnt, pv);
+    load8<VEC>(x_, e0, cnt, xv);
+    load8<VEC>(p_, e0, cnt, pv);
 #pragma unroll
     for (int j = 0; j < 8; j++) ov[j] = c_skip * xv[j] + c_out * lcm_x0<MODE>(xv[j], pv[j], al, sg);
-    lcm_store<VEC>(o_, e0, cnt, ov);
+    store8<VEC>(o_, e0, cnt, ov);
   }
 }
 
@@ -220,7 +157,7 @@ extern "C" int st355_lcm_target(void* stream, const float* x_prev32, const void*
   LcmTargetArgs a;
   a.xprev = x_prev32; a.pred = (const bf16*)pred_t; a.t = timesteps; a.sched = sched; a.target = target; a.per_sample = per_sample; a.sched_len = sched_len;
   a.scaling = timestep_scaling;
-  const dim3 grid(lcm_parts(batch, per_sample), (unsigned)batch), block(LCM_THREADS);
+  const dim3 grid(sample_parts(batch, per_sample), (unsigned)batch), block(LCM_THREADS);
   if (mode == 0) {
     if (vec) hipLaunchKernelGGL((k_lcm_target<0, true>), grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((k_lcm_target<0, false>), grid, block, 0, (hipStream_t)stream, a);
@@ -259,14 +196,14 @@ __global__ void __launch_bounds__(LCM_THREADS) k_lcm_loss(const LcmLossArgs a) {
   const float dx0 = MODE == 0 ? -(sg / al) : -sg;
   const float gcoef = (a.dscale * c_out) * dx0;
   const float c = a.huber_c, c2 = c * c;
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int64_t i = (int64_t)blockIdx.x * LCM_THREADS + threadIdx.x; i < groups; i += (int64_t)gridDim.x * LCM_THREADS) {
     const int64_t e0 = i * 8;
     const int cnt = (n - e0) >= 8 ? 8 : (int)(n - e0);
     float pv[8], xv[8], tv[8], gv[8];
-    lcm_load<VEC>(p_, e0, cnt, pv);
-    lcm_load<VEC>(x_, e0, cnt, xv);
-    lcm_load<VEC>(t_, e0, cnt, tv);
+    load8<VEC>(p_, e0, cnt, pv);
+    load8<VEC>(x_, e0, cnt, xv);
+    load8<VEC>(t_, e0, cnt, tv);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const float m = c_skip * xv[j] + c_out * lcm_x0<MODE>(xv[j], pv[j], al, sg);
@@ -280,36 +217,12 @@ __global__ void __launch_bounds__(LCM_THREADS) k_lcm_loss(const LcmLossArgs a) {
         l = r - c;
         g = d / r;
       }
-      if (VEC || j < cnt) acc += l;
+      if (VEC || j < cnt) acc[0] += l;
       gv[j] = gcoef * g;
     }
-    if (d_) lcm_store<VEC>(d_, e0, cnt, gv);
+    if (d_) store8<VEC>(d_, e0, cnt, gv);
   }
-  acc = wave_sum(acc);
-  __shared__ float red[LCM_THREADS / WAVE];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < LCM_THREADS / WAVE; i++) s += red[i];
-    a.ws[(int64_t)b * gridDim.x + blockIdx.x] = s;
-  }
-}
-
-// stage 2, one workgroup: per sample the partials in index order -> per_sample[b] = sum / n; then the batch mean in sample order
-__global__ void __launch_bounds__(LCM_THREADS) k_lcm_finish(const float* __restrict__ ws, float* __restrict__ loss, float* __restrict__ per_sample_out, int B, int parts,
-                                                           float inv_per_sample) {
-  for (int b = threadIdx.x; b < B; b += LCM_THREADS) {
-    float s = 0.f;
-    for (int p = 0; p < parts; p++) s += ws[(int64_t)b * parts + p];
-    per_sample_out[b] = s * inv_per_sample;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int b = 0; b < B; b++) s += per_sample_out[b];
-    loss[0] = s / (float)B;
-  }
+  block_reduce<1>(acc, a.ws, b);
 }
 
 template <int MODE, int LOSS>
@@ -326,7 +239,7 @@ extern "C" int st355_lcm_loss(void* stream, const void* pred, const void* x_s, c
              "lcm_loss: bad args (mode %d, loss_type %d, sched_len %d, batch %ld)", mode, loss_type, sched_len, (long)batch);
   ST_REQUIRE(dpred != pred, "lcm_loss: dpred and pred must be different buffers");
   const bool vec = per_sample % 8 == 0 && (((uintptr_t)pred | (uintptr_t)x_s | (uintptr_t)target | (uintptr_t)dpred) & 15) == 0;
-  const int parts = lcm_parts(batch, per_sample);
+  const int parts = sample_parts(batch, per_sample);
   const double n = (double)batch * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 14.0 * n, (8.0 + (dpred ? 2.0 : 0.0)) * n);
   LcmLossArgs a;
@@ -341,8 +254,7 @@ extern "C" int st355_lcm_loss(void* stream, const void* pred, const void* x_s, c
     if (loss_type == 0) lcm_loss_launch<1, 0>(vec, grid, block, (hipStream_t)stream, a);
     else lcm_loss_launch<1, 1>(vec, grid, block, (hipStream_t)stream, a);
   }
-  hipLaunchKernelGGL(k_lcm_finish, dim3(1), block, 0, (hipStream_t)stream, (const float*)workspace, loss_out, per_sample_out, (int)batch, parts,
-                     1.0f / (float)per_sample);
+  sample_mean_finish((hipStream_t)stream, (const float*)workspace, nullptr, loss_out, per_sample_out, (int)batch, parts, 1.0f / (float)per_sample);
   return st355_check_launch("lcm_loss");
 }
 
@@ -371,15 +283,15 @@ __global__ void __launch_bounds__(LCM_THREADS) k_lcm_sample(const LcmSampleArgs 
     const int64_t e0 = i * 8;
     const int cnt = (n - e0) >= 8 ? 8 : (int)(n - e0);
     float xv[8], pv[8], nv[8], ov[8];
-    lcm_load<VEC>(a.x, e0, cnt, xv);
-    lcm_load<VEC>(a.pred, e0, cnt, pv);
-    if (!last) lcm_load<VEC>(a.noise, e0, cnt, nv);
+    load8<VEC>(a.x, e0, cnt, xv);
+    load8<VEC>(a.pred, e0, cnt, pv);
+    if (!last) load8<VEC>(a.noise, e0, cnt, nv);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const float den = c_skip * xv[j] + c_out * lcm_x0<MODE>(xv[j], pv[j], al, sg);
       ov[j] = last ? den : an * den + sn * nv[j];
     }
-    lcm_store<VEC>(a.out, e0, cnt, ov);
+    store8<VEC>(a.out, e0, cnt, ov);
   }
 }
 

@@ -10,40 +10,14 @@
 // All three stream 16 bytes per lane.  Both reductions run in two stages in a fixed order — stage 1: `parts` workgroups per sample, each lane a strided run of
 // vectors, lane tree, then the wave partials in wave order; stage 2, on the device: the `parts` partials in index order — so every output repeats bit for bit, and
 // nothing is read on the host.  No atomics.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define RF_THREADS OP_THREADS
 #define RF_EPS 1e-6f
 
-// partial workgroups per sample: the op_blocks grid (at most 2048 workgroups of 256) divided among the samples
-static inline int rf_parts(int64_t batch, int64_t per_sample) {
-  int64_t p = cdiv64(per_sample >> 3, RF_THREADS);
-  const int64_t cap = (256 * 8) / batch;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
 extern "C" int64_t st355_reflexflow_workspace(int64_t batch, int64_t per_sample) {
   if (batch <= 0 || per_sample <= 0) return 0;
-  return (int64_t)sizeof(float) * 4 * batch * rf_parts(batch, per_sample);
-}
-
-// the block's NV sums -> ws[(b * parts + part) * 4 + k]: lane tree, then the wave partials in wave order
-template <int NV>
-__device__ __forceinline__ void rf_block_reduce(float (&acc)[NV], float* __restrict__ dst) {
-  __shared__ float red[NV][RF_THREADS / WAVE];
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    float s = 0.f;
-    for (int w = 0; w < RF_THREADS / WAVE; w++) s += red[threadIdx.x][w];
-    dst[threadIdx.x] = s;
-  }
+  return (int64_t)sizeof(float) * 4 * batch * sample_parts(batch, per_sample);
 }
 
 // ---- stats ----------------------------------------------------------------------------------------------------------------------------------------
@@ -73,7 +47,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_rf_stats(const bf16* __restrict_
       acc[3] += p * tau;
     }
   }
-  rf_block_reduce<4>(acc, ws + ((int64_t)b * gridDim.x + blockIdx.x) * 4);
+  block_reduce<4>(acc, ws, b);
 }
 
 // stage 2: stats[b, k] = the partials of (b, k) in index order.  grid = B, 64 threads (4 used)
@@ -91,7 +65,7 @@ extern "C" int st355_reflexflow_stats(void* stream, const void* pred, const void
   ST_REQUIRE((clean == nullptr) == (biased == nullptr), "reflexflow_stats: clean and biased come together or not at all");
   ST_REQUIRE(per_sample > 0 && per_sample % 8 == 0 && batch > 0 && batch < 65536, "reflexflow_stats: bad shape (per_sample %ld must be a multiple of 8, batch %ld < 65536)",
              (long)per_sample, (long)batch);
-  const int parts = rf_parts(batch, per_sample);
+  const int parts = sample_parts(batch, per_sample);
   const double n = (double)batch * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 8.0 * n, (clean ? 10.0 : 6.0) * n);
   float* ws = (float*)workspace;
@@ -190,7 +164,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_rf_loss(const RfLossArgs a) {
     }
     if (want_grad) *(bf16x8*)(a.dpred + base + i * 8) = dv;
   }
-  rf_block_reduce<2>(acc, a.ws + ((int64_t)b * gridDim.x + blockIdx.x) * 4);
+  block_reduce<2, 4>(acc, a.ws, b);
 }
 
 // stage 2, one workgroup: per sample the partials in index order -> per_sample[b] = sum / n + beta1 adr, adr_out[b] = beta1 adr; then the batch mean in sample order
@@ -226,7 +200,7 @@ extern "C" int st355_reflexflow_loss(void* stream, const void* pred, const void*
   ST_REQUIRE((clean == nullptr) == (biased == nullptr), "reflexflow_loss: clean and biased come together or not at all");
   ST_REQUIRE(beta1 == 0.f || (noisy && latents), "reflexflow_loss: the ADR term (beta1 != 0) needs noisy and latents");
   ST_REQUIRE(stats || (beta1 == 0.f && !(clean && alpha != 0.f)), "reflexflow_loss: the exposure weight and the ADR term need the stats of st355_reflexflow_stats");
-  const int parts = rf_parts(batch, per_sample);
+  const int parts = sample_parts(batch, per_sample);
   const double n = (double)batch * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 20.0 * n, (4.0 + (beta1 != 0.f ? 4.0 : 0.0) + (clean && alpha != 0.f ? 4.0 : 0.0) + (dpred ? 2.0 : 0.0)) * n);
   RfLossArgs a;

@@ -14,55 +14,14 @@
 //   st355_st_wgrad      g_W [R, Cc] (+)= s P, g_b [R] (+)= s db: P bf16 from gemm_tn, db fp32 from colsum_prod, s ONE fp32 on the device.
 //   st355_st_dx_add     dx[b, r, :] = bf16(float(dx) + s g[b rows + r, :]): a compact [B rows, D] addend into a strided [B, rows, D] view.
 // s is ONE fp32 on the device (weight x the upstream gradient x the accumulation division x stats[2]): G stays unscaled through the bf16 chain.
-#include "common.h"
+#include "feature_common.h"
 
-#define STR_TILE 64                   // fold: tile edge
 #define STR_BLOCK 256
 #define STR_MAX_CHUNKS 256            // loss: workgroups per sample
 #define STR_MAX_B 4096
 
-__device__ __forceinline__ void str_ld8(const float* p, float (&v)[8]) {
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void str_ld8(const bf16* p, float (&v)[8]) {
-  const bf16x8 a = *(const bf16x8*)p;
-#pragma unroll
-  for (int j = 0; j < 8; j++) v[j] = bf2f(a[j]);
-}
-
 // ---- fold ----
-// one 64 x 64 tile of src [R, Cc] fp32 -> out [R, Cc] bf16 and outT [Cc, R].  Thread (row = tid >> 3, chunk = tid & 7) converts 8 columns of rows row and row + 32,
-// stores them straight and into the LDS tile; after the barrier thread (col = tid >> 3, i = tid & 7) gathers rows 8 i .. 8 i + 7 of columns col and col + 32 and stores
-// 16 bytes of outT.  LDS: [64][64] bf16, the 16-byte chunk index XORed with (row >> 3) & 7: the 8 values of i hit 8 different chunks (the layout of nextlat.hip's fold).
-__device__ __forceinline__ void str_fold_tile(bf16* tile, const float* __restrict__ src, bf16* __restrict__ out, bf16* __restrict__ outT, int R, int Cc, int r0, int c0) {
-  const int tid = threadIdx.x, ch = tid & 7;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int r = (tid >> 3) + 32 * k, gr = r0 + r, gc = c0 + ch * 8;
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = f2bf(0.f);
-    if (gr < R && gc < Cc) {                                      // Cc % 8 == 0: a chunk lies wholly inside or outside
-      float v[8];
-      str_ld8(src + (int64_t)gr * Cc + gc, v);
-#pragma unroll
-      for (int j = 0; j < 8; j++) o[j] = f2bf(v[j]);
-      *(bf16x8*)(out + (int64_t)gr * Cc + gc) = o;
-    }
-    *(bf16x8*)(&tile[r * STR_TILE + ((ch ^ ((r >> 3) & 7)) << 3)]) = o;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int cc = (tid >> 3) + 32 * k, i = tid & 7, gcc = c0 + cc, gr = r0 + 8 * i;
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = tile[(8 * i + j) * STR_TILE + ((((cc >> 3) ^ i) << 3) | (cc & 7))];
-    if (gcc < Cc && gr < R) *(bf16x8*)(outT + (int64_t)gcc * R + gr) = o;          // R % 8 == 0
-  }
-}
-
+// the three matrices tile by tile on fold_tile of feature_common.h (fp32 sources, no column scale)
 struct StrFold {
   const float *W1, *b1, *W2, *b2, *W3, *b3;
   bf16 *W1h, *W1T, *b1h, *W2h, *W2T, *b2h, *W3h, *W3T, *b3h;
@@ -72,21 +31,21 @@ struct StrFold {
 
 // workgroup-uniform dispatch on blockIdx.x: [0, t1) W1 [Hp, D], [t1, t1 + t2) W2 [Hp, Hp], [.., + t3) the first P3 rows of W3 [D, Hp], then b1 | b2 | b3[:P3], 8 per lane
 __global__ void __launch_bounds__(STR_BLOCK) k_str_fold(StrFold a) {
-  __shared__ __attribute__((aligned(16))) bf16 tile[STR_TILE * STR_TILE];
+  __shared__ __attribute__((aligned(16))) bf16 tile[FOLD_TILE * FOLD_TILE];
   int blk = blockIdx.x;
-  const int tcD = (a.D + STR_TILE - 1) / STR_TILE, tcH = (a.Hp + STR_TILE - 1) / STR_TILE;
+  const int tcD = (a.D + FOLD_TILE - 1) / FOLD_TILE, tcH = (a.Hp + FOLD_TILE - 1) / FOLD_TILE;
   if (blk < a.t1) {
-    str_fold_tile(tile, a.W1, a.W1h, a.W1T, a.Hp, a.D, (blk / tcD) * STR_TILE, (blk % tcD) * STR_TILE);
+    fold_tile(tile, a.W1, (const float*)nullptr, a.W1h, a.W1T, a.Hp, a.D, (blk / tcD) * FOLD_TILE, (blk % tcD) * FOLD_TILE);
     return;
   }
   blk -= a.t1;
   if (blk < a.t2) {
-    str_fold_tile(tile, a.W2, a.W2h, a.W2T, a.Hp, a.Hp, (blk / tcH) * STR_TILE, (blk % tcH) * STR_TILE);
+    fold_tile(tile, a.W2, (const float*)nullptr, a.W2h, a.W2T, a.Hp, a.Hp, (blk / tcH) * FOLD_TILE, (blk % tcH) * FOLD_TILE);
     return;
   }
   blk -= a.t2;
   if (blk < a.t3) {
-    str_fold_tile(tile, a.W3, a.W3h, a.W3T, a.P3, a.Hp, (blk / tcH) * STR_TILE, (blk % tcH) * STR_TILE);
+    fold_tile(tile, a.W3, (const float*)nullptr, a.W3h, a.W3T, a.P3, a.Hp, (blk / tcH) * FOLD_TILE, (blk % tcH) * FOLD_TILE);
     return;
   }
   blk -= a.t3;
@@ -98,11 +57,8 @@ __global__ void __launch_bounds__(STR_BLOCK) k_str_fold(StrFold a) {
   else if (e < 2 * a.Hp + a.P3) { src = a.b3 + (e - 2 * a.Hp); dst = a.b3h + (e - 2 * a.Hp); }
   else return;
   float v[8];
-  str_ld8(src, v);
-  bf16x8 o;
-#pragma unroll
-  for (int j = 0; j < 8; j++) o[j] = f2bf(v[j]);
-  *(bf16x8*)dst = o;
+  ld8(src, v);
+  st8(dst, v, 0);
 }
 
 extern "C" int st355_st_fold(void* stream, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, void* W1h, void* W1T,
@@ -117,7 +73,7 @@ extern "C" int st355_st_fold(void* stream, const float* W1, const float* b1, con
   a.W1h = (bf16*)W1h; a.W1T = (bf16*)W1T; a.b1h = (bf16*)b1h; a.W2h = (bf16*)W2h; a.W2T = (bf16*)W2T; a.b2h = (bf16*)b2h;
   a.W3h = (bf16*)W3h; a.W3T = (bf16*)W3T; a.b3h = (bf16*)b3h;
   a.D = D; a.Hp = Hp; a.P3 = P3;
-  const int tcD = (D + STR_TILE - 1) / STR_TILE, tcH = (Hp + STR_TILE - 1) / STR_TILE, trP = (P3 + STR_TILE - 1) / STR_TILE;
+  const int tcD = (D + FOLD_TILE - 1) / FOLD_TILE, tcH = (Hp + FOLD_TILE - 1) / FOLD_TILE, trP = (P3 + FOLD_TILE - 1) / FOLD_TILE;
   a.t1 = tcH * tcD; a.t2 = tcH * tcH; a.t3 = trP * tcH;
   const int vec_blocks = ((2 * Hp + P3) / 8 + STR_BLOCK - 1) / STR_BLOCK;
   const double el = (double)Hp * D + (double)Hp * Hp + (double)P3 * Hp;
@@ -163,8 +119,8 @@ __global__ void __launch_bounds__(STR_BLOCK) k_str_loss(bf16* pred, StrVae va, S
     if (CFG) {
       const int64_t off = (int64_t)b * ca.bstride + (int64_t)r * ca.ld + col;
       float c[8], u[8];
-      str_ld8(ca.c + off, c);
-      str_ld8(ca.u + off, u);
+      ld8(ca.c + off, c);
+      ld8(ca.u + off, u);
 #pragma unroll
       for (int j = 0; j < 8; j++) t[j] = fmaf(ca.scale, c[j] - u[j], u[j]);
     } else {
@@ -188,6 +144,7 @@ __global__ void __launch_bounds__(STR_BLOCK) k_str_loss(bf16* pred, StrVae va, S
   acc = wave_sum(acc);
   if (lane == 0) part[w] = acc;
   __syncthreads();
+  // (pairwise, not block_reduce's wave order: this kernel's bits since its first release)
   if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
@@ -283,9 +240,9 @@ __global__ void __launch_bounds__(STR_BLOCK) k_str_wgrad(const bf16* __restrict_
   const int64_t i = (int64_t)blockIdx.x * STR_BLOCK + threadIdx.x;
   if (i >= n8) return;
   float v[8], o[8];
-  str_ld8(P + i * 8, v);
+  ld8(P + i * 8, v);
   if (accumulate) {
-    str_ld8(g_W + i * 8, o);
+    ld8(g_W + i * 8, o);
 #pragma unroll
     for (int j = 0; j < 8; j++) o[j] = fmaf(s, v[j], o[j]);
   } else {

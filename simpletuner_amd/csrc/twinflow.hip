@@ -10,22 +10,13 @@
 // All three stream 16 bytes per lane.  The loss's reduction runs in two stages in a fixed order — stage 1: `parts` workgroups per sample, each lane a strided run
 // of vectors, lane tree, then the wave partials in wave order; stage 2, one workgroup: contiguous runs of the partials in (sample, part) order, then the run
 // sums in thread order — so every output repeats bit for bit, and nothing is read on the host.  No atomics.
-#include "optim_common.h"
+#include "feature_common.h"
 
 #define TF_THREADS OP_THREADS
 
-// partial workgroups per sample: the op_blocks grid (at most 2048 workgroups of 256) divided among the samples
-static inline int tf_parts(int64_t batch, int64_t per_sample) {
-  int64_t p = cdiv64(per_sample >> 3, TF_THREADS);
-  const int64_t cap = (256 * 8) / batch;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
 extern "C" int64_t st355_twinflow_workspace(int64_t batch, int64_t per_sample) {
   if (batch <= 0 || per_sample <= 0) return 0;
-  return (int64_t)sizeof(float) * 2 * batch * tf_parts(batch, per_sample);
+  return (int64_t)sizeof(float) * 2 * batch * sample_parts(batch, per_sample);
 }
 
 // ---- RCGM step ------------------------------------------------------------------------------------------------------------------------------------
@@ -84,7 +75,6 @@ template <bool HAS_CFG>
 __global__ void __launch_bounds__(TF_THREADS) k_tf_loss(const bf16* __restrict__ pred, const bf16* __restrict__ target, const float* __restrict__ accum,
                                                        const bf16* __restrict__ cond, const bf16* __restrict__ uncond, float* __restrict__ ws,
                                                        bf16* __restrict__ dpred, int64_t per_sample, float ratio, float clampv, float gscale) {
-  __shared__ float red[2][TF_THREADS / WAVE];
   const int b = blockIdx.y;
   const int64_t base = (int64_t)b * per_sample, vecs = per_sample >> 3;
   const bool want_grad = dpred != nullptr;
@@ -112,17 +102,7 @@ __global__ void __launch_bounds__(TF_THREADS) k_tf_loss(const bf16* __restrict__
     }
     if (want_grad) *(bf16x8*)(dpred + base + i * 8) = dv;
   }
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    float s = 0.f;
-    for (int w = 0; w < TF_THREADS / WAVE; w++) s += red[threadIdx.x][w];
-    ws[((int64_t)b * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = s;
-  }
+  block_reduce<2>(acc, ws, b);
 }
 
 // stage 2, one workgroup: thread t sums its contiguous run of the B * parts partials in index order, then thread k < 2 sums the 256 run sums of k in thread order
@@ -155,7 +135,7 @@ extern "C" int st355_twinflow_loss(void* stream, const void* pred, const void* t
              (long)per_sample, (long)batch);
   ST_REQUIRE(clamp >= 0.f, "twinflow_loss: the clamp (%g) must not be negative", (double)clamp);
   ST_REQUIRE(((uintptr_t)acc & 15) == 0, "twinflow_loss: acc must be 16-byte aligned");
-  const int parts = tf_parts(batch, per_sample);
+  const int parts = sample_parts(batch, per_sample);
   const double n = (double)batch * per_sample;
   ProfScope ps(stream, ST355_K_ELEMENTWISE, 10.0 * n, (8.0 + (cond ? 4.0 : 0.0) + (dpred ? 2.0 : 0.0)) * n);
   const float gscale = (float)((double)grad_scale * 2.0 / n);

@@ -46,7 +46,7 @@ def gamma(n: int) -> float:
 
 
 def stats_depth(B: int, N: int) -> int:
-    """the most additions any term takes part in: csrc/flow_dpo.hip's grid rule (fd_parts: 256 lanes of 8 elements per partial workgroup, at most 2048 / B of them
+    """the most additions any term takes part in: csrc/flow_dpo.hip's grid rule (sample_parts of feature_common.h: 256 lanes of 8 elements per partial workgroup, at most 2048 / B of them
     per pair), restated"""
     vecs = N // 8
     parts = max(1, min(-(-vecs // 256), 2048 // B))
