@@ -1205,6 +1205,20 @@ int st355_attn_bwd_res(void* stream, const void* Q, const void* K, const void* Q
                        int64_t ld_o, const void* O_res, const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, void* dQ, void* dK,
                        void* dv_rows, int64_t ld_dv, int B, int H, int Sq, int Sqp, int Sk, int Skp, int d, float scale, void* workspace);
 
+/* ---- fused attention for heads wider than 128 channels (csrc/attention_wide.hip; d = 160: SD 1.x's 8 heads over 1280 channels), self and cross, on TOKEN-MAJOR
+ * operands.  Every bf16 tensor pointer is the first column of a column block of a [B*S, ld] projection buffer: row b*S + i holds head h at columns h*d .. h*d + d - 1
+ * (S = Sq for q, o, dO, dq; Sk for k, v, dk, dv) — the fused qkv / q / kv Linears' outputs and to_out's input as they are; no head-split, padded, transposed or
+ * head-major copy on either side.  lse2 fp32 [B, H, Sq], log2 convention.  Sq, Sk >= 1 (ragged tails are masked in the kernels).  The backward is two kernels without
+ * atomics (bit-identical launches): dq takes delta_i = sum_j P_ij dP_ij in fp32 from a first pass over the keys (the backward never reads O) and leaves it in
+ * `workspace` (st355_attn_wide_bwd_workspace bytes: fp32 [B, H, Sq]) for dk / dv.  Every element of the q / k / v column blocks of dq / dk / dv is written.
+ * Preconditions: d == 160 (otherwise ST355_ENOSYS), ld_* % 8 == 0, ld_* >= H*d, 16-byte aligned block starts. */
+int st355_attn_wide_fwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, void* o, int64_t ld_o, float* lse2,
+                        int B, int H, int Sq, int Sk, int d, float scale);
+size_t st355_attn_wide_bwd_workspace(int B, int H, int Sq, int d);
+int st355_attn_wide_bwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* dO, int64_t ld_do,
+                        const float* lse2, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk, void* dv, int64_t ld_dv, void* workspace, int B, int H, int Sq,
+                        int Sk, int d, float scale);
+
 /* ---- workspace sizing: one query for every op that takes caller-provided scratch (the library never allocates).  dims per op:
  *   ATTN_BWD {B, H, Sq, Sqp, d}   COLSUM {rows, N, rows_per_batch}   SKINNY_TN {M, P, R}   GROUPNORM {B, H, W, C}   LAYERNORM_PARAM_GRADS {D}
  *   GEMM_SPLITK {M, N, K} (upper bound: 16 fp32 slabs)   GEMM_TN {P, Q, contraction, taps}.   Returns bytes, or -1 for an unknown op / too few dims. */

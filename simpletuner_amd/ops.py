@@ -1697,6 +1697,46 @@ def attn_ds_bytes(ds) -> int:
 
 # ST355_ATTN_TR=0: the engines build head-major Q^T / K^T copies and the backward reads them (dkv2 / dq); default: no copies, transposing LDS reads
 ATTN_TR = os.environ.get("ST355_ATTN_TR", "1") != "0"
+# ST355_ATTN_WIDE=1: the UNet sends 160-wide heads (SD 1.x) to the fused token-major kernels below; default: the unfused per-(image, head) path
+ATTN_WIDE = os.environ.get("ST355_ATTN_WIDE", "0") == "1"
+
+
+def _wide_block(t, name: str, rows: int, cols: int) -> int:
+    """a token-major column block [rows, H*d] of a projection buffer (a column slice as it is): its leading dimension"""
+    _chk(t, BF16, name)
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols):
+        raise _l.St355Error(f"attn_wide: {name}: expected a [{rows}, {cols}] column block, got {tuple(t.shape)}")
+    return _rows(t, name)
+
+
+def attn_wide_fwd(q, k, v, o, lse2, B, H, Sq, Sk, d, scale: float):
+    """Fused attention on token-major column blocks (csrc/attention_wide.hip; d = 160): q / o [B*Sq, H*d], k / v [B*Sk, H*d] views of [B*S, ld] buffers with
+    unit inner stride, head h at columns h*d; lse2 fp32 [B, H, Sq] contiguous (log2 units).  Writes o and lse2."""
+    L = _l.load()
+    lds = [_wide_block(t, n, B * S_, H * d) for t, n, S_ in ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq))]
+    _chk(lse2, F32, "lse2")
+    if tuple(lse2.shape) != (B, H, Sq) or not lse2.is_contiguous():
+        raise _l.St355Error(f"attn_wide_fwd: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
+    _l.check(L.st355_attn_wide_fwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(lse2), B, H, Sq, Sk, d, scale),
+             "attn_wide_fwd")
+
+
+def attn_wide_bwd_workspace(dev, B, H, Sq, d):
+    """the fp32 delta [B, H, Sq] of attn_wide_bwd: one scratch per device under the rule of _scratch"""
+    return _scratch("attn_wide_bwd", dev, _l.load().st355_attn_wide_bwd_workspace(B, H, Sq, d))
+
+
+def attn_wide_bwd(q, k, v, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: float):
+    """Backward of attn_wide_fwd in the same layout: dq / dk / dv are column blocks like q / k / v (every element is written); two kernels, no atomics."""
+    L = _l.load()
+    lds = [_wide_block(t, n, B * S_, H * d) for t, n, S_ in ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (dO, "dO", Sq), (dq, "dq", Sq), (dk, "dk", Sk),
+                                                            (dv, "dv", Sk))]
+    _chk(lse2, F32, "lse2")
+    if tuple(lse2.shape) != (B, H, Sq) or not lse2.is_contiguous():
+        raise _l.St355Error(f"attn_wide_bwd: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
+    ws = attn_wide_bwd_workspace(q.device, B, H, Sq, d)
+    _l.check(L.st355_attn_wide_bwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(dO), lds[3], _ptr(lse2), _ptr(dq), lds[4], _ptr(dk), lds[5],
+                                   _ptr(dv), lds[6], _ptr(ws), B, H, Sq, Sk, d, scale), "attn_wide_bwd")
 
 
 def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None, ds=None, ds_bytes=None):

@@ -3,7 +3,8 @@
 `StableDiffusion1` (epsilon) and `StableDiffusion2` (v-prediction) as the reference declares them (sd1x/model.py:33-60, 351-380) and their step-path
 call `(noisy_latents, timesteps, encoder_hidden_states, return_dict=False)[0]` (sd1x/model.py:224-270) — BASELINE.json configs[0] is the SD 1.5
 UNet with LoRA rank 16 at 512^2.  The UNet is the same engine as SDXL's with the SD1.5 architecture: 4 levels (320/640/1280/1280), 8 heads per
-attention (widths 40 / 80 -> zero-padded heads on the flash kernels, 160 -> the unfused per-head path at <= 256 tokens), conv proj_in/out,
+attention (widths 40 / 80 -> zero-padded heads on the flash kernels, 160 -> the unfused per-head path at <= 256 tokens, or with
+ST355_ATTN_WIDE=1 the fused head_dim-160 kernels on the token-major projection outputs, csrc/attention_wide.hip), conv proj_in/out,
 no addition embedding, text width 768.
 """
 from __future__ import annotations

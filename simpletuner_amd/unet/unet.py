@@ -589,10 +589,13 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
     def _attention(self, T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads):
         """softmax(q k^T / sqrt(hd)) v over `heads` heads of width hd = C_/heads; q / k / v are column blocks (offsets qo / ko / vo) of the token-major
         projection outputs.  hd in {64, 128}: the flash kernels on the buffers as they are; other hd <= 128 (SD1.5's 40 -> 64, 80 -> 96; 81..128 -> 128): zero-padded
-        heads; hd > 128 (SD1.5's 160, at <= 256 tokens): unfused GEMM - softmax - GEMM per head."""
+        heads; hd > 128 (SD1.5's 160, at <= 256 tokens): unfused GEMM - softmax - GEMM per head — or, under ST355_ATTN_WIDE=1 and hd == 160, the fused
+        token-major kernels of csrc/attention_wide.hip (_attention_wide: any token count, no copies)."""
         hd = C_ // heads
         hp = 64 if hd <= 64 else 96 if hd <= 80 else 128 if hd <= 128 else 0      # (the head_dim-96 kernels contract over 80 channels: a head wider than 80 pads to 128)
         if hp == 0:
+            if ops.ATTN_WIDE and hd == 160:
+                return self._attention_wide(T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads)
             return self._attention_unfused(T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads)
         scale = 1.0 / math.sqrt(hd)
         dev = qsrc.device
@@ -715,6 +718,27 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
                 return self._linear_bwd(lq, n2, Tl, dq_src), dkv
             T.rec([Op], [n2, kv], bwd)
         return Op
+
+    def _attention_wide(self, T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads):
+        """160-wide heads under ST355_ATTN_WIDE=1: one fused forward launch and two backward launches (csrc/attention_wide.hip) on the projection buffers' column
+        blocks as they are — no per-head loop, no padded / head-major / transposed copy, no host read (a captured step replays it).  The backward takes delta from
+        sum_j P dP, not from the bf16 O, so it needs no rounding residual."""
+        hd = C_ // heads
+        scale = 1.0 / math.sqrt(hd)
+        dev = qsrc.device
+        self_attn = qsrc is kvsrc
+        q, k, v = qsrc[:, qo:qo + C_], kvsrc[:, ko:ko + C_], kvsrc[:, vo:vo + C_]
+        O = torch.empty(B * S, C_, dtype=BF16, device=dev)
+        lse = torch.empty(B, heads, S, dtype=F32, device=dev)
+        ops.attn_wide_fwd(q, k, v, O, lse, B, heads, S, Sk, hd, scale)
+        if T is not None:
+            def bwd(dO):
+                dq_src = torch.empty_like(qsrc)               # every column block is written by the kernels
+                dkv_src = dq_src if self_attn else torch.empty_like(kvsrc)
+                ops.attn_wide_bwd(q, k, v, dO, lse, dq_src[:, qo:qo + C_], dkv_src[:, ko:ko + C_], dkv_src[:, vo:vo + C_], B, heads, S, Sk, hd, scale)
+                return (dq_src,) if self_attn else (dq_src, dkv_src)
+            T.rec([O], [qsrc] if self_attn else [qsrc, kvsrc], bwd)
+        return O
 
     def _attention_unfused(self, T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads):
         """heads wider than 128 (SD1.5: 160 at the 16^2 / 8^2 levels): per (image, head) scores = q k^T (GEMM), row softmax, p v (GEMM); backward
