@@ -1137,6 +1137,13 @@ typedef struct st355_vae_encoder {
 size_t st355_vae_encode_workspace(const st355_vae_encoder* enc, int B, int H, int W);
 int st355_vae_encode(void* stream, const st355_vae_encoder* enc, const void* pixels, void* moments, int B, int H, int W, void* workspace,
                      size_t workspace_bytes);
+/* The same two entry points with a route word (the plain symbols pass 0 and are unchanged).  ST355_VAE_FUSED_ATTN: a mid block of width 512 runs its attention as
+ * ONE st355_attn_d512_fwd launch on the qkv buffer's column blocks instead of the per-image GEMM - softmax - transpose - GEMM sequence, and the workspace holds
+ * neither the [S, S] score matrix nor V^T (any other width keeps the sequence).  No process-global state: the route is an argument of each call. */
+#define ST355_VAE_FUSED_ATTN 1u
+size_t st355_vae_encode_workspace_flags(const st355_vae_encoder* enc, int B, int H, int W, uint32_t flags);
+int st355_vae_encode_flags(void* stream, const st355_vae_encoder* enc, const void* pixels, void* moments, int B, int H, int W, void* workspace,
+                           size_t workspace_bytes, uint32_t flags);
 /* in-place row softmax of a bf16 matrix: x[r, :n] = softmax(scale * x[r, :n]) (fp32 math) — the single-head d=512 attention of the VAE mid block */
 int st355_softmax_rows(void* stream, void* x, int64_t ldx, int64_t rows, int n, float scale);
 /* its backward, in place on dp: ds = scale * p * (dp - rowsum(dp * p))  (unfused attention of heads wider than 128: SD1.5's 160 at tiny S) */
@@ -1218,6 +1225,15 @@ size_t st355_attn_wide_bwd_workspace(int B, int H, int Sq, int d);
 int st355_attn_wide_bwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* dO, int64_t ld_do,
                         const float* lse2, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk, void* dv, int64_t ld_dv, void* workspace, int B, int H, int Sq,
                         int Sk, int d, float scale);
+
+/* Fused forward attention for 512-wide heads (the single head of the AutoencoderKL mid block), csrc/attention_d512.hip, under the contract of st355_attn_wide_fwd:
+ * q / o [B*Sq, H*d] and k / v [B*Sk, H*d] token-major bf16 column blocks used in place with their leading dimensions (for the VAE the three 512-column thirds
+ * of the [B*S, 3C] qkv GEMM output), head h at columns h*d, Sq, Sk >= 1 (ragged tails are masked in the kernel).  One launch for all images and heads, no buffer
+ * proportional to Sq*Sk, scores in fp32 (P rounded to bf16 once before the P V product, l sums the fp32 values), no atomics: bit-identical launches.
+ * lse2: fp32 [B, H, Sq], log2 convention, written only when non-NULL; O is bit-identical with and without it.
+ * Preconditions: d == 512 (otherwise ST355_ENOSYS), scale > 0, ld_* % 8 == 0, ld_* >= H*d, 16-byte aligned block starts. */
+int st355_attn_d512_fwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, void* o, int64_t ld_o, float* lse2,
+                        int B, int H, int Sq, int Sk, int d, float scale);
 
 /* ---- workspace sizing: one query for every op that takes caller-provided scratch (the library never allocates).  dims per op:
  *   ATTN_BWD {B, H, Sq, Sqp, d}   COLSUM {rows, N, rows_per_batch}   SKINNY_TN {M, P, R}   GROUPNORM {B, H, W, C}   LAYERNORM_PARAM_GRADS {D}

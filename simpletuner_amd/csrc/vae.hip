@@ -27,7 +27,7 @@ struct Stack {
 };
 
 struct Enc {
-  hipStream_t st; const st355_vae_encoder* e; Stack m; int B; void* gn_ws; int rc; int wi;
+  hipStream_t st; const st355_vae_encoder* e; Stack m; int B; void* gn_ws; int rc; int wi; uint32_t flags;
   const void* next() { return e->tensors[wi++]; }
   bool ok() const { return rc == 0; }
   void chk(int r) { if (rc == 0 && r != 0) rc = r; }
@@ -83,7 +83,8 @@ struct Enc {
     a.A = A; a.lda = lda; a.B = Bm; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.bias = bias; a.epilogue = ST355_EPI_NONE;
     chk(st355_gemm_bf16(st, &a));
   }
-  // UNetMidBlock2D attention: one head of width C over the S = H*W positions of each image: scores = q k^T as a plain [S, S] GEMM, row softmax, P V
+  // UNetMidBlock2D attention: one head of width C over the S = H*W positions of each image: scores = q k^T as a plain [S, S] GEMM, row softmax, P V —
+  // or, under ST355_VAE_FUSED_ATTN at width 512, one fused launch on the qkv buffer's column blocks (attention_d512.hip): no scores, no V^T
   void* mid_attention(const void* x, int H, int W, int C) {
     void* out = grid(H, W, C, false);
     const size_t mark = m.top;
@@ -93,6 +94,10 @@ struct Enc {
     bf16* qkv = (bf16*)m.alloc((size_t)B * S * 3 * C * 2);
     gemm(n, C, wqkv, C, bqkv, qkv, 3 * C, B * S, 3 * C, C);
     bf16* o = (bf16*)m.alloc((size_t)B * S * C * 2);
+    if ((flags & ST355_VAE_FUSED_ATTN) && C == 512) {
+      if (!m.dry && ok()) chk(st355_attn_d512_fwd(st, qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, o, C, nullptr, B, 1, S, S, C, 1.0f / sqrtf((float)C)));
+      return mid_attention_out(x, o, wo, bo, out, mark, H, W, C);
+    }
     bf16* scores = (bf16*)m.alloc((size_t)S * Sp * 2);
     bf16* sc_raw = Sp != S ? (bf16*)m.alloc((size_t)S * S * 2) : scores;
     bf16* vt = (bf16*)m.alloc((size_t)C * Sp * 2);
@@ -108,6 +113,10 @@ struct Enc {
       if (!m.dry && ok()) chk(st355_transpose_bf16(st, v, 3 * C, vt, Sp, S, C));
       gemm(scores, Sp, vt, Sp, nullptr, o + (size_t)b * S * C, C, S, C, Sp);
     }
+    return mid_attention_out(x, o, wo, bo, out, mark, H, W, C);
+  }
+  void* mid_attention_out(const void* x, const bf16* o, const void* wo, const void* bo, void* out, size_t mark, int H, int W, int C) {
+    const int S = H * W;
     bf16* proj = (bf16*)m.alloc((size_t)B * S * C * 2);
     gemm(o, C, wo, C, bo, proj, C, B * S, C, C);
     if (!m.dry && ok()) chk(st355_tokens_to_grid(st, proj, x, out, B, H, W, C));
@@ -164,20 +173,28 @@ int check(const st355_vae_encoder* e, int B, int H, int W) {
 }
 }  // namespace
 
-extern "C" size_t st355_vae_encode_workspace(const st355_vae_encoder* enc, int B, int H, int W) {
+extern "C" size_t st355_vae_encode_workspace_flags(const st355_vae_encoder* enc, int B, int H, int W, uint32_t flags) {
   if (check(enc, B, H, W) != ST355_OK) return 0;
-  Enc r{nullptr, enc, Stack{nullptr, 0, 0, 0, true}, B, nullptr, 0, 0};
+  Enc r{nullptr, enc, Stack{nullptr, 0, 0, 0, true}, B, nullptr, 0, 0, flags};
   r.run(nullptr, nullptr, H, W);
   return r.m.peak + 256;
 }
 
-extern "C" int st355_vae_encode(void* stream, const st355_vae_encoder* enc, const void* pixels, void* moments, int B, int H, int W, void* workspace,
-                                size_t workspace_bytes) {
+extern "C" int st355_vae_encode_flags(void* stream, const st355_vae_encoder* enc, const void* pixels, void* moments, int B, int H, int W, void* workspace,
+                                      size_t workspace_bytes, uint32_t flags) {
   int rc = check(enc, B, H, W);
   if (rc) return rc;
+  ST_REQUIRE((flags & ~ST355_VAE_FUSED_ATTN) == 0, "vae_encode: unknown flags 0x%x", flags);
   ST_REQUIRE(pixels && moments && workspace && ((uintptr_t)workspace % 256) == 0, "vae_encode: null / misaligned pointer");
-  const size_t need = st355_vae_encode_workspace(enc, B, H, W);
+  const size_t need = st355_vae_encode_workspace_flags(enc, B, H, W, flags);
   ST_REQUIRE(workspace_bytes >= need, "vae_encode: workspace of %zu bytes, %zu needed (st355_vae_encode_workspace)", workspace_bytes, need);
-  Enc r{(hipStream_t)stream, enc, Stack{(char*)workspace, workspace_bytes, 0, 0, false}, B, nullptr, 0, 0};
+  Enc r{(hipStream_t)stream, enc, Stack{(char*)workspace, workspace_bytes, 0, 0, false}, B, nullptr, 0, 0, flags};
   return r.run(pixels, moments, H, W);
+}
+
+extern "C" size_t st355_vae_encode_workspace(const st355_vae_encoder* enc, int B, int H, int W) { return st355_vae_encode_workspace_flags(enc, B, H, W, 0); }
+
+extern "C" int st355_vae_encode(void* stream, const st355_vae_encoder* enc, const void* pixels, void* moments, int B, int H, int W, void* workspace,
+                                size_t workspace_bytes) {
+  return st355_vae_encode_flags(stream, enc, pixels, moments, B, H, W, workspace, workspace_bytes, 0);
 }

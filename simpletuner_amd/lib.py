@@ -49,12 +49,12 @@ SYMBOLS = [
     "st355_workspace_bytes",
     "st355_comm_unique_id", "st355_comm_init", "st355_comm_destroy", "st355_comm_all_reduce", "st355_comm_reduce_scatter", "st355_comm_all_gather",
     # UNet path (SDXL / SD1.5)
-    "st355_conv_grid_rows", "st355_conv_bf16", "st355_conv_wgrad_bf16", "st355_conv_plan", "st355_grid_from_nchw", "st355_grid_to_nchw", "st355_im2col3x3", "st355_col2im3x3", "st355_softmax_rows", "st355_vae_encode_workspace", "st355_vae_encode", "st355_block_flux_single_fwd", "st355_block_flux_single_bwd", "st355_block_flux_double_fwd", "st355_block_flux_double_bwd", "st355_block_pixart_fwd", "st355_block_pixart_bwd", "st355_block_sd3_joint_fwd", "st355_block_sd3_joint_bwd",
+    "st355_conv_grid_rows", "st355_conv_bf16", "st355_conv_wgrad_bf16", "st355_conv_plan", "st355_grid_from_nchw", "st355_grid_to_nchw", "st355_im2col3x3", "st355_col2im3x3", "st355_softmax_rows", "st355_vae_encode_workspace", "st355_vae_encode", "st355_vae_encode_workspace_flags", "st355_vae_encode_flags", "st355_block_flux_single_fwd", "st355_block_flux_single_bwd", "st355_block_flux_double_fwd", "st355_block_flux_double_bwd", "st355_block_pixart_fwd", "st355_block_pixart_bwd", "st355_block_sd3_joint_fwd", "st355_block_sd3_joint_bwd",
     "st355_upsample2x", "st355_upsample2x_bwd", "st355_tokens_to_grid", "st355_grid_to_tokens",
     "st355_groupnorm_workspace", "st355_groupnorm_fwd", "st355_groupnorm_bwd", "st355_gn_set_apply", "st355_norm_plan",
     "st355_layernorm_fwd", "st355_layernorm_bwd", "st355_layernorm_param_grads_workspace", "st355_layernorm_param_grads",
     "st355_geglu_fwd", "st355_geglu_bwd", "st355_head_split", "st355_head_merge", "st355_head_split_pad", "st355_head_merge_pad", "st355_softmax_rows_bwd", "st355_attn_cross_fwd", "st355_attn_cross_bwd", "st355_attn_fwd_res", "st355_attn_bwd_res",
-    "st355_attn_wide_fwd", "st355_attn_wide_bwd_workspace", "st355_attn_wide_bwd",
+    "st355_attn_wide_fwd", "st355_attn_wide_bwd_workspace", "st355_attn_wide_bwd", "st355_attn_d512_fwd",
 ]
 
 KERNEL_CLASSES = [
@@ -469,6 +469,8 @@ def _declare(lib):
         "st355_softmax_rows": (C.c_int, [vp, vp, i64, i64, i32, f32]),
         "st355_vae_encode_workspace": (sz, [C.POINTER(VaeEncoder), i32, i32, i32]),
         "st355_vae_encode": (C.c_int, [vp, C.POINTER(VaeEncoder), vp, vp, i32, i32, i32, vp, sz]),
+        "st355_vae_encode_workspace_flags": (sz, [C.POINTER(VaeEncoder), i32, i32, i32, C.c_uint32]),
+        "st355_vae_encode_flags": (C.c_int, [vp, C.POINTER(VaeEncoder), vp, vp, i32, i32, i32, vp, sz, C.c_uint32]),
         "st355_block_flux_single_fwd": (C.c_int, [vp, C.POINTER(FluxSingleFwdArgs)]),
         "st355_block_flux_single_bwd": (C.c_int, [vp, C.POINTER(FluxSingleBwdArgs)]),
         "st355_block_flux_double_fwd": (C.c_int, [vp, C.POINTER(FluxDoubleFwdArgs)]),
@@ -505,6 +507,7 @@ def _declare(lib):
                                           i32, i32, i32, i32, i32, i32, i32, f32, vp]),
         "st355_attn_wide_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, f32]),
         "st355_attn_wide_bwd_workspace": (sz, [i32, i32, i32, i32]),
+        "st355_attn_d512_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, f32]),
         "st355_attn_wide_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, f32]),
     }
     for name, (res, args) in sig.items():

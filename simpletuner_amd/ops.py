@@ -1699,6 +1699,9 @@ def attn_ds_bytes(ds) -> int:
 ATTN_TR = os.environ.get("ST355_ATTN_TR", "1") != "0"
 # ST355_ATTN_WIDE=1: the UNet sends 160-wide heads (SD 1.x) to the fused token-major kernels below; default: the unfused per-(image, head) path
 ATTN_WIDE = os.environ.get("ST355_ATTN_WIDE", "0") == "1"
+# ST355_VAE_ATTN=1: a 512-wide AutoencoderKL mid block (encoder entry point and decoder sequencing alike) runs its attention as one attn_d512_fwd launch;
+# default: the per-image GEMM - softmax - transpose - GEMM sequence
+VAE_ATTN_FUSED = os.environ.get("ST355_VAE_ATTN", "0") == "1"
 
 
 def _wide_block(t, name: str, rows: int, cols: int) -> int:
@@ -1719,6 +1722,19 @@ def attn_wide_fwd(q, k, v, o, lse2, B, H, Sq, Sk, d, scale: float):
         raise _l.St355Error(f"attn_wide_fwd: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
     _l.check(L.st355_attn_wide_fwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(lse2), B, H, Sq, Sk, d, scale),
              "attn_wide_fwd")
+
+
+def attn_d512_fwd(q, k, v, o, lse2, B, H, Sq, Sk, d, scale: float):
+    """Fused forward attention for 512-wide heads (csrc/attention_d512.hip; the VAE mid block) on token-major column blocks, attn_wide_fwd's layout: q / o
+    [B*Sq, H*d], k / v [B*Sk, H*d] views of [B*S, ld] buffers with unit inner stride, head h at columns h*d.  lse2: None, or fp32 [B, H, Sq] contiguous
+    (log2 units) to be written; o has the same bits either way."""
+    L = _l.load()
+    lds = [_wide_block(t, n, B * S_, H * d) for t, n, S_ in ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq))]
+    if lse2 is not None:
+        _chk(lse2, F32, "lse2")
+        if tuple(lse2.shape) != (B, H, Sq) or not lse2.is_contiguous():
+            raise _l.St355Error(f"attn_d512_fwd: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
+    _l.check(L.st355_attn_d512_fwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(lse2), B, H, Sq, Sk, d, scale), "attn_d512_fwd")
 
 
 def attn_wide_bwd_workspace(dev, B, H, Sq, d):
@@ -2958,12 +2974,13 @@ def vae_encode(table: VaeEncoderTable, x):
     B, _, H, W = x.shape
     st = table.struct
     f = 1 << (st.n_levels - 1)
-    need = L.st355_vae_encode_workspace(C.byref(st), B, H, W)
+    flags = 1 if VAE_ATTN_FUSED else 0          # ST355_VAE_FUSED_ATTN
+    need = L.st355_vae_encode_workspace_flags(C.byref(st), B, H, W, flags)
     if need == 0:
         raise _l.St355Error("vae_encode: " + L.st355_last_error().decode("utf-8", "replace"))
     ws = _scratch("vae_encode", x.device, need)
     out = torch.empty(B, 2 * st.latent_channels, H // f, W // f, dtype=BF16, device=x.device)
-    _l.check(L.st355_vae_encode(_stream(), C.byref(st), _ptr(x), _ptr(out), B, H, W, _ptr(ws), ws.numel()), "vae_encode")
+    _l.check(L.st355_vae_encode_flags(_stream(), C.byref(st), _ptr(x), _ptr(out), B, H, W, _ptr(ws), ws.numel(), flags), "vae_encode")
     return out
 
 

@@ -6,7 +6,8 @@ Mirrors what the reference drives (caching/vae.py:1238-1396 -> models/common.py:
 (`encoder.conv_in.weight` ..., conv weights [O,I,kh,kw]); the native storage is [O, 9*I] per conv.  Everything is a libst355 launch:
 grid-buffer convolutions-as-GEMM (no im2col except conv_in's 3 -> 8 channels and the three stride-2 (0,1,0,1)-padded downsample convs),
 GroupNorm+SiLU kernels, and the single-head dim-512 mid-block attention as two plain GEMMs around a row-softmax kernel (the score matrix
-[HW, HW] bf16 is materialised per image: 512 MiB at 1024^2 — nothing on a 288 GB part).  quant_conv (1x1 on 2L channels) is folded into
+[HW, HW] bf16 is materialised per image: 512 MiB at 1024^2) — or, under ST355_VAE_ATTN=1 at mid width 512, as ONE fused launch on the qkv
+GEMM's column blocks (csrc/attention_d512.hip: scores stay in fp32 registers, nothing proportional to HW^2 is stored).  quant_conv (1x1 on 2L channels) is folded into
 conv_out at load time (both are linear).  Inference only (the VAE is frozen during training).
 
 Decoder (`decode`, `decode_scaled`): diffusers' Decoder as the validation pipelines call it (`vae.decode(z / scaling_factor + shift_factor).sample`,
@@ -239,7 +240,9 @@ class AutoencoderKL(nn.Module):
         qkv = ops.gemm(n, W[a + "qkv.weight"], bias=W[a + "qkv.bias"])                     # [B*S, 3C]
         o = torch.empty(B * S, C_, dtype=BF16, device=x.device)
         Sp = (S + 63) // 64 * 64
-        for b in range(B):                                                                  # one head of dim C: scores are a plain [S, S] GEMM per image
+        if ops.VAE_ATTN_FUSED and C_ == 512:             # ST355_VAE_ATTN=1: one launch on the qkv buffer's column blocks, no [S, S] scores
+            ops.attn_d512_fwd(qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], o, None, B, 1, S, S, C_, 1.0 / math.sqrt(C_))
+        for b in range(0 if ops.VAE_ATTN_FUSED and C_ == 512 else B):                                                               # one head of dim C: scores are a plain [S, S] GEMM per image
             q, k, v = (qkv[b * S:(b + 1) * S, i * C_:(i + 1) * C_] for i in range(3))
             scores = ops.gemm(q, k)                                                         # q k^T  [S, S] bf16
             ops.softmax_rows_(scores, 1.0 / math.sqrt(C_))
