@@ -1235,6 +1235,20 @@ int st355_attn_wide_bwd(void* stream, const void* q, int64_t ld_q, const void* k
 int st355_attn_d512_fwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, void* o, int64_t ld_o, float* lse2,
                         int B, int H, int Sq, int Sk, int d, float scale);
 
+/* ---- fused attention for 40- and 80-channel heads (csrc/attention_narrow.hip; SD 1.x's 8 heads over 320 / 640 channels), self and cross, under the layout contract
+ * of st355_attn_wide_fwd: every bf16 tensor pointer is the first column of a token-major column block of a [B*S, ld] buffer, head h at columns h*d; no head-split,
+ * zero-padded, transposed or head-major copy on either side.  lse2 fp32 [B, H, Sq], log2 convention.  Sq, Sk >= 1 (ragged tails are masked in the kernels).
+ * o_res (NULL, or a block like o): the forward writes bf16(O_fp32 - bf16(O)) there.  The backward is two kernels without atomics (bit-identical launches): dq forms
+ * delta_i = sum_c dO_ic (o_ic + o_res_ic) in fp32 (o_res NULL: from the bf16 o alone), writes it to `workspace` (st355_attn_narrow_bwd_workspace bytes: fp32
+ * [B, H, Sq]) and dk / dv read it from there.  Every element of the q / k / v column blocks of dq / dk / dv is written.
+ * Preconditions: d in {40, 80} (otherwise ST355_ENOSYS), ld_* % 8 == 0, ld_* >= H*d, 16-byte aligned block starts. */
+int st355_attn_narrow_fwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, void* o, int64_t ld_o, void* o_res,
+                          int64_t ld_ores, float* lse2, int B, int H, int Sq, int Sk, int d, float scale);
+size_t st355_attn_narrow_bwd_workspace(int B, int H, int Sq, int d);
+int st355_attn_narrow_bwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* o, int64_t ld_o,
+                          const void* o_res, int64_t ld_ores, const void* dO, int64_t ld_do, const float* lse2, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk,
+                          void* dv, int64_t ld_dv, void* workspace, int B, int H, int Sq, int Sk, int d, float scale);
+
 /* ---- workspace sizing: one query for every op that takes caller-provided scratch (the library never allocates).  dims per op:
  *   ATTN_BWD {B, H, Sq, Sqp, d}   COLSUM {rows, N, rows_per_batch}   SKINNY_TN {M, P, R}   GROUPNORM {B, H, W, C}   LAYERNORM_PARAM_GRADS {D}
  *   GEMM_SPLITK {M, N, K} (upper bound: 16 fp32 slabs)   GEMM_TN {P, Q, contraction, taps}.   Returns bytes, or -1 for an unknown op / too few dims. */

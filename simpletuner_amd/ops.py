@@ -1755,6 +1755,44 @@ def attn_wide_bwd(q, k, v, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: float):
                                    _ptr(dv), lds[6], _ptr(ws), B, H, Sq, Sk, d, scale), "attn_wide_bwd")
 
 
+# ST355_ATTN_NARROW=1: the UNet sends 40- and 80-wide heads (SD 1.x) to the fused token-major kernels below; default: the zero-padded head-major route
+ATTN_NARROW = os.environ.get("ST355_ATTN_NARROW", "0") == "1"
+
+
+def _narrow_args(fn, B, H, d, lse2, blocks):
+    """leading dimensions of the column blocks ((tensor, name, S) each; a None tensor gives 0) and the lse2 check shared by the two narrow wrappers"""
+    lds = [0 if t is None else _wide_block(t, n, B * S_, H * d) for t, n, S_ in blocks]
+    _chk(lse2, F32, "lse2")
+    Sq = blocks[0][2]
+    if tuple(lse2.shape) != (B, H, Sq) or not lse2.is_contiguous():
+        raise _l.St355Error(f"{fn}: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
+    return lds
+
+
+def attn_narrow_fwd(q, k, v, o, lse2, B, H, Sq, Sk, d, scale: float, o_res=None):
+    """Fused attention for 40- / 80-wide heads on token-major column blocks (csrc/attention_narrow.hip), attn_wide_fwd's layout: q / o / o_res [B*Sq, H*d],
+    k / v [B*Sk, H*d] views of [B*S, ld] buffers with unit inner stride, head h at columns h*d; lse2 fp32 [B, H, Sq] contiguous (log2 units).  Writes o, lse2
+    and, when given, o_res = bf16(O_fp32 - bf16(O))."""
+    lds = _narrow_args("attn_narrow_fwd", B, H, d, lse2, ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq), (o_res, "o_res", Sq)))
+    _l.check(_l.load().st355_attn_narrow_fwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(o_res), lds[4], _ptr(lse2),
+                                             B, H, Sq, Sk, d, scale), "attn_narrow_fwd")
+
+
+def attn_narrow_bwd_workspace(dev, B, H, Sq, d):
+    """the fp32 delta [B, H, Sq] of attn_narrow_bwd: one scratch per device under the rule of _scratch"""
+    return _scratch("attn_narrow_bwd", dev, _l.load().st355_attn_narrow_bwd_workspace(B, H, Sq, d))
+
+
+def attn_narrow_bwd(q, k, v, o, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: float, o_res=None):
+    """Backward of attn_narrow_fwd in the same layout: delta = sum_c dO (o + o_res) (o_res None: the bf16 o alone); dq / dk / dv are column blocks like
+    q / k / v (every element is written); two kernels, no atomics."""
+    lds = _narrow_args("attn_narrow_bwd", B, H, d, lse2, ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq), (o_res, "o_res", Sq), (dO, "dO", Sq),
+                                                         (dq, "dq", Sq), (dk, "dk", Sk), (dv, "dv", Sk)))
+    ws = attn_narrow_bwd_workspace(q.device, B, H, Sq, d)
+    _l.check(_l.load().st355_attn_narrow_bwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(o_res), lds[4], _ptr(dO), lds[5],
+                                             _ptr(lse2), _ptr(dq), lds[6], _ptr(dk), lds[7], _ptr(dv), lds[8], _ptr(ws), B, H, Sq, Sk, d, scale), "attn_narrow_bwd")
+
+
 def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None, ds=None, ds_bytes=None):
     """ds (a uint8 device tensor; ds_bytes: what the call is told it holds, default all of it): the caller's dS^T spill buffer -> st355_attn_bwd_ds"""
     L = _l.load()

@@ -589,10 +589,13 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
     def _attention(self, T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads):
         """softmax(q k^T / sqrt(hd)) v over `heads` heads of width hd = C_/heads; q / k / v are column blocks (offsets qo / ko / vo) of the token-major
         projection outputs.  hd in {64, 128}: the flash kernels on the buffers as they are; other hd <= 128 (SD1.5's 40 -> 64, 80 -> 96; 81..128 -> 128): zero-padded
-        heads; hd > 128 (SD1.5's 160, at <= 256 tokens): unfused GEMM - softmax - GEMM per head — or, under ST355_ATTN_WIDE=1 and hd == 160, the fused
+        heads — or, under ST355_ATTN_NARROW=1 and hd in {40, 80}, the fused token-major kernels of csrc/attention_narrow.hip (_attention_narrow: no copies);
+        hd > 128 (SD1.5's 160, at <= 256 tokens): unfused GEMM - softmax - GEMM per head — or, under ST355_ATTN_WIDE=1 and hd == 160, the fused
         token-major kernels of csrc/attention_wide.hip (_attention_wide: any token count, no copies)."""
         hd = C_ // heads
         hp = 64 if hd <= 64 else 96 if hd <= 80 else 128 if hd <= 128 else 0      # (the head_dim-96 kernels contract over 80 channels: a head wider than 80 pads to 128)
+        if ops.ATTN_NARROW and hd in (40, 80):
+            return self._attention_narrow(T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads)
         if hp == 0:
             if ops.ATTN_WIDE and hd == 160:
                 return self._attention_wide(T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads)
@@ -736,6 +739,30 @@ class UNet2DConditionModel(CheckpointPlanMixin, nn.Module):
                 dq_src = torch.empty_like(qsrc)               # every column block is written by the kernels
                 dkv_src = dq_src if self_attn else torch.empty_like(kvsrc)
                 ops.attn_wide_bwd(q, k, v, dO, lse, dq_src[:, qo:qo + C_], dkv_src[:, ko:ko + C_], dkv_src[:, vo:vo + C_], B, heads, S, Sk, hd, scale)
+                return (dq_src,) if self_attn else (dq_src, dkv_src)
+            T.rec([O], [qsrc] if self_attn else [qsrc, kvsrc], bwd)
+        return O
+
+    def _attention_narrow(self, T, qsrc, kvsrc, qo, ko, vo, C_, B, S, Sk, heads):
+        """40- / 80-wide heads under ST355_ATTN_NARROW=1: one fused forward launch and two backward launches (csrc/attention_narrow.hip) on the projection
+        buffers' column blocks as they are — no head split / merge, no zero-padded V / dO / dV, no slice copies, no host read (a captured step replays it).
+        The residual rule of the padded route stays: self-attention under a recording tape keeps o_res, so that the backward's delta = rowsum(dO (O + o_res))
+        comes from the un-rounded output (see _attention); cross attention takes delta from the bf16 O."""
+        hd = C_ // heads
+        scale = 1.0 / math.sqrt(hd)
+        dev = qsrc.device
+        self_attn = qsrc is kvsrc
+        q, k, v = qsrc[:, qo:qo + C_], kvsrc[:, ko:ko + C_], kvsrc[:, vo:vo + C_]
+        O = torch.empty(B * S, C_, dtype=BF16, device=dev)
+        lse = torch.empty(B, heads, S, dtype=F32, device=dev)
+        Ores = torch.empty_like(O) if (T is not None and self_attn) else None
+        ops.attn_narrow_fwd(q, k, v, O, lse, B, heads, S, Sk, hd, scale, o_res=Ores)
+        if T is not None:
+            def bwd(dO):
+                dq_src = torch.empty_like(qsrc)               # every column block is written by the kernels
+                dkv_src = dq_src if self_attn else torch.empty_like(kvsrc)
+                ops.attn_narrow_bwd(q, k, v, O, dO, lse, dq_src[:, qo:qo + C_], dkv_src[:, ko:ko + C_], dkv_src[:, vo:vo + C_], B, heads, S, Sk, hd, scale,
+                                    o_res=Ores)
                 return (dq_src,) if self_attn else (dq_src, dkv_src)
             T.rec([O], [qsrc] if self_attn else [qsrc, kvsrc], bwd)
         return O
