@@ -535,6 +535,26 @@ int st355_adafactor_step(void* stream, const int64_t* plan_host, const int64_t* 
                          float* row_var, float* col_var, float* variance, float* ws, int64_t ws_floats, float grad_scale, double one_minus_beta2,
                          double rho, double eps1, double eps2, double d, double lr_weight_decay);
 
+/* ---- AdamW with block-wise 8-bit moments (Dettmers et al. 2022; the registry's "ao-adamw8bit") over a bf16 or fp32 arena of many tensors ----
+ * One launch for the whole arena.  table_host / table_dev: the same n_segs records of ST355_ADAMW8BIT_RECORD int64, one per tensor, ascending and
+ * non-overlapping: 0 first arena element, 1 element count, 2 kind, 3 offset into m_codes / v_codes (a multiple of 4), 4 offset into m_scale / v_scale,
+ * 5 offset into m_plain / v_plain (a multiple of 4), 6 first work item, 7 work items = ceil(count / 256), cumulative over the table (n_items in all).
+ * A QUANT segment (count a multiple of 256) keeps one code byte per element and one fp32 scale per 256 consecutive elements for each moment; a PLAIN
+ * segment keeps fp32 moments.  The host copy is checked against n_arena, n_codes, n_scales, n_plain before the launch; elements between segments are
+ * never touched.  books: 1024 fp32 on the device — the signed codebook (m), the unsigned codebook (v), then for each its 255 decision points
+ * (midpoints of neighbours, rounded toward -inf; entry 255 unused), all ascending.
+ *   g' = grad_scale g;  p <- p - lr wd p;  m <- m + (1 - beta1)(g' - m);  v <- v + (1 - beta2)(g'^2 - v);
+ *   p <- p - lr (m / (1 - beta1^step)) / (sqrt(v) / sqrt(1 - beta2^step) + eps), rounded once into the arena dtype (elem_bytes 2 = bf16 nearest even, 4 = fp32);
+ * m, v on entry are codebook[code] * scale; on exit scale = max(max |x| over the block, 1e-12) and code = the index of the codebook value nearest to
+ * x / scale (the lower index at an exact tie).  fp32 arithmetic, no atomics, bit-identical run to run; a bf16 arena needs n_arena % 8 == 0. */
+#define ST355_ADAMW8BIT_RECORD 8
+#define ST355_ADAMW8BIT_PLAIN 0
+#define ST355_ADAMW8BIT_QUANT 1
+int st355_adamw8bit_step(void* stream, void* p, const void* g, int elem_bytes, int64_t n_arena, uint8_t* m_codes, uint8_t* v_codes, int64_t n_codes,
+                         float* m_scale, float* v_scale, int64_t n_scales, float* m_plain, float* v_plain, int64_t n_plain,
+                         const int64_t* table_host, const int64_t* table_dev, int n_segs, int64_t n_items, const float* books,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale);
+
 /* ---- LayerSync (helpers/training/layersync.py): self-alignment of two block outputs, cosine per token row, F.normalize semantics x / max(|x|, 1e-12) ----
  * student, teacher: [B, rows, D] bf16 views with row stride ld and their own batch strides (elements), e.g. the image rows of a joint [B * S, D] buffer; the
  * teacher is a constant (detached).  Per row c = <s^, t^> -> cos_rows[B * rows] fp32; G[B * rows, D] bf16 (compact) = (t^ - c s^) / max(|s|, 1e-12) / (B * rows)

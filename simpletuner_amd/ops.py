@@ -2132,6 +2132,101 @@ def adafactor_step(plan: AdafactorPlan, pflat, gflat, row_var, col_var, variance
                                     float(lr) * float(weight_decay)), "adafactor_step")
 
 
+ADAMW8BIT_BLOCK = 256
+ADAMW8BIT_MIN_NUMEL = 4096
+
+
+def adamw8bit_codebooks():
+    """(signed, unsigned): the two 256-entry dynamic codebooks of block-wise 8-bit Adam (Dettmers et al. 2022) as ascending fp32 tensors, built in fp64 and
+    rounded once.  Signed (m): for i = 0..6 the 2^i midpoints of linspace(0.1, 1, 2^i + 1) times 10^(i-6), both signs, plus 0 and 1.  Unsigned (v): the
+    2^(i+1) midpoints of linspace(0.1, 1, 2^(i+1) + 1) times 10^(i-6), plus 0 and 1."""
+    import numpy as np
+
+    def decades(extra_bit):
+        out = []
+        for i in range(7):
+            edges = np.linspace(0.1, 1.0, 2 ** (i + extra_bit) + 1, dtype=np.float64)
+            out += (((edges[:-1] + edges[1:]) / 2.0) * 10.0 ** (i - 6)).tolist()
+        return out
+
+    pos = decades(0)
+    signed = np.sort(np.array([-x for x in pos] + [0.0] + pos + [1.0], dtype=np.float64))
+    unsigned = np.sort(np.array([0.0] + decades(1) + [1.0], dtype=np.float64))
+    assert signed.size == 256 and unsigned.size == 256
+    return torch.from_numpy(signed.astype(np.float32)), torch.from_numpy(unsigned.astype(np.float32))
+
+
+def adamw8bit_books():
+    """the 1024 fp32 the kernel stages in LDS: signed codebook, unsigned codebook, and for each its 255 decision points — the exact midpoint of the fp32
+    neighbours k and k + 1 rounded toward -inf, so that `x > point` decides "nearer to k + 1" exactly for every fp32 x and a tie takes k (entry 255 is unused)"""
+    import numpy as np
+    out = [cb.numpy() for cb in adamw8bit_codebooks()]
+    for cb in list(out):
+        mid = (cb[:-1].astype(np.float64) + cb[1:].astype(np.float64)) / 2.0          # exact in fp64
+        r = mid.astype(np.float32)
+        r = np.where(r.astype(np.float64) > mid, np.nextafter(r, np.float32(-np.inf)), r)
+        out.append(np.concatenate([r, np.array([np.inf], dtype=np.float32)]))
+    return torch.from_numpy(np.concatenate(out).astype(np.float32))
+
+
+class Adamw8bitPlan:
+    """The segment table of st355_adamw8bit_step for the tensors of one arena (element offsets, element counts), built on the host once.  A tensor is quantised when
+    numel >= 4096 and numel % 256 == 0 (torchao's rule); a block is 256 consecutive elements of ONE tensor.  `kinds[i]`, `code_offsets[i]`, `scale_offsets[i]`,
+    `state_offsets[i]` place tensor i in the flat state buffers of `n_codes` bytes, `n_scales` and `n_plain` floats (plain offsets padded to multiples of 4)."""
+    RECORD, PLAIN, QUANT = 8, 0, 1
+
+    def __init__(self, offsets, numels, device):
+        if not numels or len(offsets) != len(numels):
+            raise _l.St355Error("adamw8bit_plan: expected one offset per tensor")
+        rows, end, codes, scales, plain, items = [], 0, 0, 0, 0, 0
+        for off, n in zip(offsets, numels):
+            off, n = int(off), int(n)
+            if n < 1 or off < end:
+                raise _l.St355Error(f"adamw8bit_plan: tensor at element {off} with {n} elements is empty or overlaps its predecessor")
+            quant = n >= ADAMW8BIT_MIN_NUMEL and n % ADAMW8BIT_BLOCK == 0
+            n_items = -(-n // ADAMW8BIT_BLOCK)
+            rows.append([off, n, self.QUANT if quant else self.PLAIN, codes if quant else 0, scales if quant else 0, 0 if quant else plain, items, n_items])
+            if quant:
+                codes, scales = codes + n, scales + n // ADAMW8BIT_BLOCK
+            else:
+                plain += -(-n // 4) * 4
+            end, items = off + n, items + n_items
+        if items >= 2 ** 31:
+            raise _l.St355Error("adamw8bit_plan: 2^31 or more work items")
+        self.host = torch.tensor(rows, dtype=torch.int64).view(-1)
+        self.n, self.end, self.n_items, self.n_codes, self.n_scales, self.n_plain = len(rows), end, items, codes, scales, plain
+        self.kinds = [r[2] for r in rows]
+        self.code_offsets, self.scale_offsets, self.state_offsets = [r[3] for r in rows], [r[4] for r in rows], [r[5] for r in rows]
+        self.dev = self.host.to(device)
+
+
+def adamw8bit_step(plan: Adamw8bitPlan, pflat, gflat, m_codes, v_codes, m_scale, v_scale, m_plain, v_plain, books, step: int, lr: float, beta1=0.9, beta2=0.999,
+                   eps=1e-8, weight_decay=1e-2, grad_scale: float = 1.0):
+    """one 8-bit block-wise AdamW step over the arena (pflat, gflat: fp32 or bf16 flat, the plan's offsets into them), in place: uint8 codes and fp32 block scales of
+    the quantised tensors, fp32 moments of the others.  `books` = adamw8bit_books() on the device; `step` is the count AFTER this step (1 for the first)"""
+    if pflat.dtype not in (F32, BF16):
+        raise _l.St355Error(f"adamw8bit_step: the arena must be fp32 or bf16, got {pflat.dtype}")
+    _chk(pflat, pflat.dtype, "pflat"); _chk(gflat, pflat.dtype, "gflat")
+    if not pflat.is_contiguous() or not gflat.is_contiguous() or gflat.numel() != pflat.numel() or pflat.numel() < plan.end:
+        raise _l.St355Error(f"adamw8bit_step: pflat and gflat must be contiguous arenas of one length >= {plan.end}")
+    if pflat.dtype == BF16 and pflat.numel() % 8:
+        raise _l.St355Error(f"adamw8bit_step: a bf16 arena must hold a multiple of 8 elements, got {pflat.numel()}")
+    for t, nm, dt, k in ((m_codes, "m_codes", torch.uint8, plan.n_codes), (v_codes, "v_codes", torch.uint8, plan.n_codes), (m_scale, "m_scale", F32, plan.n_scales),
+                         (v_scale, "v_scale", F32, plan.n_scales), (m_plain, "m_plain", F32, plan.n_plain), (v_plain, "v_plain", F32, plan.n_plain),
+                         (books, "books", F32, 1024)):
+        _chk(t, dt, nm)
+        if not t.is_contiguous() or t.numel() < k:
+            raise _l.St355Error(f"adamw8bit_step: {nm} must be a contiguous {dt} buffer of at least {k} elements (the segment table reaches that far), got {t.numel()}")
+    if plan.dev.device != pflat.device:
+        raise _l.St355Error("adamw8bit_step: the plan's table lives on another device than the arena")
+    if step < 1:
+        raise _l.St355Error("adamw8bit_step: step counts from 1")
+    L = _l.load()
+    _l.check(L.st355_adamw8bit_step(_stream(), _ptr(pflat), _ptr(gflat), pflat.element_size(), pflat.numel(), _ptr(m_codes), _ptr(v_codes), min(m_codes.numel(), v_codes.numel()),
+                                    _ptr(m_scale), _ptr(v_scale), min(m_scale.numel(), v_scale.numel()), _ptr(m_plain), _ptr(v_plain), min(m_plain.numel(), v_plain.numel()), _ptr(plan.host), _ptr(plan.dev),
+                                    plan.n, plan.n_items, _ptr(books), lr, beta1, beta2, eps, weight_decay, int(step), grad_scale), "adamw8bit_step")
+
+
 def _token_view(t, name: str):
     """a [B, rows, D] bf16 view with unit inner stride (e.g. the image rows of a joint [B * S, D] buffer): (B, rows, D, row stride, batch stride)"""
     _chk(t, BF16, name)

@@ -60,7 +60,7 @@ def _unpack_saved_state(opt: torch.optim.Optimizer, state_dict: dict):
 
 
 class _ArenaOptimizer(torch.optim.Optimizer):
-    """What the fused arena optimizers (AdamW, AdamWBF16, Lion, Muon, SOAP, Adafactor) share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
+    """What the fused arena optimizers (AdamW, AdamWBF16, Lion, Muon, SOAP, Adafactor, 8-bit AdamW) share: per parameter group, flat state buffers over the group's trainable parameters with the torch-compatible
     per-parameter state installed as views of them (`_flat[gi]`: ok, ps, n, one entry per declared buffer, the subclass's extras); a
     `load_state_dict` that copies a checkpoint INTO those buffers in the dtype each is kept in; and the test for the one-launch path.
     A subclass declares `_buffers`, adds its extras in `_group_extras` / `_load_extras`, and issues its `ops.*` calls in `step`."""
@@ -782,9 +782,128 @@ class St355Adafactor(_ArenaOptimizer):
         return loss
 
 
+# ---- 8-bit block-wise AdamW --------------------------------------------------------------------------------------------------------
+class St355AdamW8bit(_ArenaOptimizer):
+    """AdamW with block-wise 8-bit moments (Dettmers et al. 2022) — the reference's "ao-adamw8bit" entry (optimizer_param.py:205-214, torchao's
+    AdamW8bit) — as ONE st355_adamw8bit_step launch per parameter group, whatever the number of tensors.  Same constructor as torchao's class;
+    `amsgrad=True`, `bf16_stochastic_round=True` and a `block_size` other than 256 are refused.  The rule is the published one; torchao is
+    not executed anywhere in this project, and exchanging optimizer checkpoints with it is unverified.
+
+    A tensor with numel >= 4096 and numel % 256 == 0 keeps `exp_avg_codes` / `exp_avg_sq_codes` (uint8, like p) and `exp_avg_scale` /
+    `exp_avg_sq_scale` (fp32, one per 256 consecutive elements); every other tensor keeps fp32 `exp_avg` / `exp_avg_sq`.  All are views of six flat
+    buffers (2.03 B per quantised parameter); `step` is a float scalar tensor.  Parameters must be fp32 or bf16 views of one contiguous arena; there is
+    no per-tensor path.  The step count and the learning rate cross the ABI as host scalars, as St355AdamW's do."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, amsgrad: bool = False, *,
+                 block_size: int = 256, bf16_stochastic_round: bool = False):
+        if amsgrad:
+            raise NotImplementedError("ao-adamw8bit: amsgrad=True is not built on the st355 path")
+        if bf16_stochastic_round:
+            raise NotImplementedError("ao-adamw8bit: bf16_stochastic_round=True is not built on the st355 path (a bf16 parameter is rounded to nearest even)")
+        if block_size != ops.ADAMW8BIT_BLOCK:
+            raise NotImplementedError(f"ao-adamw8bit: block_size={block_size} is not built on the st355 path (one wave quantises a block of {ops.ADAMW8BIT_BLOCK})")
+        if isinstance(lr, torch.Tensor):
+            raise NotImplementedError("ao-adamw8bit: a tensor lr is not built on the st355 path (the learning rate crosses the ABI as a host scalar)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False))
+        self.abi_calls = 0              # st355 calls issued by step(): one per parameter group, whatever the number of tensors
+
+    def _group_params(self, group):
+        return list(group["params"])
+
+    def _check_param(self, p):
+        if p.dtype not in (F32, torch.bfloat16):
+            raise NotImplementedError(f"ao-adamw8bit: parameters must be fp32 or bf16 on the st355 path, got {p.dtype}")
+        if p.numel() == 0:
+            raise NotImplementedError("ao-adamw8bit: an empty parameter is not built on the st355 path")
+
+    def _group_extras(self, gi, group, st):
+        ps = st["ps"]
+        if not st["ok"]:
+            raise NotImplementedError("ao-adamw8bit: the parameters of a group must be one contiguous run of one dtype (an st355 arena)")
+        base, esz, dev = ps[0].data_ptr(), ps[0].element_size(), ps[0].device
+        plan = st["plan"] = ops.Adamw8bitPlan([(p.data_ptr() - base) // esz for p in ps], [p.numel() for p in ps], dev)
+        st["m_codes"] = torch.full((plan.n_codes,), 127, dtype=torch.uint8, device=dev)     # signed code 127 is the value 0
+        st["v_codes"] = torch.zeros(plan.n_codes, dtype=torch.uint8, device=dev)             # unsigned code 0 is the value 0
+        st["m_scale"], st["v_scale"] = (torch.zeros(plan.n_scales, dtype=F32, device=dev) for _ in range(2))
+        st["m_plain"], st["v_plain"] = (torch.zeros(plan.n_plain, dtype=F32, device=dev) for _ in range(2))
+        st["books"] = ops.adamw8bit_books().to(dev)
+        st["step"] = 0
+        st["step_t"] = torch.tensor(0.0)    # ONE tensor shared by the group's parameters, so a step is one host increment (state_dict() hands out copies)
+        for p, kind, co, so, po in zip(ps, plan.kinds, plan.code_offsets, plan.scale_offsets, plan.state_offsets):
+            n = p.numel()
+            s = self.state[p]
+            s["step"] = st["step_t"]
+            if kind == plan.QUANT:
+                nb = n // ops.ADAMW8BIT_BLOCK
+                s["exp_avg_codes"], s["exp_avg_sq_codes"] = st["m_codes"][co:co + n].view_as(p), st["v_codes"][co:co + n].view_as(p)
+                s["exp_avg_scale"], s["exp_avg_sq_scale"] = st["m_scale"][so:so + nb], st["v_scale"][so:so + nb]
+            else:
+                s["exp_avg"], s["exp_avg_sq"] = st["m_plain"][po:po + n].view_as(p), st["v_plain"][po:po + n].view_as(p)
+
+    _state_keys = ("exp_avg_codes", "exp_avg_sq_codes", "exp_avg_scale", "exp_avg_sq_scale", "exp_avg", "exp_avg_sq")
+
+    def _load_extras(self, st, mine, old):
+        """one parameter's codes and scales, or its fp32 moments, each in the dtype it is kept in (the codes never pass through a floating type)"""
+        for key in self._state_keys:
+            if (key in mine) != (old.get(key) is not None):
+                raise NotImplementedError(f"ao-adamw8bit: the saved state has {'a' if key not in mine else 'no'} '{key}' for a parameter whose moments are "
+                                          f"{'quantised' if 'exp_avg_codes' in mine else 'kept in fp32'} here")
+            if key in mine:
+                if old[key].dtype != mine[key].dtype or old[key].numel() != mine[key].numel():
+                    raise ValueError(f"ao-adamw8bit: saved '{key}' is {old[key].dtype} x {old[key].numel()}, expected {mine[key].dtype} x {mine[key].numel()}")
+                mine[key].copy_(old[key].to(mine[key].device).view_as(mine[key]))
+        k = int(float(old["step"]))
+        if st.get("_loaded") and st["step"] != k:
+            raise NotImplementedError("ao-adamw8bit: the parameters of a group must share one step count (one fused call)")
+        st.update(step=k, _loaded=True)
+        st["step_t"].fill_(float(k))
+
+    def state_dict(self):
+        """every parameter gets its own copy of the shared `step` tensor"""
+        base = super().state_dict()
+        base["state"] = {k: {**v, "step": v["step"].clone()} if "step" in v else v for k, v in base["state"].items()}
+        return base
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            if all(p.grad is None for p in group["params"]):
+                continue
+            st = self._group_flat(gi, group)
+            fused = self._fused_views(st, st["ps"])
+            if fused is None or fused[1].dtype != fused[0].dtype:
+                raise RuntimeError("St355AdamW8bit expects the gradients of every parameter of a group as one flat arena of the parameters' dtype (fused step)")
+            pflat, gflat, _ = fused
+            b1, b2 = group["betas"]
+            st["step"] += 1
+            ops.adamw8bit_step(st["plan"], pflat, gflat, st["m_codes"], st["v_codes"], st["m_scale"], st["v_scale"], st["m_plain"], st["v_plain"], st["books"],
+                               st["step"], group["lr"], b1, b2, group["eps"], group["weight_decay"], grad_scale=self.grad_scale)
+            self.abi_calls += 1
+            st["step_t"] += 1
+        return loss
+
+
 # what the reference's registry `optimizer_choices` holds for these names (optimizer_param.py:76-96 "st355-adamw"-style entry, the reference's own
-# "adamw_bf16", "muon" :432-447, "optimi-lion" :327-338, "soap" :415-431 and "torch-adafactor" :154-163), with the fused classes substituted
+# "adamw_bf16", "muon" :432-447, "optimi-lion" :327-338, "soap" :415-431, "torch-adafactor" :154-163 and "ao-adamw8bit" :205-214), with the fused classes substituted
 OPTIMIZER_CHOICE = {
+    "ao-adamw8bit": {
+        "gradient_precision": "bf16",
+        "precision": "any",
+        "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-6},
+        "class": St355AdamW8bit,
+    },
     "st355-adamw": {
         "precision": "any",
         "default_settings": {"betas": (0.9, 0.999), "weight_decay": 1e-2, "eps": 1e-8},

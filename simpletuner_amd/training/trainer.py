@@ -24,7 +24,7 @@ from .. import ops
 from .ema import EMAModel
 from .grad_sync import GradSync, sync_module_states
 from .multi_process import gather_sample_weighted_scalar
-from .optimizer import OPTIMIZER_CHOICE, St355Adafactor, St355AdamW, St355AdamWBF16, St355Lion, St355Muon, St355Soap, flat_view, optimizer_settings
+from .optimizer import OPTIMIZER_CHOICE, St355Adafactor, St355AdamW, St355AdamW8bit, St355AdamWBF16, St355Lion, St355Muon, St355Soap, flat_view, optimizer_settings
 
 
 class St355Accelerator:
@@ -108,8 +108,8 @@ class Trainer:
                        else [p for p in comp.parameters() if p.requires_grad])
         # optimizer_param.py:76-96 registry semantics: name -> class (+ default settings)
         opt_name = getattr(config, "optimizer", "st355-adamw")
-        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap", "torch-adafactor"):   # never a silently different optimizer
-            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, muon, optimi-lion, soap, torch-adafactor, st355-adamw = torch-adamw semantics)")
+        if opt_name not in ("adamw_bf16", "st355-adamw", "torch-adamw", "muon", "optimi-lion", "soap", "torch-adafactor", "ao-adamw8bit"):   # never a silently different optimizer
+            raise NotImplementedError(f"optimizer '{opt_name}' is not built on the st355 path (adamw_bf16, ao-adamw8bit, muon, optimi-lion, soap, torch-adafactor, st355-adamw = torch-adamw semantics)")
         if opt_name in ("muon", "soap") and getattr(config, "internal_guidance_enabled", False):
             raise NotImplementedError(f"optimizer '{opt_name}' with internal_guidance_enabled: the trainable arena then holds the head's 1-D tensors, which the "
                                       "matrix optimizers do not take (built: st355-adamw = torch-adamw, adamw_bf16, optimi-lion)")
@@ -156,6 +156,13 @@ class Trainer:
                 raise NotImplementedError("optimizer 'torch-adafactor' is not built for the SDXL / SD 1.5 UNet full fine-tune: the reference factors its "
                                           "[Cout, Cin, 3, 3] convolutions as 3 x 3 matrices, which only the untuned small-matrix path would serve")
             self.optimizer = St355Adafactor(self.params, lr=config.learning_rate, **optimizer_settings("torch-adafactor", config))
+        elif opt_name == "ao-adamw8bit":
+            # every LoRA arena (fp32) and the transformer full arenas (bf16): one launch per step; tensors below 4096 elements or not whole blocks of 256 keep fp32
+            # moments.  No fused EMA: EMAModel.step runs after the step.  The optimizer step runs outside the captured graph, so hip_graph works as under st355-adamw
+            if getattr(comp, "full", False) and type(comp).__name__.startswith("UNet"):
+                raise NotImplementedError("optimizer 'ao-adamw8bit' is not built for the SDXL / SD 1.5 UNet full fine-tune (built: every LoRA arena and the "
+                                          "SD3 / Flux / PixArt-ControlNet full arenas)")
+            self.optimizer = St355AdamW8bit(self.params, lr=config.learning_rate, **optimizer_settings("ao-adamw8bit", config))
         elif opt_name == "optimi-lion":
             # fp32 adapter arena or bf16 full-fine-tune arena (Kahan-compensated there), one launch either way; no override_lr_scheduler in the registry entry
             self.optimizer = St355Lion(self.params, lr=config.learning_rate, **optimizer_settings("optimi-lion", config))
