@@ -1269,6 +1269,22 @@ int st355_attn_narrow_bwd(void* stream, const void* q, int64_t ld_q, const void*
                           const void* o_res, int64_t ld_ores, const void* dO, int64_t ld_do, const float* lse2, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk,
                           void* dv, int64_t ld_dv, void* workspace, int B, int H, int Sq, int Sk, int d, float scale);
 
+/* ---- fused attention for 72-channel heads (csrc/attention_d72.hip; PixArt-Sigma's 16 heads over 1152 channels), self and cross, under the layout contract of
+ * st355_attn_narrow_* with a HEAD PITCH, a KEY BIAS and zeroed pad lanes.  Every bf16 tensor pointer is the first column of a token-major column block of a
+ * [B*S, ld] buffer; head h sits at columns h*pitch .. h*pitch + 71 (pitch = 96: PixArt's head-padded qkv / q2 / kv / O buffers used in place; pitch = 72: an
+ * unpadded layout).  Columns 72 .. pitch-1 of a head are never read as data; o, dq, dk and dv get exact ZEROS there, so every element of every head's pitch-wide
+ * block of the outputs is written.  key_bias: NULL, or fp32 [B, Sk], finite, added to scale q.k in natural-log units (as in st355_attn_fwd); it enters o, lse2
+ * (fp32 [B, H, Sq], log2 convention, bias included) and both backward kernels.  Sq, Sk >= 1 (ragged tails are masked in the kernels).  The backward is two kernels
+ * without atomics (bit-identical launches): dq forms delta_i = sum_c dO_ic o_ic in fp32 from the bf16 o, writes it to `workspace`
+ * (st355_attn_d72_bwd_workspace bytes: fp32 [B, H, Sq]) and dk / dv read it from there.
+ * Preconditions: d == 72 (otherwise ST355_ENOSYS), pitch >= 72, pitch % 8 == 0, ld_* % 8 == 0, ld_* >= H*pitch, 16-byte aligned block starts. */
+int st355_attn_d72_fwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const float* key_bias, void* o,
+                       int64_t ld_o, float* lse2, int B, int H, int Sq, int Sk, int d, int pitch, float scale);
+size_t st355_attn_d72_bwd_workspace(int B, int H, int Sq, int d);
+int st355_attn_d72_bwd(void* stream, const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* o, int64_t ld_o,
+                       const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk, void* dv,
+                       int64_t ld_dv, void* workspace, int B, int H, int Sq, int Sk, int d, int pitch, float scale);
+
 /* ---- workspace sizing: one query for every op that takes caller-provided scratch (the library never allocates).  dims per op:
  *   ATTN_BWD {B, H, Sq, Sqp, d}   COLSUM {rows, N, rows_per_batch}   SKINNY_TN {M, P, R}   GROUPNORM {B, H, W, C}   LAYERNORM_PARAM_GRADS {D}
  *   GEMM_SPLITK {M, N, K} (upper bound: 16 fp32 slabs)   GEMM_TN {P, Q, contraction, taps}.   Returns bytes, or -1 for an unknown op / too few dims. */

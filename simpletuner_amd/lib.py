@@ -57,6 +57,7 @@ SYMBOLS = [
     "st355_geglu_fwd", "st355_geglu_bwd", "st355_head_split", "st355_head_merge", "st355_head_split_pad", "st355_head_merge_pad", "st355_softmax_rows_bwd", "st355_attn_cross_fwd", "st355_attn_cross_bwd", "st355_attn_fwd_res", "st355_attn_bwd_res",
     "st355_attn_wide_fwd", "st355_attn_wide_bwd_workspace", "st355_attn_wide_bwd", "st355_attn_d512_fwd",
     "st355_attn_narrow_fwd", "st355_attn_narrow_bwd_workspace", "st355_attn_narrow_bwd",
+    "st355_attn_d72_fwd", "st355_attn_d72_bwd_workspace", "st355_attn_d72_bwd",
 ]
 
 KERNEL_CLASSES = [
@@ -516,6 +517,10 @@ def _declare(lib):
         "st355_attn_narrow_bwd_workspace": (sz, [i32, i32, i32, i32]),
         "st355_attn_narrow_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp,
                                             i32, i32, i32, i32, i32, f32]),
+        "st355_attn_d72_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32, f32]),
+        "st355_attn_d72_bwd_workspace": (sz, [i32, i32, i32, i32]),
+        "st355_attn_d72_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp,
+                                         i32, i32, i32, i32, i32, i32, f32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -1793,6 +1793,51 @@ def attn_narrow_bwd(q, k, v, o, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: fl
                                              _ptr(lse2), _ptr(dq), lds[6], _ptr(dk), lds[7], _ptr(dv), lds[8], _ptr(ws), B, H, Sq, Sk, d, scale), "attn_narrow_bwd")
 
 
+# ST355_ATTN_D72=1: PixArt blocks with 72-wide heads run their attention on the fused token-major kernels below, in place on the head-padded projection
+# buffers (no head split / merge, no transposed V); default: the zero-padded head-major d-96 route
+ATTN_D72 = os.environ.get("ST355_ATTN_D72", "0") == "1"
+
+
+def _d72_args(fn, B, H, d, pitch, lse2, key_bias, Sk, blocks):
+    """the head pitch (None: d), the leading dimensions of the column blocks ((tensor, name, S) each, [B*S, H*pitch]) and the lse2 / key_bias checks"""
+    pitch = d if pitch is None else int(pitch)
+    lds = [_wide_block(t, n, B * S_, H * pitch) for t, n, S_ in blocks]
+    _chk(lse2, F32, "lse2")
+    Sq = blocks[0][2]
+    if tuple(lse2.shape) != (B, H, Sq) or not lse2.is_contiguous():
+        raise _l.St355Error(f"{fn}: lse2: expected a contiguous [{B}, {H}, {Sq}] tensor, got {tuple(lse2.shape)}")
+    if key_bias is not None:
+        _chk(key_bias, F32, "key_bias")
+        if tuple(key_bias.shape) != (B, Sk) or not key_bias.is_contiguous():
+            raise _l.St355Error(f"{fn}: key_bias: expected a contiguous [{B}, {Sk}] tensor, got {tuple(key_bias.shape)}")
+    return pitch, lds
+
+
+def attn_d72_fwd(q, k, v, o, lse2, B, H, Sq, Sk, d, scale: float, pitch=None, key_bias=None):
+    """Fused attention for 72-wide heads on token-major column blocks (csrc/attention_d72.hip): q / o [B*Sq, H*pitch], k / v [B*Sk, H*pitch] views of [B*S, ld]
+    buffers with unit inner stride, head h at columns h*pitch .. h*pitch + 71 (pitch None: 72); key_bias None or fp32 [B, Sk] (natural-log units); lse2 fp32
+    [B, H, Sq] contiguous (log2 units).  Writes o (zeros on the pad lanes 72 .. pitch-1 of every head) and lse2."""
+    pitch, lds = _d72_args("attn_d72_fwd", B, H, d, pitch, lse2, key_bias, Sk, ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq)))
+    _l.check(_l.load().st355_attn_d72_fwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(key_bias), _ptr(o), lds[3], _ptr(lse2),
+                                          B, H, Sq, Sk, d, pitch, scale), "attn_d72_fwd")
+
+
+def attn_d72_bwd_workspace(dev, B, H, Sq, d):
+    """the fp32 delta [B, H, Sq] of attn_d72_bwd: one scratch per device under the rule of _scratch"""
+    return _scratch("attn_d72_bwd", dev, _l.load().st355_attn_d72_bwd_workspace(B, H, Sq, d))
+
+
+def attn_d72_bwd(q, k, v, o, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: float, pitch=None, key_bias=None):
+    """Backward of attn_d72_fwd in the same layout: delta = sum_c dO o from the bf16 o; dq / dk / dv are column blocks like q / k / v, every element of every
+    head's pitch-wide block is written (zeros on the pad lanes); two kernels, no atomics."""
+    pitch, lds = _d72_args("attn_d72_bwd", B, H, d, pitch, lse2, key_bias, Sk, ((q, "q", Sq), (k, "k", Sk), (v, "v", Sk), (o, "o", Sq), (dO, "dO", Sq),
+                                                                               (dq, "dq", Sq), (dk, "dk", Sk), (dv, "dv", Sk)))
+    ws = attn_d72_bwd_workspace(q.device, B, H, Sq, d)
+    _l.check(_l.load().st355_attn_d72_bwd(_stream(), _ptr(q), lds[0], _ptr(k), lds[1], _ptr(v), lds[2], _ptr(o), lds[3], _ptr(dO), lds[4], _ptr(lse2),
+                                          _ptr(key_bias), _ptr(dq), lds[5], _ptr(dk), lds[6], _ptr(dv), lds[7], _ptr(ws), B, H, Sq, Sk, d, pitch, scale),
+             "attn_d72_bwd")
+
+
 def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None, ds=None, ds_bytes=None):
     """ds (a uint8 device tensor; ds_bytes: what the call is told it holds, default all of it): the caller's dS^T spill buffer -> st355_attn_bwd_ds"""
     L = _l.load()

@@ -330,7 +330,10 @@ class PixArtTransformer2DModel(nn.Module):
         if L is not None and rpb != S:
             raise NotImplementedError("PixArt LoRA: per-sample timesteps only")
         kx = (lambda g, T: dict(a2=T, b2=g.B_blk, k2_real=g.k2_real)) if L is not None else (lambda g, T: {})
-        if _BLOCK_ABI and ops.ATTN_TR and h.is_contiguous() and ctx2d.is_contiguous() and rpb == S and L is None:
+        # ST355_ATTN_D72=1: 72-wide heads run both attentions on csrc/attention_d72.hip, in place on the column blocks of qkv / q2 / kv (head pitch HP) — the
+        # per-kernel sequencing below without head split / merge, transposed V or head-major copies; the fp8 block form (above) keeps its route
+        d72 = ops.ATTN_D72 and self.hd == 72
+        if _BLOCK_ABI and ops.ATTN_TR and h.is_contiguous() and ctx2d.is_contiguous() and rpb == S and L is None and not d72:
             # the block as ONE C entry point (st355_block_pixart_fwd): the launches of the host-side sequencing below, in its order, on its
             # operands (every buffer allocated here, kept ones handed to the backward as before) — bit-identical to it (ST355_BLOCK_ABI=0 restores it)
             dev = h.device
@@ -357,12 +360,17 @@ class PixArtTransformer2DModel(nn.Module):
         n1 = ops.ln_modulate_fwd(h, m[1], m[0], rpb)
         T_qkv = ops.gemm(n1, L.qkv.A_cat) if L is not None else None
         qkv = ops.gemm(n1, W.qkv_w, bias=W.qkv_b, **kx(L.qkv if L is not None else None, T_qkv))
-        Q, Qt, Sp = ops.head_split(qkv[:, :Dp], B, H, HP, S, want_xt=not ops.ATTN_TR)
-        K, Kt, _ = ops.head_split(qkv[:, Dp:2 * Dp], B, H, HP, S, want_xt=not ops.ATTN_TR)
-        _, Vt, _ = ops.head_split(qkv[:, 2 * Dp:], B, H, HP, S, want_x=False)
         O = torch.empty(B * S, Dp, dtype=BF16, device=h.device)
         lse = torch.empty(B, H, S, dtype=F32, device=h.device)
-        ops.attn_fwd(Q, K, Vt, O, lse, B, H, S, Sp, HP, scale)
+        Q = Qt = K = Kt = Q2 = Q2t = K2 = K2t = None
+        Sp, Skp = S, Sk
+        if d72:
+            ops.attn_d72_fwd(qkv[:, :Dp], qkv[:, Dp:2 * Dp], qkv[:, 2 * Dp:], O, lse, B, H, S, S, self.hd, scale, pitch=HP)
+        else:
+            Q, Qt, Sp = ops.head_split(qkv[:, :Dp], B, H, HP, S, want_xt=not ops.ATTN_TR)
+            K, Kt, _ = ops.head_split(qkv[:, Dp:2 * Dp], B, H, HP, S, want_xt=not ops.ATTN_TR)
+            _, Vt, _ = ops.head_split(qkv[:, 2 * Dp:], B, H, HP, S, want_x=False)
+            ops.attn_fwd(Q, K, Vt, O, lse, B, H, S, Sp, HP, scale)
         ya = torch.empty(B * S, D, dtype=BF16, device=h.device) if train else None
         T_o1 = ops.gemm(O, L.out1.A_cat) if L is not None else None
         h1 = ops.gemm(O, W.out1_w, bias=W.out1_b, epilogue=EPI_GATE_RESIDUAL, gate=m[2], aux_in=h, rows_per_batch=rpb, aux_out=ya, **kx(L.out1 if L is not None else None, T_o1))
@@ -370,12 +378,15 @@ class PixArtTransformer2DModel(nn.Module):
         q2 = ops.gemm(h1, W.q2_w, bias=W.q2_b, **kx(L.q2 if L is not None else None, T_q2))
         T_kv = ops.gemm(ctx2d, L.kv2.A_cat) if L is not None else None
         kv = ops.gemm(ctx2d, W.kv2_w, bias=W.kv2_b, **kx(L.kv2 if L is not None else None, T_kv))
-        Q2, Q2t, _ = ops.head_split(q2, B, H, HP, S, want_xt=not ops.ATTN_TR)
-        K2, K2t, Skp = ops.head_split(kv[:, :Dp], B, H, HP, Sk, want_xt=not ops.ATTN_TR)
-        _, V2t, _ = ops.head_split(kv[:, Dp:], B, H, HP, Sk, want_x=False)
         O2 = torch.empty(B * S, Dp, dtype=BF16, device=h.device)
         lse2 = torch.empty(B, H, S, dtype=F32, device=h.device)
-        ops.attn_cross_fwd(Q2, K2, V2t, O2, lse2, B, H, S, Sk, Skp, HP, scale, key_bias=kbias)
+        if d72:
+            ops.attn_d72_fwd(q2, kv[:, :Dp], kv[:, Dp:], O2, lse2, B, H, S, Sk, self.hd, scale, pitch=HP, key_bias=kbias)
+        else:
+            Q2, Q2t, _ = ops.head_split(q2, B, H, HP, S, want_xt=not ops.ATTN_TR)
+            K2, K2t, Skp = ops.head_split(kv[:, :Dp], B, H, HP, Sk, want_xt=not ops.ATTN_TR)
+            _, V2t, _ = ops.head_split(kv[:, Dp:], B, H, HP, Sk, want_x=False)
+            ops.attn_cross_fwd(Q2, K2, V2t, O2, lse2, B, H, S, Sk, Skp, HP, scale, key_bias=kbias)
         T_o2 = ops.gemm(O2, L.out2.A_cat) if L is not None else None
         h2 = ops.gemm(O2, W.out2_w, bias=W.out2_b, epilogue=EPI_ADD, aux_in=h1, **kx(L.out2 if L is not None else None, T_o2))
         n2 = ops.ln_modulate_fwd(h2, m[4], m[3], rpb)
@@ -386,7 +397,8 @@ class PixArtTransformer2DModel(nn.Module):
         sv = None
         if save:
             sv = SimpleNamespace(h=h, mod=mod, m=m, n1=n1, qkv=qkv, Q=Q, Qt=Qt, K=K, Kt=Kt, O=O, lse=lse, Sp=Sp, ya=ya, h1=h1, q2=q2, kv=kv, Q2=Q2, Q2t=Q2t, K2=K2,
-                                 K2t=K2t, Skp=Skp, O2=O2, lse2=lse2, h2=h2, n2=n2, pre=pre, a=a, yf=yf, T_qkv=T_qkv, T_o1=T_o1, T_q2=T_q2, T_kv=T_kv, T_o2=T_o2)
+                                 K2t=K2t, Skp=Skp, O2=O2, lse2=lse2, h2=h2, n2=n2, pre=pre, a=a, yf=yf, T_qkv=T_qkv, T_o1=T_o1, T_q2=T_q2, T_kv=T_kv, T_o2=T_o2,
+                                 d72=d72)          # d72: no head-major Q / K copies were made; the backward reads the column blocks of qkv / q2 / kv
         return h3, sv
 
     def _block_fwd_fp8(self, blk: _Block, h, ctx2d, kbias, mod, m, B, S, Sk, save: bool):
@@ -488,7 +500,9 @@ class PixArtTransformer2DModel(nn.Module):
             g.grads(x, T, dy, U, acc, sync)
             return dx
 
-        if _BLOCK_ABI and ops.ATTN_TR and sv.Qt is None and sv.pre is not None and d3.is_contiguous() and getattr(W, "ff2_wT", None) is not None and L is None:
+        d72 = getattr(sv, "d72", False)          # the forward that saved sv ran on csrc/attention_d72.hip (ST355_ATTN_D72=1): so does this backward
+        if _BLOCK_ABI and ops.ATTN_TR and sv.Qt is None and sv.pre is not None and d3.is_contiguous() and getattr(W, "ff2_wT", None) is not None and L is None \
+                and not d72:
             # the data path of the backward as ONE C entry point (st355_block_pixart_bwd); every intermediate gradient stays in the buffers allocated here, and a
             # trainable block takes its weight / bias / modulation gradients from them afterwards — the same launches on the same operands as the host-side
             # sequencing below, the weight-gradient launches after the data path instead of between its steps (independent of it: bit-identical results)
@@ -533,10 +547,14 @@ class PixArtTransformer2DModel(nn.Module):
         dO2 = lora_dgrad(L.out2 if L is not None else None, d2, W.out2_wT, sv.O2, getattr(sv, "T_o2", None))
         dq2 = torch.empty_like(sv.q2)
         dkv = torch.empty_like(sv.kv)
-        dQ, dK = torch.empty_like(sv.Q2), torch.empty_like(sv.K2)
-        ops.attn_cross_bwd(sv.Q2, sv.K2, sv.Q2t, sv.K2t, sv.kv[:, Dp:], sv.O2, dO2, sv.lse2, dQ, dK, dkv[:, Dp:], B, H, S, sv.Sp, Sk, sv.Skp, HP, scale, key_bias=kbias)
-        ops.head_merge(dQ, dq2, B, H, HP, S)
-        ops.head_merge(dK, dkv[:, :Dp], B, H, HP, Sk)
+        if d72:          # dq / dk / dv straight into dq2 and the halves of dkv, pad lanes zeroed by the kernels
+            ops.attn_d72_bwd(sv.q2, sv.kv[:, :Dp], sv.kv[:, Dp:], sv.O2, dO2, sv.lse2, dq2, dkv[:, :Dp], dkv[:, Dp:], B, H, S, Sk, self.hd, scale, pitch=HP,
+                             key_bias=kbias)
+        else:
+            dQ, dK = torch.empty_like(sv.Q2), torch.empty_like(sv.K2)
+            ops.attn_cross_bwd(sv.Q2, sv.K2, sv.Q2t, sv.K2t, sv.kv[:, Dp:], sv.O2, dO2, sv.lse2, dQ, dK, dkv[:, Dp:], B, H, S, sv.Sp, Sk, sv.Skp, HP, scale, key_bias=kbias)
+            ops.head_merge(dQ, dq2, B, H, HP, S)
+            ops.head_merge(dK, dkv[:, :Dp], B, H, HP, Sk)
         wgrad("q2", dq2, sv.h1, unpad_rows(["attn2.to_q"]))
         wgrad("kv2", dkv, ctx2d, unpad_rows(["attn2.to_k", "attn2.to_v"]))
         d1 = lora_dgrad(L.q2 if L is not None else None, dq2, W.q2_wT, sv.h1, getattr(sv, "T_q2", None), epilogue=EPI_ADD, aux_in=d2)
@@ -549,10 +567,14 @@ class PixArtTransformer2DModel(nn.Module):
         wgrad("out1", dya, sv.O, unpad_cols("attn1.to_out.0"))
         dO = lora_dgrad(L.out1 if L is not None else None, dya, W.out1_wT, sv.O, getattr(sv, "T_o1", None))
         dqkv = torch.empty_like(sv.qkv)
-        dQ, dK = torch.empty_like(sv.Q), torch.empty_like(sv.K)
-        ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * Dp:], sv.O, dO, sv.lse, dQ, dK, dqkv[:, 2 * Dp:], B, H, S, sv.Sp, HP, scale)
-        ops.head_merge(dQ, dqkv[:, :Dp], B, H, HP, S)
-        ops.head_merge(dK, dqkv[:, Dp:2 * Dp], B, H, HP, S)
+        if d72:
+            ops.attn_d72_bwd(sv.qkv[:, :Dp], sv.qkv[:, Dp:2 * Dp], sv.qkv[:, 2 * Dp:], sv.O, dO, sv.lse, dqkv[:, :Dp], dqkv[:, Dp:2 * Dp], dqkv[:, 2 * Dp:], B, H, S, S,
+                             self.hd, scale, pitch=HP)
+        else:
+            dQ, dK = torch.empty_like(sv.Q), torch.empty_like(sv.K)
+            ops.attn_bwd(sv.Q, sv.K, sv.Qt, sv.Kt, sv.qkv[:, 2 * Dp:], sv.O, dO, sv.lse, dQ, dK, dqkv[:, 2 * Dp:], B, H, S, sv.Sp, HP, scale)
+            ops.head_merge(dQ, dqkv[:, :Dp], B, H, HP, S)
+            ops.head_merge(dK, dqkv[:, Dp:2 * Dp], B, H, HP, S)
         wgrad("qkv", dqkv, sv.n1, unpad_rows(["attn1.to_q", "attn1.to_k", "attn1.to_v"]))
         dn1 = lora_dgrad(L.qkv if L is not None else None, dqkv, W.qkv_wT, sv.n1, getattr(sv, "T_qkv", None))
         if tr:
