@@ -1285,6 +1285,21 @@ int st355_attn_d72_bwd(void* stream, const void* q, int64_t ld_q, const void* k,
                        const void* dO, int64_t ld_do, const float* lse2, const float* key_bias, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk, void* dv,
                        int64_t ld_dv, void* workspace, int B, int H, int Sq, int Sk, int d, int pitch, float scale);
 
+/* ---- SageAttention-style quantised attention forward (csrc/attention_sage.hip; validation sampling only: no backward, no lse2, no key bias).  Operands as
+ * st355_attn_fwd: Q, K [B, H, S, d] bf16 head-major, Vt [B, H, d, Sp] bf16 with Sp = ceil64(S), O [B*S, ld_o] bf16 token-major (head h at columns h*d); d is 64
+ * or 128 (otherwise ST355_ENOSYS), any S >= 1, scale > 0.  With c = scale * log2(e):
+ *   kbar[b,h,:] = mean_{s<S} K[b,h,s,:] in fp32, fixed order: the 64-row blocks summed in row order, the block sums in block order, one division by S; K' = K - kbar;
+ *   Qh = rne(Q / sq), Kh = rne(K' / sk) as int8, sq / sk = amax / 127 per block of 64 rows (1 for an all-zero block), rows >= S zero;
+ *   Vh = e4m3(V / sv), sv = amax_{s<S}|V| / 448 per (b, h, channel) (1 for an all-zero row), columns >= S zero;          (all divisions are IEEE fp32)
+ *   per 128-key step: s2 = int32(Qh.Kh) * (sq * sk * c), keys >= S masked to -inf, online maximum m, e = exp2(s2 - m + 8), l += sum e (unquantised),
+ *   acc = acc * exp2(m_old - m) + e4m3(e) . Vh on the fp8 MFMA with unit block scales;   O = bf16(acc * sv / l).
+ * st355_attn_sage_quantize fills `workspace` (st355_attn_sage_workspace bytes, 16-byte aligned, caller-owned); every section starts on a 256-byte boundary, in
+ * this order: int8 Qh [B,H,Sp,d], int8 Kh [B,H,Sp,d], e4m3 Vh [B,H,d,Sp], fp32 sq [B,H,Sp/64], fp32 sk [B,H,Sp/64], fp32 sv [B,H,d], then the two stages of the
+ * K mean (fp32 [B,H,d] and [B,H,Sp/64,d]).  st355_attn_sage_fwd reads only the workspace.  No atomics anywhere: launches are bit-identical. */
+size_t st355_attn_sage_workspace(int B, int H, int S, int d);
+int st355_attn_sage_quantize(void* stream, const void* Q, const void* K, const void* Vt, void* workspace, int B, int H, int S, int Sp, int d);
+int st355_attn_sage_fwd(void* stream, const void* workspace, void* O, int64_t ld_o, int B, int H, int S, int Sp, int d, float scale);
+
 /* ---- workspace sizing: one query for every op that takes caller-provided scratch (the library never allocates).  dims per op:
  *   ATTN_BWD {B, H, Sq, Sqp, d}   COLSUM {rows, N, rows_per_batch}   SKINNY_TN {M, P, R}   GROUPNORM {B, H, W, C}   LAYERNORM_PARAM_GRADS {D}
  *   GEMM_SPLITK {M, N, K} (upper bound: 16 fp32 slabs)   GEMM_TN {P, Q, contraction, taps}.   Returns bytes, or -1 for an unknown op / too few dims. */

@@ -1466,3 +1466,83 @@ class FullGrads:
             self.sync.ready(0, self.mw_lo)
         else:
             self.sync.ready(0, hi)
+
+
+# ------------------------------------------------------------------------------------------------
+# attention_mechanism = sageattention (helpers/training/attention_backend.py: AttentionBackendController, AttentionBackendMode, AttentionPhase)
+# ------------------------------------------------------------------------------------------------
+SAGE_MECHANISMS = ("sageattention", "sageattention-int8-fp8-cuda")                      # -> ops.attn_sage_fwd (int8 Q K^T, fp8 P V)
+SAGE_FP16_PV = ("sageattention-int8-fp16-triton", "sageattention-int8-fp16-cuda")       # the fp16-PV kernels of the package: not built here
+SAGE_USAGES = ("training", "inference", "training+inference")                           # AttentionBackendMode
+_sage_log = __import__("logging").getLogger(__name__)
+_sage_said = set()
+
+
+def _sage_once(key, msg, *args):
+    if key not in _sage_said:
+        _sage_said.add(key)
+        _sage_log.warning(msg, *args)
+
+
+def sage_attention_enabled(config) -> bool:
+    """Does the config select the quantised validation attention?  attention_mechanism in SAGE_MECHANISMS with sageattention_usage = inference (the default,
+    AttentionBackendMode.from_raw: None / "" / "None" -> inference).  Refused by name: usage training / training+inference (the reference itself warns that the
+    attention layers do not train under it, and there is no backward here) and the fp16-PV mechanisms.  Every other mechanism, and none, is not this route."""
+    mech = str(getattr(config, "attention_mechanism", None) or "").strip().lower()
+    if mech in SAGE_FP16_PV:
+        raise NotImplementedError(f"attention_mechanism={mech}: the fp16-PV SageAttention variants are not built (built: {', '.join(SAGE_MECHANISMS)})")
+    if mech not in SAGE_MECHANISMS:
+        return False
+    raw = getattr(config, "sageattention_usage", None)
+    usage = "inference" if raw in (None, "", "None") else str(getattr(raw, "value", raw)).strip().lower()
+    if usage not in SAGE_USAGES:
+        raise ValueError(f"Unsupported attention backend mode '{raw}'. Expected one of: {', '.join(SAGE_USAGES)}")
+    if usage != "inference":
+        raise NotImplementedError(f"sageattention_usage={usage}: the quantised attention has no backward; only sageattention_usage=inference (validation sampling) is built")
+    return True
+
+
+class EvalAttentionMixin:
+    """The counterpart of AttentionPhase.EVAL for an engine: inside `eval_attention_phase()` its no-grad forwards sequence their blocks from the host and run
+    every attention on ops.attn_sage_fwd.  Nothing but sampling.sample_images enters the phase: the no-grad forwards of training (evaluation loss, TwinFlow,
+    scheduled sampling, the distillers' teachers) stay on the exact kernels."""
+    _sage_eval = False
+
+    @contextmanager
+    def eval_attention_phase(self):
+        prev, self._sage_eval = self._sage_eval, True
+        try:
+            yield self
+        finally:
+            self._sage_eval = prev
+
+    def _sage_now(self, save: bool) -> bool:
+        return self._sage_eval and not save
+
+    def _attn_fwd(self, save: bool, *a, **kw):
+        """ops.attn_fwd(*a, **kw) as it is, except in the eval attention phase: there the quantised forward, unless the call carries a key bias (attention-masked
+        Flux: the quantised kernel has none, and dropping the mask as the reference's wrapper does would change the result) or a head_dim it is not built for —
+        those keep the exact kernel, with one log line"""
+        if self._sage_now(save):
+            Q, K, Vt, O, _lse2, B, H, S, Sp, hd, scale = a
+            if kw.get("key_bias") is not None:
+                _sage_once("key_bias", "attention_mechanism=sageattention: attention with a key bias (attention mask) stays on the exact bf16 kernel")
+            elif hd not in (64, 128):
+                _sage_once(("hd", hd), "attention_mechanism=sageattention: head_dim %d is not built (64, 128): the exact bf16 kernel stays in use", hd)
+            else:
+                ops.attn_sage_fwd(Q, K, Vt, O, B, H, S, Sp, hd, scale)
+                return
+        ops.attn_fwd(*a, **kw)
+
+
+def eval_attention_phase(plugin):
+    """the context sampling.sample_images runs in: the trained component's eval attention phase when the config selects it; families whose engine has none
+    (PixArt, the UNets; the VAE never had the option) ignore the option with one warning, as the reference falls back to SDPA"""
+    from contextlib import nullcontext
+    if not sage_attention_enabled(plugin.config):
+        return nullcontext()
+    model = plugin.get_trained_component()
+    if not isinstance(model, EvalAttentionMixin):
+        _sage_once(("family", type(model).__name__), "attention_mechanism=sageattention is not built for %s: ignored, the exact attention kernels stay in use", type(model).__name__)
+        return nullcontext()
+    return model.eval_attention_phase()

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (AdapterArena, ArenaModule, FullGrads, LayerSyncTap, LoraGroup, compact, frozen, layersync_indices, lora_pairs, lora_up, mod_grads, node_backward, pad64,
+from ..engine import (AdapterArena, ArenaModule, EvalAttentionMixin, FullGrads, LayerSyncTap, LoraGroup, compact, frozen, layersync_indices, lora_pairs, lora_up, mod_grads, node_backward, pad64,
                       problems, rows_of)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_QK_NORM_ROPE
 from ..training.checkpoint_plan import CheckpointPlanMixin
@@ -58,7 +58,7 @@ def _ext_bwd(lg, U) -> dict:
     return dict(a2=U, b2=lg.A_cat_T, k2_real=lg.k2_real) if lg is not None else {}
 
 
-class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
+class FluxTransformer2DModel(EvalAttentionMixin, CheckpointPlanMixin, ArenaModule):
     def __init__(self, patch_size: int = 1, in_channels: int = 64, num_layers: int = 19, num_single_layers: int = 38,
                  attention_head_dim: int = 128, num_attention_heads: int = 24, joint_attention_dim: int = 4096,
                  pooled_projection_dim: int = 768, guidance_embeds: bool = False, axes_dims_rope: Tuple[int, ...] = (16, 56, 56),
@@ -376,12 +376,12 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             ops.qk_norm_rope_fwd(qkv[b * S:(b + 1) * S], wq, wk, env.cos_b[b], env.sin_b[b], Q[b:b + 1], K[b:b + 1],
                                  None if Qt is None else Qt[b:b + 1], None if Kt is None else Kt[b:b + 1], Vt[b:b + 1], 1, H, hd, rows, pos0, S, Sp)
 
-    def _attn_forward_fused(self, Q, K, V, Vt, O, lse2, env):
+    def _attn_forward_fused(self, Q, K, V, Vt, O, lse2, env, save: bool = True):
         """attention after the fused projection: from the head-major V^T the epilogue also wrote (default), or — ST355_FUSED_VT=0 — straight from the
         row-major V by transposing LDS reads (no V^T at all; measured r02: the forward kernel is ~4-8 % slower that way, the extra V^T write is cheaper)"""
         B, H, hd, S = env.B, self.H, self.hd, env.S
         if Vt is not None:
-            ops.attn_fwd(Q, K, Vt, O, lse2, B, H, S, S, hd, env.scale, key_bias=env.key_bias)
+            self._attn_fwd(save, Q, K, Vt, O, lse2, B, H, S, S, hd, env.scale, key_bias=env.key_bias)
         else:
             ops.attn_fwd_vrows(Q, K, V, O, lse2, B, H, S, hd, env.scale, key_bias=env.key_bias)
 
@@ -413,7 +413,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         fused = (not full) and (not getattr(env, "routed", False)) and self._fused_qkv_ok((Si, St), (blk.norm_q, blk.norm_k, blk.norm_added_q, blk.norm_added_k))
         ff_lora = any(l.lora is not None for l in (blk.ff1, blk.ff2, blk.ffc1, blk.ffc2))      # '+ffs' adapters: host sequencing
         keep_y = (full or self.mod_lora is not None) and save        # the un-gated branch outputs: gate gradients (full-rank training; adapters on the modulation Linears)
-        if (fused and not tokw and not ff_lora and self.mod_lora is None and _block_abi_ok() and _BLOCK_ABI_ONLY in ("", "double", "fwd") and _FUSED_VT and blk.add_qkv.lora is None and blk.to_add_out.lora is None and img.is_contiguous() and txt.is_contiguous()):
+        if (fused and not tokw and not ff_lora and not self._sage_now(save) and self.mod_lora is None and _block_abi_ok() and _BLOCK_ABI_ONLY in ("", "double", "fwd") and _FUSED_VT and blk.add_qkv.lora is None and blk.to_add_out.lora is None and img.is_contiguous() and txt.is_contiguous()):
             # the production form of the block as ONE C entry point (st355_block_flux_double_fwd): the same launches on the same operands as
             # the host-side sequencing below (adapters on the image stream's to_q / to_k / to_v / to_out.0, the reference's default target set)
             mk = lambda r, c: torch.empty(r, c, dtype=BF16, device=dev)
@@ -467,7 +467,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
                                                             epilogue=EPI_QK_NORM_ROPE, rows_per_batch=St,
                                                             rope=ops.qk_rope(Q, K, rrms, blk.norm_added_q, blk.norm_added_k, env.cos_p, env.sin_p, H, S, 0, Vt=Vt),
                                                             **kw_t)))
-            self._attn_forward_fused(Q, K, V, Vt, O, lse2, env)
+            self._attn_forward_fused(Q, K, V, Vt, O, lse2, env, save)
             del Vt
         else:
             qkv = torch.empty(B * S, 3 * D, dtype=BF16, device=dev)
@@ -477,7 +477,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             Q, K, Qt, Kt, Vt = self._alloc_heads(env)
             self._qk_fwd(env, qkv, blk.norm_added_q, blk.norm_added_k, Q, K, Qt, Kt, Vt, St, 0)
             self._qk_fwd(env, qkv, blk.norm_q, blk.norm_k, Q, K, Qt, Kt, Vt, Si, St)
-            ops.attn_fwd(Q, K, Vt, O, lse2, B, H, S, Sp, hd, env.scale, key_bias=env.key_bias)
+            self._attn_fwd(save, Q, K, Vt, O, lse2, B, H, S, Sp, hd, env.scale, key_bias=env.key_bias)
             del Vt
         x1_img = torch.empty(B * Si, D, dtype=BF16, device=dev); x1_txt = torch.empty(B * St, D, dtype=BF16, device=dev)
         T_o = torch.empty(B * Si, blk.to_out.lora.K2, dtype=BF16, device=dev) if blk.to_out.lora is not None else None
@@ -554,7 +554,7 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
         fused = (not full) and (not getattr(env, "routed", False)) and self._fused_qkv_ok((S,), (blk.norm_q, blk.norm_k))
         ff_lora = blk.proj_mlp.lora is not None or blk.proj_out.lora is not None      # '+ffs' / 'tiny' / 'nano' adapters: host sequencing (the C entry point knows the q / k / v adapters)
         keep_y = (full or self.mod_lora is not None) and save
-        if fused and not tokw and not ff_lora and self.mod_lora is None and _block_abi_ok() and _BLOCK_ABI_ONLY in ("", "single", "fwd") and _FUSED_VT and x.is_contiguous():
+        if fused and not tokw and not ff_lora and not self._sage_now(save) and self.mod_lora is None and _block_abi_ok() and _BLOCK_ABI_ONLY in ("", "single", "fwd") and _FUSED_VT and x.is_contiguous():
             # the production form of the block as ONE C entry point (st355_block_flux_single_fwd): the same launches on the same operands
             # as the host-side sequencing below
             lo = blk.qkv.lora
@@ -580,13 +580,13 @@ class FluxTransformer2DModel(CheckpointPlanMixin, ArenaModule):
             Vt = torch.empty(B, H, hd, S, dtype=BF16, device=dev) if _FUSED_VT else None
             _, T = self._lin_fwd(blk.qkv, n, out=V, epilogue=EPI_QK_NORM_ROPE, rows_per_batch=S,
                                  rope=ops.qk_rope(Q, K, rrms, blk.norm_q, blk.norm_k, env.cos_p, env.sin_p, H, S, 0, Vt=Vt))
-            self._attn_forward_fused(Q, K, V, Vt, O, lse2, env)
+            self._attn_forward_fused(Q, K, V, Vt, O, lse2, env, save)
             del Vt
         else:
             qkv, T = self._lin_fwd(blk.qkv, n)
             Q, K, Qt, Kt, Vt = self._alloc_heads(env)
             self._qk_fwd(env, qkv, blk.norm_q, blk.norm_k, Q, K, Qt, Kt, Vt, S, 0)
-            ops.attn_fwd(Q, K, Vt, O, lse2, B, H, S, Sp, hd, env.scale, key_bias=env.key_bias)
+            self._attn_fwd(save, Q, K, Vt, O, lse2, B, H, S, Sp, hd, env.scale, key_bias=env.key_bias)
             del Vt
         hpre = torch.empty(B * S, 4 * D, dtype=BF16, device=dev)
         lm, lp = blk.proj_mlp.lora, blk.proj_out.lora

@@ -361,6 +361,8 @@ class ModelFoundation(ExplorativeModelingMixin):
         wd = getattr(self.config, "weight_dtype", BF16)
         if wd not in (BF16, "bf16", None):
             raise ValueError(f"{self.NAME} (st355): weight_dtype {wd} — the MI355X path computes in bf16 (mixed_precision=bf16)")
+        from .engine import sage_attention_enabled
+        sage_attention_enabled(self.config)          # attention_mechanism / sageattention_usage: what is not built is refused by name here, before any step
 
     def _mixflow_enabled(self) -> bool:
         return getattr(self.config, "mixflow_enabled", False) is True

@@ -58,6 +58,7 @@ SYMBOLS = [
     "st355_attn_wide_fwd", "st355_attn_wide_bwd_workspace", "st355_attn_wide_bwd", "st355_attn_d512_fwd",
     "st355_attn_narrow_fwd", "st355_attn_narrow_bwd_workspace", "st355_attn_narrow_bwd",
     "st355_attn_d72_fwd", "st355_attn_d72_bwd_workspace", "st355_attn_d72_bwd",
+    "st355_attn_sage_workspace", "st355_attn_sage_quantize", "st355_attn_sage_fwd",
 ]
 
 KERNEL_CLASSES = [
@@ -519,6 +520,9 @@ def _declare(lib):
                                             i32, i32, i32, i32, i32, f32]),
         "st355_attn_d72_fwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32, f32]),
         "st355_attn_d72_bwd_workspace": (sz, [i32, i32, i32, i32]),
+        "st355_attn_sage_workspace": (sz, [i32, i32, i32, i32]),
+        "st355_attn_sage_quantize": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
+        "st355_attn_sage_fwd": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, f32]),
         "st355_attn_d72_bwd": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp,
                                          i32, i32, i32, i32, i32, i32, f32]),
     }

@@ -1838,6 +1838,57 @@ def attn_d72_bwd(q, k, v, o, dO, lse2, dq, dk, dv, B, H, Sq, Sk, d, scale: float
              "attn_d72_bwd")
 
 
+def _sage_args(fn, Q, K, Vt, B, H, S, Sp, d):
+    """the preconditions of the quantised attention forward, refused by name"""
+    if d not in (64, 128):
+        raise _l.St355Error(f"{fn}: head_dim {d} not built (64 or 128)")
+    if Sp != (S + 63) // 64 * 64:
+        raise _l.St355Error(f"{fn}: Sp {Sp}: expected ceil64(S) = {(S + 63) // 64 * 64}")
+    for t, n, shape in ((Q, "Q", (B, H, S, d)), (K, "K", (B, H, S, d)), (Vt, "Vt", (B, H, d, Sp))):
+        _chk(t, BF16, f"{fn}: {n}")
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _l.St355Error(f"{fn}: {n}: expected a contiguous {list(shape)} tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+        if t.device != Q.device:
+            raise _l.St355Error(f"{fn}: {n}: on {t.device}, Q on {Q.device}")
+
+
+def _sage_views(ws, B, H, Sp, d):
+    """(Qh, Kh int8 [B,H,Sp,d], Vh e4m3 [B,H,d,Sp], sq, sk fp32 [B,H,Sp/64], sv fp32 [B,H,d]): the sections of the workspace of csrc/attention_sage.hip, each
+    on a 256-byte boundary in this order (include/st355.h)"""
+    up = lambda x: (x + 255) // 256 * 256
+    BH, nb, o, out = B * H, Sp // 64, 0, []
+    for nbytes, dtype, shape in ((BH * Sp * d, torch.int8, (B, H, Sp, d)), (BH * Sp * d, torch.int8, (B, H, Sp, d)),
+                                 (BH * Sp * d, torch.float8_e4m3fn, (B, H, d, Sp)), (BH * nb * 4, F32, (B, H, nb)), (BH * nb * 4, F32, (B, H, nb)),
+                                 (BH * d * 4, F32, (B, H, d))):
+        out.append(ws[o:o + nbytes].view(dtype).view(shape))
+        o += up(nbytes)
+    return tuple(out)
+
+
+def _sage_quantize(fn, Q, K, Vt, B, H, S, Sp, d):
+    _sage_args(fn, Q, K, Vt, B, H, S, Sp, d)
+    L = _l.load()
+    ws = _scratch("attn_sage", Q.device, L.st355_attn_sage_workspace(B, H, S, d))
+    _l.check(L.st355_attn_sage_quantize(_stream(), _ptr(Q), _ptr(K), _ptr(Vt), _ptr(ws), B, H, S, Sp, d), fn)
+    return ws
+
+
+def attn_sage_quantize(Q, K, Vt, B, H, S, Sp, d):
+    """The quantise pass of attn_sage_fwd (csrc/attention_sage.hip) on attn_fwd's operands: K minus its fp32 column mean and Q to int8 with one scale per 64
+    rows, Vt to e4m3 with one scale per (b, h, channel).  Returns views (Qh, Kh, Vh, sq, sk, sv) of the per-device scratch; the next call overwrites them."""
+    return _sage_views(_sage_quantize("attn_sage_quantize", Q, K, Vt, B, H, S, Sp, d), B, H, Sp, d)
+
+
+def attn_sage_fwd(Q, K, Vt, O, B, H, S, Sp, d, scale: float):
+    """SageAttention-style forward on attn_fwd's operands: the quantise pass, then Q K^T on the int8 MFMA and P V on the fp8 MFMA with an fp32 online softmax
+    (the numerics are restated in include/st355.h).  d 64 or 128, any S >= 1; no key bias, no lse2, no O_res: a forward for sampling, with no backward."""
+    _chk(O, BF16, "attn_sage_fwd: O")
+    if O.dim() != 2 or O.shape[0] != B * S or O.shape[1] < H * d or O.device != Q.device:
+        raise _l.St355Error(f"attn_sage_fwd: O: expected a [{B * S}, >= {H * d}] view on {Q.device}, got {tuple(O.shape)} on {O.device}")
+    ws = _sage_quantize("attn_sage_fwd", Q, K, Vt, B, H, S, Sp, d)
+    _l.check(_l.load().st355_attn_sage_fwd(_stream(), _ptr(ws), _ptr(O), _rows(O, "O"), B, H, S, Sp, d, scale), "attn_sage_fwd")
+
+
 def attn_bwd(Q, K, Qt, Kt, v_rows, O, dO, lse2, dQ, dK, dv_rows, B, H, S, Sp, d, scale: float, key_bias=None, O_res=None, ds=None, ds_bytes=None):
     """ds (a uint8 device tensor; ds_bytes: what the call is told it holds, default all of it): the caller's dS^T spill buffer -> st355_attn_bwd_ds"""
     L = _l.load()

@@ -436,14 +436,16 @@ def sample_images(plugin, prompt_embeds: torch.Tensor, pooled: Optional[torch.Te
             out = (inter + ig_scale * (out.float() - inter)).to(xt.dtype)
         return cfg_combine(out, float(guidance_scale)) if do_cfg else out
 
-    if twinflow:
-        x = ucgm_sample(predict, x, num_inference_steps, stochast_ratio=1.0, generator=generator)
-    elif flow:
-        x = flow_match_euler_sample(predict, x, scheduler, num_inference_steps, mu=mu)
-    elif isinstance(scheduler, LCMScheduler):
-        x = lcm_sample(predict, x, scheduler, num_inference_steps, generator=generator)
-    else:
-        x = ddim_sample(predict, x, scheduler, num_inference_steps)
+    from .engine import eval_attention_phase
+    with eval_attention_phase(plugin):        # attention_mechanism=sageattention (usage inference): the SD3 / Flux engines sample on the quantised attention forward
+        if twinflow:
+            x = ucgm_sample(predict, x, num_inference_steps, stochast_ratio=1.0, generator=generator)
+        elif flow:
+            x = flow_match_euler_sample(predict, x, scheduler, num_inference_steps, mu=mu)
+        elif isinstance(scheduler, LCMScheduler):
+            x = lcm_sample(predict, x, scheduler, num_inference_steps, generator=generator)
+        else:
+            x = ddim_sample(predict, x, scheduler, num_inference_steps)
     if not decode:
         return x
     return plugin.get_vae().decode_scaled(x)

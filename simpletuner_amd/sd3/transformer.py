@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import (IG_NAMES, NEXTLAT_NAMES, SELF_FLOW_NAMES, ST_NAMES, SelfTranscendenceHead, SelfTranscendenceTap, self_transcendence_indices, self_transcendence_shapes, AdapterArena, CaptureTap, SelfFlowHead, SelfFlowTap, self_flow_indices, self_flow_shapes, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
+from ..engine import (EvalAttentionMixin, IG_NAMES, NEXTLAT_NAMES, SELF_FLOW_NAMES, ST_NAMES, SelfTranscendenceHead, SelfTranscendenceTap, self_transcendence_indices, self_transcendence_shapes, AdapterArena, CaptureTap, SelfFlowHead, SelfFlowTap, self_flow_indices, self_flow_shapes, ArenaModule, FullGrads, InternalGuidanceHead, InternalGuidanceTap, LayerSyncTap, LokrGroup, LoraDropout, LoraGroup, NextLatHead, TLora,
                       NextLatTap, compact, frozen, internal_guidance_index, internal_guidance_shapes, layersync_indices, lin_w, lin_wT, lokr_init_norm, lora_down, lora_dx_finish, lora_dx_kw,
                       lora_fwd_kw, lora_grads, lora_pairs, lora_up, nextlat_index, node_backward, nextlat_init_reference, nextlat_shapes, pad64_empty, problems, rows_of, sincos_2d_hw)
 from ..ops import EPI_ADD, EPI_GATE_RESIDUAL, EPI_GELU, EPI_MUL_GELU_GRAD
@@ -62,7 +62,7 @@ def _stream_problems(B: int, S: int, rows: int, pr: dict, after: Optional[list] 
     return [q]
 
 
-class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
+class SD3Transformer2DModel(EvalAttentionMixin, CheckpointPlanMixin, ArenaModule):
     def __init__(self, sample_size: int = 128, patch_size: int = 2, in_channels: int = 16, num_layers: int = 18,
                  attention_head_dim: int = 64, num_attention_heads: int = 18, joint_attention_dim: int = 4096,
                  caption_projection_dim: int = 1152, pooled_projection_dim: int = 2048, out_channels: int = 16,
@@ -527,7 +527,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         rpb = 1 if env.rpb_i == 1 else Si     # rows of the image stream that share one modulation row: the sample's (inside a TREAD route: its kept) rows, or 1 under tokenwise timesteps
         drop = getattr(env, "drop", None)      # LoRA dropout of this training forward (and of its recompute passes): the adapters' down projections draw masks
         tl = getattr(env, "tl", None)          # T-LoRA: this forward's timesteps bound to the rank table — every down projection is masked per sample behind its product
-        if self._c_entry_ok(blk, env, (img, txt), full=full, backward=False):
+        if not self._sage_now(save) and self._c_entry_ok(blk, env, (img, txt), full=full, backward=False):      # (eval attention phase: host sequencing)
             return self._block_fwd_c(blk, img, txt, env, save, ybuf)
 
         mi = env.mod_i[:, blk.mod_off:blk.mod_off + 6 * D]
@@ -558,7 +558,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
         ops.qk_norm_rope_fwd(qkv, blk.norm_q, blk.norm_k, cos, sin, Q, K, Qt, Kt, Vt, B, H, hd, Si, 0, S, Sp)
         ops.qk_norm_rope_fwd(qkv, blk.norm_added_q, blk.norm_added_k, cos, sin, Q, K, Qt, Kt, Vt, B, H, hd, St, Si, S, Sp)
         O = torch.empty(B * S, D, dtype=BF16, device=dev); lse2 = torch.empty(B, H, S, dtype=F32, device=dev)
-        ops.attn_fwd(Q, K, Vt, O, lse2, B, H, S, Sp, hd, scale)
+        self._attn_fwd(save, Q, K, Vt, O, lse2, B, H, S, Sp, hd, scale)
         del Vt
         x1_img = torch.empty(B * Si, D, dtype=BF16, device=dev)
         x1_txt = None if blk.last else torch.empty(B * St, D, dtype=BF16, device=dev)
@@ -610,7 +610,7 @@ class SD3Transformer2DModel(CheckpointPlanMixin, ArenaModule):
             V2t = mk2(B, H, hd, Sip, dtype=BF16, device=dev)
             ops.qk_norm_rope_fwd(qkv2, blk.norm_q2, blk.norm_k2, cos, sin, Q2, K2, Q2t, K2t, V2t, B, H, hd, Si, 0, Si, Sip)
             O2 = torch.empty(B * Si, D, dtype=BF16, device=dev); lse2b = torch.empty(B, H, Si, dtype=F32, device=dev)
-            ops.attn_fwd(Q2, K2, V2t, O2, lse2b, B, H, Si, Sip, hd, scale)
+            self._attn_fwd(save, Q2, K2, V2t, O2, lse2b, B, H, Si, Sip, hd, scale)
             del V2t
             ya2 = ybuf(B * Si)
             T_o2 = lora_down(blk.to_out2, O2, drop, tl=tl)
