@@ -361,10 +361,12 @@ int st355_qk_rope_norm_bwd(void* stream, const void* dQ, const void* dK, const v
  * head_dim 128, 96 and 64; every other shape (key bias, cross attention, row-major V) keeps the 32-query kernels whatever is set here.
  *   fwd: 64 = the hand-scheduled one-wave-per-SIMD forward where S % 64 == 0 (k_attn_fwd64: 64 queries per wave, stale-reference softmax; the scores are
  *        the same fp32 sums: O agrees with the 32-query kernel to bf16 rounding, lse2 to fp32 rounding), 32 = k_attn_fwd4;
+ *        2 = everything 64 does, plus k_attn_fwd64x for EVERY head_dim-64 forward that is not row-major V (64 queries per wave on the 16x16x32 MFMA, exact
+ *        running max; any Sq / Sk, key bias, O_res: the operands, results and error bounds of k_attn_fwd4<64>).  Opt-in: the default stays 64;
  *   dq:  64 = k_attn_bwd_dq64 where Sk % 64 == 0 (bit-identical to the 32-query k_attn_bwd_dq), 32 = the latter everywhere;
  *   dkv: 4 = k_attn_bwd_dkv4 (hand-scheduled body, statistics folded into the MFMA chains; same scores, another summation order: dK / dV agree
  *        with dkv3 to ~3e-4), 3 = k_attn_bwd_dkv3;
- *   -1 leaves a choice unchanged.  Defaults: 64 / 64 / 4 (environment ST355_ATTN_FWD64=0, ST355_ATTN_DQ=32, ST355_ATTN_DKV=3 flip them).
+ *   -1 leaves a choice unchanged.  Defaults: 64 / 64 / 4 (environment ST355_ATTN_FWD64=0 or =2, ST355_ATTN_DQ=32, ST355_ATTN_DKV=3 flip them).
  * Returns (previous fwd) * 65536 + (previous dq) * 256 + (previous dkv). */
 int st355_attn_set_impl(int fwd, int dq, int dkv);
 int st355_attn_fwd(void* stream, const void* Q, const void* K, const void* Vt, const float* key_bias,
@@ -413,6 +415,7 @@ enum { ST355_ATTN_PLAN_BIAS = 1, ST355_ATTN_PLAN_VROWS = 2, ST355_ATTN_PLAN_RES 
 enum { ST355_ATTN_ROUTE_FWD64 = 10 /* k_attn_fwd64 (96, 128) */, ST355_ATTN_ROUTE_FWD4 = 20, ST355_ATTN_ROUTE_FWD4_BIAS = 30,
        ST355_ATTN_ROUTE_FWD4_RES = 40 /* k_attn_fwd4 writing O_res */, ST355_ATTN_ROUTE_FWD4_RES_BIAS = 50,
        ST355_ATTN_ROUTE_FWD4_VROWS = 60 /* k_attn_fwd4<128, *, true> (128) */, ST355_ATTN_ROUTE_FWD4_VROWS_BIAS = 70,
+       ST355_ATTN_ROUTE_FWD64X = 80 /* k_attn_fwd64x: every bias / O_res form (64; st355_attn_set_impl fwd = 2) */,
        ST355_ATTN_ROUTE_PREP = 100, ST355_ATTN_ROUTE_PREP_RES = 110 /* delta from O + O_res */, ST355_ATTN_ROUTE_PREP_DOT = 120 /* + the dO^T copy */,
        ST355_ATTN_ROUTE_PREP_RES_DOT = 130,
        ST355_ATTN_ROUTE_DKV4 = 200, ST355_ATTN_ROUTE_DKV4_ROPE = 210 /* (128) */, ST355_ATTN_ROUTE_DKV3 = 220, ST355_ATTN_ROUTE_DKV3_ROPE = 230 /* (128) */,

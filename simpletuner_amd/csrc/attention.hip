@@ -353,24 +353,31 @@ __global__ void __launch_bounds__(256, 1) k_attn_fwd64(const bf16* __restrict__ 
   }
 }
 
-// forward kernel choice where k_attn_fwd64 applies: 64 (default) or 32 = k_attn_fwd4.  ST355_ATTN_FWD64=0 overrides; tools/attn_lab sets the variable directly.
+// forward kernel choice: 64 (default) = k_attn_fwd64 where it applies, 32 = k_attn_fwd4 everywhere, 2 = 64 plus k_attn_fwd64x (attention_fwd64x.hip) for every
+// head_dim-64 forward that is not row-major V.  ST355_ATTN_FWD64=0 / =2 override the default; tools/attn_lab sets the variable directly.  The one place the
+// environment is read: st355_attn_set_impl (attention_bwd.hip) calls this too.
 int g_attn_fwd_impl = -1;
 unsigned long long* g_attn_fwd_trace = nullptr;    // tools/attn_lab, trace builds of the fwd64 body only
-static int attn_fwd_impl64() {
-  if (g_attn_fwd_impl < 0) { const char* e = getenv("ST355_ATTN_FWD64"); g_attn_fwd_impl = (e && e[0] == '0') ? 32 : 64; }
+int attn_fwd_impl64() {
+  if (g_attn_fwd_impl < 0) { const char* e = getenv("ST355_ATTN_FWD64"); g_attn_fwd_impl = (e && e[0] == '0') ? 32 : (e && e[0] == '2') ? 2 : 64; }
   return g_attn_fwd_impl;
 }
 
 // The forward's kernel choice (ST355_ATTN_ROUTE_* + head_dim index), shared by attn_fwd_impl and st355_attn_plan (attention_bwd.hip); d is 64, 96 or 128.
-// k_attn_fwd4 (r02) is the general kernel; k_attn_fwd64 (r04) takes the head_dim-128 / 96, no-bias, S % 64 == 0 shapes.
+// k_attn_fwd4 (r02) is the general kernel; k_attn_fwd64 (r04) takes the head_dim-128 / 96, no-bias, S % 64 == 0 shapes; k_attn_fwd64x takes every head_dim-64
+// form but row-major V when the choice is 2 (opt-in).
 int attn_fwd_route(int d, int S, bool bias, bool vrow, bool res) {
   const int hd = d == 64 ? 0 : d == 96 ? 1 : 2;
-  if (!vrow && !bias && !res && (d == 128 || d == 96) && S % 64 == 0 && attn_fwd_impl64() == 64) return ST355_ATTN_ROUTE_FWD64 + hd;
+  const int impl = attn_fwd_impl64();
+  if (d == 64 && !vrow && impl == 2) return ST355_ATTN_ROUTE_FWD64X + hd;
+  if (!vrow && !bias && !res && (d == 128 || d == 96) && S % 64 == 0 && (impl == 64 || impl == 2)) return ST355_ATTN_ROUTE_FWD64 + hd;
   if (vrow) return (bias ? ST355_ATTN_ROUTE_FWD4_VROWS_BIAS : ST355_ATTN_ROUTE_FWD4_VROWS) + hd;
   if (res) return (bias ? ST355_ATTN_ROUTE_FWD4_RES_BIAS : ST355_ATTN_ROUTE_FWD4_RES) + hd;
   return (bias ? ST355_ATTN_ROUTE_FWD4_BIAS : ST355_ATTN_ROUTE_FWD4) + hd;
 }
 
+void attn_fwd64x_launch(void* stream, const void* Q, const void* K, const void* Vt, const float* key_bias, void* O, int64_t ld_o, void* O_res, float* lse2,
+                        int B, int H, int Sq, int Sk, int Skp, float scale2);      // attention_fwd64x.hip
 // vrow != 0: Vt is the ROW-major V (token rows, head h at columns h*d) and Sp its leading dimension (k_attn_fwd4<128, *, true>)
 static int attn_fwd_impl(void* stream, const void* Q, const void* K, const void* Vt, const float* key_bias, void* O,
                          int64_t ld_o, float* lse2, int B, int H, int Sq, int S, int Sp, int d, float scale, int vrow = 0, void* O_res = nullptr) {
@@ -385,6 +392,10 @@ static int attn_fwd_impl(void* stream, const void* Q, const void* K, const void*
   // The r01 kernel lives on in tools/attn_fwd_variants.hip as the lab's A/B baseline (r02 lab, B8 H24 S4608 d128: 862 -> 927 TFLOP/s).  Measured and deleted
   // in r02: an 8-wave / 256-query workgroup variant (843 TFLOP/s) and an 8-wave LDS-DMA half-tile-stagger variant (738); logs under profiles/archive/r02_attn_lab_*.log.
   const int route = attn_fwd_route(d, S, key_bias != nullptr, vrow != 0, O_res != nullptr);
+  if (route / 10 * 10 == ST355_ATTN_ROUTE_FWD64X) {     // head_dim 64, 64 queries per wave, every form (attention_fwd64x.hip)
+    attn_fwd64x_launch(stream, Q, K, Vt, key_bias, O, ld_o, O_res, lse2, B, H, Sq, S, Sp, scale2);
+    return st355_check_launch("attn_fwd64x");
+  }
   if (route / 10 * 10 == ST355_ATTN_ROUTE_FWD64) {      // hand-scheduled 64-queries-per-wave kernel
     dim3 grid64((Sq + 255) / 256, H, B);
     const int lds64 = 4 * 2 * 64 * 256;

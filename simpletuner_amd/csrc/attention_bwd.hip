@@ -1256,10 +1256,10 @@ static AttnBwdRoute attn_bwd_route(int d, int Sk, bool qt, bool kt, bool bias, b
 }
 
 extern int g_attn_fwd_impl;                        // attention.hip
+int attn_fwd_impl64();                             // attention.hip: the current forward choice, read from the environment on first use
 extern "C" int st355_attn_set_impl(int fwd, int dq, int dkv) {
-  if (g_attn_fwd_impl < 0) { const char* e = getenv("ST355_ATTN_FWD64"); g_attn_fwd_impl = (e && e[0] == '0') ? 32 : 64; }
-  const int prev = g_attn_fwd_impl * 65536 + attn_dq_impl() * 256 + attn_dkv_impl();
-  if (fwd == 32 || fwd == 64) g_attn_fwd_impl = fwd;
+  const int prev = attn_fwd_impl64() * 65536 + attn_dq_impl() * 256 + attn_dkv_impl();
+  if (fwd == 32 || fwd == 64 || fwd == 2) g_attn_fwd_impl = fwd;
   if (dq == 32 || dq == 64) g_attn_dq_impl = dq;
   if (dkv == 3 || dkv == 4) g_attn_dkv_impl = dkv;
   return prev;

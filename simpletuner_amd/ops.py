@@ -973,6 +973,7 @@ def gemm_set_persistent(mode: int) -> int:
 
 def attn_set_impl(fwd: int = -1, dq: int = -1, dkv: int = -1):
     """st355_attn_set_impl: fwd / dq 64 = the hand-scheduled 64-rows-per-wave kernels where they apply (default), 32 = the 32-row kernels everywhere;
+    fwd 2 = 64 plus k_attn_fwd64x for every head_dim-64 forward that is not row-major V (any Sq / Sk, key bias, O_res; opt-in);
     dkv 4 = the hand-scheduled dK/dV body (default), 3 = k_attn_bwd_dkv3; -1 = unchanged.  Returns the previous (fwd, dq, dkv)."""
     prev = int(_l.load().st355_attn_set_impl(int(fwd), int(dq), int(dkv)))
     return prev // 65536, (prev // 256) % 256, prev % 256
@@ -984,7 +985,7 @@ def attn_set_ds(mode: int = -1) -> int:
     return int(_l.load().st355_attn_set_ds(int(mode)))
 
 
-ATTN_ROUTE_KINDS = {10: "fwd64", 20: "fwd4", 30: "fwd4_bias", 40: "fwd4_res", 50: "fwd4_res_bias", 60: "fwd4_vrows", 70: "fwd4_vrows_bias",
+ATTN_ROUTE_KINDS = {10: "fwd64", 20: "fwd4", 30: "fwd4_bias", 40: "fwd4_res", 50: "fwd4_res_bias", 60: "fwd4_vrows", 70: "fwd4_vrows_bias", 80: "fwd64x",
                     100: "prep", 110: "prep_res", 120: "prep_dot", 130: "prep_res_dot",
                     200: "dkv4", 210: "dkv4_rope", 220: "dkv3", 230: "dkv3_rope", 240: "dkv2",
                     300: "dq64", 310: "dq64_rope", 320: "dq_tr", 330: "dq_tr_bias", 340: "dq", 350: "dq_bias", 360: "dq_tr_rope",

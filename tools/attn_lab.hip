@@ -16,6 +16,7 @@
 #include <unistd.h>
 #include "../simpletuner_amd/csrc/runtime.hip"
 #include "../simpletuner_amd/csrc/attention.hip"
+#include "../simpletuner_amd/csrc/attention_fwd64x.hip"
 #include "../simpletuner_amd/csrc/attention_bwd.hip"
 #include "attn_fwd_variants.hip"
 
